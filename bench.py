@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Oryon hot path on MI355X (contract: see the task brief / DESIGN.md §Measurement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,7 +9,8 @@ Workload (BASELINE.json configs[1]): per GPU B=64 synthetic 224x224 RGB-D pairs 
 maps resident in HBM; one step = masks -> ROI -> subsample 5000 -> gather+normalise -> cosine NN (fp32 MFMA)
 -> sample 500 correspondences -> lift -> PointDSC (12 x 128) -> pose, for every pair, plus (N>1) the
 all_gather collation of poses.  Weak scaling: every rank processes its own 64 pairs.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times ONE window of K steps and prints the headline; --full adds
+the median of 7 windows, the sanity / roofline / CPU-baseline figures and the other schedules and stage sets.
 """
 import argparse
 import json
@@ -298,6 +299,26 @@ def emit_line(rec, rank, grouped):
     flush_c_stdio()
 
 
+def dump_outputs(path, out, pose, status, rank, world, grouped):
+    """--dump-outputs: what the last timed step handed its caller - the collated poses / status in global pair order and the step's
+    n_valid / n_lifted (gathered over the ranks) - as path/<name>.npy: floating-point arrays as float32, integers as float64 (exact)."""
+    import numpy as np
+    arrays = {"pose": pose, "status": status}
+    for k in ("n_valid", "n_lifted"):
+        t = out[k].contiguous()
+        if grouped:
+            parts = [torch.empty_like(t) for _ in range(world)]
+            dist.all_gather(parts, t)
+            t = torch.cat(parts)
+        arrays[k] = t
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    for k, t in arrays.items():
+        x = t.detach().cpu().numpy()
+        np.save(os.path.join(path, k + ".npy"), x.astype(np.float32 if x.dtype.kind == "f" else np.float64))
+
+
 def bench_full(a, rank, world, dev):
     """`--stages full|decode`: that stage set alone, as its own JSON line (never mixed into the headline `value`)."""
     rec = run_stage_set(a, rank, world, dev, a.stages, a.steps, a.warmup, a.backbone_dtype)
@@ -383,9 +404,16 @@ def main():
     ap.add_argument("--sample-first", type=int, default=0,
                     help="MatchPoseConfig.sample_first: the matcher runs on a random subset of this many anchors per pair first (identically "
                          "distributed correspondences; pairs that come up short are redone on all anchors).  0 = off (default, the headline)")
-    ap.add_argument("--reps", type=int, default=7,
+    ap.add_argument("--reps", type=int, default=None,
                     help="repetitions of the timed window of --steps steps (each bracketed by barrier + synchronize); `value` / `ms_per_step` are "
-                         "the MEDIAN window, every window is listed in `timing.windows_ms_per_step`")
+                         "the MEDIAN window, every window is listed in `timing.windows_ms_per_step`.  Default: 7 with --full, else 1")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: 7 timed windows, the sanity / pose_sha256 step, roofline and K0 figures "
+                         "(with a serial engine of their own), the CPU baseline, the other collation mode (N > 1), the sample-first and "
+                         "hard-descriptor schedules and the decode / full stage sets.  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (collated pose / status, n_valid, n_lifted) as "
+                         "DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--engine", choices=["native", "python"], default="native",
                     help="native: one C-ABI call per step (oryon_engine_submit: engine-owned streams / events, persistent arena, no torch "
                          "allocation per step); python: the per-call schedule of oryon_amd/engine.py (torch streams, ~40 torch allocations per step)")
@@ -408,11 +436,13 @@ def main():
                          "the multi-GPU path a single-GPU box can execute (communicator created after the engine's stream pool, "
                          "all_gather_into_tensor of the [B,17] rows inside the timed region); reported in `multi_gpu`")
     ap.add_argument("--no-stage-sets", action="store_true",
-                    help="skip the 'decode+match+pose' and 'full' stage sets that the default run measures after the headline")
+                    help="skip the 'decode+match+pose' and 'full' stage sets that a --full run measures after the headline")
     ap.add_argument("--collation-selftest", action="store_true",
                     help="CPU-only check of the multi-rank launch path (gloo): every rank fabricates its poses, the collation runs, rank 0 "
                          "prints one JSON line.  Used by tests/test_cabi_and_host.py; measures nothing")
     a = ap.parse_args()
+    if a.reps is None:
+        a.reps = 7 if a.full else 1
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` (how the driver calls it): become the launcher - one rank per GPU under torch.distributed.run,
@@ -439,6 +469,8 @@ def main():
     dev = torch.device("cuda", local)
     B, H, C = a.batch, a.size, a.channels
     if a.stages in ("full", "decode"):
+        if a.dump_outputs:
+            raise SystemExit("--dump-outputs writes the headline stage set's outputs (--stages match+pose)")
         return bench_full(a, rank, world, dev)
     # N distinct input sets: set s holds the global pairs [s * world * B, (s + 1) * world * B), this rank its block of B of them
     n_sets = max(1, a.input_sets)
@@ -580,6 +612,7 @@ def main():
             a0 = alloc_counters()
             h0 = (host["submit_s"], host["submits"], native.host_stats()[1] if native else 0.0)
             first_step = native.steps if native else 0
+            host["rot"] = 0           # every window starts on input set 0: what its last step ran on depends on --steps alone
             barrier()
             t0 = time.perf_counter()
             out, pose, status = run_steps(a.steps)
@@ -600,6 +633,56 @@ def main():
     ms_med = med([w["ms_per_step"] for w in windows])
     elapsed = ms_med * 1e-3 * a.steps
 
+    # the headline line: everything in it comes from the timed windows and the warm-up before them
+    rec = None
+    if rank == 0:
+        rec = {
+            "metric": METRIC, "value": total * a.steps / elapsed, "unit": "pairs/s", "n_gpus": world, "steps": a.steps,
+            "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "multi_gpu": None,
+            "timing": {
+                "statistic": (f"median of {len(windows)} windows" if len(windows) > 1 else "one window") +
+                             f" of {a.steps} steps, each bracketed by barrier + torch.cuda.synchronize, max over ranks",
+                "windows_ms_per_step": [round(w["ms_per_step"], 4) for w in windows],
+                "engine": ("native: one oryon_engine_submit per step (engine-owned HIP streams / events, persistent arena)" if native else
+                           "python: per-call schedule (torch streams, torch allocations per step)"),
+                "host_submit_ms_per_step": med([w["host_submit_ms_per_step"] for w in windows]),
+                "host_submit_ms_per_step_c_abi": med([w["host_submit_ms_per_step_c_abi"] for w in windows]) if native else None,
+                "torch_allocs_per_step": [round(w["torch_allocs_per_step"], 2) for w in windows],
+                "device_allocs_in_window": [w["device_allocs"] for w in windows],
+                "alloc_retries_in_window": [w["alloc_retries"] for w in windows],
+                "stream_busy_ms_per_step": ({k: med([t[k] for t in sections]) for k in ("gather_ms", "match_ms", "screen_kernel_ms", "registration_ms")}
+                                            if sections else None),
+                "step_timeline_ms": ({k: med([t[k] for t in sections]) for k in ("match_start", "match_end", "registration_start", "registration_end")}
+                                     if sections else None),
+                "step_latency_ms": med([t["registration_end"] for t in sections]) if sections else None,
+                "timed_steps_with_events": len(sections),
+                "stream_roles": roles_rec["roles"] if roles_rec else None,
+                "stream_roles_tuning": roles_rec,
+            },
+            "config": {
+                "workload": f"{'cfg2' if (H, C) == (224, 256) else 'cfg4 geometry' if (H, C) == (384, 512) else 'custom'}: Batch={B} synthetic {H}x{H} pairs per GPU, C={C} fp32 descriptors given (HIP matcher + lift + "
+                            f"PointDSC 12x128), N1<=5000, n_corrs=500",
+                "stages": "match+lift+registration (descriptor maps resident in HBM; backbone not in the timed region)",
+                "descriptor_layout": "NCHW contiguous fp32 (as Oryon.forward returns them)" if a.layout == "nchw" else "channels_last (NHWC storage) fp32",
+                "match_mode": a.match_mode + ((" (MX-fp6 MFMA screen with a proven bound, exact fp32 re-scoring of the sampled anchors' candidates; anchors the bound cannot settle are resolved exactly: outputs identical to the fp32 scan)" if native is not None and engine.native_geometry.get("screen", 0) == 1 else " (int8-MFMA pre-screen, fp16-MFMA screening of the undecided anchors, exact fp32 re-scoring: outputs identical to the fp32 scan)") if use_i8 else " (fp16-MFMA screening, exact fp32 re-scoring: outputs identical to the fp32 scan)" if screened else ""),
+                "sample_first": a.sample_first or None,
+                "input_sets": f"{n_sets} distinct sets of {B} pairs per GPU (maps, masks, depths, poses, pair keys), step k runs on set k % {n_sets}; "
+                              + ("sanity / pose_sha256 on set 0" if a.full else "every timed window starts on set 0"),
+                "pairs_per_gpu": B, "global_pairs": total, "parallelism": f"pairs sharded over {world} GPU(s), all_gather of poses",
+                "pipelining": ("none" if a.no_overlap else "registration of step k on a second HIP stream under the matching of step k+1"
+                               + ("; K0 (ROI + gather) of step k+1 on a third stream under the screening / registration of step k"
+                                  if a.overlap_gather else "")),
+            },
+        }
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, pose, status, rank, world, grouped)
+    if not a.full:
+        emit_line(rec, rank, grouped)
+        return
+
+    # --full: what the headline does not need - checked and measured after the timed windows, in runs of their own
     # result sanity + algorithmic work of the dominant kernel (this rank's launch)
     out, pose, status = step(keep=True)
     torch.cuda.synchronize()
@@ -747,74 +830,36 @@ def main():
                   "moved_over_algorithmic": K0_MOVED_OVER_ALGORITHMIC if (B, H, C) == (64, 224, 256) else None,
                   "moved_source": "profiles/r05_pmc_counters.md / r06_pmc_counters.md (rocprofv3 --pmc FETCH_SIZE x 2 + WRITE_SIZE of the two gather launches)",
                   "peak_bytes_per_s": PEAK_HBM_BYTES}
-        rec = {
-            "metric": METRIC, "value": total * a.steps / elapsed, "unit": "pairs/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "multi_gpu": multi,
-            "timing": {
-                "statistic": f"median of {len(windows)} windows of {a.steps} steps, each bracketed by barrier + torch.cuda.synchronize, max over ranks",
-                "windows_ms_per_step": [round(w["ms_per_step"], 4) for w in windows],
-                "engine": ("native: one oryon_engine_submit per step (engine-owned HIP streams / events, persistent arena)" if native else
-                           "python: per-call schedule (torch streams, torch allocations per step)"),
-                "host_submit_ms_per_step": med([w["host_submit_ms_per_step"] for w in windows]),
-                "host_submit_ms_per_step_c_abi": med([w["host_submit_ms_per_step_c_abi"] for w in windows]) if native else None,
-                "torch_allocs_per_step": [round(w["torch_allocs_per_step"], 2) for w in windows],
-                "device_allocs_in_window": [w["device_allocs"] for w in windows],
-                "alloc_retries_in_window": [w["alloc_retries"] for w in windows],
-                "stream_busy_ms_per_step": ({k: med([t[k] for t in sections]) for k in ("gather_ms", "match_ms", "screen_kernel_ms", "registration_ms")}
-                                            if sections else None),
-                "step_timeline_ms": ({k: med([t[k] for t in sections]) for k in ("match_start", "match_end", "registration_start", "registration_end")}
-                                     if sections else None),
-                "step_latency_ms": med([t["registration_end"] for t in sections]) if sections else None,
-                "timed_steps_with_events": len(sections),
-                "stream_roles": roles_rec["roles"] if roles_rec else None,
-                "stream_roles_tuning": roles_rec,
-            },
-            "config": {
-                "workload": f"{'cfg2' if (H, C) == (224, 256) else 'cfg4 geometry' if (H, C) == (384, 512) else 'custom'}: Batch={B} synthetic {H}x{H} pairs per GPU, C={C} fp32 descriptors given (HIP matcher + lift + "
-                            f"PointDSC 12x128), N1<=5000, n_corrs=500",
-                "stages": "match+lift+registration (descriptor maps resident in HBM; backbone not in the timed region)",
-                "descriptor_layout": "NCHW contiguous fp32 (as Oryon.forward returns them)" if a.layout == "nchw" else "channels_last (NHWC storage) fp32",
-                "match_mode": a.match_mode + ((" (MX-fp6 MFMA screen with a proven bound, exact fp32 re-scoring of the sampled anchors' candidates; anchors the bound cannot settle are resolved exactly: outputs identical to the fp32 scan)" if native is not None and engine.native_geometry.get("screen", 0) == 1 else " (int8-MFMA pre-screen, fp16-MFMA screening of the undecided anchors, exact fp32 re-scoring: outputs identical to the fp32 scan)") if use_i8 else " (fp16-MFMA screening, exact fp32 re-scoring: outputs identical to the fp32 scan)" if screened else ""),
-                "sample_first": a.sample_first or None,
-                "input_sets": f"{n_sets} distinct sets of {B} pairs per GPU (maps, masks, depths, poses, pair keys), step k runs on set k % {n_sets}; "
-                              "sanity / pose_sha256 on set 0",
-                "pairs_per_gpu": B, "global_pairs": total, "parallelism": f"pairs sharded over {world} GPU(s), all_gather of poses",
-                "pipelining": ("none" if a.no_overlap else "registration of step k on a second HIP stream under the matching of step k+1"
-                               + ("; K0 (ROI + gather) of step k+1 on a third stream under the screening / registration of step k"
-                                  if a.overlap_gather else "")),
-                "pose_sha256": pose_sha, "first_pair": 0,
-                "pairs_ok": int(ok.sum()), "max_rot_err_vs_gt": float(rot_err.max()) if rot_err.numel() else None,
-                "max_trans_err_m_vs_gt": float(trans_err.max()) if trans_err.numel() else None,
-            },
-            "roofline": {
-                "bound": "mfma", "kernel": kernel, "achieved": achieved, "peak": peak,
-                "unit": "TFLOP/s", "op": op,
-                "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src,
-                "flops_per_launch": flops, "avg_launch_ms": launch_ms,
-                "algorithmic_bytes_per_launch": alg_bytes, "hbm_frac": hbm_frac,
-                "share_of_step": match_ms / (elapsed / a.steps * 1e3),
-                "measured": "HIP events on the launch stream around every launch of the kernel inside the timed windows (pipelined: K0 of the "
-                            "next step and the registration of the previous ones run beside it)",
-                # the same figures as scalars (a parser that keeps only scalar entries of `roofline` still sees them)
-                "unshared_avg_launch_ms": unshared_ms,
-                "unshared_frac": None if unshared_ms is None else flops / (unshared_ms * 1e-3) / 1e12 / peak,
-                "frac_of_bare_loop_rate": (flops / (unshared_ms * 1e-3) / 1e12 / BARE_FP6_32x32x64_TFLOPS) if (unshared_ms is not None and "mx6" in dispatched) else None,
-                "k0_algorithmic_frac": k0["algorithmic_frac"] if k0 else None,
-                "k0_moved_frac": k0["moved_frac"] if k0 else None,
-                "k0_unshared_ms": k0_unshared_ms,
-                "k0": k0,
-                "unshared": (None if unshared_ms is None else
-                             {"avg_launch_ms": unshared_ms, "achieved": flops / (unshared_ms * 1e-3) / 1e12,
-                              "frac": flops / (unshared_ms * 1e-3) / 1e12 / peak,
-                              # what a bare register-resident loop of the same instruction sustains on this part under its power limit
-                              # (tools/probe_mfma_mx_rates.hip, profiles/r05_mfma_mx_rates.md: fp6 e2m3 32x32x64, random operand bits)
-                              "frac_of_bare_loop_rate": (flops / (unshared_ms * 1e-3) / 1e12 / BARE_FP6_32x32x64_TFLOPS) if "mx6" in dispatched else None,
-                              "bare_loop_tflops": BARE_FP6_32x32x64_TFLOPS if "mx6" in dispatched else None,
-                              "measured": "same events, 5 steps of a serial engine (one stream, nothing beside the kernel) in this run: the "
-                                          "figure a rocprofv3 kernel trace of this command shows, since the profiler serialises the queues"}),
-            },
+        rec["multi_gpu"] = multi
+        rec["config"].update({"pose_sha256": pose_sha, "first_pair": 0, "pairs_ok": int(ok.sum()),
+                              "max_rot_err_vs_gt": float(rot_err.max()) if rot_err.numel() else None,
+                              "max_trans_err_m_vs_gt": float(trans_err.max()) if trans_err.numel() else None})
+        rec["roofline"] = {
+            "bound": "mfma", "kernel": kernel, "achieved": achieved, "peak": peak,
+            "unit": "TFLOP/s", "op": op,
+            "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src,
+            "flops_per_launch": flops, "avg_launch_ms": launch_ms,
+            "algorithmic_bytes_per_launch": alg_bytes, "hbm_frac": hbm_frac,
+            "share_of_step": match_ms / (elapsed / a.steps * 1e3),
+            "measured": "HIP events on the launch stream around every launch of the kernel inside the timed windows (pipelined: K0 of the "
+                        "next step and the registration of the previous ones run beside it)",
+            # the same figures as scalars (a parser that keeps only scalar entries of `roofline` still sees them)
+            "unshared_avg_launch_ms": unshared_ms,
+            "unshared_frac": None if unshared_ms is None else flops / (unshared_ms * 1e-3) / 1e12 / peak,
+            "frac_of_bare_loop_rate": (flops / (unshared_ms * 1e-3) / 1e12 / BARE_FP6_32x32x64_TFLOPS) if (unshared_ms is not None and "mx6" in dispatched) else None,
+            "k0_algorithmic_frac": k0["algorithmic_frac"] if k0 else None,
+            "k0_moved_frac": k0["moved_frac"] if k0 else None,
+            "k0_unshared_ms": k0_unshared_ms,
+            "k0": k0,
+            "unshared": (None if unshared_ms is None else
+                         {"avg_launch_ms": unshared_ms, "achieved": flops / (unshared_ms * 1e-3) / 1e12,
+                          "frac": flops / (unshared_ms * 1e-3) / 1e12 / peak,
+                          # what a bare register-resident loop of the same instruction sustains on this part under its power limit
+                          # (tools/probe_mfma_mx_rates.hip, profiles/r05_mfma_mx_rates.md: fp6 e2m3 32x32x64, random operand bits)
+                          "frac_of_bare_loop_rate": (flops / (unshared_ms * 1e-3) / 1e12 / BARE_FP6_32x32x64_TFLOPS) if "mx6" in dispatched else None,
+                          "bare_loop_tflops": BARE_FP6_32x32x64_TFLOPS if "mx6" in dispatched else None,
+                          "measured": "same events, 5 steps of a serial engine (one stream, nothing beside the kernel) in this run: the "
+                                      "figure a rocprofv3 kernel trace of this command shows, since the profiler serialises the queues"}),
         }
         if world == 1 and not a.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(H, C)

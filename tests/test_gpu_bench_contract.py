@@ -1,9 +1,11 @@
-"""The driver's bench.py contract, checked on the GPU box: one JSON line, BASELINE.json's metric, the roofline and cpu_baseline objects."""
+"""The driver's bench.py contract, checked on the GPU box: one JSON line, BASELINE.json's metric; a plain run times one window and can dump
+its outputs, --full adds the roofline and cpu_baseline objects and the rest."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +23,7 @@ def _run(*flags):
 
 
 def test_default_line_carries_the_contract_fields():
-    rec = _run("--steps", "2", "--warmup", "1", "--batch", "8")
+    rec = _run("--full", "--steps", "2", "--warmup", "1", "--batch", "8")
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert rec["metric"] == base["metric"] and rec["unit"] == "pairs/s" and rec["n_gpus"] == 1
     assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["higher_is_better"] is True and rec["scaling"] == "weak"
@@ -36,9 +38,29 @@ def test_default_line_carries_the_contract_fields():
     assert cpu["kind"] in ("port", "reference") and cpu["value"] > 0 and cpu["cores"] >= 1 and cpu["unit"] == "pairs/s" and cpu["sample"]
 
 
+def test_plain_run_times_one_window_and_dumps_what_its_last_step_returned(tmp_path):
+    """Without --full: set-up, warm-up, ONE window of exactly --steps timed steps and the headline line, nothing measured after it;
+    --dump-outputs writes what the last timed step returned, the same arrays from run to run with the same arguments."""
+    args = ("--steps", "5", "--warmup", "2", "--batch", "8")
+    rec = _run(*args, "--dump-outputs", str(tmp_path / "a"))
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert rec["metric"] == base["metric"] and rec["unit"] == "pairs/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert rec["steps"] == 5 and rec["warmup"] == 2 and abs(rec["value"] - 8 * 1e3 / rec["ms_per_step"]) < 1e-6 * rec["value"]
+    assert len(rec["timing"]["windows_ms_per_step"]) == 1 and rec["timing"]["timed_steps_with_events"] == 5
+    assert not {"roofline", "cpu_baseline", "stages", "hard_descriptors", "sample_first_schedule"} & set(rec)
+    _run(*args, "--dump-outputs", str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["n_lifted.npy", "n_valid.npy", "pose.npy", "status.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and x.shape[0] == 8 and np.array_equal(x, y), n
+    pose, status = np.load(tmp_path / "a" / "pose.npy"), np.load(tmp_path / "a" / "status.npy")
+    assert pose.shape == (8, 4, 4) and (status == 0).all() and np.isfinite(pose).all()
+
+
 def test_other_matcher_modes_report_their_own_kernel():
     for mode, kern in (("screened16", "match_f16_screen_kernel"), ("exact", "match_f32_regb_kernel")):
-        rec = _run("--steps", "1", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--match-mode", mode)
+        rec = _run("--full", "--steps", "1", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--match-mode", mode)
         assert kern in rec["roofline"]["kernel"] and rec["config"]["pairs_ok"] == 4 and "cpu_baseline" not in rec
 
 
@@ -50,7 +72,7 @@ def test_two_gpu_run_over_rccl_equals_single_gpu_bit_for_bit():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs >= 2 GPUs (RCCL)")
-    common = ("--steps", "3", "--warmup", "1", "--reps", "2", "--size", "96", "--no-cpu-baseline", "--no-stage-sets")
+    common = ("--full", "--steps", "3", "--warmup", "1", "--reps", "2", "--size", "96", "--no-cpu-baseline", "--no-stage-sets")
     two = _run("--gpus", "2", "--batch", "8", *common)
     one = _run("--gpus", "1", "--batch", "16", *common)
     assert two["n_gpus"] == 2 and two["config"]["global_pairs"] == 16 and two["config"]["pairs_ok"] == 16
@@ -67,7 +89,7 @@ def test_two_gpu_run_over_rccl_equals_single_gpu_bit_for_bit():
     # the N = 2 ranks inherit what the N = 1 line was tuned on: each rank's own rate within 10 % of a single-GPU run of the SAME per-GPU
     # batch on the same box (weak scaling; the placement of the engine's streams is the thing a late pool creation used to break)
     # (measured on a workload long enough for the comparison to mean something: 16 pairs of 224 x 224 per GPU, 10-step windows)
-    rate = ("--steps", "10", "--warmup", "2", "--reps", "3", "--batch", "16", "--no-cpu-baseline", "--no-stage-sets")
+    rate = ("--full", "--steps", "10", "--warmup", "2", "--reps", "3", "--batch", "16", "--no-cpu-baseline", "--no-stage-sets")
     same = _run("--gpus", "1", *rate)
     both = _run("--gpus", "2", *rate)
     for r in both["multi_gpu"]["per_rank_pairs_per_s"]:
@@ -79,7 +101,7 @@ def test_one_rank_rccl_group_on_a_single_gpu_gives_the_same_poses_and_rate():
     engine's stream pool and collates every step through `all_gather_into_tensor` inside the timed region.  The collated poses equal the
     plain run's bit for bit, both collation modes run, and the communicator's own streams do not disturb the engine's placement:
     the step rate stays within 10 % of the plain run on the same box (the concern VERDICT r05 raised for the first multi-GPU run)."""
-    common = ("--steps", "10", "--warmup", "2", "--reps", "3", "--batch", "16", "--no-cpu-baseline", "--no-stage-sets", "--stream-roles", "0")
+    common = ("--full", "--steps", "10", "--warmup", "2", "--reps", "3", "--batch", "16", "--no-cpu-baseline", "--no-stage-sets", "--stream-roles", "0")
     plain = _run(*common)
     grp = _run("--process-group", *common)
     assert plain["multi_gpu"] is None
@@ -94,7 +116,7 @@ def test_one_rank_rccl_group_on_a_single_gpu_gives_the_same_poses_and_rate():
 
 
 def test_line_carries_timing_diagnostics():
-    rec = _run("--steps", "3", "--warmup", "1", "--batch", "8", "--reps", "3", "--no-cpu-baseline", "--no-stage-sets")
+    rec = _run("--full", "--steps", "3", "--warmup", "1", "--batch", "8", "--reps", "3", "--no-cpu-baseline", "--no-stage-sets")
     t = rec["timing"]
     assert len(t["windows_ms_per_step"]) == 3 and abs(rec["ms_per_step"] - sorted(t["windows_ms_per_step"])[1]) < 1e-3
     assert t["host_submit_ms_per_step"] > 0 and t["host_submit_ms_per_step_c_abi"] > 0
@@ -107,9 +129,9 @@ def test_line_carries_timing_diagnostics():
     assert abs(roof["unshared_frac"] - roof["unshared"]["frac"]) < 1e-12 and 0 < roof["frac_of_bare_loop_rate"] < 1.2
     assert 0 < roof["k0_algorithmic_frac"] < roof["k0_moved_frac"] < 1 and roof["k0_unshared_ms"] > 0
     assert t["stream_roles"] in (2345, 6345, 2341, 6341, 2301) and len(t["stream_roles_tuning"]["ms_per_step"]) == 5
-    fixed = _run("--steps", "2", "--warmup", "1", "--batch", "8", "--reps", "1", "--no-cpu-baseline", "--no-stage-sets", "--stream-roles", "2301")
+    fixed = _run("--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--reps", "1", "--no-cpu-baseline", "--no-stage-sets", "--stream-roles", "2301")
     assert fixed["timing"]["stream_roles"] == 2301 and fixed["config"]["pose_sha256"] == rec["config"]["pose_sha256"]      # placement never changes results
-    rec8 = _run("--steps", "2", "--warmup", "1", "--batch", "8", "--reps", "1", "--no-cpu-baseline", "--no-stage-sets", "--screen", "int8")
+    rec8 = _run("--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--reps", "1", "--no-cpu-baseline", "--no-stage-sets", "--screen", "int8")
     assert rec8["roofline"]["kernel"].startswith("match_i8_screen_v2_kernel<256, 0, 8>") and rec8["roofline"]["peak"] == 5000.0
-    assert rec8["config"]["pose_sha256"] == _run("--steps", "2", "--warmup", "1", "--batch", "8", "--reps", "1", "--no-cpu-baseline",
+    assert rec8["config"]["pose_sha256"] == _run("--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--reps", "1", "--no-cpu-baseline",
                                                    "--no-stage-sets")["config"]["pose_sha256"]      # same poses from either screen and len(rec["config"]["pose_sha256"]) == 64

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collect the rocprofv3 evidence that profiles/ holds, on the GPU box:  bash tools/collect_profiles.sh <out_dir>
-#   1. kernel-trace of `python bench.py` (default workload)                     -> <out>/kernel_stats.md + the printed JSON line
+#   1. kernel-trace of `python bench.py --full` (default workload)              -> <out>/kernel_stats.md + the printed JSON line
 #   2. separate --pmc passes (no trace domains besides --kernel-trace), restricted to the heavy kernels -> <out>/pmc_counters.md
 #   3. full (feat+match+pose) stage on the fp16x3 path: kernel trace + matrix-pipe counters -> <out>/full_stage_*.md
 #   4. decode stage set (fusion + decoder fast path): kernel trace + traffic / matrix-pipe counters of the decoder kernels -> <out>/decode_stage_*.md
@@ -9,19 +9,19 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=${1:-$R/gpurun_out/profiles}
 mkdir -p "$OUT"; OUT=$(cd "$OUT" && pwd)
 cd /tmp
-python $R/bench.py --no-cpu-baseline --no-stage-sets > "$OUT/bench_line.json" 2> /tmp/bench.err
+python $R/bench.py --full --no-cpu-baseline --no-stage-sets > "$OUT/bench_line.json" 2> /tmp/bench.err
 D=/tmp/prof_trace; rm -rf $D
-rocprofv3 --kernel-trace --stats -d $D -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-stage-sets > /tmp/trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $D -o bench -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-stage-sets > /tmp/trace.log 2>&1
 python $R/tools/rocpd_summary.py $D/bench_results.db --after "distribution_elementwise|index_elementwise" > "$OUT/kernel_stats.md"
 python $R/tools/rocpd_summary.py $D/bench_results.db --between "match_mx6_screen_w4" > "$OUT/kernel_stats_steps_only.md"
 python $R/tools/rocpd_summary.py $D/bench_results.db > "$OUT/kernel_stats_whole_run.md"
 RX='mx6_screen|screen_v2_kernel|gather_q8_v3|gather_mx6_v4|pdsc_att|match_decide|match_resolve|pdsc_linear|pdsc_pcn_qkv|pdsc_mlp3|pdsc_hyp|pdsc_seed|pdsc_head'
 {
-  echo "# rocprofv3 PMC passes: bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-overlap (2 engine passes, B=64), kernels /$RX/"
+  echo "# rocprofv3 PMC passes: bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-overlap (2 engine passes, B=64), kernels /$RX/"
   for SET in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS" \
              "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
     P=/tmp/prof_pmc; rm -rf $P
-    rocprofv3 --pmc $SET --kernel-trace --kernel-include-regex "$RX" -d $P -o p -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-stage-sets --no-overlap > /tmp/pmc.log 2>&1
+    rocprofv3 --pmc $SET --kernel-trace --kernel-include-regex "$RX" -d $P -o p -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-stage-sets --no-overlap > /tmp/pmc.log 2>&1
     echo; echo "## pass: $SET"; echo
     python $R/tools/rocpd_summary.py $P/p_results.db | sed -n '/## PMC counters/,$p' | tail -n +3
   done

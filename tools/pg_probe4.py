@@ -16,7 +16,7 @@ elif mode == "warm+gloo":
     warm_engine_streams(0); dist.init_process_group("gloo", rank=0, world_size=1)
 elif mode == "eager-nowarm":
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
-sys.argv = ["bench.py", "--steps", "20", "--warmup", "3", "--reps", "3", "--batch", "16", "--no-cpu-baseline", "--no-stage-sets", "--stream-roles", "0"] + sys.argv[2:]
+sys.argv = ["bench.py", "--full", "--steps", "20", "--warmup", "3", "--reps", "3", "--batch", "16", "--no-cpu-baseline", "--no-stage-sets", "--stream-roles", "0"] + sys.argv[2:]
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
     try:
@@ -27,4 +27,4 @@ with contextlib.redirect_stdout(buf):
         print("EXC", repr(e), file=sys.stderr)
 L = [l for l in buf.getvalue().splitlines() if l.startswith("{")]
 r = json.loads(L[-1])
-print(mode, sys.argv[13:], "pairs/s", round(r["value"]), "ms_per_step", round(r["ms_per_step"], 4), "grouped", r["multi_gpu"] is not None)
+print(mode, sys.argv[14:], "pairs/s", round(r["value"]), "ms_per_step", round(r["ms_per_step"], 4), "grouped", r["multi_gpu"] is not None)
