@@ -271,6 +271,37 @@ int oryon_match_corrs_mx6_x3(const float *a_hat, const uint8_t *a_mx6, const flo
                              int32_t *n_valid, int32_t *n_sel, int32_t *status, int32_t *n_undecided, int round_f16, void *workspace,
                              size_t workspace_bytes, void *stream);
 
+/* Anchor rows on demand.  The three lazy matchers above read the anchors' fp32 unit rows a_hat [B, cap_a, C] - which K0 has to write, 1 KB
+ * per anchor at C = 256, 80 % of what its anchor pass stores - for a few hundred rows per pair only: the sampled rows with more than one
+ * candidate, the rows whose validity the screen leaves open and the ambiguous rows' compacted lists.  The `_araw` entries take the raw
+ * anchor map instead (feat_a, the map the anchor operands were gathered from - same C_true / HW / layout as feat_q - and a_norm [B, cap_a],
+ * the row_norm output of the anchor pass) and form those rows themselves, exactly as K0 does: x_k at pixel roi_a[row] (rounded to float16
+ * first under round_f16, zero for k >= C_true) divided by a_norm[row], correctly rounded - bit for bit the value K0 stores.  K0 is then
+ * called with out_f32 = NULL for the anchors.  Every output equals that of the entry without the suffix, bit for bit (utils/pcd.py:202-214
+ * as there).  Lazy route only: there is no force_eager (the eager tail reads whole pairs of rows - oryon_match_corrs_i8 on materialised
+ * rows keeps that).  Workspace: oryon_match_corrs_i8_workspace_bytes. */
+int oryon_match_corrs_i8_araw(const float *feat_a, const float *a_norm, const int8_t *a_i8, const float *a_scale, const float *feat_q, int C_true,
+                              int HW, int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
+                              const float *q_norm, const int8_t *q_i8, const float *q_scale, const float *q_eps_max, int B, int C, int cap_a,
+                              int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs, int corr_rows,
+                              uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin, uint8_t *valid, int32_t *corrs,
+                              int32_t *n_valid, int32_t *n_sel, int32_t *status, int32_t *n_undecided, int round_f16, void *workspace,
+                              size_t workspace_bytes, void *stream);
+int oryon_match_corrs_mx6_araw(const float *feat_a, const float *a_norm, const uint8_t *a_mx6, const float *a_err_max, const float *feat_q,
+                               int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
+                               const float *q_norm, const uint8_t *q_mx6, const float *q_err_max, int B, int C, int cap_a, int cap_q,
+                               const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs, int corr_rows, uint64_t seed,
+                               const int64_t *pair_key, float *min_dist, int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid,
+                               int32_t *n_sel, int32_t *status, int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes,
+                               void *stream);
+int oryon_match_corrs_mx6_x3_araw(const float *feat_a, const float *a_norm, const uint8_t *a_mx6, const float *a_err_max, const float *feat_q,
+                                  int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q,
+                                  int roi_stride_q, const float *q_norm, const uint8_t *q_mx6, const float *q_err_max, const void *q_hi_lo_f16,
+                                  const float *q_lo_sq_max, int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q,
+                                  float threshold, int W, int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist,
+                                  int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
+                                  int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream);
+
 /* "Sample first" (optional engine schedule, off by default).  Only max_corrs correspondences per pair leave the matcher
  * (utils/pcd.py:205-214), drawn uniformly from the valid anchor rows - so a uniformly random first-stage subset of the anchors that
  * already holds >= max_corrs valid rows yields an identically distributed sample.  The engine runs the matcher on such a subset;
@@ -423,8 +454,10 @@ typedef struct {
                                 default since round 5: a third set adds 3.4 ms of queueing to a step's latency (14.1 -> 10.7 ms at cfg2) and no throughput */
     int reg_streams;         /* registration streams the steps alternate over (2; <= 4) */
     int reg_lag;             /* > 0: the matcher of step k waits for the registration of step k - reg_lag (< n_slots); 0 = never (default) */
-    int screen;              /* 0 = int8 screen (oryon_gather_q8 + oryon_match_corrs_i8), 1 = MX-fp6 screen (oryon_gather_mx6 +
-                                oryon_match_corrs_mx6; steps submitted with force_eager take the int8 route) */
+    int screen;              /* 0 = int8 screen (oryon_gather_q8 + oryon_match_corrs_i8_araw), 1 = MX-fp6 screen (oryon_gather_mx6 +
+                                oryon_match_corrs_mx6_araw); steps submitted with force_eager take the int8 route on materialised fp32
+                                anchor rows (oryon_match_corrs_i8); their K0 and that of the hard route (x3_prefetch below,
+                                oryon_match_corrs_mx6_x3) are the only ones that write those rows */
     int sample_first;        /* 0 = off (default).  N > 0: the "sample first" schedule (see oryon_sample_first_gate): the matcher first
                                 sees a uniformly random N-anchor subset per pair; pairs whose subset holds fewer than n_corrs valid rows are
                                 redone on all anchors, gated on the device.  Same distribution of the sampled correspondences, not the same

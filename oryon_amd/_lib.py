@@ -84,6 +84,15 @@ _PROTOS = {
     "oryon_match_corrs_mx6_x3": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
                                          _P, _P, c_float, c_int, c_int, c_int, c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P,
                                          c_size_t, _P]),
+    "oryon_match_corrs_i8_araw": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int,
+                                          c_int, _P, _P, c_float, c_int, c_int, c_int, c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int,
+                                          _P, c_size_t, _P]),
+    "oryon_match_corrs_mx6_araw": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int,
+                                           c_int, _P, _P, c_float, c_int, c_int, c_int, c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int,
+                                           _P, c_size_t, _P]),
+    "oryon_match_corrs_mx6_x3_araw": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int,
+                                              c_int, c_int, _P, _P, c_float, c_int, c_int, c_int, c_uint64, _P, _P, _P, _P, _P, _P, _P, _P,
+                                              _P, c_int, _P, c_size_t, _P]),
     "oryon_match_screened8_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "oryon_match_screened8": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_float, _P, _P, _P,
                                       _P, _P, c_size_t, _P]),

@@ -5,7 +5,7 @@
 // enqueues everything:
 //
 //     gather stream G : K0   roi_compact x2 -> roi_subsample -> gather_q8 (queries) -> gather_q8 (anchors)
-//     match  stream M : K1s8 oryon_match_corrs_i8 (int8 screen, lazy tail, sampling)  -> K2 oryon_lift_pairs
+//     match  stream M : K1s8 oryon_match_corrs_{i8,mx6}_araw (screen, lazy tail, sampling)  -> K2 oryon_lift_pairs
 //     reg    stream R : K3-K10 oryon_pointdsc_register                                  (one stream per slot)
 //
 // on streams and events the engine owns, over a persistent arena carved once (no allocation, no torch object, no Python per
@@ -47,9 +47,10 @@ struct GatherBuf {
     float *a_sc, *q_sc, *a_eps, *q_eps, *a_norm, *q_norm, *a_hat;
     void *q_hilo;                // cfg.x3_prefetch: [2][B, cap_q, 256] halves (hi rows | lo rows of the query rows) + q_lo_max [B]
     float *q_lo_max;
-    // cfg.sample_first: the first-stage anchor subset's operands (cap_a1 rows); a8 / a_hat then serve the gated second stage
+    // cfg.sample_first: the first-stage anchor subset's operands (cap_a1 rows); a8 / a_norm then serve the gated second stage.  (No fp32
+    // rows for either stage: a_hat is written on force_eager and hard-route steps only, and neither takes the sample_first schedule)
     int8_t *a8_1;
-    float *a_sc_1, *a_eps_1, *a_norm_1, *a_hat_1;
+    float *a_sc_1, *a_eps_1, *a_norm_1;
 };
 
 struct SlotBuf {
@@ -161,13 +162,12 @@ int carve_engine(const oryon_engine_config_t &c, const oryon_pointdsc_t *solver,
             TAKE(q_lo_max, float, B);
         }
         b.a8_1 = nullptr;
-        b.a_sc_1 = b.a_eps_1 = b.a_norm_1 = b.a_hat_1 = nullptr;
+        b.a_sc_1 = b.a_eps_1 = b.a_norm_1 = nullptr;
         if (L.cap_a1) {
             TAKE(a8_1, int8_t, B * L.cap_a1 * L.c_pad);
             TAKE(a_sc_1, float, B * (L.cap_a1 / 16));
             TAKE(a_eps_1, float, B);
             TAKE(a_norm_1, float, B * L.cap_a1);
-            TAKE(a_hat_1, float, B * L.cap_a1 * L.c_pad);
         }
 #undef TAKE
     }
@@ -545,13 +545,17 @@ extern "C" int oryon_engine_submit(oryon_engine_t *e, const float *feat_a, const
     const int32_t *roi_a_k0 = b.roi_a, *n_a_k0 = b.n_a;
     int cap_a_k0 = e->L.cap_a;
     int8_t *a8_k0 = g.a8;
-    float *a_sc_k0 = g.a_sc, *a_eps_k0 = g.a_eps, *a_norm_k0 = g.a_norm, *a_hat_k0 = g.a_hat;
+    // the anchors' fp32 unit rows (g.a_hat, 1 KB per row at C_pad 256): the lazy tail reads a few hundred of them per pair at most and
+    // forms those from feat_a / roi_a / a_norm (the `_araw` matcher entries), so the anchor pass stores the screening operands and the norms
+    // alone.  Two kinds of step keep the materialised rows: force_eager (the eager tail reads whole pairs of rows) and, further down,
+    // the hard route (x3_pre)
+    float *a_sc_k0 = g.a_sc, *a_eps_k0 = g.a_eps, *a_norm_k0 = g.a_norm, *a_hat_k0 = force_eager ? g.a_hat : nullptr;
     if (sf) {
         ORYON_CHECK_HIP(hipMemcpyAsync(b.roi_a1, b.roi_a, (size_t)B * HW * sizeof(int32_t), hipMemcpyDeviceToDevice, sg));
         ORYON_CHECK_HIP(hipMemcpyAsync(b.n_a1, b.n_a, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, sg));
         if ((rc = oryon_roi_subsample(b.roi_a1, b.n_a1, B, HW, c.sample_first, c.seed ^ 0x5A17F125ull, pair_key, sg))) return rc;
         roi_a_k0 = b.roi_a1; n_a_k0 = b.n_a1; cap_a_k0 = e->L.cap_a1;
-        a8_k0 = g.a8_1; a_sc_k0 = g.a_sc_1; a_eps_k0 = g.a_eps_1; a_norm_k0 = g.a_norm_1; a_hat_k0 = g.a_hat_1;
+        a8_k0 = g.a8_1; a_sc_k0 = g.a_sc_1; a_eps_k0 = g.a_eps_1; a_norm_k0 = g.a_norm_1;
     }
     // cfg.x3_prefetch: what the most recently COMPLETED steps report (their n_und / n_a arrays in pinned memory, behind an event that is
     // only queried, never waited for) decides whether this step's K0 pass also writes the hi / lo rows of the second level
@@ -568,6 +572,9 @@ extern "C" int oryon_engine_submit(oryon_engine_t *e, const float *feat_a, const
         }
         x3_pre = e->hard_mode && !sf && g.q_hilo != nullptr;
     }
+    // hard route: every sampled anchor is ambiguous there, so the tail compacts ~500 rows per pair - 1 KB contiguous each from a_hat, but
+    // 256 scattered sectors each from the raw map (131 against 27 us per step at cfg2, more than the 57 us the anchor pass saves: DESIGN §8)
+    if (x3_pre) a_hat_k0 = g.a_hat;
     if (timing) ORYON_CHECK_HIP(hipEventRecord(tev[8], sg));          // the ROI kernels are behind us: K0's gather launches start here
     if (ablate & 1) {
     } else if (mx6) {
@@ -606,40 +613,46 @@ extern "C" int oryon_engine_submit(oryon_engine_t *e, const float *feat_a, const
     }
     // corrs rows beyond max_corrs are never written by the sampler and K2 only reads n_sel rows: no zero-fill needed
     // one matcher call (the engine's screen setting) on the given anchor operands
-    auto match_call = [&](const float *a_hat_, const int8_t *a8_, const float *a_sc_, const float *a_eps_, const int32_t *roi_a_, int cap_a_,
+    auto match_call = [&](const float *a_norm_, const int8_t *a8_, const float *a_sc_, const float *a_eps_, const int32_t *roi_a_, int cap_a_,
                           const int32_t *n_a_, int32_t *corrs_, int32_t *n_valid_, int32_t *n_sel_, int32_t *status_, int32_t *n_und_) -> int {
         if (mx6 && x3_pre)
-            return oryon_match_corrs_mx6_x3(a_hat_, reinterpret_cast<const uint8_t *>(a8_), a_eps_, feat_q, c.C, HW, c.layout, roi_a_, HW, b.roi_q, HW,
+            return oryon_match_corrs_mx6_x3(g.a_hat, reinterpret_cast<const uint8_t *>(a8_), a_eps_, feat_q, c.C, HW, c.layout, roi_a_, HW, b.roi_q, HW,
                                             g.q_norm, reinterpret_cast<const uint8_t *>(g.q8), g.q_eps, g.q_hilo, g.q_lo_max, B, e->L.c_pad, cap_a_,
                                             e->L.cap_q, n_a_, b.n_q, c.dist_th, c.FW, c.n_corrs, e->L.n_cap, c.seed, pair_key, b.min_dist, b.argmin,
                                             b.valid, corrs_, n_valid_, n_sel_, status_, n_und_, c.round_f16, e->L.match_ws, e->L.match_ws_bytes, sm);
         if (mx6)
-            return oryon_match_corrs_mx6(a_hat_, reinterpret_cast<const uint8_t *>(a8_), a_eps_, feat_q, c.C, HW, c.layout, roi_a_, HW, b.roi_q, HW,
-                                         g.q_norm, reinterpret_cast<const uint8_t *>(g.q8), g.q_eps, B, e->L.c_pad, cap_a_, e->L.cap_q, n_a_, b.n_q,
-                                         c.dist_th, c.FW, c.n_corrs, e->L.n_cap, c.seed, pair_key, b.min_dist, b.argmin, b.valid, corrs_, n_valid_,
-                                         n_sel_, status_, n_und_, c.round_f16, e->L.match_ws, e->L.match_ws_bytes, sm);
-        return oryon_match_corrs_i8(a_hat_, a8_, a_sc_, feat_q, c.C, HW, c.layout, roi_a_, HW, b.roi_q, HW, g.q_norm, g.q8, g.q_sc, g.q_eps, B,
+            return oryon_match_corrs_mx6_araw(feat_a, a_norm_, reinterpret_cast<const uint8_t *>(a8_), a_eps_, feat_q, c.C, HW, c.layout, roi_a_, HW,
+                                              b.roi_q, HW, g.q_norm, reinterpret_cast<const uint8_t *>(g.q8), g.q_eps, B, e->L.c_pad, cap_a_, e->L.cap_q,
+                                              n_a_, b.n_q, c.dist_th, c.FW, c.n_corrs, e->L.n_cap, c.seed, pair_key, b.min_dist, b.argmin, b.valid,
+                                              corrs_, n_valid_, n_sel_, status_, n_und_, c.round_f16, e->L.match_ws, e->L.match_ws_bytes, sm);
+        if (!force_eager)
+            return oryon_match_corrs_i8_araw(feat_a, a_norm_, a8_, a_sc_, feat_q, c.C, HW, c.layout, roi_a_, HW, b.roi_q, HW, g.q_norm, g.q8, g.q_sc,
+                                             g.q_eps, B, e->L.c_pad, cap_a_, e->L.cap_q, n_a_, b.n_q, c.dist_th, c.FW, c.n_corrs, e->L.n_cap, c.seed,
+                                             pair_key, b.min_dist, b.argmin, b.valid, corrs_, n_valid_, n_sel_, status_, n_und_, c.round_f16,
+                                             e->L.match_ws, e->L.match_ws_bytes, sm);
+        // force_eager: complete min_dist / argmin arrays from whole fp32 rows (K0 wrote g.a_hat on this step; never with sample_first)
+        return oryon_match_corrs_i8(g.a_hat, a8_, a_sc_, feat_q, c.C, HW, c.layout, roi_a_, HW, b.roi_q, HW, g.q_norm, g.q8, g.q_sc, g.q_eps, B,
                                     e->L.c_pad, cap_a_, e->L.cap_q, n_a_, b.n_q, c.dist_th, c.FW, c.n_corrs, e->L.n_cap, c.seed, pair_key, force_eager,
                                     b.min_dist, b.argmin, b.valid, corrs_, n_valid_, n_sel_, status_, n_und_, c.round_f16, e->L.match_ws,
                                     e->L.match_ws_bytes, sm);
     };
     if (ablate & 2) {
     } else if (sf) {
-        if ((rc = match_call(g.a_hat_1, g.a8_1, g.a_sc_1, g.a_eps_1, b.roi_a1, e->L.cap_a1, b.n_a1, b.corrs, b.n_valid, b.n_sel, b.status, b.n_und)))
+        if ((rc = match_call(g.a_norm_1, g.a8_1, g.a_sc_1, g.a_eps_1, b.roi_a1, e->L.cap_a1, b.n_a1, b.corrs, b.n_valid, b.n_sel, b.status, b.n_und)))
             return rc;
         if ((rc = oryon_sample_first_gate(b.n_valid, b.n_a1, b.n_a, B, c.n_corrs, b.n_a2, sm))) return rc;
         // second stage for the pairs that came up short: their anchors' operands (every other pair has a zero count: nothing is gathered or
         // matched for it), the matcher on all anchors, rows / counts / status of those pairs copied over the first stage's
         if (mx6) {
             if ((rc = oryon_gather_mx6(feat_a, B, c.C, HW, c.layout, b.roi_a, HW, b.n_a2, e->L.cap_a, e->L.c_pad, reinterpret_cast<uint8_t *>(g.a8),
-                                       g.a_eps, g.a_norm, g.a_hat, c.round_f16, sm))) return rc;
+                                       g.a_eps, g.a_norm, nullptr, c.round_f16, sm))) return rc;
         } else if ((rc = oryon_gather_q8(feat_a, B, c.C, HW, c.layout, b.roi_a, HW, b.n_a2, e->L.cap_a, e->L.c_pad, g.a8, g.a_sc, g.a_eps, g.a_norm,
-                                         g.a_hat, c.round_f16, sm))) return rc;
-        if ((rc = match_call(g.a_hat, g.a8, g.a_sc, g.a_eps, b.roi_a, e->L.cap_a, b.n_a2, b.corrs2, b.n_valid2, b.n_sel2, b.status2, nullptr)))
+                                         nullptr, c.round_f16, sm))) return rc;
+        if ((rc = match_call(g.a_norm, g.a8, g.a_sc, g.a_eps, b.roi_a, e->L.cap_a, b.n_a2, b.corrs2, b.n_valid2, b.n_sel2, b.status2, nullptr)))
             return rc;
         if ((rc = oryon_sample_first_merge(b.n_a2, b.corrs2, b.n_valid2, b.n_sel2, b.status2, B, e->L.n_cap, b.corrs, b.n_valid, b.n_sel, b.status,
                                            sm))) return rc;
-    } else if ((rc = match_call(g.a_hat, g.a8, g.a_sc, g.a_eps, b.roi_a, e->L.cap_a, b.n_a, b.corrs, b.n_valid, b.n_sel, b.status, b.n_und)))
+    } else if ((rc = match_call(g.a_norm, g.a8, g.a_sc, g.a_eps, b.roi_a, e->L.cap_a, b.n_a, b.corrs, b.n_valid, b.n_sel, b.status, b.n_und)))
         return rc;
     if (e->fb_host && mx6 && !(ablate & 2)) {
         int32_t *h = e->fb_host + (size_t)slot * 2 * B;

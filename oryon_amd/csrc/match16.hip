@@ -1717,8 +1717,27 @@ __device__ __forceinline__ float mx6_block_dot(const uint4 a_lo, const uint4 a_u
     return sum * ldexpf(1.0f, (int)(a_up.z & 255u) + (int)(q_up.z & 255u) - 254);
 }
 
+// Anchor rows on demand (the `_araw` entries): where K0 wrote no fp32 unit rows (a_hat == nullptr), a consumer forms the row itself from
+// the raw anchor map, exactly as K0 does - x_k at the anchor's pixel (rounded to float16 first under round_f16, zero beyond C_true),
+// divided by the norm K0 left in a_norm: __fdiv_rn(x_k, d), bit for bit the value K0 would have stored.
+struct AnchorRaw {
+    const float *feat_a;        // [B, C_true, HW] (or channels-last), the map K0 gathered the anchors from
+    const int32_t *roi_a;       // [B, roi_stride] pixel of every anchor row
+    const float *a_norm;        // [B, cap_a] K0's row norms
+    int roi_stride;
+};
+
+template <bool NHWC>
+__device__ __forceinline__ float anchor_raw_unit(const float *__restrict__ fa, int pix, float d, int k, int C_true, int HW, int round_f16)
+{
+    float x = 0.0f;
+    if (k < C_true) x = NHWC ? fa[(size_t)pix * C_true + k] : fa[(size_t)k * HW + pix];
+    if (round_f16) x = __half2float(__float2half_rn(x));
+    return __fdiv_rn(x, d);
+}
+
 template <bool NHWC, bool NEED_DIST = true, int FMT = 0>
-__device__ __forceinline__ void resolve_anchor(int p, int a, const float *__restrict__ a_hat, const int8_t *__restrict__ a8,
+__device__ __forceinline__ void resolve_anchor(int p, int a, const float *__restrict__ a_hat, const AnchorRaw &araw, const int8_t *__restrict__ a8,
                                                const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
                                                const float *__restrict__ a_scale8, const float *__restrict__ feat_q, int C_true, int HW,
                                                const int32_t *__restrict__ roi_q, int roi_stride, const float *__restrict__ norm_q,
@@ -1779,9 +1798,17 @@ __device__ __forceinline__ void resolve_anchor(int p, int a, const float *__rest
     }
     // anchor row (k-permuted: position 8g + 4h + j holds k = 8g + 2j + h) -> natural order in LDS
     float *A = lds, *Q = lds + Cp;
-    for (int pos = lane; pos < Cp; pos += 64) {
-        const int g = pos >> 3, hh = (pos >> 2) & 1, jj = pos & 3;
-        A[8 * g + 2 * jj + hh] = a_hat[arow * Cp + pos];
+    if (a_hat) {
+        for (int pos = lane; pos < Cp; pos += 64) {
+            const int g = pos >> 3, hh = (pos >> 2) & 1, jj = pos & 3;
+            A[8 * g + 2 * jj + hh] = a_hat[arow * Cp + pos];
+        }
+    } else {
+        // no materialised row: the same values from the raw map (one pass, Cp / 64 independent loads per lane), natural order as they come
+        const float *fa = araw.feat_a + (size_t)p * C_true * HW;
+        const int pix_a = araw.roi_a[(size_t)p * araw.roi_stride + a];
+        const float da = araw.a_norm[arow];
+        for (int k = lane; k < Cp; k += 64) A[k] = anchor_raw_unit<NHWC>(fa, pix_a, da, k, C_true, HW, round_f16);
     }
     float d = INFINITY;
     int j = 0x7fffffff;
@@ -1818,10 +1845,45 @@ __device__ __forceinline__ void resolve_anchor(int p, int a, const float *__rest
     j_out = j;
 }
 
+// match_compact_f32_kernel for the `_araw` entries: the listed anchors' fp32 unit rows formed from the raw map (anchor_raw_unit) and
+// written in the k-permuted order K0's rows have (position 8g + 4h + j holds k = 8g + 2j + h), which is what K1 / K1x3 read.  One wave
+// per row, one 16-byte store per lane: lane i of a pass owns positions 4i .. 4i + 3 = (g, h) = (i >> 1, i & 1), j = 0 .. 3.
+template <bool NHWC>
+__global__ __launch_bounds__(256) void match_compact_raw_kernel(const AnchorRaw araw, int C_true, int HW, int round_f16, int Cp, int cap_a,
+                                                                 int cap_c, const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
+                                                                 int idx_stride, float *__restrict__ a_c)
+{
+    const int p = blockIdx.y, lane = threadIdx.x & 63;
+    const int n = count[p] < cap_c ? count[p] : cap_c;
+    const int n_fill = (n + 127) / 128 * 128;
+    const float *fa = araw.feat_a + (size_t)p * C_true * HW;
+    for (int g = 0; g < 16; ++g) {
+        const int sl = (blockIdx.x * 16 + g) * 4 + (threadIdx.x >> 6);
+        if (sl >= n_fill || sl >= cap_c) break;
+        float4 *d = reinterpret_cast<float4 *>(a_c + ((size_t)p * cap_c + sl) * Cp);
+        if (sl >= n) {
+            for (int i = lane; i < Cp / 4; i += 64) d[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        const int a = idx[(size_t)p * idx_stride + sl];
+        const int pix = araw.roi_a[(size_t)p * araw.roi_stride + a];
+        const float da = araw.a_norm[(size_t)p * cap_a + a];
+        for (int i = lane; i < Cp / 4; i += 64) {
+            const int k0 = 8 * (i >> 1) + (i & 1);
+            float4 q;
+            q.x = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 0, C_true, HW, round_f16);
+            q.y = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 2, C_true, HW, round_f16);
+            q.z = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 4, C_true, HW, round_f16);
+            q.w = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 6, C_true, HW, round_f16);
+            d[i] = q;
+        }
+    }
+}
+
 // anchors whose VALIDITY the int8 bound could not settle (pairs on the lazy route only): exact distance now, before the sampling
 template <bool NHWC, int FMT = 0>
 __global__ __launch_bounds__(256) void match_resolve_uncertain_kernel(
-    const float *__restrict__ a_hat, const int8_t *__restrict__ a8, const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
+    const float *__restrict__ a_hat, const AnchorRaw araw, const int8_t *__restrict__ a8, const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
     const float *__restrict__ a_scale8, const float *__restrict__ feat_q, int C_true, int HW, const int32_t *__restrict__ roi_q,
     int roi_stride, const float *__restrict__ norm_q, int Cp, int cap_a, int cap_q, const int32_t *__restrict__ n_q, float thr,
     const float *__restrict__ m_final, const int32_t *__restrict__ sid_final, const float *__restrict__ margin_in,
@@ -1838,7 +1900,7 @@ __global__ __launch_bounds__(256) void match_resolve_uncertain_kernel(
         const size_t arow = (size_t)p * cap_a + a;
         float d;
         int j;
-        resolve_anchor<NHWC, true, FMT>(p, a, a_hat, a8, q8, q_scale8, a_scale8, feat_q, C_true, HW, roi_q, roi_stride, norm_q, Cp, cap_a, cap_q, n_q[p],
+        resolve_anchor<NHWC, true, FMT>(p, a, a_hat, araw, a8, q8, q_scale8, a_scale8, feat_q, C_true, HW, roi_q, roi_stride, norm_q, Cp, cap_a, cap_q, n_q[p],
                              m_final[arow], sid_final[arow], margin_in[arow], lds_res + wave * 2 * Cp, round_f16, d, j);
         if (lane == 0) {
             min_dist[arow] = d;
@@ -1852,7 +1914,7 @@ __global__ __launch_bounds__(256) void match_resolve_uncertain_kernel(
 // the sampled rows of the lazy pairs: exact argmin -> query half of the correspondence
 template <bool NHWC, int FMT = 0>
 __global__ __launch_bounds__(256) void match_resolve_selected_kernel(
-    const float *__restrict__ a_hat, const int8_t *__restrict__ a8, const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
+    const float *__restrict__ a_hat, const AnchorRaw araw, const int8_t *__restrict__ a8, const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
     const float *__restrict__ a_scale8, const float *__restrict__ feat_q, int C_true, int HW, const int32_t *__restrict__ roi_q,
     int roi_stride, const float *__restrict__ norm_q, int Cp, int cap_a, int cap_q, const int32_t *__restrict__ n_q, int W,
     const float *__restrict__ m_final, const int32_t *__restrict__ sid_final, const float *__restrict__ margin_in,
@@ -1873,7 +1935,7 @@ __global__ __launch_bounds__(256) void match_resolve_selected_kernel(
     if (state[arow] == LZ_RESOLVED) {
         j = argmin[arow];
     } else {
-        resolve_anchor<NHWC, false, FMT>(p, a, a_hat, a8, q8, q_scale8, a_scale8, feat_q, C_true, HW, roi_q, roi_stride, norm_q, Cp, cap_a, cap_q,
+        resolve_anchor<NHWC, false, FMT>(p, a, a_hat, araw, a8, q8, q_scale8, a_scale8, feat_q, C_true, HW, roi_q, roi_stride, norm_q, Cp, cap_a, cap_q,
                                     n_q[p], m_final[arow], sid_final[arow], margin_in[arow], lds_res + wave * 2 * Cp, round_f16, d, j);
         if (lane == 0) {                                                // same values from every slot that drew this row
             argmin[arow] = j;
@@ -2010,7 +2072,8 @@ static int match_corrs_lazy_impl(const float *a_hat, const int8_t *a_i8, const f
                                  int corr_rows, uint64_t seed, const int64_t *pair_key, int force_eager, float *min_dist,
                                  int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
                                  int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream, int fmt,
-                                 const void *q_hi_lo = nullptr, const float *q_lo_sq_max = nullptr);
+                                 const void *q_hi_lo = nullptr, const float *q_lo_sq_max = nullptr, const float *feat_a = nullptr,
+                                 const float *a_norm = nullptr);
 
 extern "C" int oryon_match_corrs_i8(const float *a_hat, const int8_t *a_i8, const float *a_scale, const float *feat_q, int C_true, int HW,
                                     int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
@@ -2057,6 +2120,55 @@ extern "C" int oryon_match_corrs_mx6_x3(const float *a_hat, const uint8_t *a_mx6
                                  n_undecided, round_f16, workspace, workspace_bytes, stream, 1, q_hi_lo_f16, q_lo_sq_max);
 }
 
+// ---- the same three entries WITHOUT materialised fp32 anchor rows: feat_a / a_norm (K0's row_norm of the anchor pass) in place of a_hat.
+// The few rows the lazy tail needs are formed on demand (AnchorRaw above).  Lazy route only: the eager tail (force_eager of
+// oryon_match_corrs_i8) reads whole pairs of rows and stays with the materialised ones.
+extern "C" int oryon_match_corrs_i8_araw(const float *feat_a, const float *a_norm, const int8_t *a_i8, const float *a_scale, const float *feat_q,
+                                         int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q,
+                                         int roi_stride_q, const float *q_norm, const int8_t *q_i8, const float *q_scale, const float *q_eps_max,
+                                         int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W,
+                                         int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin,
+                                         uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
+                                         int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ORYON_CHECK_ARG(feat_a && a_norm && a_scale && q_scale);
+    return match_corrs_lazy_impl(nullptr, a_i8, a_scale, feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q, roi_stride_q, q_norm, q_i8, q_scale,
+                                 q_eps_max, B, C, cap_a, cap_q, n_a, n_q, threshold, W, max_corrs, corr_rows, seed, pair_key, 0, min_dist, argmin,
+                                 valid, corrs, n_valid, n_sel, status, n_undecided, round_f16, workspace, workspace_bytes, stream, 0, nullptr, nullptr,
+                                 feat_a, a_norm);
+}
+
+extern "C" int oryon_match_corrs_mx6_araw(const float *feat_a, const float *a_norm, const uint8_t *a_mx6, const float *a_err_max,
+                                          const float *feat_q, int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a,
+                                          const int32_t *roi_q, int roi_stride_q, const float *q_norm, const uint8_t *q_mx6, const float *q_err_max,
+                                          int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W,
+                                          int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin,
+                                          uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status, int32_t *n_undecided,
+                                          int round_f16, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ORYON_CHECK_ARG(feat_a && a_norm && a_err_max && q_err_max);
+    return match_corrs_lazy_impl(nullptr, reinterpret_cast<const int8_t *>(a_mx6), a_err_max, feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q,
+                                 roi_stride_q, q_norm, reinterpret_cast<const int8_t *>(q_mx6), nullptr, q_err_max, B, C, cap_a, cap_q, n_a, n_q,
+                                 threshold, W, max_corrs, corr_rows, seed, pair_key, 0, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
+                                 n_undecided, round_f16, workspace, workspace_bytes, stream, 1, nullptr, nullptr, feat_a, a_norm);
+}
+
+extern "C" int oryon_match_corrs_mx6_x3_araw(const float *feat_a, const float *a_norm, const uint8_t *a_mx6, const float *a_err_max,
+                                             const float *feat_q, int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a,
+                                             const int32_t *roi_q, int roi_stride_q, const float *q_norm, const uint8_t *q_mx6,
+                                             const float *q_err_max, const void *q_hi_lo_f16, const float *q_lo_sq_max, int B, int C, int cap_a,
+                                             int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs,
+                                             int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin,
+                                             uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
+                                             int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ORYON_CHECK_ARG(feat_a && a_norm && a_err_max && q_err_max && q_hi_lo_f16 && q_lo_sq_max && C == 256);
+    return match_corrs_lazy_impl(nullptr, reinterpret_cast<const int8_t *>(a_mx6), a_err_max, feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q,
+                                 roi_stride_q, q_norm, reinterpret_cast<const int8_t *>(q_mx6), nullptr, q_err_max, B, C, cap_a, cap_q, n_a, n_q,
+                                 threshold, W, max_corrs, corr_rows, seed, pair_key, 0, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
+                                 n_undecided, round_f16, workspace, workspace_bytes, stream, 1, q_hi_lo_f16, q_lo_sq_max, feat_a, a_norm);
+}
+
 static int match_corrs_lazy_impl(const float *a_hat, const int8_t *a_i8, const float *a_scale, const float *feat_q, int C_true, int HW,
                                  int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
                                  const float *q_norm, const int8_t *q_i8, const float *q_scale, const float *q_eps_max, int B, int C,
@@ -2064,9 +2176,12 @@ static int match_corrs_lazy_impl(const float *a_hat, const int8_t *a_i8, const f
                                  int corr_rows, uint64_t seed, const int64_t *pair_key, int force_eager, float *min_dist,
                                  int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
                                  int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream, int fmt,
-                                 const void *q_hi_lo, const float *q_lo_sq_max)
+                                 const void *q_hi_lo, const float *q_lo_sq_max, const float *feat_a, const float *a_norm)
 {
-    ORYON_CHECK_ARG(a_hat && a_i8 && a_scale && feat_q && roi_a && roi_q && q_norm && q_i8 && q_eps_max && n_a && n_q);
+    // a_hat == nullptr (the `_araw` entries): the anchors' fp32 unit rows are formed on demand from feat_a / roi_a / a_norm.  Only the
+    // lazy route can do that: the eager tail reads whole pairs of rows
+    ORYON_CHECK_ARG((a_hat || (feat_a && a_norm && !force_eager)) && a_i8 && a_scale && feat_q && roi_a && roi_q && q_norm && q_i8 && q_eps_max && n_a && n_q);
+    const AnchorRaw araw = {feat_a, roi_a, a_norm, roi_stride_a};
     ORYON_CHECK_ARG(min_dist && argmin && valid && corrs && n_valid && n_sel && status && !(fmt == 1 && force_eager));
     ORYON_CHECK_ARG(B >= 0 && (C == 256 || C == 512) && C_true > 0 && C_true <= C && HW > 0 && W > 0 && max_corrs > 0 && corr_rows >= max_corrs);
     ORYON_CHECK_ARG(layout == ORYON_LAYOUT_NCHW || layout == ORYON_LAYOUT_NHWC);
@@ -2166,8 +2281,19 @@ static int match_corrs_lazy_impl(const float *a_hat, const int8_t *a_i8, const f
                           wr.eps_scratch, nullptr, wr.q_hat, 1, round_f16, st);
     if (rc) { set_error("oryon_match_corrs_i8: lazy fp32 gather launch failed"); return rc; }
     // (2) ambiguous anchors whose VALIDITY is open: exact fp32 scan (K1) of exactly those rows, before the sampling
-    hipLaunchKernelGGL(match_compact_f32_kernel, dim3(cap_a / 64, B), dim3(256), 0, st, a_hat, C, cap_a, cap_a, lw.n_ambu, lw.ambu_idx, cap_a,
-                       w8.a_hat_c);
+    // (the launch geometry of match_compact_f32_kernel; rows from the raw map where K0 wrote none)
+#define COMPACT_A(GRIDX, CAPC, COUNT, IDX, STRIDE)                                                                             \
+    do {                                                                                                                       \
+        if (a_hat)                                                                                                             \
+            hipLaunchKernelGGL(match_compact_f32_kernel, dim3(GRIDX, B), dim3(256), 0, st, a_hat, C, cap_a, CAPC, COUNT, IDX, STRIDE, w8.a_hat_c); \
+        else if (layout == ORYON_LAYOUT_NHWC)                                                                                  \
+            hipLaunchKernelGGL(match_compact_raw_kernel<true>, dim3(GRIDX, B), dim3(256), 0, st, araw, C_true, HW, round_f16, C, cap_a, CAPC,     \
+                               COUNT, IDX, STRIDE, w8.a_hat_c);                                                                \
+        else                                                                                                                   \
+            hipLaunchKernelGGL(match_compact_raw_kernel<false>, dim3(GRIDX, B), dim3(256), 0, st, araw, C_true, HW, round_f16, C, cap_a, CAPC,    \
+                               COUNT, IDX, STRIDE, w8.a_hat_c);                                                                \
+    } while (0)
+    COMPACT_A(cap_a / 64, cap_a, lw.n_ambu, lw.ambu_idx, cap_a);
     ORYON_CHECK_LAUNCH();
     rc = oryon_match_f32(w8.a_hat_c, wr.q_hat, B, C, cap_a, cap_q, lw.n_ambu, n_q, threshold, w8.md_c, w8.am_c, w8.va_c, lw.exact_ws,
                          lw.exact_ws_bytes, stream);
@@ -2179,7 +2305,7 @@ static int match_corrs_lazy_impl(const float *a_hat, const int8_t *a_i8, const f
     const size_t lds_res = (size_t)4 * 2 * C * sizeof(float);
 #define RESOLVE_U(NHWCV) RESOLVE_U2(NHWCV, 0)
 #define RESOLVE_U2(NHWCV, FMTV)                                                                                                \
-    hipLaunchKernelGGL((match_resolve_uncertain_kernel<NHWCV, FMTV>), dim3(64, B), dim3(256), lds_res, st, a_hat, a_i8, q_i8, q_scale, a_scale,     \
+    hipLaunchKernelGGL((match_resolve_uncertain_kernel<NHWCV, FMTV>), dim3(64, B), dim3(256), lds_res, st, a_hat, araw, a_i8, q_i8, q_scale, a_scale,     \
                        feat_q, C_true, HW, roi_q, roi_stride_q, q_norm, C, cap_a, cap_q, n_q, threshold, w.m_final, lw.sid_final, lw.margin,   \
                        lw.n_unc, lw.unc_idx, lw.pair_eager, lw.state, valid, min_dist, argmin, round_f16)
     if (fmt == 1) { if (layout == ORYON_LAYOUT_NHWC) RESOLVE_U2(true, 1); else RESOLVE_U2(false, 1); }
@@ -2210,8 +2336,8 @@ static int match_corrs_lazy_impl(const float *a_hat, const int8_t *a_i8, const f
                            lw.mark, lw.n_ambv, lw.ambv_idx);
         ORYON_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(match_compact_f32_kernel, dim3((cap_s + 63) / 64, B), dim3(256), 0, st, a_hat, C, cap_a, cap_s, lw.n_ambv, lw.ambv_idx,
-                       corr_rows, w8.a_hat_c);
+    COMPACT_A((cap_s + 63) / 64, cap_s, lw.n_ambv, lw.ambv_idx, corr_rows);
+#undef COMPACT_A
     ORYON_CHECK_LAUNCH();
     if (use_x3) {
         // K1x3: hi / lo half query rows into the (now free) fp32-row area, fp16x3 scan with candidate lists, exact chain on the few
@@ -2244,7 +2370,7 @@ static int match_corrs_lazy_impl(const float *a_hat, const int8_t *a_i8, const f
     // (6) query half of every sampled correspondence: resolved rows read their argmin, the others get it from their winning slice
 #define RESOLVE_S(NHWCV) RESOLVE_S2(NHWCV, 0)
 #define RESOLVE_S2(NHWCV, FMTV)                                                                                                \
-    hipLaunchKernelGGL((match_resolve_selected_kernel<NHWCV, FMTV>), dim3((max_corrs + 3) / 4, B), dim3(256), lds_res, st, a_hat, a_i8, q_i8,       \
+    hipLaunchKernelGGL((match_resolve_selected_kernel<NHWCV, FMTV>), dim3((max_corrs + 3) / 4, B), dim3(256), lds_res, st, a_hat, araw, a_i8, q_i8,       \
                        q_scale, a_scale, feat_q, C_true, HW, roi_q, roi_stride_q, q_norm, C, cap_a, cap_q, n_q, W, w.m_final, lw.sid_final,    \
                        lw.margin, lw.state, lw.pair_eager, n_sel, lw.sel_rows, corr_rows, min_dist, argmin, corrs, round_f16)
     if (fmt == 1) { if (layout == ORYON_LAYOUT_NHWC) RESOLVE_S2(true, 1); else RESOLVE_S2(false, 1); }

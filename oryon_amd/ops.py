@@ -541,6 +541,61 @@ def _match_corrs_i8_locked(a_hat, a8, a_scale, feat_q, C_true, HW, layout, roi_a
     return corrs, n_valid, n_sel, status, min_dist, argmin, valid
 
 
+def _match_corrs_araw(entry: str, feat_a, a_norm, a_rows, a_aux, feat_q, roi_a, roi_q, q_norm, q_rows, q_aux, n_a, n_q, threshold, W, max_corrs,
+                      seed, pair_key, corr_rows, n_undecided, round_f16):
+    """The three `_araw` entries share everything but the operand block between feat_q's geometry and B: a_aux / q_aux are the pointer
+    arguments that follow a_rows / q_rows in the C signature (include/oryon_hip.h)."""
+    dev = _lib.require_gpu(feat_a.device)
+    feat_a, layout_a = map_layout(feat_a)
+    feat_q, layout = map_layout(feat_q)
+    assert layout_a == layout and feat_a.shape[1:] == feat_q.shape[1:], "anchor and query maps share C, H, W and the memory layout"
+    B, cap_a, Cp = a_rows.shape
+    cap_q = q_rows.shape[1]
+    C_true, HW = feat_q.shape[1], feat_q.shape[2] * feat_q.shape[3]
+    corr_rows = int(corr_rows or max_corrs)
+    min_dist = torch.empty((B, cap_a), dtype=torch.float32, device=dev)
+    argmin = torch.empty((B, cap_a), dtype=torch.int32, device=dev)
+    valid = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
+    corrs = torch.zeros((B, corr_rows, 4), dtype=torch.int32, device=dev)
+    n_valid = torch.empty((B,), dtype=torch.int32, device=dev)
+    n_sel = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    wsb = lib().oryon_match_corrs_i8_workspace_bytes(B, Cp, cap_a, cap_q, corr_rows)
+    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
+    check(getattr(lib(), entry)(feat_a.data_ptr(), ptr(a_norm), ptr(a_rows), *[ptr(t) for t in a_aux], feat_q.data_ptr(), C_true, HW, layout,
+                                ptr(roi_a), roi_a.shape[1], ptr(roi_q), roi_q.shape[1], ptr(q_norm), ptr(q_rows), *[ptr(t) for t in q_aux],
+                                B, Cp, cap_a, cap_q, ptr(n_a), ptr(n_q), float(threshold), int(W), int(max_corrs), corr_rows,
+                                int(seed) & (2**64 - 1), ptr(pair_key), ptr(min_dist), ptr(argmin), ptr(valid), ptr(corrs), ptr(n_valid),
+                                ptr(n_sel), ptr(status), ptr(n_undecided), int(bool(round_f16)), ptr(ws), ws.numel(), stream_ptr(dev)), entry)
+    return corrs, n_valid, n_sel, status, min_dist, argmin, valid
+
+
+@_on_tensor_device
+def match_corrs_i8_araw(feat_a, a_norm, a8, a_scale, feat_q, roi_a, roi_q, q_norm, q8, q_scale, q_eps, n_a, n_q, threshold: float, W: int,
+                        max_corrs: int, seed: int, pair_key=None, corr_rows: Optional[int] = None, n_undecided=None, round_f16: bool = False):
+    """oryon_match_corrs_i8_araw: match_corrs_i8 (lazy route) without materialised fp32 anchor rows - the raw anchor map and K0's anchor
+    norms instead of a_hat; same outputs, bit for bit."""
+    return _match_corrs_araw("oryon_match_corrs_i8_araw", feat_a, a_norm, a8, (a_scale,), feat_q, roi_a, roi_q, q_norm, q8, (q_scale, q_eps),
+                             n_a, n_q, threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16)
+
+
+@_on_tensor_device
+def match_corrs_mx6_araw(feat_a, a_norm, a6, a_err, feat_q, roi_a, roi_q, q_norm, q6, q_err, n_a, n_q, threshold: float, W: int, max_corrs: int,
+                         seed: int, pair_key=None, corr_rows: Optional[int] = None, n_undecided=None, round_f16: bool = False):
+    """oryon_match_corrs_mx6_araw: match_corrs_mx6 without materialised fp32 anchor rows; same outputs, bit for bit."""
+    return _match_corrs_araw("oryon_match_corrs_mx6_araw", feat_a, a_norm, a6, (a_err,), feat_q, roi_a, roi_q, q_norm, q6, (q_err,), n_a, n_q,
+                             threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16)
+
+
+@_on_tensor_device
+def match_corrs_mx6_x3_araw(feat_a, a_norm, a6, a_err, feat_q, roi_a, roi_q, q_norm, q6, q_err, q_hi_lo, q_lo_max, n_a, n_q, threshold: float,
+                            W: int, max_corrs: int, seed: int, pair_key=None, corr_rows: Optional[int] = None, n_undecided=None,
+                            round_f16: bool = False):
+    """oryon_match_corrs_mx6_x3_araw: the matcher on K0's hi / lo query rows (oryon_gather_mx6_x3) without materialised fp32 anchor rows."""
+    return _match_corrs_araw("oryon_match_corrs_mx6_x3_araw", feat_a, a_norm, a6, (a_err,), feat_q, roi_a, roi_q, q_norm, q6,
+                             (q_err, q_hi_lo, q_lo_max), n_a, n_q, threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16)
+
+
 @_on_tensor_device
 def match_screened8(a_hat, q_hat, a8, q8, a_scale, q_scale, q_eps, n_a, n_q, threshold: float, c_true: int, n_undecided=None):
     """int8 pre-screen + fp16 screen + exact fp32 re-scoring (K1s8).  Same outputs as `match_screened`.
