@@ -19,6 +19,7 @@
 #include <new>
 #include <vector>
 #include "common.h"
+#include "match_common.h"
 
 using namespace oryon;
 
@@ -615,26 +616,60 @@ extern "C" int oryon_engine_submit(oryon_engine_t *e, const float *feat_a, const
     // one matcher call (the engine's screen setting) on the given anchor operands
     auto match_call = [&](const float *a_norm_, const int8_t *a8_, const float *a_sc_, const float *a_eps_, const int32_t *roi_a_, int cap_a_,
                           const int32_t *n_a_, int32_t *corrs_, int32_t *n_valid_, int32_t *n_sel_, int32_t *status_, int32_t *n_und_) -> int {
-        if (mx6 && x3_pre)
-            return oryon_match_corrs_mx6_x3(g.a_hat, reinterpret_cast<const uint8_t *>(a8_), a_eps_, feat_q, c.C, HW, c.layout, roi_a_, HW, b.roi_q, HW,
-                                            g.q_norm, reinterpret_cast<const uint8_t *>(g.q8), g.q_eps, g.q_hilo, g.q_lo_max, B, e->L.c_pad, cap_a_,
-                                            e->L.cap_q, n_a_, b.n_q, c.dist_th, c.FW, c.n_corrs, e->L.n_cap, c.seed, pair_key, b.min_dist, b.argmin,
-                                            b.valid, corrs_, n_valid_, n_sel_, status_, n_und_, c.round_f16, e->L.match_ws, e->L.match_ws_bytes, sm);
-        if (mx6)
-            return oryon_match_corrs_mx6_araw(feat_a, a_norm_, reinterpret_cast<const uint8_t *>(a8_), a_eps_, feat_q, c.C, HW, c.layout, roi_a_, HW,
-                                              b.roi_q, HW, g.q_norm, reinterpret_cast<const uint8_t *>(g.q8), g.q_eps, B, e->L.c_pad, cap_a_, e->L.cap_q,
-                                              n_a_, b.n_q, c.dist_th, c.FW, c.n_corrs, e->L.n_cap, c.seed, pair_key, b.min_dist, b.argmin, b.valid,
-                                              corrs_, n_valid_, n_sel_, status_, n_und_, c.round_f16, e->L.match_ws, e->L.match_ws_bytes, sm);
-        if (!force_eager)
-            return oryon_match_corrs_i8_araw(feat_a, a_norm_, a8_, a_sc_, feat_q, c.C, HW, c.layout, roi_a_, HW, b.roi_q, HW, g.q_norm, g.q8, g.q_sc,
-                                             g.q_eps, B, e->L.c_pad, cap_a_, e->L.cap_q, n_a_, b.n_q, c.dist_th, c.FW, c.n_corrs, e->L.n_cap, c.seed,
-                                             pair_key, b.min_dist, b.argmin, b.valid, corrs_, n_valid_, n_sel_, status_, n_und_, c.round_f16,
-                                             e->L.match_ws, e->L.match_ws_bytes, sm);
-        // force_eager: complete min_dist / argmin arrays from whole fp32 rows (K0 wrote g.a_hat on this step; never with sample_first)
-        return oryon_match_corrs_i8(g.a_hat, a8_, a_sc_, feat_q, c.C, HW, c.layout, roi_a_, HW, b.roi_q, HW, g.q_norm, g.q8, g.q_sc, g.q_eps, B,
-                                    e->L.c_pad, cap_a_, e->L.cap_q, n_a_, b.n_q, c.dist_th, c.FW, c.n_corrs, e->L.n_cap, c.seed, pair_key, force_eager,
-                                    b.min_dist, b.argmin, b.valid, corrs_, n_valid_, n_sel_, status_, n_und_, c.round_f16, e->L.match_ws,
-                                    e->L.match_ws_bytes, sm);
+        MatchCorrsArgs m;
+        m.a_i8 = a8_;
+        m.a_scale = mx6 ? a_eps_ : a_sc_;
+        m.roi_a = roi_a_;
+        m.roi_stride_a = HW;
+        m.feat_q = feat_q;
+        m.q_norm = g.q_norm;
+        m.roi_q = b.roi_q;
+        m.roi_stride_q = HW;
+        m.q_i8 = g.q8;
+        m.q_scale = mx6 ? nullptr : g.q_sc;
+        m.q_eps_max = g.q_eps;
+        m.C_true = c.C;
+        m.HW = HW;
+        m.layout = c.layout;
+        m.B = B;
+        m.C = e->L.c_pad;
+        m.cap_a = cap_a_;
+        m.cap_q = e->L.cap_q;
+        m.round_f16 = c.round_f16;
+        m.n_a = n_a_;
+        m.n_q = b.n_q;
+        m.threshold = c.dist_th;
+        m.W = c.FW;
+        m.max_corrs = c.n_corrs;
+        m.corr_rows = e->L.n_cap;
+        m.seed = c.seed;
+        m.pair_key = pair_key;
+        m.min_dist = b.min_dist;
+        m.argmin = b.argmin;
+        m.valid = b.valid;
+        m.corrs = corrs_;
+        m.n_valid = n_valid_;
+        m.n_sel = n_sel_;
+        m.status = status_;
+        m.n_undecided = n_und_;
+        m.workspace = e->L.match_ws;
+        m.workspace_bytes = e->L.match_ws_bytes;
+        m.stream = sm;
+        m.fmt = mx6 ? 1 : 0;
+        if (mx6 && x3_pre) {
+            // hard route: K0 wrote g.a_hat and the hi / lo query rows on this step (see x3_pre above)
+            m.a_hat = g.a_hat;
+            m.q_hi_lo = g.q_hilo;
+            m.q_lo_sq_max = g.q_lo_max;
+        } else if (force_eager) {
+            // force_eager: complete min_dist / argmin arrays from whole fp32 rows (K0 wrote g.a_hat on this step; never with sample_first)
+            m.a_hat = g.a_hat;
+            m.force_eager = force_eager;
+        } else {
+            m.feat_a = feat_a;
+            m.a_norm = a_norm_;
+        }
+        return match_corrs_lazy_impl(m);
     };
     if (ablate & 2) {
     } else if (sf) {

@@ -33,7 +33,6 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 constexpr float SCREEN_DELTA = 1.05e-3f;
 constexpr float SCREEN_MARGIN = 2.2e-3f;
 constexpr int SCREEN_CAP = 64;          // candidate slots per anchor
-constexpr int MT16 = 256;               // anchors per workgroup (4 waves x 2 blocks of 32)
 constexpr int screen_tile_bytes(int CP) { return CP == 512 ? 65536 : 32768; }
 
 // Out-of-line candidate append (pass 1 slow path, taken by a few % of the tiles): keeping it out of the kernel body
@@ -1012,7 +1011,7 @@ __global__ __launch_bounds__(256) void match_scatter8_kernel(int cap_a, const in
     valid[dst] = va_c[src];
 }
 
-static int pick_split16(int B, int T)
+int pick_split16(int B, int T)
 {
     static const int target = dev_env_int("ORYON_SCREEN_WGS", 8192);     // timing experiments only
     int S = (target + B * T - 1) / (B * T);
@@ -1021,48 +1020,51 @@ static int pick_split16(int B, int T)
     return S;
 }
 
-struct ScreenWs {
-    float *ws_max, *ws_m2, *m_final, *amb_max;
-    int32_t *ws_i1, *cnt, *cand, *panel_flag, *n_amb, *amb_idx;
-    __half *a16c;
-    uint8_t *row_flag;
-    size_t bytes, zero_off, zero_bytes;
-};
-
-static ScreenWs carve_screen(void *base, int B, int C, int cap_a, int S)
+static size_t carve_screen(void *base, ScreenWs &w, int B, int C, int cap_a, int S)
 {
-    ScreenWs w;
-    char *p = static_cast<char *>(base);
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off = (off + n + 255) / 256 * 256; return o; };
-    const size_t o_max = take((size_t)B * S * cap_a * sizeof(float));
-    const size_t o_m2 = take((size_t)B * S * cap_a * sizeof(float));
-    const size_t o_i1 = take((size_t)B * S * cap_a * sizeof(int32_t));
-    const size_t o_mf = take((size_t)B * cap_a * sizeof(float));
-    const size_t o_am = take((size_t)B * cap_a * sizeof(float));
-    const size_t o_ai = take((size_t)B * cap_a * sizeof(int32_t));
-    const size_t o_a16 = take((size_t)B * cap_a * C * sizeof(__half));
-    const size_t o_cand = take((size_t)B * cap_a * SCREEN_CAP * sizeof(int32_t));
-    w.zero_off = off;
-    const size_t o_cnt = take((size_t)B * cap_a * sizeof(int32_t));
-    const size_t o_rf = take((size_t)B * cap_a);
-    const size_t o_pf = take((size_t)B * (cap_a / ORYON_MATCH_TILE) * sizeof(int32_t));
-    const size_t o_na = take((size_t)B * sizeof(int32_t));
-    w.zero_bytes = off - w.zero_off;
-    w.bytes = off;
-    w.ws_m2 = base ? reinterpret_cast<float *>(p + o_m2) : nullptr;
-    w.ws_i1 = base ? reinterpret_cast<int32_t *>(p + o_i1) : nullptr;
-    w.m_final = base ? reinterpret_cast<float *>(p + o_mf) : nullptr;
-    w.amb_max = base ? reinterpret_cast<float *>(p + o_am) : nullptr;
-    w.amb_idx = base ? reinterpret_cast<int32_t *>(p + o_ai) : nullptr;
-    w.a16c = base ? reinterpret_cast<__half *>(p + o_a16) : nullptr;
-    w.n_amb = base ? reinterpret_cast<int32_t *>(p + o_na) : nullptr;
-    w.ws_max = base ? reinterpret_cast<float *>(p + o_max) : nullptr;
-    w.cand = base ? reinterpret_cast<int32_t *>(p + o_cand) : nullptr;
-    w.cnt = base ? reinterpret_cast<int32_t *>(p + o_cnt) : nullptr;
-    w.row_flag = base ? reinterpret_cast<uint8_t *>(p + o_rf) : nullptr;
-    w.panel_flag = base ? reinterpret_cast<int32_t *>(p + o_pf) : nullptr;
-    return w;
+    Carver carve(base);
+    const size_t rows = (size_t)B * cap_a;
+    carve(w.ws_max, rows * S);
+    carve(w.ws_m2, rows * S);
+    carve(w.ws_i1, rows * S);
+    carve(w.m_final, rows);
+    carve(w.amb_max, rows);
+    carve(w.amb_idx, rows);
+    carve(w.a16c, rows * C);
+    carve(w.cand, rows * SCREEN_CAP);
+    w.zero_off = carve.off;
+    carve(w.cnt, rows);
+    carve(w.row_flag, rows);
+    carve(w.panel_flag, (size_t)B * (cap_a / ORYON_MATCH_TILE));
+    carve(w.n_amb, (size_t)B);
+    w.zero_bytes = carve.off - w.zero_off;
+    return carve.off;
+}
+
+static size_t carve_screen8(void *base, Screen8Ws &w, int B, int C, int cap_a, int cap_q, int S)
+{
+    Carver carve(base, carve_screen(base, w, B, C, cap_a, S));
+    const size_t rows = (size_t)B * cap_a;
+    carve(w.q16, (size_t)B * cap_q * C);
+    carve(w.a_hat_c, rows * C);
+    carve(w.md_c, rows);
+    carve(w.am_c, rows);
+    carve(w.va_c, rows);
+    ScreenWs inner;                                                 // the nested K1s call carves this region itself
+    w.nested_bytes = carve_screen(nullptr, inner, B, C, cap_a, S);
+    carve(w.nested, w.nested_bytes);
+    return carve.off;
+}
+
+size_t carve_screen8_raw(void *base, Screen8RawWs &w, int B, int C, int cap_a, int cap_q, int S)
+{
+    Carver carve(base, carve_screen8(base, w, B, C, cap_a, cap_q, S));
+    carve(w.q_hat, (size_t)B * cap_q * C);
+    carve(w.q8_scratch, (size_t)B * cap_q * C);                     // the fall-back pass rewrites the same int8 rows here
+    carve(w.scale_scratch, (size_t)B * (cap_q / 16));
+    carve(w.eps_scratch, (size_t)B);
+    carve(w.need_f32, (size_t)B);
+    return carve.off;
 }
 
 }  // namespace oryon
@@ -1072,20 +1074,43 @@ using namespace oryon;
 extern "C" size_t oryon_match_screened_workspace_bytes(int B, int C, int cap_a)
 {
     if (B <= 0 || C <= 0 || cap_a <= 0 || cap_a % MT16) return 0;
-    return carve_screen(nullptr, B, C, cap_a, pick_split16(B, cap_a / MT16)).bytes;
+    ScreenWs w;
+    return carve_screen(nullptr, w, B, C, cap_a, pick_split16(B, cap_a / MT16));
 }
 
 namespace {
+struct Screen16Args {       // the arguments of match_f16_screen_kernel
+    const __half *a16, *q16;
+    int B, cap_a, cap_q;
+    const int32_t *n_a, *n_q;
+    int T, S;
+    float valid_cut;
+    float *ws_max;
+    int32_t *cnt, *cand;
+    int S_thr;
+    const int32_t *row_map;
+    int32_t *ws_i1;
+    float *ws_m2;
+};
+
 // one launcher per descriptor width; C = 512 needs 2 x 64 KB of dynamic LDS (opt-in above 64 KB)
-template <int CP, int MODE>
-void launch_screen(int groups, hipStream_t st, const __half *a16, const __half *q16, int B, int cap_a, int cap_q, const int32_t *n_a,
-                   const int32_t *n_q, int T, int S, float valid_cut, float *ws_max, int32_t *cnt, int32_t *cand, int S_thr,
-                   const int32_t *row_map, int32_t *ws_i1, float *ws_m2)
+template <int CP, int MODE, int VAR = 0>
+void launch_screen(int groups, hipStream_t st, const Screen16Args &k)
 {
     constexpr size_t dyn = 2 * screen_tile_bytes(CP) > 65536 ? 2 * screen_tile_bytes(CP) : 0;
-    if (dyn) allow_dynamic_lds(reinterpret_cast<const void *>(&match_f16_screen_kernel<CP, MODE, 0>), (int)dyn);
-    hipLaunchKernelGGL((match_f16_screen_kernel<CP, MODE, 0>), dim3(groups), dim3(256), dyn, st, a16, q16, B, cap_a, cap_q, n_a, n_q, T,
-                       S, valid_cut, ws_max, cnt, cand, S_thr, row_map, ws_i1, ws_m2);
+    if (dyn) allow_dynamic_lds(reinterpret_cast<const void *>(&match_f16_screen_kernel<CP, MODE, VAR>), (int)dyn);
+    hipLaunchKernelGGL((match_f16_screen_kernel<CP, MODE, VAR>), dim3(groups), dim3(256), dyn, st, k.a16, k.q16, k.B, k.cap_a, k.cap_q, k.n_a,
+                       k.n_q, k.T, k.S, k.valid_cut, k.ws_max, k.cnt, k.cand, k.S_thr, k.row_map, k.ws_i1, k.ws_m2);
+}
+
+using Screen16Fn = void (*)(int, hipStream_t, const Screen16Args &);
+
+void launch_screen16(int C, int mode, int groups, hipStream_t st, const Screen16Args &k)
+{
+    static const Screen16Fn by_width[3][3] = {{launch_screen<128, 0>, launch_screen<128, 1>, launch_screen<128, 2>},
+                                              {launch_screen<256, 0>, launch_screen<256, 1>, launch_screen<256, 2>},
+                                              {launch_screen<512, 0>, launch_screen<512, 1>, launch_screen<512, 2>}};
+    by_width[C == 128 ? 0 : C == 256 ? 1 : 2][mode](groups, st, k);
 }
 }  // namespace
 
@@ -1099,9 +1124,10 @@ extern "C" int oryon_match_screened(const float *a_hat, const float *q_hat, cons
     if (B == 0) return ORYON_OK;
     const int T = cap_a / MT16;
     const int S = pick_split16(B, T);
-    ScreenWs w = carve_screen(workspace, B, C, cap_a, S);
-    if (!workspace || workspace_bytes < w.bytes) {
-        set_error("oryon_match_screened: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
+    ScreenWs w;
+    const size_t need = carve_screen(workspace, w, B, C, cap_a, S);
+    if (!workspace || workspace_bytes < need) {
+        set_error("oryon_match_screened: workspace too small (%zu < %zu)", workspace_bytes, need);
         return ORYON_ERR_WORKSPACE;
     }
     hipStream_t st = as_stream(stream);
@@ -1110,48 +1136,61 @@ extern "C" int oryon_match_screened(const float *a_hat, const float *q_hat, cons
     const float valid_cut = (1.0f - 2.0f * threshold) - SCREEN_DELTA - 1e-6f;
     const int groups = ((B * S + 7) / 8) * 8 * T;
     const __half *a16 = static_cast<const __half *>(a_f16), *q16 = static_cast<const __half *>(q_f16);
-#define LAUNCH16(CPV, MODEV)                                                                                              \
-    launch_screen<CPV, MODEV>(groups, st, a16, q16, B, cap_a, cap_q, n_a, n_q, T, S, valid_cut, w.ws_max, w.cnt, w.cand, S, nullptr,   \
-                              w.ws_i1, w.ws_m2)
-#define LAUNCH16_AMB(CPV)                                                                                                 \
-    launch_screen<CPV, 1>(groups, st, w.a16c, q16, B, cap_a, cap_q, w.n_amb, n_q, T, S, valid_cut, w.amb_max, w.cnt, w.cand, 1,        \
-                          w.amb_idx, nullptr, nullptr)
+    Screen16Args all;           // the pass over all anchors
+    all.a16 = a16;
+    all.q16 = q16;
+    all.B = B;
+    all.cap_a = cap_a;
+    all.cap_q = cap_q;
+    all.n_a = n_a;
+    all.n_q = n_q;
+    all.T = T;
+    all.S = S;
+    all.valid_cut = valid_cut;
+    all.ws_max = w.ws_max;
+    all.cnt = w.cnt;
+    all.cand = w.cand;
+    all.S_thr = S;
+    all.row_map = nullptr;
+    all.ws_i1 = w.ws_i1;
+    all.ws_m2 = w.ws_m2;
     static const int var16 = dev_env_int("ORYON_MATCH16_VARIANT", 0);
     static const bool two_pass = dev_env_set("ORYON_SCREEN_TWOPASS");
     const float *m_final = nullptr;
-    if (two_pass || var16) {
-#define LAUNCH16V(V) hipLaunchKernelGGL((match_f16_screen_kernel<256, 0, V>), dim3(groups), dim3(256), 0, st, a16, q16, B, cap_a, cap_q, n_a, n_q, T, S, valid_cut, w.ws_max, w.cnt, w.cand, S, nullptr, w.ws_i1, w.ws_m2)
-        if (C == 256 && var16 == 8) {
-            LAUNCH16(256, 0);
-            hipLaunchKernelGGL((match_f16_screen_kernel<256, 1, 8>), dim3(groups), dim3(256), 0, st, a16, q16, B, cap_a, cap_q, n_a, n_q, T, S, valid_cut, w.ws_max, w.cnt, w.cand, S, nullptr, w.ws_i1, w.ws_m2);
-        } else if (C == 256 && var16) {
-            switch (var16) { case 1: LAUNCH16V(1); break; case 2: LAUNCH16V(2); break; case 3: LAUNCH16V(3); break; case 4: LAUNCH16V(4); break;
-                             case 5: LAUNCH16V(5); break; case 6: LAUNCH16V(6); break; default: LAUNCH16V(7); break; }
-            LAUNCH16(256, 1);
-        } else if (C == 256) { LAUNCH16(256, 0); LAUNCH16(256, 1); }
-        else if (C == 512) { LAUNCH16(512, 0); LAUNCH16(512, 1); }
-        else { LAUNCH16(128, 0); LAUNCH16(128, 1); }
-#undef LAUNCH16V
+    if (C == 256 && var16 == 8) {
+        launch_screen<256, 0>(groups, st, all);
+        launch_screen<256, 1, 8>(groups, st, all);
+    } else if (C == 256 && var16) {
+        static const Screen16Fn variant[7] = {launch_screen<256, 0, 1>, launch_screen<256, 0, 2>, launch_screen<256, 0, 3>, launch_screen<256, 0, 4>,
+                                              launch_screen<256, 0, 5>, launch_screen<256, 0, 6>, launch_screen<256, 0, 7>};
+        variant[(var16 >= 1 && var16 <= 6 ? var16 : 7) - 1](groups, st, all);
+        launch_screen<256, 1>(groups, st, all);
+    } else if (two_pass || var16) {
+        launch_screen16(C, 0, groups, st, all);
+        launch_screen16(C, 1, groups, st, all);
     } else {
         // single screening pass keeping (max, argmax, second max) per anchor; anchors whose runner-up is within MARGIN of the
         // maximum (duplicates, smooth descriptor fields) go through a second, compacted candidate pass
         profile_begin(st, C == 256 ? "match_f16_screen_kernel<256, 2>" : C == 512 ? "match_f16_screen_kernel<512, 2>" : "match_f16_screen_kernel<128, 2>");
-        if (C == 256) LAUNCH16(256, 2); else if (C == 512) LAUNCH16(512, 2); else LAUNCH16(128, 2);
+        launch_screen16(C, 2, groups, st, all);
         profile_end(st);
         ORYON_CHECK_LAUNCH();
-        if (C >= 256)
-            hipLaunchKernelGGL((match_decide_kernel<64>), dim3(cap_a / 64, B), dim3(256), 0, st, a16, q16, C, cap_a, cap_q, n_a, n_q, S,
-                               valid_cut, w.ws_max, w.ws_i1, w.ws_m2, w.m_final, w.cnt, w.cand, w.n_amb, w.amb_idx, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr);
-        else
-            hipLaunchKernelGGL((match_decide_kernel<128>), dim3(cap_a / 64, B), dim3(256), 0, st, a16, q16, C, cap_a, cap_q, n_a, n_q, S,
-                               valid_cut, w.ws_max, w.ws_i1, w.ws_m2, w.m_final, w.cnt, w.cand, w.n_amb, w.amb_idx, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr);
+        hipLaunchKernelGGL(C >= 256 ? match_decide_kernel<64> : match_decide_kernel<128>, dim3(cap_a / 64, B), dim3(256), 0, st, a16, q16, C,
+                           cap_a, cap_q, n_a, n_q, S, valid_cut, w.ws_max, w.ws_i1, w.ws_m2, w.m_final, w.cnt, w.cand, w.n_amb, w.amb_idx,
+                           nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr);
         hipLaunchKernelGGL(match_compact_kernel, dim3(cap_a / 64, B), dim3(256), 0, st, a16, C, cap_a, w.n_amb, w.amb_idx, w.m_final,
                            w.a16c, w.amb_max);
-        if (C == 256) LAUNCH16_AMB(256); else if (C == 512) LAUNCH16_AMB(512); else LAUNCH16_AMB(128);
+        Screen16Args amb = all;     // the candidate pass over the compacted ambiguous anchors
+        amb.a16 = w.a16c;
+        amb.n_a = w.n_amb;
+        amb.ws_max = w.amb_max;
+        amb.S_thr = 1;
+        amb.row_map = w.amb_idx;
+        amb.ws_i1 = nullptr;
+        amb.ws_m2 = nullptr;
+        launch_screen16(C, 1, groups, st, amb);
         m_final = w.m_final;
     }
-#undef LAUNCH16
-#undef LAUNCH16_AMB
     ORYON_CHECK_LAUNCH();
     // 4 lanes per anchor: 16 -> 394 us, 8 -> 230, 4 -> 184, 2 -> 175, 1 -> 200 us at cfg2 (almost every anchor has one candidate)
     hipLaunchKernelGGL((match_rescore_kernel<4>), dim3(cap_a / 64, B), dim3(256), 0, st, a_hat, q_hat, C, cap_a, cap_q, n_a, n_q, S,
@@ -1163,45 +1202,10 @@ extern "C" int oryon_match_screened(const float *a_hat, const float *q_hat, cons
 }
 
 
-// ------------------------------------------------------------------------------------------------ K1s8 entry points
+// ------------------------------------------------------------------------------------------------ K1s8: host steps and entry points
 namespace {
-struct Screen8Ws {
-    ScreenWs top;
-    __half *q16;
-    float *a_hat_c, *md_c;
-    int32_t *am_c;
-    uint8_t *va_c;
-    void *nested;
-    size_t nested_bytes, bytes;
-};
-
-Screen8Ws carve_screen8(void *base, int B, int C, int cap_a, int cap_q, int S)
-{
-    Screen8Ws w;
-    w.top = carve_screen(base, B, C, cap_a, S);
-    char *p = static_cast<char *>(base);
-    size_t off = (w.top.bytes + 255) / 256 * 256;
-    auto take = [&](size_t n) { size_t o = off; off = (off + n + 255) / 256 * 256; return o; };
-    const size_t o_q16 = take((size_t)B * cap_q * C * sizeof(__half));
-    const size_t o_ah = take((size_t)B * cap_a * C * sizeof(float));
-    const size_t o_md = take((size_t)B * cap_a * sizeof(float));
-    const size_t o_am = take((size_t)B * cap_a * sizeof(int32_t));
-    const size_t o_va = take((size_t)B * cap_a);
-    w.nested_bytes = carve_screen(nullptr, B, C, cap_a, S).bytes;
-    const size_t o_ne = take(w.nested_bytes);
-    w.bytes = off;
-    w.q16 = base ? reinterpret_cast<__half *>(p + o_q16) : nullptr;
-    w.a_hat_c = base ? reinterpret_cast<float *>(p + o_ah) : nullptr;
-    w.md_c = base ? reinterpret_cast<float *>(p + o_md) : nullptr;
-    w.am_c = base ? reinterpret_cast<int32_t *>(p + o_am) : nullptr;
-    w.va_c = base ? reinterpret_cast<uint8_t *>(p + o_va) : nullptr;
-    w.nested = base ? static_cast<void *>(p + o_ne) : nullptr;
-    return w;
-}
-
 // the kernel launch_screen8<CP> dispatches under the current development switches (for oryon_dominant_kernel)
-template <int CP>
-const char *screen8_name()
+const char *screen8_name(int CP)
 {
     const int variant = dev_env_int("ORYON_SCREEN8_VARIANT", 2);
     const int ablate = dev_env_int("ORYON_SCREEN8_ABLATE", 0);
@@ -1217,38 +1221,101 @@ void launch_screen8(int groups, hipStream_t st, const int8_t *a8, const int8_t *
                     const int32_t *n_a, const int32_t *n_q, int T, int S, float *ws_max, int32_t *ws_i1, float *ws_m2)
 {
     constexpr size_t dyn = 2 * screen8_tile_bytes(CP) > 65536 ? 2 * screen8_tile_bytes(CP) : 0;
+    auto launch = [&](auto kernel, int grid, int block, size_t lds, int tiles) {
+        if (lds) allow_dynamic_lds(reinterpret_cast<const void *>(kernel), (int)lds);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, st, a8, q8, q_scale, B, cap_a, cap_q, n_a, n_q, tiles, S, ws_max, ws_i1,
+                           ws_m2);
+    };
     static const int variant = dev_env_int("ORYON_SCREEN8_VARIANT", 2);
-    if (variant == 1) {                 // round-1 loop (kept for A/B timing)
-        if (dyn) allow_dynamic_lds(reinterpret_cast<const void *>(&match_i8_screen_kernel<CP>), (int)dyn);
-        hipLaunchKernelGGL((match_i8_screen_kernel<CP>), dim3(groups), dim3(256), dyn, st, a8, q8, q_scale, B, cap_a, cap_q, n_a, n_q, T, S,
-                           ws_max, ws_i1, ws_m2);
-        return;
-    }
+    if (variant == 1) return launch(match_i8_screen_kernel<CP>, groups, 256, dyn, T);                 // round-1 loop (kept for A/B timing)
     static const int ablate = dev_env_int("ORYON_SCREEN8_ABLATE", 0);
     if (ablate && CP == 256) {
-#define ABL(V) case V: hipLaunchKernelGGL((match_i8_screen_v2_kernel<256, V>), dim3(groups), dim3(256), 0, st, a8, q8, q_scale, B, cap_a, cap_q, n_a, n_q, T, S, ws_max, ws_i1, ws_m2); break
-        switch (ablate) { ABL(1); ABL(2); ABL(3); default: ABL(8); }
-#undef ABL
-        return;
+        switch (ablate) {
+        case 1: return launch(match_i8_screen_v2_kernel<256, 1>, groups, 256, 0, T);
+        case 2: return launch(match_i8_screen_v2_kernel<256, 2>, groups, 256, 0, T);
+        case 3: return launch(match_i8_screen_v2_kernel<256, 3>, groups, 256, 0, T);
+        default: return launch(match_i8_screen_v2_kernel<256, 8>, groups, 256, 0, T);
+        }
     }
     static const int waves = dev_env_int("ORYON_SCREEN8_WAVES", 8);
     if (waves == 8 && CP == 256) {
         const int T8 = (cap_a + 511) / 512;
-        hipLaunchKernelGGL((match_i8_screen_v2_kernel<256, 0, 8>), dim3(groups / T * T8), dim3(512), 0, st, a8, q8, q_scale, B, cap_a, cap_q, n_a,
-                           n_q, T8, S, ws_max, ws_i1, ws_m2);
-        return;
+        return launch(match_i8_screen_v2_kernel<256, 0, 8>, groups / T * T8, 512, 0, T8);
     }
-    if (dyn) allow_dynamic_lds(reinterpret_cast<const void *>(&match_i8_screen_v2_kernel<CP>), (int)dyn);
-    hipLaunchKernelGGL((match_i8_screen_v2_kernel<CP>), dim3(groups), dim3(256), dyn, st, a8, q8, q_scale, B, cap_a, cap_q, n_a, n_q, T, S,
-                       ws_max, ws_i1, ws_m2);
+    launch(match_i8_screen_v2_kernel<CP>, groups, 256, dyn, T);
 }
 }  // namespace
 
+namespace oryon {
+void screen8_step(const Screen8Args &m, int S, const int32_t *n_a, const ScreenWs &w)
+{
+    hipStream_t st = as_stream(m.stream);
+    const int T = m.cap_a / MT16, groups = ((m.B * S + 7) / 8) * 8 * T;
+    profile_begin(st, screen8_name(m.C));
+    (m.C == 256 ? launch_screen8<256> : launch_screen8<512>)(groups, st, m.a_i8, m.q_i8, m.q_scale, m.B, m.cap_a, m.cap_q, n_a, m.n_q, T, S,
+                                                             w.ws_max, w.ws_i1, w.ws_m2);
+    profile_end(st);
+}
+
+void decide8_step(const Screen8Args &m, int S, const int32_t *n_a, const ScreenWs &w)
+{
+    const float cut0 = 1.0f - 2.0f * m.threshold;
+    const float valid_cut16 = cut0 - SCREEN_DELTA - 1e-6f;
+    hipLaunchKernelGGL((match_decide_kernel<128>), dim3(m.cap_a / 64, m.B), dim3(256), 0, as_stream(m.stream),
+                       static_cast<const __half *>(nullptr), static_cast<const __half *>(nullptr), m.C, m.cap_a, m.cap_q, n_a, m.n_q, S,
+                       valid_cut16, w.ws_max, w.ws_i1, w.ws_m2, w.m_final, w.cnt, w.cand, w.n_amb, w.amb_idx, m.a_scale, nullptr, m.q_eps_max,
+                       cut0, sqrtf((float)m.C_true), (float)m.C_true, m.a_i8, m.q_i8, m.q_scale);
+}
+
+void rescore_raw_step(const Screen8Args &m, const int32_t *n_a, int rescore_lanes, const Screen8RawWs &w)
+{
+    const bool nhwc = m.layout == ORYON_LAYOUT_NHWC;
+    const int lanes = (rescore_lanes == 1 || rescore_lanes == 4) ? rescore_lanes : 2;
+    auto rescore = lanes == 1   ? (nhwc ? match_rescore_raw_kernel<1, true> : match_rescore_raw_kernel<1, false>)
+                   : lanes == 4 ? (nhwc ? match_rescore_raw_kernel<4, true> : match_rescore_raw_kernel<4, false>)
+                                : (nhwc ? match_rescore_raw_kernel<2, true> : match_rescore_raw_kernel<2, false>);
+    hipLaunchKernelGGL(rescore, dim3(m.cap_a / (256 / lanes), m.B), dim3(256), 0, as_stream(m.stream), m.a_hat, m.feat_q, m.C_true, m.HW,
+                       m.roi_q, m.roi_stride_q, m.q_norm, m.C, m.cap_a, m.cap_q, n_a, m.n_q, m.threshold, w.m_final, w.cnt, w.cand,
+                       m.min_dist, m.argmin, m.valid, w.row_flag, w.panel_flag, w.need_f32, m.round_f16);
+}
+
+int screen16_fallback(const Screen8Args &m, const float *q_hat, const Screen8Ws &w, const char *who)
+{
+    hipStream_t st = as_stream(m.stream);
+    hipLaunchKernelGGL(match_compact8_kernel, dim3(m.cap_a / 64, m.B), dim3(256), 0, st, m.a_hat, static_cast<const __half *>(nullptr), m.C,
+                       m.cap_a, w.n_amb, w.amb_idx, w.a_hat_c, w.a16c);
+    hipLaunchKernelGGL(match_make_q16_kernel, dim3(64, m.B), dim3(256), 0, st, q_hat, m.C, m.cap_q, m.n_q, w.n_amb, w.q16);
+    int rc = check_launch(who);
+    if (rc) return rc;
+    rc = oryon_match_screened(w.a_hat_c, q_hat, w.a16c, w.q16, m.B, m.C, m.cap_a, m.cap_q, w.n_amb, m.n_q, m.threshold, w.md_c,
+                              w.am_c, w.va_c, w.nested, w.nested_bytes, m.stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(match_scatter8_kernel, dim3(m.cap_a / 256, m.B), dim3(256), 0, st, m.cap_a, w.n_amb, w.amb_idx, w.md_c, w.am_c,
+                       w.va_c, m.min_dist, m.argmin, m.valid);
+    return check_launch(who);
+}
+
+// Both rare, both gated per pair on the device: pairs with undecided anchors or an overflowed candidate list get their canonical fp32
+// query rows materialised now - the price round 1 paid for EVERY pair - and then take the round-1 route.
+int raw_fallbacks(const Screen8Args &m, const int32_t *n_a, const Screen8RawWs &w, const char *who, const char *entry)
+{
+    hipStream_t st = as_stream(m.stream);
+    hipLaunchKernelGGL(match_need_f32_kernel, dim3((m.B + 255) / 256), dim3(256), 0, st, m.B, w.n_amb, w.need_f32);
+    int rc = gather_q8_launch(m.feat_q, m.B, m.C_true, m.HW, m.layout, m.roi_q, m.roi_stride_q, m.n_q, w.need_f32, m.cap_q, m.C, w.q8_scratch,
+                              w.scale_scratch, w.eps_scratch, nullptr, w.q_hat, 1, m.round_f16, st);
+    if (rc) { set_error("%s: fall-back gather launch failed", entry); return rc; }
+    rc = match_f32_flagged(m.a_hat, w.q_hat, m.B, m.C, m.cap_a, m.cap_q, n_a, m.n_q, m.threshold, m.min_dist, m.argmin, m.valid, w.panel_flag,
+                           w.row_flag, m.stream);
+    if (rc) return rc;
+    return screen16_fallback(m, w.q_hat, w, who);
+}
+}  // namespace oryon
 
 extern "C" size_t oryon_match_screened8_workspace_bytes(int B, int C, int cap_a, int cap_q)
 {
     if (B <= 0 || C <= 0 || cap_a <= 0 || cap_a % MT16 || cap_q <= 0) return 0;
-    return carve_screen8(nullptr, B, C, cap_a, cap_q, pick_split16(B, cap_a / MT16)).bytes;
+    Screen8Ws w;
+    return carve_screen8(nullptr, w, B, C, cap_a, cap_q, pick_split16(B, cap_a / MT16));
 }
 
 extern "C" int oryon_match_screened8(const float *a_hat, const float *q_hat, const int8_t *a_i8, const int8_t *q_i8, const float *a_scale, const float *q_scale, const float *q_eps_max, int B,
@@ -1260,28 +1327,36 @@ extern "C" int oryon_match_screened8(const float *a_hat, const float *q_hat, con
     ORYON_CHECK_ARG(min_dist && argmin && valid && B >= 0 && (C == 256 || C == 512) && C_true > 0 && C_true <= C);
     ORYON_CHECK_ARG(cap_a > 0 && cap_a % MT16 == 0 && cap_q > 0 && cap_q % 256 == 0 && threshold > 0.0f && threshold <= 0.5f);
     if (B == 0) return ORYON_OK;
-    const int T = cap_a / MT16;
-    const int S = pick_split16(B, T);
-    Screen8Ws w8 = carve_screen8(workspace, B, C, cap_a, cap_q, S);
-    if (!workspace || workspace_bytes < w8.bytes) {
-        set_error("oryon_match_screened8: workspace too small (%zu < %zu)", workspace_bytes, w8.bytes);
+    const int S = pick_split16(B, cap_a / MT16);
+    Screen8Ws w;
+    const size_t need = carve_screen8(workspace, w, B, C, cap_a, cap_q, S);
+    if (!workspace || workspace_bytes < need) {
+        set_error("oryon_match_screened8: workspace too small (%zu < %zu)", workspace_bytes, need);
         return ORYON_ERR_WORKSPACE;
     }
-    ScreenWs &w = w8.top;
     hipStream_t st = as_stream(stream);
+    Screen8Args m;                 // the query rows are fp32 rows here (q_hat): no raw map
+    m.a_hat = a_hat;
+    m.a_i8 = a_i8;
+    m.q_i8 = q_i8;
+    m.a_scale = a_scale;
+    m.q_scale = q_scale;
+    m.q_eps_max = q_eps_max;
+    m.B = B;
+    m.C_true = C_true;
+    m.C = C;
+    m.cap_a = cap_a;
+    m.cap_q = cap_q;
+    m.n_q = n_q;
+    m.threshold = threshold;
+    m.min_dist = min_dist;
+    m.argmin = argmin;
+    m.valid = valid;
+    m.stream = stream;
     ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(workspace) + w.zero_off, 0, w.zero_bytes, st));
-    const float cut0 = 1.0f - 2.0f * threshold;
-    const float valid_cut16 = cut0 - SCREEN_DELTA - 1e-6f;
-    const int groups = ((B * S + 7) / 8) * 8 * T;
-    profile_begin(st, C == 256 ? screen8_name<256>() : screen8_name<512>());
-    if (C == 256) launch_screen8<256>(groups, st, a_i8, q_i8, q_scale, B, cap_a, cap_q, n_a, n_q, T, S, w.ws_max, w.ws_i1, w.ws_m2);
-    else launch_screen8<512>(groups, st, a_i8, q_i8, q_scale, B, cap_a, cap_q, n_a, n_q, T, S, w.ws_max, w.ws_i1, w.ws_m2);
-    profile_end(st);
+    screen8_step(m, S, n_a, w);
     ORYON_CHECK_LAUNCH();
-    hipLaunchKernelGGL((match_decide_kernel<128>), dim3(cap_a / 64, B), dim3(256), 0, st, static_cast<const __half *>(nullptr),
-                       static_cast<const __half *>(nullptr), C, cap_a, cap_q, n_a, n_q, S, valid_cut16,
-                       w.ws_max, w.ws_i1, w.ws_m2, w.m_final, w.cnt, w.cand, w.n_amb, w.amb_idx, a_scale, nullptr, q_eps_max, cut0,
-                       sqrtf((float)C_true), (float)C_true, a_i8, q_i8, q_scale);
+    decide8_step(m, S, n_a, w);
     ORYON_CHECK_LAUNCH();
     hipLaunchKernelGGL((match_rescore_kernel<4>), dim3(cap_a / 64, B), dim3(256), 0, st, a_hat, q_hat, C, cap_a, cap_q, n_a, n_q, S,
                        threshold, -INFINITY, w.ws_max, w.m_final, w.cnt, w.cand, min_dist, argmin, valid, w.row_flag, w.panel_flag);
@@ -1290,63 +1365,15 @@ extern "C" int oryon_match_screened8(const float *a_hat, const float *q_hat, con
                                stream);
     if (rc) return rc;
     if (n_undecided) ORYON_CHECK_HIP(hipMemcpyAsync(n_undecided, w.n_amb, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    // anchors the int8 stage could not decide: complete fp16 pipeline on the compacted set, results scattered back
-    // (their fp16 operands are made here, and only for pairs that have such anchors: K0 does not write fp16 rows for this path)
-    hipLaunchKernelGGL(match_compact8_kernel, dim3(cap_a / 64, B), dim3(256), 0, st, a_hat, static_cast<const __half *>(nullptr), C, cap_a,
-                       w.n_amb, w.amb_idx, w8.a_hat_c, w.a16c);
-    hipLaunchKernelGGL(match_make_q16_kernel, dim3(64, B), dim3(256), 0, st, q_hat, C, cap_q, n_q, w.n_amb, w8.q16);
-    ORYON_CHECK_LAUNCH();
-    rc = oryon_match_screened(w8.a_hat_c, q_hat, w.a16c, w8.q16, B, C, cap_a, cap_q, w.n_amb, n_q, threshold, w8.md_c, w8.am_c, w8.va_c,
-                              w8.nested, w8.nested_bytes, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(match_scatter8_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, w.n_amb, w.amb_idx, w8.md_c, w8.am_c, w8.va_c,
-                       min_dist, argmin, valid);
-    ORYON_CHECK_LAUNCH();
-    return ORYON_OK;
+    return screen16_fallback(m, q_hat, w, __func__);
 }
 
 // ------------------------------------------------------------------------------------------------ K1s8 on K0v3 operands (no fp32 query rows)
-namespace oryon {
-int gather_q8_launch(const float *feat, int n_maps, int C, int HW, int layout, const int32_t *roi, int roi_stride, const int32_t *count,
-                     const int32_t *map_enable, int rows_cap, int C_pad, int8_t *out8, float *scale, float *eps, float *norm,
-                     float *out32, int lanes_per_row, int round_f16, hipStream_t st, int fmt = 0, void *aux = nullptr);
-}
-
-namespace {
-struct Screen8RawWs {
-    Screen8Ws base;
-    float *q_hat, *scale_scratch, *eps_scratch;
-    int8_t *q8_scratch;
-    int32_t *need_f32;
-    size_t bytes;
-};
-
-Screen8RawWs carve_screen8_raw(void *base, int B, int C, int cap_a, int cap_q, int S)
-{
-    Screen8RawWs w;
-    w.base = carve_screen8(base, B, C, cap_a, cap_q, S);
-    char *p = static_cast<char *>(base);
-    size_t off = (w.base.bytes + 255) / 256 * 256;
-    auto take = [&](size_t n) { size_t o = off; off = (off + n + 255) / 256 * 256; return o; };
-    const size_t o_qh = take((size_t)B * cap_q * C * sizeof(float));
-    const size_t o_q8 = take((size_t)B * cap_q * C);                       // the fall-back pass rewrites the same int8 rows here
-    const size_t o_sc = take((size_t)B * (cap_q / 16) * sizeof(float));
-    const size_t o_ep = take((size_t)B * sizeof(float));
-    const size_t o_nf = take((size_t)B * sizeof(int32_t));
-    w.bytes = off;
-    w.q_hat = base ? reinterpret_cast<float *>(p + o_qh) : nullptr;
-    w.q8_scratch = base ? reinterpret_cast<int8_t *>(p + o_q8) : nullptr;
-    w.scale_scratch = base ? reinterpret_cast<float *>(p + o_sc) : nullptr;
-    w.eps_scratch = base ? reinterpret_cast<float *>(p + o_ep) : nullptr;
-    w.need_f32 = base ? reinterpret_cast<int32_t *>(p + o_nf) : nullptr;
-    return w;
-}
-}  // namespace
-
 extern "C" size_t oryon_match_screened8_raw_workspace_bytes(int B, int C, int cap_a, int cap_q)
 {
     if (B <= 0 || C <= 0 || cap_a <= 0 || cap_a % MT16 || cap_q <= 0) return 0;
-    return carve_screen8_raw(nullptr, B, C, cap_a, cap_q, pick_split16(B, cap_a / MT16)).bytes;
+    Screen8RawWs w;
+    return carve_screen8_raw(nullptr, w, B, C, cap_a, cap_q, pick_split16(B, cap_a / MT16));
 }
 
 extern "C" int oryon_match_screened8_raw(const float *a_hat, const int8_t *a_i8, const float *a_scale, const float *feat_q, int C_true,
@@ -1361,1032 +1388,48 @@ extern "C" int oryon_match_screened8_raw(const float *a_hat, const int8_t *a_i8,
     ORYON_CHECK_ARG(layout == ORYON_LAYOUT_NCHW || layout == ORYON_LAYOUT_NHWC);
     ORYON_CHECK_ARG(cap_a > 0 && cap_a % MT16 == 0 && cap_q > 0 && cap_q % 256 == 0 && threshold > 0.0f && threshold <= 0.5f);
     if (B == 0) return ORYON_OK;
-    const int T = cap_a / MT16;
-    const int S = pick_split16(B, T);
-    Screen8RawWs wr = carve_screen8_raw(workspace, B, C, cap_a, cap_q, S);
-    if (!workspace || workspace_bytes < wr.bytes) {
-        set_error("oryon_match_screened8_raw: workspace too small (%zu < %zu)", workspace_bytes, wr.bytes);
+    const int S = pick_split16(B, cap_a / MT16);
+    Screen8RawWs w;
+    const size_t need = carve_screen8_raw(workspace, w, B, C, cap_a, cap_q, S);
+    if (!workspace || workspace_bytes < need) {
+        set_error("oryon_match_screened8_raw: workspace too small (%zu < %zu)", workspace_bytes, need);
         return ORYON_ERR_WORKSPACE;
     }
-    Screen8Ws &w8 = wr.base;
-    ScreenWs &w = w8.top;
     hipStream_t st = as_stream(stream);
+    Screen8Args m;
+    m.a_hat = a_hat;
+    m.a_i8 = a_i8;
+    m.q_i8 = q_i8;
+    m.a_scale = a_scale;
+    m.q_scale = q_scale;
+    m.q_eps_max = q_eps_max;
+    m.B = B;
+    m.C_true = C_true;
+    m.C = C;
+    m.cap_a = cap_a;
+    m.cap_q = cap_q;
+    m.n_q = n_q;
+    m.threshold = threshold;
+    m.feat_q = feat_q;
+    m.HW = HW;
+    m.layout = layout;
+    m.roi_q = roi_q;
+    m.roi_stride_q = roi_stride;
+    m.q_norm = q_norm;
+    m.round_f16 = round_f16;
+    m.min_dist = min_dist;
+    m.argmin = argmin;
+    m.valid = valid;
+    m.stream = stream;
     ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(workspace) + w.zero_off, 0, w.zero_bytes, st));
-    ORYON_CHECK_HIP(hipMemsetAsync(wr.need_f32, 0, (size_t)B * sizeof(int32_t), st));
-    const float cut0 = 1.0f - 2.0f * threshold;
-    const float valid_cut16 = cut0 - SCREEN_DELTA - 1e-6f;
-    const int groups = ((B * S + 7) / 8) * 8 * T;
-    profile_begin(st, C == 256 ? screen8_name<256>() : screen8_name<512>());
-    if (C == 256) launch_screen8<256>(groups, st, a_i8, q_i8, q_scale, B, cap_a, cap_q, n_a, n_q, T, S, w.ws_max, w.ws_i1, w.ws_m2);
-    else launch_screen8<512>(groups, st, a_i8, q_i8, q_scale, B, cap_a, cap_q, n_a, n_q, T, S, w.ws_max, w.ws_i1, w.ws_m2);
-    profile_end(st);
+    ORYON_CHECK_HIP(hipMemsetAsync(w.need_f32, 0, (size_t)B * sizeof(int32_t), st));
+    screen8_step(m, S, n_a, w);
     ORYON_CHECK_LAUNCH();
-    hipLaunchKernelGGL((match_decide_kernel<128>), dim3(cap_a / 64, B), dim3(256), 0, st, static_cast<const __half *>(nullptr),
-                       static_cast<const __half *>(nullptr), C, cap_a, cap_q, n_a, n_q, S, valid_cut16,
-                       w.ws_max, w.ws_i1, w.ws_m2, w.m_final, w.cnt, w.cand, w.n_amb, w.amb_idx, a_scale, nullptr, q_eps_max, cut0,
-                       sqrtf((float)C_true), (float)C_true, a_i8, q_i8, q_scale);
+    decide8_step(m, S, n_a, w);
     ORYON_CHECK_LAUNCH();
     static const int resc_l = dev_env_int("ORYON_RESCORE_LANES", 2);
-#define RESCORE_RAW(LV, NHWCV)                                                                                                 \
-    hipLaunchKernelGGL((match_rescore_raw_kernel<LV, NHWCV>), dim3(cap_a / (256 / LV), B), dim3(256), 0, st, a_hat, feat_q, C_true, HW, \
-                       roi_q, roi_stride, q_norm, C, cap_a, cap_q, n_a, n_q, threshold, w.m_final, w.cnt, w.cand, min_dist, argmin,  \
-                       valid, w.row_flag, w.panel_flag, wr.need_f32, round_f16)
-    if (layout == ORYON_LAYOUT_NHWC) { if (resc_l == 1) RESCORE_RAW(1, true); else if (resc_l == 4) RESCORE_RAW(4, true); else RESCORE_RAW(2, true); }
-    else { if (resc_l == 1) RESCORE_RAW(1, false); else if (resc_l == 4) RESCORE_RAW(4, false); else RESCORE_RAW(2, false); }
-#undef RESCORE_RAW
+    rescore_raw_step(m, n_a, resc_l, w);
     ORYON_CHECK_LAUNCH();
     if (n_undecided) ORYON_CHECK_HIP(hipMemcpyAsync(n_undecided, w.n_amb, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    // Fall-backs (both rare, both gated per pair on the device): pairs with undecided anchors or an overflowed candidate list get their
-    // canonical fp32 query rows materialised now - the price round 1 paid for EVERY pair - and then take the round-1 route.
-    hipLaunchKernelGGL(match_need_f32_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, w.n_amb, wr.need_f32);
-    int rc = gather_q8_launch(feat_q, B, C_true, HW, layout, roi_q, roi_stride, n_q, wr.need_f32, cap_q, C, wr.q8_scratch, wr.scale_scratch,
-                              wr.eps_scratch, nullptr, wr.q_hat, 1, round_f16, st);
-    if (rc) { set_error("oryon_match_screened8_raw: fall-back gather launch failed"); return rc; }
-    rc = match_f32_flagged(a_hat, wr.q_hat, B, C, cap_a, cap_q, n_a, n_q, threshold, min_dist, argmin, valid, w.panel_flag, w.row_flag,
-                           stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(match_compact8_kernel, dim3(cap_a / 64, B), dim3(256), 0, st, a_hat, static_cast<const __half *>(nullptr), C, cap_a,
-                       w.n_amb, w.amb_idx, w8.a_hat_c, w.a16c);
-    hipLaunchKernelGGL(match_make_q16_kernel, dim3(64, B), dim3(256), 0, st, wr.q_hat, C, cap_q, n_q, w.n_amb, w8.q16);
-    ORYON_CHECK_LAUNCH();
-    rc = oryon_match_screened(w8.a_hat_c, wr.q_hat, w.a16c, w8.q16, B, C, cap_a, cap_q, w.n_amb, n_q, threshold, w8.md_c, w8.am_c, w8.va_c,
-                              w8.nested, w8.nested_bytes, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(match_scatter8_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, w.n_amb, w.amb_idx, w8.md_c, w8.am_c, w8.va_c,
-                       min_dist, argmin, valid);
-    ORYON_CHECK_LAUNCH();
-    return ORYON_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ lazy tail: K1s8 -> sampled correspondences
-// The batched engine consumes the matcher through oryon_select_corrs only: it needs the VALID FLAG of every anchor and the argmin of the
-// <= max_corrs anchors that get sampled (utils/pcd.py:205-214).  The int8 bound decides validity outright for almost every anchor:
-//     m1 - DELTA8 > 1 - 2 thr   =>  the exact distance is below the threshold   (valid, whatever the argmin)
-//     m1 + DELTA8 < 1 - 2 thr   =>  it is not                                   (as before)
-// so candidate generation (16 int8 rows per anchor) and exact re-scoring (256 strided reads per candidate) are deferred to the sampled
-// anchors - 500 per pair instead of 5000.  Anchors whose validity the bound cannot settle are resolved (exactly) before the sampling;
-// a pair in which a possibly-valid anchor is AMBIGUOUS (runner-up slice within the int8 margin: its argmin needs the fp16 stage) takes
-// the eager route of oryon_match_screened8_raw for all of its anchors.  Outputs are what select(match_screened8_raw(...)) gives,
-// bit for bit: same valid set, same sampled rows (the sampling keys depend on the valid set only), same argmin for every sampled row.
-namespace oryon {
-int select_corrs_launch(const int32_t *roi_a, const int32_t *roi_q, int roi_stride_a, int roi_stride_q, const int32_t *n_a,
-                        const int32_t *n_q, const int32_t *argmin, const uint8_t *valid, int cap_a, int B, int W, int max_corrs,
-                        int corr_rows, uint64_t seed, const int64_t *pair_key, int32_t *scratch, int32_t *corrs, int32_t *n_valid,
-                        int32_t *n_sel, int32_t *status, int32_t *sel_rows, const int32_t *pair_eager, hipStream_t st);
-
-// INVALID / VALID: settled by the int8 bound.  UNCERTAIN: unambiguous winner slice, validity not settled (resolved from that slice before
-// the sampling).  AMB_VALID: validity settled (valid) but the runner-up slice is within the int8 margin - the exact argmin is computed
-// only if the row gets sampled.  AMB_UNCERTAIN: neither settled - resolved before the sampling.  Both AMB kinds are resolved by the EXACT
-// fp32 scan (K1) on a compacted list of just those anchor rows against the pair's materialised fp32 query rows.
-constexpr uint8_t LZ_INVALID = 0, LZ_VALID = 1, LZ_UNCERTAIN = 2, LZ_AMB_VALID = 3, LZ_RESOLVED = 4, LZ_AMB_UNCERTAIN = 5;
-
-// one THREAD per anchor: merge the per-split (m1, slice, m2) triples and classify
-__global__ __launch_bounds__(256) void match_decide_lite_kernel(
-    int cap_a, const int32_t *__restrict__ n_a, int S, const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
-    const float *__restrict__ ws_m2, const float *__restrict__ a_scale8, const float *__restrict__ eps_q8, float cut0, float sqrt_c,
-    float c_true, int force_eager, int fmt, int x3, float *__restrict__ m_final, int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
-    uint8_t *__restrict__ state, uint8_t *__restrict__ valid, float *__restrict__ min_dist, int32_t *__restrict__ argmin,
-    int32_t *__restrict__ pair_eager, int32_t *__restrict__ n_unc, int32_t *__restrict__ unc_idx, int32_t *__restrict__ n_ambu,
-    int32_t *__restrict__ ambu_idx, int32_t *__restrict__ need_f32_lazy, int32_t *__restrict__ n_amb_total)
-{
-    const int p = blockIdx.y, a = blockIdx.x * 256 + threadIdx.x;
-    if (a >= n_a[p]) return;
-    const size_t arow = (size_t)p * cap_a + a;
-    float m1 = -INFINITY, m2 = -INFINITY;
-    int sid = 0;
-    for (int s = 0; s < S; ++s) {
-        const size_t o = ((size_t)p * S + s) * cap_a + a;
-        const float x1 = ws_m1[o], x2 = ws_m2[o];
-        m2 = fmaxf(fminf(m1, x1), fmaxf(m2, x2));
-        if (x1 > m1) { m1 = x1; sid = ws_i1[o]; }
-    }
-    float delta;
-    if (fmt == 1) {
-        // mx6 screen: scores are dequantised dot products; a_scale8 / eps_q8 hold the pair's largest measured row error |e|_2 of the
-        // anchor / query rows (K0, FMT = 1): |s6 - a^.q^| <= |ea| + |eq| + |ea||eq| + fp32 accumulation slack
-        const float ea = a_scale8[p], eq = eps_q8[p];
-        delta = ea + eq + ea * eq + 1.2e-4f;       // + fp32 accumulation of <= 512 products in the MFMA and in the canonical chain (<= 7e-5)
-    } else {
-        const float sa = a_scale8[(size_t)p * (cap_a / 16) + (a >> 5) * 2 + ((a >> 2) & 1)];
-        m1 *= sa;
-        m2 *= sa;
-        const float ea = 0.50003f * sa, eq = 1.00006f * eps_q8[p];
-        delta = (ea + eq) * sqrt_c + c_true * ea * eq + 4e-5f;
-    }
-    const bool usable = delta < 0.2f;
-    const float margin = usable ? 2.0f * delta + 2e-7f : INFINITY;
-    m_final[arow] = m1;
-    sid_final[arow] = sid;
-    margin_out[arow] = margin;
-    uint8_t st;
-    const bool certain_valid = usable && m1 > cut0 + delta + 1e-5f;
-    if (usable && !(m1 >= cut0 - delta - 1e-6f)) st = LZ_INVALID;
-    else if (!(m1 - m2 > margin)) st = certain_valid ? LZ_AMB_VALID : LZ_AMB_UNCERTAIN;
-    else if (certain_valid) st = LZ_VALID;
-    else st = LZ_UNCERTAIN;
-    state[arow] = st;
-    // provisional outputs: the distance is the screening estimate until (unless) the row is resolved exactly
-    min_dist[arow] = __fmaf_rn(-0.5f, m1, 0.5f);
-    argmin[arow] = 0;
-    valid[arow] = (st == LZ_VALID || st == LZ_AMB_VALID) ? 1 : 0;
-    if (force_eager) { pair_eager[p] = 1; return; }
-    if (st == LZ_UNCERTAIN) unc_idx[(size_t)p * cap_a + atomicAdd(&n_unc[p], 1)] = a;
-    if (st == LZ_AMB_UNCERTAIN) ambu_idx[(size_t)p * cap_a + atomicAdd(&n_ambu[p], 1)] = a;
-    if (st == LZ_AMB_VALID || st == LZ_AMB_UNCERTAIN) {
-        // this pair's fp32 query rows get materialised (device-gated launch) - with the fp16x3 second level (x3) only when an
-        // ambiguous anchor's VALIDITY is open too: the sampled valid ones are then resolved from hi / lo half rows made later
-        if (st == LZ_AMB_UNCERTAIN || !x3) need_f32_lazy[p] = 1;
-        atomicAdd(&n_amb_total[p], 1);
-    }
-}
-
-__global__ void match_mask_counts_kernel(int B, const int32_t *__restrict__ n_a, const int32_t *__restrict__ pair_eager,
-                                         int32_t *__restrict__ n_a_eager, int32_t *__restrict__ n_a_lazy)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= B) return;
-    n_a_eager[p] = pair_eager[p] ? n_a[p] : 0;
-    n_a_lazy[p] = pair_eager[p] ? 0 : n_a[p];
-}
-
-__global__ void match_cascade_counts_kernel(int B, const int32_t *__restrict__ n_amb_total, const int32_t *__restrict__ n_after,
-                                            const int32_t *__restrict__ n_before, int32_t *__restrict__ out)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= B) return;
-    const long long tot = n_amb_total[p], nb = n_before[p], na = n_after[p];
-    out[p] = nb > 0 ? (int32_t)(tot * na / nb) : (int32_t)tot;
-}
-
-__global__ void match_sum_counts_kernel(int B, const int32_t *__restrict__ a, const int32_t *__restrict__ b, int32_t *__restrict__ out)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < B) out[p] = a[p] + b[p];
-}
-
-// fp32 anchor rows of a work list -> dense panels for the exact scan (rows [count, round_up(count, 128)) zero-filled)
-__global__ __launch_bounds__(256) void match_compact_f32_kernel(const float *__restrict__ a_hat, int Cp, int cap_a, int cap_c,
-                                                                 const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
-                                                                 int idx_stride, float *__restrict__ a_c)
-{
-    const int p = blockIdx.y, lane = threadIdx.x & 63;
-    const int n = count[p] < cap_c ? count[p] : cap_c;
-    const int n_fill = (n + 127) / 128 * 128;
-    for (int g = 0; g < 16; ++g) {
-        const int sl = (blockIdx.x * 16 + g) * 4 + (threadIdx.x >> 6);
-        if (sl >= n_fill || sl >= cap_c) break;
-        uint4 *d = reinterpret_cast<uint4 *>(a_c + ((size_t)p * cap_c + sl) * Cp);
-        if (sl >= n) {
-            for (int i = lane; i < Cp / 4; i += 64) d[i] = make_uint4(0, 0, 0, 0);
-            continue;
-        }
-        const uint4 *src = reinterpret_cast<const uint4 *>(a_hat + ((size_t)p * cap_a + idx[(size_t)p * idx_stride + sl]) * Cp);
-        for (int i = lane; i < Cp / 4; i += 64) d[i] = src[i];
-    }
-}
-
-// results of an exact scan on a compacted work list -> the anchors' rows; the rows are marked RESOLVED (argmin / min_dist exact)
-__global__ __launch_bounds__(256) void match_scatter_exact_kernel(int cap_a, int cap_c, const int32_t *__restrict__ count,
-                                                                   const int32_t *__restrict__ idx, int idx_stride,
-                                                                   const float *__restrict__ md_c, const int32_t *__restrict__ am_c,
-                                                                   const uint8_t *__restrict__ va_c, float *__restrict__ min_dist,
-                                                                   int32_t *__restrict__ argmin, uint8_t *__restrict__ valid,
-                                                                   uint8_t *__restrict__ state)
-{
-    const int p = blockIdx.y, sl = blockIdx.x * 256 + threadIdx.x;
-    const int n = count[p] < cap_c ? count[p] : cap_c;
-    if (sl >= n) return;
-    const size_t src = (size_t)p * cap_c + sl, dst = (size_t)p * cap_a + idx[(size_t)p * idx_stride + sl];
-    min_dist[dst] = md_c[src];
-    argmin[dst] = am_c[src];
-    valid[dst] = va_c[src];
-    state[dst] = LZ_RESOLVED;
-}
-
-// the sampled slots whose anchor row is AMB_VALID (argmin still unknown) -> work list for the second level (K1x3 / exact scan).  One
-// workgroup per pair.  The list comes out in ASCENDING anchor-row order, i.e. in image order: neighbouring anchors share a wave of
-// match_x3_scan_kernel, their matches are neighbours in the query map, and the scan can skip the query tiles none of a wave's anchors
-// can match (it is also deterministic; the first version appended in atomic order).
-__global__ __launch_bounds__(256) void match_list_sampled_amb_kernel(int cap_a, const uint8_t *__restrict__ state,
-                                                                      const int32_t *__restrict__ pair_eager, const int32_t *__restrict__ n_sel,
-                                                                      const int32_t *__restrict__ sel_rows, int corr_rows,
-                                                                      int32_t *__restrict__ mark, int32_t *__restrict__ n_list,
-                                                                      int32_t *__restrict__ list)
-{
-    __shared__ int wave_cnt[4];
-    const int p = blockIdx.x;
-    if (pair_eager[p]) return;
-    const int n = n_sel[p], t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    // a row drawn several times (sampling with replacement) is marked once
-    for (int s = t; s < n; s += 256) {
-        const int a = sel_rows[(size_t)p * corr_rows + s];
-        if (state[(size_t)p * cap_a + a] == LZ_AMB_VALID) mark[(size_t)p * cap_a + a] = 1;
-    }
-    __threadfence_block();
-    __syncthreads();
-    // ordered compaction in ONE scan: thread t owns the consecutive rows [t R, (t + 1) R), counts its marks, the block scans the 256 counts
-    const int R = (cap_a + 255) / 256;
-    const int32_t *mk = mark + (size_t)p * cap_a;
-    int mine = 0;
-    for (int i = 0; i < R; ++i) {
-        const int a = t * R + i;
-        mine += (a < cap_a && mk[a] != 0) ? 1 : 0;
-    }
-    int incl = mine;                                            // inclusive scan inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wave_cnt[wave] = incl;
-    __syncthreads();
-    int off0 = incl - mine;
-    for (int w = 0; w < wave; ++w) off0 += wave_cnt[w];
-    for (int i = 0; i < R; ++i) {
-        const int a = t * R + i;
-        if (a < cap_a && mk[a] != 0) list[(size_t)p * corr_rows + off0++] = a;
-    }
-    if (t == 255) n_list[p] = off0;
-}
-
-// ---- validity cascade, second pass (round 6; oryon_match_corrs_mx6_x3).  The first screening pass stops a panel once its anchors are all
-// valid for sure and leaves their runner-up open (match_mx6_screen_w4_kernel<.., EXIT>); the sampled ones among them (the list of
-// match_list_sampled_amb_kernel, <= corr_rows per pair) get the COMPLETE screen here: their operand rows compacted into one panel per pair,
-// the same kernel over all query tiles, and the (m1, slice, m2) triples merged back into the per-anchor arrays - a row whose winner turns
-// out unambiguous becomes LZ_VALID (resolved from its winning slice like any other), the others keep LZ_AMB_VALID with their true winning
-// slice as the second level's seed.
-// after the windowed first launch: is every live anchor of a 1024-row panel valid for sure already (its best score over the splits' windows
-// above match_decide_lite_kernel's line)?  Then gate = 0 and its runner-ups read +inf (no margin: a partial scan rules nothing out);
-// otherwise gate = 1: the gated launch scans everything for this panel and overwrites the triples.
-__global__ __launch_bounds__(256) void match_panel_settle_kernel(int cap_a, int T8, int S, const int32_t *__restrict__ n_a,
-                                                                  const float *__restrict__ ws_m1, float *__restrict__ ws_m2,
-                                                                  const float *__restrict__ a_err, const float *__restrict__ q_err,
-                                                                  float cut0, int32_t *__restrict__ gate)
-{
-    __shared__ int bad;
-    const int p = blockIdx.y, panel = blockIdx.x, t = threadIdx.x;
-    const int na = n_a[p], a0 = panel * 1024;
-    if (a0 >= na) return;
-    if (t == 0) bad = 0;
-    __syncthreads();
-    const float ea = a_err[p], eq = q_err[p];
-    const float delta = ea + eq + ea * eq + 1.2e-4f;
-    const float thr = delta < 0.2f ? cut0 + delta + 2e-5f : INFINITY;      // (match_decide_lite_kernel: m1 > cut0 + delta + 1e-5)
-    int mine = 0;
-    for (int a = a0 + t; a < a0 + 1024 && a < na; a += 256) {
-        float m1 = -INFINITY;
-        for (int s_ = 0; s_ < S; ++s_) m1 = fmaxf(m1, ws_m1[((size_t)p * S + s_) * cap_a + a]);
-        mine |= !(m1 > thr);
-    }
-    if (mine) atomicOr(&bad, 1);
-    __syncthreads();
-    const int open = bad;
-    if (t == 0) gate[p * T8 + panel] = open;
-    if (!open)
-        for (int a = a0 + t; a < a0 + 1024 && a < na; a += 256)
-            for (int s_ = 0; s_ < S; ++s_) ws_m2[((size_t)p * S + s_) * cap_a + a] = INFINITY;
-}
-
-__global__ __launch_bounds__(256) void match_compact_rows_kernel(const uint8_t *__restrict__ rows, int row_bytes, int cap_a, int cap_c,
-                                                                  const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
-                                                                  int idx_stride, uint8_t *__restrict__ out)
-{
-    // 16 lanes per 256-byte row (uint4 each); rows [count, cap_c) are zero rows (exponent byte 0: finite scores nobody reads)
-    const int p = blockIdx.y, sl = blockIdx.x * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
-    if (sl >= cap_c) return;
-    const int n = count[p] < cap_c ? count[p] : cap_c;
-    uint4 *d = reinterpret_cast<uint4 *>(out + ((size_t)p * cap_c + sl) * row_bytes);
-    if (sl >= n) {
-        for (int i = l; i < row_bytes / 16; i += 16) d[i] = make_uint4(0, 0, 0, 0);
-        return;
-    }
-    const uint4 *src = reinterpret_cast<const uint4 *>(rows + ((size_t)p * cap_a + idx[(size_t)p * idx_stride + sl]) * row_bytes);
-    for (int i = l; i < row_bytes / 16; i += 16) d[i] = src[i];
-}
-
-__global__ __launch_bounds__(256) void match_decide_sampled_kernel(int cap_a, int cap_c, int S, const int32_t *__restrict__ count,
-                                                                    const int32_t *__restrict__ idx, int idx_stride,
-                                                                    const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
-                                                                    const float *__restrict__ ws_m2, const float *__restrict__ a_err,
-                                                                    const float *__restrict__ q_err, float *__restrict__ m_final,
-                                                                    int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
-                                                                    uint8_t *__restrict__ state, int32_t *__restrict__ mark,
-                                                                    int32_t *__restrict__ count_before)
-{
-    const int p = blockIdx.y, sl = blockIdx.x * 256 + threadIdx.x;
-    const int n = count[p] < cap_c ? count[p] : cap_c;
-    if (sl == 0) count_before[p] = n;
-    if (sl >= n) return;
-    const int a = idx[(size_t)p * idx_stride + sl];
-    float m1 = -INFINITY, m2 = -INFINITY;
-    int sid = 0;
-    for (int s = 0; s < S; ++s) {
-        const size_t o = ((size_t)p * S + s) * cap_c + sl;
-        const float x1 = ws_m1[o], x2 = ws_m2[o];
-        m2 = fmaxf(fminf(m1, x1), fmaxf(m2, x2));
-        if (x1 > m1) { m1 = x1; sid = ws_i1[o]; }
-    }
-    const float ea = a_err[p], eq = q_err[p];
-    const float delta = ea + eq + ea * eq + 1.2e-4f;                  // match_decide_lite_kernel, fmt 1
-    const float margin = delta < 0.2f ? 2.0f * delta + 2e-7f : INFINITY;
-    const size_t arow = (size_t)p * cap_a + a;
-    m_final[arow] = m1;                                                // the complete scan's maximum (>= the partial one that settled validity)
-    sid_final[arow] = sid;
-    margin_out[arow] = margin;
-    if (m1 - m2 > margin) {                                            // unambiguous after all: no second level for this row
-        state[arow] = LZ_VALID;
-        mark[arow] = 0;
-    }
-}
-
-// Exact resolution of ONE unambiguous anchor by one wave: candidates = rows of the winning 16-row slice within the int8 margin of its
-// maximum (re-scored from the int8 rows, as match_decide_kernel does), then the canonical fp32 chain per candidate on x_k / d read
-// from the raw map (as match_rescore_raw_kernel does).  Returns (distance, first index of the minimum) in lane 0.
-typedef float f32x32r __attribute__((ext_vector_type(32)));
-typedef unsigned u32x6r __attribute__((ext_vector_type(6)));
-
-// dequantised dot product of two mx6 slots (32 channels): codes decoded by the conversion instruction (exact: multiples of 1/8 up to
-// 7.5), 32 exact products summed in fp32 (every partial sum is a multiple of 1/64 below 2^11: exact), times both block exponents
-__device__ __forceinline__ float mx6_block_dot(const uint4 a_lo, const uint4 a_up, const uint4 q_lo, const uint4 q_up)
-{
-    const u32x6r ca = {a_lo.x, a_lo.y, a_lo.z, a_lo.w, a_up.x, a_up.y}, cq = {q_lo.x, q_lo.y, q_lo.z, q_lo.w, q_up.x, q_up.y};
-    const f32x32r fa = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(ca, 1.0f), fq = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(cq, 1.0f);
-    float sum = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) sum = __fmaf_rn(fa[i], fq[i], sum);
-    return sum * ldexpf(1.0f, (int)(a_up.z & 255u) + (int)(q_up.z & 255u) - 254);
-}
-
-// Anchor rows on demand (the `_araw` entries): where K0 wrote no fp32 unit rows (a_hat == nullptr), a consumer forms the row itself from
-// the raw anchor map, exactly as K0 does - x_k at the anchor's pixel (rounded to float16 first under round_f16, zero beyond C_true),
-// divided by the norm K0 left in a_norm: __fdiv_rn(x_k, d), bit for bit the value K0 would have stored.
-struct AnchorRaw {
-    const float *feat_a;        // [B, C_true, HW] (or channels-last), the map K0 gathered the anchors from
-    const int32_t *roi_a;       // [B, roi_stride] pixel of every anchor row
-    const float *a_norm;        // [B, cap_a] K0's row norms
-    int roi_stride;
-};
-
-template <bool NHWC>
-__device__ __forceinline__ float anchor_raw_unit(const float *__restrict__ fa, int pix, float d, int k, int C_true, int HW, int round_f16)
-{
-    float x = 0.0f;
-    if (k < C_true) x = NHWC ? fa[(size_t)pix * C_true + k] : fa[(size_t)k * HW + pix];
-    if (round_f16) x = __half2float(__float2half_rn(x));
-    return __fdiv_rn(x, d);
-}
-
-template <bool NHWC, bool NEED_DIST = true, int FMT = 0>
-__device__ __forceinline__ void resolve_anchor(int p, int a, const float *__restrict__ a_hat, const AnchorRaw &araw, const int8_t *__restrict__ a8,
-                                               const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
-                                               const float *__restrict__ a_scale8, const float *__restrict__ feat_q, int C_true, int HW,
-                                               const int32_t *__restrict__ roi_q, int roi_stride, const float *__restrict__ norm_q,
-                                               int Cp, int cap_a, int cap_q, int nq, float m1, int sid, float margin, float *lds /*[2*Cp]*/,
-                                               int round_f16, float &d_out, int &j_out)
-{
-    const int lane = threadIdx.x & 63;
-    const size_t arow = (size_t)p * cap_a + a;
-    const int half = sid & 1, blk = sid >> 1;
-    const int r = lane >> 2, seg = lane & 3;
-    const int q = blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-    bool hit;
-    if constexpr (FMT == 1) {
-        // mx6 rows: the 16 rows of the winning slice re-scored from the very operands the screen multiplied (software sum: the order of
-        // the additions differs from the MFMA's, inside the bound's slack); candidates = rows within the margin of the SLICE maximum
-        // (every exact minimiser lies in this slice and scores at least max - 2 delta)
-        float s6 = 0.0f;
-        if (q < nq) {
-            const uint4 *ar = reinterpret_cast<const uint4 *>(a8 + arow * Cp) + seg * (Cp / 64);
-            const uint4 *qr = reinterpret_cast<const uint4 *>(q8 + ((size_t)p * cap_q + q) * Cp) + seg * (Cp / 64);
-            for (int b = 0; b < Cp / 128; ++b) s6 += mx6_block_dot(ar[2 * b], ar[2 * b + 1], qr[2 * b], qr[2 * b + 1]);
-        }
-        s6 += __shfl_xor(s6, 1);
-        s6 += __shfl_xor(s6, 2);
-        float mx = (q < nq) ? s6 : -INFINITY;
-        mx = fmaxf(mx, __shfl_xor(mx, 4));
-        mx = fmaxf(mx, __shfl_xor(mx, 8));
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        hit = (seg == 0) && (q < nq) && (s6 >= mx - margin - 4e-5f);
-        (void)m1;
-    } else {
-    const float sa = a_scale8[(size_t)p * (cap_a / 16) + (a >> 5) * 2 + ((a >> 2) & 1)];
-    int idot = 0;
-    if (q < nq) {
-        const uint4 *ar = reinterpret_cast<const uint4 *>(a8 + arow * Cp) + seg * (Cp / 64);
-        const uint4 *qr = reinterpret_cast<const uint4 *>(q8 + ((size_t)p * cap_q + q) * Cp) + seg * (Cp / 64);
-        for (int i0 = 0; i0 < Cp / 64; ++i0) {
-            const uint4 av = ar[i0], qv = qr[i0];
-            idot = __builtin_amdgcn_sdot4((int)av.x, (int)qv.x, idot, false);
-            idot = __builtin_amdgcn_sdot4((int)av.y, (int)qv.y, idot, false);
-            idot = __builtin_amdgcn_sdot4((int)av.z, (int)qv.z, idot, false);
-            idot = __builtin_amdgcn_sdot4((int)av.w, (int)qv.w, idot, false);
-        }
-    }
-    idot += __shfl_xor(idot, 1);
-    idot += __shfl_xor(idot, 2);
-    const float s8 = (float)idot * q_scale8[(size_t)p * (cap_q / 16) + sid] * sa;
-    hit = (seg == 0) && (q < nq) && (s8 >= m1 - margin);
-    }
-    unsigned long long hits = __ballot(hit);
-    if (!NEED_DIST && __popcll(hits) == 1) {
-        // a single row inside the int8 margin IS the argmin (every other row is provably farther): no fp32 work, and none of the 256
-        // scattered 4-byte reads of its raw descriptor (the NCHW gather is what bounds this kernel: one 64-byte sector per channel)
-        j_out = __shfl(q, __ffsll((long long)hits) - 1);
-        d_out = __builtin_nanf("");
-        return;
-    }
-    // anchor row (k-permuted: position 8g + 4h + j holds k = 8g + 2j + h) -> natural order in LDS
-    float *A = lds, *Q = lds + Cp;
-    if (a_hat) {
-        for (int pos = lane; pos < Cp; pos += 64) {
-            const int g = pos >> 3, hh = (pos >> 2) & 1, jj = pos & 3;
-            A[8 * g + 2 * jj + hh] = a_hat[arow * Cp + pos];
-        }
-    } else {
-        // no materialised row: the same values from the raw map (one pass, Cp / 64 independent loads per lane), natural order as they come
-        const float *fa = araw.feat_a + (size_t)p * C_true * HW;
-        const int pix_a = araw.roi_a[(size_t)p * araw.roi_stride + a];
-        const float da = araw.a_norm[arow];
-        for (int k = lane; k < Cp; k += 64) A[k] = anchor_raw_unit<NHWC>(fa, pix_a, da, k, C_true, HW, round_f16);
-    }
-    float d = INFINITY;
-    int j = 0x7fffffff;
-    const float *fq = feat_q + (size_t)p * C_true * HW;
-    while (hits) {
-        const int src = __ffsll((long long)hits) - 1;
-        hits &= hits - 1;
-        const int jj = __shfl(q, src);
-        const int pix = roi_q[(size_t)p * roi_stride + jj];
-        const float dq = norm_q[(size_t)p * cap_q + jj];
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int k = lane; k < Cp; k += 64) {
-            float x = 0.0f;
-            if (k < C_true) x = NHWC ? fq[(size_t)pix * C_true + k] : fq[(size_t)k * HW + pix];
-            if (round_f16) x = __half2float(__float2half_rn(x));
-            Q[k] = __fdiv_rn(x, dq);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        float dot = 0.0f;                               // every lane runs the same chain on broadcast LDS reads
-        for (int k = 0; k < C_true; k += 8) {
-            float av[8], qv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { av[e] = A[k + e]; qv[e] = Q[k + e]; }
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                if (k + e < C_true) dot = __fmaf_rn(av[e], qv[e], dot);
-        }
-        lex_min(d, j, __fmaf_rn(-0.5f, dot, 0.5f), jj);
-    }
-    d_out = d;
-    j_out = j;
-}
-
-// match_compact_f32_kernel for the `_araw` entries: the listed anchors' fp32 unit rows formed from the raw map (anchor_raw_unit) and
-// written in the k-permuted order K0's rows have (position 8g + 4h + j holds k = 8g + 2j + h), which is what K1 / K1x3 read.  One wave
-// per row, one 16-byte store per lane: lane i of a pass owns positions 4i .. 4i + 3 = (g, h) = (i >> 1, i & 1), j = 0 .. 3.
-template <bool NHWC>
-__global__ __launch_bounds__(256) void match_compact_raw_kernel(const AnchorRaw araw, int C_true, int HW, int round_f16, int Cp, int cap_a,
-                                                                 int cap_c, const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
-                                                                 int idx_stride, float *__restrict__ a_c)
-{
-    const int p = blockIdx.y, lane = threadIdx.x & 63;
-    const int n = count[p] < cap_c ? count[p] : cap_c;
-    const int n_fill = (n + 127) / 128 * 128;
-    const float *fa = araw.feat_a + (size_t)p * C_true * HW;
-    for (int g = 0; g < 16; ++g) {
-        const int sl = (blockIdx.x * 16 + g) * 4 + (threadIdx.x >> 6);
-        if (sl >= n_fill || sl >= cap_c) break;
-        float4 *d = reinterpret_cast<float4 *>(a_c + ((size_t)p * cap_c + sl) * Cp);
-        if (sl >= n) {
-            for (int i = lane; i < Cp / 4; i += 64) d[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            continue;
-        }
-        const int a = idx[(size_t)p * idx_stride + sl];
-        const int pix = araw.roi_a[(size_t)p * araw.roi_stride + a];
-        const float da = araw.a_norm[(size_t)p * cap_a + a];
-        for (int i = lane; i < Cp / 4; i += 64) {
-            const int k0 = 8 * (i >> 1) + (i & 1);
-            float4 q;
-            q.x = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 0, C_true, HW, round_f16);
-            q.y = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 2, C_true, HW, round_f16);
-            q.z = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 4, C_true, HW, round_f16);
-            q.w = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 6, C_true, HW, round_f16);
-            d[i] = q;
-        }
-    }
-}
-
-// anchors whose VALIDITY the int8 bound could not settle (pairs on the lazy route only): exact distance now, before the sampling
-template <bool NHWC, int FMT = 0>
-__global__ __launch_bounds__(256) void match_resolve_uncertain_kernel(
-    const float *__restrict__ a_hat, const AnchorRaw araw, const int8_t *__restrict__ a8, const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
-    const float *__restrict__ a_scale8, const float *__restrict__ feat_q, int C_true, int HW, const int32_t *__restrict__ roi_q,
-    int roi_stride, const float *__restrict__ norm_q, int Cp, int cap_a, int cap_q, const int32_t *__restrict__ n_q, float thr,
-    const float *__restrict__ m_final, const int32_t *__restrict__ sid_final, const float *__restrict__ margin_in,
-    const int32_t *__restrict__ n_unc, const int32_t *__restrict__ unc_idx, const int32_t *__restrict__ pair_eager,
-    uint8_t *__restrict__ state, uint8_t *__restrict__ valid, float *__restrict__ min_dist, int32_t *__restrict__ argmin, int round_f16)
-{
-    extern __shared__ float lds_res[];
-    const int p = blockIdx.y;
-    if (pair_eager[p]) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int n = n_unc[p];
-    for (int i = blockIdx.x * 4 + wave; i < n; i += gridDim.x * 4) {
-        const int a = unc_idx[(size_t)p * cap_a + i];
-        const size_t arow = (size_t)p * cap_a + a;
-        float d;
-        int j;
-        resolve_anchor<NHWC, true, FMT>(p, a, a_hat, araw, a8, q8, q_scale8, a_scale8, feat_q, C_true, HW, roi_q, roi_stride, norm_q, Cp, cap_a, cap_q, n_q[p],
-                             m_final[arow], sid_final[arow], margin_in[arow], lds_res + wave * 2 * Cp, round_f16, d, j);
-        if (lane == 0) {
-            min_dist[arow] = d;
-            argmin[arow] = j;
-            valid[arow] = (d < thr) ? 1 : 0;
-            state[arow] = LZ_RESOLVED;
-        }
-    }
-}
-
-// the sampled rows of the lazy pairs: exact argmin -> query half of the correspondence
-template <bool NHWC, int FMT = 0>
-__global__ __launch_bounds__(256) void match_resolve_selected_kernel(
-    const float *__restrict__ a_hat, const AnchorRaw araw, const int8_t *__restrict__ a8, const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
-    const float *__restrict__ a_scale8, const float *__restrict__ feat_q, int C_true, int HW, const int32_t *__restrict__ roi_q,
-    int roi_stride, const float *__restrict__ norm_q, int Cp, int cap_a, int cap_q, const int32_t *__restrict__ n_q, int W,
-    const float *__restrict__ m_final, const int32_t *__restrict__ sid_final, const float *__restrict__ margin_in,
-    const uint8_t *__restrict__ state, const int32_t *__restrict__ pair_eager, const int32_t *__restrict__ n_sel,
-    const int32_t *__restrict__ sel_rows, int corr_rows, float *__restrict__ min_dist, int32_t *__restrict__ argmin,
-    int32_t *__restrict__ corrs, int round_f16)
-{
-    extern __shared__ float lds_res[];
-    const int p = blockIdx.y;
-    if (pair_eager[p]) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int slot = blockIdx.x * 4 + wave;
-    if (slot >= n_sel[p]) return;
-    const int a = sel_rows[(size_t)p * corr_rows + slot];
-    const size_t arow = (size_t)p * cap_a + a;
-    float d = 0.0f;
-    int j;
-    if (state[arow] == LZ_RESOLVED) {
-        j = argmin[arow];
-    } else {
-        resolve_anchor<NHWC, false, FMT>(p, a, a_hat, araw, a8, q8, q_scale8, a_scale8, feat_q, C_true, HW, roi_q, roi_stride, norm_q, Cp, cap_a, cap_q,
-                                    n_q[p], m_final[arow], sid_final[arow], margin_in[arow], lds_res + wave * 2 * Cp, round_f16, d, j);
-        if (lane == 0) {                                                // same values from every slot that drew this row
-            argmin[arow] = j;
-            if (d == d) min_dist[arow] = d;                             // NaN: single candidate, the distance was never needed
-        }
-    }
-    if (lane == 0) {
-        j = (j < 0 || j >= n_q[p]) ? 0 : j;                            // cannot happen for a row that passed the validity cut
-        const int pq = roi_q[(size_t)p * roi_stride + j];
-        corrs[((size_t)p * corr_rows + slot) * 4 + 2] = pq / W;
-        corrs[((size_t)p * corr_rows + slot) * 4 + 3] = pq % W;
-    }
-}
-}  // namespace oryon
-
-namespace {
-struct LazyWs {
-    Screen8RawWs raw;
-    float *margin;
-    int32_t *sid_final, *pair_eager, *n_unc, *unc_idx, *n_a_eager, *n_a_lazy, *sel_rows, *scratch;
-    int32_t *n_ambu, *ambu_idx, *n_ambv, *ambv_idx, *need_f32_lazy, *n_amb_total, *mark;
-    void *exact_ws;
-    size_t exact_ws_bytes;
-    // K1x3 (C_pad 256): hi / lo anchor rows, the overflow fall-back's compact rows and outputs, candidate lists
-    __half *x3_ah, *x3_al;
-    float *x3_a_ovf, *x3_md_o;
-    int32_t *x3_am_o;
-    uint8_t *x3_va_o;
-    void *x3_scratch;
-    uint8_t *state;
-    // validity cascade (hard route, C_pad 256): the sampled anchors' mx6 rows as one 512-row panel per pair + the second pass's triples
-    uint8_t *cs_panel;
-    float *cs_max, *cs_m2;
-    int32_t *cs_i1;
-    int32_t *n_ambv0, *cs_gate;
-    size_t bytes, zero_off, zero_bytes;
-};
-
-LazyWs carve_lazy(void *base, int B, int C, int cap_a, int cap_q, int S, int corr_rows)
-{
-    LazyWs w;
-    w.raw = carve_screen8_raw(base, B, C, cap_a, cap_q, S);
-    char *p = static_cast<char *>(base);
-    size_t off = (w.raw.bytes + 255) / 256 * 256;
-    auto take = [&](size_t n) { size_t o = off; off = (off + n + 255) / 256 * 256; return o; };
-    const size_t o_mg = take((size_t)B * cap_a * sizeof(float));
-    const size_t o_sf = take((size_t)B * cap_a * sizeof(int32_t));
-    const size_t o_ui = take((size_t)B * cap_a * sizeof(int32_t));
-    const size_t o_st = take((size_t)B * cap_a);
-    const size_t o_sr = take((size_t)B * corr_rows * sizeof(int32_t));
-    const size_t o_sc = take((size_t)B * cap_a * sizeof(int32_t));
-    const size_t o_ne = take((size_t)B * sizeof(int32_t));
-    const size_t o_nl = take((size_t)B * sizeof(int32_t));
-    const size_t o_au = take((size_t)B * cap_a * sizeof(int32_t));
-    const size_t o_av = take((size_t)B * corr_rows * sizeof(int32_t));
-    const int cap_s0 = (corr_rows + 127) / 128 * 128;
-    const int cap_s = cap_s0 < cap_a ? cap_s0 : cap_a;
-    const size_t e1 = oryon_match_workspace_bytes(B, cap_a), e2 = oryon_match_workspace_bytes(B, cap_s);
-    w.exact_ws_bytes = e1 > e2 ? e1 : e2;                                  // split-merge scratch of the exact scan (either list capacity)
-    const size_t o_ew = take(w.exact_ws_bytes > 16 ? w.exact_ws_bytes : 16);
-    const size_t o_xah = take((size_t)B * cap_s * C * sizeof(__half));
-    const size_t o_xal = take((size_t)B * cap_s * C * sizeof(__half));
-    const size_t o_xao = take((size_t)B * cap_s * C * sizeof(float));
-    const size_t o_xmd = take((size_t)B * cap_s * sizeof(float));
-    const size_t o_xam = take((size_t)B * cap_s * sizeof(int32_t));
-    const size_t o_xva = take((size_t)B * cap_s);
-    const size_t o_xsc = take(match_x3_scratch_bytes(B, cap_s, 8, cap_q));
-    const bool cascade = C == 256 && corr_rows <= MX6_SAMPLED_PANEL;
-    const int csS = mx6_sampled_splits(B);
-    const size_t o_csp = take(cascade ? (size_t)B * MX6_SAMPLED_PANEL * C : 16);
-    const size_t o_csm = take(cascade ? (size_t)B * csS * MX6_SAMPLED_PANEL * sizeof(float) : 16);
-    const size_t o_cs2 = take(cascade ? (size_t)B * csS * MX6_SAMPLED_PANEL * sizeof(float) : 16);
-    const size_t o_csi = take(cascade ? (size_t)B * csS * MX6_SAMPLED_PANEL * sizeof(int32_t) : 16);
-    const size_t o_na0 = take((size_t)B * sizeof(int32_t));
-    const size_t o_gat = take((size_t)B * mx6_panels_per_pair(cap_a) * sizeof(int32_t));
-    w.zero_off = off;
-    const size_t o_pe = take((size_t)B * sizeof(int32_t));
-    const size_t o_nu = take((size_t)B * sizeof(int32_t));
-    const size_t o_nau = take((size_t)B * sizeof(int32_t));
-    const size_t o_nav = take((size_t)B * sizeof(int32_t));
-    const size_t o_nfl = take((size_t)B * sizeof(int32_t));
-    const size_t o_nat = take((size_t)B * sizeof(int32_t));
-    const size_t o_mk = take((size_t)B * cap_a * sizeof(int32_t));
-    w.zero_bytes = off - w.zero_off;
-    w.bytes = off;
-    auto at = [&](size_t o) { return base ? p + o : nullptr; };
-    w.margin = reinterpret_cast<float *>(at(o_mg));
-    w.sid_final = reinterpret_cast<int32_t *>(at(o_sf));
-    w.unc_idx = reinterpret_cast<int32_t *>(at(o_ui));
-    w.state = reinterpret_cast<uint8_t *>(at(o_st));
-    w.sel_rows = reinterpret_cast<int32_t *>(at(o_sr));
-    w.scratch = reinterpret_cast<int32_t *>(at(o_sc));
-    w.n_a_eager = reinterpret_cast<int32_t *>(at(o_ne));
-    w.n_a_lazy = reinterpret_cast<int32_t *>(at(o_nl));
-    w.pair_eager = reinterpret_cast<int32_t *>(at(o_pe));
-    w.n_unc = reinterpret_cast<int32_t *>(at(o_nu));
-    w.ambu_idx = reinterpret_cast<int32_t *>(at(o_au));
-    w.ambv_idx = reinterpret_cast<int32_t *>(at(o_av));
-    w.exact_ws = at(o_ew);
-    w.x3_ah = reinterpret_cast<__half *>(at(o_xah));
-    w.x3_al = reinterpret_cast<__half *>(at(o_xal));
-    w.x3_a_ovf = reinterpret_cast<float *>(at(o_xao));
-    w.x3_md_o = reinterpret_cast<float *>(at(o_xmd));
-    w.x3_am_o = reinterpret_cast<int32_t *>(at(o_xam));
-    w.x3_va_o = reinterpret_cast<uint8_t *>(at(o_xva));
-    w.x3_scratch = at(o_xsc);
-    w.cs_panel = cascade ? reinterpret_cast<uint8_t *>(at(o_csp)) : nullptr;
-    w.cs_max = reinterpret_cast<float *>(at(o_csm));
-    w.cs_m2 = reinterpret_cast<float *>(at(o_cs2));
-    w.cs_i1 = reinterpret_cast<int32_t *>(at(o_csi));
-    w.n_ambv0 = reinterpret_cast<int32_t *>(at(o_na0));
-    w.cs_gate = reinterpret_cast<int32_t *>(at(o_gat));
-    w.n_ambu = reinterpret_cast<int32_t *>(at(o_nau));
-    w.n_ambv = reinterpret_cast<int32_t *>(at(o_nav));
-    w.need_f32_lazy = reinterpret_cast<int32_t *>(at(o_nfl));
-    w.n_amb_total = reinterpret_cast<int32_t *>(at(o_nat));
-    w.mark = reinterpret_cast<int32_t *>(at(o_mk));
-    return w;
-}
-}  // namespace
-
-extern "C" size_t oryon_match_corrs_i8_workspace_bytes(int B, int C, int cap_a, int cap_q, int corr_rows)
-{
-    if (B <= 0 || C <= 0 || cap_a <= 0 || cap_a % MT16 || cap_q <= 0 || corr_rows <= 0) return 0;
-    return carve_lazy(nullptr, B, C, cap_a, cap_q, pick_split16(B, cap_a / MT16), corr_rows).bytes;
-}
-
-// fmt 0: int8 rows (a_scale / q_scale per 16-row slice, q_eps_max per pair).  fmt 1: mx6 rows in a_i8 / q_i8, a_scale = the largest
-// anchor-row error norm per pair [B], q_eps_max = the largest query-row error norm per pair [B], q_scale unused; lazy route only.
-static int match_corrs_lazy_impl(const float *a_hat, const int8_t *a_i8, const float *a_scale, const float *feat_q, int C_true, int HW,
-                                 int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
-                                 const float *q_norm, const int8_t *q_i8, const float *q_scale, const float *q_eps_max, int B, int C,
-                                 int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs,
-                                 int corr_rows, uint64_t seed, const int64_t *pair_key, int force_eager, float *min_dist,
-                                 int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
-                                 int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream, int fmt,
-                                 const void *q_hi_lo = nullptr, const float *q_lo_sq_max = nullptr, const float *feat_a = nullptr,
-                                 const float *a_norm = nullptr);
-
-extern "C" int oryon_match_corrs_i8(const float *a_hat, const int8_t *a_i8, const float *a_scale, const float *feat_q, int C_true, int HW,
-                                    int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
-                                    const float *q_norm, const int8_t *q_i8, const float *q_scale, const float *q_eps_max, int B, int C,
-                                    int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs,
-                                    int corr_rows, uint64_t seed, const int64_t *pair_key, int force_eager, float *min_dist,
-                                    int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
-                                    int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream)
-{
-    ORYON_CHECK_ARG(a_scale && q_scale);
-    return match_corrs_lazy_impl(a_hat, a_i8, a_scale, feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q, roi_stride_q, q_norm, q_i8, q_scale,
-                                 q_eps_max, B, C, cap_a, cap_q, n_a, n_q, threshold, W, max_corrs, corr_rows, seed, pair_key, force_eager, min_dist,
-                                 argmin, valid, corrs, n_valid, n_sel, status, n_undecided, round_f16, workspace, workspace_bytes, stream, 0);
-}
-
-extern "C" int oryon_match_corrs_mx6(const float *a_hat, const uint8_t *a_mx6, const float *a_err_max, const float *feat_q, int C_true, int HW,
-                                     int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
-                                     const float *q_norm, const uint8_t *q_mx6, const float *q_err_max, int B, int C, int cap_a, int cap_q,
-                                     const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs, int corr_rows,
-                                     uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin, uint8_t *valid,
-                                     int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status, int32_t *n_undecided, int round_f16,
-                                     void *workspace, size_t workspace_bytes, void *stream)
-{
-    ORYON_CHECK_ARG(a_err_max && q_err_max);
-    return match_corrs_lazy_impl(a_hat, reinterpret_cast<const int8_t *>(a_mx6), a_err_max, feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q,
-                                 roi_stride_q, q_norm, reinterpret_cast<const int8_t *>(q_mx6), nullptr, q_err_max, B, C, cap_a, cap_q, n_a, n_q,
-                                 threshold, W, max_corrs, corr_rows, seed, pair_key, 0, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
-                                 n_undecided, round_f16, workspace, workspace_bytes, stream, 1);
-}
-
-extern "C" int oryon_match_corrs_mx6_x3(const float *a_hat, const uint8_t *a_mx6, const float *a_err_max, const float *feat_q, int C_true, int HW,
-                                        int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
-                                        const float *q_norm, const uint8_t *q_mx6, const float *q_err_max, const void *q_hi_lo_f16,
-                                        const float *q_lo_sq_max, int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q,
-                                        float threshold, int W, int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key,
-                                        float *min_dist, int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel,
-                                        int32_t *status, int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes,
-                                        void *stream)
-{
-    ORYON_CHECK_ARG(a_err_max && q_err_max && q_hi_lo_f16 && q_lo_sq_max && C == 256);
-    return match_corrs_lazy_impl(a_hat, reinterpret_cast<const int8_t *>(a_mx6), a_err_max, feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q,
-                                 roi_stride_q, q_norm, reinterpret_cast<const int8_t *>(q_mx6), nullptr, q_err_max, B, C, cap_a, cap_q, n_a, n_q,
-                                 threshold, W, max_corrs, corr_rows, seed, pair_key, 0, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
-                                 n_undecided, round_f16, workspace, workspace_bytes, stream, 1, q_hi_lo_f16, q_lo_sq_max);
-}
-
-// ---- the same three entries WITHOUT materialised fp32 anchor rows: feat_a / a_norm (K0's row_norm of the anchor pass) in place of a_hat.
-// The few rows the lazy tail needs are formed on demand (AnchorRaw above).  Lazy route only: the eager tail (force_eager of
-// oryon_match_corrs_i8) reads whole pairs of rows and stays with the materialised ones.
-extern "C" int oryon_match_corrs_i8_araw(const float *feat_a, const float *a_norm, const int8_t *a_i8, const float *a_scale, const float *feat_q,
-                                         int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q,
-                                         int roi_stride_q, const float *q_norm, const int8_t *q_i8, const float *q_scale, const float *q_eps_max,
-                                         int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W,
-                                         int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin,
-                                         uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
-                                         int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream)
-{
-    ORYON_CHECK_ARG(feat_a && a_norm && a_scale && q_scale);
-    return match_corrs_lazy_impl(nullptr, a_i8, a_scale, feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q, roi_stride_q, q_norm, q_i8, q_scale,
-                                 q_eps_max, B, C, cap_a, cap_q, n_a, n_q, threshold, W, max_corrs, corr_rows, seed, pair_key, 0, min_dist, argmin,
-                                 valid, corrs, n_valid, n_sel, status, n_undecided, round_f16, workspace, workspace_bytes, stream, 0, nullptr, nullptr,
-                                 feat_a, a_norm);
-}
-
-extern "C" int oryon_match_corrs_mx6_araw(const float *feat_a, const float *a_norm, const uint8_t *a_mx6, const float *a_err_max,
-                                          const float *feat_q, int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a,
-                                          const int32_t *roi_q, int roi_stride_q, const float *q_norm, const uint8_t *q_mx6, const float *q_err_max,
-                                          int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W,
-                                          int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin,
-                                          uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status, int32_t *n_undecided,
-                                          int round_f16, void *workspace, size_t workspace_bytes, void *stream)
-{
-    ORYON_CHECK_ARG(feat_a && a_norm && a_err_max && q_err_max);
-    return match_corrs_lazy_impl(nullptr, reinterpret_cast<const int8_t *>(a_mx6), a_err_max, feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q,
-                                 roi_stride_q, q_norm, reinterpret_cast<const int8_t *>(q_mx6), nullptr, q_err_max, B, C, cap_a, cap_q, n_a, n_q,
-                                 threshold, W, max_corrs, corr_rows, seed, pair_key, 0, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
-                                 n_undecided, round_f16, workspace, workspace_bytes, stream, 1, nullptr, nullptr, feat_a, a_norm);
-}
-
-extern "C" int oryon_match_corrs_mx6_x3_araw(const float *feat_a, const float *a_norm, const uint8_t *a_mx6, const float *a_err_max,
-                                             const float *feat_q, int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a,
-                                             const int32_t *roi_q, int roi_stride_q, const float *q_norm, const uint8_t *q_mx6,
-                                             const float *q_err_max, const void *q_hi_lo_f16, const float *q_lo_sq_max, int B, int C, int cap_a,
-                                             int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs,
-                                             int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin,
-                                             uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
-                                             int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream)
-{
-    ORYON_CHECK_ARG(feat_a && a_norm && a_err_max && q_err_max && q_hi_lo_f16 && q_lo_sq_max && C == 256);
-    return match_corrs_lazy_impl(nullptr, reinterpret_cast<const int8_t *>(a_mx6), a_err_max, feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q,
-                                 roi_stride_q, q_norm, reinterpret_cast<const int8_t *>(q_mx6), nullptr, q_err_max, B, C, cap_a, cap_q, n_a, n_q,
-                                 threshold, W, max_corrs, corr_rows, seed, pair_key, 0, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
-                                 n_undecided, round_f16, workspace, workspace_bytes, stream, 1, q_hi_lo_f16, q_lo_sq_max, feat_a, a_norm);
-}
-
-static int match_corrs_lazy_impl(const float *a_hat, const int8_t *a_i8, const float *a_scale, const float *feat_q, int C_true, int HW,
-                                 int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
-                                 const float *q_norm, const int8_t *q_i8, const float *q_scale, const float *q_eps_max, int B, int C,
-                                 int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs,
-                                 int corr_rows, uint64_t seed, const int64_t *pair_key, int force_eager, float *min_dist,
-                                 int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
-                                 int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream, int fmt,
-                                 const void *q_hi_lo, const float *q_lo_sq_max, const float *feat_a, const float *a_norm)
-{
-    // a_hat == nullptr (the `_araw` entries): the anchors' fp32 unit rows are formed on demand from feat_a / roi_a / a_norm.  Only the
-    // lazy route can do that: the eager tail reads whole pairs of rows
-    ORYON_CHECK_ARG((a_hat || (feat_a && a_norm && !force_eager)) && a_i8 && a_scale && feat_q && roi_a && roi_q && q_norm && q_i8 && q_eps_max && n_a && n_q);
-    const AnchorRaw araw = {feat_a, roi_a, a_norm, roi_stride_a};
-    ORYON_CHECK_ARG(min_dist && argmin && valid && corrs && n_valid && n_sel && status && !(fmt == 1 && force_eager));
-    ORYON_CHECK_ARG(B >= 0 && (C == 256 || C == 512) && C_true > 0 && C_true <= C && HW > 0 && W > 0 && max_corrs > 0 && corr_rows >= max_corrs);
-    ORYON_CHECK_ARG(layout == ORYON_LAYOUT_NCHW || layout == ORYON_LAYOUT_NHWC);
-    ORYON_CHECK_ARG(cap_a > 0 && cap_a % MT16 == 0 && cap_q > 0 && cap_q % 256 == 0 && threshold > 0.0f && threshold <= 0.5f);
-    if (B == 0) return ORYON_OK;
-    const int T = cap_a / MT16;
-    const int S = pick_split16(B, T);
-    LazyWs lw = carve_lazy(workspace, B, C, cap_a, cap_q, S, corr_rows);
-    if (!workspace || workspace_bytes < lw.bytes) {
-        set_error("oryon_match_corrs_i8: workspace too small (%zu < %zu)", workspace_bytes, lw.bytes);
-        return ORYON_ERR_WORKSPACE;
-    }
-    Screen8RawWs &wr = lw.raw;
-    Screen8Ws &w8 = wr.base;
-    ScreenWs &w = w8.top;
-    hipStream_t st = as_stream(stream);
-    ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(workspace) + w.zero_off, 0, w.zero_bytes, st));
-    if (force_eager) ORYON_CHECK_HIP(hipMemsetAsync(wr.need_f32, 0, (size_t)B * sizeof(int32_t), st));      // only the eager route reads it
-    ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(workspace) + lw.zero_off, 0, lw.zero_bytes, st));
-    const float cut0 = 1.0f - 2.0f * threshold;
-    const float valid_cut16 = cut0 - SCREEN_DELTA - 1e-6f;
-    const int groups = ((B * S + 7) / 8) * 8 * T;
-    // second level for the sampled anchors no screen can separate: fp16x3 two-sweep scan (K1x3, match_x3.hip; C_pad 256) instead of the
-    // exact fp32 scan - same results, hard-descriptor step 9.8 -> 8.5 ms; ~30 us of empty launches per step when no anchor needs it.
-    // ORYON_AMB_X3=0 keeps the exact scan (the tests run both settings).
-    static const bool x3_env = dev_env_int("ORYON_AMB_X3", 1) != 0;
-    const int use_x3 = (x3_env && C == 256 && !force_eager) ? 1 : 0;
-    // validity cascade (round 6): on the route the engine takes once its feedback says "hard" (q_hi_lo given: K0 wrote the hi / lo rows),
-    // the screen stops a panel whose anchors are all valid for sure, and a second, complete pass serves the sampled anchors only
-    static const bool cascade_env = dev_env_int("ORYON_CASCADE", 1) != 0;
-    const bool cascade = cascade_env && fmt == 1 && use_x3 && q_hi_lo != nullptr && lw.cs_panel != nullptr;
-    if (fmt == 1) {
-        const uint8_t *a6 = reinterpret_cast<const uint8_t *>(a_i8), *q6 = reinterpret_cast<const uint8_t *>(q_i8);
-        profile_begin(st, screen_mx6_name(C));
-        if (cascade) {
-            // first pass of the cascade: two tiles per (panel, split) near the panel's own place in the map, then the complete scan for the
-            // panels that still hold an anchor whose validity is open (device-gated: the others return at once)
-            const int T8 = mx6_panels_per_pair(cap_a);
-            launch_screen_mx6(C, groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, w.ws_max, w.ws_i1, w.ws_m2, C_true, 1, nullptr, 2);
-            hipLaunchKernelGGL(match_panel_settle_kernel, dim3(T8, B), dim3(256), 0, st, cap_a, T8, S, n_a, w.ws_max, w.ws_m2, a_scale, q_eps_max,
-                               cut0, lw.cs_gate);
-            launch_screen_mx6(C, groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, w.ws_max, w.ws_i1, w.ws_m2, C_true, 1, lw.cs_gate, 0);
-        } else
-        launch_screen_mx6(C, groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, w.ws_max, w.ws_i1, w.ws_m2, C_true);
-        profile_end(st);
-    } else {
-    profile_begin(st, C == 256 ? screen8_name<256>() : screen8_name<512>());
-    if (C == 256) launch_screen8<256>(groups, st, a_i8, q_i8, q_scale, B, cap_a, cap_q, n_a, n_q, T, S, w.ws_max, w.ws_i1, w.ws_m2);
-    else launch_screen8<512>(groups, st, a_i8, q_i8, q_scale, B, cap_a, cap_q, n_a, n_q, T, S, w.ws_max, w.ws_i1, w.ws_m2);
-    profile_end(st);
-    }
-    ORYON_CHECK_LAUNCH();
-    const float sqrt_c = sqrtf((float)C_true);
-    hipLaunchKernelGGL(match_decide_lite_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, n_a, S, w.ws_max, w.ws_i1, w.ws_m2, a_scale,
-                       q_eps_max, cut0, sqrt_c, (float)C_true, force_eager, fmt, use_x3, w.m_final, lw.sid_final, lw.margin, lw.state, valid, min_dist,
-                       argmin, lw.pair_eager, lw.n_unc, lw.unc_idx, lw.n_ambu, lw.ambu_idx, lw.need_f32_lazy, lw.n_amb_total);
-    hipLaunchKernelGGL(match_mask_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, n_a, lw.pair_eager, lw.n_a_eager, lw.n_a_lazy);
-    ORYON_CHECK_LAUNCH();
-    if (force_eager) {
-    // ---- eager route: the complete tail of oryon_match_screened8_raw for every pair (pair_eager is set only by force_eager since the
-    // ambiguous anchors of lazy pairs are resolved by compacted exact scans), then the sampler on the complete outputs
-    const int32_t *nae = lw.n_a_eager;
-    hipLaunchKernelGGL((match_decide_kernel<128>), dim3(cap_a / 64, B), dim3(256), 0, st, static_cast<const __half *>(nullptr),
-                       static_cast<const __half *>(nullptr), C, cap_a, cap_q, nae, n_q, S, valid_cut16, w.ws_max, w.ws_i1, w.ws_m2, w.m_final,
-                       w.cnt, w.cand, w.n_amb, w.amb_idx, a_scale, nullptr, q_eps_max, cut0, sqrt_c, (float)C_true, a_i8, q_i8, q_scale);
-#define RESCORE_RAW_E(NHWCV)                                                                                                   \
-    hipLaunchKernelGGL((match_rescore_raw_kernel<2, NHWCV>), dim3(cap_a / 128, B), dim3(256), 0, st, a_hat, feat_q, C_true, HW, roi_q,  \
-                       roi_stride_q, q_norm, C, cap_a, cap_q, nae, n_q, threshold, w.m_final, w.cnt, w.cand, min_dist, argmin, valid,    \
-                       w.row_flag, w.panel_flag, wr.need_f32, round_f16)
-    if (layout == ORYON_LAYOUT_NHWC) RESCORE_RAW_E(true); else RESCORE_RAW_E(false);
-#undef RESCORE_RAW_E
-    ORYON_CHECK_LAUNCH();
-    hipLaunchKernelGGL(match_need_f32_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, w.n_amb, wr.need_f32);
-    int rc = gather_q8_launch(feat_q, B, C_true, HW, layout, roi_q, roi_stride_q, n_q, wr.need_f32, cap_q, C, wr.q8_scratch, wr.scale_scratch,
-                              wr.eps_scratch, nullptr, wr.q_hat, 1, round_f16, st);
-    if (rc) { set_error("oryon_match_corrs_i8: fall-back gather launch failed"); return rc; }
-    rc = match_f32_flagged(a_hat, wr.q_hat, B, C, cap_a, cap_q, nae, n_q, threshold, min_dist, argmin, valid, w.panel_flag, w.row_flag, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(match_compact8_kernel, dim3(cap_a / 64, B), dim3(256), 0, st, a_hat, static_cast<const __half *>(nullptr), C, cap_a,
-                       w.n_amb, w.amb_idx, w8.a_hat_c, w.a16c);
-    hipLaunchKernelGGL(match_make_q16_kernel, dim3(64, B), dim3(256), 0, st, wr.q_hat, C, cap_q, n_q, w.n_amb, w8.q16);
-    ORYON_CHECK_LAUNCH();
-    rc = oryon_match_screened(w8.a_hat_c, wr.q_hat, w.a16c, w8.q16, B, C, cap_a, cap_q, w.n_amb, n_q, threshold, w8.md_c, w8.am_c, w8.va_c,
-                              w8.nested, w8.nested_bytes, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(match_scatter8_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, w.n_amb, w.amb_idx, w8.md_c, w8.am_c, w8.va_c,
-                       min_dist, argmin, valid);
-    ORYON_CHECK_LAUNCH();
-    rc = select_corrs_launch(roi_a, roi_q, roi_stride_a, roi_stride_q, n_a, n_q, argmin, valid, cap_a, B, W, max_corrs, corr_rows, seed,
-                             pair_key, lw.scratch, corrs, n_valid, n_sel, status, lw.sel_rows, lw.pair_eager, st);
-    if (rc) { set_error("oryon_match_corrs_i8: select launch failed"); return rc; }
-    if (n_undecided) ORYON_CHECK_HIP(hipMemcpyAsync(n_undecided, w.n_amb, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    return ORYON_OK;
-    }
-    // ---- lazy route.  (1) pairs with ambiguous possibly-valid anchors get their fp32 query rows (device-gated, as on the eager route)
-    int rc = gather_q8_launch(feat_q, B, C_true, HW, layout, roi_q, roi_stride_q, n_q, lw.need_f32_lazy, cap_q, C, wr.q8_scratch, wr.scale_scratch,
-                          wr.eps_scratch, nullptr, wr.q_hat, 1, round_f16, st);
-    if (rc) { set_error("oryon_match_corrs_i8: lazy fp32 gather launch failed"); return rc; }
-    // (2) ambiguous anchors whose VALIDITY is open: exact fp32 scan (K1) of exactly those rows, before the sampling
-    // (the launch geometry of match_compact_f32_kernel; rows from the raw map where K0 wrote none)
-#define COMPACT_A(GRIDX, CAPC, COUNT, IDX, STRIDE)                                                                             \
-    do {                                                                                                                       \
-        if (a_hat)                                                                                                             \
-            hipLaunchKernelGGL(match_compact_f32_kernel, dim3(GRIDX, B), dim3(256), 0, st, a_hat, C, cap_a, CAPC, COUNT, IDX, STRIDE, w8.a_hat_c); \
-        else if (layout == ORYON_LAYOUT_NHWC)                                                                                  \
-            hipLaunchKernelGGL(match_compact_raw_kernel<true>, dim3(GRIDX, B), dim3(256), 0, st, araw, C_true, HW, round_f16, C, cap_a, CAPC,     \
-                               COUNT, IDX, STRIDE, w8.a_hat_c);                                                                \
-        else                                                                                                                   \
-            hipLaunchKernelGGL(match_compact_raw_kernel<false>, dim3(GRIDX, B), dim3(256), 0, st, araw, C_true, HW, round_f16, C, cap_a, CAPC,    \
-                               COUNT, IDX, STRIDE, w8.a_hat_c);                                                                \
-    } while (0)
-    COMPACT_A(cap_a / 64, cap_a, lw.n_ambu, lw.ambu_idx, cap_a);
-    ORYON_CHECK_LAUNCH();
-    rc = oryon_match_f32(w8.a_hat_c, wr.q_hat, B, C, cap_a, cap_q, lw.n_ambu, n_q, threshold, w8.md_c, w8.am_c, w8.va_c, lw.exact_ws,
-                         lw.exact_ws_bytes, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(match_scatter_exact_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, cap_a, lw.n_ambu, lw.ambu_idx, cap_a, w8.md_c,
-                       w8.am_c, w8.va_c, min_dist, argmin, valid, lw.state);
-    ORYON_CHECK_LAUNCH();
-    // (3) unambiguous anchors whose validity is open: exact distance from the winning slice's candidates
-    const size_t lds_res = (size_t)4 * 2 * C * sizeof(float);
-#define RESOLVE_U(NHWCV) RESOLVE_U2(NHWCV, 0)
-#define RESOLVE_U2(NHWCV, FMTV)                                                                                                \
-    hipLaunchKernelGGL((match_resolve_uncertain_kernel<NHWCV, FMTV>), dim3(64, B), dim3(256), lds_res, st, a_hat, araw, a_i8, q_i8, q_scale, a_scale,     \
-                       feat_q, C_true, HW, roi_q, roi_stride_q, q_norm, C, cap_a, cap_q, n_q, threshold, w.m_final, lw.sid_final, lw.margin,   \
-                       lw.n_unc, lw.unc_idx, lw.pair_eager, lw.state, valid, min_dist, argmin, round_f16)
-    if (fmt == 1) { if (layout == ORYON_LAYOUT_NHWC) RESOLVE_U2(true, 1); else RESOLVE_U2(false, 1); }
-    else if (layout == ORYON_LAYOUT_NHWC) RESOLVE_U(true); else RESOLVE_U(false);
-#undef RESOLVE_U
-#undef RESOLVE_U2
-    ORYON_CHECK_LAUNCH();
-    // (4) the sampling, on the exact valid set
-    rc = select_corrs_launch(roi_a, roi_q, roi_stride_a, roi_stride_q, n_a, n_q, argmin, valid, cap_a, B, W, max_corrs, corr_rows, seed,
-                             pair_key, lw.scratch, corrs, n_valid, n_sel, status, lw.sel_rows, lw.pair_eager, st);
-    if (rc) { set_error("oryon_match_corrs_i8: select launch failed"); return rc; }
-    // (5) sampled rows that are ambiguous (valid for sure, argmin open): exact fp32 scan of just those <= max_corrs rows per pair
-    const int cap_s0 = (corr_rows + 127) / 128 * 128;
-    const int cap_s = cap_s0 < cap_a ? cap_s0 : cap_a;           // distinct sampled rows <= min(max_corrs, n_a)
-    hipLaunchKernelGGL(match_list_sampled_amb_kernel, dim3(B), dim3(256), 0, st, cap_a, lw.state, lw.pair_eager, n_sel, lw.sel_rows, corr_rows,
-                       lw.mark, lw.n_ambv, lw.ambv_idx);
-    if (cascade) {
-        // second pass: the complete screen for the listed rows (one 512-row panel per pair), triples merged back, list rebuilt
-        const int csS = mx6_sampled_splits(B);
-        hipLaunchKernelGGL(match_compact_rows_kernel, dim3(MX6_SAMPLED_PANEL / 16, B), dim3(256), 0, st, reinterpret_cast<const uint8_t *>(a_i8), C,
-                           cap_a, MX6_SAMPLED_PANEL, lw.n_ambv, lw.ambv_idx, corr_rows, lw.cs_panel);
-        launch_screen_mx6_sampled(st, lw.cs_panel, reinterpret_cast<const uint8_t *>(q_i8), B, cap_q, lw.n_ambv, n_q, csS, lw.cs_max, lw.cs_i1,
-                                  lw.cs_m2, C_true);
-        hipLaunchKernelGGL(match_decide_sampled_kernel, dim3((MX6_SAMPLED_PANEL + 255) / 256, B), dim3(256), 0, st, cap_a, MX6_SAMPLED_PANEL, csS,
-                           lw.n_ambv, lw.ambv_idx, corr_rows, lw.cs_max, lw.cs_i1, lw.cs_m2, a_scale, q_eps_max, w.m_final, lw.sid_final,
-                           lw.margin, lw.state, lw.mark, lw.n_ambv0);
-        hipLaunchKernelGGL(match_list_sampled_amb_kernel, dim3(B), dim3(256), 0, st, cap_a, lw.state, lw.pair_eager, n_sel, lw.sel_rows, corr_rows,
-                           lw.mark, lw.n_ambv, lw.ambv_idx);
-        ORYON_CHECK_LAUNCH();
-    }
-    COMPACT_A((cap_s + 63) / 64, cap_s, lw.n_ambv, lw.ambv_idx, corr_rows);
-#undef COMPACT_A
-    ORYON_CHECK_LAUNCH();
-    if (use_x3) {
-        // K1x3: hi / lo half query rows into the (now free) fp32-row area, fp16x3 scan with candidate lists, exact chain on the few
-        // candidates; anchors whose lists overflowed (duplicate crowds) fall back to the exact scan on fp32 rows materialised for their pair
-        __half *qh = reinterpret_cast<__half *>(wr.q_hat), *ql = qh + (size_t)B * cap_q * C;
-        int32_t *n_ovf = nullptr, *ovf_idx = nullptr;
-        rc = match_x3_resolve(w8.a_hat_c, lw.n_ambv, cap_s, feat_q, C_true, HW, layout, roi_q, roi_stride_q, q_norm, n_q, B, cap_q, threshold,
-                              round_f16, qh, ql, lw.x3_ah, lw.x3_al, lw.x3_scratch, w8.md_c, w8.am_c, w8.va_c, &n_ovf, &ovf_idx, lw.ambv_idx, corr_rows,
-                              lw.sid_final, cap_a, static_cast<const __half *>(q_hi_lo), q_lo_sq_max, st);
-        if (rc) { set_error("oryon_match_corrs: fp16x3 second-level launch failed"); return rc; }
-        // fp32 query rows for the pairs with overflowed anchors only: the gather's per-map gate reads n_ovf itself
-        rc = gather_q8_launch(feat_q, B, C_true, HW, layout, roi_q, roi_stride_q, n_q, n_ovf, cap_q, C, wr.q8_scratch, wr.scale_scratch,
-                              wr.eps_scratch, nullptr, wr.q_hat, 1, round_f16, st);
-        if (rc) { set_error("oryon_match_corrs: overflow fp32 gather launch failed"); return rc; }
-        hipLaunchKernelGGL(match_compact_f32_kernel, dim3((cap_s + 63) / 64, B), dim3(256), 0, st, w8.a_hat_c, C, cap_s, cap_s, n_ovf, ovf_idx,
-                           cap_s, lw.x3_a_ovf);
-        ORYON_CHECK_LAUNCH();
-        rc = oryon_match_f32(lw.x3_a_ovf, wr.q_hat, B, C, cap_s, cap_q, n_ovf, n_q, threshold, lw.x3_md_o, lw.x3_am_o, lw.x3_va_o, lw.exact_ws,
-                             lw.exact_ws_bytes, stream);
-        if (rc) return rc;
-        match_x3_scatter_ovf(B, cap_s, n_ovf, ovf_idx, lw.x3_md_o, lw.x3_am_o, lw.x3_va_o, w8.md_c, w8.am_c, w8.va_c, st);
-    } else {
-    rc = oryon_match_f32(w8.a_hat_c, wr.q_hat, B, C, cap_s, cap_q, lw.n_ambv, n_q, threshold, w8.md_c, w8.am_c, w8.va_c, lw.exact_ws,
-                         lw.exact_ws_bytes, stream);
-    if (rc) return rc;
-    }
-    hipLaunchKernelGGL(match_scatter_exact_kernel, dim3((cap_s + 255) / 256, B), dim3(256), 0, st, cap_a, cap_s, lw.n_ambv, lw.ambv_idx, corr_rows,
-                       w8.md_c, w8.am_c, w8.va_c, min_dist, argmin, valid, lw.state);
-    ORYON_CHECK_LAUNCH();
-    // (6) query half of every sampled correspondence: resolved rows read their argmin, the others get it from their winning slice
-#define RESOLVE_S(NHWCV) RESOLVE_S2(NHWCV, 0)
-#define RESOLVE_S2(NHWCV, FMTV)                                                                                                \
-    hipLaunchKernelGGL((match_resolve_selected_kernel<NHWCV, FMTV>), dim3((max_corrs + 3) / 4, B), dim3(256), lds_res, st, a_hat, araw, a_i8, q_i8,       \
-                       q_scale, a_scale, feat_q, C_true, HW, roi_q, roi_stride_q, q_norm, C, cap_a, cap_q, n_q, W, w.m_final, lw.sid_final,    \
-                       lw.margin, lw.state, lw.pair_eager, n_sel, lw.sel_rows, corr_rows, min_dist, argmin, corrs, round_f16)
-    if (fmt == 1) { if (layout == ORYON_LAYOUT_NHWC) RESOLVE_S2(true, 1); else RESOLVE_S2(false, 1); }
-    else if (layout == ORYON_LAYOUT_NHWC) RESOLVE_S(true); else RESOLVE_S(false);
-#undef RESOLVE_S
-#undef RESOLVE_S2
-    ORYON_CHECK_LAUNCH();
-    if (n_undecided && cascade) {
-        // cascade: the first pass calls every anchor of a panel that stopped early "ambiguous"; the feedback the engine steers by is that
-        // count scaled by the share of the SAMPLED ambiguous rows which the complete second pass left ambiguous
-        hipLaunchKernelGGL(match_cascade_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, lw.n_amb_total, lw.n_ambv, lw.n_ambv0, n_undecided);
-        ORYON_CHECK_LAUNCH();
-    } else
-    if (n_undecided) {       // anchors the int8 stage could not fully decide: the fp16-stage anchors of eager pairs + the ambiguous anchors of lazy pairs
-        hipLaunchKernelGGL(match_sum_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, w.n_amb, lw.n_amb_total, n_undecided);
-        ORYON_CHECK_LAUNCH();
-    }
-    return ORYON_OK;
+    return raw_fallbacks(m, n_a, w, __func__, __func__);
 }

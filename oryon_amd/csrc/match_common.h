@@ -1,6 +1,8 @@
-// Shared bits of the matcher translation units (match.hip, match16.hip).
+// Shared bits of the matcher translation units (match.hip, match16.hip, match_corrs.hip, screen_mx6.hip, match_x3.hip).
+// Where a comment elsewhere says resolve_anchor of match16.hip (screen_mx6.hip does): it lives in match_corrs.hip with the lazy tail.
 #pragma once
 #include <hip/hip_fp16.h>
+#include <type_traits>
 #include "common.h"
 
 namespace oryon {
@@ -42,5 +44,142 @@ void launch_screen_mx6_sampled(hipStream_t st, const uint8_t *a6_panel, const ui
                                const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true);
 constexpr int MX6_SAMPLED_PANEL = 512;          // rows of that panel (>= the sampled rows of a pair: corr_rows <= 512 on this route)
 inline int mx6_sampled_splits(int B) { int s = (512 + B - 1) / B; return s < 1 ? 1 : s > 16 ? 16 : s; }      // ~512 four-wave workgroups
+
+// ------------------------------------------------------------------------------------------------ workspaces of the screened matchers
+// One allocation, 256-byte aligned buffers, one line per buffer: carve(w.ws_max, B * S * cap_a) assigns the pointer (typed by it) and
+// advances.  The carve_* functions are walked twice with the same code: on a null base every pointer comes out null and only the
+// size (their return value) is of interest.
+struct Carver {
+    char *base;
+    size_t off;
+    explicit Carver(void *b, size_t start = 0) : base(static_cast<char *>(b)), off(start) {}
+    template <class T> void operator()(T *&p, size_t count)             // count elements (bytes for a void pointer)
+    {
+        p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off = (off + count * sizeof(std::conditional_t<std::is_void<T>::value, char, T>) + 255) / 256 * 256;
+    }
+};
+
+constexpr int MT16 = 256;               // anchors per workgroup of the screens (4 waves x 2 blocks of 32)
+
+// K1s (oryon_match_screened).  [zero_off, zero_off + zero_bytes) of the allocation is zeroed at the start of every call
+struct ScreenWs {
+    float *ws_max, *ws_m2, *m_final, *amb_max;
+    int32_t *ws_i1, *cnt, *cand, *panel_flag, *n_amb, *amb_idx;
+    __half *a16c;
+    uint8_t *row_flag;
+    size_t zero_off, zero_bytes;
+};
+// K1s8: + the fp16 fall-back's operands and outputs for the undecided anchors, and the workspace of its nested K1s call
+struct Screen8Ws : ScreenWs {
+    __half *q16;
+    float *a_hat_c, *md_c;
+    int32_t *am_c;
+    uint8_t *va_c;
+    void *nested;
+    size_t nested_bytes;
+};
+// K1s8 on K0v3 operands: + the fp32 query rows (and the scratch of the gather that makes them) of the pairs that need a fall-back
+struct Screen8RawWs : Screen8Ws {
+    float *q_hat, *scale_scratch, *eps_scratch;
+    int8_t *q8_scratch;
+    int32_t *need_f32;
+};
+int pick_split16(int B, int T);         // query splits S of a call with T anchor panels per pair
+size_t carve_screen8_raw(void *base, Screen8RawWs &w, int B, int C, int cap_a, int cap_q, int S);
+
+// gather8.hip: K0v3 on the maps map_enable flags (device-gated)
+int gather_q8_launch(const float *feat, int n_maps, int C, int HW, int layout, const int32_t *roi, int roi_stride, const int32_t *count,
+                     const int32_t *map_enable, int rows_cap, int C_pad, int8_t *out8, float *scale, float *eps, float *norm,
+                     float *out32, int lanes_per_row, int round_f16, hipStream_t st, int fmt = 0, void *aux = nullptr);
+// post.hip: the sampler; sel_rows / pair_eager as the lazy matcher uses them
+int select_corrs_launch(const int32_t *roi_a, const int32_t *roi_q, int roi_stride_a, int roi_stride_q, const int32_t *n_a,
+                        const int32_t *n_q, const int32_t *argmin, const uint8_t *valid, int cap_a, int B, int W, int max_corrs,
+                        int corr_rows, uint64_t seed, const int64_t *pair_key, int32_t *scratch, int32_t *corrs, int32_t *n_valid,
+                        int32_t *n_sel, int32_t *status, int32_t *sel_rows, const int32_t *pair_eager, hipStream_t st);
+
+// ------------------------------------------------------------------------------------------------ host steps of K1s8 (match16.hip)
+// What the steps below read: oryon_match_screened8 and oryon_match_screened8_raw fill one, MatchCorrsArgs extends it.
+struct Screen8Args {
+    const float *a_hat = nullptr;       // fp32 unit rows of the anchors (k-permuted)
+    const int8_t *a_i8 = nullptr;
+    const int8_t *q_i8 = nullptr;
+    const float *a_scale = nullptr;
+    const float *q_scale = nullptr;
+    const float *q_eps_max = nullptr;
+    int B = 0;
+    int C_true = 0;
+    int C = 0;
+    int cap_a = 0;
+    int cap_q = 0;
+    const int32_t *n_q = nullptr;
+    float threshold = 0.0f;
+    // the query rows as K0v3 leaves them (raw map + pixel + norm of every row): rescore_raw_step and raw_fallbacks only
+    const float *feat_q = nullptr;
+    int HW = 0;
+    int layout = 0;
+    const int32_t *roi_q = nullptr;
+    int roi_stride_q = 0;
+    const float *q_norm = nullptr;
+    int round_f16 = 0;
+    // per-anchor outputs
+    float *min_dist = nullptr;
+    int32_t *argmin = nullptr;
+    uint8_t *valid = nullptr;
+    void *stream = nullptr;
+};
+// oryon_match_screened8, oryon_match_screened8_raw and the eager route of the lazy matcher are sequences of these.  The single-launch
+// steps leave the launch check to the caller; the others check with the caller's name (who), so the error texts stay what they were.
+inline int check_launch(const char *who)       // ORYON_CHECK_LAUNCH with a given name in place of __func__
+{
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return ORYON_OK;
+    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
+    return ORYON_ERR_HIP;
+}
+// the int8 screen (between the profile events): per-split (max, slice, runner-up) of every anchor
+void screen8_step(const Screen8Args &m, int S, const int32_t *n_a, const ScreenWs &w);
+// match_decide_kernel on those triples: candidates of the decided anchors, list of the undecided ones
+void decide8_step(const Screen8Args &m, int S, const int32_t *n_a, const ScreenWs &w);
+// exact re-scoring of the candidates from the raw query map, rescore_lanes lanes per anchor
+void rescore_raw_step(const Screen8Args &m, const int32_t *n_a, int rescore_lanes, const Screen8RawWs &w);
+// anchors the int8 stage could not decide: complete fp16 pipeline (K1s) on the compacted set against q_hat, results scattered back
+// (the fp16 operands are made here, and only for pairs that have such anchors: K0 does not write fp16 rows for this path)
+int screen16_fallback(const Screen8Args &m, const float *q_hat, const Screen8Ws &w, const char *who);
+// both fall-backs of the raw route on fp32 query rows materialised for the pairs that need them: overflowed candidate lists
+// (exact scan), then screen16_fallback.  entry: the C entry named in the gather's error text
+int raw_fallbacks(const Screen8Args &m, const int32_t *n_a, const Screen8RawWs &w, const char *who, const char *entry);
+
+// ------------------------------------------------------------------------------------------------ the lazy matcher (match_corrs.hip)
+// What the six oryon_match_corrs_* entries and the engine fill; pointers left null are operands the route does not have.
+// Of Screen8Args: a_i8 / q_i8 hold mx6 slots when fmt == 1; a_scale is per 16-row slice (fmt 0) or the largest anchor-row error norm
+// per pair (fmt 1); q_scale is fmt 0 only; q_eps_max per pair (fmt 1: the largest query-row error norm); a_hat may be null when
+// feat_a + a_norm are given (rows formed on demand, lazy route only).
+struct MatchCorrsArgs : Screen8Args {
+    const float *feat_a = nullptr;      // raw anchor map and K0's anchor norms, in place of a_hat
+    const float *a_norm = nullptr;
+    const int32_t *roi_a = nullptr;     // pixel of every anchor row
+    int roi_stride_a = 0;
+    const void *q_hi_lo = nullptr;      // K0's hi / lo half query rows for the fp16x3 second level (C == 256), with q_lo_sq_max
+    const float *q_lo_sq_max = nullptr;
+    const int32_t *n_a = nullptr;
+    // sampling
+    int W = 0;
+    int max_corrs = 0;
+    int corr_rows = 0;
+    uint64_t seed = 0;
+    const int64_t *pair_key = nullptr;
+    // outputs (n_undecided optional)
+    int32_t *corrs = nullptr;
+    int32_t *n_valid = nullptr;
+    int32_t *n_sel = nullptr;
+    int32_t *status = nullptr;
+    int32_t *n_undecided = nullptr;
+    void *workspace = nullptr;
+    size_t workspace_bytes = 0;
+    int fmt = 0;                        // 0: int8 rows, 1: mx6 rows (lazy route only)
+    int force_eager = 0;                // complete min_dist / argmin arrays from whole fp32 rows (needs a_hat)
+};
+int match_corrs_lazy_impl(const MatchCorrsArgs &m);
 
 }  // namespace oryon

@@ -1,0 +1,1012 @@
+// The lazy matcher: int8 / MX-fp6 screen -> validity of every anchor -> sampled correspondences (oryon_match_corrs_*).
+// Kernels of the tail, its workspace and host sequence, and the C entries.  The screens, K1s and the host steps of K1s8 it is built
+// from are in match16.hip / screen_mx6.hip; the second level in match_x3.hip; the exact scan in match.hip; the sampler in post.hip.
+#include <hip/hip_fp16.h>
+#include "common.h"
+#include "match_common.h"
+
+// ------------------------------------------------------------------------------------------------ lazy tail: K1s8 -> sampled correspondences
+// The batched engine consumes the matcher through oryon_select_corrs only: it needs the VALID FLAG of every anchor and the argmin of the
+// <= max_corrs anchors that get sampled (utils/pcd.py:205-214).  The int8 bound decides validity outright for almost every anchor:
+//     m1 - DELTA8 > 1 - 2 thr   =>  the exact distance is below the threshold   (valid, whatever the argmin)
+//     m1 + DELTA8 < 1 - 2 thr   =>  it is not                                   (as before)
+// so candidate generation (16 int8 rows per anchor) and exact re-scoring (256 strided reads per candidate) are deferred to the sampled
+// anchors - 500 per pair instead of 5000.  Anchors whose validity the bound cannot settle are resolved (exactly) before the sampling;
+// a pair in which a possibly-valid anchor is AMBIGUOUS (runner-up slice within the int8 margin: its argmin needs the fp16 stage) takes
+// the eager route of oryon_match_screened8_raw for all of its anchors.  Outputs are what select(match_screened8_raw(...)) gives,
+// bit for bit: same valid set, same sampled rows (the sampling keys depend on the valid set only), same argmin for every sampled row.
+namespace oryon {
+// INVALID / VALID: settled by the int8 bound.  UNCERTAIN: unambiguous winner slice, validity not settled (resolved from that slice before
+// the sampling).  AMB_VALID: validity settled (valid) but the runner-up slice is within the int8 margin - the exact argmin is computed
+// only if the row gets sampled.  AMB_UNCERTAIN: neither settled - resolved before the sampling.  Both AMB kinds are resolved by the EXACT
+// fp32 scan (K1) on a compacted list of just those anchor rows against the pair's materialised fp32 query rows.
+constexpr uint8_t LZ_INVALID = 0, LZ_VALID = 1, LZ_UNCERTAIN = 2, LZ_AMB_VALID = 3, LZ_RESOLVED = 4, LZ_AMB_UNCERTAIN = 5;
+
+// one THREAD per anchor: merge the per-split (m1, slice, m2) triples and classify
+__global__ __launch_bounds__(256) void match_decide_lite_kernel(
+    int cap_a, const int32_t *__restrict__ n_a, int S, const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
+    const float *__restrict__ ws_m2, const float *__restrict__ a_scale8, const float *__restrict__ eps_q8, float cut0, float sqrt_c,
+    float c_true, int force_eager, int fmt, int x3, float *__restrict__ m_final, int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
+    uint8_t *__restrict__ state, uint8_t *__restrict__ valid, float *__restrict__ min_dist, int32_t *__restrict__ argmin,
+    int32_t *__restrict__ pair_eager, int32_t *__restrict__ n_unc, int32_t *__restrict__ unc_idx, int32_t *__restrict__ n_ambu,
+    int32_t *__restrict__ ambu_idx, int32_t *__restrict__ need_f32_lazy, int32_t *__restrict__ n_amb_total)
+{
+    const int p = blockIdx.y, a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= n_a[p]) return;
+    const size_t arow = (size_t)p * cap_a + a;
+    float m1 = -INFINITY, m2 = -INFINITY;
+    int sid = 0;
+    for (int s = 0; s < S; ++s) {
+        const size_t o = ((size_t)p * S + s) * cap_a + a;
+        const float x1 = ws_m1[o], x2 = ws_m2[o];
+        m2 = fmaxf(fminf(m1, x1), fmaxf(m2, x2));
+        if (x1 > m1) { m1 = x1; sid = ws_i1[o]; }
+    }
+    float delta;
+    if (fmt == 1) {
+        // mx6 screen: scores are dequantised dot products; a_scale8 / eps_q8 hold the pair's largest measured row error |e|_2 of the
+        // anchor / query rows (K0, FMT = 1): |s6 - a^.q^| <= |ea| + |eq| + |ea||eq| + fp32 accumulation slack
+        const float ea = a_scale8[p], eq = eps_q8[p];
+        delta = ea + eq + ea * eq + 1.2e-4f;       // + fp32 accumulation of <= 512 products in the MFMA and in the canonical chain (<= 7e-5)
+    } else {
+        const float sa = a_scale8[(size_t)p * (cap_a / 16) + (a >> 5) * 2 + ((a >> 2) & 1)];
+        m1 *= sa;
+        m2 *= sa;
+        const float ea = 0.50003f * sa, eq = 1.00006f * eps_q8[p];
+        delta = (ea + eq) * sqrt_c + c_true * ea * eq + 4e-5f;
+    }
+    const bool usable = delta < 0.2f;
+    const float margin = usable ? 2.0f * delta + 2e-7f : INFINITY;
+    m_final[arow] = m1;
+    sid_final[arow] = sid;
+    margin_out[arow] = margin;
+    uint8_t st;
+    const bool certain_valid = usable && m1 > cut0 + delta + 1e-5f;
+    if (usable && !(m1 >= cut0 - delta - 1e-6f)) st = LZ_INVALID;
+    else if (!(m1 - m2 > margin)) st = certain_valid ? LZ_AMB_VALID : LZ_AMB_UNCERTAIN;
+    else if (certain_valid) st = LZ_VALID;
+    else st = LZ_UNCERTAIN;
+    state[arow] = st;
+    // provisional outputs: the distance is the screening estimate until (unless) the row is resolved exactly
+    min_dist[arow] = __fmaf_rn(-0.5f, m1, 0.5f);
+    argmin[arow] = 0;
+    valid[arow] = (st == LZ_VALID || st == LZ_AMB_VALID) ? 1 : 0;
+    if (force_eager) { pair_eager[p] = 1; return; }
+    if (st == LZ_UNCERTAIN) unc_idx[(size_t)p * cap_a + atomicAdd(&n_unc[p], 1)] = a;
+    if (st == LZ_AMB_UNCERTAIN) ambu_idx[(size_t)p * cap_a + atomicAdd(&n_ambu[p], 1)] = a;
+    if (st == LZ_AMB_VALID || st == LZ_AMB_UNCERTAIN) {
+        // this pair's fp32 query rows get materialised (device-gated launch) - with the fp16x3 second level (x3) only when an
+        // ambiguous anchor's VALIDITY is open too: the sampled valid ones are then resolved from hi / lo half rows made later
+        if (st == LZ_AMB_UNCERTAIN || !x3) need_f32_lazy[p] = 1;
+        atomicAdd(&n_amb_total[p], 1);
+    }
+}
+
+__global__ void match_mask_counts_kernel(int B, const int32_t *__restrict__ n_a, const int32_t *__restrict__ pair_eager,
+                                         int32_t *__restrict__ n_a_eager, int32_t *__restrict__ n_a_lazy)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= B) return;
+    n_a_eager[p] = pair_eager[p] ? n_a[p] : 0;
+    n_a_lazy[p] = pair_eager[p] ? 0 : n_a[p];
+}
+
+__global__ void match_cascade_counts_kernel(int B, const int32_t *__restrict__ n_amb_total, const int32_t *__restrict__ n_after,
+                                            const int32_t *__restrict__ n_before, int32_t *__restrict__ out)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= B) return;
+    const long long tot = n_amb_total[p], nb = n_before[p], na = n_after[p];
+    out[p] = nb > 0 ? (int32_t)(tot * na / nb) : (int32_t)tot;
+}
+
+__global__ void match_sum_counts_kernel(int B, const int32_t *__restrict__ a, const int32_t *__restrict__ b, int32_t *__restrict__ out)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < B) out[p] = a[p] + b[p];
+}
+
+// fp32 anchor rows of a work list -> dense panels for the exact scan (rows [count, round_up(count, 128)) zero-filled)
+__global__ __launch_bounds__(256) void match_compact_f32_kernel(const float *__restrict__ a_hat, int Cp, int cap_a, int cap_c,
+                                                                 const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
+                                                                 int idx_stride, float *__restrict__ a_c)
+{
+    const int p = blockIdx.y, lane = threadIdx.x & 63;
+    const int n = count[p] < cap_c ? count[p] : cap_c;
+    const int n_fill = (n + 127) / 128 * 128;
+    for (int g = 0; g < 16; ++g) {
+        const int sl = (blockIdx.x * 16 + g) * 4 + (threadIdx.x >> 6);
+        if (sl >= n_fill || sl >= cap_c) break;
+        uint4 *d = reinterpret_cast<uint4 *>(a_c + ((size_t)p * cap_c + sl) * Cp);
+        if (sl >= n) {
+            for (int i = lane; i < Cp / 4; i += 64) d[i] = make_uint4(0, 0, 0, 0);
+            continue;
+        }
+        const uint4 *src = reinterpret_cast<const uint4 *>(a_hat + ((size_t)p * cap_a + idx[(size_t)p * idx_stride + sl]) * Cp);
+        for (int i = lane; i < Cp / 4; i += 64) d[i] = src[i];
+    }
+}
+
+// results of an exact scan on a compacted work list -> the anchors' rows; the rows are marked RESOLVED (argmin / min_dist exact)
+__global__ __launch_bounds__(256) void match_scatter_exact_kernel(int cap_a, int cap_c, const int32_t *__restrict__ count,
+                                                                   const int32_t *__restrict__ idx, int idx_stride,
+                                                                   const float *__restrict__ md_c, const int32_t *__restrict__ am_c,
+                                                                   const uint8_t *__restrict__ va_c, float *__restrict__ min_dist,
+                                                                   int32_t *__restrict__ argmin, uint8_t *__restrict__ valid,
+                                                                   uint8_t *__restrict__ state)
+{
+    const int p = blockIdx.y, sl = blockIdx.x * 256 + threadIdx.x;
+    const int n = count[p] < cap_c ? count[p] : cap_c;
+    if (sl >= n) return;
+    const size_t src = (size_t)p * cap_c + sl, dst = (size_t)p * cap_a + idx[(size_t)p * idx_stride + sl];
+    min_dist[dst] = md_c[src];
+    argmin[dst] = am_c[src];
+    valid[dst] = va_c[src];
+    state[dst] = LZ_RESOLVED;
+}
+
+// the sampled slots whose anchor row is AMB_VALID (argmin still unknown) -> work list for the second level (K1x3 / exact scan).  One
+// workgroup per pair.  The list comes out in ASCENDING anchor-row order, i.e. in image order: neighbouring anchors share a wave of
+// match_x3_scan_kernel, their matches are neighbours in the query map, and the scan can skip the query tiles none of a wave's anchors
+// can match (it is also deterministic; the first version appended in atomic order).
+__global__ __launch_bounds__(256) void match_list_sampled_amb_kernel(int cap_a, const uint8_t *__restrict__ state,
+                                                                      const int32_t *__restrict__ pair_eager, const int32_t *__restrict__ n_sel,
+                                                                      const int32_t *__restrict__ sel_rows, int corr_rows,
+                                                                      int32_t *__restrict__ mark, int32_t *__restrict__ n_list,
+                                                                      int32_t *__restrict__ list)
+{
+    __shared__ int wave_cnt[4];
+    const int p = blockIdx.x;
+    if (pair_eager[p]) return;
+    const int n = n_sel[p], t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // a row drawn several times (sampling with replacement) is marked once
+    for (int s = t; s < n; s += 256) {
+        const int a = sel_rows[(size_t)p * corr_rows + s];
+        if (state[(size_t)p * cap_a + a] == LZ_AMB_VALID) mark[(size_t)p * cap_a + a] = 1;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // ordered compaction in ONE scan: thread t owns the consecutive rows [t R, (t + 1) R), counts its marks, the block scans the 256 counts
+    const int R = (cap_a + 255) / 256;
+    const int32_t *mk = mark + (size_t)p * cap_a;
+    int mine = 0;
+    for (int i = 0; i < R; ++i) {
+        const int a = t * R + i;
+        mine += (a < cap_a && mk[a] != 0) ? 1 : 0;
+    }
+    int incl = mine;                                            // inclusive scan inside the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+    }
+    if (lane == 63) wave_cnt[wave] = incl;
+    __syncthreads();
+    int off0 = incl - mine;
+    for (int w = 0; w < wave; ++w) off0 += wave_cnt[w];
+    for (int i = 0; i < R; ++i) {
+        const int a = t * R + i;
+        if (a < cap_a && mk[a] != 0) list[(size_t)p * corr_rows + off0++] = a;
+    }
+    if (t == 255) n_list[p] = off0;
+}
+
+// ---- validity cascade, second pass (round 6; oryon_match_corrs_mx6_x3).  The first screening pass stops a panel once its anchors are all
+// valid for sure and leaves their runner-up open (match_mx6_screen_w4_kernel<.., EXIT>); the sampled ones among them (the list of
+// match_list_sampled_amb_kernel, <= corr_rows per pair) get the COMPLETE screen here: their operand rows compacted into one panel per pair,
+// the same kernel over all query tiles, and the (m1, slice, m2) triples merged back into the per-anchor arrays - a row whose winner turns
+// out unambiguous becomes LZ_VALID (resolved from its winning slice like any other), the others keep LZ_AMB_VALID with their true winning
+// slice as the second level's seed.
+// after the windowed first launch: is every live anchor of a 1024-row panel valid for sure already (its best score over the splits' windows
+// above match_decide_lite_kernel's line)?  Then gate = 0 and its runner-ups read +inf (no margin: a partial scan rules nothing out);
+// otherwise gate = 1: the gated launch scans everything for this panel and overwrites the triples.
+__global__ __launch_bounds__(256) void match_panel_settle_kernel(int cap_a, int T8, int S, const int32_t *__restrict__ n_a,
+                                                                  const float *__restrict__ ws_m1, float *__restrict__ ws_m2,
+                                                                  const float *__restrict__ a_err, const float *__restrict__ q_err,
+                                                                  float cut0, int32_t *__restrict__ gate)
+{
+    __shared__ int bad;
+    const int p = blockIdx.y, panel = blockIdx.x, t = threadIdx.x;
+    const int na = n_a[p], a0 = panel * 1024;
+    if (a0 >= na) return;
+    if (t == 0) bad = 0;
+    __syncthreads();
+    const float ea = a_err[p], eq = q_err[p];
+    const float delta = ea + eq + ea * eq + 1.2e-4f;
+    const float thr = delta < 0.2f ? cut0 + delta + 2e-5f : INFINITY;      // (match_decide_lite_kernel: m1 > cut0 + delta + 1e-5)
+    int mine = 0;
+    for (int a = a0 + t; a < a0 + 1024 && a < na; a += 256) {
+        float m1 = -INFINITY;
+        for (int s_ = 0; s_ < S; ++s_) m1 = fmaxf(m1, ws_m1[((size_t)p * S + s_) * cap_a + a]);
+        mine |= !(m1 > thr);
+    }
+    if (mine) atomicOr(&bad, 1);
+    __syncthreads();
+    const int open = bad;
+    if (t == 0) gate[p * T8 + panel] = open;
+    if (!open)
+        for (int a = a0 + t; a < a0 + 1024 && a < na; a += 256)
+            for (int s_ = 0; s_ < S; ++s_) ws_m2[((size_t)p * S + s_) * cap_a + a] = INFINITY;
+}
+
+__global__ __launch_bounds__(256) void match_compact_rows_kernel(const uint8_t *__restrict__ rows, int row_bytes, int cap_a, int cap_c,
+                                                                  const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
+                                                                  int idx_stride, uint8_t *__restrict__ out)
+{
+    // 16 lanes per 256-byte row (uint4 each); rows [count, cap_c) are zero rows (exponent byte 0: finite scores nobody reads)
+    const int p = blockIdx.y, sl = blockIdx.x * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
+    if (sl >= cap_c) return;
+    const int n = count[p] < cap_c ? count[p] : cap_c;
+    uint4 *d = reinterpret_cast<uint4 *>(out + ((size_t)p * cap_c + sl) * row_bytes);
+    if (sl >= n) {
+        for (int i = l; i < row_bytes / 16; i += 16) d[i] = make_uint4(0, 0, 0, 0);
+        return;
+    }
+    const uint4 *src = reinterpret_cast<const uint4 *>(rows + ((size_t)p * cap_a + idx[(size_t)p * idx_stride + sl]) * row_bytes);
+    for (int i = l; i < row_bytes / 16; i += 16) d[i] = src[i];
+}
+
+__global__ __launch_bounds__(256) void match_decide_sampled_kernel(int cap_a, int cap_c, int S, const int32_t *__restrict__ count,
+                                                                    const int32_t *__restrict__ idx, int idx_stride,
+                                                                    const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
+                                                                    const float *__restrict__ ws_m2, const float *__restrict__ a_err,
+                                                                    const float *__restrict__ q_err, float *__restrict__ m_final,
+                                                                    int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
+                                                                    uint8_t *__restrict__ state, int32_t *__restrict__ mark,
+                                                                    int32_t *__restrict__ count_before)
+{
+    const int p = blockIdx.y, sl = blockIdx.x * 256 + threadIdx.x;
+    const int n = count[p] < cap_c ? count[p] : cap_c;
+    if (sl == 0) count_before[p] = n;
+    if (sl >= n) return;
+    const int a = idx[(size_t)p * idx_stride + sl];
+    float m1 = -INFINITY, m2 = -INFINITY;
+    int sid = 0;
+    for (int s = 0; s < S; ++s) {
+        const size_t o = ((size_t)p * S + s) * cap_c + sl;
+        const float x1 = ws_m1[o], x2 = ws_m2[o];
+        m2 = fmaxf(fminf(m1, x1), fmaxf(m2, x2));
+        if (x1 > m1) { m1 = x1; sid = ws_i1[o]; }
+    }
+    const float ea = a_err[p], eq = q_err[p];
+    const float delta = ea + eq + ea * eq + 1.2e-4f;                  // match_decide_lite_kernel, fmt 1
+    const float margin = delta < 0.2f ? 2.0f * delta + 2e-7f : INFINITY;
+    const size_t arow = (size_t)p * cap_a + a;
+    m_final[arow] = m1;                                                // the complete scan's maximum (>= the partial one that settled validity)
+    sid_final[arow] = sid;
+    margin_out[arow] = margin;
+    if (m1 - m2 > margin) {                                            // unambiguous after all: no second level for this row
+        state[arow] = LZ_VALID;
+        mark[arow] = 0;
+    }
+}
+
+// Exact resolution of ONE unambiguous anchor by one wave: candidates = rows of the winning 16-row slice within the int8 margin of its
+// maximum (re-scored from the int8 rows, as match_decide_kernel does), then the canonical fp32 chain per candidate on x_k / d read
+// from the raw map (as match_rescore_raw_kernel does).  Returns (distance, first index of the minimum) in lane 0.
+typedef float f32x32r __attribute__((ext_vector_type(32)));
+typedef unsigned u32x6r __attribute__((ext_vector_type(6)));
+
+// dequantised dot product of two mx6 slots (32 channels): codes decoded by the conversion instruction (exact: multiples of 1/8 up to
+// 7.5), 32 exact products summed in fp32 (every partial sum is a multiple of 1/64 below 2^11: exact), times both block exponents
+__device__ __forceinline__ float mx6_block_dot(const uint4 a_lo, const uint4 a_up, const uint4 q_lo, const uint4 q_up)
+{
+    const u32x6r ca = {a_lo.x, a_lo.y, a_lo.z, a_lo.w, a_up.x, a_up.y}, cq = {q_lo.x, q_lo.y, q_lo.z, q_lo.w, q_up.x, q_up.y};
+    const f32x32r fa = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(ca, 1.0f), fq = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(cq, 1.0f);
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) sum = __fmaf_rn(fa[i], fq[i], sum);
+    return sum * ldexpf(1.0f, (int)(a_up.z & 255u) + (int)(q_up.z & 255u) - 254);
+}
+
+// Anchor rows on demand (the `_araw` entries): where K0 wrote no fp32 unit rows (a_hat == nullptr), a consumer forms the row itself from
+// the raw anchor map, exactly as K0 does - x_k at the anchor's pixel (rounded to float16 first under round_f16, zero beyond C_true),
+// divided by the norm K0 left in a_norm: __fdiv_rn(x_k, d), bit for bit the value K0 would have stored.
+struct AnchorRaw {
+    const float *feat_a;        // [B, C_true, HW] (or channels-last), the map K0 gathered the anchors from
+    const int32_t *roi_a;       // [B, roi_stride] pixel of every anchor row
+    const float *a_norm;        // [B, cap_a] K0's row norms
+    int roi_stride;
+};
+
+template <bool NHWC>
+__device__ __forceinline__ float anchor_raw_unit(const float *__restrict__ fa, int pix, float d, int k, int C_true, int HW, int round_f16)
+{
+    float x = 0.0f;
+    if (k < C_true) x = NHWC ? fa[(size_t)pix * C_true + k] : fa[(size_t)k * HW + pix];
+    if (round_f16) x = __half2float(__float2half_rn(x));
+    return __fdiv_rn(x, d);
+}
+
+template <bool NHWC, bool NEED_DIST = true, int FMT = 0>
+__device__ __forceinline__ void resolve_anchor(int p, int a, const float *__restrict__ a_hat, const AnchorRaw &araw, const int8_t *__restrict__ a8,
+                                               const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
+                                               const float *__restrict__ a_scale8, const float *__restrict__ feat_q, int C_true, int HW,
+                                               const int32_t *__restrict__ roi_q, int roi_stride, const float *__restrict__ norm_q,
+                                               int Cp, int cap_a, int cap_q, int nq, float m1, int sid, float margin, float *lds /*[2*Cp]*/,
+                                               int round_f16, float &d_out, int &j_out)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t arow = (size_t)p * cap_a + a;
+    const int half = sid & 1, blk = sid >> 1;
+    const int r = lane >> 2, seg = lane & 3;
+    const int q = blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+    bool hit;
+    if constexpr (FMT == 1) {
+        // mx6 rows: the 16 rows of the winning slice re-scored from the very operands the screen multiplied (software sum: the order of
+        // the additions differs from the MFMA's, inside the bound's slack); candidates = rows within the margin of the SLICE maximum
+        // (every exact minimiser lies in this slice and scores at least max - 2 delta)
+        float s6 = 0.0f;
+        if (q < nq) {
+            const uint4 *ar = reinterpret_cast<const uint4 *>(a8 + arow * Cp) + seg * (Cp / 64);
+            const uint4 *qr = reinterpret_cast<const uint4 *>(q8 + ((size_t)p * cap_q + q) * Cp) + seg * (Cp / 64);
+            for (int b = 0; b < Cp / 128; ++b) s6 += mx6_block_dot(ar[2 * b], ar[2 * b + 1], qr[2 * b], qr[2 * b + 1]);
+        }
+        s6 += __shfl_xor(s6, 1);
+        s6 += __shfl_xor(s6, 2);
+        float mx = (q < nq) ? s6 : -INFINITY;
+        mx = fmaxf(mx, __shfl_xor(mx, 4));
+        mx = fmaxf(mx, __shfl_xor(mx, 8));
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        hit = (seg == 0) && (q < nq) && (s6 >= mx - margin - 4e-5f);
+        (void)m1;
+    } else {
+    const float sa = a_scale8[(size_t)p * (cap_a / 16) + (a >> 5) * 2 + ((a >> 2) & 1)];
+    int idot = 0;
+    if (q < nq) {
+        const uint4 *ar = reinterpret_cast<const uint4 *>(a8 + arow * Cp) + seg * (Cp / 64);
+        const uint4 *qr = reinterpret_cast<const uint4 *>(q8 + ((size_t)p * cap_q + q) * Cp) + seg * (Cp / 64);
+        for (int i0 = 0; i0 < Cp / 64; ++i0) {
+            const uint4 av = ar[i0], qv = qr[i0];
+            idot = __builtin_amdgcn_sdot4((int)av.x, (int)qv.x, idot, false);
+            idot = __builtin_amdgcn_sdot4((int)av.y, (int)qv.y, idot, false);
+            idot = __builtin_amdgcn_sdot4((int)av.z, (int)qv.z, idot, false);
+            idot = __builtin_amdgcn_sdot4((int)av.w, (int)qv.w, idot, false);
+        }
+    }
+    idot += __shfl_xor(idot, 1);
+    idot += __shfl_xor(idot, 2);
+    const float s8 = (float)idot * q_scale8[(size_t)p * (cap_q / 16) + sid] * sa;
+    hit = (seg == 0) && (q < nq) && (s8 >= m1 - margin);
+    }
+    unsigned long long hits = __ballot(hit);
+    if (!NEED_DIST && __popcll(hits) == 1) {
+        // a single row inside the int8 margin IS the argmin (every other row is provably farther): no fp32 work, and none of the 256
+        // scattered 4-byte reads of its raw descriptor (the NCHW gather is what bounds this kernel: one 64-byte sector per channel)
+        j_out = __shfl(q, __ffsll((long long)hits) - 1);
+        d_out = __builtin_nanf("");
+        return;
+    }
+    // anchor row (k-permuted: position 8g + 4h + j holds k = 8g + 2j + h) -> natural order in LDS
+    float *A = lds, *Q = lds + Cp;
+    if (a_hat) {
+        for (int pos = lane; pos < Cp; pos += 64) {
+            const int g = pos >> 3, hh = (pos >> 2) & 1, jj = pos & 3;
+            A[8 * g + 2 * jj + hh] = a_hat[arow * Cp + pos];
+        }
+    } else {
+        // no materialised row: the same values from the raw map (one pass, Cp / 64 independent loads per lane), natural order as they come
+        const float *fa = araw.feat_a + (size_t)p * C_true * HW;
+        const int pix_a = araw.roi_a[(size_t)p * araw.roi_stride + a];
+        const float da = araw.a_norm[arow];
+        for (int k = lane; k < Cp; k += 64) A[k] = anchor_raw_unit<NHWC>(fa, pix_a, da, k, C_true, HW, round_f16);
+    }
+    float d = INFINITY;
+    int j = 0x7fffffff;
+    const float *fq = feat_q + (size_t)p * C_true * HW;
+    while (hits) {
+        const int src = __ffsll((long long)hits) - 1;
+        hits &= hits - 1;
+        const int jj = __shfl(q, src);
+        const int pix = roi_q[(size_t)p * roi_stride + jj];
+        const float dq = norm_q[(size_t)p * cap_q + jj];
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        for (int k = lane; k < Cp; k += 64) {
+            float x = 0.0f;
+            if (k < C_true) x = NHWC ? fq[(size_t)pix * C_true + k] : fq[(size_t)k * HW + pix];
+            if (round_f16) x = __half2float(__float2half_rn(x));
+            Q[k] = __fdiv_rn(x, dq);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        float dot = 0.0f;                               // every lane runs the same chain on broadcast LDS reads
+        for (int k = 0; k < C_true; k += 8) {
+            float av[8], qv[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { av[e] = A[k + e]; qv[e] = Q[k + e]; }
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if (k + e < C_true) dot = __fmaf_rn(av[e], qv[e], dot);
+        }
+        lex_min(d, j, __fmaf_rn(-0.5f, dot, 0.5f), jj);
+    }
+    d_out = d;
+    j_out = j;
+}
+
+// match_compact_f32_kernel for the `_araw` entries: the listed anchors' fp32 unit rows formed from the raw map (anchor_raw_unit) and
+// written in the k-permuted order K0's rows have (position 8g + 4h + j holds k = 8g + 2j + h), which is what K1 / K1x3 read.  One wave
+// per row, one 16-byte store per lane: lane i of a pass owns positions 4i .. 4i + 3 = (g, h) = (i >> 1, i & 1), j = 0 .. 3.
+template <bool NHWC>
+__global__ __launch_bounds__(256) void match_compact_raw_kernel(const AnchorRaw araw, int C_true, int HW, int round_f16, int Cp, int cap_a,
+                                                                 int cap_c, const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
+                                                                 int idx_stride, float *__restrict__ a_c)
+{
+    const int p = blockIdx.y, lane = threadIdx.x & 63;
+    const int n = count[p] < cap_c ? count[p] : cap_c;
+    const int n_fill = (n + 127) / 128 * 128;
+    const float *fa = araw.feat_a + (size_t)p * C_true * HW;
+    for (int g = 0; g < 16; ++g) {
+        const int sl = (blockIdx.x * 16 + g) * 4 + (threadIdx.x >> 6);
+        if (sl >= n_fill || sl >= cap_c) break;
+        float4 *d = reinterpret_cast<float4 *>(a_c + ((size_t)p * cap_c + sl) * Cp);
+        if (sl >= n) {
+            for (int i = lane; i < Cp / 4; i += 64) d[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        const int a = idx[(size_t)p * idx_stride + sl];
+        const int pix = araw.roi_a[(size_t)p * araw.roi_stride + a];
+        const float da = araw.a_norm[(size_t)p * cap_a + a];
+        for (int i = lane; i < Cp / 4; i += 64) {
+            const int k0 = 8 * (i >> 1) + (i & 1);
+            float4 q;
+            q.x = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 0, C_true, HW, round_f16);
+            q.y = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 2, C_true, HW, round_f16);
+            q.z = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 4, C_true, HW, round_f16);
+            q.w = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 6, C_true, HW, round_f16);
+            d[i] = q;
+        }
+    }
+}
+
+// anchors whose VALIDITY the int8 bound could not settle (pairs on the lazy route only): exact distance now, before the sampling
+template <bool NHWC, int FMT = 0>
+__global__ __launch_bounds__(256) void match_resolve_uncertain_kernel(
+    const float *__restrict__ a_hat, const AnchorRaw araw, const int8_t *__restrict__ a8, const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
+    const float *__restrict__ a_scale8, const float *__restrict__ feat_q, int C_true, int HW, const int32_t *__restrict__ roi_q,
+    int roi_stride, const float *__restrict__ norm_q, int Cp, int cap_a, int cap_q, const int32_t *__restrict__ n_q, float thr,
+    const float *__restrict__ m_final, const int32_t *__restrict__ sid_final, const float *__restrict__ margin_in,
+    const int32_t *__restrict__ n_unc, const int32_t *__restrict__ unc_idx, const int32_t *__restrict__ pair_eager,
+    uint8_t *__restrict__ state, uint8_t *__restrict__ valid, float *__restrict__ min_dist, int32_t *__restrict__ argmin, int round_f16)
+{
+    extern __shared__ float lds_res[];
+    const int p = blockIdx.y;
+    if (pair_eager[p]) return;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = n_unc[p];
+    for (int i = blockIdx.x * 4 + wave; i < n; i += gridDim.x * 4) {
+        const int a = unc_idx[(size_t)p * cap_a + i];
+        const size_t arow = (size_t)p * cap_a + a;
+        float d;
+        int j;
+        resolve_anchor<NHWC, true, FMT>(p, a, a_hat, araw, a8, q8, q_scale8, a_scale8, feat_q, C_true, HW, roi_q, roi_stride, norm_q, Cp, cap_a, cap_q, n_q[p],
+                             m_final[arow], sid_final[arow], margin_in[arow], lds_res + wave * 2 * Cp, round_f16, d, j);
+        if (lane == 0) {
+            min_dist[arow] = d;
+            argmin[arow] = j;
+            valid[arow] = (d < thr) ? 1 : 0;
+            state[arow] = LZ_RESOLVED;
+        }
+    }
+}
+
+// the sampled rows of the lazy pairs: exact argmin -> query half of the correspondence
+template <bool NHWC, int FMT = 0>
+__global__ __launch_bounds__(256) void match_resolve_selected_kernel(
+    const float *__restrict__ a_hat, const AnchorRaw araw, const int8_t *__restrict__ a8, const int8_t *__restrict__ q8, const float *__restrict__ q_scale8,
+    const float *__restrict__ a_scale8, const float *__restrict__ feat_q, int C_true, int HW, const int32_t *__restrict__ roi_q,
+    int roi_stride, const float *__restrict__ norm_q, int Cp, int cap_a, int cap_q, const int32_t *__restrict__ n_q, int W,
+    const float *__restrict__ m_final, const int32_t *__restrict__ sid_final, const float *__restrict__ margin_in,
+    const uint8_t *__restrict__ state, const int32_t *__restrict__ pair_eager, const int32_t *__restrict__ n_sel,
+    const int32_t *__restrict__ sel_rows, int corr_rows, float *__restrict__ min_dist, int32_t *__restrict__ argmin,
+    int32_t *__restrict__ corrs, int round_f16)
+{
+    extern __shared__ float lds_res[];
+    const int p = blockIdx.y;
+    if (pair_eager[p]) return;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slot = blockIdx.x * 4 + wave;
+    if (slot >= n_sel[p]) return;
+    const int a = sel_rows[(size_t)p * corr_rows + slot];
+    const size_t arow = (size_t)p * cap_a + a;
+    float d = 0.0f;
+    int j;
+    if (state[arow] == LZ_RESOLVED) {
+        j = argmin[arow];
+    } else {
+        resolve_anchor<NHWC, false, FMT>(p, a, a_hat, araw, a8, q8, q_scale8, a_scale8, feat_q, C_true, HW, roi_q, roi_stride, norm_q, Cp, cap_a, cap_q,
+                                    n_q[p], m_final[arow], sid_final[arow], margin_in[arow], lds_res + wave * 2 * Cp, round_f16, d, j);
+        if (lane == 0) {                                                // same values from every slot that drew this row
+            argmin[arow] = j;
+            if (d == d) min_dist[arow] = d;                             // NaN: single candidate, the distance was never needed
+        }
+    }
+    if (lane == 0) {
+        j = (j < 0 || j >= n_q[p]) ? 0 : j;                            // cannot happen for a row that passed the validity cut
+        const int pq = roi_q[(size_t)p * roi_stride + j];
+        corrs[((size_t)p * corr_rows + slot) * 4 + 2] = pq / W;
+        corrs[((size_t)p * corr_rows + slot) * 4 + 3] = pq % W;
+    }
+}
+}  // namespace oryon
+
+using namespace oryon;
+
+namespace {
+struct LazyWs : Screen8RawWs {
+    float *margin;
+    int32_t *sid_final, *pair_eager, *n_unc, *unc_idx, *n_a_eager, *n_a_lazy, *sel_rows, *scratch;
+    int32_t *n_ambu, *ambu_idx, *n_ambv, *ambv_idx, *need_f32_lazy, *n_amb_total, *mark;
+    void *exact_ws;
+    size_t exact_ws_bytes;
+    // K1x3 (C_pad 256): hi / lo anchor rows, the overflow fall-back's compact rows and outputs, candidate lists
+    __half *x3_ah, *x3_al;
+    float *x3_a_ovf, *x3_md_o;
+    int32_t *x3_am_o;
+    uint8_t *x3_va_o;
+    void *x3_scratch;
+    uint8_t *state;
+    // validity cascade (hard route, C_pad 256): the sampled anchors' mx6 rows as one 512-row panel per pair + the second pass's triples
+    uint8_t *cs_panel;                  // null where the shape has no cascade (C_pad 512, or corr_rows beyond the panel)
+    float *cs_max, *cs_m2;
+    int32_t *cs_i1;
+    int32_t *n_ambv0, *cs_gate;
+    size_t lazy_zero_off, lazy_zero_bytes;      // the second zeroed region (ScreenWs has the first)
+};
+
+// list capacity of the second level: distinct sampled rows <= min(max_corrs, n_a)
+int sampled_cap(int corr_rows, int cap_a)
+{
+    const int cap_s0 = (corr_rows + 127) / 128 * 128;
+    return cap_s0 < cap_a ? cap_s0 : cap_a;
+}
+
+size_t carve_lazy(void *base, LazyWs &w, int B, int C, int cap_a, int cap_q, int S, int corr_rows)
+{
+    Carver carve(base, carve_screen8_raw(base, w, B, C, cap_a, cap_q, S));
+    const size_t rows = (size_t)B * cap_a, pairs = (size_t)B;
+    carve(w.margin, rows);
+    carve(w.sid_final, rows);
+    carve(w.unc_idx, rows);
+    carve(w.state, rows);
+    carve(w.sel_rows, pairs * corr_rows);
+    carve(w.scratch, rows);
+    carve(w.n_a_eager, pairs);
+    carve(w.n_a_lazy, pairs);
+    carve(w.ambu_idx, rows);
+    carve(w.ambv_idx, pairs * corr_rows);
+    const size_t cap_s = sampled_cap(corr_rows, cap_a);
+    const size_t e1 = oryon_match_workspace_bytes(B, cap_a), e2 = oryon_match_workspace_bytes(B, (int)cap_s);
+    w.exact_ws_bytes = e1 > e2 ? e1 : e2;                                  // split-merge scratch of the exact scan (either list capacity)
+    carve(w.exact_ws, w.exact_ws_bytes > 16 ? w.exact_ws_bytes : 16);
+    carve(w.x3_ah, pairs * cap_s * C);
+    carve(w.x3_al, pairs * cap_s * C);
+    carve(w.x3_a_ovf, pairs * cap_s * C);
+    carve(w.x3_md_o, pairs * cap_s);
+    carve(w.x3_am_o, pairs * cap_s);
+    carve(w.x3_va_o, pairs * cap_s);
+    carve(w.x3_scratch, match_x3_scratch_bytes(B, (int)cap_s, 8, cap_q));
+    const bool cascade = C == 256 && corr_rows <= MX6_SAMPLED_PANEL;
+    const size_t triples = cascade ? pairs * mx6_sampled_splits(B) * MX6_SAMPLED_PANEL : 4;      // 16-byte placeholders without it
+    carve(w.cs_panel, cascade ? pairs * MX6_SAMPLED_PANEL * C : 16);
+    if (!cascade) w.cs_panel = nullptr;
+    carve(w.cs_max, triples);
+    carve(w.cs_m2, triples);
+    carve(w.cs_i1, triples);
+    carve(w.n_ambv0, pairs);
+    carve(w.cs_gate, pairs * mx6_panels_per_pair(cap_a));
+    w.lazy_zero_off = carve.off;
+    carve(w.pair_eager, pairs);
+    carve(w.n_unc, pairs);
+    carve(w.n_ambu, pairs);
+    carve(w.n_ambv, pairs);
+    carve(w.need_f32_lazy, pairs);
+    carve(w.n_amb_total, pairs);
+    carve(w.mark, rows);
+    w.lazy_zero_bytes = carve.off - w.lazy_zero_off;
+    return carve.off;
+}
+}  // namespace
+
+extern "C" size_t oryon_match_corrs_i8_workspace_bytes(int B, int C, int cap_a, int cap_q, int corr_rows)
+{
+    if (B <= 0 || C <= 0 || cap_a <= 0 || cap_a % MT16 || cap_q <= 0 || corr_rows <= 0) return 0;
+    LazyWs w;
+    return carve_lazy(nullptr, w, B, C, cap_a, cap_q, pick_split16(B, cap_a / MT16), corr_rows);
+}
+
+namespace {
+constexpr const char *IMPL = "match_corrs_lazy_impl";       // the name launch failures of its two routes are reported under
+
+int select_step(const MatchCorrsArgs &m, const LazyWs &w, hipStream_t st)
+{
+    const int rc = select_corrs_launch(m.roi_a, m.roi_q, m.roi_stride_a, m.roi_stride_q, m.n_a, m.n_q, m.argmin, m.valid, m.cap_a, m.B, m.W,
+                                       m.max_corrs, m.corr_rows, m.seed, m.pair_key, w.scratch, m.corrs, m.n_valid, m.n_sel, m.status,
+                                       w.sel_rows, w.pair_eager, st);
+    if (rc) set_error("oryon_match_corrs_i8: select launch failed");
+    return rc;
+}
+
+// ---- eager route: the complete tail of oryon_match_screened8_raw for every pair (pair_eager is set only by force_eager since the
+// ambiguous anchors of lazy pairs are resolved by compacted exact scans), then the sampler on the complete outputs
+int eager_route(const MatchCorrsArgs &m, const LazyWs &w, int S)
+{
+    decide8_step(m, S, w.n_a_eager, w);
+    rescore_raw_step(m, w.n_a_eager, 2, w);
+    int rc = check_launch(IMPL);
+    if (rc) return rc;
+    if ((rc = raw_fallbacks(m, w.n_a_eager, w, IMPL, "oryon_match_corrs_i8"))) return rc;
+    return select_step(m, w, as_stream(m.stream));
+}
+
+// anchor rows of a work list -> dense fp32 panels in w.a_hat_c (the launch geometry of match_compact_f32_kernel; rows from the raw map
+// where K0 wrote none)
+void compact_anchors(const MatchCorrsArgs &m, const AnchorRaw &araw, const LazyWs &w, hipStream_t st, int cap_c, const int32_t *count,
+                     const int32_t *idx, int idx_stride)
+{
+    const dim3 grid((cap_c + 63) / 64, m.B);
+    if (m.a_hat)
+        hipLaunchKernelGGL(match_compact_f32_kernel, grid, dim3(256), 0, st, m.a_hat, m.C, m.cap_a, cap_c, count, idx, idx_stride, w.a_hat_c);
+    else
+        hipLaunchKernelGGL(m.layout == ORYON_LAYOUT_NHWC ? match_compact_raw_kernel<true> : match_compact_raw_kernel<false>, grid, dim3(256), 0,
+                           st, araw, m.C_true, m.HW, m.round_f16, m.C, m.cap_a, cap_c, count, idx, idx_stride, w.a_hat_c);
+}
+
+int lazy_route(const MatchCorrsArgs &m, const LazyWs &w, hipStream_t st, int use_x3, bool cascade)
+{
+    const int B = m.B, C = m.C, cap_a = m.cap_a, cap_q = m.cap_q, corr_rows = m.corr_rows;
+    const bool nhwc = m.layout == ORYON_LAYOUT_NHWC;
+    const AnchorRaw araw = {m.feat_a, m.roi_a, m.a_norm, m.roi_stride_a};
+    // (1) pairs with ambiguous possibly-valid anchors get their fp32 query rows (device-gated, as on the eager route)
+    int rc = gather_q8_launch(m.feat_q, B, m.C_true, m.HW, m.layout, m.roi_q, m.roi_stride_q, m.n_q, w.need_f32_lazy, cap_q, C, w.q8_scratch,
+                              w.scale_scratch, w.eps_scratch, nullptr, w.q_hat, 1, m.round_f16, st);
+    if (rc) { set_error("oryon_match_corrs_i8: lazy fp32 gather launch failed"); return rc; }
+    // (2) ambiguous anchors whose VALIDITY is open: exact fp32 scan (K1) of exactly those rows, before the sampling
+    compact_anchors(m, araw, w, st, cap_a, w.n_ambu, w.ambu_idx, cap_a);
+    if ((rc = check_launch(IMPL))) return rc;
+    rc = oryon_match_f32(w.a_hat_c, w.q_hat, B, C, cap_a, cap_q, w.n_ambu, m.n_q, m.threshold, w.md_c, w.am_c, w.va_c, w.exact_ws,
+                         w.exact_ws_bytes, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(match_scatter_exact_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, cap_a, w.n_ambu, w.ambu_idx, cap_a, w.md_c,
+                       w.am_c, w.va_c, m.min_dist, m.argmin, m.valid, w.state);
+    if ((rc = check_launch(IMPL))) return rc;
+    // (3) unambiguous anchors whose validity is open: exact distance from the winning slice's candidates
+    const size_t lds_res = (size_t)4 * 2 * C * sizeof(float);
+    auto resolve_uncertain = m.fmt == 1 ? (nhwc ? match_resolve_uncertain_kernel<true, 1> : match_resolve_uncertain_kernel<false, 1>)
+                                        : (nhwc ? match_resolve_uncertain_kernel<true, 0> : match_resolve_uncertain_kernel<false, 0>);
+    hipLaunchKernelGGL(resolve_uncertain, dim3(64, B), dim3(256), lds_res, st, m.a_hat, araw, m.a_i8, m.q_i8, m.q_scale, m.a_scale, m.feat_q,
+                       m.C_true, m.HW, m.roi_q, m.roi_stride_q, m.q_norm, C, cap_a, cap_q, m.n_q, m.threshold, w.m_final, w.sid_final, w.margin,
+                       w.n_unc, w.unc_idx, w.pair_eager, w.state, m.valid, m.min_dist, m.argmin, m.round_f16);
+    if ((rc = check_launch(IMPL))) return rc;
+    // (4) the sampling, on the exact valid set
+    if ((rc = select_step(m, w, st))) return rc;
+    // (5) sampled rows that are ambiguous (valid for sure, argmin open): exact fp32 scan of just those <= max_corrs rows per pair
+    const int cap_s = sampled_cap(corr_rows, cap_a);
+    hipLaunchKernelGGL(match_list_sampled_amb_kernel, dim3(B), dim3(256), 0, st, cap_a, w.state, w.pair_eager, m.n_sel, w.sel_rows, corr_rows,
+                       w.mark, w.n_ambv, w.ambv_idx);
+    if (cascade) {
+        // second pass: the complete screen for the listed rows (one 512-row panel per pair), triples merged back, list rebuilt
+        const int csS = mx6_sampled_splits(B);
+        hipLaunchKernelGGL(match_compact_rows_kernel, dim3(MX6_SAMPLED_PANEL / 16, B), dim3(256), 0, st, reinterpret_cast<const uint8_t *>(m.a_i8),
+                           C, cap_a, MX6_SAMPLED_PANEL, w.n_ambv, w.ambv_idx, corr_rows, w.cs_panel);
+        launch_screen_mx6_sampled(st, w.cs_panel, reinterpret_cast<const uint8_t *>(m.q_i8), B, cap_q, w.n_ambv, m.n_q, csS, w.cs_max, w.cs_i1,
+                                  w.cs_m2, m.C_true);
+        hipLaunchKernelGGL(match_decide_sampled_kernel, dim3((MX6_SAMPLED_PANEL + 255) / 256, B), dim3(256), 0, st, cap_a, MX6_SAMPLED_PANEL, csS,
+                           w.n_ambv, w.ambv_idx, corr_rows, w.cs_max, w.cs_i1, w.cs_m2, m.a_scale, m.q_eps_max, w.m_final, w.sid_final,
+                           w.margin, w.state, w.mark, w.n_ambv0);
+        hipLaunchKernelGGL(match_list_sampled_amb_kernel, dim3(B), dim3(256), 0, st, cap_a, w.state, w.pair_eager, m.n_sel, w.sel_rows,
+                           corr_rows, w.mark, w.n_ambv, w.ambv_idx);
+        if ((rc = check_launch(IMPL))) return rc;
+    }
+    compact_anchors(m, araw, w, st, cap_s, w.n_ambv, w.ambv_idx, corr_rows);
+    if ((rc = check_launch(IMPL))) return rc;
+    if (use_x3) {
+        // K1x3: hi / lo half query rows into the (now free) fp32-row area, fp16x3 scan with candidate lists, exact chain on the few
+        // candidates; anchors whose lists overflowed (duplicate crowds) fall back to the exact scan on fp32 rows materialised for their pair
+        __half *qh = reinterpret_cast<__half *>(w.q_hat), *ql = qh + (size_t)B * cap_q * C;
+        int32_t *n_ovf = nullptr, *ovf_idx = nullptr;
+        rc = match_x3_resolve(w.a_hat_c, w.n_ambv, cap_s, m.feat_q, m.C_true, m.HW, m.layout, m.roi_q, m.roi_stride_q, m.q_norm, m.n_q, B, cap_q,
+                              m.threshold, m.round_f16, qh, ql, w.x3_ah, w.x3_al, w.x3_scratch, w.md_c, w.am_c, w.va_c, &n_ovf, &ovf_idx,
+                              w.ambv_idx, corr_rows, w.sid_final, cap_a, static_cast<const __half *>(m.q_hi_lo), m.q_lo_sq_max, st);
+        if (rc) { set_error("oryon_match_corrs: fp16x3 second-level launch failed"); return rc; }
+        // fp32 query rows for the pairs with overflowed anchors only: the gather's per-map gate reads n_ovf itself
+        rc = gather_q8_launch(m.feat_q, B, m.C_true, m.HW, m.layout, m.roi_q, m.roi_stride_q, m.n_q, n_ovf, cap_q, C, w.q8_scratch,
+                              w.scale_scratch, w.eps_scratch, nullptr, w.q_hat, 1, m.round_f16, st);
+        if (rc) { set_error("oryon_match_corrs: overflow fp32 gather launch failed"); return rc; }
+        hipLaunchKernelGGL(match_compact_f32_kernel, dim3((cap_s + 63) / 64, B), dim3(256), 0, st, w.a_hat_c, C, cap_s, cap_s, n_ovf, ovf_idx,
+                           cap_s, w.x3_a_ovf);
+        if ((rc = check_launch(IMPL))) return rc;
+        rc = oryon_match_f32(w.x3_a_ovf, w.q_hat, B, C, cap_s, cap_q, n_ovf, m.n_q, m.threshold, w.x3_md_o, w.x3_am_o, w.x3_va_o, w.exact_ws,
+                             w.exact_ws_bytes, st);
+        if (rc) return rc;
+        match_x3_scatter_ovf(B, cap_s, n_ovf, ovf_idx, w.x3_md_o, w.x3_am_o, w.x3_va_o, w.md_c, w.am_c, w.va_c, st);
+    } else {
+        rc = oryon_match_f32(w.a_hat_c, w.q_hat, B, C, cap_s, cap_q, w.n_ambv, m.n_q, m.threshold, w.md_c, w.am_c, w.va_c, w.exact_ws,
+                             w.exact_ws_bytes, st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(match_scatter_exact_kernel, dim3((cap_s + 255) / 256, B), dim3(256), 0, st, cap_a, cap_s, w.n_ambv, w.ambv_idx,
+                       corr_rows, w.md_c, w.am_c, w.va_c, m.min_dist, m.argmin, m.valid, w.state);
+    if ((rc = check_launch(IMPL))) return rc;
+    // (6) query half of every sampled correspondence: resolved rows read their argmin, the others get it from their winning slice
+    auto resolve_selected = m.fmt == 1 ? (nhwc ? match_resolve_selected_kernel<true, 1> : match_resolve_selected_kernel<false, 1>)
+                                       : (nhwc ? match_resolve_selected_kernel<true, 0> : match_resolve_selected_kernel<false, 0>);
+    hipLaunchKernelGGL(resolve_selected, dim3((m.max_corrs + 3) / 4, B), dim3(256), lds_res, st, m.a_hat, araw, m.a_i8, m.q_i8, m.q_scale,
+                       m.a_scale, m.feat_q, m.C_true, m.HW, m.roi_q, m.roi_stride_q, m.q_norm, C, cap_a, cap_q, m.n_q, m.W, w.m_final,
+                       w.sid_final, w.margin, w.state, w.pair_eager, m.n_sel, w.sel_rows, corr_rows, m.min_dist, m.argmin, m.corrs,
+                       m.round_f16);
+    if ((rc = check_launch(IMPL))) return rc;
+    if (m.n_undecided && cascade) {
+        // cascade: the first pass calls every anchor of a panel that stopped early "ambiguous"; the feedback the engine steers by is that
+        // count scaled by the share of the SAMPLED ambiguous rows which the complete second pass left ambiguous
+        hipLaunchKernelGGL(match_cascade_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, w.n_amb_total, w.n_ambv, w.n_ambv0,
+                           m.n_undecided);
+        if ((rc = check_launch(IMPL))) return rc;
+    } else if (m.n_undecided) {
+        // anchors the int8 stage could not fully decide: the fp16-stage anchors of eager pairs + the ambiguous anchors of lazy pairs
+        hipLaunchKernelGGL(match_sum_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, w.n_amb, w.n_amb_total, m.n_undecided);
+        if ((rc = check_launch(IMPL))) return rc;
+    }
+    return ORYON_OK;
+}
+}  // namespace
+
+// fmt 0: int8 rows (a_scale / q_scale per 16-row slice, q_eps_max per pair).  fmt 1: mx6 rows in a_i8 / q_i8, a_scale = the largest
+// anchor-row error norm per pair [B], q_eps_max = the largest query-row error norm per pair [B], q_scale unused; lazy route only.
+int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
+{
+    // a_hat == nullptr (the `_araw` entries): the anchors' fp32 unit rows are formed on demand from feat_a / roi_a / a_norm.  Only the
+    // lazy route can do that: the eager tail reads whole pairs of rows
+    ORYON_CHECK_ARG((m.a_hat || (m.feat_a && m.a_norm && !m.force_eager)) && m.a_i8 && m.a_scale && m.feat_q && m.roi_a && m.roi_q && m.q_norm && m.q_i8 && m.q_eps_max && m.n_a && m.n_q);
+    ORYON_CHECK_ARG((m.fmt == 0 || m.fmt == 1) && (m.fmt == 1 || m.q_scale) && !(m.fmt == 1 && m.force_eager));
+    ORYON_CHECK_ARG(!m.q_hi_lo || (m.q_lo_sq_max && m.C == 256));
+    ORYON_CHECK_ARG(m.min_dist && m.argmin && m.valid && m.corrs && m.n_valid && m.n_sel && m.status);
+    ORYON_CHECK_ARG(m.B >= 0 && (m.C == 256 || m.C == 512) && m.C_true > 0 && m.C_true <= m.C && m.HW > 0 && m.W > 0 && m.max_corrs > 0 && m.corr_rows >= m.max_corrs);
+    ORYON_CHECK_ARG(m.layout == ORYON_LAYOUT_NCHW || m.layout == ORYON_LAYOUT_NHWC);
+    ORYON_CHECK_ARG(m.cap_a > 0 && m.cap_a % MT16 == 0 && m.cap_q > 0 && m.cap_q % 256 == 0 && m.threshold > 0.0f && m.threshold <= 0.5f);
+    if (m.B == 0) return ORYON_OK;
+    const int B = m.B, C = m.C, cap_a = m.cap_a, cap_q = m.cap_q;
+    const int T = cap_a / MT16;
+    const int S = pick_split16(B, T);
+    LazyWs w;
+    const size_t need = carve_lazy(m.workspace, w, B, C, cap_a, cap_q, S, m.corr_rows);
+    if (!m.workspace || m.workspace_bytes < need) {
+        set_error("oryon_match_corrs_i8: workspace too small (%zu < %zu)", m.workspace_bytes, need);
+        return ORYON_ERR_WORKSPACE;
+    }
+    hipStream_t st = as_stream(m.stream);
+    ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(m.workspace) + w.zero_off, 0, w.zero_bytes, st));
+    if (m.force_eager) ORYON_CHECK_HIP(hipMemsetAsync(w.need_f32, 0, (size_t)B * sizeof(int32_t), st));     // only the eager route reads it
+    ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(m.workspace) + w.lazy_zero_off, 0, w.lazy_zero_bytes, st));
+    const float cut0 = 1.0f - 2.0f * m.threshold;
+    // second level for the sampled anchors no screen can separate: fp16x3 two-sweep scan (K1x3, match_x3.hip; C_pad 256) instead of the
+    // exact fp32 scan - same results, hard-descriptor step 9.8 -> 8.5 ms; ~30 us of empty launches per step when no anchor needs it.
+    // ORYON_AMB_X3=0 keeps the exact scan (the tests run both settings).
+    static const bool x3_env = dev_env_int("ORYON_AMB_X3", 1) != 0;
+    const int use_x3 = (x3_env && C == 256 && !m.force_eager) ? 1 : 0;
+    // validity cascade (round 6): on the route the engine takes once its feedback says "hard" (q_hi_lo given: K0 wrote the hi / lo rows),
+    // the screen stops a panel whose anchors are all valid for sure, and a second, complete pass serves the sampled anchors only
+    static const bool cascade_env = dev_env_int("ORYON_CASCADE", 1) != 0;
+    const bool cascade = cascade_env && m.fmt == 1 && use_x3 && m.q_hi_lo != nullptr && w.cs_panel != nullptr;
+    if (m.fmt == 1) {
+        const uint8_t *a6 = reinterpret_cast<const uint8_t *>(m.a_i8), *q6 = reinterpret_cast<const uint8_t *>(m.q_i8);
+        const int groups = ((B * S + 7) / 8) * 8 * T;
+        profile_begin(st, screen_mx6_name(C));
+        if (cascade) {
+            // first pass of the cascade: two tiles per (panel, split) near the panel's own place in the map, then the complete scan for the
+            // panels that still hold an anchor whose validity is open (device-gated: the others return at once)
+            const int T8 = mx6_panels_per_pair(cap_a);
+            launch_screen_mx6(C, groups, T, st, a6, q6, B, cap_a, cap_q, m.n_a, m.n_q, S, w.ws_max, w.ws_i1, w.ws_m2, m.C_true, 1, nullptr, 2);
+            hipLaunchKernelGGL(match_panel_settle_kernel, dim3(T8, B), dim3(256), 0, st, cap_a, T8, S, m.n_a, w.ws_max, w.ws_m2, m.a_scale,
+                               m.q_eps_max, cut0, w.cs_gate);
+            launch_screen_mx6(C, groups, T, st, a6, q6, B, cap_a, cap_q, m.n_a, m.n_q, S, w.ws_max, w.ws_i1, w.ws_m2, m.C_true, 1, w.cs_gate, 0);
+        } else {
+            launch_screen_mx6(C, groups, T, st, a6, q6, B, cap_a, cap_q, m.n_a, m.n_q, S, w.ws_max, w.ws_i1, w.ws_m2, m.C_true);
+        }
+        profile_end(st);
+    } else {
+        screen8_step(m, S, m.n_a, w);
+    }
+    ORYON_CHECK_LAUNCH();
+    hipLaunchKernelGGL(match_decide_lite_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, m.n_a, S, w.ws_max, w.ws_i1, w.ws_m2, m.a_scale,
+                       m.q_eps_max, cut0, sqrtf((float)m.C_true), (float)m.C_true, m.force_eager, m.fmt, use_x3, w.m_final, w.sid_final, w.margin,
+                       w.state, m.valid, m.min_dist, m.argmin, w.pair_eager, w.n_unc, w.unc_idx, w.n_ambu, w.ambu_idx, w.need_f32_lazy,
+                       w.n_amb_total);
+    hipLaunchKernelGGL(match_mask_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, m.n_a, w.pair_eager, w.n_a_eager, w.n_a_lazy);
+    ORYON_CHECK_LAUNCH();
+    if (!m.force_eager) return lazy_route(m, w, st, use_x3, cascade);
+    const int rc = eager_route(m, w, S);
+    if (rc) return rc;
+    if (m.n_undecided) ORYON_CHECK_HIP(hipMemcpyAsync(m.n_undecided, w.n_amb, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    return ORYON_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ C entries
+// Each keeps its own argument check, names its operands in a MatchCorrsArgs and calls the one implementation.
+namespace {
+// the arguments all six entries have, under these names and in this order; the operands that differ by entry are set by name there
+MatchCorrsArgs shared_args(const float *feat_q, int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q,
+                           int roi_stride_q, const float *q_norm, int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q,
+                           float threshold, int W, int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist,
+                           int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
+                           int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream)
+{
+    MatchCorrsArgs m;
+    m.feat_q = feat_q;
+    m.C_true = C_true;
+    m.HW = HW;
+    m.layout = layout;
+    m.roi_a = roi_a;
+    m.roi_stride_a = roi_stride_a;
+    m.roi_q = roi_q;
+    m.roi_stride_q = roi_stride_q;
+    m.q_norm = q_norm;
+    m.B = B;
+    m.C = C;
+    m.cap_a = cap_a;
+    m.cap_q = cap_q;
+    m.n_a = n_a;
+    m.n_q = n_q;
+    m.threshold = threshold;
+    m.W = W;
+    m.max_corrs = max_corrs;
+    m.corr_rows = corr_rows;
+    m.seed = seed;
+    m.pair_key = pair_key;
+    m.min_dist = min_dist;
+    m.argmin = argmin;
+    m.valid = valid;
+    m.corrs = corrs;
+    m.n_valid = n_valid;
+    m.n_sel = n_sel;
+    m.status = status;
+    m.n_undecided = n_undecided;
+    m.round_f16 = round_f16;
+    m.workspace = workspace;
+    m.workspace_bytes = workspace_bytes;
+    m.stream = stream;
+    return m;
+}
+}  // namespace
+
+extern "C" int oryon_match_corrs_i8(const float *a_hat, const int8_t *a_i8, const float *a_scale, const float *feat_q, int C_true, int HW,
+                                    int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
+                                    const float *q_norm, const int8_t *q_i8, const float *q_scale, const float *q_eps_max, int B, int C,
+                                    int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs,
+                                    int corr_rows, uint64_t seed, const int64_t *pair_key, int force_eager, float *min_dist,
+                                    int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
+                                    int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ORYON_CHECK_ARG(a_scale && q_scale);
+    MatchCorrsArgs m = shared_args(feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q, roi_stride_q, q_norm, B, C, cap_a, cap_q, n_a, n_q,
+                                   threshold, W, max_corrs, corr_rows, seed, pair_key, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
+                                   n_undecided, round_f16, workspace, workspace_bytes, stream);
+    m.a_hat = a_hat;
+    m.a_i8 = a_i8;
+    m.a_scale = a_scale;
+    m.q_i8 = q_i8;
+    m.q_scale = q_scale;
+    m.q_eps_max = q_eps_max;
+    m.force_eager = force_eager;
+    return match_corrs_lazy_impl(m);
+}
+
+extern "C" int oryon_match_corrs_mx6(const float *a_hat, const uint8_t *a_mx6, const float *a_err_max, const float *feat_q, int C_true, int HW,
+                                     int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
+                                     const float *q_norm, const uint8_t *q_mx6, const float *q_err_max, int B, int C, int cap_a, int cap_q,
+                                     const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs, int corr_rows,
+                                     uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin, uint8_t *valid,
+                                     int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status, int32_t *n_undecided, int round_f16,
+                                     void *workspace, size_t workspace_bytes, void *stream)
+{
+    ORYON_CHECK_ARG(a_err_max && q_err_max);
+    MatchCorrsArgs m = shared_args(feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q, roi_stride_q, q_norm, B, C, cap_a, cap_q, n_a, n_q,
+                                   threshold, W, max_corrs, corr_rows, seed, pair_key, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
+                                   n_undecided, round_f16, workspace, workspace_bytes, stream);
+    m.a_hat = a_hat;
+    m.fmt = 1;
+    m.a_i8 = reinterpret_cast<const int8_t *>(a_mx6);
+    m.a_scale = a_err_max;
+    m.q_i8 = reinterpret_cast<const int8_t *>(q_mx6);
+    m.q_eps_max = q_err_max;
+    return match_corrs_lazy_impl(m);
+}
+
+extern "C" int oryon_match_corrs_mx6_x3(const float *a_hat, const uint8_t *a_mx6, const float *a_err_max, const float *feat_q, int C_true, int HW,
+                                        int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q, int roi_stride_q,
+                                        const float *q_norm, const uint8_t *q_mx6, const float *q_err_max, const void *q_hi_lo_f16,
+                                        const float *q_lo_sq_max, int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q,
+                                        float threshold, int W, int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key,
+                                        float *min_dist, int32_t *argmin, uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel,
+                                        int32_t *status, int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes,
+                                        void *stream)
+{
+    ORYON_CHECK_ARG(a_err_max && q_err_max && q_hi_lo_f16 && q_lo_sq_max && C == 256);
+    MatchCorrsArgs m = shared_args(feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q, roi_stride_q, q_norm, B, C, cap_a, cap_q, n_a, n_q,
+                                   threshold, W, max_corrs, corr_rows, seed, pair_key, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
+                                   n_undecided, round_f16, workspace, workspace_bytes, stream);
+    m.a_hat = a_hat;
+    m.fmt = 1;
+    m.a_i8 = reinterpret_cast<const int8_t *>(a_mx6);
+    m.a_scale = a_err_max;
+    m.q_i8 = reinterpret_cast<const int8_t *>(q_mx6);
+    m.q_eps_max = q_err_max;
+    m.q_hi_lo = q_hi_lo_f16;
+    m.q_lo_sq_max = q_lo_sq_max;
+    return match_corrs_lazy_impl(m);
+}
+
+// ---- the same three entries WITHOUT materialised fp32 anchor rows: feat_a / a_norm (K0's row_norm of the anchor pass) in place of a_hat.
+// The few rows the lazy tail needs are formed on demand (AnchorRaw above).  Lazy route only: the eager tail (force_eager of
+// oryon_match_corrs_i8) reads whole pairs of rows and stays with the materialised ones.
+extern "C" int oryon_match_corrs_i8_araw(const float *feat_a, const float *a_norm, const int8_t *a_i8, const float *a_scale, const float *feat_q,
+                                         int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a, const int32_t *roi_q,
+                                         int roi_stride_q, const float *q_norm, const int8_t *q_i8, const float *q_scale, const float *q_eps_max,
+                                         int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W,
+                                         int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin,
+                                         uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
+                                         int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ORYON_CHECK_ARG(feat_a && a_norm && a_scale && q_scale);
+    MatchCorrsArgs m = shared_args(feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q, roi_stride_q, q_norm, B, C, cap_a, cap_q, n_a, n_q,
+                                   threshold, W, max_corrs, corr_rows, seed, pair_key, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
+                                   n_undecided, round_f16, workspace, workspace_bytes, stream);
+    m.feat_a = feat_a;
+    m.a_norm = a_norm;
+    m.a_i8 = a_i8;
+    m.a_scale = a_scale;
+    m.q_i8 = q_i8;
+    m.q_scale = q_scale;
+    m.q_eps_max = q_eps_max;
+    return match_corrs_lazy_impl(m);
+}
+
+extern "C" int oryon_match_corrs_mx6_araw(const float *feat_a, const float *a_norm, const uint8_t *a_mx6, const float *a_err_max,
+                                          const float *feat_q, int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a,
+                                          const int32_t *roi_q, int roi_stride_q, const float *q_norm, const uint8_t *q_mx6, const float *q_err_max,
+                                          int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W,
+                                          int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin,
+                                          uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status, int32_t *n_undecided,
+                                          int round_f16, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ORYON_CHECK_ARG(feat_a && a_norm && a_err_max && q_err_max);
+    MatchCorrsArgs m = shared_args(feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q, roi_stride_q, q_norm, B, C, cap_a, cap_q, n_a, n_q,
+                                   threshold, W, max_corrs, corr_rows, seed, pair_key, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
+                                   n_undecided, round_f16, workspace, workspace_bytes, stream);
+    m.feat_a = feat_a;
+    m.a_norm = a_norm;
+    m.fmt = 1;
+    m.a_i8 = reinterpret_cast<const int8_t *>(a_mx6);
+    m.a_scale = a_err_max;
+    m.q_i8 = reinterpret_cast<const int8_t *>(q_mx6);
+    m.q_eps_max = q_err_max;
+    return match_corrs_lazy_impl(m);
+}
+
+extern "C" int oryon_match_corrs_mx6_x3_araw(const float *feat_a, const float *a_norm, const uint8_t *a_mx6, const float *a_err_max,
+                                             const float *feat_q, int C_true, int HW, int layout, const int32_t *roi_a, int roi_stride_a,
+                                             const int32_t *roi_q, int roi_stride_q, const float *q_norm, const uint8_t *q_mx6,
+                                             const float *q_err_max, const void *q_hi_lo_f16, const float *q_lo_sq_max, int B, int C, int cap_a,
+                                             int cap_q, const int32_t *n_a, const int32_t *n_q, float threshold, int W, int max_corrs,
+                                             int corr_rows, uint64_t seed, const int64_t *pair_key, float *min_dist, int32_t *argmin,
+                                             uint8_t *valid, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status,
+                                             int32_t *n_undecided, int round_f16, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ORYON_CHECK_ARG(feat_a && a_norm && a_err_max && q_err_max && q_hi_lo_f16 && q_lo_sq_max && C == 256);
+    MatchCorrsArgs m = shared_args(feat_q, C_true, HW, layout, roi_a, roi_stride_a, roi_q, roi_stride_q, q_norm, B, C, cap_a, cap_q, n_a, n_q,
+                                   threshold, W, max_corrs, corr_rows, seed, pair_key, min_dist, argmin, valid, corrs, n_valid, n_sel, status,
+                                   n_undecided, round_f16, workspace, workspace_bytes, stream);
+    m.feat_a = feat_a;
+    m.a_norm = a_norm;
+    m.fmt = 1;
+    m.a_i8 = reinterpret_cast<const int8_t *>(a_mx6);
+    m.a_scale = a_err_max;
+    m.q_i8 = reinterpret_cast<const int8_t *>(q_mx6);
+    m.q_eps_max = q_err_max;
+    m.q_hi_lo = q_hi_lo_f16;
+    m.q_lo_sq_max = q_lo_sq_max;
+    return match_corrs_lazy_impl(m);
+}

@@ -662,7 +662,7 @@ __global__ __launch_bounds__(256, 1) void match_x3_sweep2_kernel(const __half *_
 }
 
 // one wave per compacted anchor: final maximum over the lists of all query splits, stale entries dropped, canonical fp32 chain on the raw
-// map for the rest (as resolve_anchor in match16.hip), result -> md_c / am_c / va_c; overflowed lists -> the pair's overflow list
+// map for the rest (as resolve_anchor in match_corrs.hip), result -> md_c / am_c / va_c; overflowed lists -> the pair's overflow list
 template <bool NHWC>
 __global__ __launch_bounds__(256) void match_x3_rescore_kernel(const float *__restrict__ a_c, int Cp, int cap_s, const int32_t *__restrict__ n_c,
                                                                 const float *__restrict__ feat_q, int C_true, int HW,
@@ -819,10 +819,6 @@ __global__ __launch_bounds__(256) void match_x3_scatter_ovf_kernel(int cap_s, co
     am_c[dst] = am_o[src];
     va_c[dst] = va_o[src];
 }
-
-int gather_q8_launch(const float *feat, int n_maps, int C, int HW, int layout, const int32_t *roi, int roi_stride, const int32_t *count,
-                     const int32_t *map_enable, int rows_cap, int C_pad, int8_t *out8, float *scale, float *eps, float *norm,
-                     float *out32, int lanes_per_row, int round_f16, hipStream_t st, int fmt, void *aux);
 
 // jobs a (split, 64-anchor group) can post: its tiles in chunks of X3_JOB_TILES
 static int x3_jobs_per_owner(int cap_q, int S)

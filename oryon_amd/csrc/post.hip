@@ -64,7 +64,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_corrs_kernel(
     int32_t *__restrict__ n_valid, int32_t *__restrict__ n_sel, int32_t *__restrict__ status,
     int32_t *__restrict__ sel_rows, const int32_t *__restrict__ pair_eager)
 {
-    // sel_rows != NULL (lazy matcher, match16.hip): also record WHICH anchor row fills every slot; for pairs whose argmin column is
+    // sel_rows != NULL (lazy matcher, match_corrs.hip): also record WHICH anchor row fills every slot; for pairs whose argmin column is
     // not materialised yet (pair_eager[p] == 0) the query half of the row is left to match_resolve_selected_kernel
     __shared__ int s_wave[SEL_WAVES];
     __shared__ unsigned s_hist[256];
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256) void sample_first_merge_kernel(int corr_rows, 
     if (threadIdx.x == 0) { n_valid1[p] = n_valid2[p]; n_sel1[p] = n_sel2[p]; status1[p] = status2[p]; }
 }
 
-// internal entry shared with the lazy matcher (match16.hip)
+// internal entry shared with the lazy matcher (match_corrs.hip)
 int select_corrs_launch(const int32_t *roi_a, const int32_t *roi_q, int roi_stride_a, int roi_stride_q, const int32_t *n_a,
                         const int32_t *n_q, const int32_t *argmin, const uint8_t *valid, int cap_a, int B, int W, int max_corrs,
                         int corr_rows, uint64_t seed, const int64_t *pair_key, int32_t *scratch, int32_t *corrs, int32_t *n_valid,

@@ -428,33 +428,6 @@ def gather_mx6(feat: torch.Tensor, roi: torch.Tensor, count: torch.Tensor, rows_
     return out6, err, norm, out32
 
 
-@_on_tensor_device
-def match_corrs_mx6(a_hat, a6, a_err, feat_q, roi_a, roi_q, q_norm, q6, q_err, n_a, n_q, threshold: float, W: int, max_corrs: int,
-                    seed: int, pair_key=None, corr_rows: Optional[int] = None, n_undecided=None, round_f16: bool = False):
-    """oryon_match_corrs_mx6: the lazy matcher + sampler on MX-fp6 operands; same outputs as match_corrs_i8."""
-    dev = _lib.require_gpu(a_hat.device)
-    feat_q, layout = map_layout(feat_q)
-    B, cap_a, Cp = a_hat.shape
-    cap_q = q6.shape[1]
-    C_true, HW = feat_q.shape[1], feat_q.shape[2] * feat_q.shape[3]
-    corr_rows = int(corr_rows or max_corrs)
-    min_dist = torch.empty((B, cap_a), dtype=torch.float32, device=dev)
-    argmin = torch.empty((B, cap_a), dtype=torch.int32, device=dev)
-    valid = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
-    corrs = torch.zeros((B, corr_rows, 4), dtype=torch.int32, device=dev)
-    n_valid = torch.empty((B,), dtype=torch.int32, device=dev)
-    n_sel = torch.empty((B,), dtype=torch.int32, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    wsb = lib().oryon_match_corrs_i8_workspace_bytes(B, Cp, cap_a, cap_q, corr_rows)
-    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
-    check(lib().oryon_match_corrs_mx6(ptr(a_hat), ptr(a6), ptr(a_err), feat_q.data_ptr(), C_true, HW, layout, ptr(roi_a), roi_a.shape[1],
-                                      ptr(roi_q), roi_q.shape[1], ptr(q_norm), ptr(q6), ptr(q_err), B, Cp, cap_a, cap_q, ptr(n_a), ptr(n_q),
-                                      float(threshold), int(W), int(max_corrs), corr_rows, int(seed) & (2**64 - 1), ptr(pair_key),
-                                      ptr(min_dist), ptr(argmin), ptr(valid), ptr(corrs), ptr(n_valid), ptr(n_sel), ptr(status),
-                                      ptr(n_undecided), int(bool(round_f16)), ptr(ws), ws.numel(), stream_ptr(dev)), "oryon_match_corrs_mx6")
-    return corrs, n_valid, n_sel, status, min_dist, argmin, valid
-
-
 import threading
 
 _raw_ws = {}                      # (device, stream) -> cached matcher workspace (holds room for the rarely used fp32 fall-back rows)
@@ -467,6 +440,69 @@ def release_workspaces() -> None:
     with _raw_ws_lock:
         _raw_ws.clear()
 
+
+def _cached_raw_ws(dev, wsb: int):
+    """The cached workspace of the current stream, grown to wsb bytes.  Call with _raw_ws_lock held, and keep it until the launches
+    that use the buffer are issued."""
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _raw_ws.get(key)
+    if ws is None or ws.numel() < wsb:
+        ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
+        _raw_ws[key] = ws
+    return ws
+
+
+def _match_corrs(entry: str, a_hat, feat_a, a_norm, a_rows, a_aux, feat_q, roi_a, roi_q, q_norm, q_rows, q_aux, n_a, n_q, threshold, W,
+                 max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16, force_eager=None, cached_ws=False):
+    """Every oryon_match_corrs_* entry: allocates the outputs and makes the call.  The entries share everything but the operand block
+    between feat_q's geometry and B and the leading anchor rows: a_hat, or (a_hat None) feat_a + a_norm for the `_araw` entries;
+    a_aux / q_aux are the pointer arguments that follow a_rows / q_rows in the C signature (include/oryon_hip.h).  force_eager: the
+    argument only oryon_match_corrs_i8 has (None: the entry has none).  cached_ws: the per-stream workspace under _raw_ws_lock
+    instead of a fresh allocation."""
+    dev = _lib.require_gpu(a_rows.device)
+    feat_q, layout = map_layout(feat_q)
+    if a_hat is None:
+        feat_a, layout_a = map_layout(feat_a)
+        assert layout_a == layout and feat_a.shape[1:] == feat_q.shape[1:], "anchor and query maps share C, H, W and the memory layout"
+        lead = (feat_a.data_ptr(), ptr(a_norm))
+    else:
+        lead = (ptr(a_hat),)
+    B, cap_a, Cp = a_rows.shape
+    cap_q = q_rows.shape[1]
+    C_true, HW = feat_q.shape[1], feat_q.shape[2] * feat_q.shape[3]
+    corr_rows = int(corr_rows or max_corrs)
+    min_dist = torch.empty((B, cap_a), dtype=torch.float32, device=dev)
+    argmin = torch.empty((B, cap_a), dtype=torch.int32, device=dev)
+    valid = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
+    corrs = torch.zeros((B, corr_rows, 4), dtype=torch.int32, device=dev)
+    n_valid = torch.empty((B,), dtype=torch.int32, device=dev)
+    n_sel = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    wsb = lib().oryon_match_corrs_i8_workspace_bytes(B, Cp, cap_a, cap_q, corr_rows)
+    eager = () if force_eager is None else (int(bool(force_eager)),)
+
+    def call(ws):
+        check(getattr(lib(), entry)(*lead, ptr(a_rows), *[ptr(t) for t in a_aux], feat_q.data_ptr(), C_true, HW, layout, ptr(roi_a),
+                                    roi_a.shape[1], ptr(roi_q), roi_q.shape[1], ptr(q_norm), ptr(q_rows), *[ptr(t) for t in q_aux], B, Cp,
+                                    cap_a, cap_q, ptr(n_a), ptr(n_q), float(threshold), int(W), int(max_corrs), corr_rows,
+                                    int(seed) & (2**64 - 1), ptr(pair_key), *eager, ptr(min_dist), ptr(argmin), ptr(valid), ptr(corrs),
+                                    ptr(n_valid), ptr(n_sel), ptr(status), ptr(n_undecided), int(bool(round_f16)), ptr(ws), ws.numel(),
+                                    stream_ptr(dev)), entry)
+
+    if cached_ws:
+        with _raw_ws_lock:
+            call(_cached_raw_ws(dev, wsb))
+    else:
+        call(torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev))
+    return corrs, n_valid, n_sel, status, min_dist, argmin, valid
+
+
+@_on_tensor_device
+def match_corrs_mx6(a_hat, a6, a_err, feat_q, roi_a, roi_q, q_norm, q6, q_err, n_a, n_q, threshold: float, W: int, max_corrs: int,
+                    seed: int, pair_key=None, corr_rows: Optional[int] = None, n_undecided=None, round_f16: bool = False):
+    """oryon_match_corrs_mx6: the lazy matcher + sampler on MX-fp6 operands; same outputs as match_corrs_i8."""
+    return _match_corrs("oryon_match_corrs_mx6", a_hat, None, None, a6, (a_err,), feat_q, roi_a, roi_q, q_norm, q6, (q_err,), n_a, n_q,
+                        threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16)
 
 
 @_on_tensor_device
@@ -485,12 +521,8 @@ def match_screened8_raw(a_hat, a8, a_scale, feat_q, roi_q, q_norm, q8, q_scale, 
     wsb = lib().oryon_match_screened8_raw_workspace_bytes(B, Cp, cap_a, cap_q)
     # the workspace holds room for the (rarely used) fp32 fall-back rows of every pair: cached per (device, stream) instead of
     # being re-requested from the allocator on every call
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
     with _raw_ws_lock:
-        ws = _raw_ws.get(key)
-        if ws is None or ws.numel() < wsb:
-            ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
-            _raw_ws[key] = ws
+        ws = _cached_raw_ws(dev, wsb)
         check(lib().oryon_match_screened8_raw(ptr(a_hat), ptr(a8), ptr(a_scale), feat_q.data_ptr(), C_true, HW, layout, ptr(roi_q),
                                               roi_q.shape[1], ptr(q_norm), ptr(q8), ptr(q_scale), ptr(q_eps), B, Cp, cap_a, cap_q, ptr(n_a),
                                               ptr(n_q), float(threshold), ptr(min_dist), ptr(argmin), ptr(valid), ptr(n_undecided),
@@ -504,70 +536,8 @@ def match_corrs_i8(a_hat, a8, a_scale, feat_q, roi_a, roi_q, q_norm, q8, q_scale
                    round_f16: bool = False):
     """Lazy K1s8 + K1b (oryon_match_corrs_i8): -> (corrs [B,corr_rows,4] i32, n_valid [B], n_sel [B], status [B], min_dist, argmin, valid).
     Same correspondences as select_corrs(match_screened8_raw(...)); min_dist / argmin are exact only on sampled rows unless force_eager."""
-    dev = _lib.require_gpu(a_hat.device)
-    feat_q, layout = map_layout(feat_q)
-    B, cap_a, Cp = a_hat.shape
-    cap_q = q8.shape[1]
-    C_true, HW = feat_q.shape[1], feat_q.shape[2] * feat_q.shape[3]
-    corr_rows = int(corr_rows or max_corrs)
-    min_dist = torch.empty((B, cap_a), dtype=torch.float32, device=dev)
-    argmin = torch.empty((B, cap_a), dtype=torch.int32, device=dev)
-    valid = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
-    corrs = torch.zeros((B, corr_rows, 4), dtype=torch.int32, device=dev)
-    n_valid = torch.empty((B,), dtype=torch.int32, device=dev)
-    n_sel = torch.empty((B,), dtype=torch.int32, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    wsb = lib().oryon_match_corrs_i8_workspace_bytes(B, Cp, cap_a, cap_q, corr_rows)
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    with _raw_ws_lock:
-        ws = _raw_ws.get(key)
-        if ws is None or ws.numel() < wsb:
-            ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
-            _raw_ws[key] = ws
-        return _match_corrs_i8_locked(a_hat, a8, a_scale, feat_q, C_true, HW, layout, roi_a, roi_q, q_norm, q8, q_scale, q_eps, B, Cp, cap_a,
-                                      cap_q, n_a, n_q, threshold, W, max_corrs, corr_rows, seed, pair_key, force_eager, min_dist, argmin, valid,
-                                      corrs, n_valid, n_sel, status, n_undecided, round_f16, ws, dev)
-
-
-def _match_corrs_i8_locked(a_hat, a8, a_scale, feat_q, C_true, HW, layout, roi_a, roi_q, q_norm, q8, q_scale, q_eps, B, Cp, cap_a, cap_q, n_a,
-                           n_q, threshold, W, max_corrs, corr_rows, seed, pair_key, force_eager, min_dist, argmin, valid, corrs, n_valid, n_sel,
-                           status, n_undecided, round_f16, ws, dev):
-    check(lib().oryon_match_corrs_i8(ptr(a_hat), ptr(a8), ptr(a_scale), feat_q.data_ptr(), C_true, HW, layout, ptr(roi_a), roi_a.shape[1],
-                                     ptr(roi_q), roi_q.shape[1], ptr(q_norm), ptr(q8), ptr(q_scale), ptr(q_eps), B, Cp, cap_a, cap_q,
-                                     ptr(n_a), ptr(n_q), float(threshold), int(W), int(max_corrs), corr_rows, int(seed) & (2**64 - 1),
-                                     ptr(pair_key), int(bool(force_eager)), ptr(min_dist), ptr(argmin), ptr(valid), ptr(corrs), ptr(n_valid),
-                                     ptr(n_sel), ptr(status), ptr(n_undecided), int(bool(round_f16)), ptr(ws), ws.numel(), stream_ptr(dev)),
-          "oryon_match_corrs_i8")
-    return corrs, n_valid, n_sel, status, min_dist, argmin, valid
-
-
-def _match_corrs_araw(entry: str, feat_a, a_norm, a_rows, a_aux, feat_q, roi_a, roi_q, q_norm, q_rows, q_aux, n_a, n_q, threshold, W, max_corrs,
-                      seed, pair_key, corr_rows, n_undecided, round_f16):
-    """The three `_araw` entries share everything but the operand block between feat_q's geometry and B: a_aux / q_aux are the pointer
-    arguments that follow a_rows / q_rows in the C signature (include/oryon_hip.h)."""
-    dev = _lib.require_gpu(feat_a.device)
-    feat_a, layout_a = map_layout(feat_a)
-    feat_q, layout = map_layout(feat_q)
-    assert layout_a == layout and feat_a.shape[1:] == feat_q.shape[1:], "anchor and query maps share C, H, W and the memory layout"
-    B, cap_a, Cp = a_rows.shape
-    cap_q = q_rows.shape[1]
-    C_true, HW = feat_q.shape[1], feat_q.shape[2] * feat_q.shape[3]
-    corr_rows = int(corr_rows or max_corrs)
-    min_dist = torch.empty((B, cap_a), dtype=torch.float32, device=dev)
-    argmin = torch.empty((B, cap_a), dtype=torch.int32, device=dev)
-    valid = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
-    corrs = torch.zeros((B, corr_rows, 4), dtype=torch.int32, device=dev)
-    n_valid = torch.empty((B,), dtype=torch.int32, device=dev)
-    n_sel = torch.empty((B,), dtype=torch.int32, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    wsb = lib().oryon_match_corrs_i8_workspace_bytes(B, Cp, cap_a, cap_q, corr_rows)
-    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
-    check(getattr(lib(), entry)(feat_a.data_ptr(), ptr(a_norm), ptr(a_rows), *[ptr(t) for t in a_aux], feat_q.data_ptr(), C_true, HW, layout,
-                                ptr(roi_a), roi_a.shape[1], ptr(roi_q), roi_q.shape[1], ptr(q_norm), ptr(q_rows), *[ptr(t) for t in q_aux],
-                                B, Cp, cap_a, cap_q, ptr(n_a), ptr(n_q), float(threshold), int(W), int(max_corrs), corr_rows,
-                                int(seed) & (2**64 - 1), ptr(pair_key), ptr(min_dist), ptr(argmin), ptr(valid), ptr(corrs), ptr(n_valid),
-                                ptr(n_sel), ptr(status), ptr(n_undecided), int(bool(round_f16)), ptr(ws), ws.numel(), stream_ptr(dev)), entry)
-    return corrs, n_valid, n_sel, status, min_dist, argmin, valid
+    return _match_corrs("oryon_match_corrs_i8", a_hat, None, None, a8, (a_scale,), feat_q, roi_a, roi_q, q_norm, q8, (q_scale, q_eps), n_a, n_q,
+                        threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16, force_eager=force_eager, cached_ws=True)
 
 
 @_on_tensor_device
@@ -575,16 +545,16 @@ def match_corrs_i8_araw(feat_a, a_norm, a8, a_scale, feat_q, roi_a, roi_q, q_nor
                         max_corrs: int, seed: int, pair_key=None, corr_rows: Optional[int] = None, n_undecided=None, round_f16: bool = False):
     """oryon_match_corrs_i8_araw: match_corrs_i8 (lazy route) without materialised fp32 anchor rows - the raw anchor map and K0's anchor
     norms instead of a_hat; same outputs, bit for bit."""
-    return _match_corrs_araw("oryon_match_corrs_i8_araw", feat_a, a_norm, a8, (a_scale,), feat_q, roi_a, roi_q, q_norm, q8, (q_scale, q_eps),
-                             n_a, n_q, threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16)
+    return _match_corrs("oryon_match_corrs_i8_araw", None, feat_a, a_norm, a8, (a_scale,), feat_q, roi_a, roi_q, q_norm, q8, (q_scale, q_eps),
+                        n_a, n_q, threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16)
 
 
 @_on_tensor_device
 def match_corrs_mx6_araw(feat_a, a_norm, a6, a_err, feat_q, roi_a, roi_q, q_norm, q6, q_err, n_a, n_q, threshold: float, W: int, max_corrs: int,
                          seed: int, pair_key=None, corr_rows: Optional[int] = None, n_undecided=None, round_f16: bool = False):
     """oryon_match_corrs_mx6_araw: match_corrs_mx6 without materialised fp32 anchor rows; same outputs, bit for bit."""
-    return _match_corrs_araw("oryon_match_corrs_mx6_araw", feat_a, a_norm, a6, (a_err,), feat_q, roi_a, roi_q, q_norm, q6, (q_err,), n_a, n_q,
-                             threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16)
+    return _match_corrs("oryon_match_corrs_mx6_araw", None, feat_a, a_norm, a6, (a_err,), feat_q, roi_a, roi_q, q_norm, q6, (q_err,), n_a, n_q,
+                        threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16)
 
 
 @_on_tensor_device
@@ -592,8 +562,8 @@ def match_corrs_mx6_x3_araw(feat_a, a_norm, a6, a_err, feat_q, roi_a, roi_q, q_n
                             W: int, max_corrs: int, seed: int, pair_key=None, corr_rows: Optional[int] = None, n_undecided=None,
                             round_f16: bool = False):
     """oryon_match_corrs_mx6_x3_araw: the matcher on K0's hi / lo query rows (oryon_gather_mx6_x3) without materialised fp32 anchor rows."""
-    return _match_corrs_araw("oryon_match_corrs_mx6_x3_araw", feat_a, a_norm, a6, (a_err,), feat_q, roi_a, roi_q, q_norm, q6,
-                             (q_err, q_hi_lo, q_lo_max), n_a, n_q, threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16)
+    return _match_corrs("oryon_match_corrs_mx6_x3_araw", None, feat_a, a_norm, a6, (a_err,), feat_q, roi_a, roi_q, q_norm, q6,
+                        (q_err, q_hi_lo, q_lo_max), n_a, n_q, threshold, W, max_corrs, seed, pair_key, corr_rows, n_undecided, round_f16)
 
 
 @_on_tensor_device

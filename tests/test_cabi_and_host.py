@@ -58,6 +58,30 @@ def test_argument_validation_without_gpu():
     assert L.oryon_conv24_f16x3(None, 1, 80, None, None, 128, 7, 0, None, None) == -1
 
 
+def test_matcher_workspace_sizes_are_the_layout_contract():
+    """The four matcher workspaces nest (K1s inside K1s8 inside K1s8-raw inside the lazy matcher) and callers size their arenas by
+    these entries: the byte counts are pinned to what the library returned before the carving code was rewritten."""
+    from oryon_amd import _lib
+    L = _lib.lib()
+    # (B, C_pad, cap_a, cap_q, corr_rows) -> screened, screened8, screened8_raw, corrs_i8
+    table = {
+        (64, 256, 5120, 50176, 512): (284764416, 2552189440, 6663410688, 7304239360),             # cfg2
+        (64, 256, 5120, 50176, 500): (284764416, 2552189440, 6663410688, 7304233216),
+        (128, 512, 5120, 147456, 512): (881480192, 22438388736, 70761490432, 72145371648),        # cfg4 shard
+        (2, 512, 5120, 147456, 512): (15248128, 353549824, 1108598784, 1131385600),
+        (1, 256, 256, 256, 8): (250624, 896768, 1225216, 3918080),
+        (8, 256, 1024, 36864, 640): (8004096, 175465472, 553027072, 649915648),                   # corr_rows > 512: no cascade panel
+        (64, 256, 1280, 50176, 512): (80038656, 1888867840, 6000089088, 6632806912),
+    }
+    for (B, C, cap_a, cap_q, corr_rows), want in table.items():
+        got = (L.oryon_match_screened_workspace_bytes(B, C, cap_a), L.oryon_match_screened8_workspace_bytes(B, C, cap_a, cap_q),
+               L.oryon_match_screened8_raw_workspace_bytes(B, C, cap_a, cap_q),
+               L.oryon_match_corrs_i8_workspace_bytes(B, C, cap_a, cap_q, corr_rows))
+        assert got == want, ((B, C, cap_a, cap_q, corr_rows), got, want)
+    # shapes the entries reject size to 0
+    assert L.oryon_match_screened_workspace_bytes(64, 256, 5000) == 0 and L.oryon_match_corrs_i8_workspace_bytes(64, 256, 5120, 50176, 0) == 0
+
+
 def test_no_cpu_fallback():
     from oryon_amd import pcd
     from oryon_amd._lib import OryonError
