@@ -399,6 +399,27 @@ int oryon_pointdsc_refine(oryon_pointdsc_t *handle, const float *src, const floa
                           int n_cap, const float *T_in, float *T_out, uint8_t *labels, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * RANSAC pose solver (test.solver = ransac): best_fit_transform_with_RANSAC (utils/geo6d.py:40-120) as pipeline.py:462-466 calls
+ *         it (max_iter = 10000, fix_percent = 0.9999, match_err = 0.001), for B pairs, two kernels, no allocation, no synchronisation.
+ * Hypothesis numbering: hypothesis 0 is best_fit_transform over all n rows; hypothesis k >= 1 is best_fit_transform over the four rows
+ *         of draw k - 1.  Iterations evaluate hypotheses 0 .. max_iter - 1 (the reference makes the last draw and never evaluates it).
+ *         count_k = number of rows with |R a + t - b| <= match_err, classified as float64 classifies them.  If some count_k exceeds
+ *         fix_percent * n (float64 product) the FIRST such k is taken and the result is best_fit_transform over its inliers
+ *         (exited = 1); otherwise the hypothesis of the largest count wins, lowest k on ties, without a refit.  If every count is 0 or
+ *         n < 4 the 3x4 result is zero (T = rows of zeros over 0 0 0 1, as eye(4) with the zero matrix placed in it; winner = -1).
+ * src,tgt [B, n_cap, 3] fp32 metres (n_cap <= 2048; rows >= n[b] are never read); n [B] int32; status_in [B] or NULL: pairs with a
+ *         non-zero status get the identity and pass the status on, exactly as oryon_pointdsc_register does.
+ * sample_idx [B, max_iter, 4] int32, rows in [0, n[b]) (row max_iter - 1 is unused), or NULL = device RNG: row k, column j is
+ *         (rng_u32(seed, key, 3, 4 k + j) * (uint64_t) n) >> 32 with key = pair_key[b] (NULL: b), so results depend on the global pair
+ *         index, never on sharding.
+ * T [B,16] fp32; winner [B] or NULL: the chosen hypothesis, -1 = none; exited [B] or NULL; counts [B, max_iter] or NULL. */
+size_t oryon_ransac_workspace_bytes(int B, int n_cap, int max_iter);
+int oryon_ransac_register(const float *src, const float *tgt, const int32_t *n, int B, int n_cap, int max_iter, double match_err,
+                          double fix_percent, const int32_t *sample_idx, uint64_t seed, const int64_t *pair_key,
+                          const int32_t *status_in, void *workspace, size_t workspace_bytes, float *T, int32_t *winner,
+                          int32_t *exited, int32_t *counts, int32_t *status_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * The whole batched step as ONE call (round 3): what the per-sample loop of FPM_Pipeline.test_step does for every pair of a batch
  * (pipeline.py:313-355: is_detection_valid -> get_featmap_corrs [utils/pcd.py:177-216] -> get_pose [pipeline.py:429-472:
  * scale / validate / lift, get_pointdsc_pose]), for B pairs, enqueued from C++ on streams and events the engine owns, over a
@@ -476,6 +497,15 @@ typedef struct {
                                 own process with oryon_engine_set_stream_roles (oryon_amd.engine.MatchPoseEngine.tune_stream_roles does).
                                 Results never
                                 depend on it */
+    int solver;              /* 0 = PointDSC (default: everything above), 1 = RANSAC: the registration stream calls oryon_ransac_register with
+                                the step's pair_key and cfg.seed instead of oryon_pointdsc_register; oryon_engine_arena_bytes /
+                                oryon_engine_create then accept a NULL PointDSC handle and the arena holds the RANSAC workspace in place of
+                                PointDSC's.  Streams, slots and every other buffer are the same */
+    int ransac_max_iter;     /* solver == 1: 10000 (pipeline.py:463) */
+    float ransac_match_err;  /* 0.001.  The engine passes this float, widened, as oryon_ransac_register's double match_err: 0.001f is
+                                0.0010000000475, not the double 0.001 (a caller that wants the engine's results from the entry point itself
+                                passes the same rounded value; oryon_amd/engine.py does) */
+    float ransac_fix_percent; /* 0.9999, widened the same way */
 } oryon_engine_config_t;
 size_t oryon_engine_config_bytes(void);      /* sizeof(oryon_engine_config_t) in the built library: a binding's mirror of the struct must match */
 size_t oryon_engine_arena_bytes(const oryon_engine_config_t *cfg, const oryon_pointdsc_t *solver);

@@ -22,7 +22,8 @@ class OryonError(RuntimeError):
 class EngineConfig(ctypes.Structure):
     _fields_ = [("B", c_int), ("C", c_int), ("FH", c_int), ("FW", c_int), ("HA", c_int), ("WA", c_int), ("HQ", c_int), ("WQ", c_int),
                 ("layout", c_int), ("dist_th", c_float), ("n_corrs", c_int), ("src_sampling", c_int), ("seed", c_uint64),
-                ("round_f16", c_int), ("n_slots", c_int), ("overlap", c_int), ("gather_sets", c_int), ("reg_streams", c_int), ("reg_lag", c_int), ("screen", c_int), ("sample_first", c_int), ("x3_prefetch", c_int), ("stream_roles", c_int)]
+                ("round_f16", c_int), ("n_slots", c_int), ("overlap", c_int), ("gather_sets", c_int), ("reg_streams", c_int), ("reg_lag", c_int), ("screen", c_int), ("sample_first", c_int), ("x3_prefetch", c_int), ("stream_roles", c_int),
+                ("solver", c_int), ("ransac_max_iter", c_int), ("ransac_match_err", c_float), ("ransac_fix_percent", c_float)]
 
 
 class DecoderWeights(ctypes.Structure):
@@ -146,6 +147,9 @@ _PROTOS = {
     "oryon_pointdsc_finalize": (c_int, [c_void_p, _P]),
     "oryon_pointdsc_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "oryon_pointdsc_register": (c_int, [c_void_p, _P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P, _P, _P, _P]),
+    "oryon_ransac_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "oryon_ransac_register": (c_int, [_P, _P, _P, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, _P, c_uint64, _P, _P, _P, c_size_t,
+                                      _P, _P, _P, _P, _P, _P]),
     "oryon_pointdsc_encode": (c_int, [c_void_p, _P, _P, _P, c_int, c_int, _P, c_size_t, _P, _P, _P]),
     "oryon_pointdsc_seeds": (c_int, [c_void_p, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "oryon_pointdsc_hypotheses": (c_int, [c_void_p, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P, _P,

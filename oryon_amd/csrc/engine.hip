@@ -6,7 +6,7 @@
 //
 //     gather stream G : K0   roi_compact x2 -> roi_subsample -> gather_q8 (queries) -> gather_q8 (anchors)
 //     match  stream M : K1s8 oryon_match_corrs_{i8,mx6}_araw (screen, lazy tail, sampling)  -> K2 oryon_lift_pairs
-//     reg    stream R : K3-K10 oryon_pointdsc_register                                  (one stream per slot)
+//     reg    stream R : K3-K10 oryon_pointdsc_register, or oryon_ransac_register (cfg.solver == 1)   (one stream per slot)
 //
 // on streams and events the engine owns, over a persistent arena carved once (no allocation, no torch object, no Python per
 // launch).  The K0 outputs alternate between two buffer sets and everything a step hands on or hands back (ROI lists, matcher
@@ -136,7 +136,8 @@ int carve_engine(const oryon_engine_config_t &c, const oryon_pointdsc_t *solver,
         if (!w1) return ORYON_ERR_INVALID_ARG;
         if (w1 > L.match_ws_bytes) L.match_ws_bytes = w1;
     }
-    L.pdsc_ws_bytes = oryon_pointdsc_workspace_bytes(solver, c.B, L.n_cap);
+    // the registration workspace of a slot: PointDSC's, or with cfg.solver == 1 the RANSAC solver's in its place
+    L.pdsc_ws_bytes = c.solver == 1 ? oryon_ransac_workspace_bytes(c.B, L.n_cap, c.ransac_max_iter) : oryon_pointdsc_workspace_bytes(solver, c.B, L.n_cap);
     if (!L.match_ws_bytes || !L.pdsc_ws_bytes) return ORYON_ERR_INVALID_ARG;
     size_t off = 0;
     for (int g = 0; g < c.gather_sets; ++g) {
@@ -234,6 +235,7 @@ int check_cfg(const oryon_engine_config_t *c)
     ORYON_CHECK_ARG((size_t)c->C * (size_t)c->FH * (size_t)c->FW * 4u < (1ull << 32));
     ORYON_CHECK_ARG(c->sample_first >= 0 && (c->x3_prefetch == 0 || c->x3_prefetch == 1));
     ORYON_CHECK_ARG(roles_valid(c->stream_roles));
+    ORYON_CHECK_ARG(c->solver == 0 || (c->solver == 1 && c->ransac_max_iter > 0 && c->ransac_match_err >= 0.0f));
     return ORYON_OK;
 }
 }  // namespace
@@ -255,7 +257,7 @@ extern "C" size_t oryon_engine_config_bytes(void) { return sizeof(oryon_engine_c
 
 extern "C" size_t oryon_engine_arena_bytes(const oryon_engine_config_t *cfg, const oryon_pointdsc_t *solver)
 {
-    if (check_cfg(cfg) || !solver) return 0;
+    if (check_cfg(cfg) || (!solver && cfg->solver != 1)) return 0;
     Layout L;
     if (carve_engine(*cfg, solver, nullptr, L)) return 0;
     return L.bytes;
@@ -324,9 +326,10 @@ int assign_roles(oryon_engine *e, int roles)
 extern "C" int oryon_engine_create(oryon_engine_t **handle, const oryon_engine_config_t *cfg, oryon_pointdsc_t *solver, void *arena,
                                    size_t arena_bytes)
 {
-    ORYON_CHECK_ARG(handle && solver && arena);
+    ORYON_CHECK_ARG(handle && arena);
     int rc = check_cfg(cfg);
     if (rc) return rc;
+    ORYON_CHECK_ARG(solver || cfg->solver == 1);
     oryon_engine *e = new (std::nothrow) oryon_engine();
     ORYON_CHECK_ARG(e != nullptr);
     e->cfg = *cfg;
@@ -705,7 +708,11 @@ extern "C" int oryon_engine_submit(oryon_engine_t *e, const float *feat_a, const
     }
     // ---- K3-K10 on the slot's registration stream
     if (timing) ORYON_CHECK_HIP(hipEventRecord(tev[6], sr));
-    if (!(ablate & 4) && (rc = oryon_pointdsc_register(e->solver, b.pcd_a, b.pcd_q, b.n_lift, B, e->L.n_cap, b.status, b.pdsc_ws, e->L.pdsc_ws_bytes,
+    if (c.solver == 1) {
+        if (!(ablate & 4) && (rc = oryon_ransac_register(b.pcd_a, b.pcd_q, b.n_lift, B, e->L.n_cap, c.ransac_max_iter, (double)c.ransac_match_err,
+                                                         (double)c.ransac_fix_percent, nullptr, c.seed, pair_key, b.status, b.pdsc_ws,
+                                                         e->L.pdsc_ws_bytes, b.pose, nullptr, nullptr, nullptr, b.status_out, sr))) return rc;
+    } else if (!(ablate & 4) && (rc = oryon_pointdsc_register(e->solver, b.pcd_a, b.pcd_q, b.n_lift, B, e->L.n_cap, b.status, b.pdsc_ws, e->L.pdsc_ws_bytes,
                                                        b.pose, nullptr, b.status_out, sr))) return rc;
     // the two per-pair counters a caller reads with the pose: copied on the registration stream (which is always ordered after the
     // caller's stream) into the slot's protected block, so that result views of them stay valid for the slot's whole lifetime

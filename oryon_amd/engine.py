@@ -14,7 +14,7 @@ Differences from the drop-in per-sample facade (oryon_amd.pcd / oryon_amd.pointd
 from __future__ import annotations
 
 import ctypes
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -25,6 +25,21 @@ from ._lib import check, lib
 from .pointdsc import PointDSC
 
 PAIR_OK, PAIR_NO_MASK, PAIR_NO_CORR = 0, 1, 2
+SOLVERS = ("pointdsc", "ransac")
+_default_solver = "pointdsc"
+
+
+def set_default_solver(name: str) -> None:
+    """The process-wide default of test.solver: what `MatchPoseConfig()` and `pipeline.default_args()` choose when the caller names no
+    solver ('pointdsc' unless set).  A driver sets it once, before it builds pipelines (run_pose.py --solver does)."""
+    global _default_solver
+    if name not in SOLVERS:
+        raise ValueError(f"Solver {name} not implemented")
+    _default_solver = name
+
+
+def default_solver() -> str:
+    return _default_solver
 
 
 @dataclass
@@ -48,6 +63,27 @@ class MatchPoseConfig:
     # are redone on all of their anchors (device-gated, no host round trip).  Off (0) by default: the default route computes the
     # validity of every one of the <= src_sampling anchors, as the reference does.
     sample_first: int = 0
+    # test.solver: "pointdsc" (K3-K10) or "ransac" (best_fit_transform_with_RANSAC, utils/geo6d.py:75-120, with the arguments of
+    # pipeline.py:463; draws from the device RNG keyed by (seed, pair_key)).  "ransac" needs no PointDSC weights: solver=None is accepted
+    solver: str = field(default_factory=default_solver)
+    ransac_max_iter: int = 10000
+    ransac_match_err: float = 0.001
+    ransac_fix_percent: float = 0.9999
+
+
+def _check_solver(cfg: "MatchPoseConfig", solver) -> bool:
+    """True for the RANSAC solver; a PointDSC model is required by the other one only."""
+    if cfg.solver not in SOLVERS:
+        raise ValueError(f"Solver {cfg.solver} not implemented")
+    if cfg.solver == "pointdsc" and solver is None:
+        raise ValueError("solver='pointdsc' needs a PointDSC model")
+    return cfg.solver == "ransac"
+
+
+def _cfg_sig(cfg: "MatchPoseConfig", overlap: int) -> Tuple:
+    """What a NativeStep bakes into its C engine: a change of any of these rebuilds it."""
+    return (cfg.dist_th, cfg.n_corrs, cfg.src_sampling, cfg.seed, cfg.half_descriptors, overlap, int(cfg.sample_first), cfg.solver,
+            cfg.ransac_max_iter, cfg.ransac_match_err, cfg.ransac_fix_percent)
 
 
 class NativeStep:
@@ -68,7 +104,7 @@ class NativeStep:
         "pcd_a": (torch.float32, lambda g: (g["B"], g["n_cap"], 3)), "pcd_q": (torch.float32, lambda g: (g["B"], g["n_cap"], 3)),
     }
 
-    def __init__(self, solver: PointDSC, cfg: "MatchPoseConfig", key: Tuple, dev: torch.device, overlap: int, n_slots: int = 6,
+    def __init__(self, solver: Optional[PointDSC], cfg: "MatchPoseConfig", key: Tuple, dev: torch.device, overlap: int, n_slots: int = 6,
                  gather_sets: int = 2, reg_streams: int = 2, reg_lag: int = 0, screen: int = 1, x3_prefetch: int = 1,
                  stream_roles: int = 0):
         B, C, FH, FW, HA, WA, HQ, WQ, layout = key
@@ -76,8 +112,11 @@ class NativeStep:
         if overlap >= 2:
             from . import configure
             configure()                 # no-op when the host program configured the process; warns when HIP started with too few queues
-        solver._ensure_handle(dev)
+        ransac = _check_solver(cfg, solver)
+        if not ransac:
+            solver._ensure_handle(dev)
         self._solver = solver                                   # keeps the C handle alive
+        handle = None if ransac else solver._handle
         self.ecfg = _lib.EngineConfig(B=B, C=C, FH=FH, FW=FW, HA=HA, WA=WA, HQ=HQ, WQ=WQ, layout=layout, dist_th=cfg.dist_th,
                                       n_corrs=cfg.n_corrs, src_sampling=int(cfg.src_sampling or 0), seed=int(cfg.seed) & (2**64 - 1),
                                       round_f16=int(cfg.half_descriptors), n_slots=n_slots, overlap=overlap,
@@ -85,15 +124,16 @@ class NativeStep:
                                       reg_lag=reg_lag if overlap else 0, screen=screen,
                                       sample_first=int(cfg.sample_first) if cfg.sample_first and cfg.sample_first > 0 else 0,
                                       x3_prefetch=int(bool(x3_prefetch)) if (C <= 256 and screen == 1) else 0,
-                                      stream_roles=int(stream_roles))
-        self.cfg_sig = (cfg.dist_th, cfg.n_corrs, cfg.src_sampling, cfg.seed, cfg.half_descriptors, overlap, int(cfg.sample_first))
-        need = lib().oryon_engine_arena_bytes(ctypes.byref(self.ecfg), solver._handle)
+                                      stream_roles=int(stream_roles), solver=int(ransac), ransac_max_iter=int(cfg.ransac_max_iter),
+                                      ransac_match_err=float(cfg.ransac_match_err), ransac_fix_percent=float(cfg.ransac_fix_percent))
+        self.cfg_sig = _cfg_sig(cfg, overlap)
+        need = lib().oryon_engine_arena_bytes(ctypes.byref(self.ecfg), handle)
         if need == 0:
             raise _lib.OryonError(f"oryon_engine_arena_bytes: {lib().oryon_last_error().decode()}")
         with torch.cuda.device(dev):
             self.arena = torch.empty((need,), dtype=torch.uint8, device=dev)
             self._h = ctypes.c_void_p()
-            check(lib().oryon_engine_create(ctypes.byref(self._h), ctypes.byref(self.ecfg), solver._handle, self.arena.data_ptr(), need),
+            check(lib().oryon_engine_create(ctypes.byref(self._h), ctypes.byref(self.ecfg), handle, self.arena.data_ptr(), need),
                   "oryon_engine_create")
         ca, cq, cp, nc = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         check(lib().oryon_engine_geometry(self._h, ctypes.byref(ca), ctypes.byref(cq), ctypes.byref(cp), ctypes.byref(nc)))
@@ -197,7 +237,7 @@ class NativeStep:
 
 
 class MatchPoseEngine:
-    def __init__(self, solver: PointDSC, cfg: Optional[MatchPoseConfig] = None, overlap_registration: bool = False,
+    def __init__(self, solver: Optional[PointDSC], cfg: Optional[MatchPoseConfig] = None, overlap_registration: bool = False,
                  overlap_gather: bool = False, native: bool = True, result_views: bool = False):
         """result_views: `finish` leaves the native step's results as views of its slot buffers
         instead of copying pose / status / counts (four tiny tensors) out of the arena: the allocation-free mode of bench.py
@@ -213,6 +253,7 @@ class MatchPoseEngine:
         the next batch overlaps the MFMA-bound screening of the current one."""
         self.solver = solver
         self.cfg = cfg or MatchPoseConfig()
+        _check_solver(self.cfg, solver)
         self.n_cap = ops.round_up(self.cfg.n_corrs, 128)
         self.overlap = overlap_registration
         self.overlap_gather = overlap_gather
@@ -361,6 +402,18 @@ class MatchPoseEngine:
                 finally:
                     self.result_views = views
 
+    def _register(self, pcd_a: Tensor, pcd_q: Tensor, n_lift: Tensor, status: Tensor, pair_key: Tensor, ws_slot: int):
+        """Registration stage of the per-call schedule: the configured solver on the lifted points -> (pose [B,4,4], status [B])."""
+        cfg = self.cfg
+        if cfg.solver == "ransac":
+            # the two thresholds rounded through float32, as oryon_engine_config_t carries them: both schedules are one computation
+            f32 = lambda x: ctypes.c_float(x).value
+            out = ops.ransac_register(pcd_a, pcd_q, n_lift, cfg.ransac_max_iter, f32(cfg.ransac_match_err), f32(cfg.ransac_fix_percent), None,
+                                      cfg.seed, pair_key, status)
+            return out["T"], out["status"]
+        pose, _, status_out = self.solver.register(pcd_a, pcd_q, n_lift, status, ws_slot=ws_slot)
+        return pose, status_out
+
     def _run_native(self, feat_a, feat_q, mask_a, mask_q, depth_a, depth_q, cam_a, cam_q, pair_key, keep, inputs_event, inputs_resident, dev):
         """The step through `oryon_engine_submit`.  Inputs are handed over as they are when they already have the C ABI's types
         (fp32 maps in NCHW or channels_last storage, int32 masks, fp32 depth, fp32 [B,9] intrinsics); anything else is converted on the
@@ -389,7 +442,7 @@ class MatchPoseEngine:
         cam_a, cam_q = as_type(cam_a, torch.float32, (B, 9)), as_type(cam_q, torch.float32, (B, 9))
         key = (B, C, FH, FW, depth_a.shape[1], depth_a.shape[2], depth_q.shape[1], depth_q.shape[2], lay_a)
         overlap = 2 if (self.overlap and self.overlap_gather) else (1 if self.overlap else 0)
-        sig = (cfg.dist_th, cfg.n_corrs, cfg.src_sampling, cfg.seed, cfg.half_descriptors, overlap, int(cfg.sample_first))
+        sig = _cfg_sig(cfg, overlap)
         nat = self._native
         if nat is None or nat.key != key or nat.cfg_sig != sig or nat.dev != dev:
             self._collect_inflight()                  # results still living in the old arena
@@ -571,12 +624,12 @@ class MatchPoseEngine:
                 for t_ in (pcd_a, pcd_q, n_lift, status):
                     t_.record_stream(rs)
                 self._py_mark(6, rs)
-                pose, _, status_out = self.solver.register(pcd_a, pcd_q, n_lift, status, ws_slot=slot)
+                pose, status_out = self._register(pcd_a, pcd_q, n_lift, status, pair_key, slot)
                 self._py_mark(7, rs)
                 done = torch.cuda.Event()
                 done.record(rs)
         else:
-            pose, _, status_out = self.solver.register(pcd_a, pcd_q, n_lift, status)
+            pose, status_out = self._register(pcd_a, pcd_q, n_lift, status, pair_key, 0)
             done = None
         out = dict(pose=pose, status=status_out, n_valid=n_valid, n_lifted=n_lift)
         if done is not None:

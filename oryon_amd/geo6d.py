@@ -1,0 +1,79 @@
+"""Drop-in counterpart of the used half of the reference's utils/geo6d.py (lines 40-120): `best_fit_transform` and
+`best_fit_transform_with_RANSAC`, same names, argument order and defaults, numpy in / numpy out.
+
+    from oryon_amd.geo6d import best_fit_transform_with_RANSAC      # instead of: from utils.geo6d import ...
+
+The arithmetic runs in liboryon_hip.so (csrc/ransac.hip: every hypothesis of a call is scored in ONE launch); this module only
+moves the arrays and keeps numpy's global generator where the reference leaves it.  The points are handed to the kernel as
+float32 (what pipeline.py:459-463 passes); fits and the inlier test are float64, as numpy computes them for float64 input.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import ops
+
+MAX_ROWS = 2048          # oryon_ransac_register: rows per pair
+
+
+def _as_points(x) -> np.ndarray:
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    assert x.ndim == 2 and x.shape[1] == 3, "points are [n, 3]"
+    return x
+
+
+def _device_rows(A: np.ndarray, B: np.ndarray, device):
+    n = A.shape[0]
+    if n > MAX_ROWS:
+        raise ValueError(f"at most {MAX_ROWS} correspondences per call ({n} given)")
+    n_cap = max(4, n)
+    src = torch.zeros((1, n_cap, 3), dtype=torch.float32, device=device)
+    tgt = torch.zeros((1, n_cap, 3), dtype=torch.float32, device=device)
+    src[0, :n] = torch.from_numpy(np.ascontiguousarray(A, dtype=np.float32))
+    tgt[0, :n] = torch.from_numpy(np.ascontiguousarray(B, dtype=np.float32))
+    return src, tgt, torch.tensor([n], dtype=torch.int32, device=device)
+
+
+def best_fit_transform(A, B, *, device="cuda") -> np.ndarray:
+    """utils/geo6d.py:40-73: least-squares rigid transform of A onto B, [3,4] float64 (hypothesis 0 of the RANSAC kernel)."""
+    A, B = _as_points(A), _as_points(B)
+    assert A.shape == B.shape and A.shape[0] >= 1
+    if A.shape[0] < 4:                           # the kernel wants four rows; repeating every row changes neither means nor rotation
+        A, B = np.tile(A, (4, 1)), np.tile(B, (4, 1))
+    src, tgt, n = _device_rows(A, B, device)
+    # one iteration = the fit over all rows; a threshold nothing exceeds and a fraction nothing reaches: no refit, the fit as it is
+    out = ops.ransac_register(src, tgt, n, max_iter=1, match_err=1e30, fix_percent=2.0,
+                              sample_idx=torch.zeros((1, 1, 4), dtype=torch.int32, device=src.device))
+    return out["T"][0, :3, :].double().cpu().numpy()
+
+
+def best_fit_transform_with_RANSAC(A, B, max_iter=20, match_err=0.015, fix_percent=0.7, *, sample_idx: Optional[np.ndarray] = None,
+                                   device="cuda") -> np.ndarray:
+    """utils/geo6d.py:75-120.  Without `sample_idx` ([max_iter, 4] row indices) the draws come from numpy's global generator exactly
+    as the reference makes them - one bulk randint gives the rows of its per-iteration calls - and the generator is left in the
+    state the reference leaves it in: after an exit at iteration k only k draws have been consumed."""
+    A, B = _as_points(A), _as_points(B)
+    assert A.shape == B.shape
+    n = A.shape[0]
+    max_iter = int(max_iter)
+    if n < 4 or max_iter <= 0:                   # geo6d.py:79-80 (and a loop that never runs): zeros, no draw
+        return np.zeros((3, 4), dtype=np.float32)
+    state = None
+    if sample_idx is None:
+        state = np.random.get_state()
+        sample_idx = np.random.randint(0, n, (max_iter, 4))
+    idx = torch.from_numpy(np.ascontiguousarray(np.asarray(sample_idx).reshape(1, max_iter, 4), dtype=np.int32))
+    src, tgt, nn = _device_rows(A, B, device)
+    out = ops.ransac_register(src, tgt, nn, max_iter=max_iter, match_err=float(match_err), fix_percent=float(fix_percent),
+                              sample_idx=idx.to(src.device))
+    if state is not None and int(out["exited"][0]) == 1:
+        k = int(out["winner"][0])
+        np.random.set_state(state)
+        if k > 0:
+            np.random.randint(0, n, (k, 4))
+    return out["T"][0, :3, :].double().cpu().numpy()

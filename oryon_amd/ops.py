@@ -649,6 +649,36 @@ def kabsch_batched(A: torch.Tensor, B: torch.Tensor, w: Optional[torch.Tensor] =
 
 
 @_on_tensor_device
+def ransac_register(src: torch.Tensor, tgt: torch.Tensor, n: torch.Tensor, max_iter: int = 10000, match_err: float = 0.001,
+                    fix_percent: float = 0.9999, sample_idx: Optional[torch.Tensor] = None, seed: int = 1,
+                    pair_key: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, want_counts: bool = False,
+                    workspace: Optional[torch.Tensor] = None):
+    """src, tgt [B,n_cap,3] fp32 (metres, n_cap <= 2048), n [B] int32 -> dict(T [B,4,4], winner [B], exited [B], status [B],
+    counts [B,max_iter] | None).  sample_idx [B,max_iter,4] int32 names the rows of every draw; None = the device RNG keyed by
+    (seed, pair_key).  Hypothesis numbering and the zero / identity results: include/oryon_hip.h, oryon_ransac_register."""
+    dev = _lib.require_gpu(src.device)
+    assert src.dtype == torch.float32 and tgt.dtype == torch.float32 and src.shape == tgt.shape and src.shape[2] == 3
+    assert n.dtype == torch.int32 and (status is None or status.dtype == torch.int32) and (pair_key is None or pair_key.dtype == torch.int64)
+    B, n_cap = src.shape[0], src.shape[1]
+    max_iter = int(max_iter)
+    if sample_idx is not None:
+        assert sample_idx.dtype == torch.int32 and tuple(sample_idx.shape) == (B, max_iter, 4)
+    need = lib().oryon_ransac_workspace_bytes(B, n_cap, max_iter)
+    if need == 0 and B > 0:
+        raise _lib.OryonError(f"oryon_ransac_workspace_bytes({B}, {n_cap}, {max_iter}): shape not supported (n_cap <= 2048, max_iter > 0)")
+    ws = workspace if workspace is not None else torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+    winner = torch.empty((B,), dtype=torch.int32, device=dev)
+    exited = torch.empty((B,), dtype=torch.int32, device=dev)
+    st_out = torch.empty((B,), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, max_iter), dtype=torch.int32, device=dev) if want_counts else None
+    check(lib().oryon_ransac_register(ptr(src), ptr(tgt), ptr(n), B, n_cap, max_iter, float(match_err), float(fix_percent), ptr(sample_idx),
+                                      int(seed) & (2**64 - 1), ptr(pair_key), ptr(status), ptr(ws), ws.numel(), ptr(T), ptr(winner),
+                                      ptr(exited), ptr(counts), ptr(st_out), stream_ptr(dev)), "oryon_ransac_register")
+    return dict(T=T, winner=winner, exited=exited, status=st_out, counts=counts)
+
+
+@_on_tensor_device
 def pose_metrics(pred_pose: torch.Tensor, gt_pose: torch.Tensor, model_pts: torch.Tensor, pts_offset: Optional[torch.Tensor] = None,
                  model_of_pair: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pred/gt [B,4,4] (metres), model_pts [M,3] (or the concatenation of several models with pts_offset [n+1] int32 and

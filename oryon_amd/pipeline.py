@@ -21,7 +21,8 @@ import torch
 from torch import Tensor
 
 from . import _lib, ops
-from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK, PAIR_OK
+from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK, PAIR_OK, default_solver
+from .geo6d import best_fit_transform_with_RANSAC
 from .pcd import nn_correspondences
 from .pointdsc import PointDSC, get_pointdsc_pose
 
@@ -32,7 +33,7 @@ def default_args(**overrides) -> SimpleNamespace:
         device="cuda", corrs_device="cpu", seed=1,
         dataset=SimpleNamespace(img_size=[224, 224], max_corrs=500),
         model=SimpleNamespace(image_encoder=SimpleNamespace(img_size=[192, 192], out_channels=32)),
-        test=SimpleNamespace(mask="predicted", src_sampling=5000, solver="pointdsc", n_corrs=500, dist_th=0.25,
+        test=SimpleNamespace(mask="predicted", src_sampling=5000, solver=default_solver(), n_corrs=500, dist_th=0.25,
                              mask_threshold=0.5),
         loss=SimpleNamespace(hard_negatives=True),
     )
@@ -65,7 +66,14 @@ def mask_iou(gt: Tensor, pred: Tensor) -> Tensor:
 
 class Pipeline:
     def __init__(self, args: SimpleNamespace, model=None, pointdsc_solver: Optional[PointDSC] = None):
+        """pointdsc_solver may be None with test.solver = 'ransac' (the solver that needs no pretrained weights).
+        The solver is a property of the pipeline, read from args.test.solver HERE: `pointdsc_solver` is handed in for it, and the
+        batched engine bakes it into its arena and registration stream.  The reference reads the flag at every call; this class has
+        always refused `args.test.solver = "ransac"` set on a pipeline that was built for PointDSC (the suite pins that), and still
+        does now that the solver exists: `get_pose` raises when the flag no longer names the solver the pipeline was built with, so
+        the per-sample and the batched route of one pipeline can never use different solvers.  Build a new Pipeline to switch."""
         self.args = args
+        self.solver = args.test.solver
         self.device = args.device
         self.corrs_device = args.corrs_device
         self.model = model if model is not None else PrecomputedFeatures()
@@ -131,14 +139,23 @@ class Pipeline:
         camera_a = batch["anchor"]["camera"][idx].reshape(1, 9).to(torch.float32).to(dev)
         camera_q = batch["query"]["camera"][idx].reshape(1, 9).to(torch.float32).to(dev)
         HO, WO = self.args.model.image_encoder.img_size
-        if self.args.test.solver == "pointdsc":
-            c = corrs.to(dev).to(torch.int32).contiguous()[None]
-            pcd_a, pcd_q, n = ops.lift_pairs(c, None, (HO, WO), depth_a[None].contiguous(), depth_q[None].contiguous(),
-                                             camera_a, camera_q)
-            m = int(n.item())
-            pose4 = get_pointdsc_pose(self.pointdsc_solver, pcd_a[0, :m], pcd_q[0, :m], self.device)
-        else:
+        if self.args.test.solver not in ("pointdsc", "ransac"):
             raise RuntimeError(f"Solver {self.args.test.solver} not implemented")
+        if self.args.test.solver != self.solver:
+            raise RuntimeError(f"test.solver was changed from '{self.solver}' to '{self.args.test.solver}' after this Pipeline was built: "
+                               "the solver is fixed at construction, build a new Pipeline")
+        c = corrs.to(dev).to(torch.int32).contiguous()[None]
+        pcd_a, pcd_q, n = ops.lift_pairs(c, None, (HO, WO), depth_a[None].contiguous(), depth_q[None].contiguous(),
+                                         camera_a, camera_q)
+        m = int(n.item())
+        if self.args.test.solver == "ransac":                  # pipeline.py:462-466
+            pose = best_fit_transform_with_RANSAC(pcd_a[0, :m], pcd_q[0, :m], max_iter=10000, fix_percent=0.9999, match_err=0.001,
+                                                  device=dev)
+            pose4 = np.eye(4)
+            pose4[:3, :] = pose
+            pose4 = torch.tensor(pose4)
+        else:
+            pose4 = get_pointdsc_pose(self.pointdsc_solver, pcd_a[0, :m], pcd_q[0, :m], self.device)
         return pose4.to(torch.float32)
 
     # ------------------------------------------------------------------ pipeline.py:490-497
@@ -234,7 +251,7 @@ class Pipeline:
         if self._engine is None:
             self._engine = MatchPoseEngine(self.pointdsc_solver, MatchPoseConfig(
                 dist_th=self.args.test.dist_th, n_corrs=self.args.test.n_corrs, src_sampling=self.args.test.src_sampling,
-                seed=self.args.seed if self.args.seed is not None else 1))
+                seed=self.args.seed if self.args.seed is not None else 1, solver=self.solver))
 
         def stack(x):
             return (torch.stack([d.squeeze() for d in x]) if isinstance(x, (list, tuple)) else x).to(dev, torch.float32).contiguous()
