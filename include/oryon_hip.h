@@ -614,6 +614,39 @@ int oryon_pose_bop_errors(const double *pred_pose, const double *gt_pose, const 
                           const int32_t *pts_offset, const double *syms, const int32_t *sym_offset, int n_models, int max_syms,
                           const int32_t *model_of_pair, int max_points, double *workspace, double *out, void *stream);
 
+/* f3  depth render of triangle meshes for N images (image = pose x camera x model) of one size H x W.
+ *     Replaces bop_toolkit_lib/renderer_vispy.py:512-617 (render_object(..)['depth']: the OpenGL depth pass of the reference's VSD,
+ *     which needs vispy + EGL + a GL driver) with a rasteriser whose arithmetic is DEFINED (csrc/vsd.hip header) and restated
+ *     in numpy (oryon_amd/evaluation.py rasterize_depth): both give the same bits.
+ * pose [N,16] fp32 row-major 4x4 (rotation, translation in MILLIMETRES); K [N,9] fp32 (fx = K[0], cx = K[2], fy = K[4], cy = K[5] are
+ * read); verts_mm [sum V,3] fp32 with vert_offset [n_models+1]; faces [sum F,3] int32, zero-based and local to their model, with
+ * face_offset [n_models+1]; max_faces = largest model; model_of_image [N] or NULL (every image shows model 0).
+ * Output pixel (row r, column c) samples the projection at (u, v) = (c + 0.5, r + 0.5); both windings are drawn, the nearest surface
+ * wins, background 0, depth = eye-space Z in millimetres, perspective-correct.  A triangle with a vertex at Z <= 0 (or further than 2^15
+ * pixels from the origin) is dropped whole - no near-plane clipping; the reference's 16 / 24-bit z-buffer quantisation is not
+ * reproduced.  workspace: oryon_render_depth_workspace_bytes(N, max_faces); its first two uint32 hold, after the call, the number of
+ * triangles drawn by the one-wave-per-triangle route and by the one-thread-per-triangle route.  depth [N,H,W] fp32. */
+size_t oryon_render_depth_workspace_bytes(int N, int max_faces);
+int oryon_render_depth(const float *pose, const float *K, int N, const float *verts_mm, const int32_t *vert_offset, const int32_t *faces,
+                       const int32_t *face_offset, int n_models, int max_faces, const int32_t *model_of_image, int H, int W, void *workspace,
+                       float *depth, void *stream);
+
+/* f3  the integer counts behind VSD for B pairs: renders the model at the estimated and at the ground-truth pose (as oryon_render_depth)
+ *     and counts, against the test depth image, the pixels of the two bop19 visibility masks.
+ *     Replaces utils/evaluator.py:263-266 + :281-283 (float16 pose rounding, the call) and bop_toolkit_lib/pose_error.py:17-93 (vsd,
+ *     'step' cost, normalised by the diameter), misc.py:143-163 (depth_im_to_dist_im_fast, float64) and visibility.py (bop19, the
+ *     difference taken in fp32).
+ * pred_pose / gt_pose [B,16] float64 (metres; rounded to float16 inside like oryon_pose_bop_errors); K [B,9] float64; depth_test
+ * [B,H,W] fp32 millimetres (0 = no measurement); mesh arguments as oryon_render_depth, model_of_pair [B] or NULL; diameter_mm [B]
+ * float64; delta (millimetres; compared in fp32); taus [n_tau] float64, n_tau <= 16.
+ * workspace: oryon_vsd_workspace_bytes(B, H, W, max_faces).  counts [B, 2 + n_tau] int32 = (n_union, n_inter, n_cost[tau]...); the
+ * error at tau is (n_cost + n_union - n_inter) / n_union, or 1 when n_union is 0. */
+size_t oryon_vsd_workspace_bytes(int B, int H, int W, int max_faces);
+int oryon_vsd_counts(const double *pred_pose, const double *gt_pose, const double *K, const float *depth_test, int B, int H, int W,
+                     const float *verts_mm, const int32_t *vert_offset, const int32_t *faces, const int32_t *face_offset, int n_models,
+                     int max_faces, const int32_t *model_of_pair, const double *diameter_mm, double delta, const double *taus, int n_tau,
+                     void *workspace, int32_t *counts, void *stream);
+
 /* a5  StandardDecoder.forward (models/decoder.py:82-108) on the device, fp32 in / fp32 out, for the decoder the reference builds
  *     (get_decoder, models/decoder.py:119-125: input_dim 128, decoder_dims [64, 32], extra_upsampling, guidance projections 256->32 and
  *     128->16): three Up blocks (ConvTranspose2d 2x2 s2 -> cat guidance -> (conv3x3 - GroupNorm(C/16) - ReLU) x 2, :9-42), the two

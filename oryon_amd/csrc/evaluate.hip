@@ -11,6 +11,7 @@
 // One workgroup = 256 predicted points of one pair; the ground-truth cloud streams through LDS for the nearest-neighbour search.
 #include <hip/hip_fp16.h>
 #include "common.h"
+#include "pose_f16.h"
 
 namespace oryon {
 
@@ -122,34 +123,6 @@ __global__ void pose_finish_kernel(int B, const float *__restrict__ pred, const 
 //   MSPD = the same with both points projected by K first                                              (pixels)
 // max_points: the reference's np_transform slices `pts[:, :3]` on the POINT axis of its [1,N,3] array (pose_error.py:345), so its
 // maxima run over the first three model points only; max_points = 3 reproduces that, 0 evaluates every point (BOP's definition).
-__device__ __forceinline__ double round_to_half(double d)
-{
-    // numpy's float64 -> float16 cast rounds once (to nearest even).  Going through float would round twice, so the intermediate
-    // float is made by ROUND-TO-ODD (truncate, set the last bit if inexact): a following round-to-nearest to 11 bits is then exact.
-    float f = (float)d;
-    const double back = (double)f;
-    if (back != d) {
-        unsigned u = __float_as_uint(f);
-        if (fabs(back) > fabs(d)) u -= 1u;              // undo a rounding away from zero (sign-magnitude: one step towards zero)
-        u |= 1u;
-        f = __uint_as_float(u);
-    }
-    return (double)__half2float(__float2half_rn(f));
-}
-
-struct Pose34 { double m[12]; };
-
-__device__ __forceinline__ Pose34 pose_f16_mm(const double *P)          // [4,4] row-major, metres -> R16 | half(t16 * 1000)
-{
-    Pose34 o;
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) o.m[4 * r + c] = round_to_half(P[4 * r + c]);
-        const float t16 = (float)round_to_half(P[4 * r + 3]);
-        o.m[4 * r + 3] = (double)__half2float(__float2half_rn(__fmul_rn(t16, 1000.0f)));
-    }
-    return o;
-}
-
 __device__ __forceinline__ void apply34(const Pose34 &T, double x, double y, double z, double &ox, double &oy, double &oz)
 {
     ox = (x * T.m[0] + y * T.m[1] + z * T.m[2]) + T.m[3];

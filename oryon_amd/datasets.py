@@ -46,6 +46,10 @@ def _png(path: str, mode: Optional[str]) -> np.ndarray:
     return np.asarray(img.convert(mode) if mode else img)
 
 
+_PLY_CODE = {"float": "f", "float32": "f", "double": "d", "float64": "d", "uchar": "B", "uint8": "B", "char": "b", "int8": "b",
+             "short": "h", "int16": "h", "ushort": "H", "uint16": "H", "int": "i", "int32": "i", "uint": "I", "uint32": "I"}
+
+
 def read_ply_vertices(path: str) -> np.ndarray:
     """x, y, z of a PLY file's vertex element (ascii or binary_little_endian; what the reference reads through `plyfile`)."""
     with open(path, "rb") as f:
@@ -73,15 +77,100 @@ def read_ply_vertices(path: str) -> np.ndarray:
             return np.asarray([[float(r[ix]), float(r[iy]), float(r[iz])] for r in rows], dtype=np.float64)
         if fmt != "binary_little_endian":
             raise ValueError(f"{path}: unsupported PLY format {fmt}")
-        code = {"float": "f", "float32": "f", "double": "d", "float64": "d", "uchar": "B", "uint8": "B", "char": "b", "int8": "b",
-                "short": "h", "int16": "h", "ushort": "H", "uint16": "H", "int": "i", "int32": "i", "uint": "I", "uint32": "I"}
-        rec = struct.Struct("<" + "".join(code[t] for t, _ in props))
+        rec = struct.Struct("<" + "".join(_PLY_CODE[t] for t, _ in props))
         raw = f.read(rec.size * n_vert)
         out = np.empty((n_vert, 3), dtype=np.float64)
         for i in range(n_vert):
             v = rec.unpack_from(raw, i * rec.size)
             out[i] = (v[ix], v[iy], v[iz])
         return out
+
+
+def read_ply_faces(path: str) -> np.ndarray:
+    """[F,3] int32 vertex indices (zero-based, as PLY stores them) of a PLY file's face element: ascii or binary_little_endian, the
+    list property named `vertex_indices` or `vertex_index`, any count / index type of the table above (what the reference reads
+    through `plyfile`, utils/data/toyl.py:72-73).  A face that is not a triangle is an error."""
+    with open(path, "rb") as f:
+        fmt, elements = None, []                         # elements: [name, count, [property tuples]] in file order
+        while True:
+            raw = f.readline()
+            if not raw:
+                raise ValueError(f"{path}: PLY header without end_header")
+            tok = raw.decode("ascii", "replace").split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append([tok[1], int(tok[2]), []])
+            elif tok[0] == "property" and elements:
+                elements[-1][2].append(tuple(tok[1:]))
+            elif tok[0] == "end_header":
+                break
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise ValueError(f"{path}: unsupported PLY format {fmt}")
+        for name, count, props in elements:
+            if name != "face":                           # skip the elements in front (the vertices)
+                if any(p[0] == "list" for p in props):
+                    raise ValueError(f"{path}: list property in element {name!r} in front of the faces is not supported")
+                if fmt == "ascii":
+                    for _ in range(count):
+                        f.readline()
+                else:
+                    f.seek(struct.calcsize("<" + "".join(_PLY_CODE[p[0]] for p in props)) * count, os.SEEK_CUR)
+                continue
+            which = [i for i, p in enumerate(props) if p[0] == "list" and p[3] in ("vertex_indices", "vertex_index")]
+            if not which:
+                raise ValueError(f"{path}: the face element has no vertex_indices / vertex_index list")
+            if any(p[0] == "list" for i, p in enumerate(props) if i != which[0]):
+                raise ValueError(f"{path}: a second list property in the face element is not supported")
+            out = np.empty((count, 3), dtype=np.int64)
+            if fmt == "ascii":
+                for k in range(count):
+                    row = f.readline().split()
+                    at = which[0]                        # scalar properties in front of the list take one token each
+                    if int(row[at]) != 3:
+                        raise ValueError(f"{path}: face {k} has {int(row[at])} vertices; only triangles are supported")
+                    out[k] = [int(v) for v in row[at + 1:at + 4]]
+            else:
+                head = struct.Struct("<" + "".join(_PLY_CODE[p[0]] for p in props[:which[0]]))
+                cnt = struct.Struct("<" + _PLY_CODE[props[which[0]][1]])
+                tri = struct.Struct("<3" + _PLY_CODE[props[which[0]][2]])
+                tail = struct.Struct("<" + "".join(_PLY_CODE[p[0]] for p in props[which[0] + 1:]))
+                raw = f.read((head.size + cnt.size + tri.size + tail.size) * count)
+                at = 0
+                for k in range(count):
+                    at += head.size
+                    if at + cnt.size > len(raw):
+                        raise ValueError(f"{path}: face data ends early")
+                    n = cnt.unpack_from(raw, at)[0]
+                    if n != 3:
+                        raise ValueError(f"{path}: face {k} has {n} vertices; only triangles are supported")
+                    at += cnt.size
+                    out[k] = tri.unpack_from(raw, at)
+                    at += tri.size + tail.size
+            return out.astype(np.int32)
+    raise ValueError(f"{path}: no face element")
+
+
+def read_obj_faces(path: str, n_vertices: int) -> np.ndarray:
+    """[F,3] int32 ZERO-based vertex indices of the `f a/b/c d/e/f g/h/i` lines of a Wavefront OBJ file (the NOCS models).
+    Deliberate deviation: the reference hands OBJ's one-based indices to its index buffer as they are (utils/data/nocs.py:81-85), so
+    every triangle it draws uses the vertices one position further on and the largest index reads past the end of the vertex buffer,
+    which OpenGL leaves undefined.  Here the indices are converted to zero-based and checked against the vertex count."""
+    faces = []
+    with open(path) as f:
+        for line in f:
+            tok = line.split()
+            if not tok or tok[0] != "f":
+                continue
+            if len(tok) != 4:
+                raise ValueError(f"{path}: face with {len(tok) - 1} vertices; only triangles are supported")
+            faces.append([int(t.split("/")[0]) - 1 for t in tok[1:]])
+    out = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if out.size and (out.min() < 0 or out.max() >= n_vertices):
+        raise ValueError(f"{path}: face index outside 1..{n_vertices} (found {int(out.min()) + 1}..{int(out.max()) + 1})")
+    return out.astype(np.int32)
 
 
 def unique_matches(matches: torch.Tensor) -> torch.Tensor:
@@ -164,6 +253,7 @@ class FixedSplit:
                 self.obj_names = json.load(f)
             self._toyl_scenes: Dict[int, Dict] = {}
         self._models: Dict = {}
+        self._faces: Dict = {}
 
     def __len__(self) -> int:
         return len(self.instances)
@@ -273,9 +363,11 @@ class FixedSplit:
         return item_a, item_q, prompt, sampled, corrs, self.poses[index], obj_key, instance_id, valid
 
     # ------------------------------------------------------------------ object models (evaluation)
-    def object_info(self, obj_key) -> Dict:
+    def object_info(self, obj_key, faces: bool = False) -> Dict:
         """{'pts' [N,3] millimetres, 'diameter' (BOP, mm), 'syms' [S,3,4] the BOP symmetry set, 'symmetric' bool}: what the evaluator
-        needs (utils/evaluator.py:246-275: ADD-S iff the symmetry set has more than the identity; MSSD / MSPD minimise over it)."""
+        needs (utils/evaluator.py:246-275: ADD-S iff the symmetry set has more than the identity; MSSD / MSPD minimise over it).
+        faces=True adds 'faces' [F,3] int32, zero-based indices into 'pts' (VSD renders the mesh; read on the first such request:
+        the NOCS `<obj>.obj`, utils/data/nocs.py:81-85, or the face element of the TOYL PLY, utils/data/toyl.py:72-73)."""
         if obj_key not in self._models:
             if self.kind == "nocs":
                 d = join(self.base, "obj_models", "real_test")
@@ -293,4 +385,15 @@ class FixedSplit:
             syms = format_sym_set(get_symmetry_transformations(info, max_sym_disc_step=0.05))
             self._models[obj_key] = {"pts": np.asarray(pts, dtype=np.float64), "diameter": float(info["diameter"]), "syms": syms,
                                      "symmetric": syms.shape[0] > 1}
-        return self._models[obj_key]
+        if not faces:
+            return self._models[obj_key]
+        if obj_key not in self._faces:
+            n = self._models[obj_key]["pts"].shape[0]
+            if self.kind == "nocs":
+                self._faces[obj_key] = read_obj_faces(join(self.base, "obj_models", "real_test", f"{obj_key}.obj"), n)
+            else:
+                fc = read_ply_faces(join(self.base, "models_bop", f"obj_{int(obj_key):06d}.ply"))
+                if fc.size and (fc.min() < 0 or fc.max() >= n):
+                    raise ValueError(f"obj_{int(obj_key):06d}.ply: face index outside its {n} vertices")
+                self._faces[obj_key] = fc
+        return dict(self._models[obj_key], faces=self._faces[obj_key])

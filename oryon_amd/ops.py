@@ -727,6 +727,73 @@ def pose_bop_errors(pred_pose: torch.Tensor, gt_pose: torch.Tensor, K: torch.Ten
     return out
 
 
+
+def _mesh_args(dev, verts_mm, faces, vert_offset, face_offset):
+    """Device copies of a (concatenated) mesh and what the C ABI wants to know about it."""
+    verts = verts_mm.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    fc = faces.to(dev, torch.int32).reshape(-1, 3).contiguous()
+    vo = (torch.tensor([0, verts.shape[0]]) if vert_offset is None else vert_offset).to(torch.int32).cpu()
+    fo = (torch.tensor([0, fc.shape[0]]) if face_offset is None else face_offset).to(torch.int32).cpu()
+    assert vo.numel() == fo.numel() and int(vo[-1]) == verts.shape[0] and int(fo[-1]) == fc.shape[0]
+    n_models = fo.numel() - 1
+    max_faces = max(1, int((fo[1:] - fo[:-1]).max()))
+    return verts, fc, vo.to(dev), fo.to(dev), n_models, max_faces
+
+
+@_on_tensor_device
+def render_depth(pose: torch.Tensor, K: torch.Tensor, verts_mm: torch.Tensor, faces: torch.Tensor, H: int, W: int,
+                 vert_offset: Optional[torch.Tensor] = None, face_offset: Optional[torch.Tensor] = None,
+                 model_of_image: Optional[torch.Tensor] = None, return_route_counts: bool = False):
+    """Depth images [N,H,W] float32 (millimetres, 0 = background) of triangle meshes on the device (f3, csrc/vsd.hip; replaces the
+    OpenGL depth render of bop_toolkit_lib/renderer_vispy.py:512-617).  pose [N,4,4] (rotation, translation in millimetres), K [N,3,3];
+    verts_mm [V,3] and faces [F,3] (zero-based) of one model, or the concatenation of several with vert_offset / face_offset [n+1]
+    (face indices local to their model) and model_of_image [N].  return_route_counts: also the workspace's two counters as a host
+    tuple (triangles drawn one wave each, triangles drawn one thread each) - a host sync, for tests."""
+    dev = _lib.require_gpu(pose.device if pose.is_cuda else verts_mm.device)
+    N = pose.shape[0]
+    P = pose.to(dev, torch.float32).reshape(N, 16).contiguous()
+    Kc = K.to(dev, torch.float32).reshape(N, 9).contiguous()
+    verts, fc, vo_d, fo_d, n_models, max_faces = _mesh_args(dev, verts_mm, faces, vert_offset, face_offset)
+    moi = None if model_of_image is None else model_of_image.to(dev, torch.int32).contiguous()
+    ws = torch.empty((max(8, lib().oryon_render_depth_workspace_bytes(N, max_faces)),), dtype=torch.uint8, device=dev)
+    depth = torch.empty((N, int(H), int(W)), dtype=torch.float32, device=dev)
+    check(lib().oryon_render_depth(ptr(P), ptr(Kc), N, ptr(verts), ptr(vo_d), ptr(fc), ptr(fo_d), n_models, max_faces, ptr(moi), int(H),
+                                   int(W), ptr(ws), ptr(depth), stream_ptr(dev)), "oryon_render_depth")
+    if return_route_counts:
+        large, small = ws[:8].view(torch.int32).tolist() if N > 0 else (0, 0)
+        return depth, (large, small)
+    return depth
+
+
+@_on_tensor_device
+def vsd_counts(pred_pose: torch.Tensor, gt_pose: torch.Tensor, K: torch.Tensor, depth_test: torch.Tensor, verts_mm: torch.Tensor,
+               faces: torch.Tensor, diameter_mm: torch.Tensor, vert_offset: Optional[torch.Tensor] = None,
+               face_offset: Optional[torch.Tensor] = None, model_of_pair: Optional[torch.Tensor] = None, delta: float = 15.0,
+               taus=None) -> torch.Tensor:
+    """The integer counts behind VSD for B pairs -> [B, 2 + n_tau] int32 = (n_union, n_inter, n_cost[tau]...) (f3, csrc/vsd.hip;
+    bop_toolkit_lib/pose_error.py:17-93 behind the float16 pose rounding of utils/evaluator.py:263-266).  pred / gt [B,4,4] metres,
+    K [B,3,3], depth_test [B,H,W] millimetres, mesh as render_depth, diameter_mm [B]; taus default to the evaluator's
+    arange(0.05, 0.51, 0.05).  evaluation.vsd_errors turns the counts into the errors."""
+    dev = _lib.require_gpu(depth_test.device if depth_test.is_cuda else verts_mm.device)
+    B, H, W = depth_test.shape
+    f64 = lambda t, shape: t.to(dev, torch.float64).reshape(shape).contiguous()
+    pred, gt, Kc, diam = f64(pred_pose, (B, 16)), f64(gt_pose, (B, 16)), f64(K, (B, 9)), f64(diameter_mm, (B,))
+    dt = depth_test.to(dev, torch.float32).contiguous()
+    if taus is None:
+        import numpy as np
+        taus = np.arange(0.05, 0.51, 0.05)
+    taus_d = torch.as_tensor(taus, dtype=torch.float64).to(dev).contiguous()
+    n_tau = taus_d.numel()
+    verts, fc, vo_d, fo_d, n_models, max_faces = _mesh_args(dev, verts_mm, faces, vert_offset, face_offset)
+    mop = None if model_of_pair is None else model_of_pair.to(dev, torch.int32).contiguous()
+    ws = torch.empty((max(8, lib().oryon_vsd_workspace_bytes(B, H, W, max_faces)),), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B, 2 + n_tau), dtype=torch.int32, device=dev)
+    check(lib().oryon_vsd_counts(ptr(pred), ptr(gt), ptr(Kc), ptr(dt), B, H, W, ptr(verts), ptr(vo_d), ptr(fc), ptr(fo_d), n_models, max_faces,
+                                 ptr(mop), ptr(diam), float(delta), ptr(taus_d), n_tau, ptr(ws), ptr(counts), stream_ptr(dev)),
+          "oryon_vsd_counts")
+    return counts
+
+
 _x3_weights = {}
 # Validation mode of the fp16x3 path (backbone.enable_fp16x3(True, guard=True)): every call first checks max|activation| against the
 # float16 range (one reduction + a host sync per linear - for a first run with a real checkpoint, not for throughput) and evaluates

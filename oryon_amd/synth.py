@@ -123,3 +123,112 @@ def make_batch(first_index: int, B: int, H: int, W: int, C: int, device: str = "
         out[k] = torch.stack([it[k] for it in items])
     out["sizes"] = (H, W)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ VSD fixtures (closed form, no RNG)
+# Meshes in millimetres, poses in metres, a 640 x 480 camera: what tools/gen_goldens.py `vsd` feeds to the reference's evaluator and
+# what tests/test_vsd.py / tests/test_gpu_vsd.py rebuild.  Only +, -, *, / and sqrt are used for the meshes (correctly rounded
+# everywhere); the poses use sin / cos, so the golden file stores them and the tests read them from there.
+def icosphere(level: int, radius: float = 60.0):
+    """(verts [V,3] float64, faces [F,3] int32): an icosahedron subdivided `level` times, vertices pushed onto the sphere; 20 * 4^level
+    faces, outward winding."""
+    import numpy as np
+    phi = (1.0 + np.sqrt(5.0)) / 2.0
+    v = [(-1, phi, 0), (1, phi, 0), (-1, -phi, 0), (1, -phi, 0), (0, -1, phi), (0, 1, phi), (0, -1, -phi), (0, 1, -phi),
+         (phi, 0, -1), (phi, 0, 1), (-phi, 0, -1), (-phi, 0, 1)]
+    verts = [np.asarray(p, dtype=np.float64) / np.sqrt(1.0 + phi * phi) for p in v]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+             (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(level):
+        mid, nxt = {}, []
+
+        def midpoint(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                m = verts[key[0]] + verts[key[1]]
+                verts.append(m / np.sqrt(np.dot(m, m)))
+                mid[key] = len(verts) - 1
+            return mid[key]
+        for a, b, c in faces:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            nxt += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        faces = nxt
+    return np.stack(verts) * radius, np.asarray(faces, dtype=np.int32)
+
+
+def box_mesh(sx: float, sy: float, sz: float, centre=(0.0, 0.0, 0.0)):
+    """(verts [8,3] float64, faces [12,3] int32) of an axis-aligned box, outward winding."""
+    import numpy as np
+    h = np.array([sx, sy, sz]) / 2.0
+    verts = np.array([[x, y, z] for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)], dtype=np.float64) * h + np.asarray(centre, dtype=np.float64)
+    faces = np.array([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6], [0, 2, 6], [0, 6, 4],
+                      [1, 5, 7], [1, 7, 3]], dtype=np.int32)
+    return verts, faces
+
+
+def two_part_mesh():
+    """A plate with a post standing on it (two closed boxes, 24 faces): seen from the side the post hides part of the plate."""
+    import numpy as np
+    v0, f0 = box_mesh(110.0, 110.0, 24.0)
+    v1, f1 = box_mesh(28.0, 28.0, 90.0, centre=(20.0, -15.0, 57.0))
+    return np.concatenate([v0, v1]), np.concatenate([f0, f1 + 8]).astype(np.int32)
+
+
+def vsd_objects():
+    """name -> {'pts' [V,3] float64 mm (the mesh vertices), 'faces' [F,3] int32, 'diameter' mm}."""
+    import numpy as np
+    out = {}
+    for name, (v, f) in (("ico2", icosphere(2)), ("ico3", icosphere(3)), ("box", box_mesh(120.0, 90.0, 60.0)), ("twopart", two_part_mesh())):
+        d = v[:, None, :] - v[None, :, :]
+        out[name] = {"pts": v, "faces": f, "diameter": float(np.sqrt((d * d).sum(-1).max()))}
+    return out
+
+
+VSD_H, VSD_W = 480, 640
+VSD_K = ((591.0125, 0.0, 322.525), (0.0, 590.16775, 244.11084), (0.0, 0.0, 1.0))
+VSD_CLS = ("ico2", "ico3", "box", "twopart", "box", "ico3", "twopart", "box")
+VSD_FAILURES = (6,)
+
+
+def vsd_poses():
+    """(gt [8,4,4], pred [8,4,4]) float64, metres: exact, a few mm / degrees off, grossly wrong, behind the camera (pair 5)."""
+    import numpy as np
+
+    def pose(axis, deg, t):
+        a = np.asarray(axis, dtype=np.float64)
+        a = a / np.sqrt(np.dot(a, a))
+        Kx = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+        th = np.deg2rad(deg)
+        P = np.eye(4)
+        P[:3, :3] = np.eye(3) + np.sin(th) * Kx + (1.0 - np.cos(th)) * (Kx @ Kx)
+        P[:3, 3] = t
+        return P
+    gt = [pose((1, 2, 3), 20.0, (0.010, -0.020, 0.800)), pose((0, 1, 0), 35.0, (-0.030, 0.015, 0.900)),
+          pose((1, 1, 0), 40.0, (0.020, 0.010, 0.750)), pose((1, 0.2, 0), 115.0, (0.000, 0.000, 0.850)),
+          pose((0, 1, 1), 25.0, (-0.040, -0.030, 0.950)), pose((1, 0, 0), 10.0, (0.030, 0.020, 0.700)),
+          pose((1, 0.2, 0), 100.0, (0.010, 0.010, 0.900)), pose((2, 1, 0), 50.0, (0.000, -0.010, 0.800))]
+    err = [np.eye(4), pose((0, 0, 1), 2.0, (0.003, -0.002, 0.004)), pose((1, 0, 0), 3.0, (0.002, 0.003, -0.005)),
+           pose((0, 1, 0), 2.0, (-0.004, 0.001, 0.006)), pose((1, 1, 1), 60.0, (0.100, -0.050, 0.080)), np.eye(4),
+           pose((0, 0, 1), 1.0, (0.001, 0.001, 0.001)), pose((0, 1, 0), 4.0, (0.001, -0.002, 0.012))]
+    pred = []
+    for g_, e_ in zip(gt, err):
+        p = g_.copy()
+        p[:3, :3] = e_[:3, :3] @ g_[:3, :3]
+        p[:3, 3] = g_[:3, 3] + e_[:3, 3]
+        pred.append(p)
+    pred[5][2, 3] = -0.700                                  # behind the camera: nothing is rendered
+    return np.stack(gt), np.stack(pred)
+
+
+def vsd_test_depth(depth_gt):
+    """The test depth image [H,W] float32 (mm) of a pair from the rasterised ground-truth depth: the object's surface moved by a
+    sin-shaped offset of up to +-20 mm (quantised to 1/8 mm; both sides of delta = 15 occur), a smooth background plane elsewhere,
+    an occluder patch in front and a hole of zeros."""
+    import numpy as np
+    H, W = depth_gt.shape
+    r, c = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    off = np.round(20.0 * np.sin(c / 7.0 + r / 11.0) * 8.0) / 8.0
+    d = np.where(depth_gt > 0, depth_gt.astype(np.float64) + off, 1500.0 + 0.25 * c + 0.125 * r)
+    d[H * 5 // 12:H * 13 // 24, W * 15 // 32:W * 33 // 64] = 300.0
+    d[H * 23 // 48:H * 7 // 12, W * 33 // 64:W * 35 // 64] = 0.0
+    return d.astype(np.float32)

@@ -8,8 +8,16 @@
 `--solver {pointdsc,ransac}` (default pointdsc) becomes the process-wide default solver (oryon_amd.engine.set_default_solver): every
 `default_args()` and `MatchPoseConfig()` that run_test.py builds - the per-sample loop, the batched engine, its --half-descriptors
 engine - then selects it.  Everything else goes to run_test.py unchanged.  With `ransac` (best_fit_transform_with_RANSAC,
-utils/geo6d.py:75-120, max_iter=10000, fix_percent=0.9999, match_err=0.001 as pipeline.py:463) no PointDSC weights take part in a pose."""
+utils/geo6d.py:75-120, max_iter=10000, fix_percent=0.9999, match_err=0.001 as pipeline.py:463) no PointDSC weights take part in a pose.
+
+    python run_pose.py --vsd --data-root /data --dataset nocs --ckpt ... --out preds/nocs.csv
+
+`--vsd` (real-asset mode only) also reports VSD and AR = (VSD + MSSD + MSPD) / 3, the reference's headline column
+(utils/evaluator.py:281-288): once run_test.py has written its prediction CSV, compute_metrics.py scores that file over the same pairs
+with `Evaluator(compute_vsd=True)` on the device (model meshes rendered by csrc/vsd.hip) and the summary printed last carries `VSD`, `AR`
+and the full table row in place of run_test.py's `not_computed` note.  The split's images are decoded a second time for it."""
 import argparse
+import json
 import os
 import sys
 
@@ -31,12 +39,39 @@ def parse(argv=None):
     return a.solver, rest
 
 
+def take_vsd(argv):
+    """-> (whether `--vsd` was given, argv without it)."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    return "--vsd" in argv, [x for x in argv if x != "--vsd"]
+
+
+def add_vsd(summary: dict, rest) -> dict:
+    """Score the CSV that run_test.py just wrote with VSD and AR and fold the result into its summary."""
+    import compute_metrics
+    ap = argparse.ArgumentParser(add_help=False)
+    for name, default in (("--data-root", None), ("--dataset", "nocs"), ("--dataset-name", None), ("--split", "cross_scene_test"),
+                          ("--obj", "all"), ("--mask", "predicted")):
+        ap.add_argument(name, default=default)
+    a, _ = ap.parse_known_args(rest)
+    m = compute_metrics.main([summary["csv"], "--data-root", a.data_root, "--dataset", a.dataset, "--split", a.split, "--obj", a.obj,
+                              "--mask", a.mask, "--pairs", str(summary["pairs"])] +
+                             (["--dataset-name", a.dataset_name] if a.dataset_name else []))
+    out = {k: v for k, v in summary.items() if k != "not_computed"}
+    out.update({"VSD": m["VSD"], "AR": m["AR"], "latex_row": m["latex_row"], "metrics_json": m["metrics_json"]})
+    print(json.dumps(out))
+    return out
+
+
 def main(argv=None):
+    vsd, argv = take_vsd(argv)
     solver, rest = parse(argv)
+    if vsd and "--data-root" not in rest and not any(r.startswith("--data-root=") for r in rest):
+        raise SystemExit("run_pose.py --vsd needs real-asset mode (--data-root ...): the synthetic pairs have no object mesh")
     from oryon_amd.engine import set_default_solver
     set_default_solver(solver)
     import run_test
-    return run_test.main(rest)
+    summary = run_test.main(rest)
+    return add_vsd(summary, rest) if vsd and summary.get("pairs") else summary
 
 
 if __name__ == "__main__":

@@ -16,6 +16,8 @@ Reference entry points executed here:
                               cal_leading_eigenvector, post_refinement, forward)
   utils/pointdsc/init.py      get_pointdsc_pose
   utils/geo6d.py              best_fit_transform_with_RANSAC (gen_ransac; `python tools/gen_goldens.py ransac`)
+  utils/evaluator.py          Evaluator(compute_vsd=True) + bop_toolkit_lib/pose_error.py vsd, misc.py, visibility.py (gen_vsd;
+                              `python tools/gen_goldens.py vsd`; the OpenGL renderer is stood in for by evaluation.rasterize_depth)
 """
 import json
 import os
@@ -700,6 +702,95 @@ def gen_ransac():
             raise RuntimeError(f"ransac_{tag}: no seed satisfies the fixture's conditions")
 
 
+# ---------------------------------------------------------------------------------------------- G11 (VSD)
+def gen_vsd():
+    """g11_vsd: the reference's Evaluator with compute_vsd=True run for real (add_object_info, register_test, register_test_failure,
+    get_means, get_latex_str) and bop_toolkit_lib/pose_error.vsd called directly, on the closed-form meshes, poses and test depth
+    images of oryon_amd/synth.py.  The one thing the reference cannot do here - bop_toolkit_lib/renderer_vispy (vispy + EGL + a GL
+    driver) - is replaced by a stand-in module whose RendererVispy renders with oryon_amd.evaluation.rasterize_depth, the numpy
+    statement of the project's rasteriser; everything downstream of the depth render is the reference's own code.  The counts are
+    taken with the reference's depth_im_to_dist_im_fast and visibility functions on the same renders."""
+    from oryon_amd import synth
+    from oryon_amd.evaluation import rasterize_depth
+
+    class RendererVispy:
+        def __init__(self, width, height, mode="depth"):
+            self.width, self.height, self.models = width, height, {}
+
+        def my_add_object(self, model, obj_id):
+            self.models[obj_id] = model
+
+        def render_object(self, obj_id, R, t, fx, fy, cx, cy):
+            P = np.eye(4, dtype=np.float32)
+            P[:3, :3], P[:3, 3] = R, np.asarray(t).squeeze()
+            K = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+            m = self.models[obj_id]
+            return {"depth": rasterize_depth(P, K, m["pts"], m["faces"], self.height, self.width)}
+    stand_in = types.ModuleType("bop_toolkit_lib.renderer_vispy")
+    stand_in.RendererVispy = RendererVispy
+    sys.modules["bop_toolkit_lib.renderer_vispy"] = stand_in
+    from utils.evaluator import Evaluator                                             # reference
+    from bop_toolkit_lib.misc import get_symmetry_transformations, depth_im_to_dist_im_fast    # reference
+    from bop_toolkit_lib import pose_error, visibility                                # reference
+    objects = synth.vsd_objects()
+    models = {k: {"pts": o["pts"], "faces": o["faces"]} for k, o in objects.items()}
+    diams = {k: o["diameter"] for k, o in objects.items()}
+    symms = {k: get_symmetry_transformations({"diameter": o["diameter"]}, max_sym_disc_step=0.05) for k, o in objects.items()}
+    H, W, K = synth.VSD_H, synth.VSD_W, np.array(synth.VSD_K)
+    gt, pred = synth.vsd_poses()
+    cls, n = list(synth.VSD_CLS), len(synth.VSD_CLS)
+    rel32, anchor32 = pred.astype(np.float32), np.tile(np.eye(4, dtype=np.float32), (n, 1, 1))
+    ev = Evaluator("g11", compute_vsd=True, compute_iou=True)
+    ev0 = Evaluator("g11", compute_vsd=False, compute_iou=True)
+    for e in (ev, ev0):
+        e.add_object_info(models, diams, symms)
+        e.init_test()
+    renderer = ev.renderer
+    assert isinstance(renderer, RendererVispy)
+    taus, delta = ev.vsd_taus, ev.vsd_delta
+    counts, errors, crops = np.zeros((n, 2 + len(taus)), np.int32), np.zeros((n, len(taus))), {}
+    for i in range(n):
+        p16, g16 = (rel32[i] @ anchor32[i]).astype(np.float16), gt[i].astype(np.float16)
+        Re, te, Rg, tg = p16[:3, :3], np.expand_dims(p16[:3, 3], 1) * 1000, g16[:3, :3], np.expand_dims(g16[:3, 3], 1) * 1000
+        d_gt = renderer.render_object(cls[i], Rg, tg, K[0, 0], K[1, 1], K[0, 2], K[1, 2])["depth"]
+        d_est = renderer.render_object(cls[i], Re, te, K[0, 0], K[1, 1], K[0, 2], K[1, 2])["depth"]
+        depth = synth.vsd_test_depth(d_gt)
+        errors[i] = pose_error.vsd(Re, te, Rg, tg, depth, K, delta, taus, True, diams[cls[i]], renderer, cls[i])
+        dist_t, dist_g, dist_e = (depth_im_to_dist_im_fast(d, K) for d in (depth, d_gt, d_est))
+        vis_g = visibility.estimate_visib_mask_gt(dist_t, dist_g, delta, visib_mode="bop19")
+        vis_e = visibility.estimate_visib_mask_est(dist_t, dist_e, vis_g, delta, visib_mode="bop19")
+        inter = np.logical_and(vis_g, vis_e)
+        dists = np.abs(dist_g[inter] - dist_e[inter]) / diams[cls[i]]
+        counts[i] = [np.logical_or(vis_g, vis_e).sum(), inter.sum()] + [(dists >= tau).sum() for tau in taus]
+        u = counts[i, 0]
+        assert np.array_equal(errors[i], (counts[i, 2:] + (u - counts[i, 1])) / float(u) if u else np.ones(len(taus))), i
+        if i == 1:
+            crops["crop_gt_1"] = d_gt[230:278, 270:334].copy()
+        if i == 3:
+            crops["crop_est_3"] = d_est[200:248, 290:354].copy()
+        iou_a, iou_q = torch.tensor([0.5 + 0.04 * i]), torch.tensor([0.9 - 0.05 * i])
+        for e in (ev, ev0):
+            if i in synth.VSD_FAILURES:
+                e.register_test_failure({"iou_a": iou_a, "iou_q": iou_q, "cls_id": [cls[i]], "instance_id": [f"inst{i}"]})
+                continue
+            pred_rel = torch.tensor(rel32[i])
+            e.register_test({"iou_a": iou_a, "iou_q": iou_q, "gt_pose": torch.tensor(gt[i]).unsqueeze(0),
+                             "pred_pose": (pred_rel @ torch.tensor(anchor32[i])).unsqueeze(0), "pred_pose_rel": pred_rel.unsqueeze(0),
+                             "cls_id": [cls[i]], "camera": [K.copy()], "depth": [depth], "instance_id": [f"inst{i}"]})
+        print(f"vsd pair {i} ({cls[i]}): counts {counts[i].tolist()}, errors {np.round(errors[i], 3).tolist()}")
+    assert (counts[:, 0] > 0).all() and (errors[0] == 0).all() and (errors[5] == 1).all()
+    means = ev.get_means()
+    out = {f"metric_{k}": np.asarray(v, dtype=np.float64) for k, v in ev.metrics.items() if k not in ("cls_id", "instance_id")}
+    out.update({f"count_{k}": np.asarray(v) for k, v in ev.counts.items()})
+    out.update(crops)
+    save("g11_vsd", K=K, hw=np.array([H, W]), gt=gt, pred=pred, cls=np.array(cls), failures=np.array(synth.VSD_FAILURES),
+         iou_a=np.array([0.5 + 0.04 * i for i in range(n)], np.float32), iou_q=np.array([0.9 - 0.05 * i for i in range(n)], np.float32),
+         taus=np.asarray(taus, np.float64), delta=np.float64(delta), diameters=np.array([diams[c] for c in cls]), counts=counts,
+         errors=errors, crop_gt_1_origin=np.array([230, 270]), crop_est_3_origin=np.array([200, 290]),
+         mean_names=np.array(list(means)), mean_values=np.array([means[k] for k in means], np.float64),
+         latex=np.array(ev.get_latex_str()), latex_no_vsd=np.array(ev0.get_latex_str()), **out)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["matcher", "lift", "kabsch", "pointdsc", "e2e", "backbone", "metrics", "bop", "tokenizer", "data"]
     if "data" in which:
@@ -726,3 +817,5 @@ if __name__ == "__main__":
         gen_tokenizer()
     if "ransac" in which:
         gen_ransac()
+    if "vsd" in which:
+        gen_vsd()
