@@ -420,6 +420,38 @@ int oryon_ransac_register(const float *src, const float *tgt, const int32_t *n, 
                           int32_t *exited, int32_t *counts, int32_t *status_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Validation step: the contrastive terms of FeatureLoss.forward (losses.py:64-141) for B pairs in three launches, no allocation, no
+ *         synchronisation, no float atomics (every output is bit-stable across runs, streams and batch shapes).  fp32 throughout, as the
+ *         reference runs on the CPU; cosine in the matcher's form (rows / max(|x|, 1e-8), then a dot product).
+ * feat_a, feat_q [B,C,FH,FW] fp32 (C <= 256); corrs [B,n_corr,4] int32 (y_a,x_a,y_q,x_q) in FEATURE-MAP pixels, i.e. after
+ *         rescale_coords and the clamp of losses.py:77-78 (out-of-map values are clamped to the map); valid [B] int32: pairs whose value
+ *         is not 1 do no work and write zeros (losses.py:158,189).
+ * pool_mode 0, the hardest negative (losses.py:165-220): pool [B,2,n_pool] int32 linear pixel indices (side 0 = anchor map, 1 = query
+ *         map: the torch_sample_select draw of losses.py:196-199), or NULL = every pixel of the map in row-major order.  The negative of
+ *         positive n is the argmin over pool positions j of
+ *             0.5 (1 - cos(pos[n], map[pool[j]])) + 1e6 relu(neg_kernel - sqrt(dy^2 + dx^2 + 1e-7))       (losses.py:205-211)
+ *         in the reference's fp32 expression (correctly rounded sqrt, no contraction), lowest j on ties (torch.argmin); entries outside
+ *         [0, FH*FW) never win.
+ * pool_mode 1, loss.hard_negatives = False (losses.py:222-263): pool [B,2,n_corr] holds THE negative of every positive (the
+ *         torch.randint draw of losses.py:254); no exclusion disc.
+ * d_pos [B,n_corr] = 0.5 (1 - cos(pos_a, pos_q)) (losses.py:91); d_neg [B,2,n_corr] the same against the chosen negative
+ *         (losses.py:92-93); neg_idx [B,2,n_corr] its linear pixel index (losses.py:214-218); pair_terms [B,3] = mean_n relu(d_pos -
+ *         pos_margin), mean_n relu(neg_margin - d_neg) for the anchor and the query side (losses.py:95-101); losses [3] = their means
+ *         over the pairs with valid == 1, zeros when there is none (losses.py:103-111). */
+size_t oryon_feature_loss_workspace_bytes(int B, int n_corr, int n_pool);
+int oryon_feature_loss(const float *feat_a, const float *feat_q, int B, int C, int FH, int FW, const int32_t *corrs, int n_corr,
+                       const int32_t *valid, const int32_t *pool, int n_pool, int pool_mode, float pos_margin, float neg_margin,
+                       float neg_kernel, void *workspace, size_t workspace_bytes, float *d_pos, float *d_neg, int32_t *neg_idx,
+                       float *pair_terms, float *losses, void *stream);
+/* The sums behind the dice mask loss (losses.py:40-62 with mask_type 'dice'; utils/losses/dice.py:27-89), one pass per image.
+ * logits [B,H,W] fp32; gt [B,H,W] int32 at the logits' size (non-zero = object).  sums [B,4] float64 = sum p, sum p^2, sum p t, sum t
+ *         with p = sigmoid(2 x), the softmax over (x, -x) of dice.py:69-78, by a fixed-order tree; mask [B,H,W] int32 = sigmoid(x) >
+ *         threshold (losses.py:59, the expression of oryon_mask_from_logits); counts [B,2] int32 = |mask and gt|, |mask or gt|
+ *         (utils/metrics.py:32-36). */
+int oryon_mask_dice_sums(const float *logits, const int32_t *gt, int B, int H, int W, float threshold, double *sums, int32_t *mask,
+                         int32_t *counts, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * The whole batched step as ONE call (round 3): what the per-sample loop of FPM_Pipeline.test_step does for every pair of a batch
  * (pipeline.py:313-355: is_detection_valid -> get_featmap_corrs [utils/pcd.py:177-216] -> get_pose [pipeline.py:429-472:
  * scale / validate / lift, get_pointdsc_pose]), for B pairs, enqueued from C++ on streams and events the engine owns, over a

@@ -5,6 +5,7 @@ path - SURVEY.md §8f-3):
                                    the model points in FLOAT16, which must be replicated for 0.1-point parity)
     compute_RT_distances           utils/metrics.py:222-259 (degrees, centimetres)
     mask_iou                       utils/metrics.py:18-40
+    compute_fmr / fmr_from_distances   utils/metrics.py:59-77 (feature-matching recall of ground-truth correspondence sets)
     format_pred_line / read_pred_csv   pipeline.py:490-497 and scripts/evaluation/compute_metrics.py:14-47
     get_symmetry_transformations / format_sym_set   bop_toolkit_lib/misc.py:43-90, :402-411 (the symmetry set of a BOP model)
     mssd_error / mspd_error        bop_toolkit_lib/pose_error.py:370-427 (my_mssd / my_mspd) behind the float16 pose rounding of
@@ -72,6 +73,29 @@ def mask_iou(mask1: np.ndarray, mask2: np.ndarray) -> np.ndarray:
     inter, union = (a & b).sum(1).astype(np.float32), (a | b).sum(1).astype(np.float32)
     with np.errstate(invalid="ignore", divide="ignore"):
         return inter / union
+
+
+def fmr_from_distances(dist_pos, dist_th: float, inlier_th: float) -> np.ndarray:
+    """utils/metrics.py:72-77 from the distances 0.5 (1 - cos) of the correspondences themselves ([B,N] or [N], numpy or torch - e.g. the
+    `d_pos` of losses.FeatureLoss.forward): 1.0 for every set whose share of distances below dist_th exceeds inlier_th."""
+    d = np.asarray(dist_pos.detach().cpu().numpy() if hasattr(dist_pos, "detach") else dist_pos)
+    if d.ndim == 1:
+        d = d[None]
+    inlier_ratio = (d < dist_th).astype(float).mean(1)
+    return (inlier_ratio > inlier_th).astype(float)
+
+
+def compute_fmr(feats1, feats2, dist_th: float, inlier_th: float) -> np.ndarray:
+    """FMR between two correspondence sets [B,N,D] (or [N,D]) of descriptors (utils/metrics.py:59-77): cosine distance per
+    correspondence (torch's cosine_similarity: each norm clamped at 1e-8), then fmr_from_distances."""
+    import torch
+    import torch.nn.functional as F
+    f1, f2 = torch.as_tensor(feats1), torch.as_tensor(feats2)
+    assert f1.shape == f2.shape
+    if f1.dim() == 2:
+        f1, f2 = f1.unsqueeze(0), f2.unsqueeze(0)
+    dist_pos = 0.5 * (-1 * F.cosine_similarity(f1, f2, dim=2) + 1)
+    return fmr_from_distances(dist_pos, dist_th, inlier_th)
 
 
 def format_pred_line(id_a: str, id_q: str, iou_a, iou_q, pred_pose: np.ndarray) -> str:
@@ -308,7 +332,8 @@ class Evaluator:
     `register_test` takes the per-pair ERRORS of a batch (from the device kernels or the numpy functions above) and applies the
     reference's bookkeeping: zero-pose rule, failed-pose count, ADD(S)-0.1d against the ADD diameter, MSSD / MSPD recall means,
     rotation / translation recalls; `register_test_failure` is the automatic failure of an invalid detection or a matcher that
-    returned nothing (pipeline.py:335-350: every score 0)."""
+    returned nothing (pipeline.py:335-350: every score 0).  The validation loop (pipeline.py:196-247) keeps the same lists without the
+    `instance_id` / `cls_id` columns: `init_validation`, `register_eval`, `register_valid_failure`; the test methods add the two columns."""
 
     def __init__(self, exp_tag: str = "", compute_iou: bool = True, compute_vsd: bool = False):
         self.exp_tag = exp_tag
@@ -325,6 +350,11 @@ class Evaluator:
         self.init_test()
 
     def init_test(self) -> None:
+        self.init_validation()
+        self.metrics["instance_id"], self.metrics["cls_id"] = [], []
+
+    def init_validation(self) -> None:
+        """utils/evaluator.py:143-167: the lists of the test run without the `instance_id` / `cls_id` columns."""
         self.metrics, self.counts = {}, {}
         if self.compute_iou:
             for k in ("Anchor IoU", "Query IoU", "Mean IoU", "IoU > .25", "IoU > .5", "IoU > .75"):
@@ -335,7 +365,6 @@ class Evaluator:
             self.counts[k] = []
         for r_th, t_th in self.pose_recall_th:
             self.metrics[f"Recall ({r_th}deg, {t_th}cm)"] = []
-        self.metrics["instance_id"], self.metrics["cls_id"] = [], []
 
     @staticmethod
     def effective_pose(pred_pose: np.ndarray, pred_pose_rel: np.ndarray) -> np.ndarray:
@@ -347,6 +376,15 @@ class Evaluator:
                       iou_q: Optional[float] = None, vsd_errs: Optional[Sequence[float]] = None) -> None:
         """One pair that went through the registration.  The errors must have been computed on `effective_pose`.  vsd_errs: the
         pair's VSD error per tau (vsd_errors), required with compute_vsd."""
+        self.register_eval(pred_pose_rel=pred_pose_rel, rot_deg=rot_deg, trans_cm=trans_cm, add_s=add_s, add_diam=add_diam, mssd_mm=mssd_mm,
+                           mspd_px=mspd_px, bop_diam_mm=bop_diam_mm, iou_a=iou_a, iou_q=iou_q, vsd_errs=vsd_errs)
+        self.metrics["cls_id"].append(cls_id)
+        self.metrics["instance_id"].append(instance_id)
+
+    def register_eval(self, *, pred_pose_rel: np.ndarray, rot_deg: float, trans_cm: float, add_s: float, add_diam: float, mssd_mm: float,
+                      mspd_px: float, bop_diam_mm: float, iou_a: Optional[float] = None, iou_q: Optional[float] = None,
+                      vsd_errs: Optional[Sequence[float]] = None) -> None:
+        """The validation-time registration of one pair (utils/evaluator.py:206-288): register_test without the two id columns."""
         if self.compute_iou:
             mean = (iou_a + iou_q) / 2.0
             self.metrics["Anchor IoU"].append(float(iou_a)); self.metrics["Query IoU"].append(float(iou_q))
@@ -371,10 +409,14 @@ class Evaluator:
             mean_vsd = np.stack([e < rec for rec in self.vsd_rec], axis=1).mean()
             self.metrics["VSD"].append(float(mean_vsd))
             self.metrics["AR"].append(float((mean_mssd + mean_mspd + mean_vsd) / 3.0))
+
+    def register_test_failure(self, *, cls_id, instance_id, iou_a: Optional[float] = None, iou_q: Optional[float] = None) -> None:
+        self.register_valid_failure(iou_a=iou_a, iou_q=iou_q)
         self.metrics["cls_id"].append(cls_id)
         self.metrics["instance_id"].append(instance_id)
 
-    def register_test_failure(self, *, cls_id, instance_id, iou_a: Optional[float] = None, iou_q: Optional[float] = None) -> None:
+    def register_valid_failure(self, *, iou_a: Optional[float] = None, iou_q: Optional[float] = None) -> None:
+        """utils/evaluator.py:296-328: the automatic failure of a wrong detection, every score 0."""
         for k in ("R error", "T error", "ADD(S)-0.1d", "MSSD", "MSPD") + (("VSD", "AR") if self.compute_vsd else ()):
             self.metrics[k].append(0.0)
         if self.compute_iou:
@@ -386,8 +428,6 @@ class Evaluator:
         self.counts["Zero pose"].append(0)
         for r_th, t_th in self.pose_recall_th:
             self.metrics[f"Recall ({r_th}deg, {t_th}cm)"].append(0)
-        self.metrics["cls_id"].append(cls_id)
-        self.metrics["instance_id"].append(instance_id)
 
     def get_means(self, cls_id=None) -> Dict[str, float]:
         sel = None if cls_id is None else np.asarray(self.metrics["cls_id"]) == cls_id
@@ -418,14 +458,16 @@ class Evaluator:
 
 def evaluate_batch(evaluator: Evaluator, *, pred_pose_rel: np.ndarray, anchor_pose: np.ndarray, gt_pose: np.ndarray, K: np.ndarray,
                    status: Sequence[int], cls_ids: Sequence, instance_ids: Sequence[str], objects: Dict, iou_a=None, iou_q=None,
-                   device: Optional[str] = None, depth: Optional[Sequence[np.ndarray]] = None) -> None:
+                   device: Optional[str] = None, depth: Optional[Sequence[np.ndarray]] = None, validation: bool = False) -> None:
     """What the per-sample loop of FPM_Pipeline.test_step registers for a batch (pipeline.py:313-350): pairs whose status is not
     PAIR_OK are automatic failures (`register_test_failure`), the others are scored on pred_q = pred_pose_rel @ anchor_pose (fp32,
     pipeline.py:320) after the zero-pose rule.  objects[cls_id] = {'pts' [N,3] mm (float64), 'diameter' (BOP, mm), 'syms' [S,3,4]}.
     device: a torch device string -> per-pair errors from the HIP kernels (oryon_pose_metrics, oryon_pose_bop_errors); None -> the
     numpy restatements in this file.
     With evaluator.compute_vsd: depth = one [H,W] test depth image (millimetres) per pair, all of one size, and objects[cls_id] also
-    holds 'faces' [F,3] (zero-based indices into 'pts'); VSD comes from oryon_vsd_counts on the device, else from vsd_counts_np."""
+    holds 'faces' [F,3] (zero-based indices into 'pts'); VSD comes from oryon_vsd_counts on the device, else from vsd_counts_np.
+    validation: register through register_eval / register_valid_failure (the validation loop, pipeline.py:206-243: the same scores without
+    the id columns; the evaluator must have been reset with init_validation)."""
     n = len(status)
     vsd = evaluator.compute_vsd
     if vsd and depth is None:
@@ -477,14 +519,15 @@ def evaluate_batch(evaluator: Evaluator, *, pred_pose_rel: np.ndarray, anchor_po
     for i in range(n):
         ia = None if iou_a is None else float(iou_a[i])
         iq = None if iou_q is None else float(iou_q[i])
+        ids = {} if validation else dict(cls_id=cls_ids[i], instance_id=instance_ids[i])
         if i not in errs:
-            evaluator.register_test_failure(cls_id=cls_ids[i], instance_id=instance_ids[i], iou_a=ia, iou_q=iq)
+            (evaluator.register_valid_failure if validation else evaluator.register_test_failure)(iou_a=ia, iou_q=iq, **ids)
             continue
         o = objects[cls_ids[i]]
         rot, tr, add, ms, mp, ve = errs[i]
-        evaluator.register_test(pred_pose_rel=rel[i], rot_deg=rot, trans_cm=tr, add_s=add, add_diam=extent_diameter(o["pts"]) / 1000.0,
-                                mssd_mm=ms, mspd_px=mp, bop_diam_mm=float(o["diameter"]), cls_id=cls_ids[i], instance_id=instance_ids[i],
-                                iou_a=ia, iou_q=iq, vsd_errs=ve)
+        (evaluator.register_eval if validation else evaluator.register_test)(
+            pred_pose_rel=rel[i], rot_deg=rot, trans_cm=tr, add_s=add, add_diam=extent_diameter(o["pts"]) / 1000.0, mssd_mm=ms, mspd_px=mp,
+            bop_diam_mm=float(o["diameter"]), iou_a=ia, iou_q=iq, vsd_errs=ve, **ids)
 
 
 def extent_diameter(pts: np.ndarray) -> float:

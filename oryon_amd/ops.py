@@ -679,6 +679,56 @@ def ransac_register(src: torch.Tensor, tgt: torch.Tensor, n: torch.Tensor, max_i
 
 
 @_on_tensor_device
+def feature_loss(feat_a: torch.Tensor, feat_q: torch.Tensor, corrs: torch.Tensor, valid: torch.Tensor, pool: Optional[torch.Tensor] = None,
+                 pos_margin: float = 0.2, neg_margin: float = 0.9, neg_kernel: float = 5.0, pool_per_positive: bool = False,
+                 workspace: Optional[torch.Tensor] = None):
+    """feat_a, feat_q [B,C,FH,FW] fp32, corrs [B,N,4] int32 feature-map pixels (y_a,x_a,y_q,x_q), valid [B] int32 ->
+    dict(d_pos [B,N], d_neg [B,2,N], neg_idx [B,2,N] int32 linear pixels, pair_terms [B,3], losses [3] = pos, neg_a, neg_q).
+    pool [B,2,n_pool] int32 linear pixels: the candidates of the hardest-negative search (None = the whole map, row-major), or with
+    pool_per_positive the negative of every positive itself ([B,2,N]).  Definition: include/oryon_hip.h, oryon_feature_loss."""
+    dev = _lib.require_gpu(feat_a.device)
+    assert feat_a.dtype == torch.float32 and feat_q.dtype == torch.float32 and feat_a.shape == feat_q.shape and feat_a.dim() == 4
+    assert corrs.dtype == torch.int32 and corrs.dim() == 3 and corrs.shape[2] == 4 and corrs.shape[0] == feat_a.shape[0]
+    assert valid.dtype == torch.int32 and tuple(valid.shape) == (feat_a.shape[0],)
+    B, C, FH, FW = feat_a.shape
+    N = corrs.shape[1]
+    n_pool = 0
+    if pool is not None:
+        assert pool.dtype == torch.int32 and pool.dim() == 3 and tuple(pool.shape[:2]) == (B, 2)
+        n_pool = pool.shape[2]
+    need = lib().oryon_feature_loss_workspace_bytes(B, N, n_pool)
+    if need == 0 and B > 0:
+        raise _lib.OryonError(f"oryon_feature_loss_workspace_bytes({B}, {N}, {n_pool}): shape not supported")
+    ws = workspace if workspace is not None else torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    d_pos = torch.empty((B, N), dtype=torch.float32, device=dev)
+    d_neg = torch.empty((B, 2, N), dtype=torch.float32, device=dev)
+    neg_idx = torch.empty((B, 2, N), dtype=torch.int32, device=dev)
+    pair_terms = torch.empty((B, 3), dtype=torch.float32, device=dev)
+    losses = torch.empty((3,), dtype=torch.float32, device=dev)
+    check(lib().oryon_feature_loss(ptr(feat_a), ptr(feat_q), B, C, FH, FW, ptr(corrs), N, ptr(valid), ptr(pool), n_pool,
+                                   1 if pool_per_positive else 0, float(pos_margin), float(neg_margin), float(neg_kernel), ptr(ws), ws.numel(),
+                                   ptr(d_pos), ptr(d_neg), ptr(neg_idx), ptr(pair_terms), ptr(losses), stream_ptr(dev)), "oryon_feature_loss")
+    return dict(d_pos=d_pos, d_neg=d_neg, neg_idx=neg_idx, pair_terms=pair_terms, losses=losses)
+
+
+@_on_tensor_device
+def mask_dice_sums(logits: torch.Tensor, gt: torch.Tensor, threshold: float):
+    """logits [B,H,W] fp32, gt [B,H,W] (non-zero = object, at the logits' size) -> (sums [B,4] float64 = sum p, sum p^2, sum p t, sum t
+    with p = sigmoid(2 logits); mask [B,H,W] int32 = sigmoid(logits) > threshold; counts [B,2] int32 = |mask and gt|, |mask or gt|)."""
+    dev = _lib.require_gpu(logits.device)
+    assert logits.dim() == 3 and gt.shape == logits.shape
+    logits = logits.to(torch.float32).contiguous()
+    gt = gt.to(dev).to(torch.int32).contiguous()
+    B, H, W = logits.shape
+    sums = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    mask = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    check(lib().oryon_mask_dice_sums(ptr(logits), ptr(gt), B, H, W, float(threshold), ptr(sums), ptr(mask), ptr(counts), stream_ptr(dev)),
+          "oryon_mask_dice_sums")
+    return sums, mask, counts
+
+
+@_on_tensor_device
 def pose_metrics(pred_pose: torch.Tensor, gt_pose: torch.Tensor, model_pts: torch.Tensor, pts_offset: Optional[torch.Tensor] = None,
                  model_of_pair: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pred/gt [B,4,4] (metres), model_pts [M,3] (or the concatenation of several models with pts_offset [n+1] int32 and

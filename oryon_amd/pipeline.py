@@ -8,8 +8,13 @@
     test_step(batch, batch_idx)                       # per-sample loop, host RNG: reference semantics
     test_step_batched(batch, first_pair_index=0)      # same work for the whole batch with no host sync
 
-Training, logging, the evaluator (ADD/VSD) and the dataloaders of the reference are out of scope
-(SURVEY.md §2.1).  Config flags keep the names of configs/config.yaml.
+and the validation step (pipeline.py:196-247, 579-590):
+
+    on_validation_start(objects=None) / validation_step(batch, batch_idx) -> (loss, log) / on_validation_end() -> dict
+    reduce_losses(losses) -> (loss, weighted losses)
+
+Training, logging and the dataloaders of the reference are out of scope.  Config flags keep the names of
+configs/config.yaml.
 """
 from __future__ import annotations
 
@@ -30,12 +35,13 @@ from .pointdsc import PointDSC, get_pointdsc_pose
 def default_args(**overrides) -> SimpleNamespace:
     """The hot-path subset of configs/config.yaml (same names, same defaults)."""
     args = SimpleNamespace(
-        device="cuda", corrs_device="cpu", seed=1,
+        device="cuda", corrs_device="cpu", seed=1, debug_valid=False,
         dataset=SimpleNamespace(img_size=[224, 224], max_corrs=500),
         model=SimpleNamespace(image_encoder=SimpleNamespace(img_size=[192, 192], out_channels=32)),
         test=SimpleNamespace(mask="predicted", src_sampling=5000, solver=default_solver(), n_corrs=500, dist_th=0.25,
                              mask_threshold=0.5),
-        loss=SimpleNamespace(hard_negatives=True),
+        loss=SimpleNamespace(hard_negatives=True, pos_margin=0.2, neg_margin=0.9, neg_kernel_size=5, mask_type="dice",
+                             w={"mask": 1.0, "pos": 0.5, "neg": 0.5}),
     )
     for k, v in overrides.items():
         node = args
@@ -81,6 +87,12 @@ class Pipeline:
         self.pred_lines: List[str] = []
         self.failures: List[str] = []
         self._engine: Optional[MatchPoseEngine] = None
+        self._feature_loss = None
+        self.evaluator = None
+        self._valid_objects: Optional[Dict] = None
+        self._valid_log: List[Dict[str, float]] = []
+        self._valid_fmr: List[float] = []
+        self.last_validation: Optional[Dict] = None      # the latest validation_step's {'poses', 'status', 'results', 'losses'}
 
     # ------------------------------------------------------------------ mask post-processing (losses.py:56-60)
     def mask_results(self, batch: Dict, outputs: Dict) -> Dict[str, Tensor]:
@@ -263,4 +275,119 @@ class Pipeline:
         out["pred_q"] = torch.bmm(out["pose"], anchor_pose)
         if res is not None:
             out["iou_a"], out["iou_q"] = res["iou_a"], res["iou_q"]
+        return out
+
+    # ------------------------------------------------------------------ validation (pipeline.py:196-247, 579-590)
+    @property
+    def feature_loss(self):
+        """The reference's `self.feature_loss` (pipeline.py:60), built on first use."""
+        if self._feature_loss is None:
+            from .losses import FeatureLoss
+            self._feature_loss = FeatureLoss(self.args, self.device)
+        return self._feature_loss
+
+    def reduce_losses(self, losses: Dict) -> Tuple[Tensor, Dict]:
+        """pipeline.py:579-590: every loss times its weight `loss.w[k]`, and their sum."""
+        w_losses = {}
+        final_loss = 0.0
+        weights = self.args.loss.w
+        for k in losses.keys():
+            w_loss = losses[k] * weights[k]
+            final_loss = final_loss + w_loss
+            w_losses[k] = w_loss
+        return final_loss, w_losses
+
+    def on_validation_start(self, objects: Optional[Dict] = None, compute_vsd: bool = False) -> None:
+        """A fresh evaluator in validation mode (evaluator.init_validation).  objects[cls_id] = {'pts' [N,3] mm, 'diameter' mm (BOP),
+        'syms' [S,3,4]} as evaluation.evaluate_batch takes them (the reference's add_object_info of the validation dataset); None = one
+        stand-in model for every class, a 512-point sphere of 0.2 m, what the synthetic drivers score against."""
+        from .evaluation import Evaluator
+        self.evaluator = Evaluator(exp_tag="valid", compute_iou=True, compute_vsd=compute_vsd)
+        self.evaluator.init_validation()
+        self._valid_objects = dict(objects) if objects is not None else None
+        self._valid_log, self._valid_fmr = [], []
+        self.last_validation = None
+
+    def add_validation_objects(self, objects: Dict) -> None:
+        """More object models for the running validation pass (the reference's add_object_info, called as classes turn up)."""
+        self._valid_objects = {**(self._valid_objects or {}), **objects}
+
+    @staticmethod
+    def _stand_in_object() -> Dict:
+        sphere = np.random.default_rng(0).normal(size=(512, 3))
+        sphere = 100.0 * sphere / np.linalg.norm(sphere, axis=1, keepdims=True)
+        return {"pts": sphere, "diameter": 200.0, "syms": np.eye(3, 4)[None]}
+
+    def gt_featmap_corrs(self, batch: Dict, net_output: Dict, idx: int) -> Tensor:
+        """The batch's ground-truth correspondences of pair idx in feature-map pixels [N,4] (losses.py:77-78)."""
+        from .losses import batch_corrs, featmap_corrs
+        CH, CW = batch["anchor"]["rgb"].shape[2:]
+        FH, FW = net_output["featmap_a"].shape[2:]
+        return featmap_corrs(batch_corrs(batch)[idx:idx + 1], (CH, CW), (FH, FW))[0]
+
+    def validation_step(self, batch: Dict, batch_idx: int = 0):
+        """pipeline.py:196-247: forward, feature_loss.forward, then per pair is_detection_valid -> get_featmap_corrs -> get_pose ->
+        evaluator.register_eval, or register_valid_failure; returns (the weighted loss, {'valid/mask', 'valid/pos', 'valid/neg',
+        'valid/loss'}) - what the reference returns and what its structured_log records.  The masks fed to the matcher follow test.mask.
+        args.debug_valid: the pose is solved from the batch's GROUND-TRUTH correspondences (rescaled to the feature-map frame, the same
+        get_pose) instead of the matcher's; a pair with valid != 1 goes to the failure path.  That is what the flag's comment in
+        configs/config.yaml:11 promises; the reference at this commit only prints a warning (pipeline.py:293-294) and changes the
+        sampling of its datasets (datasets.py:126-127)."""
+        from .evaluation import evaluate_batch, fmr_from_distances
+        if self.evaluator is None:
+            self.on_validation_start()
+        outputs = self.model.forward(batch)
+        losses, results = self.feature_loss.forward(batch, outputs)
+        BS = outputs["featmap_a"].shape[0]
+        poses, status = [], []
+        for i_b in range(BS):
+            st, pred_pose = PAIR_OK, torch.eye(4)
+            if self.args.debug_valid:
+                if int(batch["valid"][i_b]) == 1:
+                    pred_pose = self.get_pose(batch, self.gt_featmap_corrs(batch, outputs, i_b), idx=i_b)
+                else:
+                    st = PAIR_NO_CORR
+            elif self.is_detection_valid(results, batch, i_b):
+                pred_corrs, _, _ = self.get_featmap_corrs(batch, outputs, results, idx=i_b)
+                if pred_corrs is not None:
+                    pred_pose = self.get_pose(batch, pred_corrs, idx=i_b)
+                else:
+                    st = PAIR_NO_CORR
+            else:
+                st = PAIR_NO_MASK
+            poses.append(pred_pose.cpu())
+            status.append(st)
+        cls_ids = list(batch["cls_id"])
+        objects = self._valid_objects
+        if objects is None:
+            stand_in = self._stand_in_object()
+            objects = {k: stand_in for k in dict.fromkeys(cls_ids)}
+        depth = None
+        if self.evaluator.compute_vsd:
+            depth = [np.asarray(d.squeeze().cpu().numpy(), dtype=np.float32) for d in batch["query"]["eval_depth"]]
+        evaluate_batch(self.evaluator, pred_pose_rel=torch.stack(poses).numpy(), anchor_pose=batch["anchor"]["pose"].cpu().numpy(),
+                       gt_pose=batch["query"]["pose"].cpu().numpy(), K=batch["query"]["camera"].cpu().numpy().reshape(-1, 3, 3),
+                       status=status, cls_ids=cls_ids, instance_ids=[None] * BS, objects=objects,
+                       iou_a=results["iou_a"].cpu().numpy(), iou_q=results["iou_q"].cpu().numpy(), device=self.device, depth=depth,
+                       validation=True)
+        loss, w_losses = self.reduce_losses(losses)
+        log = {"valid/" + k: v for k, v in w_losses.items()}
+        log["valid/loss"] = loss
+        self._valid_log.append({k: float(v) for k, v in log.items()})
+        keep = [i for i in range(BS) if int(batch["valid"][i]) == 1]
+        if keep:
+            self._valid_fmr.extend(fmr_from_distances(results["d_pos"][keep], self.args.test.dist_th, 0.05).tolist())
+        self.last_validation = dict(poses=poses, status=status, results=results, losses=losses)
+        return loss, log
+
+    def on_validation_end(self) -> Dict:
+        """The epoch's summary: the means of the logged (weighted) losses, FMR at (test.dist_th, 0.05) over the valid pairs, the
+        evaluator's means and its failure counts."""
+        out: Dict[str, object] = {}
+        for k in ("valid/mask", "valid/pos", "valid/neg", "valid/loss"):
+            out[k] = float(np.mean([r[k] for r in self._valid_log])) if self._valid_log else None
+        out["FMR"] = float(np.mean(self._valid_fmr)) if self._valid_fmr else None
+        if self.evaluator is not None:
+            out.update(self.evaluator.get_means())
+            out.update({k: int(sum(v)) for k, v in self.evaluator.counts.items()})
         return out

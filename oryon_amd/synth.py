@@ -49,15 +49,9 @@ def smooth_field(index: int, H: int, W: int, C: int, dev: torch.device, salt: in
     return (basis @ coef.reshape(coef.shape[0], H * W)).contiguous()
 
 
-def make_pair(index: int, H: int, W: int, C: int, device: str = "cpu", noise: float = 0.05,
-              feat_dtype: torch.dtype = torch.float32, smooth: float = 0.0) -> Dict[str, torch.Tensor]:
-    """One synthetic pair.  Returns feat_a/feat_q [C,H,W], mask_a/mask_q [H,W] int32,
-    depth_a/depth_q [H,W] fp32 (mm), camera [3,3] fp64, sizes (H,W), pose [4,4] fp64 (metres,
-    maps anchor-camera points to query-camera points).
-    smooth > 0: the Gaussian descriptors become `smooth` x N(0,1) noise on top of rank-8 smooth fields (one for the anchor map, another
-    for the query background); the re-projected query pixels still carry their anchor pixel's descriptor + `noise` x N(0,1), so the
-    geometry (and the ground-truth pose) is unchanged while every anchor now has a crowd of near-ties around its true match."""
-    dev = torch.device(device)
+def _pair_geometry(index: int, H: int, W: int):
+    """The closed-form geometry of pair `index`: (R, t, c, D_a [H,W], K, winner [HW] = the anchor pixel whose re-projection owns each
+    query pixel or -1, hit = winner >= 0, D_q [HW])."""
     g = torch.Generator(device="cpu")
     g.manual_seed(1000 + index)
     axis = torch.randn(3, generator=g, dtype=torch.float64)
@@ -86,6 +80,20 @@ def make_pair(index: int, H: int, W: int, C: int, device: str = "cpu", noise: fl
     hit = winner >= 0
     D_q = torch.zeros(H * W, dtype=torch.float64)
     D_q[hit] = P_q[winner[hit], 2]
+
+    return R, t, c, D_a, K, winner, hit, D_q
+
+
+def make_pair(index: int, H: int, W: int, C: int, device: str = "cpu", noise: float = 0.05,
+              feat_dtype: torch.dtype = torch.float32, smooth: float = 0.0) -> Dict[str, torch.Tensor]:
+    """One synthetic pair.  Returns feat_a/feat_q [C,H,W], mask_a/mask_q [H,W] int32,
+    depth_a/depth_q [H,W] fp32 (mm), camera [3,3] fp64, sizes (H,W), pose [4,4] fp64 (metres,
+    maps anchor-camera points to query-camera points).
+    smooth > 0: the Gaussian descriptors become `smooth` x N(0,1) noise on top of rank-8 smooth fields (one for the anchor map, another
+    for the query background); the re-projected query pixels still carry their anchor pixel's descriptor + `noise` x N(0,1), so the
+    geometry (and the ground-truth pose) is unchanged while every anchor now has a crowd of near-ties around its true match."""
+    dev = torch.device(device)
+    R, t, c, D_a, K, winner, hit, D_q = _pair_geometry(index, H, W)
 
     gd = torch.Generator(device=dev)
     gd.manual_seed(7000 + index)
@@ -123,6 +131,27 @@ def make_batch(first_index: int, B: int, H: int, W: int, C: int, device: str = "
         out[k] = torch.stack([it[k] for it in items])
     out["sizes"] = (H, W)
     return out
+
+
+def pair_gt_corrs(index: int, H: int, W: int, max_corrs: int) -> torch.Tensor:
+    """Ground-truth correspondences of pair `index` as the generator itself made them: [n,4] int64 rows (y_a, x_a, y_q, x_q), one per
+    query pixel (y_q, x_q) that carries the descriptor of its winning anchor pixel (y_a, x_a) with the anchor pixel inside mask_a, in
+    H x W pixels.  More than max_corrs candidates are thinned to max_corrs by a permutation seeded with the index (sorted back into
+    row-major order), as the reference's loaders sample `dataset.max_corrs` of a pair's correspondences; n can be smaller."""
+    _, _, _, _, _, winner, hit, _ = _pair_geometry(index, H, W)
+    tgt = torch.nonzero(hit).flatten()
+    src = winner[tgt]
+    ya, xa = src // W, src % W
+    h0, w0 = H // 4, W // 4
+    inside = (ya >= h0) & (ya < h0 + H // 2) & (xa >= w0) & (xa < w0 + W // 2)
+    tgt, ya, xa = tgt[inside], ya[inside], xa[inside]
+    corrs = torch.stack([ya, xa, tgt // W, tgt % W], dim=1)
+    if corrs.shape[0] > max_corrs:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(5000 + index)
+        keep = torch.randperm(corrs.shape[0], generator=g)[:max_corrs].sort().values
+        corrs = corrs[keep]
+    return corrs
 
 
 # ------------------------------------------------------------------------------------------------ VSD fixtures (closed form, no RNG)

@@ -18,6 +18,8 @@ Reference entry points executed here:
   utils/geo6d.py              best_fit_transform_with_RANSAC (gen_ransac; `python tools/gen_goldens.py ransac`)
   utils/evaluator.py          Evaluator(compute_vsd=True) + bop_toolkit_lib/pose_error.py vsd, misc.py, visibility.py (gen_vsd;
                               `python tools/gen_goldens.py vsd`; the OpenGL renderer is stood in for by evaluation.rasterize_depth)
+  losses.py                   FeatureLoss.forward (sample_positives, sample_hardest_negatives, sample_negatives, mask_loss) and
+                              utils/metrics.py compute_fmr (gen_feature_loss; `python tools/gen_goldens.py floss`)
 """
 import json
 import os
@@ -791,6 +793,173 @@ def gen_vsd():
          latex=np.array(ev.get_latex_str()), latex_no_vsd=np.array(ev0.get_latex_str()), **out)
 
 
+# ---------------------------------------------------------------------------------------------- validation step (floss_*)
+def gen_feature_loss():
+    """floss_*.npz: the reference's FeatureLoss.forward (losses.py:64-141) run for real on the CPU - the form that is fp32 throughout -
+    on seeded inputs, with the stubs of SURVEY Appendix C plus permissive ones for the packages utils/metrics.py imports and never
+    calls here.  Stored per fixture: the maps (fp16-valued, as float16), corrs, valid, the pool tables the run drew, logits and
+    ground-truth masks; the reference's losses, results and per-correspondence distances; compute_fmr of the positives; the float64
+    top-2 gap of every row's penalised cost.
+    Asserted (a seed that misses is redrawn):
+      * every row of a fixture in GAP has a top-2 gap >= 1e-5 - except rows whose positive descriptor is zero: all their costs are
+        exactly 0.5 in any arithmetic (every product is 0), the lowest unpenalised position wins, `gap_exempt` marks them;
+      * fixtures outside GAP (penalised ties are their point): no PENALISED candidate's float64 cost d + penalty lies within 1e-5 of
+        the midpoint of two neighbouring float32 values, so the float32 sum rounds the same way whatever the last bits of d; a row
+        that has unpenalised candidates (one of them wins) has its gap >= 1e-5 like everywhere else."""
+    class _Any(types.ModuleType):
+        def __getattr__(self, k):
+            if k.startswith("__"):
+                raise AttributeError(k)
+            return type(k, (), {})
+    for name in ("tqdm", "sklearn", "sklearn.neighbors", "scipy.optimize"):
+        try:
+            __import__(name)
+        except ImportError:
+            sys.modules[name] = _Any(name)
+    if isinstance(sys.modules.get("tqdm"), _Any):
+        sys.modules["tqdm"].tqdm = lambda x, *a, **k: x
+    import losses as ref_losses  # noqa: E402  (reference)
+    from utils.metrics import compute_fmr as ref_fmr  # noqa: E402  (reference)
+    from types import SimpleNamespace as NS
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import feature_loss_restatement as fr  # noqa: E402  (ours)
+
+    # tag, B, invalid pairs, C, (FH, FW), image, N, hard negatives
+    cases = [("1_rescale", 3, (1,), 32, (40, 40), 48, 64), ("2_nonsquare", 2, (), 20, (40, 44), 48, 37),
+             ("3_pool", 2, (), 32, (48, 48), 56, 500), ("4_c256", 1, (), 256, (16, 16), 32, 64), ("5_disc", 1, (), 8, (6, 6), 6, 16),
+             ("6_zero_dup_border", 2, (), 32, (24, 24), 24, 32), ("7_none_valid", 2, (0, 1), 32, (24, 24), 24, 32)]
+    GAP = ("1_rescale", "2_nonsquare", "3_pool", "4_c256", "6_zero_dup_border")
+    args = NS(loss=NS(pos_margin=0.2, neg_margin=0.9, neg_kernel_size=5, hard_negatives=True, mask_type="dice"), test=NS(mask_threshold=0.5))
+    real_multinomial, real_cuda = torch.multinomial, torch.Tensor.cuda
+    for tag, B, invalid, C, (FH, FW), IMG, N in cases:
+        for seed in range(100, 400):
+            g = torch.Generator().manual_seed(seed)
+            corrs = torch.randint(0, IMG, (B, N, 4), generator=g)
+            if tag == "6_zero_dup_border":
+                corrs[:, 1] = corrs[:, 0]                                  # duplicates
+                corrs[:, 2] = torch.tensor([0, 0, IMG - 1, IMG - 1])       # the corners
+                corrs[:, 3] = torch.tensor([IMG - 1, 0, 0, IMG - 1])
+                corrs[:, 4, :2] = torch.tensor([12, 12])
+            fa = torch.randn(B, C, FH, FW, generator=g)
+            fq = torch.randn(B, C, FH, FW, generator=g)
+            pix = torch.from_numpy(fr.feature_pixels(corrs.numpy(), (IMG, IMG), (FH, FW)))
+            for b in range(B):                                              # query = anchor + noise of a per-correspondence size
+                nz = torch.rand(N, generator=g) * 1.5
+                fq[b][:, pix[b, :, 2], pix[b, :, 3]] = fa[b][:, pix[b, :, 0], pix[b, :, 1]] + nz[None] * torch.randn(C, N, generator=g)
+            if tag == "6_zero_dup_border":
+                fa[0][:, 12, 12] = 0.0                                      # a zero descriptor at a positive (corrs[0, 4]) ...
+                fa[1][:, 3, 17] = 0.0                                       # ... and one that is only in the pool
+                fq[1][:, 20, 5] = 0.0
+            fa, fq = fa.half().float(), fq.half().float()
+            logits_a = (3.0 * torch.randn(B, 1, FH, FW, generator=g)).half().float()
+            logits_q = (3.0 * torch.randn(B, 1, FH, FW, generator=g)).half().float()
+            yy, xx = torch.meshgrid(torch.arange(IMG), torch.arange(IMG), indexing="ij")
+            gt_a = torch.stack([((yy - IMG // 2 - b) ** 2 + (xx - IMG // 2) ** 2 < (IMG // 3) ** 2).float() for b in range(B)])
+            gt_q = torch.stack([((yy > IMG // 4) & (yy < IMG - 2 - b) & (xx > IMG // 5)).float() for b in range(B)])
+            valid = torch.tensor([0.0 if b in invalid else 1.0 for b in range(B)])
+            batch = {"corrs": corrs.clone(), "valid": valid, "anchor": {"rgb": torch.zeros(B, 3, IMG, IMG), "mask": gt_a},
+                     "query": {"rgb": torch.zeros(B, 3, IMG, IMG), "mask": gt_q}}
+            outputs = {"featmap_a": fa, "featmap_q": fq, "mask_a": logits_a, "mask_q": logits_q}
+            drawn = []
+
+            def recording_multinomial(*a, **k):
+                r = real_multinomial(*a, **k)
+                drawn.append(r.clone())
+                return r
+            floss = ref_losses.FeatureLoss(args, "cpu")
+            torch.manual_seed(seed)
+            torch.multinomial, torch.Tensor.cuda = recording_multinomial, (lambda self, *a, **k: self)    # losses.py:109-111 on a CPU host
+            try:
+                t0 = time.perf_counter()
+                losses, results = floss.forward(batch, outputs)
+                t_ref = time.perf_counter() - t0
+            finally:
+                torch.multinomial, torch.Tensor.cuda = real_multinomial, real_cuda
+            n_valid = int(valid.sum())
+            HW = FH * FW
+            pool = None
+            if HW > 2000:
+                assert len(drawn) == 2 * n_valid
+                pool = torch.zeros(B, 2, 2000, dtype=torch.int64)
+                it = iter(drawn)
+                for side in (0, 1):
+                    for b in range(B):
+                        if valid[b] == 1:
+                            pool[b, side] = next(it)
+            # per-correspondence distances with the reference's own expressions (losses.py:82,91-93)
+            gtc = torch.clamp(ref_losses.rescale_coords(corrs.clone(), (IMG, IMG), (FH, FW)), min=0, max=FH - 1)
+            assert np.array_equal(gtc.numpy(), pix.numpy()), "coordinate restatement differs from the reference"
+            pos_a, pos_q = floss.sample_positives(fa, fq, gtc, valid)
+
+            def rows_at(fm, yx):
+                yx = yx.long()
+                return torch.stack([fm[b][:, yx[b, :, 0], yx[b, :, 1]].T for b in range(B)])
+            d_pos = 0.5 * (-1 * F.cosine_similarity(pos_a, pos_q, dim=2) + 1)
+            d_neg_a = 0.5 * (-1 * F.cosine_similarity(pos_a, rows_at(fa, results["neg_a"]), dim=2) + 1)
+            d_neg_q = 0.5 * (-1 * F.cosine_similarity(pos_q, rows_at(fq, results["neg_q"]), dim=2) + 1)
+            for b in range(B):
+                if valid[b] != 1:
+                    d_pos[b], d_neg_a[b], d_neg_q[b] = 0.0, 0.0, 0.0
+            fmr = ref_fmr(pos_a, pos_q, 0.25, 0.05).numpy()
+            # float64 costs: gaps, margins to the float32 rounding boundaries
+            gap = np.full((B, 2, N), np.inf)
+            exempt = np.zeros((B, 2, N), dtype=bool)
+            margin = np.inf
+            for b in range(B):
+                if valid[b] != 1:
+                    continue
+                for side, fm in ((0, fa), (1, fq)):
+                    rows = fr.unit(fm[b].reshape(C, HW).T.double().numpy())
+                    pl = np.arange(HW) if pool is None else pool[b, side].numpy()
+                    yx = pix[b].numpy()[:, 2 * side:2 * side + 2]
+                    p = rows[yx[:, 0] * FW + yx[:, 1]]
+                    d = 0.5 * (1.0 - p @ rows[pl].T)
+                    for n in range(N):
+                        pen = fr.penalty32(yx[n, 0], yx[n, 1], pl // FW, pl % FW, 5).astype(np.float64)
+                        c = np.sort(d[n] + pen)
+                        gap[b, side, n] = c[1] - c[0]
+                        exempt[b, side, n] = not p[n].any()
+                        if tag not in GAP and (pen == 0).any() and gap[b, side, n] < 1e-5:
+                            margin = 0.0                                    # an unpenalised winner needs its gap like everywhere else
+                        if tag not in GAP:
+                            v = (d[n] + pen)[pen > 0]
+                            if v.size == 0:
+                                continue
+                            f32 = v.astype(np.float32)
+                            lo = np.minimum(f32, np.nextafter(f32, np.float32(-np.inf))).astype(np.float64)
+                            hi = np.maximum(f32, np.nextafter(f32, np.float32(np.inf))).astype(np.float64)
+                            mids = np.stack([(f32.astype(np.float64) + lo) / 2, (f32.astype(np.float64) + hi) / 2])
+                            margin = min(margin, float(np.abs(mids - v[None]).min()))
+            if tag in GAP and not (gap[~exempt] >= 1e-5).all():
+                continue
+            if tag not in GAP and not margin >= 1e-5:
+                continue
+            r = fr.restate(fa.numpy(), fq.numpy(), corrs.numpy(), valid.numpy(), (IMG, IMG), None if pool is None else pool.numpy())
+            want_idx = np.stack([results["neg_a"].numpy(), results["neg_q"].numpy()], axis=1)
+            got_idx = np.stack([r["neg_idx"] // FW, r["neg_idx"] % FW], axis=-1)
+            assert np.array_equal(want_idx, got_idx), (tag, seed, "restatement argmin differs from the reference")
+            if tag == "6_zero_dup_border":
+                assert exempt.sum() == 1 and exempt[0, 0, 4]
+            if tag == "5_disc":                         # the point of the fixture: some positive has its whole pool inside the disc
+                yx = pix[0].numpy()
+                far = [(np.hypot(np.arange(HW) // FW - y, np.arange(HW) % FW - x) >= 5).any() for y, x in yx[:, :2]]
+                if all(far):
+                    continue
+            print(f"floss_{tag}: seed {seed}, min gap {gap[~exempt].min() if (~exempt).any() and np.isfinite(gap).any() else float('nan'):.2e}, "
+                  f"losses {[float(losses[k]) for k in ('mask', 'pos', 'neg')]}, reference forward {t_ref:.3f} s on this host")
+            save(f"floss_{tag}", feat_a=fa.numpy().astype(np.float16), feat_q=fq.numpy().astype(np.float16), corrs=corrs.numpy().astype(np.int32),
+                 valid=valid.numpy(), image_hw=np.array([IMG, IMG], np.int32), pool=(np.zeros((0,), np.int32) if pool is None else pool.numpy().astype(np.int32)),
+                 logits_a=logits_a.numpy().astype(np.float16), logits_q=logits_q.numpy().astype(np.float16), gt_a=gt_a.numpy().astype(np.uint8),
+                 gt_q=gt_q.numpy().astype(np.uint8), seed=np.int64(seed),
+                 loss_mask=np.float32(losses["mask"]), loss_pos=np.float32(losses["pos"]), loss_neg=np.float32(losses["neg"]),
+                 neg_a=results["neg_a"], neg_q=results["neg_q"], mask_a=results["mask_a"].numpy().astype(np.uint8),
+                 mask_q=results["mask_q"].numpy().astype(np.uint8), iou_a=results["iou_a"], iou_q=results["iou_q"],
+                 d_pos=d_pos, d_neg_a=d_neg_a, d_neg_q=d_neg_q, fmr=fmr, gap=gap, gap_exempt=exempt, has_gap=np.bool_(tag in GAP))
+            break
+        else:
+            raise RuntimeError(f"floss_{tag}: no seed satisfies the fixture's conditions")
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["matcher", "lift", "kabsch", "pointdsc", "e2e", "backbone", "metrics", "bop", "tokenizer", "data"]
     if "data" in which:
@@ -819,3 +988,5 @@ if __name__ == "__main__":
         gen_ransac()
     if "vsd" in which:
         gen_vsd()
+    if "floss" in which:
+        gen_feature_loss()
