@@ -452,6 +452,39 @@ int oryon_mask_dice_sums(const float *logits, const int32_t *gt, int B, int H, i
                          int32_t *counts, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Training step: the backward pass of the two entries above (what torch autograd does to losses.py:64-141 and utils/losses/dice.py:27-89
+ *         in the reference's training_step, pipeline.py:170-181).  Two launches and two memsets for the maps, one launch for a mask; no
+ *         allocation, no synchronisation, no float atomics: the bytes of every output depend on the pair's inputs and on g alone.
+ * Notation: eps = 1e-8, u^ = u / max(|u|, eps), d(u,v) = 0.5 (1 - <u^, v^>), V = number of pairs with valid == 1, N = n_corr.
+ * g [3] fp32 ON THE DEVICE: the upstream gradients (g_pos, g_neg_a, g_neg_q) of the three entries of `losses`; never read by the host.
+ * Cosine: for |u| >= eps, d<u^,v^>/du = (v^ - <u^,v^> u^) / |u|; for |u| < eps the clamped norm is a constant and d/du = v^ / eps
+ *         without the projection term; a zero partner v has v^ = 0 and gives no gradient (torch's cosine_similarity, losses.py:91-93).
+ * Margins: the relu subgradient is strict.  A row contributes through d_pos only if d_pos - pos_margin > 0 and through d_neg_s only if
+ *         neg_margin - d_neg_s > 0, both subtractions in fp32 on the forward's own d_pos / d_neg (losses.py:95-101), so backward and
+ *         forward never disagree about a row.  alpha_n = g_pos / (V N), beta_{s,n} = -g_neg_s / (V N) (the means of losses.py:95-111).
+ * Negatives: neg_idx [B,2,N] (the forward's) is a constant, the argmin is not differentiated; the negative's descriptor is a gather
+ *         from the same map, so gradient flows to its pixel.  An index outside [0, FH*FW) names no pixel: a zero row, no gradient.
+ * Per pair b and side s, with u_n the side's positive, v_n the other side's positive, w_n the side's negative, 2 N slots:
+ *         slot n     at the positive's pixel = alpha_n d d_pos/d u_n + beta_{s,n} d d(u_n,w_n)/d u_n  (added in that order)
+ *         slot N + n at the negative's pixel = beta_{s,n} d d(u_n,w_n)/d w_n
+ *         (each evaluated in float64 from the fp32 maps and rounded once to fp32).  grad_s[b,:,y,x] = the sum of the slots at that
+ *         pixel in ascending slot order, in fp32; every other element is exactly 0; a pair with valid != 1 gets an all-zero map.
+ * feat_a, feat_q, corrs, valid as oryon_feature_loss takes them (C <= 256, n_corr <= 4096); grad_a, grad_q [B,C,FH,FW] fp32.
+ * workspace: oryon_feature_loss_grad_workspace_bytes(B, C, n_corr) bytes (the 2 N contribution vectors of every pair and side). */
+size_t oryon_feature_loss_grad_workspace_bytes(int B, int C, int n_corr);
+int oryon_feature_loss_grad(const float *feat_a, const float *feat_q, int B, int C, int FH, int FW, const int32_t *corrs, int n_corr,
+                            const int32_t *valid, const int32_t *neg_idx, const float *d_pos, const float *d_neg, const float *g,
+                            float pos_margin, float neg_margin, void *workspace, size_t workspace_bytes, float *grad_a, float *grad_q,
+                            void *stream);
+/* Backward of the dice mask loss (utils/losses/dice.py:27-89 with weight [0.5, 0.5] as losses.py:40-62 builds it) of B images.
+ * logits, gt as oryon_mask_dice_sums takes them; sums [B,4] float64 = that call's output; g_mask [1] fp32 ON THE DEVICE.
+ * With p = sigmoid(2x), q = 1 - p, u = 1 - t, D_f = S_pp + S_t + 1, D_b = S_qq + S_u + 1 (S_qq, S_u, S_qu from the four sums and H W):
+ *     grad_logits_i = g_mask (0.25 / B) 2 p_i q_i [(-t_i / D_f + 2 p_i (S_pt + 1) / D_f^2) - (-u_i / D_b + 2 q_i (S_qu + 1) / D_b^2)]
+ * evaluated in float64, stored as fp32, for all B images (validity does not enter).  grad_logits [B,H,W] fp32. */
+int oryon_mask_dice_grad(const float *logits, const int32_t *gt, int B, int H, int W, const double *sums, const float *g_mask,
+                         float *grad_logits, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * The whole batched step as ONE call (round 3): what the per-sample loop of FPM_Pipeline.test_step does for every pair of a batch
  * (pipeline.py:313-355: is_detection_valid -> get_featmap_corrs [utils/pcd.py:177-216] -> get_pose [pipeline.py:429-472:
  * scale / validate / lift, get_pointdsc_pose]), for B pairs, enqueued from C++ on streams and events the engine owns, over a

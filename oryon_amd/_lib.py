@@ -159,6 +159,10 @@ _PROTOS = {
     "oryon_feature_loss": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, c_int, c_float, c_float, c_float, _P, c_size_t,
                                    _P, _P, _P, _P, _P, _P]),
     "oryon_mask_dice_sums": (c_int, [_P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, _P]),
+    "oryon_feature_loss_grad_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "oryon_feature_loss_grad": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, c_float, c_float, _P, c_size_t,
+                                        _P, _P, _P]),
+    "oryon_mask_dice_grad": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     "oryon_pointdsc_encode": (c_int, [c_void_p, _P, _P, _P, c_int, c_int, _P, c_size_t, _P, _P, _P]),
     "oryon_pointdsc_seeds": (c_int, [c_void_p, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "oryon_pointdsc_hypotheses": (c_int, [c_void_p, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P, _P,

@@ -353,12 +353,30 @@ class Evaluator:
         self.init_validation()
         self.metrics["instance_id"], self.metrics["cls_id"] = [], []
 
-    def init_validation(self) -> None:
-        """utils/evaluator.py:143-167: the lists of the test run without the `instance_id` / `cls_id` columns."""
+    def init_training(self) -> None:
+        """utils/evaluator.py:130-141: training keeps the IoU lists only."""
         self.metrics, self.counts = {}, {}
         if self.compute_iou:
             for k in ("Anchor IoU", "Query IoU", "Mean IoU", "IoU > .25", "IoU > .5", "IoU > .75"):
                 self.metrics[k] = []
+
+    def register_train(self, results: Dict, clear: bool = False) -> None:
+        """utils/evaluator.py:178-204: the IoUs of one training batch (`results` of FeatureLoss.forward: 'iou_a', 'iou_q' [B])."""
+        if clear:
+            self.init_training()
+        if self.compute_iou:
+            import torch
+            iou_a, iou_q = (np.asarray(torch.as_tensor(results[k]).detach().cpu().numpy()) for k in ("iou_a", "iou_q"))
+            mean = (iou_a + iou_q) / 2.0
+            self.metrics["Anchor IoU"].extend(iou_a.tolist())
+            self.metrics["Query IoU"].extend(iou_q.tolist())
+            self.metrics["Mean IoU"].extend(mean.tolist())
+            for k, th in (("IoU > .25", 0.25), ("IoU > .5", 0.5), ("IoU > .75", 0.75)):
+                self.metrics[k].extend((mean > th).astype(int).tolist())
+
+    def init_validation(self) -> None:
+        """utils/evaluator.py:143-167: the lists of the test run without the `instance_id` / `cls_id` columns."""
+        self.init_training()
         for k in ("R error", "T error", "ADD(S)-0.1d") + (("AR", "VSD") if self.compute_vsd else ()) + ("MSSD", "MSPD"):
             self.metrics[k] = []
         for k in ("Missing segm", "Failed pose", "Zero pose"):

@@ -1,5 +1,6 @@
-"""The reference's FeatureLoss (losses.py:12-263) at inference time: the contrastive terms and the dice mask loss of a whole batch on
-the HIP kernels of csrc/feature_loss.hip (ops.feature_loss, ops.mask_dice_sums), with the reference's names and return shapes.
+"""The reference's FeatureLoss (losses.py:12-263): the contrastive terms and the dice mask loss of a whole batch on the HIP kernels of
+csrc/feature_loss.hip (ops.feature_loss, ops.mask_dice_sums), with the reference's names and return shapes, and their backward pass on
+the kernels of csrc/feature_loss_grad.hip (ops.feature_loss_grad, ops.mask_dice_grad).
 
     FeatureLoss(args, device).forward(batch, net_output) -> (losses, results)
         losses  = {'mask', 'pos', 'neg'}                                                  (losses.py:124-128)
@@ -9,13 +10,21 @@ the HIP kernels of csrc/feature_loss.hip (ops.feature_loss, ops.mask_dice_sums),
 
 What stays in Python is what the reference does once per batch: the coordinate rescale (the reference's own torch expressions, on the
 device) and the random draws, which are made with the reference's calls in the reference's order so that a forward leaves the
-generators exactly where the reference's forward - and Pipeline.feature_loss_rng_draws - leaves them.  No backward pass exists."""
+generators exactly where the reference's forward - and Pipeline.feature_loss_rng_draws - leaves them.
+
+Backward.  With grad enabled and a map (a mask logit tensor) that requires grad, the contrastive part (the dice loss) goes through a
+torch.autograd.Function whose forward makes the same kernel calls and whose backward hands the upstream gradient to the gradient
+kernel as a device tensor (no host read; definition: include/oryon_hip.h, oryon_feature_loss_grad / oryon_mask_dice_grad).  The index of
+a negative is a constant; both functions are once_differentiable.  mask_type 'cross_entropy' is torch's own differentiable
+BCEWithLogitsLoss; 'lovasz' and 'focal' raise.  Under no_grad, or for inputs that do not require grad, nothing differs from the
+inference path: the same calls, the same bytes, the same random draws.  The entries of `results` are always detached."""
 from __future__ import annotations
 
 from typing import Dict, Tuple
 
 import torch
 from torch import Tensor
+from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
 
@@ -52,8 +61,52 @@ def batch_corrs(batch: Dict) -> Tensor:
     return torch.stack(list(corrs))
 
 
+def _dice_from_sums(sums: Tensor, hw: float) -> Tensor:
+    sp, spp, spt, st = sums[:, 0], sums[:, 1], sums[:, 2], sums[:, 3]
+    fg = 1.0 - (spt + 1.0) / (spp + st + 1.0)
+    # background: p' t' = 1 - p - t + p t, p'^2 = 1 - 2 p + p^2, t' = 1 - t, summed over the image
+    bg = 1.0 - ((hw - sp - st + spt) + 1.0) / ((hw - 2.0 * sp + spp) + (hw - st) + 1.0)
+    return (0.25 * (fg.mean() + bg.mean())).to(torch.float32)
+
+
+class _ContrastiveTerms(torch.autograd.Function):
+    """maps -> (losses [3], d_pos, d_neg, neg_idx, pair_terms): ops.feature_loss forward, ops.feature_loss_grad backward."""
+
+    @staticmethod
+    def forward(ctx, feat_a, feat_q, corrs, valid, pool, pos_margin, neg_margin, neg_kernel, per_positive):
+        out = ops.feature_loss(feat_a, feat_q, corrs, valid, pool, pos_margin, neg_margin, neg_kernel, pool_per_positive=per_positive)
+        ctx.save_for_backward(feat_a, feat_q, corrs, valid, out["neg_idx"], out["d_pos"], out["d_neg"])
+        ctx.margins = (pos_margin, neg_margin)
+        rest = (out["d_pos"], out["d_neg"], out["neg_idx"], out["pair_terms"])
+        ctx.mark_non_differentiable(*rest)
+        return (out["losses"],) + rest
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_):
+        feat_a, feat_q, corrs, valid, neg_idx, d_pos, d_neg = ctx.saved_tensors
+        g = g.to(feat_a.device, torch.float32).contiguous()
+        grad_a, grad_q = ops.feature_loss_grad(feat_a, feat_q, corrs, valid, neg_idx, d_pos, d_neg, g, *ctx.margins)
+        return (grad_a if ctx.needs_input_grad[0] else None, grad_q if ctx.needs_input_grad[1] else None) + (None,) * 7
+
+
+class _DiceLoss(torch.autograd.Function):
+    """logits -> dice loss from the sums of ops.mask_dice_sums: the closed form forward, ops.mask_dice_grad backward."""
+
+    @staticmethod
+    def forward(ctx, logits, gt, sums):
+        ctx.save_for_backward(logits, gt, sums)
+        return _dice_from_sums(sums, float(logits.shape[-2] * logits.shape[-1]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        logits, gt, sums = ctx.saved_tensors
+        return ops.mask_dice_grad(logits, gt, sums, g.to(logits.device, torch.float32).reshape(1).contiguous()), None, None
+
+
 class FeatureLoss:
-    """Contrastive loss with positive and hardest-negative samples plus the mask loss (losses.py:12-141), forward only."""
+    """Contrastive loss with positive and hardest-negative samples plus the mask loss (losses.py:12-141)."""
 
     def __init__(self, args, device: str):
         self.device = device
@@ -67,7 +120,7 @@ class FeatureLoss:
         if self.mask_type == "cross_entropy":
             self._bce = torch.nn.BCEWithLogitsLoss()
         elif self.mask_type in ("lovasz", "focal"):
-            raise NotImplementedError(f"Mask loss function {self.mask_type} is not part of the validation step of this build")
+            raise NotImplementedError(f"Mask loss function {self.mask_type} is not part of this build")
         elif self.mask_type != "dice":
             raise RuntimeError(f"Mask loss function {self.mask_type} not implemented.")
 
@@ -77,24 +130,23 @@ class FeatureLoss:
         The ground truth is resized with nearest interpolation to the logits' size.  'dice': DiceLoss(weight=[0.5, 0.5]) in closed
         form from the four sums of oryon_mask_dice_sums,
             loss = 1/4 [mean_b(1 - (S_pt + 1) / (S_pp + S_t + 1)) + mean_b(1 - (S_p't' + 1) / (S_p'p' + S_t' + 1))]
-        with the background class p' = 1 - p, t' = 1 - t from the same sums and H W; the means are over all B images."""
+        with the background class p' = 1 - p, t' = 1 - t from the same sums and H W; the means are over all B images.  The loss is
+        differentiable when pred_logits requires grad; the mask, the returned logits and the IoU never are."""
         dev = _lib.require_gpu(self.device)
         logits = (pred_logits.squeeze(1) if pred_logits.dim() == 4 else pred_logits).to(dev, torch.float32).contiguous()
         gt = gt.to(dev)
         if tuple(gt.shape[-2:]) != tuple(logits.shape[-2:]):
             gt = ops.mask_resize_nearest(gt, tuple(logits.shape[-2:]))
-        sums, pred_mask, counts = ops.mask_dice_sums(logits, gt, self.mask_th)
+        sums, pred_mask, counts = ops.mask_dice_sums(logits.detach(), gt, self.mask_th)
         if self.mask_type == "dice":
-            hw = float(logits.shape[-2] * logits.shape[-1])
-            sp, spp, spt, st = sums[:, 0], sums[:, 1], sums[:, 2], sums[:, 3]
-            fg = 1.0 - (spt + 1.0) / (spp + st + 1.0)
-            # background: p' t' = 1 - p - t + p t, p'^2 = 1 - 2 p + p^2, t' = 1 - t, summed over the image
-            bg = 1.0 - ((hw - sp - st + spt) + 1.0) / ((hw - 2.0 * sp + spp) + (hw - st) + 1.0)
-            loss = (0.25 * (fg.mean() + bg.mean())).to(torch.float32)
+            if torch.is_grad_enabled() and logits.requires_grad:
+                loss = _DiceLoss.apply(logits, gt.to(torch.int32).contiguous(), sums)
+            else:
+                loss = _dice_from_sums(sums, float(logits.shape[-2] * logits.shape[-1]))
         else:
             loss = self._bce(logits, (gt != 0).to(torch.float32))
         iou = counts[:, 0].to(torch.float32) / counts[:, 1].to(torch.float32)         # 0 / 0 = NaN, as utils/metrics.py:38
-        return loss, pred_mask, logits, iou
+        return loss, pred_mask, logits.detach(), iou
 
     # ------------------------------------------------------------------ losses.py:196-199, 254
     def draw_pool(self, featmap: Tensor, valid, n_corr: int):
@@ -127,8 +179,14 @@ class FeatureLoss:
         valid_host = batch["valid"].cpu().tolist() if isinstance(batch["valid"], Tensor) else list(batch["valid"])
         valid = torch.tensor([int(v) for v in valid_host], dtype=torch.int32, device=dev)
         pool, per_positive = self.draw_pool(featmap_a, valid_host, gt_corrs.shape[1])
-        out = ops.feature_loss(featmap_a, featmap_q, gt_corrs.to(torch.int32).contiguous(), valid, pool, self.pos_margin, self.neg_margin,
-                               float(self.neg_kernel), pool_per_positive=per_positive)
+        corrs32 = gt_corrs.to(torch.int32).contiguous()
+        if torch.is_grad_enabled() and (featmap_a.requires_grad or featmap_q.requires_grad):
+            keys = ("losses", "d_pos", "d_neg", "neg_idx", "pair_terms")
+            out = dict(zip(keys, _ContrastiveTerms.apply(featmap_a, featmap_q, corrs32, valid, pool, self.pos_margin, self.neg_margin,
+                                                         float(self.neg_kernel), per_positive)))
+        else:
+            out = ops.feature_loss(featmap_a, featmap_q, corrs32, valid, pool, self.pos_margin, self.neg_margin,
+                                   float(self.neg_kernel), pool_per_positive=per_positive)
         mask_loss_a, pred_mask_a, pred_logits_a, iou_a = self.mask_loss(net_output["mask_a"], batch["anchor"]["mask"])
         mask_loss_q, pred_mask_q, pred_logits_q, iou_q = self.mask_loss(net_output["mask_q"], batch["query"]["mask"])
         losses = {"mask": 0.5 * (mask_loss_a + mask_loss_q), "pos": out["losses"][0], "neg": 0.5 * (out["losses"][1] + out["losses"][2])}

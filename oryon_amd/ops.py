@@ -729,6 +729,54 @@ def mask_dice_sums(logits: torch.Tensor, gt: torch.Tensor, threshold: float):
 
 
 @_on_tensor_device
+def feature_loss_grad(feat_a: torch.Tensor, feat_q: torch.Tensor, corrs: torch.Tensor, valid: torch.Tensor, neg_idx: torch.Tensor,
+                      d_pos: torch.Tensor, d_neg: torch.Tensor, g: torch.Tensor, pos_margin: float = 0.2, neg_margin: float = 0.9,
+                      workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """The backward pass of ops.feature_loss: feat_a, feat_q, corrs, valid as there, neg_idx / d_pos / d_neg = that call's outputs,
+    g [3] fp32 on the device = the gradients of its `losses` -> (grad_a, grad_q) [B,C,FH,FW] fp32.  `out`: two contiguous fp32 buffers of
+    that shape to write into.  Definition: include/oryon_hip.h, oryon_feature_loss_grad."""
+    dev = _lib.require_gpu(feat_a.device)
+    assert feat_a.dtype == torch.float32 and feat_q.dtype == torch.float32 and feat_a.shape == feat_q.shape and feat_a.dim() == 4
+    B, C, FH, FW = feat_a.shape
+    assert corrs.dtype == torch.int32 and corrs.dim() == 3 and corrs.shape[2] == 4 and corrs.shape[0] == B
+    N = corrs.shape[1]
+    assert valid.dtype == torch.int32 and tuple(valid.shape) == (B,)
+    assert neg_idx.dtype == torch.int32 and tuple(neg_idx.shape) == (B, 2, N)
+    assert d_pos.dtype == torch.float32 and tuple(d_pos.shape) == (B, N) and d_neg.dtype == torch.float32 and tuple(d_neg.shape) == (B, 2, N)
+    assert g.dtype == torch.float32 and g.numel() == 3 and g.device == feat_a.device
+    need = lib().oryon_feature_loss_grad_workspace_bytes(B, C, N)
+    if need == 0 and B > 0:
+        raise _lib.OryonError(f"oryon_feature_loss_grad_workspace_bytes({B}, {C}, {N}): shape not supported (C <= 256, n_corr <= 4096)")
+    ws = workspace if workspace is not None else torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = (torch.empty((B, C, FH, FW), dtype=torch.float32, device=dev), torch.empty((B, C, FH, FW), dtype=torch.float32, device=dev))
+    grad_a, grad_q = out
+    assert all(t.dtype == torch.float32 and tuple(t.shape) == (B, C, FH, FW) for t in out)
+    check(lib().oryon_feature_loss_grad(ptr(feat_a), ptr(feat_q), B, C, FH, FW, ptr(corrs), N, ptr(valid), ptr(neg_idx), ptr(d_pos), ptr(d_neg),
+                                        ptr(g), float(pos_margin), float(neg_margin), ptr(ws), ws.numel(), ptr(grad_a), ptr(grad_q),
+                                        stream_ptr(dev)), "oryon_feature_loss_grad")
+    return grad_a, grad_q
+
+
+@_on_tensor_device
+def mask_dice_grad(logits: torch.Tensor, gt: torch.Tensor, sums: torch.Tensor, g_mask: torch.Tensor,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward pass of the dice loss behind ops.mask_dice_sums: logits [B,H,W] fp32, gt [B,H,W] at the logits' size, sums [B,4]
+    float64 = that call's output, g_mask [1] fp32 on the device -> grad_logits [B,H,W] fp32.  Definition: oryon_mask_dice_grad."""
+    dev = _lib.require_gpu(logits.device)
+    assert logits.dim() == 3 and gt.shape == logits.shape and logits.dtype == torch.float32
+    B, H, W = logits.shape
+    assert sums.dtype == torch.float64 and tuple(sums.shape) == (B, 4)
+    assert g_mask.dtype == torch.float32 and g_mask.numel() == 1 and g_mask.device == logits.device
+    gt = gt.to(dev).to(torch.int32).contiguous()
+    grad = out if out is not None else torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    assert grad.dtype == torch.float32 and tuple(grad.shape) == (B, H, W)
+    check(lib().oryon_mask_dice_grad(ptr(logits), ptr(gt), B, H, W, ptr(sums), ptr(g_mask), ptr(grad), stream_ptr(dev)),
+          "oryon_mask_dice_grad")
+    return grad
+
+
+@_on_tensor_device
 def pose_metrics(pred_pose: torch.Tensor, gt_pose: torch.Tensor, model_pts: torch.Tensor, pts_offset: Optional[torch.Tensor] = None,
                  model_of_pair: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pred/gt [B,4,4] (metres), model_pts [M,3] (or the concatenation of several models with pts_offset [n+1] int32 and

@@ -13,11 +13,18 @@ and the validation step (pipeline.py:196-247, 579-590):
     on_validation_start(objects=None) / validation_step(batch, batch_idx) -> (loss, log) / on_validation_end() -> dict
     reduce_losses(losses) -> (loss, weighted losses)
 
-Training, logging and the dataloaders of the reference are out of scope.  Config flags keep the names of
-configs/config.yaml.
+and the training step (pipeline.py:100-152, 170-181):
+
+    configure_optimizers() -> ([optimizer], [scheduler]) / training_step(batch, batch_idx) -> (loss, log)
+
+The loss of a training step is differentiable: losses.FeatureLoss carries its own backward pass (csrc/feature_loss_grad.hip), fusion
+and decoder - the only trainable modules, net.py:148 - are torch modules under torch autograd.  run_train.py is the loop around it.
+Logging (wandb), the dataloaders' augmentations and DDP of the reference are out of scope.  Config flags keep the
+names of configs/config.yaml.
 """
 from __future__ import annotations
 
+import math
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
@@ -42,6 +49,8 @@ def default_args(**overrides) -> SimpleNamespace:
                              mask_threshold=0.5),
         loss=SimpleNamespace(hard_negatives=True, pos_margin=0.2, neg_margin=0.9, neg_kernel_size=5, mask_type="dice",
                              w={"mask": 1.0, "pos": 0.5, "neg": 0.5}),
+        optimization=SimpleNamespace(optim_type="Adam", scheduler_type="cosine", lr=0.001, momentum=0.0, w_decay=0.0005, gamma=0.1),
+        training=SimpleNamespace(n_epochs=20, freq_save=5, freq_valid=5),
     )
     for k, v in overrides.items():
         node = args
@@ -89,6 +98,9 @@ class Pipeline:
         self._engine: Optional[MatchPoseEngine] = None
         self._feature_loss = None
         self.evaluator = None
+        self.train_evaluator = None                      # the reference shares one evaluator; here a validation pass inside an epoch
+        self.optimizer = self.scheduler = None           # keeps its lists while training registers its own
+        self.last_training: Optional[Dict] = None        # the latest training_step's {'losses', 'results'} (detached)
         self._valid_objects: Optional[Dict] = None
         self._valid_log: List[Dict[str, float]] = []
         self._valid_fmr: List[float] = []
@@ -296,6 +308,52 @@ class Pipeline:
             final_loss = final_loss + w_loss
             w_losses[k] = w_loss
         return final_loss, w_losses
+
+    # ------------------------------------------------------------------ training (pipeline.py:100-152, 170-181)
+    def configure_optimizers(self):
+        """pipeline.py:100-152: SGD or AdamW ('Adam') over model.get_trainable_parameters(), and the scheduler `step` (x gamma after 50,
+        75 and 90 % of the epochs), `cosine` (down to gamma lr over n_epochs - 1), `exp` or 'None' (a step that never comes).  The
+        scheduler steps once per epoch.  -> ([optimizer], [scheduler]), also kept as self.optimizer / self.scheduler."""
+        opt, n_epochs = self.args.optimization, self.args.training.n_epochs
+        parameters = self.model.get_trainable_parameters()
+        if opt.optim_type == "SGD":
+            optimizer = torch.optim.SGD(params=parameters, lr=opt.lr, momentum=opt.momentum, weight_decay=opt.w_decay, nesterov=False)
+        elif opt.optim_type == "Adam":
+            optimizer = torch.optim.AdamW(params=parameters, lr=opt.lr, weight_decay=opt.w_decay)
+        else:
+            raise RuntimeError("Optimizer type {} not implemented!".format(opt.optim_type))
+        sched = torch.optim.lr_scheduler
+        if opt.scheduler_type == "step":
+            scheduler = sched.MultiStepLR(optimizer, milestones=[math.ceil(n_epochs * s) for s in (0.5, 0.75, 0.9)], gamma=opt.gamma)
+        elif opt.scheduler_type == "cosine":
+            scheduler = sched.CosineAnnealingLR(optimizer, T_max=n_epochs - 1, eta_min=opt.gamma * opt.lr)
+        elif opt.scheduler_type == "exp":
+            scheduler = sched.ExponentialLR(optimizer, gamma=opt.gamma)
+        elif opt.scheduler_type in ("None", None):
+            scheduler = sched.MultiStepLR(optimizer, milestones=[n_epochs * 2], gamma=opt.gamma)
+        else:
+            raise RuntimeError("Scheduler type {} not implemented!".format(opt.scheduler_type))
+        self.optimizer, self.scheduler = optimizer, scheduler
+        return [optimizer], [scheduler]
+
+    def training_step(self, batch: Dict, batch_idx: int = 0):
+        """pipeline.py:170-181: the model in train mode, forward, feature_loss.forward, reduce_losses, evaluator.register_train (the
+        batch's IoUs).  -> (the weighted loss, differentiable with respect to the trainable parameters; {'train/mask', 'train/pos',
+        'train/neg', 'train/loss'} detached, what the reference's structured_log records)."""
+        from .evaluation import Evaluator
+        if self.train_evaluator is None:
+            self.train_evaluator = Evaluator(exp_tag="train", compute_iou=True)
+        if hasattr(self.model, "train"):                     # PrecomputedFeatures has no modes
+            self.model.train()
+        with torch.enable_grad():
+            outputs = self.model.forward(batch)
+            losses, results = self.feature_loss.forward(batch, outputs)
+            loss, w_losses = self.reduce_losses(losses)
+        self.train_evaluator.register_train(results, clear=True)
+        self.last_training = dict(losses={k: v.detach() for k, v in losses.items()}, results=results)
+        log = {"train/" + k: v.detach() for k, v in w_losses.items()}
+        log["train/loss"] = loss.detach()
+        return loss, log
 
     def on_validation_start(self, objects: Optional[Dict] = None, compute_vsd: bool = False) -> None:
         """A fresh evaluator in validation mode (evaluator.init_validation).  objects[cls_id] = {'pts' [N,3] mm, 'diameter' mm (BOP),

@@ -133,6 +133,19 @@ def make_batch(first_index: int, B: int, H: int, W: int, C: int, device: str = "
     return out
 
 
+def pair_rgb(index: int, H: int, W: int):
+    """Images for pair `index` (what a network that is being TRAINED on synthetic pairs sees): (rgb_a, rgb_q) [3,H,W] fp32 in [0,1].
+    The anchor is a smooth 3-channel texture (smooth_field, squashed by a sigmoid); every query pixel that `_pair_geometry`'s `winner`
+    assigns an anchor pixel shows that pixel's colour, the rest another smooth field as background - so corresponding pixels look
+    alike, which is what the contrastive loss can learn from."""
+    _, _, _, _, _, winner, hit, _ = _pair_geometry(index, H, W)
+    cpu = torch.device("cpu")
+    rgb_a = torch.sigmoid(smooth_field(index, H, W, 3, cpu, 0))
+    rgb_q = torch.sigmoid(smooth_field(index, H, W, 3, cpu, 1))
+    rgb_q[:, hit] = rgb_a[:, winner[hit]]
+    return rgb_a.reshape(3, H, W).contiguous(), rgb_q.reshape(3, H, W).contiguous()
+
+
 def pair_gt_corrs(index: int, H: int, W: int, max_corrs: int) -> torch.Tensor:
     """Ground-truth correspondences of pair `index` as the generator itself made them: [n,4] int64 rows (y_a, x_a, y_q, x_q), one per
     query pixel (y_q, x_q) that carries the descriptor of its winning anchor pixel (y_a, x_a) with the anchor pixel inside mask_a, in

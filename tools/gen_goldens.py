@@ -19,7 +19,8 @@ Reference entry points executed here:
   utils/evaluator.py          Evaluator(compute_vsd=True) + bop_toolkit_lib/pose_error.py vsd, misc.py, visibility.py (gen_vsd;
                               `python tools/gen_goldens.py vsd`; the OpenGL renderer is stood in for by evaluation.rasterize_depth)
   losses.py                   FeatureLoss.forward (sample_positives, sample_hardest_negatives, sample_negatives, mask_loss) and
-                              utils/metrics.py compute_fmr (gen_feature_loss; `python tools/gen_goldens.py floss`)
+                              utils/metrics.py compute_fmr (gen_feature_loss; `python tools/gen_goldens.py floss`); the same forward
+                              followed by torch's backward (gen_feature_loss_grad; `python tools/gen_goldens.py floss_grad`)
 """
 import json
 import os
@@ -960,6 +961,96 @@ def gen_feature_loss():
             raise RuntimeError(f"floss_{tag}: no seed satisfies the fixture's conditions")
 
 
+# ---------------------------------------------------------------------------------------------- training step (flossgrad_*)
+def gen_feature_loss_grad():
+    """flossgrad_*.npz: the gradients torch autograd gives the reference's FeatureLoss.forward (losses.py:64-141) on the CPU, for the
+    inputs and the seed of every floss_*.npz, of 1.0 mask + 0.5 pos + 0.5 neg (config.yaml's loss.w) with respect to the two maps and
+    the two logit tensors; fixture 1 a second time with neg_margin = 0.2 (`1_rescale_m02`), where part of the negative rows is
+    clamped.  (The files are not named floss_grad_*: tests/test_feature_loss_restatement.py takes every floss_*.npz for a forward
+    fixture.)  Stored as fp32 - the zero descriptor of fixture 6 produces entries of 1e5 - the map gradients sparsely: `pix_a`,
+    `pix_q` [K] = pair * FH * FW + pixel of every pixel some slot sits at, `vec_a`, `vec_q` [K,C]; the logit gradients dense.
+    Asserted: the run's negatives are the forward fixture's; every element outside the listed pixels is exactly 0; every valid row's
+    float64 |d_pos - m_pos| and |m_neg - d_neg| is >= 1e-5; a fixture with valid pairs has active and clamped positive rows; the file is
+    no larger than the largest forward fixture."""
+    class _Any(types.ModuleType):
+        def __getattr__(self, k):
+            if k.startswith("__"):
+                raise AttributeError(k)
+            return type(k, (), {})
+    for name in ("tqdm", "sklearn", "sklearn.neighbors", "scipy.optimize"):
+        try:
+            __import__(name)
+        except ImportError:
+            sys.modules[name] = _Any(name)
+    if isinstance(sys.modules.get("tqdm"), _Any):
+        sys.modules["tqdm"].tqdm = lambda x, *a, **k: x
+    import glob
+    import losses as ref_losses  # noqa: E402  (reference)
+    from types import SimpleNamespace as NS
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import feature_loss_restatement as fr  # noqa: E402  (ours)
+    import feature_loss_grad_restatement as gr  # noqa: E402  (ours)
+
+    forward = sorted(glob.glob(os.path.join(OUT, "floss_*.npz")))
+    limit = max(os.path.getsize(p) for p in forward)
+    real_cuda = torch.Tensor.cuda
+    for path in forward:
+        tag = os.path.basename(path)[len("floss_"):-len(".npz")]
+        z = np.load(path)
+        for suffix, neg_margin in (("", 0.9),) + ((("_m02", 0.2),) if tag == "1_rescale" else ()):
+            args = NS(loss=NS(pos_margin=0.2, neg_margin=neg_margin, neg_kernel_size=5, hard_negatives=True, mask_type="dice"),
+                      test=NS(mask_threshold=0.5))
+            fa, fq = (torch.from_numpy(z[k].astype(np.float32)).requires_grad_() for k in ("feat_a", "feat_q"))
+            la, lq = (torch.from_numpy(z[k].astype(np.float32)).requires_grad_() for k in ("logits_a", "logits_q"))
+            B, C, FH, FW = fa.shape
+            IH, IW = (int(v) for v in z["image_hw"])
+            valid = torch.from_numpy(z["valid"])
+            batch = {"corrs": torch.from_numpy(z["corrs"]).long(), "valid": valid,
+                     "anchor": {"rgb": torch.zeros(B, 3, IH, IW), "mask": torch.from_numpy(z["gt_a"]).float()},
+                     "query": {"rgb": torch.zeros(B, 3, IH, IW), "mask": torch.from_numpy(z["gt_q"]).float()}}
+            floss = ref_losses.FeatureLoss(args, "cpu")
+            torch.manual_seed(int(z["seed"]))
+            torch.Tensor.cuda = lambda self, *a, **k: self                   # losses.py:109-111 on a CPU host
+            try:
+                losses, results = floss.forward(batch, {"featmap_a": fa, "featmap_q": fq, "mask_a": la, "mask_q": lq})
+            finally:
+                torch.Tensor.cuda = real_cuda
+            assert np.array_equal(results["neg_a"].numpy(), z["neg_a"]) and np.array_equal(results["neg_q"].numpy(), z["neg_q"]), tag
+            total = 1.0 * losses["mask"] + 0.5 * losses["pos"] + 0.5 * losses["neg"]
+            total.backward()
+            grads = [np.zeros((B, C, FH, FW), np.float32) if t.grad is None else t.grad.numpy() for t in (fa, fq)]
+            assert all(g.dtype == np.float32 and np.isfinite(g).all() for g in grads)
+            pix = fr.feature_pixels(z["corrs"], (IH, IW), (FH, FW))
+            neg_idx = np.stack([z["neg_a"][..., 0] * FW + z["neg_a"][..., 1], z["neg_q"][..., 0] * FW + z["neg_q"][..., 1]], axis=1).astype(np.int64)
+            on = gr.touched(pix, z["valid"], neg_idx, (FH, FW))
+            sparse = {}
+            for s, key in enumerate("aq"):
+                rows = grads[s].transpose(0, 2, 3, 1).reshape(B * FH * FW, C)
+                flat = on[s].reshape(-1)
+                assert not rows[~flat].any(), (tag, key, "gradient outside the touched pixels")
+                sparse["pix_" + key] = np.flatnonzero(flat).astype(np.int32)
+                sparse["vec_" + key] = rows[flat]
+            r = fr.restate(z["feat_a"].astype(np.float32), z["feat_q"].astype(np.float32), z["corrs"], z["valid"], (IH, IW),
+                           z["pool"].astype(np.int64) if z["pool"].size else None, 0.2, neg_margin)
+            keep = z["valid"] == 1
+            if keep.any():
+                m_pos, m_neg = np.abs(r["d_pos"][keep] - 0.2).min(), np.abs(neg_margin - r["d_neg"][keep]).min()
+                act = (r["d_pos"][keep] - 0.2 > 0).mean()
+                act_neg = (neg_margin - r["d_neg"][keep] > 0).mean()
+                assert m_pos >= 1e-5 and m_neg >= 1e-5, (tag, m_pos, m_neg)
+                assert 0.0 < act < 1.0, (tag, act)
+                print(f"flossgrad_{tag}{suffix}: closest row to a margin {m_pos:.1e} (pos) {m_neg:.1e} (neg); active rows {act:.0%} (pos) "
+                      f"{act_neg:.0%} (neg); largest |gradient| {max(np.abs(g).max() for g in grads):.3g}")
+            else:
+                assert fa.grad is None and fq.grad is None
+            name = f"flossgrad_{tag}{suffix}"
+            save(name, fixture=np.array("floss_" + tag), pos_margin=np.float64(0.2), neg_margin=np.float64(neg_margin),
+                 g=np.array([0.5, 0.25, 0.25], np.float32), g_mask=np.float32(0.5), grad_logits_a=la.grad.numpy()[:, 0],
+                 grad_logits_q=lq.grad.numpy()[:, 0], **sparse)
+            size = os.path.getsize(os.path.join(OUT, name + ".npz"))
+            assert size <= limit, (name, size, limit)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["matcher", "lift", "kabsch", "pointdsc", "e2e", "backbone", "metrics", "bop", "tokenizer", "data"]
     if "data" in which:
@@ -990,3 +1081,5 @@ if __name__ == "__main__":
         gen_vsd()
     if "floss" in which:
         gen_feature_loss()
+    if "floss_grad" in which:
+        gen_feature_loss_grad()
