@@ -28,10 +28,11 @@ def dcos(u, v):
     return (vh - np.where(lu >= EPS, c, 0.0) * uh) / nu, c[:, 0]
 
 
-def map_grads(feat_a, feat_q, pix, valid, neg_idx, g, pos_margin=0.2, neg_margin=0.9, d_pos=None, d_neg=None):
+def map_grads(feat_a, feat_q, pix, valid, neg_idx, g, pos_margin=0.2, neg_margin=0.9, d_pos=None, d_neg=None, slots=None):
     """feat_* [B,C,FH,FW], pix [B,N,4] feature pixels, neg_idx [B,2,N] linear pixels (outside the map: no pixel), g = (g_pos, g_neg_a,
     g_neg_q) -> (G [2,B,C,FH,FW], S [2,B,C,FH,FW], active [B,3,N] bool = rows inside the margins (pos, neg_a, neg_q)).
-    d_pos [B,N] / d_neg [B,2,N]: the distances the margins are tested on (default: the float64 ones)."""
+    d_pos [B,N] / d_neg [B,2,N]: the distances the margins are tested on (default: the float64 ones).
+    slots: a dict that receives, per (side, b) of a valid pair, (keys [2 N] linear pixels or -1, values [2 N, C]): the 2 N slots."""
     feat = (np.asarray(feat_a, dtype=np.float64), np.asarray(feat_q, dtype=np.float64))
     B, C, FH, FW = feat[0].shape
     HW, N = FH * FW, pix.shape[1]
@@ -67,6 +68,8 @@ def map_grads(feat_a, feat_q, pix, valid, neg_idx, g, pos_margin=0.2, neg_margin
             np.add.at(S[s, b].T, key[s], np.abs(t_pos) + np.abs(t_neg))
             np.add.at(G[s, b].T, wi[has_w], t_w[has_w])
             np.add.at(S[s, b].T, wi[has_w], np.abs(t_w[has_w]))
+            if slots is not None:
+                slots[s, b] = (np.concatenate([key[s], np.where(has_w, wi, -1)]), np.concatenate([t_pos + t_neg, np.where(has_w[:, None], t_w, 0.0)]))
     shape = (2, B, C, FH, FW)
     return G.reshape(shape), S.reshape(shape), active
 

@@ -12,9 +12,10 @@ Given descriptor maps F_a, F_q [B,C,FH,FW], correspondences (y_a, x_a, y_q, x_q)
   negative   per side, with p = the side's positive descriptor at pixel (y, x): over the pool positions j (every pixel in row-major order,
              or the listed pixels) the first minimiser of
                  float32(d(p, F[:, pool_j])) + 1e6 max(5 - sqrt(dy^2 + dx^2 + 1e-7), 0)        [the sum and the penalty in float32]
-             The penalty is an fp32 quantity by definition; it vanishes for dy^2 + dx^2 >= 25.
-  terms      per pair mean_n max(d_pos - m_pos, 0), mean_n max(m_neg - d_neg, 0) per side; over the batch the mean of each over the
-             valid pairs, 0 without any
+             The penalty is an fp32 quantity by definition; it vanishes for dy^2 + dx^2 >= 25.  A listed position that names no
+             pixel (< 0 or >= FH FW) is no candidate; a side without any candidate has d_neg = NaN and pixel 0 on every row
+  terms      per pair mean_n max(d_pos - m_pos, 0), mean_n max(m_neg - d_neg, 0) per side (a NaN distance is inside no margin: it
+             adds 0, and the backward gives it no gradient); over the batch the mean of each over the valid pairs, 0 without any
   dice       p = 1 / (1 + exp(-2 x)); per image S_p, S_pp, S_pt, S_t;
              loss = 1/4 [mean_b(1 - (S_pt + 1) / (S_pp + S_t + 1)) + mean_b(1 - (S_qu + 1) / (S_qq + S_u + 1))], q = 1 - p, u = 1 - t
 """
@@ -46,30 +47,51 @@ def penalty32(py, px, cy, cx, neg_kernel):
     return np.float32(1e6) * np.maximum(np.float32(neg_kernel) - pd, np.float32(0.0))
 
 
-def hardest_negatives(fmap, yx, pool, neg_kernel):
-    """fmap [C,FH,FW], yx [N,2] feature pixels, pool [P] linear pixels -> (position in the pool [N], distance [N], pixel [N])."""
+def penalised_costs(fmap, yx, pool, neg_kernel):
+    """fmap [C,FH,FW], yx [N,2] feature pixels, pool [P] linear pixels that all name a pixel -> (d [N,P] float64, penalty [N,P] float32)."""
     C, FH, FW = fmap.shape
     rows = unit(fmap.reshape(C, FH * FW).T)
-    cand = rows[pool]
-    cy, cx = pool // FW, pool % FW
     pos = rows[yx[:, 0] * FW + yx[:, 1]]
-    d = 0.5 * (1.0 - pos @ cand.T)
-    where = np.empty(len(yx), dtype=np.int64)
-    for n in range(len(yx)):
-        cost = d[n].astype(np.float32) + penalty32(yx[n, 0], yx[n, 1], cy, cx, neg_kernel)
-        where[n] = int(np.argmin(cost))
-    return where, d[np.arange(len(yx)), where], pool[where]
+    d = 0.5 * (1.0 - pos @ rows[pool].T)
+    return d, penalty32(yx[:, 0:1], yx[:, 1:2], (pool // FW)[None], (pool % FW)[None], neg_kernel)
 
 
-def restate(feat_a, feat_q, corrs, valid, image_hw, pool=None, pos_margin=0.2, neg_margin=0.9, neg_kernel=5, per_positive=False):
+def hardest_negatives(fmap, yx, pool, neg_kernel):
+    """fmap [C,FH,FW], yx [N,2] feature pixels, pool [P] linear pixels -> (position in the pool [N], distance [N], pixel [N]).
+    A pool position that names no pixel (< 0 or >= FH FW) is no candidate; without any candidate: position -1, distance NaN, pixel 0."""
+    HW = fmap.shape[1] * fmap.shape[2]
+    pool = np.asarray(pool, dtype=np.int64)
+    at = np.flatnonzero((pool >= 0) & (pool < HW))
+    if at.size == 0:
+        return np.full(len(yx), -1, dtype=np.int64), np.full(len(yx), np.nan), np.zeros(len(yx), dtype=np.int64)
+    d, pen = penalised_costs(fmap, yx, pool[at], neg_kernel)
+    where = np.argmin(d.astype(np.float32) + pen, axis=1)
+    return at[where], d[np.arange(len(yx)), where], pool[at[where]]
+
+
+def hinge(x):
+    """max(x, 0) as the strict test x > 0 states it: a NaN distance (no candidate) is inside no margin and adds 0."""
+    with np.errstate(invalid="ignore"):
+        return np.where(x > 0, x, 0.0)
+
+
+def terms(d_pos, d_neg, valid, pos_margin, neg_margin):
+    """d_pos [B,N], d_neg [B,2,N] -> (pair_terms [B,3], losses [3]); the rows of an invalid pair are 0."""
+    keep = np.asarray([v == 1 for v in valid])
+    pair_terms = np.stack([hinge(d_pos - pos_margin).mean(1), hinge(neg_margin - d_neg[:, 0]).mean(1), hinge(neg_margin - d_neg[:, 1]).mean(1)], axis=1)
+    pair_terms[~keep] = 0.0
+    return pair_terms, (pair_terms[keep].mean(0) if keep.any() else np.zeros(3))
+
+
+def restate(feat_a, feat_q, corrs, valid, image_hw, pool=None, pos_margin=0.2, neg_margin=0.9, neg_kernel=5, per_positive=False, pix=None):
     """-> dict(d_pos [B,N], d_neg [B,2,N], neg_idx [B,2,N] linear pixels, pair_terms [B,3], losses (pos, neg_a, neg_q)).
-    pool [B,2,P] linear pixels or None (the whole map); per_positive: pool [B,2,N] names every positive's negative directly."""
+    pool [B,2,P] linear pixels or None (the whole map); per_positive: pool [B,2,N] names every positive's negative directly.
+    pix [B,N,4]: the feature pixels themselves, each inside its axis (what the kernels take); corrs and image_hw are then not read."""
     feat = (np.asarray(feat_a, dtype=np.float64), np.asarray(feat_q, dtype=np.float64))
     B, C, FH, FW = feat[0].shape
-    pix = feature_pixels(corrs, image_hw, (FH, FW))
+    pix = feature_pixels(corrs, image_hw, (FH, FW)) if pix is None else np.asarray(pix, dtype=np.int64)
     N = pix.shape[1]
     d_pos, d_neg, neg_idx = np.zeros((B, N)), np.zeros((B, 2, N)), np.zeros((B, 2, N), dtype=np.int64)
-    pair_terms = np.zeros((B, 3))
     for b in range(B):
         if valid[b] != 1:
             continue
@@ -86,10 +108,7 @@ def restate(feat_a, feat_q, corrs, valid, image_hw, pool=None, pos_margin=0.2, n
             else:
                 pl = np.arange(FH * FW) if pool is None else np.asarray(pool[b, side], dtype=np.int64)
                 _, d_neg[b, side], neg_idx[b, side] = hardest_negatives(feat[side][b], yx, pl, neg_kernel)
-        pair_terms[b] = (np.maximum(d_pos[b] - pos_margin, 0).mean(), np.maximum(neg_margin - d_neg[b, 0], 0).mean(),
-                         np.maximum(neg_margin - d_neg[b, 1], 0).mean())
-    keep = np.asarray([v == 1 for v in valid])
-    losses = pair_terms[keep].mean(0) if keep.any() else np.zeros(3)
+    pair_terms, losses = terms(d_pos, d_neg, valid, pos_margin, neg_margin)
     return dict(pix=pix, d_pos=d_pos, d_neg=d_neg, neg_idx=neg_idx, pair_terms=pair_terms, losses=losses)
 
 
