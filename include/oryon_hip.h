@@ -63,6 +63,37 @@ int oryon_device_check(int device);
 int oryon_rgb_resize_bilinear(const uint8_t *rgb_hwc, int n, int HI, int WI, int HO, int WO, float *out, void *stream);
 int oryon_resize_bilinear_f32(const float *in, int n, int HI, int WI, int HO, int WO, int round_output, float *out, void *stream);
 
+/* K-1a the reference's training augmentations (datasets.py:98-114 build_augs; utils/augmentations.py:17-127: random_jitter,
+ *     random_brightness, horizontal_flip, vertical_flip, each per sample in front of the resize) fused into the K-1 resizes.
+ * table [n, ORYON_AUG_STRIDE] float64, one row per image, 8-byte aligned:
+ *     [0]          flip bits as a number: ORYON_AUG_HFLIP | ORYON_AUG_VFLIP (the image is mirrored in x / in y before the resize)
+ *     [1]          reserved, 0
+ *     [2+2k, 3+2k] slot k < ORYON_AUG_SLOTS of the colour chain, in execution order: op id (0 brightness, 1 contrast, 2 saturation, 3 hue;
+ *                  anything else, e.g. -1: empty slot) and its factor.  At most ONE contrast slot per image (two ColorJitter applications
+ *                  of the reference never hold more: random_brightness has no contrast); with more, all of them use the first one's mean.
+ *     Arithmetic (DESIGN.md "7b", transcribed from torchvision's tensor path; x = pixel / 255. in float64 like the reference's tensor):
+ *     gray = (0.2989 r + 0.587 g) + 0.114 b;  blend(a, b, f) = clamp(f a + (1 - f) b, 0, 1);  brightness blend(x, 0, f);  contrast
+ *     blend(x, mean over the image of gray(x as it is when the op runs), f);  saturation blend(x, gray(x), f);  hue: to fp32, rgb -> hsv,
+ *     h <- (h + f) mod 1, hsv -> rgb, back to float64.  No contraction, correctly rounded divisions.
+ * oryon_rgb_augment_resize: rgb_hwc [n,HI,WI,3] uint8 -> out [n,3,HO,WO] fp32 = oryon_rgb_resize_bilinear of the flipped, colour-jittered
+ *     image (each touched texel goes through the chain in front of the interpolation; one rounding to fp32).  Two launches: the per-image
+ *     gray mean for images with a contrast slot (fp64, fixed reduction tree, no float atomics: bit-stable), then the resize.  A table
+ *     of zero flip bits and empty slots gives oryon_rgb_resize_bilinear's output bit for bit.  workspace: 8-byte aligned,
+ *     oryon_rgb_augment_workspace_bytes(n) bytes, written and read by this call only.  HI*WI and HO*WO below 2^29.
+ * oryon_resize_bilinear_f32_flip / oryon_mask_resize_nearest_flip: oryon_resize_bilinear_f32 / oryon_mask_resize_nearest applied to the
+ *     image flipped as entry [0] of its table row says (the same table; nothing else of it is read), bit for bit. */
+#define ORYON_AUG_SLOTS 8
+#define ORYON_AUG_STRIDE 18
+#define ORYON_AUG_HFLIP 1
+#define ORYON_AUG_VFLIP 2
+size_t oryon_rgb_augment_workspace_bytes(int n);
+int oryon_rgb_augment_resize(const uint8_t *rgb_hwc, const double *table, int n, int HI, int WI, int HO, int WO,
+                             void *workspace, size_t workspace_bytes, float *out, void *stream);
+int oryon_resize_bilinear_f32_flip(const float *in, const double *table, int n, int HI, int WI, int HO, int WO, int round_output,
+                                   float *out, void *stream);
+int oryon_mask_resize_nearest_flip(const uint8_t *mask_in, const double *table, int n_maps, int HI, int WI, int HO, int WO,
+                                   int32_t *mask_out, void *stream);
+
 /* K1' the reference's fp16 matcher branch (corrs_device='cuda', utils/pcd.py:195-197) casts the descriptors to float16 first:
  *     out[i] = float(half(in[i])) (round to nearest even; may alias).  The exact matcher then runs on the rounded values. */
 int oryon_round_to_f16_f32(const float *in, float *out, int64_t n, void *stream);

@@ -59,6 +59,10 @@ _PROTOS = {
     "oryon_round_to_f16_f32": (c_int, [_P, _P, ctypes.c_int64, _P]),
     "oryon_rgb_resize_bilinear": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "oryon_resize_bilinear_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "oryon_rgb_augment_workspace_bytes": (c_size_t, [c_int]),
+    "oryon_rgb_augment_resize": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P, _P]),
+    "oryon_resize_bilinear_f32_flip": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "oryon_mask_resize_nearest_flip": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "oryon_roi_compact": (c_int, [_P, c_int, c_int, _P, _P, _P]),
     "oryon_mask_from_logits": (c_int, [_P, c_int64, c_float, _P, _P]),
     "oryon_mask_resize_nearest": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),

@@ -11,25 +11,9 @@
 // (datasets.py:204): the rgb kernel therefore computes in fp64 and rounds once.  HBM-bound: 3*HI*WI bytes in (only the
 // touched texels), 12*HO*WO bytes out per image.
 #include "common.h"
+#include "resample.h"
 
 namespace oryon {
-
-template <typename T>
-struct Tap { int i0, i1; T l0, l1; };
-
-template <typename T>
-__device__ __forceinline__ Tap<T> make_tap(int dst, T scale, int in_size)
-{
-    T src = scale * ((T)dst + (T)0.5) - (T)0.5;
-    src = src < (T)0 ? (T)0 : src;
-    Tap<T> t;
-    t.i0 = (int)src;
-    if (t.i0 > in_size - 1) t.i0 = in_size - 1;
-    t.i1 = t.i0 + (t.i0 < in_size - 1 ? 1 : 0);
-    t.l1 = src - (T)t.i0;
-    t.l0 = (T)1 - t.l1;
-    return t;
-}
 
 __global__ __launch_bounds__(256) void rgb_resize_bilinear_kernel(const uint8_t *__restrict__ in, int HI, int WI, int HO, int WO,
                                                                    float *__restrict__ out)

@@ -13,13 +13,13 @@ read live on the device, bookkeeping stays on the host.  No CPU pixel path exist
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib, ops
+from . import _lib, augment, ops
 from .coordinates import scale_coords
 
 
@@ -79,34 +79,74 @@ class DeviceCollate:
     """`CollateWrapper(corr_n)` ∘ `resize(img_size)` for items that went through `preprocess_item` (datasets.py:138-245,
     utils/augmentations.py:129-164).  Call with the list of dataset tuples
         (item_a, item_q, prompt, sampled_corrs, all_corrs, pose, cls_id, instance_id, valid)
-    and get the reference's batch dict.  Images of one side must share one sensor size (NOCS / TOYL: 480x640)."""
+    and get the reference's batch dict.  Images of one side must share one sensor size (NOCS / TOYL: 480x640).
 
-    def __init__(self, corr_n: int, img_size: Sequence[int] = (224, 224), device: str = "cuda"):
+    `augs` = the `augs` node of the config (augs.rgb.jitter / bright / hflip / vflip; datasets.py:98-114 build_augs): the training
+    augmentations, drawn once per tuple in batch order (`augment.draw_pair_params`: the reference's calls to `random` and torch's global
+    generator) and applied in front of the resize - boxes and sampled correspondences on the host at sensor resolution, pixels inside the
+    resize launches (K-1a: one table per side, one small H2D copy per side).  `orig_rgb`, `orig_depth`, `eval_depth` and `camera` are
+    not touched, as in the reference.  With `augs=None` or all four off nothing is drawn and the calls are the plain K-1 ones."""
+
+    def __init__(self, corr_n: int, img_size: Sequence[int] = (224, 224), device: str = "cuda", augs=None):
         self.max_corrs = int(corr_n)
         self.size = (int(img_size[0]), int(img_size[1]))
         self.device = device
+        self.augs = augs if any(augment.enabled(augs)) else None
 
-    def _side(self, items: List[dict]) -> Dict:
+    def draw(self, n: int) -> Optional[List[Tuple[augment.AugParams, augment.AugParams]]]:
+        """(anchor, query) parameters of n tuples in batch order; None without augmentations."""
+        return None if self.augs is None else [augment.draw_pair_params(self.augs) for _ in range(n)]
+
+    def side_boxes(self, items: List[dict], params: Optional[Sequence[augment.AugParams]] = None) -> List[Tensor]:
+        """The resized boxes of one side: flipped at sensor resolution first when `params` says so (host only)."""
+        boxes = []
+        for i, it in enumerate(items):
+            if params is not None and (params[i].hflip or params[i].vflip):
+                it = {"mask": it["mask"], "metadata": {"boxes": augment.flip_box(it["metadata"]["boxes"], it["hw_size"], params[i].hflip,
+                                                                                 params[i].vflip)}}
+            box, _ = resize_annotations(it, torch.zeros((0, 2)), self.size)
+            boxes.append(box.squeeze())
+        return boxes
+
+    def pair_corrs(self, item_a: dict, item_q: dict, sampled_corrs: Tensor, params=None) -> Tensor:
+        """[N,4] sampled correspondences at the network's input size: flipped at sensor resolution (params = the pair's (anchor, query)
+        parameters), then `scale_coords` (host only)."""
+        ca, cq = sampled_corrs[:, :2], sampled_corrs[:, 2:]
+        if params is not None:
+            ca = augment.flip_coords(ca, item_a["hw_size"], params[0].hflip, params[0].vflip)
+            cq = augment.flip_coords(cq, item_q["hw_size"], params[1].hflip, params[1].vflip)
+        _, ca = resize_annotations(item_a, ca, self.size)
+        _, cq = resize_annotations(item_q, cq, self.size)
+        return torch.cat([ca, cq], dim=1)
+
+    def _side(self, items: List[dict], params: Optional[Sequence[augment.AugParams]] = None) -> Dict:
         dev = _lib.require_gpu(self.device)
         rgb_u8 = torch.stack([it["rgb"] for it in items]).to(dev, non_blocking=True)                   # [B,H,W,3] uint8
         depth_raw = torch.stack([it["depth"] for it in items])
         integer_depth = not depth_raw.dtype.is_floating_point
         depth_dev = depth_raw.to(torch.float32).to(dev, non_blocking=True)                              # [B,H,W]
         mask_dev = torch.stack([it["mask"] for it in items]).to(torch.uint8).to(dev, non_blocking=True)
-        boxes, sizes = [], []
+        boxes, sizes = self.side_boxes(items, params), []
         for it in items:
-            box, _ = resize_annotations(it, torch.zeros((0, 2)), self.size)
-            boxes.append(box.squeeze())
             s = it["hw_size"]
             sizes.append(s if isinstance(s, Tensor) else torch.tensor(s))
         orig_depth = [depth_dev[i] for i in range(len(items))]
+        if params is None:
+            rgb = ops.rgb_resize_bilinear(rgb_u8, self.size)
+            mask = ops.mask_resize_nearest(mask_dev, self.size)
+            depth = ops.resize_bilinear(depth_dev, self.size, round_output=integer_depth)
+        else:
+            table = augment.build_table(params).to(dev, non_blocking=True)
+            rgb = ops.rgb_augment_resize(rgb_u8, table, self.size)
+            mask = ops.mask_resize_nearest(mask_dev, self.size, flip_table=table)
+            depth = ops.resize_bilinear(depth_dev, self.size, round_output=integer_depth, flip_table=table)
         return {
-            "rgb": ops.rgb_resize_bilinear(rgb_u8, self.size),
+            "rgb": rgb,
             "orig_rgb": [it["orig_rgb"] for it in items],
-            "mask": ops.mask_resize_nearest(mask_dev, self.size).to(torch.uint8),
+            "mask": mask.to(torch.uint8),
             "orig_depth": orig_depth,
             "eval_depth": orig_depth,
-            "depth": ops.resize_bilinear(depth_dev, self.size, round_output=integer_depth),
+            "depth": depth,
             "camera": torch.stack([torch.as_tensor(it["camera"]).squeeze() for it in items]),
             "pose": torch.stack([it["metadata"]["poses"][0].squeeze() for it in items]),
             "box": torch.stack(boxes),
@@ -116,13 +156,12 @@ class DeviceCollate:
 
     def __call__(self, data: Sequence[Tuple]) -> dict:
         items_a, items_q = [d[0] for d in data], [d[1] for d in data]
+        params = self.draw(len(data))
         corr_list, all_corr_list, poses, valids = [], [], [], []
-        for item_a, item_q, prompt, sampled_corrs, all_corrs, pose, cls_id, instance_id, valid in data:
+        for i, (item_a, item_q, prompt, sampled_corrs, all_corrs, pose, cls_id, instance_id, valid) in enumerate(data):
             if valid and sampled_corrs.shape[0] > 0:
                 valids.append(1.0)
-                _, ca = resize_annotations(item_a, sampled_corrs[:, :2], self.size)
-                _, cq = resize_annotations(item_q, sampled_corrs[:, 2:], self.size)
-                sampled_corrs = torch.cat([ca, cq], dim=1)
+                sampled_corrs = self.pair_corrs(item_a, item_q, sampled_corrs, None if params is None else params[i])
             else:
                 valids.append(0.0)
                 sampled_corrs = torch.zeros((self.max_corrs, 4)).to(torch.long)
@@ -132,8 +171,8 @@ class DeviceCollate:
             if pose is not None:
                 poses.append(pose)
         batch = {
-            "anchor": self._side(items_a),
-            "query": self._side(items_q),
+            "anchor": self._side(items_a, None if params is None else [p[0] for p in params]),
+            "query": self._side(items_q, None if params is None else [p[1] for p in params]),
             "corrs": torch.stack(corr_list, dim=0).to(torch.long) if len({c.shape for c in corr_list}) == 1 else corr_list,
             "all_corrs": all_corr_list,
             "prompt": [d[2] for d in data],

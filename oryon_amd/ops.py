@@ -18,6 +18,7 @@ MATCH_TILE = 128
 ROW_PAD = 256      # row capacities are multiples of 256; K0 zero-fills rows [n, round_up(n, 256)) of every map - rows beyond that
                    # are NOT written (the matchers never read past ceil(n / 256) * 256)
 K_PAD = 32
+AUG_SLOTS, AUG_STRIDE = 8, 18      # ORYON_AUG_SLOTS, ORYON_AUG_STRIDE (include/oryon_hip.h): the augmentation table of K-1a
 
 
 def _on_tensor_device(fn):
@@ -237,13 +238,41 @@ def rgb_resize_bilinear(rgb_hwc: torch.Tensor, out_hw: Tuple[int, int]) -> torch
     return out
 
 
+def _flip_table(table: torch.Tensor, n: int, device) -> torch.Tensor:
+    """The per-image augmentation table [n, AUG_STRIDE] float64 (include/oryon_hip.h, K-1a; oryon_amd.augment.build_table) on `device`."""
+    assert table.dtype == torch.float64 and tuple(table.shape) == (n, AUG_STRIDE) and table.device == device, (table.dtype, table.shape, table.device)
+    return table.contiguous()
+
+
 @_on_tensor_device
-def resize_bilinear(x: torch.Tensor, out_hw: Tuple[int, int], round_output: bool = False) -> torch.Tensor:
-    """fp32 [n,HI,WI] -> fp32 [n,HO,WO], torch bilinear (align_corners=False); round_output mimics torchvision on integer images."""
+def rgb_augment_resize(rgb_hwc: torch.Tensor, table: torch.Tensor, out_hw: Tuple[int, int]) -> torch.Tensor:
+    """uint8 [n,HI,WI,3] + table [n, AUG_STRIDE] float64 (flip bits and the colour chain of every image) -> fp32 [n,3,HO,WO]: K-1a,
+    rgb_resize_bilinear of the flipped, colour-jittered images in two launches (gray mean for the contrast op, then the fused resize)."""
+    _lib.require_gpu(rgb_hwc.device)
+    assert rgb_hwc.dtype == torch.uint8 and rgb_hwc.dim() == 4 and rgb_hwc.shape[3] == 3
+    rgb_hwc = rgb_hwc.contiguous()
+    n, HI, WI = rgb_hwc.shape[:3]
+    table = _flip_table(table, n, rgb_hwc.device)
+    out = torch.empty((n, 3, int(out_hw[0]), int(out_hw[1])), dtype=torch.float32, device=rgb_hwc.device)
+    ws_bytes = int(lib().oryon_rgb_augment_workspace_bytes(n))
+    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=rgb_hwc.device)
+    check(lib().oryon_rgb_augment_resize(ptr(rgb_hwc), ptr(table), n, HI, WI, int(out_hw[0]), int(out_hw[1]), ptr(ws), ws_bytes, ptr(out),
+                                         stream_ptr(rgb_hwc.device)), "oryon_rgb_augment_resize")
+    return out
+
+
+@_on_tensor_device
+def resize_bilinear(x: torch.Tensor, out_hw: Tuple[int, int], round_output: bool = False, flip_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [n,HI,WI] -> fp32 [n,HO,WO], torch bilinear (align_corners=False); round_output mimics torchvision on integer images.
+    flip_table [n, AUG_STRIDE] float64: image i is mirrored as the flip bits of row i say before the resize (K-1a)."""
     _lib.require_gpu(x.device)
     x = x.to(torch.float32).contiguous()
     n, HI, WI = x.shape
     out = torch.empty((n, int(out_hw[0]), int(out_hw[1])), dtype=torch.float32, device=x.device)
+    if flip_table is not None:
+        check(lib().oryon_resize_bilinear_f32_flip(ptr(x), ptr(_flip_table(flip_table, n, x.device)), n, HI, WI, int(out_hw[0]), int(out_hw[1]),
+                                                   int(round_output), ptr(out), stream_ptr(x.device)), "oryon_resize_bilinear_f32_flip")
+        return out
     check(lib().oryon_resize_bilinear_f32(ptr(x), n, HI, WI, int(out_hw[0]), int(out_hw[1]), int(round_output), ptr(out),
                                           stream_ptr(x.device)), "oryon_resize_bilinear_f32")
     return out
@@ -274,14 +303,19 @@ def mask_from_logits(logits: torch.Tensor, threshold: float) -> torch.Tensor:
 
 
 @_on_tensor_device
-def mask_resize_nearest(mask: torch.Tensor, out_hw: Tuple[int, int]) -> torch.Tensor:
-    """uint8 masks [n,HI,WI] -> int32 [n,HO,WO] with torch's legacy 'nearest' index rule."""
+def mask_resize_nearest(mask: torch.Tensor, out_hw: Tuple[int, int], flip_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 masks [n,HI,WI] -> int32 [n,HO,WO] with torch's legacy 'nearest' index rule.
+    flip_table [n, AUG_STRIDE] float64: mask i is mirrored as the flip bits of row i say before the resize (K-1a)."""
     if mask.dim() == 2:
         mask = mask[None]
     _lib.require_gpu(mask.device)
     m = mask.to(torch.uint8).contiguous()
     n, HI, WI = m.shape
     out = torch.empty((n, int(out_hw[0]), int(out_hw[1])), dtype=torch.int32, device=m.device)
+    if flip_table is not None:
+        check(lib().oryon_mask_resize_nearest_flip(ptr(m), ptr(_flip_table(flip_table, n, m.device)), n, HI, WI, int(out_hw[0]), int(out_hw[1]),
+                                                   ptr(out), stream_ptr(m.device)), "oryon_mask_resize_nearest_flip")
+        return out
     check(lib().oryon_mask_resize_nearest(ptr(m), n, HI, WI, int(out_hw[0]), int(out_hw[1]), ptr(out), stream_ptr(m.device)),
           "oryon_mask_resize_nearest")
     return out

@@ -51,6 +51,8 @@ def default_args(**overrides) -> SimpleNamespace:
                              w={"mask": 1.0, "pos": 0.5, "neg": 0.5}),
         optimization=SimpleNamespace(optim_type="Adam", scheduler_type="cosine", lr=0.001, momentum=0.0, w_decay=0.0005, gamma=0.1),
         training=SimpleNamespace(n_epochs=20, freq_save=5, freq_valid=5),
+        # the training augmentations (datasets.py:98-114); read by nothing unless handed to data.DeviceCollate(augs=...)
+        augs=SimpleNamespace(rgb=SimpleNamespace(jitter=True, bright=True, hflip=True, vflip=True)),
     )
     for k, v in overrides.items():
         node = args

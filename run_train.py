@@ -8,13 +8,18 @@ modules - are torch modules under torch autograd.
 
     python run_train.py --pairs 8 --batch 2 --epochs 2                       # synthetic pairs: images from oryon_amd.synth.pair_rgb, a small
                                                                              # Oryon (small frozen random CLIP towers) trained from scratch
-    python run_train.py --data-root data --dataset nocs --split cross_scene_test --ckpt ... --catseg ... --bpe ... --epochs 20
+    python run_train.py --data-root data --dataset nocs --split cross_scene_test --ckpt ... --catseg ... --bpe ... --epochs 20 --augs all
 
 A checkpoint is `{"state_dict": {"model.<key>": tensor}, "epoch": e}`: what run_test.load_oryon_checkpoint reads, so a trained model goes
 straight into `run_test.py --ckpt` / `run_valid.py --ckpt`.  Files: `<out>/epoch=NNNN.ckpt` and `<out>/last.ckpt`.  The last stdout line
 is one JSON line with the per-epoch means of the weighted losses.
 
-Not here: DDP / gradient all-reduce, the reference's augmentations, the lovasz and focal mask losses.
+`--augs` turns the reference's training augmentations on for the training loader of the real-asset mode (config.yaml's default recipe is
+`--augs all`: colour jitter, brightness, horizontal and vertical flip, each with probability 0.5 per image): drawn in the
+collate with the reference's calls to `random` and torch's generator, applied inside the resize kernels.  The validation loader never
+augments; the synthetic mode builds its batches without the collate and takes `--augs none` only.
+
+Not here: DDP / gradient all-reduce, the text augmentation (augs.text.synset), the lovasz and focal mask losses.
 
 Needs an MI355X (no CPU fallback by design)."""
 import argparse
@@ -42,6 +47,8 @@ def parse(argv=None):
     ap.add_argument("--scheduler", choices=["step", "cosine", "exp", "None"], default=None)
     ap.add_argument("--out", default=os.path.join("exp_data", "train", "models"), help="checkpoint directory")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--augs", default="none", help="training augmentations of the real-asset mode: none (default), all, or a comma list of "
+                    "jitter,bright,hflip,vflip (augs.rgb.* of config.yaml; with any of them on, Python's `random` is seeded with --seed)")
     g = ap.add_argument_group("real assets (as run_valid.py)")
     g.add_argument("--data-root", default=None)
     g.add_argument("--dataset", choices=["nocs", "toyl"], default="nocs")
@@ -56,6 +63,19 @@ def parse(argv=None):
     g.add_argument("--bpe", default=None)
     g.add_argument("--hash-prompts", action="store_true")
     return ap.parse_args(argv)
+
+
+AUG_NAMES = ("jitter", "bright", "hflip", "vflip")
+
+
+def parse_augs(text):
+    """--augs -> {name: bool} for the four augs.rgb switches."""
+    text = text.strip().lower()
+    names = () if text in ("", "none") else AUG_NAMES if text == "all" else tuple(t.strip() for t in text.split(","))
+    unknown = [n for n in names if n not in AUG_NAMES]
+    if unknown:
+        raise SystemExit(f"--augs: unknown augmentation(s) {unknown}; choose none, all or a comma list of {', '.join(AUG_NAMES)}")
+    return {n: n in names for n in AUG_NAMES}
 
 
 def training_args(a, **extra):
@@ -108,6 +128,10 @@ def save_checkpoint(model, path, epoch):
 
 def main(argv=None):
     a = parse(argv)
+    augs_on = parse_augs(a.augs)
+    if any(augs_on.values()) and not a.data_root:
+        raise SystemExit("--augs: the synthetic mode builds its batches without the collate and cannot augment them; "
+                         "use --augs none, or --data-root ... for the real-asset mode")
     import oryon_amd
     oryon_amd.configure()
     import torch
@@ -130,8 +154,15 @@ def main(argv=None):
         if a.ckpt:
             run_test.load_oryon_checkpoint(model, a.ckpt)
         collate = DeviceCollate(args.dataset.max_corrs, args.dataset.img_size, dev)
+        train_collate = collate
+        if any(augs_on.values()):
+            import random
+            random.seed(a.seed)                              # the gates of the augmentations (their factors come from torch's generator)
+            for name, on in augs_on.items():
+                setattr(args.augs.rgb, name, on)
+            train_collate = DeviceCollate(args.dataset.max_corrs, args.dataset.img_size, dev, augs=args.augs)
 
-        def loader(split, n_pairs):
+        def loader(split, n_pairs, collate=collate):
             n = len(split) if n_pairs <= 0 else min(n_pairs, len(split))
 
             def batches():
@@ -141,7 +172,8 @@ def main(argv=None):
                         batch["prompt_tokens"] = run_test.hashed_prompt_tokens(batch["prompt"])
                     yield batch, {k: split.object_info(k) for k in dict.fromkeys(batch["cls_id"])}
             return batches
-        train_batches = loader(FixedSplit(a.dataset, a.data_root, a.dataset_name or a.dataset, a.split, a.obj, mask_type=a.mask), a.pairs)
+        train_batches = loader(FixedSplit(a.dataset, a.data_root, a.dataset_name or a.dataset, a.split, a.obj, mask_type=a.mask), a.pairs,
+                               train_collate)
         if a.valid_split:
             valid_batches = loader(FixedSplit(a.dataset, a.data_root, a.dataset_name or a.dataset, a.valid_split, a.obj, mask_type=a.mask),
                                    a.valid_pairs)
