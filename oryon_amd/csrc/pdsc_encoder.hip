@@ -15,13 +15,9 @@
 #include <stdlib.h>
 #include "common.h"
 #include "pdsc.h"
+#include "pdsc_blocks.h"
 
 namespace oryon {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// row index inside a 32x32 MFMA C/D block held by (register r, lane half hi)
-__device__ __forceinline__ int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // ------------------------------------------------------------------------------------------------
 // corr_pos = cat(src, tgt) - mean over the n rows (utils/pointdsc/init.py:18-19); rows >= n are zeroed.
@@ -149,7 +145,6 @@ __global__ __launch_bounds__(256) void pdsc_linear_kernel(const float *__restric
 // kernel so that a lane fetches its 32 values of a (32-query, 64-key) tile with 8 coalesced 16-byte loads:
 //   sc[b][q_block32][key_tile64][v4 = kb*4 + r/4][lane][r%4],  key = kb*32 + crow(r, lane/32), query = lane%32.
 // Keys >= n hold -1 (masked).
-constexpr int ATT_Q = 128, ATT_KT = 64;
 __global__ __launch_bounds__(256) void pdsc_sc_kernel(const float *__restrict__ src, const float *__restrict__ tgt,
                                                        const int32_t *__restrict__ n_rows, int n_cap, float inv_sigma2,
                                                        float *__restrict__ sc)
@@ -367,32 +362,6 @@ __global__ __launch_bounds__(256) void pdsc_attention_kernel(const float *__rest
 //   V tile   arranged so that the MFMA k-slot (lane half h, element e) of block (kb, t) IS the key the softmax registers hold:
 //            Vp[kb][t][h][channel][e] with key = kb*32 + 16t + 8(e>>2) + 4h + (e&3)  - again one ds_read_b128 per operand
 //   P        split in registers right after the softmax (B operand of the second product)
-typedef _Float16 xhalf8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split_half(float x, _Float16 &hi, _Float16 &lo)
-{
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
-
-// Two values at a time: packed conversions (v_cvt_pk_f16_f32 on gfx950, round-to-nearest-even) - same results as split_half.
-typedef float xf32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 xf16x2 __attribute__((ext_vector_type(2)));
-// Round 6: the residuals x - float(hi) come from v_fma_mix_f32 (hi's half read as the f16 source of an fp32 fma: float(hi) * -1 + x, one
-// rounding of an exactly representable difference - the bits of the subtraction it replaces), four instructions per pair instead of six.
-__device__ __forceinline__ void split_pair(float a, float b, unsigned &hi, unsigned &lo)
-{
-    const xf32x2 v = {a, b};
-    const xf16x2 h = __builtin_convertvector(v, xf16x2);
-    const unsigned hb = __builtin_bit_cast(unsigned, h);
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hb), "v"(a));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hb), "v"(b));
-    const xf32x2 lv = {l0, l1};
-    hi = hb;
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(lv, xf16x2));
-}
-
 template <int C>
 __global__ __launch_bounds__(256) void pdsc_attention_x3_kernel(const float *__restrict__ QKV, const float *__restrict__ sc,
                                                                  const int32_t *__restrict__ n_rows, int n_cap,
@@ -630,210 +599,15 @@ __global__ __launch_bounds__(256) void pdsc_attention_x3_kernel(const float *__r
         }
 }
 
-// The same kernel fed by pdsc_pcn_qkv_x3_kernel's K / V tile images (C = 128, no key split across workgroups): K / V of a tile arrive
-// pre-split and in LDS layout, 66 pieces of 1 KB by LDS-DMA - no staging registers, no conversion work (the fp32-fed kernel splits the same
+// The same attention fed by pdsc_pcn_qkv_x3_kernel's K / V tile images (C = 128, no key split across workgroups): K / V of a tile arrive
+// pre-split and in LDS layout, 64 pieces of 1 KB by LDS-DMA - no staging registers, no conversion work (the fp32-fed kernel splits the same
 // K / V in each of a pair's four query-block workgroups) - and the next tile lands in a second buffer while this one is multiplied: one
 // barrier per tile instead of two.
-template <int C>
-__global__ __launch_bounds__(256) void pdsc_attention_x3_img_kernel(const float *__restrict__ QKV, const char *__restrict__ kv_img,
-                                                                     const float *__restrict__ sc, const int32_t *__restrict__ n_rows,
-                                                                     int n_cap, float inv_sqrt_c, float *__restrict__ msg, int n_pairs)
-{
-    static_assert(C == 128, "tile image geometry");
-    constexpr int CB = C / 32;
-    constexpr int NS = C / 16;                    // k16 steps of the first product
-    // (K rows of the tile image: pdsc_k_img_elem, pdsc.h)
-    extern __shared__ __attribute__((aligned(1024))) char att_lds[];            // two tile images
-    // XCD-aware block map: the query blocks of one pair read the same K / V tile images, so they go to ONE XCD (linear block id mod 8) and
-    // share the images through its L2 (with the plain (query block, pair) grid a pair's four blocks landed on four XCDs and each fetched
-    // the pair's 540 KB of images for itself).  The grid's z extent is B rounded up to a multiple of 8.
-    const int lin = blockIdx.x + gridDim.x * blockIdx.z;
-    const int b = (lin / 8 / (int)gridDim.x) * 8 + (lin & 7);
-    const int qblk = (lin / 8) % (int)gridDim.x;
-    if (b >= n_pairs) return;
-    const int n = n_rows[b];
-    const int q0 = qblk * ATT_Q;
-    if (q0 >= n) return;
-    const int j_begin = 0, j_end = n;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const int qrow = q0 + wave * 32 + l31;
-    const float *base = QKV + (size_t)b * n_cap * 3 * C;
-    const char *img = kv_img + (size_t)b * (n_cap / ATT_KT) * PDSC_KV_TILE_BYTES;
-    const float4 *sc_q = reinterpret_cast<const float4 *>(sc) + (((size_t)b * (n_cap / 32) + (q0 / 32 + wave)) * (n_cap / ATT_KT)) * 8 * 64 + lane;
-    const bool q_live = q0 + wave * 32 < n;
-    float4 scv[8];
-    auto dma_tile = [&](int j0, int buf) {
-        const char *src = img + (size_t)(j0 / ATT_KT) * PDSC_KV_TILE_BYTES;
-#pragma unroll
-        for (int j = 0; j < 17; ++j) {
-            const int piece = wave_u * 17 + j;
-            if (piece < PDSC_KV_TILE_BYTES / 1024)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + piece * 1024 + lane * 16),
-                                                 (__attribute__((address_space(3))) void *)(att_lds + buf * PDSC_KV_TILE_BYTES + piece * 1024), 16, 0, 0);
-        }
-    };
-    auto fetch_sc = [&](int j0) {
-        const float4 *sp = sc_q + (size_t)(j0 / ATT_KT) * 8 * 64;
-#pragma unroll
-        for (int v4 = 0; v4 < 8; ++v4) scv[v4] = q_live ? sp[(size_t)v4 * 64] : make_float4(-1.f, -1.f, -1.f, -1.f);
-    };
-
-    // Q^T as B operand: lane (query l31, half hi), k16 step s -> channels 16s + 8hi .. +7, split once
-    xhalf8 qh[NS], ql[NS];
-    {
-        const float4 *qv = reinterpret_cast<const float4 *>(base + (size_t)qrow * 3 * C);
-#pragma unroll
-        for (int s_ = 0; s_ < NS; ++s_) {
-            const float4 a = qv[4 * s_ + 2 * hi], c = qv[4 * s_ + 2 * hi + 1];
-            const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                _Float16 h_, l_;
-                split_half(x[e], h_, l_);
-                qh[s_][e] = h_;
-                ql[s_][e] = l_;
-            }
-        }
-    }
-    f32x16 acc_o[CB];
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc_o[cb][r] = 0.0f;
-    float m_run = -INFINITY, l_run = 0.0f;
-
-    dma_tile(0, 0);
-    fetch_sc(0);
-    int buf = 0;
-    for (int j0 = j_begin; j0 < j_end; j0 += ATT_KT, buf ^= 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // this tile's pieces (and SC values) have landed
-        __syncthreads();                                                 // ... everybody's; and the other buffer is no longer read
-        if (j0 + ATT_KT < j_end) dma_tile(j0 + ATT_KT, buf ^ 1);
-        const _Float16 *Kh = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES);
-        const _Float16 *Kl = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES + PDSC_KV_KL);
-        const _Float16 *Vh = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES + PDSC_KV_VH);
-        const _Float16 *Vl = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES + PDSC_KV_VL);
-
-        // S^T = K Q^T, three fp16 products per k16 step and key block
-        f32x16 s[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kb][r] = 0.0f;
-        // One wave per SIMD: nobody hides an LDS read that is waited for right after its issue, and that is how the compiler orders
-        // this loop when left alone (ds_read -> s_waitcnt lgkmcnt(0) -> 1-2 MFMAs, 32 times per tile).  The fragments of k16 step
-        // s_+1 are therefore requested before the MFMAs of step s_, and sched_barrier keeps it that way.
-        xhalf8 kf[2][2][2];                           // [buffer][key block][hi | lo]
-        auto read_k = [&](int s_, int buf) {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                kf[buf][kb][0] = *reinterpret_cast<const xhalf8 *>(Kh + pdsc_k_img_elem(kb * 32 + l31, 2 * s_ + hi));
-                kf[buf][kb][1] = *reinterpret_cast<const xhalf8 *>(Kl + pdsc_k_img_elem(kb * 32 + l31, 2 * s_ + hi));
-            }
-        };
-        read_k(0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s_ = 0; s_ < NS; ++s_) {
-            const int buf = s_ & 1;
-            if (s_ + 1 < NS) read_k(s_ + 1, buf ^ 1);
-            __builtin_amdgcn_sched_barrier(0);
-            // the two key blocks alternate: back-to-back MFMAs are independent; per accumulator the order stays hi*hi, hi*lo, lo*hi
-            s[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[buf][0][0], qh[s_], s[0], 0, 0, 0);
-            s[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[buf][1][0], qh[s_], s[1], 0, 0, 0);
-            s[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[buf][0][0], ql[s_], s[0], 0, 0, 0);
-            s[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[buf][1][0], ql[s_], s[1], 0, 0, 0);
-            s[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[buf][0][1], qh[s_], s[0], 0, 0, 0);
-            s[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[buf][1][1], qh[s_], s[1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        float m_tile = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float4 q4 = scv[kb * 4 + (r >> 2)];
-                const float scq = (r & 3) == 0 ? q4.x : (r & 3) == 1 ? q4.y : (r & 3) == 2 ? q4.z : q4.w;
-                float v = scq * (s[kb][r] * inv_sqrt_c);
-                v = (scq >= 0.0f) ? v : -INFINITY;
-                s[kb][r] = v;
-                m_tile = fmaxf(m_tile, v);
-            }
-        if (j0 + ATT_KT < j_end) fetch_sc(j0 + ATT_KT);
-        m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32));
-        const float m_new = fmaxf(m_run, m_tile);
-        const float alpha = __expf(m_run - m_new);
-        float l_tile = 0.0f;
-        xhalf8 ph[2][2], pl[2][2];                  // [kb][t2]: keys crow(8*t2 + e, hi)
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const float p0 = __expf(s[kb][r] - m_new);    // v_exp_f32 path: ~1e-6 relative, VALU issue is what bounds this kernel
-                const float p1 = __expf(s[kb][r + 1] - m_new);
-                l_tile += p0;
-                l_tile += p1;
-                unsigned uh, ul;
-                split_pair(p0, p1, uh, ul);
-                const xf16x2 h2 = __builtin_bit_cast(xf16x2, uh), l2 = __builtin_bit_cast(xf16x2, ul);
-                ph[kb][r >> 3][r & 7] = h2[0]; ph[kb][r >> 3][(r & 7) + 1] = h2[1];
-                pl[kb][r >> 3][r & 7] = l2[0]; pl[kb][r >> 3][(r & 7) + 1] = l2[1];
-            }
-        l_run = l_run * alpha + l_tile;
-        m_run = m_new;
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc_o[cb][r] *= alpha;
-        // O^T += V^T P^T.  ONE fragment buffer, channel-block-major: the three MFMAs of block cb are followed by the read of cb's fragments
-        // for the next octet pair, which then has the nine MFMAs of the other blocks to arrive (a second buffer costs 32 registers this
-        // kernel does not have: every value beyond 256 is parked in AGPRs and copied back, ~100 v_accvgpr moves per tile)
-        xhalf8 vf[CB][2];
-        auto read_v1 = [&](int o, int cb) {
-            const int oct = o * 2 + hi;
-            vf[cb][0] = *reinterpret_cast<const xhalf8 *>(Vh + ((size_t)oct * C + cb * 32 + l31) * 8);
-            vf[cb][1] = *reinterpret_cast<const xhalf8 *>(Vl + ((size_t)oct * C + cb * 32 + l31) * 8);
-        };
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) read_v1(0, cb);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            const int kb = o >> 1, t2 = o & 1;
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[cb][0], ph[kb][t2], acc_o[cb], 0, 0, 0);
-                acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[cb][0], pl[kb][t2], acc_o[cb], 0, 0, 0);
-                acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[cb][1], ph[kb][t2], acc_o[cb], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (o + 1 < 4) read_v1(o + 1, cb);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-    const float l_all = l_run + __shfl_xor(l_run, 32);
-    const float inv_l = 1.0f / l_all;
-    float *mo = msg + ((size_t)b * n_cap + qrow) * C;
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float4 v;
-            v.x = acc_o[cb][4 * g + 0] * inv_l;
-            v.y = acc_o[cb][4 * g + 1] * inv_l;
-            v.z = acc_o[cb][4 * g + 2] * inv_l;
-            v.w = acc_o[cb][4 * g + 3] * inv_l;
-            *reinterpret_cast<float4 *>(mo + cb * 32 + 8 * g + 4 * hi) = v;
-        }
-}
-
-// The same attention with EIGHT waves per workgroup (round 3): the two 32-key blocks of every 64-key tile go to two different waves of a
-// query block (wave = query block w | key half kh), each with its own online softmax over its keys; the two partial results (O, m, l) of
-// a query block are merged once at the end through LDS - the exact softmax algebra of pdsc_attention_merge_kernel.  A wave then holds ONE
-// score block, half of the P / K / V fragments and SC values: 248 registers instead of 312 + AGPR parking, so two waves share a SIMD and
-// one's softmax VALU runs under the other's MFMAs (the 4-wave kernel is a strict sequence of phases with one wave per SIMD: MFMA 43 %,
-// softmax VALU 25 %, nothing overlapping).  Same K / V tile images, same DMA, one barrier per tile.
+// EIGHT waves per workgroup: the two 32-key blocks of every 64-key tile go to two different waves of a query block (wave = query block w |
+// key half kh), each with its own online softmax over its keys; the two partial results (O, m, l) of a query block are merged once at the
+// end through LDS - the exact softmax algebra of pdsc_attention_merge_kernel.  A wave then holds ONE score block, half of the P / K / V
+// fragments and SC values, so two waves share a SIMD and one's softmax VALU runs under the other's MFMAs (with four waves, one per SIMD,
+// the kernel is a strict sequence of phases: MFMA 43 %, softmax VALU 25 %, nothing overlapping).
 template <int C>
 __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float *__restrict__ QKV, const char *__restrict__ kv_img,
                                                                       const float *__restrict__ sc, const int32_t *__restrict__ n_rows,
@@ -843,9 +617,8 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
     constexpr int CB = C / 32;
     constexpr int NS = C / 16;
     extern __shared__ __attribute__((aligned(1024))) char att_lds[];
-    const int lin = blockIdx.x + gridDim.x * blockIdx.z;
-    const int b = (lin / 8 / (int)gridDim.x) * 8 + (lin & 7);
-    const int qblk = (lin / 8) % (int)gridDim.x;
+    int b, qblk;
+    att8_block_map(b, qblk);
     if (b >= n_pairs) return;
     const int n = n_rows[b];
     const int q0 = qblk * ATT_Q;
@@ -859,21 +632,6 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
     const float4 *sc_q = reinterpret_cast<const float4 *>(sc) + (((size_t)b * (n_cap / 32) + (q0 / 32 + wave)) * (n_cap / ATT_KT)) * 8 * 64 + lane;
     const bool q_live = q0 + wave * 32 < n;
     float4 scv[4];
-    auto dma_tile = [&](int j0, int buf) {
-        const char *src = img + (size_t)(j0 / ATT_KT) * PDSC_KV_TILE_BYTES;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const int piece = wave_u * 9 + j;
-            if (piece < PDSC_KV_TILE_BYTES / 1024)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + piece * 1024 + lane * 16),
-                                                 (__attribute__((address_space(3))) void *)(att_lds + buf * PDSC_KV_TILE_BYTES + piece * 1024), 16, 0, 0);
-        }
-    };
-    auto fetch_sc = [&](int j0) {
-        const float4 *sp = sc_q + (size_t)(j0 / ATT_KT) * 8 * 64 + (size_t)kb * 4 * 64;
-#pragma unroll
-        for (int v4 = 0; v4 < 4; ++v4) scv[v4] = q_live ? sp[(size_t)v4 * 64] : make_float4(-1.f, -1.f, -1.f, -1.f);
-    };
     xhalf8 qh[NS], ql[NS];
     {
         const float4 *qv = reinterpret_cast<const float4 *>(base + (size_t)qrow * 3 * C);
@@ -897,31 +655,24 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
         for (int r = 0; r < 16; ++r) acc_o[cb][r] = 0.0f;
     float m_run = -INFINITY, l_run = 0.0f;
 
-    dma_tile(0, 0);
-    fetch_sc(0);
+    dma_kv_tile(img, 0, att_lds, wave_u, lane);
+    fetch_sc(sc_q, q_live, kb, 0, scv);
     int buf = 0;
     for (int j0 = 0; j0 < n; j0 += ATT_KT, buf ^= 1) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (j0 + ATT_KT < n) dma_tile(j0 + ATT_KT, buf ^ 1);
-        const _Float16 *Kh = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES);
-        const _Float16 *Kl = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES + PDSC_KV_KL);
-        const _Float16 *Vh = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES + PDSC_KV_VH);
-        const _Float16 *Vl = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES + PDSC_KV_VL);
+        if (j0 + ATT_KT < n) dma_kv_tile(img, j0 + ATT_KT, att_lds + (buf ^ 1) * PDSC_KV_TILE_BYTES, wave_u, lane);
+        const char *tile = att_lds + buf * PDSC_KV_TILE_BYTES;
         // S^T (this wave's 32 keys x 32 queries)
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.0f;
         xhalf8 kf[2][2];                              // [buffer][hi | lo]
-        auto read_k = [&](int s_, int bf) {
-            kf[bf][0] = *reinterpret_cast<const xhalf8 *>(Kh + pdsc_k_img_elem(kb * 32 + l31, 2 * s_ + hi));
-            kf[bf][1] = *reinterpret_cast<const xhalf8 *>(Kl + pdsc_k_img_elem(kb * 32 + l31, 2 * s_ + hi));
-        };
-        read_k(0, 0);
+        read_k(tile, kb * 32 + l31, 0, hi, kf[0]);
 #pragma unroll
         for (int s_ = 0; s_ < NS; ++s_) {
             const int bf = s_ & 1;
-            if (s_ + 1 < NS) read_k(s_ + 1, bf ^ 1);
+            if (s_ + 1 < NS) read_k(tile, kb * 32 + l31, s_ + 1, hi, kf[bf ^ 1]);
             s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[bf][0], qh[s_], s, 0, 0, 0);
             s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[bf][0], ql[s_], s, 0, 0, 0);
             s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[bf][1], qh[s_], s, 0, 0, 0);
@@ -936,7 +687,7 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
             s[r] = v;
             m_tile = fmaxf(m_tile, v);
         }
-        if (j0 + ATT_KT < n) fetch_sc(j0 + ATT_KT);
+        if (j0 + ATT_KT < n) fetch_sc(sc_q, q_live, kb, j0 + ATT_KT, scv);
         m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32));
         const float m_new = fmaxf(m_run, m_tile);
         // a block whose keys are all masked so far keeps m = -inf: exp(-inf - (-inf)) must not produce NaN
@@ -969,8 +720,7 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
             const int oct = (kb * 2 + t2) * 2 + hi;
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
-                const xhalf8 vh = *reinterpret_cast<const xhalf8 *>(Vh + ((size_t)oct * C + cb * 32 + l31) * 8);
-                const xhalf8 vl = *reinterpret_cast<const xhalf8 *>(Vl + ((size_t)oct * C + cb * 32 + l31) * 8);
+                const xhalf8 vh = read_v(tile + PDSC_KV_VH, oct, cb * 32 + l31), vl = read_v(tile + PDSC_KV_VL, oct, cb * 32 + l31);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[t2], acc_o[cb], 0, 0, 0);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[t2], acc_o[cb], 0, 0, 0);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[t2], acc_o[cb], 0, 0, 0);
@@ -1107,16 +857,6 @@ __global__ __launch_bounds__(256) void pdsc_linear_x3_kernel(const float *__rest
 // order.  oryon_pointdsc_finalize stores the three matrices that way (pre-split into fp16 hi / lo, rows swizzled: PDSC_MLP_* image), so the
 // intermediate activations never leave the registers: bias + ReLU + split, next MFMA.  A wave owns 32 points and all channels; a workgroup
 // (4 waves, 128 points) copies the 80 KB weight image into LDS once (LDS-DMA) while its waves fetch and split their input rows.
-// A bias float4 at a WAVE-UNIFORM offset for lane half `hi` (channels off + 4 hi .. + 3): both halves come through the scalar cache
-// (uniform address -> s_load, lgkmcnt) and the lane picks one.  Round 6: as vector loads (address + 16 hi) they sat on the vector-memory
-// counter between the epilogue's stores, and the compiler's s_waitcnt vmcnt(0) in front of each use made every store of the per-point
-// chain wait for the acknowledgement of the one before it - 5 to 8 us per 16 KB of output (the phase clocks of ORYON_PDSC_CLOCKS).
-__device__ __forceinline__ float4 bias4(const float *__restrict__ b, int off, int hi)
-{
-    const float4 lo = *reinterpret_cast<const float4 *>(b + off), up = *reinterpret_cast<const float4 *>(b + off + 4);
-    return hi ? up : lo;
-}
-
 template <int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void pdsc_mlp3_x3_kernel(const float *__restrict__ msg, const float *__restrict__ resid,
                                                             const char *__restrict__ img, const float *__restrict__ b1,
@@ -1129,106 +869,24 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_mlp3_x3_kernel(const float *_
     if (q0 >= n_rows[b]) return;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    // weight image -> LDS: 80 pieces of 1 KB, 80 / WAVES per wave, lane-linear
-    static_assert((PDSC_MLP_IMG_BYTES / 1024) % WAVES == 0, "pieces per wave");
-#pragma unroll
-    for (int j = 0; j < PDSC_MLP_IMG_BYTES / 1024 / WAVES; ++j) {
-        const int piece = wave_u * (PDSC_MLP_IMG_BYTES / 1024 / WAVES) + j;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(img + piece * 1024 + lane * 16),
-                                         (__attribute__((address_space(3))) void *)(mlp_lds + piece * 1024), 16, 0, 0);
-    }
-    // this lane's point: channels 16 s + 8 hi .. + 7 of k-step s, split into B-operand fragments
-    const size_t prow = ((size_t)b * n_cap + q0 + wave * 32 + l31) * C;
+    dma_mlp_image<WAVES>(img, mlp_lds, wave_u, lane);
+    const size_t prow = ((size_t)b * n_cap + q0 + wave * 32 + l31) * C;       // this lane's point
     xhalf8 xh[8], xl[8];
-    {
-        const float4 *xp = reinterpret_cast<const float4 *>(msg + prow);
-        float4 raw[16];
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) { raw[2 * s_] = xp[4 * s_ + 2 * hi]; raw[2 * s_ + 1] = xp[4 * s_ + 2 * hi + 1]; }
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
-            uint4 uh, ul;
-            split_pair(raw[2 * s_].x, raw[2 * s_].y, uh.x, ul.x);
-            split_pair(raw[2 * s_].z, raw[2 * s_].w, uh.y, ul.y);
-            split_pair(raw[2 * s_ + 1].x, raw[2 * s_ + 1].y, uh.z, ul.z);
-            split_pair(raw[2 * s_ + 1].z, raw[2 * s_ + 1].w, uh.w, ul.w);
-            xh[s_] = __builtin_bit_cast(xhalf8, uh);
-            xl[s_] = __builtin_bit_cast(xhalf8, ul);
-        }
-    }
+    load_split_row(msg + prow, hi, xh, xl);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    // A fragments: 256-byte rows (W1) slot ^ (row & 15), 128-byte rows (W2, W3) slot ^ ((row >> 1) & 7)
-    auto w1_frag = [&](int base, int rb, int s_) {
-        const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(mlp_lds + base + o * 256 + (((2 * s_ + hi) ^ (o & 15)) << 4));
-    };
-    auto w23_frag = [&](int base, int rb, int s_) {
-        const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(mlp_lds + base + o * 128 + (((2 * s_ + hi) ^ ((o >> 1) & 7)) << 4));
-    };
-    // bias + ReLU + split of two 32-channel accumulator blocks -> the 4 B fragments (k-steps) of the next layer
-    auto next_operand = [&](const f32x16 (&acc)[2], const float *bias, xhalf8 (&oh)[4], xhalf8 (&ol)[4]) {
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                uint4 uh, ul;
-                unsigned *ph = &uh.x, *pl = &ul.x;
-#pragma unroll
-                for (int g2 = 0; g2 < 2; ++g2) {                 // registers 8 j + 4 g2 .. + 3: channels rb*32 + 8 (2 j + g2) + 4 hi + 0..3
-                    const float4 bv = *reinterpret_cast<const float4 *>(bias + rb * 32 + 8 * (2 * j + g2) + 4 * hi);
-                    const int r0 = 8 * j + 4 * g2;
-                    const float v0 = fmaxf(acc[rb][r0] + bv.x, 0.0f), v1 = fmaxf(acc[rb][r0 + 1] + bv.y, 0.0f);
-                    const float v2 = fmaxf(acc[rb][r0 + 2] + bv.z, 0.0f), v3 = fmaxf(acc[rb][r0 + 3] + bv.w, 0.0f);
-                    split_pair(v0, v1, ph[2 * g2], pl[2 * g2]);
-                    split_pair(v2, v3, ph[2 * g2 + 1], pl[2 * g2 + 1]);
-                }
-                oh[rb * 2 + j] = __builtin_bit_cast(xhalf8, uh);
-                ol[rb * 2 + j] = __builtin_bit_cast(xhalf8, ul);
-            }
-    };
-    // Two 32-channel output blocks (rb0, rb0 + 1) over NS k-steps: the four weight fragments of step s+1 are requested before the six
-    // MFMAs of step s (left alone the compiler reads each fragment right before its first use: one exposed LDS latency per fragment).
-    // The two accumulators alternate, per accumulator the order is hi*hi, hi*lo, lo*hi.
-    auto two_blocks = [&](auto &&frag, int base_h, int base_l, int rb0, int NS, const xhalf8 *bh, const xhalf8 *bl, f32x16 (&acc)[2]) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
-        xhalf8 w[2][2][2];                            // [buffer][block][hi | lo]
-#pragma unroll
-        for (int i = 0; i < 2; ++i) { w[0][i][0] = frag(base_h, rb0 + i, 0); w[0][i][1] = frag(base_l, rb0 + i, 0); }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
-            if (s_ < NS) {
-                const int cur = s_ & 1;
-                if (s_ + 1 < NS) {
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) { w[cur ^ 1][i][0] = frag(base_h, rb0 + i, s_ + 1); w[cur ^ 1][i][1] = frag(base_l, rb0 + i, s_ + 1); }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][0], bh[s_], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][0], bh[s_], acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][0], bl[s_], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][0], bl[s_], acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][1], bh[s_], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][1], bh[s_], acc[1], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
+    const Frag256 w1_frag{mlp_lds, l31, hi};
+    const Frag128 w23_frag{mlp_lds, l31, hi};
     // layer 1: [64, 128] x [128, points]
     f32x16 a1[2];
-    two_blocks(w1_frag, PDSC_MLP_W1H, PDSC_MLP_W1L, 0, 8, xh, xl, a1);
+    two_blocks<8, false>(w1_frag, PDSC_MLP_W1H, PDSC_MLP_W1L, 0, xh, xl, a1);
     xhalf8 h1h[4], h1l[4];
-    next_operand(a1, b1, h1h, h1l);
+    next_operand(a1, BiasVector{b1}, 0, hi, h1h, h1l);
     // layer 2: [64, 64] x [64, points]
     f32x16 a2[2];
-    two_blocks(w23_frag, PDSC_MLP_W2H, PDSC_MLP_W2L, 0, 4, h1h, h1l, a2);
+    two_blocks<4, false>(w23_frag, PDSC_MLP_W2H, PDSC_MLP_W2L, 0, h1h, h1l, a2);
     xhalf8 h2h[4], h2l[4];
-    next_operand(a2, b2, h2h, h2l);
+    next_operand(a2, BiasVector{b2}, 0, hi, h2h, h2l);
     // layer 3: [128, 64] x [64, points], + bias + residual, stored as float4 groups (channels rb*32 + 8 g + 4 hi + 0..3 of the lane's point)
 #pragma unroll
     for (int rp = 0; rp < 2; ++rp) {
@@ -1238,7 +896,7 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_mlp3_x3_kernel(const float *_
 #pragma unroll
             for (int g = 0; g < 4; ++g) rv[i][g] = *reinterpret_cast<const float4 *>(resid + prow + (2 * rp + i) * 32 + 8 * g + 4 * hi);
         f32x16 a3[2];
-        two_blocks(w23_frag, PDSC_MLP_W3H, PDSC_MLP_W3L, 2 * rp, 4, h2h, h2l, a3);
+        two_blocks<4, false>(w23_frag, PDSC_MLP_W3H, PDSC_MLP_W3L, 2 * rp, h2h, h2l, a3);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1273,34 +931,11 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_pcn_qkv_x3_kernel(const float
     if (q0 >= n_rows[b]) return;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    auto dma_chunk = [&](int chunk, int area) {                       // 64 pieces of 1 KB, 64 / WAVES per wave
-#pragma unroll
-        for (int j = 0; j < 64 / WAVES; ++j) {
-            const int piece = wave_u * (64 / WAVES) + j;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(img + (size_t)chunk * PDSC_PQ_CHUNK_BYTES + piece * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void *)(pq_lds + area * PDSC_PQ_CHUNK_BYTES + piece * 1024), 16, 0, 0);
-        }
-    };
-    dma_chunk(0, 0);
-    dma_chunk(1, 1);
+    dma_pq_chunk<WAVES>(img, 0, pq_lds, wave_u, lane);
+    dma_pq_chunk<WAVES>(img, 1, pq_lds + PDSC_PQ_CHUNK_BYTES, wave_u, lane);
     const size_t prow = (size_t)b * n_cap + q0 + wave * 32 + l31;
     xhalf8 xh[8], xl[8];
-    {
-        const float4 *xp = reinterpret_cast<const float4 *>(feat + prow * C);
-        float4 raw[16];
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) { raw[2 * s_] = xp[4 * s_ + 2 * hi]; raw[2 * s_ + 1] = xp[4 * s_ + 2 * hi + 1]; }
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
-            uint4 uh, ul;
-            split_pair(raw[2 * s_].x, raw[2 * s_].y, uh.x, ul.x);
-            split_pair(raw[2 * s_].z, raw[2 * s_].w, uh.y, ul.y);
-            split_pair(raw[2 * s_ + 1].x, raw[2 * s_ + 1].y, uh.z, ul.z);
-            split_pair(raw[2 * s_ + 1].z, raw[2 * s_ + 1].w, uh.w, ul.w);
-            xh[s_] = __builtin_bit_cast(xhalf8, uh);
-            xl[s_] = __builtin_bit_cast(xhalf8, ul);
-        }
-    }
+    load_split_row(feat + prow * C, hi, xh, xl);
     // v's bias is per lane (lane = channel): fetched here, with the inputs, so that the wait below covers it - a load waited for between the
     // parts' stores would be waited for with vmcnt(0), i.e. behind every earlier store's acknowledgement
     float bias_v[4];
@@ -1309,55 +944,13 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_pcn_qkv_x3_kernel(const float
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("" ::"v"(bias_v[0]), "v"(bias_v[1]), "v"(bias_v[2]), "v"(bias_v[3]));
     __syncthreads();
-    auto frag = [&](int base, int rb, int s_) {
-        const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(pq_lds + base + o * 256 + (((2 * s_ + hi) ^ (o & 15)) << 4));
-    };
-    // two 32-channel output blocks over the 8 k-steps, fragments of step s+1 requested before the MFMAs of step s (see pdsc_mlp3_x3_kernel)
-    // swap = false: weights are the A operand (accumulator: lane = point, registers = channels); swap = true: the activations are (lane =
-    // channel, registers = points crow(r, hi)) - the same fragments either way, the 32x32x16 A and B register layouts are mirror images
-    auto two_blocks = [&](int area, int rb0, const xhalf8 *bh, const xhalf8 *bl, f32x16 (&acc)[2], bool swap) {
-        const int base_h = area * PDSC_PQ_CHUNK_BYTES, base_l = base_h + HALF;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
-        xhalf8 w[2][2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) { w[0][i][0] = frag(base_h, rb0 + i, 0); w[0][i][1] = frag(base_l, rb0 + i, 0); }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
-            const int cur = s_ & 1;
-            if (s_ + 1 < 8) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) { w[cur ^ 1][i][0] = frag(base_h, rb0 + i, s_ + 1); w[cur ^ 1][i][1] = frag(base_l, rb0 + i, s_ + 1); }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (!swap) {
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][0], bh[s_], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][0], bh[s_], acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][0], bl[s_], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][0], bl[s_], acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][1], bh[s_], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][1], bh[s_], acc[1], 0, 0, 0);
-            } else {
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][0][0], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][1][0], acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s_], w[cur][0][0], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s_], w[cur][1][0], acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][0][1], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][1][1], acc[1], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
+    const Frag256 frag{pq_lds, l31, hi};
     // layer 1 (PointCN, area 0): bias + ReLU, stored as feat1 and kept as the 8 B fragments of layer 2
     xhalf8 fh[8], fl[8];
 #pragma unroll
     for (int rp = 0; rp < 2; ++rp) {
         f32x16 acc[2];
-        two_blocks(0, 2 * rp, xh, xl, acc, false);
+        two_blocks<8, false>(frag, 0, HALF, 2 * rp, xh, xl, acc);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int rb = 2 * rp + i;
@@ -1394,36 +987,24 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_pcn_qkv_x3_kernel(const float
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                            // every wave is done with the other area; part's chunk visible
         asm volatile("" ::: "memory");
-        if (part < 2) dma_chunk(part + 2, area ^ 1);
+        if (part < 2) dma_pq_chunk<WAVES>(img, part + 2, pq_lds + (area ^ 1) * PDSC_PQ_CHUNK_BYTES, wave_u, lane);
         // q (and k, v without an image buffer): fp32 rows of the q|k|v array.  With `kv_img`: k and v leave as the attention kernel's LDS
-        // tile image, already split into fp16 hi / lo - k rows [key][136 halves] from the transposed product (lane = key: 8-byte pieces),
-        // v from the un-transposed one (lane = channel, registers 8 t2 .. 8 t2 + 7 = the 8 keys of octet (kb, t2, hi): 16-byte pieces).
+        // tile image (pdsc.h), already split into fp16 hi / lo - k from the transposed product (lane = key: store_k), v from the
+        // un-transposed one (lane = channel: store_v).
         const int p_pair = q0 + wave * 32;                           // first point of this wave inside its pair
         char *tile = kv_img ? kv_img + ((size_t)b * (n_cap / 64) + (p_pair >> 6)) * PDSC_KV_TILE_BYTES : nullptr;
         const bool as_v = kv_img && part == 2;
 #pragma unroll
         for (int rp = 0; rp < 2; ++rp) {
             f32x16 acc[2];
-            two_blocks(area, 2 * rp, fh, fl, acc, as_v);
+            const int base_h = area * PDSC_PQ_CHUNK_BYTES;
             if (as_v) {
+                two_blocks<8, true>(frag, base_h, base_h + HALF, 2 * rp, fh, fl, acc);
                 const int kb = (p_pair >> 5) & 1;
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int ch = (2 * rp + i) * 32 + l31;
-                    const float bv = bias_v[2 * rp + i];
-#pragma unroll
-                    for (int t2 = 0; t2 < 2; ++t2) {
-                        uint4 uh, ul;
-                        split_pair(acc[i][8 * t2 + 0] + bv, acc[i][8 * t2 + 1] + bv, uh.x, ul.x);
-                        split_pair(acc[i][8 * t2 + 2] + bv, acc[i][8 * t2 + 3] + bv, uh.y, ul.y);
-                        split_pair(acc[i][8 * t2 + 4] + bv, acc[i][8 * t2 + 5] + bv, uh.z, ul.z);
-                        split_pair(acc[i][8 * t2 + 6] + bv, acc[i][8 * t2 + 7] + bv, uh.w, ul.w);
-                        const int oct = (kb * 2 + t2) * 2 + hi;
-                        *reinterpret_cast<uint4 *>(tile + PDSC_KV_VH + ((size_t)oct * C + ch) * 16) = uh;
-                        *reinterpret_cast<uint4 *>(tile + PDSC_KV_VL + ((size_t)oct * C + ch) * 16) = ul;
-                    }
-                }
+                for (int i = 0; i < 2; ++i) store_v(tile, acc[i], bias_v[2 * rp + i], kb, (2 * rp + i) * 32 + l31, hi);
             } else {
+                two_blocks<8, false>(frag, base_h, base_h + HALF, 2 * rp, fh, fl, acc);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1434,272 +1015,9 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_pcn_qkv_x3_kernel(const float
                         o.x = acc[i][4 * g + 0] + bv.x; o.y = acc[i][4 * g + 1] + bv.y;
                         o.z = acc[i][4 * g + 2] + bv.z; o.w = acc[i][4 * g + 3] + bv.w;
                         if (kv_img && part == 1) {
-                            uint2 uh, ul;
-                            split_pair(o.x, o.y, uh.x, ul.x);
-                            split_pair(o.z, o.w, uh.y, ul.y);
-                            const size_t off = (size_t)pdsc_k_img_elem((p_pair & 63) + l31, cc >> 3) * 2 + (cc & 7) * 2;
-                            *reinterpret_cast<uint2 *>(tile + off) = uh;
-                            *reinterpret_cast<uint2 *>(tile + PDSC_KV_KL + off) = ul;
+                            store_k(tile, o, (p_pair & 63) + l31, cc);
                         } else if (g4 && part == 0) {
                             reinterpret_cast<float4 *>(qkv + (size_t)b * n_cap * 3 * C)[pdsc_g4_index(n_cap, q0 + wave * 32 + l31, cc >> 2)] = o;
-                        } else {
-                            *reinterpret_cast<float4 *>(qkv + prow * 3 * C + c) = o;
-                        }
-                    }
-            }
-        }
-    }
-}
-
-// fc_message of layer l AND PointCN + q|k|v of layer l + 1 as ONE kernel (round 4): both are per-point chains on the same transposed
-// register layout, so the layer output  feat = feat1 + W3 relu(W2 relu(W1 msg + b1) + b2) + b3  never leaves the registers - bias +
-// residual + split and it IS the B operand of the next layer's PointCN, whose weights therefore come with their K axis in
-// accumulator-register order (chunk 4 of the next layer's image; chunk 0 keeps the natural order for layer 0, whose input comes from
-// memory).  One launch, one fetch of the rows and one write of the features less per layer (11 of the encoder's 36 launches).
-// LDS: the 80 KB fc_message image at 0, PointCN' (64 KB) beside it from the start; q, k, v then stream through the two areas as in
-// pdsc_pcn_qkv_x3_kernel (area 1 = offset 0 once the fc_message image is dead, area 0 = offset 80 KB).
-// resid / feat1 may be the same buffer (a lane reads its residual row before it writes the row of the next layer): no __restrict__.
-template <int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void pdsc_mlp3_pcn_qkv_x3_kernel(const float *__restrict__ msg, const float *resid,
-                                                                    const char *__restrict__ mlp_img, const float *__restrict__ b1,
-                                                                    const float *__restrict__ b2, const float *__restrict__ b3,
-                                                                    const char *__restrict__ pq_img, const float *__restrict__ bp,
-                                                                    const float *__restrict__ bq, const int32_t *__restrict__ n_rows, int n_cap,
-                                                                    float *feat1, float *__restrict__ qkv, char *__restrict__ kv_img)
-{
-    constexpr int C = 128, HALF = PDSC_PQ_CHUNK_BYTES / 2;
-    constexpr int AREA0 = PDSC_MLP_IMG_BYTES, AREA1 = 0;               // byte offsets of the two 64 KB weight areas
-    extern __shared__ __attribute__((aligned(1024))) char fz_lds[];
-    const int b = blockIdx.y, q0 = blockIdx.x * (32 * WAVES);
-    if (q0 >= n_rows[b]) return;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    static_assert((PDSC_MLP_IMG_BYTES / 1024) % WAVES == 0, "pieces per wave");
-#pragma unroll
-    for (int j = 0; j < PDSC_MLP_IMG_BYTES / 1024 / WAVES; ++j) {
-        const int piece = wave_u * (PDSC_MLP_IMG_BYTES / 1024 / WAVES) + j;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(mlp_img + piece * 1024 + lane * 16),
-                                         (__attribute__((address_space(3))) void *)(fz_lds + piece * 1024), 16, 0, 0);
-    }
-    auto dma_chunk = [&](int chunk, int area_off) {                   // 64 pieces of 1 KB, 64 / WAVES per wave
-#pragma unroll
-        for (int j = 0; j < 64 / WAVES; ++j) {
-            const int piece = wave_u * (64 / WAVES) + j;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(pq_img + (size_t)chunk * PDSC_PQ_CHUNK_BYTES + piece * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void *)(fz_lds + area_off + piece * 1024), 16, 0, 0);
-        }
-    };
-    dma_chunk(4, AREA0);                                               // PointCN with the permuted K axis
-    const size_t prow = (size_t)b * n_cap + q0 + wave * 32 + l31;
-    xhalf8 xh[8], xl[8];
-    {
-        const float4 *xp = reinterpret_cast<const float4 *>(msg + prow * C);
-        float4 raw[16];
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) { raw[2 * s_] = xp[4 * s_ + 2 * hi]; raw[2 * s_ + 1] = xp[4 * s_ + 2 * hi + 1]; }
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
-            uint4 uh, ul;
-            split_pair(raw[2 * s_].x, raw[2 * s_].y, uh.x, ul.x);
-            split_pair(raw[2 * s_].z, raw[2 * s_].w, uh.y, ul.y);
-            split_pair(raw[2 * s_ + 1].x, raw[2 * s_ + 1].y, uh.z, ul.z);
-            split_pair(raw[2 * s_ + 1].z, raw[2 * s_ + 1].w, uh.w, ul.w);
-            xh[s_] = __builtin_bit_cast(xhalf8, uh);
-            xl[s_] = __builtin_bit_cast(xhalf8, ul);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    auto w1_frag = [&](int base, int rb, int s_) {
-        const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(fz_lds + base + o * 256 + (((2 * s_ + hi) ^ (o & 15)) << 4));
-    };
-    auto w23_frag = [&](int base, int rb, int s_) {
-        const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(fz_lds + base + o * 128 + (((2 * s_ + hi) ^ ((o >> 1) & 7)) << 4));
-    };
-    auto next_operand = [&](const f32x16 (&acc)[2], const float *bias, xhalf8 (&oh)[4], xhalf8 (&ol)[4]) {
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                uint4 uh, ul;
-                unsigned *ph = &uh.x, *pl = &ul.x;
-#pragma unroll
-                for (int g2 = 0; g2 < 2; ++g2) {
-                    const float4 bv = *reinterpret_cast<const float4 *>(bias + rb * 32 + 8 * (2 * j + g2) + 4 * hi);
-                    const int r0 = 8 * j + 4 * g2;
-                    const float v0 = fmaxf(acc[rb][r0] + bv.x, 0.0f), v1 = fmaxf(acc[rb][r0 + 1] + bv.y, 0.0f);
-                    const float v2 = fmaxf(acc[rb][r0 + 2] + bv.z, 0.0f), v3 = fmaxf(acc[rb][r0 + 3] + bv.w, 0.0f);
-                    split_pair(v0, v1, ph[2 * g2], pl[2 * g2]);
-                    split_pair(v2, v3, ph[2 * g2 + 1], pl[2 * g2 + 1]);
-                }
-                oh[rb * 2 + j] = __builtin_bit_cast(xhalf8, uh);
-                ol[rb * 2 + j] = __builtin_bit_cast(xhalf8, ul);
-            }
-    };
-    // two 32-row output blocks over NS k-steps (see pdsc_mlp3_x3_kernel); swap: the activations are the A operand (lane = channel)
-    auto two_blocks = [&](auto &&frag, int base_h, int base_l, int rb0, int NS, const xhalf8 *bh, const xhalf8 *bl, f32x16 (&acc)[2], bool swap) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
-        xhalf8 w[2][2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) { w[0][i][0] = frag(base_h, rb0 + i, 0); w[0][i][1] = frag(base_l, rb0 + i, 0); }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
-            if (s_ < NS) {
-                const int cur = s_ & 1;
-                if (s_ + 1 < NS) {
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) { w[cur ^ 1][i][0] = frag(base_h, rb0 + i, s_ + 1); w[cur ^ 1][i][1] = frag(base_l, rb0 + i, s_ + 1); }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (!swap) {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][0], bh[s_], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][0], bh[s_], acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][0], bl[s_], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][0], bl[s_], acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][1], bh[s_], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][1], bh[s_], acc[1], 0, 0, 0);
-                } else {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][0][0], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][1][0], acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s_], w[cur][0][0], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s_], w[cur][1][0], acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][0][1], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][1][1], acc[1], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
-    // ---- fc_message of layer l
-    f32x16 a1[2];
-    two_blocks(w1_frag, PDSC_MLP_W1H, PDSC_MLP_W1L, 0, 8, xh, xl, a1, false);
-    xhalf8 h1h[4], h1l[4];
-    next_operand(a1, b1, h1h, h1l);
-    f32x16 a2[2];
-    two_blocks(w23_frag, PDSC_MLP_W2H, PDSC_MLP_W2L, 0, 4, h1h, h1l, a2, false);
-    xhalf8 h2h[4], h2l[4];
-    next_operand(a2, b2, h2h, h2l);
-    // layer 3 + bias + residual = the layer's output features, kept as the 8 B fragments (permuted K order) of the next layer's PointCN
-#pragma unroll
-    for (int rp = 0; rp < 2; ++rp) {
-        float4 rv[2][4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) rv[i][g] = *reinterpret_cast<const float4 *>(resid + prow * C + (2 * rp + i) * 32 + 8 * g + 4 * hi);
-        f32x16 a3[2];
-        two_blocks(w23_frag, PDSC_MLP_W3H, PDSC_MLP_W3L, 2 * rp, 4, h2h, h2l, a3, false);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int rb = 2 * rp + i;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                uint4 uh, ul;
-                unsigned *ph = &uh.x, *pl = &ul.x;
-#pragma unroll
-                for (int g2 = 0; g2 < 2; ++g2) {
-                    const int g = 2 * j + g2;
-                    const float4 bv = *reinterpret_cast<const float4 *>(b3 + rb * 32 + 8 * g + 4 * hi);
-                    const float v0 = a3[i][4 * g + 0] + bv.x + rv[i][g].x, v1 = a3[i][4 * g + 1] + bv.y + rv[i][g].y;
-                    const float v2 = a3[i][4 * g + 2] + bv.z + rv[i][g].z, v3 = a3[i][4 * g + 3] + bv.w + rv[i][g].w;
-                    split_pair(v0, v1, ph[2 * g2], pl[2 * g2]);
-                    split_pair(v2, v3, ph[2 * g2 + 1], pl[2 * g2 + 1]);
-                }
-                xh[rb * 2 + j] = __builtin_bit_cast(xhalf8, uh);       // (the message fragments are dead: their registers take the features)
-                xl[rb * 2 + j] = __builtin_bit_cast(xhalf8, ul);
-            }
-        }
-    }
-    // ---- PointCN + q|k|v of layer l + 1.  The fc_message image is dead once every wave is here: q lands on top of it.
-    __syncthreads();
-    dma_chunk(1, AREA1);
-    auto frag = [&](int base, int rb, int s_) {
-        const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(fz_lds + base + o * 256 + (((2 * s_ + hi) ^ (o & 15)) << 4));
-    };
-    xhalf8 fh[8], fl[8];
-#pragma unroll
-    for (int rp = 0; rp < 2; ++rp) {
-        f32x16 acc[2];
-        two_blocks(frag, AREA0, AREA0 + HALF, 2 * rp, 8, xh, xl, acc, false);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int rb = 2 * rp + i;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                uint4 uh, ul;
-                unsigned *ph = &uh.x, *pl = &ul.x;
-#pragma unroll
-                for (int g2 = 0; g2 < 2; ++g2) {
-                    const int c = rb * 32 + 8 * (2 * j + g2) + 4 * hi, r0 = 8 * j + 4 * g2;
-                    const float4 bv = *reinterpret_cast<const float4 *>(bp + c);
-                    float4 v;
-                    v.x = fmaxf(acc[i][r0] + bv.x, 0.0f); v.y = fmaxf(acc[i][r0 + 1] + bv.y, 0.0f);
-                    v.z = fmaxf(acc[i][r0 + 2] + bv.z, 0.0f); v.w = fmaxf(acc[i][r0 + 3] + bv.w, 0.0f);
-                    *reinterpret_cast<float4 *>(feat1 + prow * C + c) = v;
-                    split_pair(v.x, v.y, ph[2 * g2], pl[2 * g2]);
-                    split_pair(v.z, v.w, ph[2 * g2 + 1], pl[2 * g2 + 1]);
-                }
-                fh[rb * 2 + j] = __builtin_bit_cast(xhalf8, uh);
-                fl[rb * 2 + j] = __builtin_bit_cast(xhalf8, ul);
-            }
-        }
-    }
-    // q from area 1 while k lands in area 0, k from area 0 while v lands in area 1, v from area 1
-#pragma unroll
-    for (int part = 0; part < 3; ++part) {
-        const int area_off = ((part + 1) & 1) ? AREA1 : AREA0, other_off = ((part + 1) & 1) ? AREA0 : AREA1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this part's chunk has landed (the feat1 stores drain with it)
-        __syncthreads();                                                // every wave is done with the other area; this part's chunk is visible
-        if (part < 2) dma_chunk(part + 2, other_off);
-        const int p_pair = q0 + wave * 32;
-        char *tile = kv_img ? kv_img + ((size_t)b * (n_cap / 64) + (p_pair >> 6)) * PDSC_KV_TILE_BYTES : nullptr;
-        const bool as_v = kv_img && part == 2;
-#pragma unroll
-        for (int rp = 0; rp < 2; ++rp) {
-            f32x16 acc[2];
-            two_blocks(frag, area_off, area_off + HALF, 2 * rp, 8, fh, fl, acc, as_v);
-            if (as_v) {
-                const int kb = (p_pair >> 5) & 1;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int ch = (2 * rp + i) * 32 + l31;
-                    const float bv = bq[2 * C + ch];
-#pragma unroll
-                    for (int t2 = 0; t2 < 2; ++t2) {
-                        uint4 uh, ul;
-                        split_pair(acc[i][8 * t2 + 0] + bv, acc[i][8 * t2 + 1] + bv, uh.x, ul.x);
-                        split_pair(acc[i][8 * t2 + 2] + bv, acc[i][8 * t2 + 3] + bv, uh.y, ul.y);
-                        split_pair(acc[i][8 * t2 + 4] + bv, acc[i][8 * t2 + 5] + bv, uh.z, ul.z);
-                        split_pair(acc[i][8 * t2 + 6] + bv, acc[i][8 * t2 + 7] + bv, uh.w, ul.w);
-                        const int oct = (kb * 2 + t2) * 2 + hi;
-                        *reinterpret_cast<uint4 *>(tile + PDSC_KV_VH + ((size_t)oct * C + ch) * 16) = uh;
-                        *reinterpret_cast<uint4 *>(tile + PDSC_KV_VL + ((size_t)oct * C + ch) * 16) = ul;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int cc = (2 * rp + i) * 32 + 8 * g + 4 * hi, c = part * C + cc;
-                        const float4 bv = *reinterpret_cast<const float4 *>(bq + c);
-                        float4 o;
-                        o.x = acc[i][4 * g + 0] + bv.x; o.y = acc[i][4 * g + 1] + bv.y;
-                        o.z = acc[i][4 * g + 2] + bv.z; o.w = acc[i][4 * g + 3] + bv.w;
-                        if (kv_img && part == 1) {
-                            uint2 uh, ul;
-                            split_pair(o.x, o.y, uh.x, ul.x);
-                            split_pair(o.z, o.w, uh.y, ul.y);
-                            const size_t off = (size_t)pdsc_k_img_elem((p_pair & 63) + l31, cc >> 3) * 2 + (cc & 7) * 2;
-                            *reinterpret_cast<uint2 *>(tile + off) = uh;
-                            *reinterpret_cast<uint2 *>(tile + PDSC_KV_KL + off) = ul;
                         } else {
                             *reinterpret_cast<float4 *>(qkv + prow * 3 * C + c) = o;
                         }
@@ -1735,9 +1053,8 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     // development aid (ORYON_PDSC_CLOCKS, dev build only): phase timestamps (100 MHz wall clock) of waves 0 (key half 0) and 4 (key half 1) of workgroup 0
 #define CLK(i) do { if constexpr (DBG) { if (blockIdx.x == 0 && blockIdx.z == 0 && (threadIdx.x & 255) == 0) dbg_clk[(threadIdx.x >> 8) * 16 + (i)] = wall_clock64(); } } while (0)
     CLK(0);
-    constexpr int AREA0 = PDSC_MLP_IMG_BYTES, AREA1 = 0;               // byte offsets of the two 64 KB weight areas (see pdsc_mlp3_pcn_qkv_x3_kernel)
-    const char *kv_img_rd = kv_img_in;
-#define kv_img kv_img_rd
+    // byte offsets of the two 64 KB weight areas: area 0 behind the fc_message image, area 1 on top of it once it is dead
+    constexpr int AREA0 = PDSC_MLP_IMG_BYTES, AREA1 = 0;
     static_assert(C == 128, "tile image geometry");
     constexpr int CB = C / 32;
     constexpr int NS = C / 16;
@@ -1747,13 +1064,9 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     // vector-memory counter its stores sit on nor a cold scalar cache in front of every epilogue (round 6, see bias4)
     float *lds_bias = reinterpret_cast<float *>(att_lds + PDSC_AC_BIAS_OFF);
     constexpr int SEG_B1 = 0, SEG_B2 = 64, SEG_B3 = 128, SEG_BP = 256, SEG_BQ = 384;
-    auto bias4l = [&](int seg_off, int hi_) {                       // seg_off: wave-uniform multiple of 8; lane half hi_ -> + 4 channels
-        const int q = (seg_off >> 2) + hi_;
-        return make_float4(lds_bias[q], lds_bias[192 + q], lds_bias[384 + q], lds_bias[576 + q]);
-    };
-    const int lin = blockIdx.x + gridDim.x * blockIdx.z;
-    const int b = (lin / 8 / (int)gridDim.x) * 8 + (lin & 7);
-    const int qblk = (lin / 8) % (int)gridDim.x;
+    const BiasLds bias4l{lds_bias};
+    int b, qblk;
+    att8_block_map(b, qblk);
     if (b >= n_pairs) return;
     const int n = n_rows[b];
     const int q0 = qblk * ATT_Q;
@@ -1767,29 +1080,14 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     }
     const int qrow = q0 + wave * 32 + l31;
     const float *base = QKV + (size_t)b * n_cap * 3 * C;
-    const char *img = kv_img + (size_t)b * (n_cap / ATT_KT) * PDSC_KV_TILE_BYTES;
+    const char *img = kv_img_in + (size_t)b * (n_cap / ATT_KT) * PDSC_KV_TILE_BYTES;
     const float4 *sc_q = reinterpret_cast<const float4 *>(sc) + (((size_t)b * (n_cap / 32) + (q0 / 32 + wave)) * (n_cap / ATT_KT)) * 8 * 64 + lane;
     const bool q_live = q0 + wave * 32 < n;
     float4 scv[4];
-    auto dma_tile = [&](int j0, int buf) {
-        const char *src = img + (size_t)(j0 / ATT_KT) * PDSC_KV_TILE_BYTES;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const int piece = wave_u * 9 + j;
-            if (piece < PDSC_KV_TILE_BYTES / 1024)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + piece * 1024 + lane * 16),
-                                                 (__attribute__((address_space(3))) void *)(att_lds + buf * PDSC_KV_TILE_BYTES + piece * 1024), 16, 0, 0);
-        }
-    };
-    auto fetch_sc = [&](int j0) {
-        const float4 *sp = sc_q + (size_t)(j0 / ATT_KT) * 8 * 64 + (size_t)kb * 4 * 64;
-#pragma unroll
-        for (int v4 = 0; v4 < 4; ++v4) scv[v4] = q_live ? sp[(size_t)v4 * 64] : make_float4(-1.f, -1.f, -1.f, -1.f);
-    };
     // round 6: the first tile's DMA and SC rows are requested BEFORE the query rows are split (they used to be issued behind the ~300
     // instructions of the split, their latency exposed in front of the first tile)
-    dma_tile(0, 0);
-    fetch_sc(0);
+    dma_kv_tile(img, 0, att_lds, wave_u, lane);
+    fetch_sc(sc_q, q_live, kb, 0, scv);
     xhalf8 qh[NS], ql[NS];
     {
         // q in the G4 row-fragment layout (pdsc.h): the 8 channels of k-step s_ for lane half hi are the quads 4 s_ + 2 hi, + 1
@@ -1824,25 +1122,18 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     for (int j0 = 0; j0 < n; j0 += ATT_KT, buf ^= 1) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (j0 + ATT_KT < n) dma_tile(j0 + ATT_KT, buf ^ 1);
-        const _Float16 *Kh = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES);
-        const _Float16 *Kl = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES + PDSC_KV_KL);
-        const _Float16 *Vh = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES + PDSC_KV_VH);
-        const _Float16 *Vl = reinterpret_cast<const _Float16 *>(att_lds + buf * PDSC_KV_TILE_BYTES + PDSC_KV_VL);
+        if (j0 + ATT_KT < n) dma_kv_tile(img, j0 + ATT_KT, att_lds + (buf ^ 1) * PDSC_KV_TILE_BYTES, wave_u, lane);
+        const char *tile = att_lds + buf * PDSC_KV_TILE_BYTES;
         // S^T (this wave's 32 keys x 32 queries)
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.0f;
         xhalf8 kf[2][2];                              // [buffer][hi | lo]
-        auto read_k = [&](int s_, int bf) {
-            kf[bf][0] = *reinterpret_cast<const xhalf8 *>(Kh + pdsc_k_img_elem(kb * 32 + l31, 2 * s_ + hi));
-            kf[bf][1] = *reinterpret_cast<const xhalf8 *>(Kl + pdsc_k_img_elem(kb * 32 + l31, 2 * s_ + hi));
-        };
-        read_k(0, 0);
+        read_k(tile, kb * 32 + l31, 0, hi, kf[0]);
 #pragma unroll
         for (int s_ = 0; s_ < NS; ++s_) {
             const int bf = s_ & 1;
-            if (s_ + 1 < NS) read_k(s_ + 1, bf ^ 1);
+            if (s_ + 1 < NS) read_k(tile, kb * 32 + l31, s_ + 1, hi, kf[bf ^ 1]);
             s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[bf][0], qh[s_], s, 0, 0, 0);
             s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[bf][0], ql[s_], s, 0, 0, 0);
             s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[bf][1], qh[s_], s, 0, 0, 0);
@@ -1860,7 +1151,7 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
                 s[r] = v;
                 m_tile = fmaxf(m_tile, v);
             }
-            if (j0 + ATT_KT < n) fetch_sc(j0 + ATT_KT);
+            if (j0 + ATT_KT < n) fetch_sc(sc_q, q_live, kb, j0 + ATT_KT, scv);
             m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32));
             const float m_new = fmaxf(m_run, m_tile);
             const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
@@ -1895,7 +1186,7 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
             s[r] = v;
             m_tile = fmaxf(m_tile, v);
         }
-        if (j0 + ATT_KT < n) fetch_sc(j0 + ATT_KT);
+        if (j0 + ATT_KT < n) fetch_sc(sc_q, q_live, kb, j0 + ATT_KT, scv);
         m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32));
         const float m_new = fmaxf(m_run, m_tile);
         // a block whose keys are all masked so far keeps m = -inf: exp(-inf - (-inf)) must not produce NaN
@@ -1928,26 +1219,18 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
             const int oct = (kb * 2 + t2) * 2 + hi;
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
-                const xhalf8 vh = *reinterpret_cast<const xhalf8 *>(Vh + ((size_t)oct * C + cb * 32 + l31) * 8);
-                const xhalf8 vl = *reinterpret_cast<const xhalf8 *>(Vl + ((size_t)oct * C + cb * 32 + l31) * 8);
+                const xhalf8 vh = read_v(tile + PDSC_KV_VH, oct, cb * 32 + l31), vl = read_v(tile + PDSC_KV_VL, oct, cb * 32 + l31);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[t2], acc_o[cb], 0, 0, 0);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[t2], acc_o[cb], 0, 0, 0);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[t2], acc_o[cb], 0, 0, 0);
             }
         }
     }
-#undef kv_img
     // ---- the tiles are done: the fc_message image starts landing at [0, 80 KB) while the two key halves merge through [80 KB, 146 KB)
     CLK(2);
     float l_all = l_run + __shfl_xor(l_run, 32);
     __syncthreads();
-    static_assert((PDSC_MLP_IMG_BYTES / 1024) % WAVES == 0, "pieces per wave");
-#pragma unroll
-    for (int j = 0; j < PDSC_MLP_IMG_BYTES / 1024 / WAVES; ++j) {
-        const int piece = wave_u * (PDSC_MLP_IMG_BYTES / 1024 / WAVES) + j;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(mlp_img + piece * 1024 + lane * 16),
-                                         (__attribute__((address_space(3))) void *)(att_lds + piece * 1024), 16, 0, 0);
-    }
+    dma_mlp_image<WAVES>(mlp_img, att_lds, wave_u, lane);
     float *xo = reinterpret_cast<float *>(att_lds + PDSC_MLP_IMG_BYTES) + (size_t)wave * (64 * (CB * 16 + 2));
     if (kb == 1) {
 #pragma unroll
@@ -1989,97 +1272,18 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     }
     CLK(3);
     __syncthreads();                                                    // the merge area is free: PointCN' lands there
-    auto dma_chunk = [&](int chunk, int area_off) {                   // 64 pieces of 1 KB, 64 / WAVES per wave
-#pragma unroll
-        for (int j = 0; j < 64 / WAVES; ++j) {
-            const int piece = wave_u * (64 / WAVES) + j;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(pq_img + (size_t)chunk * PDSC_PQ_CHUNK_BYTES + piece * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void *)(att_lds + area_off + piece * 1024), 16, 0, 0);
-        }
-    };
     // The q | k | v chunks are requested by the four key-half-1 waves alone (16 pieces each): they have no stores, so their
     // s_waitcnt vmcnt(0) waits for the LDS-DMA only, and the four live waves - whose feat1 / q / k / v stores sit on the same in-order
     // counter - never wait on it between the parts: their stores drain behind the next part's MFMAs (round 6; with every wave requesting
     // an eighth and waiting vmcnt(0), each part paid the acknowledgement of its 16 KB of stores)
     auto dma_chunk_idle = [&](int chunk, int area_off) {
-        if (kb == 1) {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int piece = (wave_u - 4) * 16 + j;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(pq_img + (size_t)chunk * PDSC_PQ_CHUNK_BYTES + piece * 1024 + lane * 16),
-                                                 (__attribute__((address_space(3))) void *)(att_lds + area_off + piece * 1024), 16, 0, 0);
-            }
-        }
+        if (kb == 1) dma_pq_chunk<4>(pq_img, chunk, att_lds + area_off, wave_u - 4, lane);
     };
-    if constexpr (HAS_NEXT) dma_chunk(4, AREA0);                       // PointCN with the permuted K axis
+    if constexpr (HAS_NEXT) dma_pq_chunk<WAVES>(pq_img, 4, att_lds + AREA0, wave_u, lane);     // PointCN with the permuted K axis
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    auto w1_frag = [&](int base, int rb, int s_) {
-        const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(att_lds + base + o * 256 + (((2 * s_ + hi) ^ (o & 15)) << 4));
-    };
-    auto w23_frag = [&](int base, int rb, int s_) {
-        const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(att_lds + base + o * 128 + (((2 * s_ + hi) ^ ((o >> 1) & 7)) << 4));
-    };
-    auto next_operand = [&](const f32x16 (&acc)[2], int bias_seg, xhalf8 (&oh)[4], xhalf8 (&ol)[4]) {
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                uint4 uh, ul;
-                unsigned *ph = &uh.x, *pl = &ul.x;
-#pragma unroll
-                for (int g2 = 0; g2 < 2; ++g2) {
-                    const float4 bv = bias4l(bias_seg + rb * 32 + 8 * (2 * j + g2), hi);
-                    const int r0 = 8 * j + 4 * g2;
-                    const float v0 = fmaxf(acc[rb][r0] + bv.x, 0.0f), v1 = fmaxf(acc[rb][r0 + 1] + bv.y, 0.0f);
-                    const float v2 = fmaxf(acc[rb][r0 + 2] + bv.z, 0.0f), v3 = fmaxf(acc[rb][r0 + 3] + bv.w, 0.0f);
-                    split_pair(v0, v1, ph[2 * g2], pl[2 * g2]);
-                    split_pair(v2, v3, ph[2 * g2 + 1], pl[2 * g2 + 1]);
-                }
-                oh[rb * 2 + j] = __builtin_bit_cast(xhalf8, uh);
-                ol[rb * 2 + j] = __builtin_bit_cast(xhalf8, ul);
-            }
-    };
-    // two 32-row output blocks over NS k-steps (see pdsc_mlp3_x3_kernel); swap: the activations are the A operand (lane = channel)
-    auto two_blocks = [&](auto &&frag, int base_h, int base_l, int rb0, int NS, const xhalf8 *bh, const xhalf8 *bl, f32x16 (&acc)[2], bool swap) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
-        xhalf8 w[2][2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) { w[0][i][0] = frag(base_h, rb0 + i, 0); w[0][i][1] = frag(base_l, rb0 + i, 0); }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
-            if (s_ < NS) {
-                const int cur = s_ & 1;
-                if (s_ + 1 < NS) {
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) { w[cur ^ 1][i][0] = frag(base_h, rb0 + i, s_ + 1); w[cur ^ 1][i][1] = frag(base_l, rb0 + i, s_ + 1); }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (!swap) {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][0], bh[s_], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][0], bh[s_], acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][0], bl[s_], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][0], bl[s_], acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][0][1], bh[s_], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[cur][1][1], bh[s_], acc[1], 0, 0, 0);
-                } else {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][0][0], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][1][0], acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s_], w[cur][0][0], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s_], w[cur][1][0], acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][0][1], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s_], w[cur][1][1], acc[1], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
+    const Frag256 w1_frag{att_lds, l31, hi}, frag = w1_frag;          // (W1 and the PointCN / q / k / v chunks share the row format)
+    const Frag128 w23_frag{att_lds, l31, hi};
     CLK(4);
     // v's bias is per lane (lane = channel in the swapped product): fetched here, long before the first store of the chain - a vector load
     // issued between stores waits for every earlier store's acknowledgement (s_waitcnt vmcnt is one in-order counter)
@@ -2101,20 +1305,20 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
                 rv[rp][i][g] = reinterpret_cast<const float4 *>(resid + (size_t)b * n_cap * C)[pdsc_g4_index(n_cap, qrow, (2 * rp + i) * 8 + 2 * g + hi)];
     // ---- fc_message of layer l
     f32x16 a1[2];
-    two_blocks(w1_frag, PDSC_MLP_W1H, PDSC_MLP_W1L, 0, 8, xh, xl, a1, false);
+    two_blocks<8, false>(w1_frag, PDSC_MLP_W1H, PDSC_MLP_W1L, 0, xh, xl, a1);
     xhalf8 h1h[4], h1l[4];
-    next_operand(a1, SEG_B1, h1h, h1l);
+    next_operand(a1, bias4l, SEG_B1, hi, h1h, h1l);
     CLK(5);
     f32x16 a2[2];
-    two_blocks(w23_frag, PDSC_MLP_W2H, PDSC_MLP_W2L, 0, 4, h1h, h1l, a2, false);
+    two_blocks<4, false>(w23_frag, PDSC_MLP_W2H, PDSC_MLP_W2L, 0, h1h, h1l, a2);
     xhalf8 h2h[4], h2l[4];
-    next_operand(a2, SEG_B2, h2h, h2l);
+    next_operand(a2, bias4l, SEG_B2, hi, h2h, h2l);
     CLK(6);
     // layer 3 + bias + residual = the layer's output features, kept as the 8 B fragments (permuted K order) of the next layer's PointCN
 #pragma unroll
     for (int rp = 0; rp < 2; ++rp) {
         f32x16 a3[2];
-        two_blocks(w23_frag, PDSC_MLP_W3H, PDSC_MLP_W3L, 2 * rp, 4, h2h, h2l, a3, false);
+        two_blocks<4, false>(w23_frag, PDSC_MLP_W3H, PDSC_MLP_W3L, 2 * rp, h2h, h2l, a3);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int rb = 2 * rp + i;
@@ -2157,16 +1361,12 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     // ---- PointCN + q|k|v of layer l + 1.  The fc_message image is dead once every wave is here: q lands on top of it.
     __syncthreads();
     dma_chunk_idle(1, AREA1);
-    auto frag = [&](int base, int rb, int s_) {
-        const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(att_lds + base + o * 256 + (((2 * s_ + hi) ^ (o & 15)) << 4));
-    };
     xhalf8 fh[8], fl[8];
     if (live) {
 #pragma unroll
     for (int rp = 0; rp < 2; ++rp) {
         f32x16 acc[2];
-        two_blocks(frag, AREA0, AREA0 + HALF, 2 * rp, 8, xh, xl, acc, false);
+        two_blocks<8, false>(frag, AREA0, AREA0 + HALF, 2 * rp, xh, xl, acc);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int rb = 2 * rp + i;
@@ -2240,26 +1440,13 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
         const int rp = kb;
         {
             f32x16 acc[2];
-            two_blocks(frag, area_off, area_off + HALF, 2 * rp, 8, fh, fl, acc, as_v);
             if (as_v) {
+                two_blocks<8, true>(frag, area_off, area_off + HALF, 2 * rp, fh, fl, acc);
                 const int kb = (p_pair >> 5) & 1;
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int ch = (2 * rp + i) * 32 + l31;
-                    const float bv = bias_v[i];
-#pragma unroll
-                    for (int t2 = 0; t2 < 2; ++t2) {
-                        uint4 uh, ul;
-                        split_pair(acc[i][8 * t2 + 0] + bv, acc[i][8 * t2 + 1] + bv, uh.x, ul.x);
-                        split_pair(acc[i][8 * t2 + 2] + bv, acc[i][8 * t2 + 3] + bv, uh.y, ul.y);
-                        split_pair(acc[i][8 * t2 + 4] + bv, acc[i][8 * t2 + 5] + bv, uh.z, ul.z);
-                        split_pair(acc[i][8 * t2 + 6] + bv, acc[i][8 * t2 + 7] + bv, uh.w, ul.w);
-                        const int oct = (kb * 2 + t2) * 2 + hi;
-                        *reinterpret_cast<uint4 *>(tile + PDSC_KV_VH + ((size_t)oct * C + ch) * 16) = uh;
-                        *reinterpret_cast<uint4 *>(tile + PDSC_KV_VL + ((size_t)oct * C + ch) * 16) = ul;
-                    }
-                }
+                for (int i = 0; i < 2; ++i) store_v(tile, acc[i], bias_v[i], kb, (2 * rp + i) * 32 + l31, hi);
             } else {
+                two_blocks<8, false>(frag, area_off, area_off + HALF, 2 * rp, fh, fl, acc);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -2270,12 +1457,7 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
                         o.x = acc[i][4 * g + 0] + bv.x; o.y = acc[i][4 * g + 1] + bv.y;
                         o.z = acc[i][4 * g + 2] + bv.z; o.w = acc[i][4 * g + 3] + bv.w;
                         if (kv_img && part == 1) {
-                            uint2 uh, ul;
-                            split_pair(o.x, o.y, uh.x, ul.x);
-                            split_pair(o.z, o.w, uh.y, ul.y);
-                            const size_t off = (size_t)pdsc_k_img_elem((p_pair & 63) + l31, cc >> 3) * 2 + (cc & 7) * 2;
-                            *reinterpret_cast<uint2 *>(tile + off) = uh;
-                            *reinterpret_cast<uint2 *>(tile + PDSC_KV_KL + off) = ul;
+                            store_k(tile, o, (p_pair & 63) + l31, cc);
                         } else if (part == 0) {
                             reinterpret_cast<float4 *>(qkv + (size_t)b * n_cap * 3 * C)[pdsc_g4_index(n_cap, qrow, cc >> 2)] = o;
                         } else {
@@ -2449,33 +1631,63 @@ __global__ __launch_bounds__(256) void pdsc_head_x3_kernel(const float *__restri
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+static bool pdsc_x3()       // the fp16x3 kernels, unless the development build is asked for the pure-fp32 ones
+{
+    static const bool x3 = !dev_env_set("ORYON_PDSC_FP32_MFMA");
+    return x3;
+}
+
+// Launch of a kernel with dynamic LDS beyond the default limit
+template <class... P, class... A>
+static void launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, int lds, hipStream_t st, A... args)
+{
+    allow_dynamic_lds(reinterpret_cast<const void *>(kernel), lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+}
+
 static int launch_linear(bool relu, bool resid, const float *X, int ldx, size_t xb, const float *W, const float *bias,
                          const float *R, int ldr, size_t rb, float *Y, int ldy, size_t yb, int K, int N, int B, int n_cap,
                          const int32_t *n_rows, hipStream_t st)
 {
-    dim3 grid(n_cap / LIN_ROWS, ceil_div(N, LIN_COLS), B), block(256);
-    static const bool x3 = !dev_env_set("ORYON_PDSC_FP32_MFMA");
-    if (x3 && K % LIN_BK == 0 && ldx % 2 == 0) {
-        if (relu && !resid) hipLaunchKernelGGL((pdsc_linear_x3_kernel<true, false>), grid, block, 0, st, X, ldx, xb, W, bias, R, ldr, rb, Y, ldy, yb, K, N, n_rows);
-        else if (!relu && resid) hipLaunchKernelGGL((pdsc_linear_x3_kernel<false, true>), grid, block, 0, st, X, ldx, xb, W, bias, R, ldr, rb, Y, ldy, yb, K, N, n_rows);
-        else if (!relu && !resid) hipLaunchKernelGGL((pdsc_linear_x3_kernel<false, false>), grid, block, 0, st, X, ldx, xb, W, bias, R, ldr, rb, Y, ldy, yb, K, N, n_rows);
-        else hipLaunchKernelGGL((pdsc_linear_x3_kernel<true, true>), grid, block, 0, st, X, ldx, xb, W, bias, R, ldr, rb, Y, ldy, yb, K, N, n_rows);
-        return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
-    }
-    if (relu && !resid)
-        hipLaunchKernelGGL((pdsc_linear_kernel<true, false>), grid, block, 0, st, X, ldx, xb, W, bias, R, ldr, rb, Y, ldy, yb, K, N, n_rows);
-    else if (!relu && resid)
-        hipLaunchKernelGGL((pdsc_linear_kernel<false, true>), grid, block, 0, st, X, ldx, xb, W, bias, R, ldr, rb, Y, ldy, yb, K, N, n_rows);
-    else if (!relu && !resid)
-        hipLaunchKernelGGL((pdsc_linear_kernel<false, false>), grid, block, 0, st, X, ldx, xb, W, bias, R, ldr, rb, Y, ldy, yb, K, N, n_rows);
-    else
-        hipLaunchKernelGGL((pdsc_linear_kernel<true, true>), grid, block, 0, st, X, ldx, xb, W, bias, R, ldr, rb, Y, ldy, yb, K, N, n_rows);
+    using Kernel = decltype(&pdsc_linear_kernel<false, false>);
+    static const Kernel table[2][2][2] = {        // [fp16x3][relu][resid]
+        {{pdsc_linear_kernel<false, false>, pdsc_linear_kernel<false, true>}, {pdsc_linear_kernel<true, false>, pdsc_linear_kernel<true, true>}},
+        {{pdsc_linear_x3_kernel<false, false>, pdsc_linear_x3_kernel<false, true>}, {pdsc_linear_x3_kernel<true, false>, pdsc_linear_x3_kernel<true, true>}}};
+    const bool x3 = pdsc_x3() && K % LIN_BK == 0 && ldx % 2 == 0;
+    hipLaunchKernelGGL(table[x3][relu][resid], dim3(n_cap / LIN_ROWS, ceil_div(N, LIN_COLS), B), dim3(256), 0, st, X, ldx, xb, W, bias, R, ldr, rb,
+                       Y, ldy, yb, K, N, n_rows);
     return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
 }
 
 void pdsc_launch_normalise(const float *feat, int C, int n_cap, int B, const int32_t *n_rows, float *out, hipStream_t st)
 {
     hipLaunchKernelGGL(pdsc_normalise_kernel, dim3(n_cap / 4, B), dim3(256), 0, st, feat, C, n_cap, n_rows, out);
+}
+
+// The route of the encoder's layers, decided once per call:
+//   chain  (C = 128, n_cap % 256 == 0, no key split): pdsc_pcn_qkv_x3_kernel<8> (G4 layout) for layer 0, then ONE
+//          pdsc_att_chain_x3_kernel launch per layer (attention + fc_message + the next layer's PointCN + q|k|v)
+//   fused  (any other C = 128 case): pdsc_pcn_qkv_x3_kernel, attention, pdsc_mlp3_x3_kernel per layer
+//   plain  (C != 128, or the pure-fp32 kernels): one pdsc_linear kernel per 1x1 conv + the fp32-fed attention
+enum class PdscRoute { plain, fused, chain };
+struct PdscPlan {
+    PdscRoute route;
+    bool x3;        // plain: fp16x3 linears and (C = 128) attention; the other routes are fp16x3 by construction
+    // 8-wave workgroups (256 points) of the per-point kernels when n_cap allows: the same 128 KB of weights feed twice the points and the
+    // launch occupies half the CUs with two waves per SIMD - latency-bound kernels lose nothing, and K0 / the other registration stream
+    // find free CUs beside them
+    int waves;
+    bool img;       // fused: no key split - K / V leave PointCN + q|k|v as tile images for pdsc_attention_x3_img8_kernel
+};
+static PdscPlan plan_encoder(const PdscModel &M, const PdscWorkspace &ws, int n_cap)
+{
+    static const int forced = dev_env_int("ORYON_PDSC_ROUTE", 0);         // dev: 1 = plain, 2 = at most fused
+    PdscPlan p = {PdscRoute::plain, pdsc_x3(), n_cap % 256 == 0 ? 8 : 4, ws.att_splits == 1 && ws.kv_img != nullptr};
+    bool images = true;                                                   // (oryon_pointdsc_finalize makes them for every layer at C = 128)
+    for (const PdscLayer &L : M.layers) images = images && L.mlp_img && L.mlp_img_p && L.pq_img;
+    if (M.cfg.num_channels != 128 || !p.x3 || !images || forced == 1) return p;
+    p.route = (p.waves == 8 && p.img && ws.kv_img2 && forced != 2) ? PdscRoute::chain : PdscRoute::fused;
+    return p;
 }
 
 // Runs the whole encoder: features [B,n_cap,C] (un-normalised) into ws.feat, confidence into ws.conf.
@@ -2493,145 +1705,91 @@ int pdsc_run_encoder(const PdscModel &M, const PdscWorkspace &ws, const float *s
     const float inv_sqrt_c = 1.0f / sqrtf((float)C);
     // spatial-consistency tiles, shared by all layers
     hipLaunchKernelGGL(pdsc_sc_kernel, dim3(n_cap / 128, n_cap / ATT_KT, B), dim3(256), 0, st, src, tgt, n_rows, n_cap, inv_sigma2, ws.sc);
+
+    const PdscPlan plan = plan_encoder(M, ws, n_cap);
+    const dim3 att8_grid(n_cap / ATT_Q, 1, (B + 7) / 8 * 8);               // att8_block_map
+    // PointCN (conv + BN + ReLU, BN folded) and the q | k | v projections in one launch
+    auto pcn_qkv = [&](const PdscLayer &L, int waves, char *kv_img, int g4) {
+        launch_lds(waves == 8 ? pdsc_pcn_qkv_x3_kernel<8> : pdsc_pcn_qkv_x3_kernel<4>, dim3(n_cap / (32 * waves), B), dim3(64 * waves),
+                   2 * PDSC_PQ_CHUNK_BYTES, st, ws.feat, L.pq_img, L.b_pcn, L.b_qkv, n_rows, n_cap, ws.feat1, ws.qkv, kv_img, g4);
+    };
+    // the attention fed by fp32 q | k | v rows, key-split over att_splits workgroups (+ the merge of their partials)
+    auto attention = [&]() {
+        const int KS = ws.att_splits;
+        const auto kernel = (C == 128 && plan.x3) ? pdsc_attention_x3_kernel<128> : C == 128 ? pdsc_attention_kernel<128>
+                            : C == 64             ? pdsc_attention_kernel<64> : pdsc_attention_kernel<32>;
+        hipLaunchKernelGGL(kernel, dim3(n_cap / ATT_Q, KS, B), dim3(256), 0, st, ws.qkv, ws.sc, n_rows, n_cap, inv_sqrt_c, ws.msg, KS, ws.att_o, ws.att_ml);
+        if (KS > 1)
+            hipLaunchKernelGGL(pdsc_attention_merge_kernel, dim3((n_cap * (C / 4) + 255) / 256, B), dim3(256), 0, st, ws.att_o, ws.att_ml,
+                               n_rows, n_cap, C, KS, B, ws.msg);
+    };
     for (int l = 0; l < M.cfg.num_layers; ++l) {
         const PdscLayer &L = M.layers[l];
-        static const bool x3 = !dev_env_set("ORYON_PDSC_FP32_MFMA");     // fp16x3 unless the pure-fp32 kernels are asked for
-        static const bool fused_pq = dev_env_int("ORYON_PDSC_FUSED_PQ", 1) != 0;       // dev: 0 = two launches
-        static const bool att_img = dev_env_int("ORYON_PDSC_ATT_IMG", 1) != 0;           // dev: 0 = fp32 K / V
-        bool use_img = false;
-        // round 4: fc_message of layer l - 1 and PointCN + q|k|v of layer l came as ONE launch at the end of the previous iteration
-        static const bool fuse_chain = dev_env_int("ORYON_PDSC_FUSED_CHAIN", 1) != 0;     // dev: 0 = separate launches
-        static const bool fuse_att = dev_env_int("ORYON_PDSC_FUSED_ATT", 1) != 0;           // dev: 0 = attention as its own launch
-        const bool chain_ok = C == 128 && x3 && fused_pq && fuse_chain && n_cap % 256 == 0 && ws.att_splits == 1 && ws.kv_img != nullptr && att_img &&
-                              (dev_env_int("ORYON_PDSC_FUSED_MLP", 1) != 0) &&
-                              (dev_env_int("ORYON_PDSC_WAVES", 8) == 8);
-        // K / V images alternate between two buffers when the attention is part of the one-launch-per-layer kernel (its workgroups write
-        // layer l + 1's tiles while others still read layer l's)
-        // (every layer or none: the kernel hands q and the PointCN output from layer to layer in its own G4 layout)
-        bool all_imgs = true;
-        for (const PdscLayer &Lx : M.layers) all_imgs = all_imgs && Lx.mlp_img_p && Lx.mlp_img && Lx.pq_img;
-        const bool att_chain = chain_ok && fuse_att && ws.kv_img2 != nullptr && all_imgs &&
-                               (dev_env_int("ORYON_PDSC_ATT8", 1) != 0);
-        char *kv_cur = (att_chain && (l & 1)) ? ws.kv_img2 : ws.kv_img, *kv_nxt = (att_chain && !(l & 1)) ? ws.kv_img2 : ws.kv_img;
-        if (l > 0 && chain_ok && L.pq_img && M.layers[l - 1].mlp_img) {
-            use_img = true;                                            // (launched at the end of the previous iteration)
-        } else
-        if (C == 128 && x3 && fused_pq && L.pq_img) {
-            // PointCN (conv + BN + ReLU, BN folded) and the q | k | v projections in one launch
-            // 8-wave workgroups (256 points): the same 128 KB of weights feed twice the points and the launch occupies half the CUs with
-            // two waves per SIMD - latency-bound kernels lose nothing, and K0 / the other registration stream find free CUs beside them
-            static const int pw = dev_env_int("ORYON_PDSC_WAVES", 8);
-            const bool w8 = pw == 8 && n_cap % 256 == 0;
-            if (w8) allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_pcn_qkv_x3_kernel<8>), 2 * PDSC_PQ_CHUNK_BYTES);
-            else allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_pcn_qkv_x3_kernel<4>), 2 * PDSC_PQ_CHUNK_BYTES);
-            use_img = ws.att_splits == 1 && ws.kv_img != nullptr && att_img;
-            if (w8)
-                hipLaunchKernelGGL(pdsc_pcn_qkv_x3_kernel<8>, dim3(n_cap / 256, B), dim3(512), 2 * PDSC_PQ_CHUNK_BYTES, st, ws.feat, L.pq_img, L.b_pcn,
-                                   L.b_qkv, n_rows, n_cap, ws.feat1, ws.qkv, use_img ? ws.kv_img : nullptr, (att_chain && use_img) ? 1 : 0);
+        switch (plan.route) {
+        case PdscRoute::chain: {
+            constexpr int AC_LDS = PDSC_AC_BIAS_OFF + PDSC_AC_BIAS_BYTES;        // tile buffers / weight areas / merge area, then the biases
+            static_assert(PDSC_AC_BIAS_OFF >= 2 * PDSC_KV_TILE_BYTES && AC_LDS <= 160 * 1024, "att_chain LDS budget");
+            // the K / V images alternate between two buffers: workgroups write layer l + 1's tiles while others still read layer l's
+            char *kv_cur = (l & 1) ? ws.kv_img2 : ws.kv_img, *kv_nxt = (l & 1) ? ws.kv_img : ws.kv_img2;
+            if (l == 0) pcn_qkv(L, 8, ws.kv_img, 1);
+            const bool has_next = l + 1 < M.cfg.num_layers;
+            const PdscLayer &N = M.layers[has_next ? l + 1 : l];
+#ifdef ORYON_DEV
+            static const int clocks = dev_env_int("ORYON_PDSC_CLOCKS", 0);      // > 0: print the phase clocks of layer `clocks` of every call
+            if (clocks > 0 && l == clocks && has_next) {
+                static long long *dclk = nullptr;
+                if (!dclk) { (void)hipMalloc(reinterpret_cast<void **>(&dclk), 32 * sizeof(long long)); }
+                (void)hipMemsetAsync(dclk, 0, 32 * sizeof(long long), st);
+                launch_lds(pdsc_att_chain_x3_kernel<128, true, true>, att8_grid, dim3(512), AC_LDS, st, ws.qkv, kv_cur, ws.sc, n_rows, n_cap, inv_sqrt_c, B,
+                           ws.feat1, L.mlp_img_p, L.b_m1, L.b_m2, L.b_m3, N.pq_img, N.b_pcn, N.b_qkv, ws.feat1, ws.qkv, kv_nxt, ws.feat, dclk);
+                long long hc[32];
+                (void)hipMemcpyAsync(hc, dclk, sizeof(hc), hipMemcpyDeviceToHost, st);
+                (void)hipStreamSynchronize(st);
+                fprintf(stderr, "att_chain clocks (us since entry) wave0:");
+                for (int i = 1; i <= 15; ++i) fprintf(stderr, " %.2f", hc[i] ? (hc[i] - hc[0]) * 0.01 : -1.0);
+                fprintf(stderr, "  wave4:");
+                for (int i = 1; i <= 12; ++i) fprintf(stderr, " %.2f", hc[16 + i] ? (hc[16 + i] - hc[16]) * 0.01 : -1.0);
+                fprintf(stderr, "\n");
+                continue;
+            }
+#endif
+            if (has_next)
+                launch_lds(pdsc_att_chain_x3_kernel<128, true>, att8_grid, dim3(512), AC_LDS, st, ws.qkv, kv_cur, ws.sc, n_rows, n_cap, inv_sqrt_c, B,
+                           ws.feat1, L.mlp_img_p, L.b_m1, L.b_m2, L.b_m3, N.pq_img, N.b_pcn, N.b_qkv, ws.feat1, ws.qkv, kv_nxt, ws.feat, nullptr);
             else
-                hipLaunchKernelGGL(pdsc_pcn_qkv_x3_kernel<4>, dim3(n_cap / 128, B), dim3(256), 2 * PDSC_PQ_CHUNK_BYTES, st, ws.feat, L.pq_img, L.b_pcn,
-                                   L.b_qkv, n_rows, n_cap, ws.feat1, ws.qkv, use_img ? ws.kv_img : nullptr, 0);
-            if (hipGetLastError() != hipSuccess) return ORYON_ERR_HIP;
-        } else {
+                launch_lds(pdsc_att_chain_x3_kernel<128, false>, att8_grid, dim3(512), AC_LDS, st, ws.qkv, kv_cur, ws.sc, n_rows, n_cap, inv_sqrt_c, B,
+                           ws.feat1, L.mlp_img_p, L.b_m1, L.b_m2, L.b_m3, nullptr, nullptr, nullptr, ws.feat1, ws.qkv, kv_nxt, ws.feat, nullptr);
+            break;
+        }
+        case PdscRoute::fused:
+            pcn_qkv(L, plan.waves, plan.img ? ws.kv_img : nullptr, 0);
+            if (plan.img)
+                launch_lds(pdsc_attention_x3_img8_kernel<128>, att8_grid, dim3(512), 2 * PDSC_KV_TILE_BYTES, st, ws.qkv, ws.kv_img, ws.sc, n_rows, n_cap,
+                           inv_sqrt_c, ws.msg, B);
+            else
+                attention();
+            // fc_message: C -> C/2 -> C/2 -> C, residual onto the PointCN output
+            launch_lds(plan.waves == 8 ? pdsc_mlp3_x3_kernel<8> : pdsc_mlp3_x3_kernel<4>, dim3(n_cap / (32 * plan.waves), B), dim3(64 * plan.waves),
+                       PDSC_MLP_IMG_BYTES, st, ws.msg, ws.feat1, L.mlp_img, L.b_m1, L.b_m2, L.b_m3, n_rows, n_cap, ws.feat);
+            break;
+        case PdscRoute::plain:
             // PointCN: conv + BN + ReLU (BN folded)
             rc = launch_linear(true, false, ws.feat, C, fb, L.w_pcn, L.b_pcn, nullptr, 0, 0, ws.feat1, C, fb, C, C, B, n_cap, n_rows, st);
             if (rc) return rc;
             // q | k | v projections as one GEMM with N = 3C
             rc = launch_linear(false, false, ws.feat1, C, fb, L.w_qkv, L.b_qkv, nullptr, 0, 0, ws.qkv, 3 * C, qb, C, 3 * C, B, n_cap, n_rows, st);
             if (rc) return rc;
+            attention();
+            // fc_message: C -> C/2 -> C/2 -> C, residual onto the PointCN output
+            rc = launch_linear(true, false, ws.msg, C, fb, L.w_m1, L.b_m1, nullptr, 0, 0, ws.h1, H, hb, C, H, B, n_cap, n_rows, st);
+            if (rc) return rc;
+            rc = launch_linear(true, false, ws.h1, H, hb, L.w_m2, L.b_m2, nullptr, 0, 0, ws.h2, H, hb, H, H, B, n_cap, n_rows, st);
+            if (rc) return rc;
+            rc = launch_linear(false, true, ws.h2, H, hb, L.w_m3, L.b_m3, ws.feat1, C, fb, ws.feat, C, fb, H, C, B, n_cap, n_rows, st);
+            if (rc) return rc;
+            break;
         }
-        if (att_chain && use_img) {
-            // attention + fc_message (+ PointCN + q|k|v of the next layer) in one launch
-            constexpr int AC_LDS = PDSC_AC_BIAS_OFF + PDSC_AC_BIAS_BYTES;        // tile buffers / weight areas / merge area, then the biases
-            static_assert(PDSC_AC_BIAS_OFF >= 2 * PDSC_KV_TILE_BYTES && AC_LDS <= 160 * 1024, "att_chain LDS budget");
-            const dim3 grid(n_cap / ATT_Q, 1, (B + 7) / 8 * 8);
-            if (l + 1 < M.cfg.num_layers && M.layers[l + 1].pq_img) {
-                const PdscLayer &N = M.layers[l + 1];
-#ifdef ORYON_DEV
-                static const int clocks = dev_env_int("ORYON_PDSC_CLOCKS", 0);      // > 0: print the phase clocks of layer `clocks` of every call
-                if (clocks > 0 && l == clocks) {
-                    static long long *dclk = nullptr;
-                    if (!dclk) { (void)hipMalloc(reinterpret_cast<void **>(&dclk), 32 * sizeof(long long)); }
-                    (void)hipMemsetAsync(dclk, 0, 32 * sizeof(long long), st);
-                    allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_att_chain_x3_kernel<128, true, true>), AC_LDS);
-                    hipLaunchKernelGGL((pdsc_att_chain_x3_kernel<128, true, true>), grid, dim3(512), AC_LDS, st, ws.qkv, kv_cur, ws.sc, n_rows, n_cap, inv_sqrt_c, B,
-                                       ws.feat1, L.mlp_img_p, L.b_m1, L.b_m2, L.b_m3, N.pq_img, N.b_pcn, N.b_qkv, ws.feat1, ws.qkv, kv_nxt, ws.feat, dclk);
-                    long long hc[32];
-                    (void)hipMemcpyAsync(hc, dclk, sizeof(hc), hipMemcpyDeviceToHost, st);
-                    (void)hipStreamSynchronize(st);
-                    fprintf(stderr, "att_chain clocks (us since entry) wave0:");
-                    for (int i = 1; i <= 15; ++i) fprintf(stderr, " %.2f", hc[i] ? (hc[i] - hc[0]) * 0.01 : -1.0);
-                    fprintf(stderr, "  wave4:");
-                    for (int i = 1; i <= 12; ++i) fprintf(stderr, " %.2f", hc[16 + i] ? (hc[16 + i] - hc[16]) * 0.01 : -1.0);
-                    fprintf(stderr, "\n");
-                    continue;
-                }
-#endif
-                allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_att_chain_x3_kernel<128, true>), AC_LDS);
-                hipLaunchKernelGGL((pdsc_att_chain_x3_kernel<128, true>), grid, dim3(512), AC_LDS, st, ws.qkv, kv_cur, ws.sc, n_rows, n_cap, inv_sqrt_c, B,
-                                   ws.feat1, L.mlp_img_p, L.b_m1, L.b_m2, L.b_m3, N.pq_img, N.b_pcn, N.b_qkv, ws.feat1, ws.qkv, kv_nxt, ws.feat);
-            } else {
-                allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_att_chain_x3_kernel<128, false>), AC_LDS);
-                hipLaunchKernelGGL((pdsc_att_chain_x3_kernel<128, false>), grid, dim3(512), AC_LDS, st, ws.qkv, kv_cur, ws.sc, n_rows, n_cap, inv_sqrt_c, B,
-                                   ws.feat1, L.mlp_img_p, L.b_m1, L.b_m2, L.b_m3, nullptr, nullptr, nullptr, ws.feat1, ws.qkv, kv_nxt, ws.feat);
-            }
-            if (hipGetLastError() != hipSuccess) return ORYON_ERR_HIP;
-            continue;
-        }
-        const int KS = ws.att_splits;
-        dim3 ag(n_cap / ATT_Q, KS, B);
-        static const bool att8 = dev_env_int("ORYON_PDSC_ATT8", 1) != 0;       // 0: the 4-wave attention kernel
-        if (C == 128 && x3 && use_img && att8) {
-            allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_attention_x3_img8_kernel<128>), 2 * PDSC_KV_TILE_BYTES);
-            hipLaunchKernelGGL((pdsc_attention_x3_img8_kernel<128>), dim3(n_cap / ATT_Q, 1, (B + 7) / 8 * 8), dim3(512), 2 * PDSC_KV_TILE_BYTES, st,
-                               ws.qkv, ws.kv_img, ws.sc, n_rows, n_cap, inv_sqrt_c, ws.msg, B);
-        } else if (C == 128 && x3 && use_img) {
-            allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_attention_x3_img_kernel<128>), 2 * PDSC_KV_TILE_BYTES);
-            hipLaunchKernelGGL((pdsc_attention_x3_img_kernel<128>), dim3(n_cap / ATT_Q, 1, (B + 7) / 8 * 8), dim3(256), 2 * PDSC_KV_TILE_BYTES, st,
-                               ws.qkv, ws.kv_img, ws.sc, n_rows, n_cap, inv_sqrt_c, ws.msg, B);
-        } else if (C == 128 && x3)
-            hipLaunchKernelGGL((pdsc_attention_x3_kernel<128>), ag, dim3(256), 0, st, ws.qkv, ws.sc, n_rows, n_cap, inv_sqrt_c, ws.msg, KS, ws.att_o, ws.att_ml);
-        else if (C == 128)
-            hipLaunchKernelGGL((pdsc_attention_kernel<128>), ag, dim3(256), 0, st, ws.qkv, ws.sc, n_rows, n_cap, inv_sqrt_c, ws.msg, KS, ws.att_o, ws.att_ml);
-        else if (C == 64)
-            hipLaunchKernelGGL((pdsc_attention_kernel<64>), ag, dim3(256), 0, st, ws.qkv, ws.sc, n_rows, n_cap, inv_sqrt_c, ws.msg, KS, ws.att_o, ws.att_ml);
-        else
-            hipLaunchKernelGGL((pdsc_attention_kernel<32>), ag, dim3(256), 0, st, ws.qkv, ws.sc, n_rows, n_cap, inv_sqrt_c, ws.msg, KS, ws.att_o, ws.att_ml);
-        if (KS > 1)
-            hipLaunchKernelGGL(pdsc_attention_merge_kernel, dim3((n_cap * (C / 4) + 255) / 256, B), dim3(256), 0, st, ws.att_o, ws.att_ml,
-                               n_rows, n_cap, C, KS, B, ws.msg);
         if (hipGetLastError() != hipSuccess) return ORYON_ERR_HIP;
-        // fc_message: C -> C/2 -> C/2 -> C, residual onto the PointCN output
-        static const bool fused_mlp = dev_env_int("ORYON_PDSC_FUSED_MLP", 1) != 0;   // dev: 0 = three launches
-        if (chain_ok && L.mlp_img && l + 1 < M.cfg.num_layers && M.layers[l + 1].pq_img) {
-            const PdscLayer &N = M.layers[l + 1];
-            constexpr int FZ_LDS = PDSC_MLP_IMG_BYTES + PDSC_PQ_CHUNK_BYTES;
-            allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_mlp3_pcn_qkv_x3_kernel<8>), FZ_LDS);
-            hipLaunchKernelGGL(pdsc_mlp3_pcn_qkv_x3_kernel<8>, dim3(n_cap / 256, B), dim3(512), FZ_LDS, st, ws.msg, ws.feat1, L.mlp_img, L.b_m1, L.b_m2,
-                               L.b_m3, N.pq_img, N.b_pcn, N.b_qkv, n_rows, n_cap, ws.feat1, ws.qkv, ws.kv_img);
-            if (hipGetLastError() != hipSuccess) return ORYON_ERR_HIP;
-            continue;
-        }
-        if (C == 128 && x3 && fused_mlp && L.mlp_img) {
-            static const int mw = dev_env_int("ORYON_PDSC_WAVES", 8);
-            if (mw == 8 && n_cap % 256 == 0) {
-                allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_mlp3_x3_kernel<8>), PDSC_MLP_IMG_BYTES);
-                hipLaunchKernelGGL(pdsc_mlp3_x3_kernel<8>, dim3(n_cap / 256, B), dim3(512), PDSC_MLP_IMG_BYTES, st, ws.msg, ws.feat1, L.mlp_img, L.b_m1,
-                                   L.b_m2, L.b_m3, n_rows, n_cap, ws.feat);
-            } else {
-                allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_mlp3_x3_kernel<4>), PDSC_MLP_IMG_BYTES);
-                hipLaunchKernelGGL(pdsc_mlp3_x3_kernel<4>, dim3(n_cap / 128, B), dim3(256), PDSC_MLP_IMG_BYTES, st, ws.msg, ws.feat1, L.mlp_img, L.b_m1,
-                                   L.b_m2, L.b_m3, n_rows, n_cap, ws.feat);
-            }
-            if (hipGetLastError() != hipSuccess) return ORYON_ERR_HIP;
-            continue;
-        }
-        rc = launch_linear(true, false, ws.msg, C, fb, L.w_m1, L.b_m1, nullptr, 0, 0, ws.h1, H, hb, C, H, B, n_cap, n_rows, st);
-        if (rc) return rc;
-        rc = launch_linear(true, false, ws.h1, H, hb, L.w_m2, L.b_m2, nullptr, 0, 0, ws.h2, H, hb, H, H, B, n_cap, n_rows, st);
-        if (rc) return rc;
-        rc = launch_linear(false, true, ws.h2, H, hb, L.w_m3, L.b_m3, ws.feat1, C, fb, ws.feat, C, fb, H, C, B, n_cap, n_rows, st);
-        if (rc) return rc;
     }
     static const bool fused_head = dev_env_int("ORYON_PDSC_FUSED_HEAD", 1) != 0;       // dev: 0 = three linears + the normalisation
     if (fused_head && C == 128 && n_cap % LIN_ROWS == 0) {
@@ -2646,7 +1804,7 @@ int pdsc_run_encoder(const PdscModel &M, const PdscWorkspace &ws, const float *s
     if (rc) return rc;
     rc = launch_linear(false, false, ws.h2, 32, (size_t)n_cap * 32, M.w_c3, M.b_c3, nullptr, 0, 0, ws.conf, 1, (size_t)n_cap, 32, 1, B, n_cap, n_rows, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(pdsc_normalise_kernel, dim3(n_cap / 4, B), dim3(256), 0, st, ws.feat, C, n_cap, n_rows, ws.feat_n);
+    pdsc_launch_normalise(ws.feat, C, n_cap, B, n_rows, ws.feat_n, st);
     return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
 }
 

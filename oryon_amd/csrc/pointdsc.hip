@@ -298,7 +298,7 @@ extern "C" int oryon_pointdsc_finalize(oryon_pointdsc_t *h, void *stream)
                             put_half(ch, ch + PDSC_PQ_CHUNK_BYTES / 2, (size_t)o * 256 + (size_t)((q ^ (o & 15)) << 4) + e * 2,
                                      wq[((size_t)part * C + o) * C + perm_src(q, e)]);
             }
-            // chunk 4: PointCN once more with K in accumulator-register order, for pdsc_mlp3_pcn_qkv_x3_kernel (its input is the previous
+            // chunk 4: PointCN once more with K in accumulator-register order, for pdsc_att_chain_x3_kernel (its input is the previous
             // layer's output still in registers)
             char *c4 = im + (size_t)4 * PDSC_PQ_CHUNK_BYTES;
             for (int o = 0; o < C; ++o)
