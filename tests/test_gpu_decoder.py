@@ -22,12 +22,28 @@ def _nhwc(buf, off, n, H, W, C):
     return buf[off:off + n * H * W * C * 4].view(torch.float32).view(n, H, W, C).permute(0, 3, 1, 2)
 
 
-@pytest.mark.parametrize("n,h,w", [(2, 24, 24), (3, 8, 16)])
+def persistent_conv_items(n, h, w):
+    """Work items (n * 16 x 16 tiles) of decoder2's and decoder3's cin == cout == 32 convolutions for an [n, 128, h, w] input.  launch_conv
+    (csrc/decoder.hip) takes the persistent register-weight instantiation dec_conv3x3_kernel<1, false, IN_GN, true> when that count is
+    above 512; the source line is checked so that a moved threshold breaks the tests that rely on it instead of un-covering the variant."""
+    src = open(os.path.join(os.path.dirname(GOLD), os.pardir, "oryon_amd", "csrc", "decoder.hip")).read()
+    assert "if (a.cin == 32 && a.cout == 32 && total > 512) {" in src and "dim3(512), dim3(256), 0, st, a, tiles, total);" in src
+    return n * (4 * h // 16) * (4 * w // 16), n * (8 * h // 16) * (8 * w // 16)
+
+
+@pytest.mark.parametrize("n,h,w", [(2, 24, 24), (3, 8, 16), (3, 32, 24), (5, 48, 40)])
 def test_hip_decoder_layers_match_torch_fp32(n, h, w):
     """Every intermediate the workspace exposes (cat buffers, raw convolution outputs) and both outputs against the torch modules run
-    in fp32 on the same device: <= 2e-5 of the tensor's largest magnitude (the fp16x3 products are ~2^-22 relative)."""
+    in fp32 on the same device: <= 2e-5 of the tensor's largest magnitude (the fp16x3 products are ~2^-22 relative).  The first two
+    shapes stay on the one-item-per-workgroup convolutions; (3, 32, 24) puts decoder3's two convolutions (576 items on 512 workgroups:
+    one or two items each, streams crossing image boundaries) and (5, 48, 40) also decoder2's second (600 items; decoder3: 2400, ~4.7
+    per workgroup) on the persistent register-weight variant."""
     from oryon_amd.backbone import fusion
     from oryon_amd.backbone.decoder_hip import HipDecoder
+    d2_items, d3_items = persistent_conv_items(n, h, w)
+    assert {(2, 24, 24): d2_items == 72 and d3_items == 288, (3, 8, 16): d3_items == 96 and d2_items <= 512,
+            (3, 32, 24): d2_items == 144 and d3_items == 576 and d2_items <= 512 < d3_items,
+            (5, 48, 40): d2_items == 600 and d3_items == 2400 and 512 < d2_items}[(n, h, w)], (d2_items, d3_items)
     torch.backends.cudnn.allow_tf32 = False
     torch.manual_seed(5)
     dec = _decoder(7)
