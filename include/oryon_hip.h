@@ -743,6 +743,48 @@ int oryon_vsd_counts(const double *pred_pose, const double *gt_pose, const doubl
                      int max_faces, const int32_t *model_of_pair, const double *diameter_mm, double delta, const double *taus, int n_tau,
                      void *workspace, int32_t *counts, void *stream);
 
+/* g1  ground-truth pixel correspondences of B RGB-D pairs with known poses (csrc/gt_corrs.hip): what the reference's data-preparation
+ *     scripts store as annots.pkl 'corrs'.  Replaces scripts/data/make_toyl_test.py:47-85 + :175-243 (make_nocs_test.py alike): lift the
+ *     object's pixels of both views (utils/data/toyl.py:237-278 get_pcd + filter_pcd over utils/pcd.py:44-74), move the anchor cloud by
+ *     pose_q @ inv(pose_a), torch.cdist in float64 (a 20 000 x 20 000 matrix, 3.2 GB), amin / argmin, min_dist <= threshold.
+ * DEFINITION.  All arithmetic is float64 without contraction, sums left to right, unless noted; tests/gt_corrs_restatement.py is the
+ * same sequence of correctly rounded operations in numpy and agrees bit for bit.
+ *   lift       pixel p of the list -> y = p / W, x = p % W, z = double(depth[p]) (fp32 millimetres),
+ *              X = (double(fp32(x) - fp32(cx)) * z) / fx / 1000,  Y = (double(fp32(y) - fp32(cy)) * z) / fy / 1000,  Z = z / 1000.
+ *              The difference is an fp32 one: the reference's xmap / ymap are float32 tensors and cx / cy 0-dim float64 tensors, which
+ *              torch's promotion leaves in float32 (an all-float64 lift differs by up to 1.7e-5 mm).  fx = cam9[0], cx = cam9[2],
+ *              fy = cam9[4], cy = cam9[5].  A zero-depth pixel lifts to the origin and is KEPT, as in the reference; a list entry
+ *              outside [0, H W) reads no depth and lifts like a zero-depth pixel (0, 0).
+ *   transform  anchor side only: p' = ((R0 x + R1 y) + R2 z) + t per coordinate, pose_aq [B,12] float64 = the rows [R | t] of
+ *              pose_q @ inv(pose_a), translation in metres (formed by the caller, in numpy, as make_toyl_test.py:212 does).
+ *   nearest    for every anchor row i: d2_j = ((dx dx + dy dy) + dz dz) over the query rows j = 0 .. n_q - 1, idx_i = the FIRST minimiser
+ *              (lowest j on ties: torch.argmin), d2_i its value.  A NaN distance never wins; idx = -1, d2 = +inf when no row compares
+ *              below +inf (n_q = 0).  The reference's cdist uses the matmul form above 25 rows; the two can differ in the last bits of
+ *              a distance, never in an index unless two candidates lie within ~1e-12 (relative) of each other.
+ *   keep       row i is kept when sqrt(d2_i) <= threshold; kept rows are written in anchor (list) order as (y_a, x_a, y_q, x_q).
+ * The reference's draws (at most 20 000 points per side, at most max_corrs kept rows; torch.multinomial) are the caller's: the lists
+ * arrive already drawn, in drawn order (oryon_amd/pairs.py).
+ * Counts n [B] are DEVICE arrays; a count above its capacity is read as the capacity and rows beyond the count are never read.
+ * float64 pointers must be 8-byte aligned.  No entry allocates, synchronises or uses atomics: outputs are bit-stable.
+ *
+ * oryon_gtc_lift: the lift (+ transform when pose is not NULL) alone.  depth [B,H,W] fp32; pix [B,cap] int32; cam9 [B,9] float64 ->
+ *   xyz [B,cap,3] float64 metres, yx [B,cap,2] int32 (rows < n[b] written).
+ * oryon_pcd_nearest_f64: the nearest stage alone.  src [B,cap_src,3], dst [B,cap_dst,3] float64 -> idx [B,cap_src] int32,
+ *   d2 [B,cap_src] float64 (rows < n_src[b] written).
+ * oryon_gt_corrs: the whole routine.  depth_a [B,HA,WA], depth_q [B,HQ,WQ]; pix_a [B,cap_a], pix_q [B,cap_q]; cam_a, cam_q [B,9];
+ *   threshold in metres (>= 0); status_in [B] or NULL: a pair with a non-zero status is skipped and gets n_corr = 0.
+ *   workspace: oryon_gt_corrs_workspace_bytes(B, cap_a, cap_q) bytes (0 = unsupported shape), 256-byte aligned.
+ *   corrs [B,cap_a,4] int32 (rows < n_corr[b] written), n_corr [B]; idx / d2 [B,cap_a] or NULL: the nearest stage's outputs. */
+int oryon_gtc_lift(const float *depth, int B, int H, int W, const int32_t *pix, const int32_t *n, int cap, const double *cam9,
+                   const double *pose, double *xyz, int32_t *yx, void *stream);
+int oryon_pcd_nearest_f64(const double *src, const int32_t *n_src, const double *dst, const int32_t *n_dst, int B, int cap_src,
+                          int cap_dst, int32_t *idx, double *d2, void *stream);
+size_t oryon_gt_corrs_workspace_bytes(int B, int cap_a, int cap_q);
+int oryon_gt_corrs(const float *depth_a, const float *depth_q, int B, int HA, int WA, int HQ, int WQ, const int32_t *pix_a,
+                   const int32_t *n_a, int cap_a, const int32_t *pix_q, const int32_t *n_q, int cap_q, const double *cam_a,
+                   const double *cam_q, const double *pose_aq, double threshold, const int32_t *status_in, void *workspace,
+                   size_t workspace_bytes, int32_t *corrs, int32_t *n_corr, int32_t *idx, double *d2, void *stream);
+
 /* a5  StandardDecoder.forward (models/decoder.py:82-108) on the device, fp32 in / fp32 out, for the decoder the reference builds
  *     (get_decoder, models/decoder.py:119-125: input_dim 128, decoder_dims [64, 32], extra_upsampling, guidance projections 256->32 and
  *     128->16): three Up blocks (ConvTranspose2d 2x2 s2 -> cat guidance -> (conv3x3 - GroupNorm(C/16) - ReLU) x 2, :9-42), the two

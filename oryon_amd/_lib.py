@@ -172,6 +172,11 @@ _PROTOS = {
     "oryon_pointdsc_hypotheses": (c_int, [c_void_p, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P, _P,
                                           _P, _P]),
     "oryon_pointdsc_refine": (c_int, [c_void_p, _P, _P, _P, c_int, c_int, _P, _P, _P, _P]),
+    "oryon_gtc_lift": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, _P]),
+    "oryon_pcd_nearest_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "oryon_gt_corrs_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "oryon_gt_corrs": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, _P, _P, _P, ctypes.c_double, _P,
+                               _P, c_size_t, _P, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_PROTOS)

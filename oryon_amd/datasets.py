@@ -12,6 +12,7 @@ per-image annotations live:
           NOCS line:  "<part>, <scene_a> <img_a>, <scene_q> <img_q>, <cat_id> <obj_name>"
           TOYL line:  "<part>, <scene_a> <img_a>, <scene_q> <img_q>, <cls_id>"
     <root>/<name>/fixed_split/<split>/annots.pkl  {"<sa>_<ia>_<sq>_<iq>_<cat>[_<obj_name>]": {"gt": 4x4 (translation mm), "corrs": [n,4]}}
+          (both files are written by make_split.py / oryon_amd.pairs.make_fixed_split here, or by the reference's scripts/data/make_*_test.py)
     NOCS:  split/real_test/scene_<s>/<img:04d>_{color,mask,depth}.png, _meta.txt ("<mask_id> <cls_id> <obj_name>"), _detection.txt,
            gts/real_test/results_real_test_scene_<s>_<img:04d>.pkl ({"gt_RTs": [k,4,4]}, scaled rotations), obj_names.json,
            obj_models/real_test/{models_info.json, <obj>_vertices.txt}

@@ -926,6 +926,114 @@ def vsd_counts(pred_pose: torch.Tensor, gt_pose: torch.Tensor, K: torch.Tensor, 
     return counts
 
 
+def _host_counts(n, B: int, cap: int, what: str):
+    """Counts given on the host (None, ints, lists, CPU tensors) -> a [B] int32 CPU tensor, checked against the capacity BEFORE anything
+    touches the GPU (the kernels read a device count above its capacity as the capacity; here it is the caller's mistake).  Device
+    tensors pass through unchecked: reading them back would synchronise."""
+    if isinstance(n, torch.Tensor) and n.is_cuda:
+        if n.dtype != torch.int32 or tuple(n.shape) != (B,):
+            raise ValueError(f"{what}: device counts must be [B] int32, got {tuple(n.shape)} {n.dtype}")
+        return n
+    t = torch.full((B,), cap, dtype=torch.int64) if n is None else torch.as_tensor(n, dtype=torch.int64).reshape(-1)
+    if t.numel() != B:
+        raise ValueError(f"{what}: {t.numel()} counts for {B} pairs")
+    if bool((t < 0).any()) or bool((t > cap).any()):
+        raise ValueError(f"{what}: counts {t.tolist()} outside [0, cap = {cap}]")
+    return t.to(torch.int32)
+
+
+def _gt_device(*tensors):
+    for t in tensors:
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cuda")
+
+
+def pcd_nearest(src: torch.Tensor, dst: torch.Tensor, n_src=None, n_dst=None):
+    """All-pairs nearest neighbour in 3-D, float64 (g1, csrc/gt_corrs.hip; torch.cdist + argmin of make_toyl_test.py:68-72 without the
+    distance matrix).  src [B,cap_src,3], dst [B,cap_dst,3] (or [n,3]: one pair) float64; n_src / n_dst [B] rows in use (None = all)
+    -> (idx [B,cap_src] int32 = the first minimiser, d2 [B,cap_src] float64 = its squared distance); rows >= n_src[b] are not written.
+    Definition: include/oryon_hip.h, oryon_gt_corrs."""
+    if src.dim() == 2:
+        src, dst = src[None], dst[None]
+    if src.dim() != 3 or dst.dim() != 3 or src.shape[2] != 3 or dst.shape[2] != 3 or src.shape[0] != dst.shape[0]:
+        raise ValueError(f"pcd_nearest: src {tuple(src.shape)} / dst {tuple(dst.shape)} are not [B,n,3] clouds of one batch")
+    B, cap_src, cap_dst = src.shape[0], src.shape[1], dst.shape[1]
+    if cap_src < 1 or cap_dst < 1:
+        raise ValueError("pcd_nearest: a capacity of 0 rows (pass one row and a count of 0)")
+    ns, nd = _host_counts(n_src, B, cap_src, "pcd_nearest n_src"), _host_counts(n_dst, B, cap_dst, "pcd_nearest n_dst")
+    dev = _lib.require_gpu(_gt_device(src, dst))
+    with torch.cuda.device(dev):
+        src, dst = src.to(dev, torch.float64).contiguous(), dst.to(dev, torch.float64).contiguous()
+        ns, nd = ns.to(dev).contiguous(), nd.to(dev).contiguous()
+        idx = torch.empty((B, cap_src), dtype=torch.int32, device=dev)
+        d2 = torch.empty((B, cap_src), dtype=torch.float64, device=dev)
+        check(lib().oryon_pcd_nearest_f64(ptr(src), ptr(ns), ptr(dst), ptr(nd), B, cap_src, cap_dst, ptr(idx), ptr(d2), stream_ptr(dev)),
+              "oryon_pcd_nearest_f64")
+    return idx, d2
+
+
+def gtc_lift(depth: torch.Tensor, pix: torch.Tensor, n, cam9: torch.Tensor, pose: Optional[torch.Tensor] = None):
+    """Lift listed pixels (g1): depth [B,H,W] fp32 millimetres, pix [B,cap] int32 linear pixels, n [B], cam9 [B,9] float64, pose [B,12]
+    float64 rows of [R | t] or None -> (xyz [B,cap,3] float64 metres, yx [B,cap,2] int32); rows >= n[b] are not written."""
+    B, H, W = depth.shape
+    if pix.dim() != 2 or pix.shape[0] != B or pix.shape[1] < 1:
+        raise ValueError(f"gtc_lift: pix {tuple(pix.shape)} is not [B = {B}, cap >= 1]")
+    cap = pix.shape[1]
+    nn = _host_counts(n, B, cap, "gtc_lift n")
+    dev = _lib.require_gpu(_gt_device(depth, pix))
+    with torch.cuda.device(dev):
+        depth, pix = depth.to(dev, torch.float32).contiguous(), pix.to(dev, torch.int32).contiguous()
+        cam = cam9.to(dev, torch.float64).reshape(B, 9).contiguous()
+        T = None if pose is None else pose.to(dev, torch.float64).reshape(B, 12).contiguous()
+        nn = nn.to(dev).contiguous()
+        xyz = torch.empty((B, cap, 3), dtype=torch.float64, device=dev)
+        yx = torch.empty((B, cap, 2), dtype=torch.int32, device=dev)
+        check(lib().oryon_gtc_lift(ptr(depth), B, H, W, ptr(pix), ptr(nn), cap, ptr(cam), ptr(T), ptr(xyz), ptr(yx), stream_ptr(dev)),
+              "oryon_gtc_lift")
+    return xyz, yx
+
+
+def gt_corrs(depth_a: torch.Tensor, depth_q: torch.Tensor, pix_a: torch.Tensor, n_a, pix_q: torch.Tensor, n_q, cam_a: torch.Tensor,
+             cam_q: torch.Tensor, pose_aq: torch.Tensor, threshold: float, status: Optional[torch.Tensor] = None, want_nn: bool = False):
+    """Ground-truth correspondences of B pairs (g1, csrc/gt_corrs.hip).  depth_* [B,H,W] fp32 millimetres; pix_* [B,cap] int32 pixel
+    lists (roi_compact, or drawn through the reference's 20 000-point table) with n_* [B]; cam_* [B,9] or [B,3,3] float64; pose_aq
+    [B,4,4] or [B,12] float64 (metres) -> dict(corrs [B,cap_a,4] int32 (y_a,x_a,y_q,x_q), n_corr [B] int32, idx / d2 [B,cap_a] | None)."""
+    B = depth_a.shape[0]
+    if depth_a.dim() != 3 or depth_q.dim() != 3 or depth_q.shape[0] != B:
+        raise ValueError("gt_corrs: depth maps are [B,H,W]")
+    if pix_a.dim() != 2 or pix_q.dim() != 2 or pix_a.shape[0] != B or pix_q.shape[0] != B or pix_a.shape[1] < 1 or pix_q.shape[1] < 1:
+        raise ValueError(f"gt_corrs: pixel lists {tuple(pix_a.shape)} / {tuple(pix_q.shape)} are not [B = {B}, cap >= 1]")
+    if not float(threshold) >= 0.0:
+        raise ValueError(f"gt_corrs: threshold {threshold} is not >= 0")
+    cap_a, cap_q = pix_a.shape[1], pix_q.shape[1]
+    na, nq = _host_counts(n_a, B, cap_a, "gt_corrs n_a"), _host_counts(n_q, B, cap_q, "gt_corrs n_q")
+    pose = pose_aq.reshape(B, -1)
+    pose = pose[:, :12] if pose.shape[1] == 16 else pose
+    if pose.shape[1] != 12:
+        raise ValueError("gt_corrs: pose_aq is [B,4,4] or [B,12]")
+    dev = _lib.require_gpu(_gt_device(depth_a, pix_a))
+    with torch.cuda.device(dev):
+        da, dq = depth_a.to(dev, torch.float32).contiguous(), depth_q.to(dev, torch.float32).contiguous()
+        pa, pq = pix_a.to(dev, torch.int32).contiguous(), pix_q.to(dev, torch.int32).contiguous()
+        ca, cq = cam_a.to(dev, torch.float64).reshape(B, 9).contiguous(), cam_q.to(dev, torch.float64).reshape(B, 9).contiguous()
+        T = pose.to(dev, torch.float64).contiguous()
+        na, nq = na.to(dev).contiguous(), nq.to(dev).contiguous()
+        st = None if status is None else status.to(dev, torch.int32).contiguous()
+        need = lib().oryon_gt_corrs_workspace_bytes(B, cap_a, cap_q)
+        if need == 0 and B > 0:
+            raise _lib.OryonError(f"oryon_gt_corrs_workspace_bytes({B}, {cap_a}, {cap_q}): shape not supported")
+        ws = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+        corrs = torch.empty((B, cap_a, 4), dtype=torch.int32, device=dev)
+        n_corr = torch.empty((B,), dtype=torch.int32, device=dev)
+        idx = torch.empty((B, cap_a), dtype=torch.int32, device=dev) if want_nn else None
+        d2 = torch.empty((B, cap_a), dtype=torch.float64, device=dev) if want_nn else None
+        check(lib().oryon_gt_corrs(ptr(da), ptr(dq), B, da.shape[1], da.shape[2], dq.shape[1], dq.shape[2], ptr(pa), ptr(na), cap_a, ptr(pq),
+                                   ptr(nq), cap_q, ptr(ca), ptr(cq), ptr(T), float(threshold), ptr(st), ptr(ws), ws.numel(), ptr(corrs),
+                                   ptr(n_corr), ptr(idx), ptr(d2), stream_ptr(dev)), "oryon_gt_corrs")
+    return dict(corrs=corrs, n_corr=n_corr, idx=idx, d2=d2)
+
+
 _x3_weights = {}
 # Validation mode of the fp16x3 path (backbone.enable_fp16x3(True, guard=True)): every call first checks max|activation| against the
 # float16 range (one reduction + a host sync per linear - for a first run with a real checkpoint, not for throughput) and evaluates

@@ -21,6 +21,7 @@ Reference entry points executed here:
   losses.py                   FeatureLoss.forward (sample_positives, sample_hardest_negatives, sample_negatives, mask_loss) and
                               utils/metrics.py compute_fmr (gen_feature_loss; `python tools/gen_goldens.py floss`); the same forward
                               followed by torch's backward (gen_feature_loss_grad; `python tools/gen_goldens.py floss_grad`)
+  scripts/data/make_toyl_test.py  pcd_correspondences (gen_gt_corrs; `python tools/gen_goldens.py gt_corrs`): recorded results only
 """
 import json
 import os
@@ -1051,6 +1052,59 @@ def gen_feature_loss_grad():
             assert size <= limit, (name, size, limit)
 
 
+def _reference_pcd_correspondences():
+    """The reference's own `pcd_correspondences` (scripts/data/make_toyl_test.py:47-85), compiled from its file without importing the
+    script around it (whose module level pulls in the dataset readers, PIL, matplotlib and an argument parser)."""
+    import ast
+    from typing import Tuple
+    path = os.path.join(REF, "scripts", "data", "make_toyl_test.py")
+    tree = ast.parse(open(path).read(), filename=path)
+    fn = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "pcd_correspondences"]
+    assert len(fn) == 1
+    ns = {"torch": torch, "Tensor": torch.Tensor, "Tuple": Tuple}
+    exec(compile(ast.Module(body=fn, type_ignores=[]), path, "exec"), ns)
+    return ns["pcd_correspondences"]
+
+
+def gen_gt_corrs():
+    """Ground-truth correspondences: the reference's pcd_correspondences on the CPU (torch.cdist float64, amin / argmin, the multinomial
+    draws) on the seeded clouds of tests/gt_corrs_restatement.py.  A fixture holds the RECORDED RESULTS and the seeds only: the tests
+    regenerate the clouds.  Asserted here for every fixture, so that the reference's matmul-form cdist and the direct form of the
+    definition cannot disagree on it: every row's best and second-best distance are exact duplicates or at least 1e-9 apart (relative
+    to the larger), and no row's minimum lies within 1e-9 (relative) of the threshold."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gt_corrs_restatement as R
+    ref_fn = _reference_pcd_correspondences()
+    for name, (seed, n1, n2, threshold, max_corrs, tseed) in R.GOLDEN_CASES.items():
+        f1, f2 = R.golden_clouds(name)
+        assert f1.shape == (n1, 3) and f2.shape == (n2, 3)
+        torch.manual_seed(tseed)
+        i1, i2 = ref_fn(torch.as_tensor(f1), torch.as_tensor(f2), threshold, max_corrs)
+        state = torch.get_rng_state().numpy().copy()
+        # the margins, on the clouds the distance matrix was built on (the same draws again)
+        torch.manual_seed(tseed)
+        s1 = f1[torch.multinomial(torch.ones(n1, dtype=float), R.SAMPLE, replacement=False).numpy()] if n1 >= R.SAMPLE else f1
+        s2 = f2[torch.multinomial(torch.ones(n2, dtype=float), R.SAMPLE, replacement=False).numpy()] if n2 >= R.SAMPLE else f2
+        idx, d2, d2b = R.nearest(s1, s2, second=True)
+        best, sec = np.sqrt(d2), np.sqrt(d2b)
+        fin = np.isfinite(sec)
+        with np.errstate(invalid="ignore"):
+            gap = np.where(fin, (sec - best) / np.where(fin & (sec > 0), sec, 1.0), np.inf)
+        assert np.all((gap == 0.0) | (gap >= 1e-9)), (name, float(gap[gap > 0].min()))
+        margin = R.threshold_margin(d2, threshold)
+        assert margin >= 1e-9, (name, margin)
+        d_ref = torch.cdist(torch.as_tensor(s1), torch.as_tensor(s2), p=2)
+        assert np.array_equal(torch.argmin(d_ref, dim=1).numpy(), idx), name
+        err = float((torch.amin(d_ref, dim=1) - torch.as_tensor(best)).abs().max())
+        n_kept = int(R.keep(d2, threshold).sum())
+        print(f"gtcorr_{name}: {n1} x {n2}, kept {n_kept}, returned {i1.shape[0]}; |d - d_ref| <= {err:.1e}; smallest positive gap "
+              f"{float(gap[gap > 0].min()) if (gap > 0).any() else float('inf'):.1e}, threshold margin {margin:.1e}")
+        save(f"gtcorr_{name}", case=np.array(name), numpy_seed=np.int64(seed), torch_seed=np.int64(tseed), n1=np.int64(n1), n2=np.int64(n2),
+             threshold=np.float64(threshold), max_corrs=np.int64(max_corrs), n_kept=np.int64(n_kept), idx1=i1.numpy(), idx2=i2.numpy(),
+             rng_state=state)
+        assert os.path.getsize(os.path.join(OUT, f"gtcorr_{name}.npz")) <= 256 * 1024
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["matcher", "lift", "kabsch", "pointdsc", "e2e", "backbone", "metrics", "bop", "tokenizer", "data"]
     if "data" in which:
@@ -1083,3 +1137,5 @@ if __name__ == "__main__":
         gen_feature_loss()
     if "floss_grad" in which:
         gen_feature_loss_grad()
+    if "gt_corrs" in which:
+        gen_gt_corrs()
