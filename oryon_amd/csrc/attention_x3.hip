@@ -1,8 +1,7 @@
 // B5: multi-head self-attention of the frozen CLIP image tower (models/vlm.py:46-56 -> clip's ResidualAttentionBlock: nn.MultiheadAttention
 // on [L = 577, N, 1024], 16 heads of 64) in fp32-grade arithmetic on the fp16 matrix pipe.  torch evaluates it with an fp32 flash kernel at
-// ~70 TFLOP/s (2.5 ms per layer for 128 images); here both products run error-compensated (x = hi + lo halves, a.b accumulated as
-// a_hi.b_hi + a_hi.b_lo + a_lo.b_hi on v_mfma_f32_32x32x16_f16), the scheme of pdsc_attention_x3_kernel without the spatial-consistency
-// weights:
+// ~70 TFLOP/s (2.5 ms per layer for 128 images); here both products run error-compensated (the fp16x3 scheme and its split: x3.h),
+// transposed:
 //     S^T = K Q^T / 8   (rows = keys, columns = queries: a lane owns ONE query column, so the softmax statistics are lane-local)
 //     O^T = V^T P^T     (the P registers of the softmax ARE the B operand of the second product; the V tile is laid out in LDS so that
 //                        MFMA k-slot (lane half h, element e) of block (kb, t) is the key those registers hold)
@@ -12,36 +11,12 @@
 #include <hip/hip_fp16.h>
 #include <type_traits>
 #include "common.h"
+#include "x3.h"
 
 namespace oryon {
 
-typedef _Float16 ahalf8 __attribute__((ext_vector_type(8)));
-typedef float af32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int MHA_D = 64, MHA_KT = 64, MHA_Q = 128;
 constexpr int MHA_KLD = MHA_D + 8;
-
-// Two values at a time (round 6): packed conversion for hi, x - float(hi) as ONE v_fma_mix_f32 (hi's half read as the f16 source of an fp32
-// fma), packed conversion for lo - four instructions per pair where mha_split takes four per ELEMENT plus the packing; the same bits
-// (tools/probe_cvt_pk_f16.hip).  The kernel's VALU and MFMA instructions do not overlap on this part, so the split is wave time.
-typedef float mha_f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 mha_f16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void mha_split2(float a, float b, unsigned &hi, unsigned &lo)
-{
-    const mha_f32x2 v = {a, b};
-    const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v, mha_f16x2));
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hb), "v"(a));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hb), "v"(b));
-    const mha_f32x2 lv = {l0, l1};
-    hi = hb;
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(lv, mha_f16x2));
-}
-__device__ __forceinline__ void mha_split(float x, _Float16 &hi, _Float16 &lo)
-{
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
 
 // Round 5 rework of the loop around the same arithmetic (results bit-identical to the round-2 kernel): the ISA of that kernel spent ~790
 // VALU-class instructions per 64-key tile and wave against 48 MFMAs (1536 matrix-pipe cycles), a quarter of them 64-bit address arithmetic
@@ -115,8 +90,8 @@ __global__ __launch_bounds__(256, 2) void mha_x3_kernel(const float *__restrict_
         for (int i = 0; i < 4; ++i) {
             const int row = (int)krow0 + 16 * i;
             uint2 ph, pl;
-            mha_split2(kv[i].x, kv[i].y, ph.x, pl.x);
-            mha_split2(kv[i].z, kv[i].w, ph.y, pl.y);
+            split2(kv[i].x, kv[i].y, ph.x, pl.x);
+            split2(kv[i].z, kv[i].w, ph.y, pl.y);
             *reinterpret_cast<uint2 *>(Kh + row * MHA_KLD + 4 * (int)kc4) = ph;
             *reinterpret_cast<uint2 *>(Kl + row * MHA_KLD + 4 * (int)kc4) = pl;
         }
@@ -124,32 +99,32 @@ __global__ __launch_bounds__(256, 2) void mha_x3_kernel(const float *__restrict_
         for (int o = 0; o < 2; ++o) {
             const int oct = wave + 4 * o;
             uint4 ph, pl;
-            mha_split2(vv[o * 8 + 0], vv[o * 8 + 1], ph.x, pl.x);
-            mha_split2(vv[o * 8 + 2], vv[o * 8 + 3], ph.y, pl.y);
-            mha_split2(vv[o * 8 + 4], vv[o * 8 + 5], ph.z, pl.z);
-            mha_split2(vv[o * 8 + 6], vv[o * 8 + 7], ph.w, pl.w);
+            split2(vv[o * 8 + 0], vv[o * 8 + 1], ph.x, pl.x);
+            split2(vv[o * 8 + 2], vv[o * 8 + 3], ph.y, pl.y);
+            split2(vv[o * 8 + 4], vv[o * 8 + 5], ph.z, pl.z);
+            split2(vv[o * 8 + 6], vv[o * 8 + 7], ph.w, pl.w);
             *reinterpret_cast<uint4 *>(Vh + ((size_t)oct * C + lane) * 8) = ph;
             *reinterpret_cast<uint4 *>(Vl + ((size_t)oct * C + lane) * 8) = pl;
         }
     };
 
     // Q^T as B operand (scaled once): lane (query l31, half hi), k16 step s -> channels 16s + 8hi .. +7
-    ahalf8 qh[NS], ql[NS];
+    f16x8 qh[NS], ql[NS];
     {
         const float4 *qv = reinterpret_cast<const float4 *>(base + (size_t)qsafe * rs);
 #pragma unroll
         for (int s_ = 0; s_ < NS; ++s_) {
             const float4 a = qv[4 * s_ + 2 * hi], c = qv[4 * s_ + 2 * hi + 1];
             uint4 uh, ul;                                 // scale = 2^-3 for head dim 64: exact
-            mha_split2(a.x * scale, a.y * scale, uh.x, ul.x);
-            mha_split2(a.z * scale, a.w * scale, uh.y, ul.y);
-            mha_split2(c.x * scale, c.y * scale, uh.z, ul.z);
-            mha_split2(c.z * scale, c.w * scale, uh.w, ul.w);
-            qh[s_] = __builtin_bit_cast(ahalf8, uh);
-            ql[s_] = __builtin_bit_cast(ahalf8, ul);
+            split2(a.x * scale, a.y * scale, uh.x, ul.x);
+            split2(a.z * scale, a.w * scale, uh.y, ul.y);
+            split2(c.x * scale, c.y * scale, uh.z, ul.z);
+            split2(c.z * scale, c.w * scale, uh.w, ul.w);
+            qh[s_] = __builtin_bit_cast(f16x8, uh);
+            ql[s_] = __builtin_bit_cast(f16x8, ul);
         }
     }
-    af32x16 acc_o[CB];
+    f32x16 acc_o[CB];
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
@@ -160,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void mha_x3_kernel(const float *__restrict_
     auto tile = [&](auto nkb_tag, auto ragged_tag, int j0) {
         constexpr int NKB = decltype(nkb_tag)::value;
         constexpr bool RAGGED = decltype(ragged_tag)::value;
-        af32x16 s[NKB];
+        f32x16 s[NKB];
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
@@ -169,8 +144,8 @@ __global__ __launch_bounds__(256, 2) void mha_x3_kernel(const float *__restrict_
         for (int s_ = 0; s_ < NS; ++s_) {
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
-                const ahalf8 ah = *reinterpret_cast<const ahalf8 *>(Kh + (kb * 32 + l31) * MHA_KLD + 16 * s_ + 8 * hi);
-                const ahalf8 al = *reinterpret_cast<const ahalf8 *>(Kl + (kb * 32 + l31) * MHA_KLD + 16 * s_ + 8 * hi);
+                const f16x8 ah = *reinterpret_cast<const f16x8 *>(Kh + (kb * 32 + l31) * MHA_KLD + 16 * s_ + 8 * hi);
+                const f16x8 al = *reinterpret_cast<const f16x8 *>(Kl + (kb * 32 + l31) * MHA_KLD + 16 * s_ + 8 * hi);
                 s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, qh[s_], s[kb], 0, 0, 0);
                 s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ql[s_], s[kb], 0, 0, 0);
                 s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, qh[s_], s[kb], 0, 0, 0);
@@ -183,7 +158,7 @@ __global__ __launch_bounds__(256, 2) void mha_x3_kernel(const float *__restrict_
             for (int r = 0; r < 16; ++r) {
                 float v = s[kb][r];
                 if constexpr (RAGGED) {
-                    if (j0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= L) v = -INFINITY;
+                    if (j0 + kb * 32 + crow(r, hi) >= L) v = -INFINITY;
                     s[kb][r] = v;
                 }
                 m_tile = fmaxf(m_tile, v);
@@ -200,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void mha_x3_kernel(const float *__restrict_
             m_run = m_new;
         }
         float l_tile = 0.0f;
-        ahalf8 ph[NKB][2], pl[NKB][2];
+        f16x8 ph[NKB][2], pl[NKB][2];
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
@@ -209,8 +184,8 @@ __global__ __launch_bounds__(256, 2) void mha_x3_kernel(const float *__restrict_
                 l_tile += p0;
                 l_tile += p1;
                 unsigned uh, ul;
-                mha_split2(p0, p1, uh, ul);
-                const mha_f16x2 h2 = __builtin_bit_cast(mha_f16x2, uh), l2 = __builtin_bit_cast(mha_f16x2, ul);
+                split2(p0, p1, uh, ul);
+                const f16x2 h2 = __builtin_bit_cast(f16x2, uh), l2 = __builtin_bit_cast(f16x2, ul);
                 ph[kb][r >> 3][r & 7] = h2[0]; ph[kb][r >> 3][(r & 7) + 1] = h2[1];
                 pl[kb][r >> 3][r & 7] = l2[0]; pl[kb][r >> 3][(r & 7) + 1] = l2[1];
             }
@@ -222,8 +197,8 @@ __global__ __launch_bounds__(256, 2) void mha_x3_kernel(const float *__restrict_
                 const int oct = (kb * 2 + t2) * 2 + hi;
 #pragma unroll
                 for (int cb = 0; cb < CB; ++cb) {
-                    const ahalf8 vh = *reinterpret_cast<const ahalf8 *>(Vh + ((size_t)oct * C + cb * 32 + l31) * 8);
-                    const ahalf8 vl = *reinterpret_cast<const ahalf8 *>(Vl + ((size_t)oct * C + cb * 32 + l31) * 8);
+                    const f16x8 vh = *reinterpret_cast<const f16x8 *>(Vh + ((size_t)oct * C + cb * 32 + l31) * 8);
+                    const f16x8 vl = *reinterpret_cast<const f16x8 *>(Vl + ((size_t)oct * C + cb * 32 + l31) * 8);
                     acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[kb][t2], acc_o[cb], 0, 0, 0);
                     acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[kb][t2], acc_o[cb], 0, 0, 0);
                     acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[kb][t2], acc_o[cb], 0, 0, 0);

@@ -7,6 +7,7 @@
 // that the reference-pinned fp32 numerics are untouched.
 #include <hip/hip_bf16.h>
 #include "common.h"
+#include "x3.h"
 
 namespace oryon {
 
@@ -432,168 +433,187 @@ extern "C" int oryon_swin_window_attention_bf16(const void *qkv, const void *pad
 //                 statistics are in-lane loops plus one cross-lane exchange;
 //   O^T = V^T P^T: B = P^T = the exponentials exactly where the accumulators left them (k-step ks = registers 8 (ks & 1) .. + 7 of key
 //                 block ks / 2), A = V^T from an LDS tile whose key axis is stored in that register order.
-// Operands are split hi + lo (fp16) and multiplied as lo.hi + hi.lo + hi.hi with fp32 accumulation, like every fp16x3 kernel here.
-typedef _Float16 fwa_h8 __attribute__((ext_vector_type(8)));
-typedef float fwa_acc __attribute__((ext_vector_type(16)));
-
-static __device__ __forceinline__ void fwa_split8(const float (&x)[8], fwa_h8 &hi, fwa_h8 &lo)
-{
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const _Float16 h = (_Float16)x[e];
-        hi[e] = h;
-        lo[e] = (_Float16)(x[e] - (float)h);
-    }
-}
+// Operands are split hi + lo (fp16) and multiplied as lo.hi + hi.lo + hi.hi with fp32 accumulation, like every fp16x3 kernel here (x3.h).
 
 // slot of key j on the key axis of the V^T tile: k-step (j / 32) * 2 + (j % 32) / 16, lane half ((j % 16) % 8) / 4, element 4 ((j % 16) / 8) + j % 4
-// - the inverse of "register r of key block mb holds key 32 mb + 8 (r / 4) + 4 kg + r % 4"
+// - the inverse of "register r of key block mb holds key 32 mb + crow(r, kg)"
 static __device__ __forceinline__ int fwa_slot(int j)
 {
     const int jj = j & 31, u = jj & 15;
     return ((j >> 5) * 2 + (jj >> 4)) * 16 + ((u & 7) >> 2) * 8 + 4 * (u >> 3) + (u & 3);
 }
 
-__global__ __launch_bounds__(320) void fusion_window_attention_x3_kernel(const float *__restrict__ qk, const float *__restrict__ v, int H, int W,
-                                                                         int C, int shift, float scale, float *__restrict__ out)
+// The one body of the two window-attention kernels below.  P gives the geometry at compile time - WS (window side), NP (query / key slots:
+// WS * WS rounded up to whole 32-blocks; one wave per block, so the workgroup has 2 NP threads), VLD (halves per V^T row in LDS), PAD (the map
+// is padded to a multiple of WS before the roll: slots can hold padding tokens, -2), BIAS (a relative-position bias is added) and ex(), the
+// exponential - and at run time where a token's rows live: q(tk), k(tk), v(tk) (tk >= 0, or -2 under PAD) and, under BIAS, bias_col(head, qn).
+template <class P>
+__device__ __forceinline__ void window_attention_x3(const P &p, int H, int W, int C, int shift, float scale, float *out)
 {
-    constexpr int WS = 12, N = 144, NP = 160, HD = 32;
-    constexpr int VLD = 168;                                  // halves per V^T row (336 bytes: conflict-free 16-byte fragment reads)
+    constexpr int WS = P::WS, N = WS * WS, NP = P::NP, MB = NP / 32, VLD = P::VLD, HD = 32, NT = 2 * NP;
+    static_assert(NP % 32 == 0 && NP >= N && VLD >= NP + 8, "whole query blocks; padded V^T rows");
     __shared__ __attribute__((aligned(16))) _Float16 Vh[HD * VLD];
     __shared__ __attribute__((aligned(16))) _Float16 Vl[HD * VLD];
-    __shared__ int toks[NP];
+    __shared__ int toks[NP];                                  // >= 0: token, -2: padding token (PAD), -1: no token (slots N .. NP - 1)
     __shared__ int labs[NP];
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li = lane & 31, kg = lane >> 5;
     const int head = blockIdx.z, b = blockIdx.y;
-    const int nwx = W / WS, wy = blockIdx.x / nwx, wx = blockIdx.x % nwx;
+    const int Hp = P::PAD ? (H + WS - 1) / WS * WS : H, Wp = P::PAD ? (W + WS - 1) / WS * WS : W;
+    const int nwx = Wp / WS, wy = blockIdx.x / nwx, wx = blockIdx.x % nwx;
     if (t < NP) {
         int tk = -1, lab = -1;
         if (t < N) {
-            const int py = wy * WS + t / WS, px = wx * WS + t % WS;
-            const int sy = (py + shift) % H, sx = (px + shift) % W;
-            tk = (b * H + sy) * W + sx;
+            const int py = wy * WS + t / WS, px = wx * WS + t % WS;                          // rolled (and padded) frame
+            const int sy = (py + shift) % Hp, sx = (px + shift) % Wp;
+            tk = !P::PAD || (sy < H && sx < W) ? (b * H + sy) * W + sx : -2;
             lab = 0;
             if (shift > 0) {
-                const int by = py < H - WS ? 0 : (py < H - shift ? 1 : 2);
-                const int bx = px < W - WS ? 0 : (px < W - shift ? 1 : 2);
+                const int by = py < Hp - WS ? 0 : (py < Hp - shift ? 1 : 2);
+                const int bx = px < Wp - WS ? 0 : (px < Wp - shift ? 1 : 2);
                 lab = by * 3 + bx;
             }
         }
         toks[t] = tk;
         labs[t] = lab;
     }
-    // the padded key slots of V^T are zero (their probabilities are zero too, but 0 x garbage is not)
-    for (int i = t; i < HD * 16; i += 320) {
-        const int d = i >> 4, sig = fwa_slot(N + (i & 15));
+    // the unused key slots of V^T are zero (their probabilities are zero too, but 0 x garbage is not)
+    for (int i = t; i < HD * (NP - N); i += NT) {
+        const int d = i / (NP - N), sig = fwa_slot(N + i % (NP - N));
         Vh[d * VLD + sig] = (_Float16)0.0f;
         Vl[d * VLD + sig] = (_Float16)0.0f;
     }
     __syncthreads();
     // V^T tile: key j -> slot sigma(j) (the order in which the accumulators of S^T hold the keys)
-    for (int i = t; i < N * 8; i += 320) {
+    for (int i = t; i < N * 8; i += NT) {
         const int j = i >> 3, dq = i & 7;
-        const float4 x = *reinterpret_cast<const float4 *>(v + (size_t)toks[j] * C + head * HD + dq * 4);
+        const float4 x = *reinterpret_cast<const float4 *>(p.v(toks[j]) + head * HD + dq * 4);
         const int sig = fwa_slot(j);
         const float xv[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const _Float16 h = (_Float16)xv[c];
+            _Float16 h, l;
+            split1(xv[c], h, l);
             Vh[(dq * 4 + c) * VLD + sig] = h;
-            Vl[(dq * 4 + c) * VLD + sig] = (_Float16)(xv[c] - (float)h);
+            Vl[(dq * 4 + c) * VLD + sig] = l;
         }
     }
-    // Q fragments of the wave's query block (B operand: column = query, 8 dims per lane and k-step)
+    // Q fragments of the wave's query block (B operand: column = query, 8 dims per lane and k-step), scaled by hd^-0.5 first
     const int qn = wave * 32 + li;
     const int qtok = toks[qn];
-    fwa_h8 qh[2], ql[2];
+    f16x8 qh[2], ql[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         float x[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) x[e] = 0.0f;
-        if (qtok >= 0) {
-            const float4 a0 = *reinterpret_cast<const float4 *>(qk + (size_t)qtok * 2 * C + head * HD + 16 * s + 8 * kg);
-            const float4 a1 = *reinterpret_cast<const float4 *>(qk + (size_t)qtok * 2 * C + head * HD + 16 * s + 8 * kg + 4);
+        if (P::PAD ? qtok != -1 : qtok >= 0) {                             // the slot holds a token; without padding tokens: the sign test
+            const float *src = p.q(qtok) + head * HD + 16 * s + 8 * kg;
+            const float4 a0 = *reinterpret_cast<const float4 *>(src), a1 = *reinterpret_cast<const float4 *>(src + 4);
             x[0] = a0.x * scale; x[1] = a0.y * scale; x[2] = a0.z * scale; x[3] = a0.w * scale;
             x[4] = a1.x * scale; x[5] = a1.y * scale; x[6] = a1.z * scale; x[7] = a1.w * scale;
         }
-        fwa_split8(x, qh[s], ql[s]);
+        split8(x, qh[s], ql[s]);
     }
     // S^T = K Q^T, key block by key block
-    fwa_acc sc[5];
+    f32x16 sc[MB];
 #pragma unroll
-    for (int mb = 0; mb < 5; ++mb) {
+    for (int mb = 0; mb < MB; ++mb) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) sc[mb][r] = 0.0f;
         const int ktok = toks[mb * 32 + li];
+        float x[2][8];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[s][e] = 0.0f;
+        if (P::PAD ? ktok != -1 : ktok >= 0) {                              // one test per key block, both k-steps' loads under it
+            const float *src = p.k(ktok) + head * HD + 8 * kg;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float4 a0 = *reinterpret_cast<const float4 *>(src + 16 * s), a1 = *reinterpret_cast<const float4 *>(src + 16 * s + 4);
+                x[s][0] = a0.x; x[s][1] = a0.y; x[s][2] = a0.z; x[s][3] = a0.w; x[s][4] = a1.x; x[s][5] = a1.y; x[s][6] = a1.z; x[s][7] = a1.w;
+            }
+        }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            float x[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = 0.0f;
-            if (ktok >= 0) {
-                const float4 a0 = *reinterpret_cast<const float4 *>(qk + (size_t)ktok * 2 * C + C + head * HD + 16 * s + 8 * kg);
-                const float4 a1 = *reinterpret_cast<const float4 *>(qk + (size_t)ktok * 2 * C + C + head * HD + 16 * s + 8 * kg + 4);
-                x[0] = a0.x; x[1] = a0.y; x[2] = a0.z; x[3] = a0.w; x[4] = a1.x; x[5] = a1.y; x[6] = a1.z; x[7] = a1.w;
-            }
-            fwa_h8 kh, kl;
-            fwa_split8(x, kh, kl);
-            sc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[s], sc[mb], 0, 0, 0);
-            sc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[s], sc[mb], 0, 0, 0);
-            sc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[s], sc[mb], 0, 0, 0);
+            f16x8 kh, kl;
+            split8(x[s], kh, kl);
+            mfma_x3(sc[mb], kh, kl, qh[s], ql[s]);
         }
     }
-    // mask + softmax statistics of the lane's query: register r of key block mb = key 32 mb + 8 (r / 4) + 4 kg + r % 4
+    // bias (32 consecutive queries per load), the additive shift mask (models/fusion.py:166-167) and the softmax statistics of the lane's
+    // query: register r of key block mb = key 32 mb + crow(r, kg)
     const int qlab = labs[qn];
+    const float *bt = nullptr;
+    if constexpr (P::BIAS) bt = p.bias_col(head, qn < N ? qn : 0);
     float m = -3.0e38f;
 #pragma unroll
-    for (int mb = 0; mb < 5; ++mb)
+    for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int j = 32 * mb + 8 * (r >> 2) + 4 * kg + (r & 3);
+            const int j = 32 * mb + crow(r, kg);
             const int klab = labs[j];
-            float s = sc[mb][r];
-            if (klab < 0) s = -3.0e38f;                                    // padding
-            else if (klab != qlab) s += -100.0f;                           // the additive shift mask (models/fusion.py:166-167)
+            float s = -3.0e38f;                                            // no key in this slot
+            if (klab >= 0) {
+                s = sc[mb][r];
+                if constexpr (P::BIAS) s += bt[j * N];
+                if (klab != qlab) s += -100.0f;
+            }
             sc[mb][r] = s;
             m = fmaxf(m, s);
         }
     m = fmaxf(m, __shfl_xor(m, 32));
     float sum = 0.0f;
 #pragma unroll
-    for (int mb = 0; mb < 5; ++mb)
+    for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float p = sc[mb][r] > -1.0e38f ? __expf(sc[mb][r] - m) : 0.0f;
-            sc[mb][r] = p;
-            sum += p;
+            const float pe = sc[mb][r] > -1.0e38f ? P::ex(sc[mb][r] - m) : 0.0f;
+            sc[mb][r] = pe;
+            sum += pe;
         }
     sum += __shfl_xor(sum, 32);
     __syncthreads();                                                        // the V^T tile is complete
-    // O^T = V^T P^T: ten k-steps of 16 keys
-    fwa_acc o;
+    // O^T = V^T P^T: k-steps of 16 keys, k-step ks = registers 8 (ks & 1) .. + 7 of key block ks / 2
+    f32x16 o;
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[r] = 0.0f;
 #pragma unroll
-    for (int ks = 0; ks < 10; ++ks) {
+    for (int ks = 0; ks < 2 * MB; ++ks) {
         float x[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) x[e] = sc[ks >> 1][8 * (ks & 1) + e];
-        fwa_h8 ph, pl;
-        fwa_split8(x, ph, pl);
-        const fwa_h8 vh = *reinterpret_cast<const fwa_h8 *>(Vh + li * VLD + ks * 16 + kg * 8);
-        const fwa_h8 vl = *reinterpret_cast<const fwa_h8 *>(Vl + li * VLD + ks * 16 + kg * 8);
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, o, 0, 0, 0);
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, o, 0, 0, 0);
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph, o, 0, 0, 0);
+        f16x8 ph, pl;
+        split8(x, ph, pl);
+        const f16x8 vh = *reinterpret_cast<const f16x8 *>(Vh + li * VLD + ks * 16 + kg * 8);
+        const f16x8 vl = *reinterpret_cast<const f16x8 *>(Vl + li * VLD + ks * 16 + kg * 8);
+        mfma_x3(o, vh, vl, ph, pl);
     }
-    if (qn < N) {
+    if (P::PAD ? qtok >= 0 : qn < N) {                                      // empty slots and padding tokens (cropped away) store nothing
         const float inv = 1.0f / sum;
         float *dst = out + (size_t)qtok * C + head * HD;
 #pragma unroll
         for (int g = 0; g < 4; ++g)                                         // registers 4 g .. 4 g + 3 = dims 8 g + 4 kg + 0..3
             *reinterpret_cast<float4 *>(dst + 8 * g + 4 * kg) = make_float4(o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv);
     }
+}
+
+// The fusion blocks' window: 12 x 12 on maps that are whole windows, q | k and v in two tensors, no bias; 336-byte V^T rows give
+// conflict-free 16-byte fragment reads.
+struct FusionWindow {
+    static constexpr int WS = 12, NP = 160, VLD = 168;
+    static constexpr bool PAD = false, BIAS = false;
+    const float *qk, *vv;
+    int C;
+    __device__ __forceinline__ const float *q(int tk) const { return qk + (size_t)tk * 2 * C; }
+    __device__ __forceinline__ const float *k(int tk) const { return qk + (size_t)tk * 2 * C + C; }
+    __device__ __forceinline__ const float *v(int tk) const { return vv + (size_t)tk * C; }
+    static __device__ __forceinline__ float ex(float x) { return __expf(x); }
+};
+__global__ __launch_bounds__(320) void fusion_window_attention_x3_kernel(const float *__restrict__ qk, const float *__restrict__ v, int H, int W,
+                                                                         int C, int shift, float scale, float *__restrict__ out)
+{
+    window_attention_x3(FusionWindow{qk, v, C}, H, W, C, shift, scale, out);
 }
 
 extern "C" int oryon_fusion_window_attention_f32(const float *qk, const float *v, int B, int H, int W, int C, int heads, int window, int shift,
@@ -610,152 +630,27 @@ extern "C" int oryon_fusion_window_attention_f32(const float *qk, const float *v
 }
 
 // The Swin guidance tower's shifted-window attention (torchvision shifted_window_attention, window 7, head dim 32) on the fp16 matrix pipe for
-// the fp32 evaluation - the same transposed scheme as fusion_window_attention_x3_kernel: one workgroup per (window, image, head), two waves of
-// 32 queries (49 tokens = 1.5 blocks), S^T = K Q^T + relative-position bias + shift mask, in-lane softmax, O^T = V^T P^T.  Padding tokens (the
-// map is padded to a multiple of 7 before the roll) carry q | k | v = the Linear's bias (`pad_qkv`) and take part as keys; their outputs are
-// cropped.  The VALU kernel above (one query per lane, fp32 fmaf) took 1.2-2.4 ms per call on the tower's 96 x 96 / 48 x 48 maps.
+// the fp32 evaluation - the same body: one workgroup per (window, image, head), two waves of 32 queries (49 tokens = 1.5 blocks), S^T = K Q^T +
+// relative-position bias (bias_t[head][key][query]) + shift mask, in-lane softmax, O^T = V^T P^T.  Padding tokens (the map is padded to a
+// multiple of 7 before the roll) carry q | k | v = the Linear's bias (`pad_qkv`) and take part as keys; their outputs are cropped.  The VALU
+// kernel above (one query per lane, fp32 fmaf) took 1.2-2.4 ms per call on the tower's 96 x 96 / 48 x 48 maps.
+struct SwinWindow {
+    static constexpr int WS = SWIN_WS, NP = 64, VLD = 72;
+    static constexpr bool PAD = true, BIAS = true;
+    const float *qkv, *pad_qkv, *bias_t;
+    int C;
+    __device__ __forceinline__ const float *row(int tk) const { return tk >= 0 ? qkv + (size_t)tk * 3 * C : pad_qkv; }
+    __device__ __forceinline__ const float *q(int tk) const { return row(tk); }
+    __device__ __forceinline__ const float *k(int tk) const { return row(tk) + C; }
+    __device__ __forceinline__ const float *v(int tk) const { return row(tk) + 2 * C; }
+    __device__ __forceinline__ const float *bias_col(int head, int qn) const { return bias_t + (size_t)head * SWIN_N * SWIN_N + qn; }
+    static __device__ __forceinline__ float ex(float x) { return expf(x); }
+};
 __global__ __launch_bounds__(128) void swin_window_attention_x3_kernel(const float *__restrict__ qkv, const float *__restrict__ pad_qkv,
                                                                       const float *__restrict__ bias_t, int H, int W, int C, int shift,
                                                                       float *__restrict__ out)
 {
-    constexpr int WS = SWIN_WS, N = SWIN_N, NP = 64, HD = SWIN_HD;
-    constexpr int VLD = 72;                                   // halves per V^T row (144 bytes)
-    __shared__ __attribute__((aligned(16))) _Float16 Vh[HD * VLD];
-    __shared__ __attribute__((aligned(16))) _Float16 Vl[HD * VLD];
-    __shared__ int toks[NP];                                  // >= 0: token, -2: padding token, -1: no token (slots 49..63)
-    __shared__ int labs[NP];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li = lane & 31, kg = lane >> 5;
-    const int head = blockIdx.z, b = blockIdx.y;
-    const int Hp = (H + WS - 1) / WS * WS, Wp = (W + WS - 1) / WS * WS;
-    const int nwx = Wp / WS, wy = blockIdx.x / nwx, wx = blockIdx.x % nwx;
-    if (t < NP) {
-        int tk = -1, lab = -1;
-        if (t < N) {
-            const int py = wy * WS + t / WS, px = wx * WS + t % WS;                          // rolled, padded frame
-            const int sy = (py + shift) % Hp, sx = (px + shift) % Wp;
-            tk = (sy < H && sx < W) ? (b * H + sy) * W + sx : -2;
-            lab = 0;
-            if (shift > 0) {
-                const int by = py < Hp - WS ? 0 : (py < Hp - shift ? 1 : 2);
-                const int bx = px < Wp - WS ? 0 : (px < Wp - shift ? 1 : 2);
-                lab = by * 3 + bx;
-            }
-        }
-        toks[t] = tk;
-        labs[t] = lab;
-    }
-    for (int i = t; i < HD * (NP - N); i += 128) {                                          // zero the unused key slots of V^T
-        const int d = i / (NP - N), sig = fwa_slot(N + i % (NP - N));
-        Vh[d * VLD + sig] = (_Float16)0.0f;
-        Vl[d * VLD + sig] = (_Float16)0.0f;
-    }
-    __syncthreads();
-    auto row = [&](int tk) { return tk >= 0 ? qkv + (size_t)tk * 3 * C : pad_qkv; };
-    for (int i = t; i < N * 8; i += 128) {
-        const int j = i >> 3, dq = i & 7;
-        const float4 x = *reinterpret_cast<const float4 *>(row(toks[j]) + 2 * C + head * HD + dq * 4);
-        const int sig = fwa_slot(j);
-        const float xv[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const _Float16 h = (_Float16)xv[c];
-            Vh[(dq * 4 + c) * VLD + sig] = h;
-            Vl[(dq * 4 + c) * VLD + sig] = (_Float16)(xv[c] - (float)h);
-        }
-    }
-    const int qn = wave * 32 + li;
-    const int qtok = toks[qn];
-    const float scale = 0.17677669529663687f;                                                // 32^-0.5
-    fwa_h8 qh[2], ql[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        float x[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = 0.0f;
-        if (qtok != -1) {
-            const float *src = row(qtok) + head * HD + 16 * s + 8 * kg;
-            const float4 a0 = *reinterpret_cast<const float4 *>(src), a1 = *reinterpret_cast<const float4 *>(src + 4);
-            x[0] = a0.x * scale; x[1] = a0.y * scale; x[2] = a0.z * scale; x[3] = a0.w * scale;
-            x[4] = a1.x * scale; x[5] = a1.y * scale; x[6] = a1.z * scale; x[7] = a1.w * scale;
-        }
-        fwa_split8(x, qh[s], ql[s]);
-    }
-    fwa_acc sc[2];
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sc[mb][r] = 0.0f;
-        const int ktok = toks[mb * 32 + li];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            float x[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = 0.0f;
-            if (ktok != -1) {
-                const float *src = row(ktok) + C + head * HD + 16 * s + 8 * kg;
-                const float4 a0 = *reinterpret_cast<const float4 *>(src), a1 = *reinterpret_cast<const float4 *>(src + 4);
-                x[0] = a0.x; x[1] = a0.y; x[2] = a0.z; x[3] = a0.w; x[4] = a1.x; x[5] = a1.y; x[6] = a1.z; x[7] = a1.w;
-            }
-            fwa_h8 kh, kl;
-            fwa_split8(x, kh, kl);
-            sc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[s], sc[mb], 0, 0, 0);
-            sc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[s], sc[mb], 0, 0, 0);
-            sc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[s], sc[mb], 0, 0, 0);
-        }
-    }
-    // relative-position bias (bias_t[head][key][query]: 32 consecutive queries per load), shift mask, softmax of the lane's query
-    const int qlab = labs[qn];
-    const float *bt = bias_t + (size_t)head * N * N + (qn < N ? qn : 0);
-    float m = -3.0e38f;
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int j = 32 * mb + 8 * (r >> 2) + 4 * kg + (r & 3);
-            const int klab = labs[j];
-            float s = -3.0e38f;
-            if (klab >= 0) {
-                s = sc[mb][r] + bt[j * N];
-                if (klab != qlab) s -= 100.0f;
-            }
-            sc[mb][r] = s;
-            m = fmaxf(m, s);
-        }
-    m = fmaxf(m, __shfl_xor(m, 32));
-    float sum = 0.0f;
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float p = sc[mb][r] > -1.0e38f ? expf(sc[mb][r] - m) : 0.0f;
-            sc[mb][r] = p;
-            sum += p;
-        }
-    sum += __shfl_xor(sum, 32);
-    __syncthreads();
-    fwa_acc o;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] = 0.0f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        float x[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = sc[ks >> 1][8 * (ks & 1) + e];
-        fwa_h8 ph, pl;
-        fwa_split8(x, ph, pl);
-        const fwa_h8 vh = *reinterpret_cast<const fwa_h8 *>(Vh + li * VLD + ks * 16 + kg * 8);
-        const fwa_h8 vl = *reinterpret_cast<const fwa_h8 *>(Vl + li * VLD + ks * 16 + kg * 8);
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, o, 0, 0, 0);
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, o, 0, 0, 0);
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph, o, 0, 0, 0);
-    }
-    if (qtok >= 0) {                                                                         // padding tokens are cropped away
-        const float inv = 1.0f / sum;
-        float *dst = out + (size_t)qtok * C + head * HD;
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4 *>(dst + 8 * g + 4 * kg) = make_float4(o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv);
-    }
+    window_attention_x3(SwinWindow{qkv, pad_qkv, bias_t, C}, H, W, C, shift, 0.17677669529663687f, out);      // 32^-0.5
 }
 
 extern "C" int oryon_swin_window_attention_f32(const float *qkv, const float *pad_qkv, const float *bias_t, int B, int H, int W, int C,

@@ -2,8 +2,8 @@
 // cat guidance -> (conv3x3 - GroupNorm - ReLU) x 2, models/decoder.py:9-42), the two guidance projections (conv3x3 + ReLU, :66-72) and
 // the 3x3 head (:80), fp32 tensors in and out.
 //
-// Arithmetic: every convolution is an implicit GEMM on the fp16 matrix pipe with error-compensated operands, like the towers' linears
-// (gemm_x3.hip): x = x_hi + x_lo, w = w_hi + w_lo (two float16 each), product = x_hi*w_hi + x_hi*w_lo + x_lo*w_hi accumulated in fp32 by
+// Arithmetic: every convolution is an implicit GEMM on the fp16 matrix pipe with error-compensated operands (the fp16x3 scheme and its
+// split: x3.h): x = x_hi + x_lo, w = w_hi + w_lo (two float16 each), product = x_hi*w_hi + x_hi*w_lo + x_lo*w_hi accumulated in fp32 by
 // three v_mfma_f32_32x32x16_f16 - ~2^-22 relative per product, fp32-grade results (the G5 golden of the imported reference holds to
 // 1e-4, tests/test_gpu_decoder.py) at about three times the rate of the fp32-input MFMAs the library convolutions use.
 //
@@ -21,13 +21,12 @@
 // 9 taps x 2 k-steps, its B fragments (pre-packed hi / lo weight images, fragment order, L2-resident) come straight from global memory.
 // ~52 KB of LDS per workgroup: three workgroups per CU, the slab loads of one overlap the MFMAs of the others.
 #include "common.h"
+#include "x3.h"
 #include <hip/hip_fp16.h>
 
 namespace oryon {
 
-typedef _Float16 dh8 __attribute__((ext_vector_type(8)));
 typedef _Float16 dh4 __attribute__((ext_vector_type(4)));
-typedef float dacc16 __attribute__((ext_vector_type(16)));
 
 constexpr int DEC_HALO = 18;                     // 16 + 2
 constexpr int DEC_PIX = DEC_HALO * DEC_HALO;     // 324 halo pixels per tile
@@ -38,19 +37,13 @@ constexpr int DEC_RING = 2;                      // steps of B fragments in flig
 struct DecConv {
     const float *in;          // NHWC [n, H, W, in_cstride] (channels in_coff ..) or NCHW [n, cin, H, W]
     const float *affine;      // [n, cin, 2] (a, b): the loader applies relu(a x + b) - the previous layer's GroupNorm + ReLU - or NULL
-    const dh8 *wimg;          // packed weights, see dec_pack_conv3x3_kernel
+    const f16x8 *wimg;        // packed weights, see dec_pack_conv3x3_kernel
     const float *bias;        // [cout] or NULL
     float *out;               // NHWC [n, H, W, out_cstride], channels out_coff .. out_coff + cout - 1
     float *stats;             // [n, tiles, cout / 16, 2] partial (sum, sum of squares) of the raw outputs, or NULL
     int H, W, cin, in_cstride, in_coff, out_cstride, out_coff, cout, relu;
     unsigned *range_flag;     // per-device flag word (common.h: x3_range_flag), or NULL
 };
-
-static __device__ __forceinline__ void split_h(float v, _Float16 &hi, _Float16 &lo)
-{
-    hi = (_Float16)v;
-    lo = (_Float16)(v - (float)hi);
-}
 
 // Weight image of a 3x3 convolution (torch layout w[cout, cin, 3, 3]): fragment ((((slab * 9 + tap) * 2 + kstep) * NB + nb) * 2 + part),
 // 64 lanes x 8 halves each: lane l holds output channel nb * 32 + (l & 31), input channels slab * 32 + kstep * 16 + (l >> 5) * 8 + 0..7 -
@@ -69,7 +62,7 @@ __global__ void dec_pack_conv3x3_kernel(const float *__restrict__ w, int cout, i
     float v = 0.0f;
     if (n < cout && c < cin) v = w[((size_t)n * cin + c) * T + tap];
     _Float16 hi, lo;
-    split_h(v, hi, lo);
+    split1(v, hi, lo);
     img[idx] = part ? lo : hi;
 }
 
@@ -88,7 +81,7 @@ __global__ void dec_pack_upconv_kernel(const float *__restrict__ w, int cin, int
     float v = 0.0f;
     if (co < cout) v = w[((size_t)c * cout + co) * 4 + dydx];
     _Float16 hi, lo;
-    split_h(v, hi, lo);
+    split1(v, hi, lo);
     img[idx] = part ? lo : hi;
 }
 
@@ -114,8 +107,8 @@ __global__ __launch_bounds__(256, (WREG ? 2 : (NB == 1 ? 3 : 2))) void dec_conv3
     // global memory (L2-resident) they need ~0.5 us; one step ahead - what the compiler schedules by itself - left every step waiting
     // for its weights (decoder3's convolutions: 0.49 ms, MFMA pipe 20 % busy).
     constexpr int RING = DEC_RING;
-    const dh8 *wf0 = a.wimg + lane;
-    dh8 wb[WREG ? 18 : 1][2];
+    const f16x8 *wf0 = a.wimg + lane;
+    f16x8 wb[WREG ? 18 : 1][2];
     if constexpr (WREG) {
 #pragma unroll
         for (int j = 0; j < 18; ++j) {
@@ -127,14 +120,14 @@ __global__ __launch_bounds__(256, (WREG ? 2 : (NB == 1 ? 3 : 2))) void dec_conv3
     for (int item = blockIdx.x; item < total; item += gridDim.x) {
     const int img = item / tiles, tile = item % tiles;
     const int y0 = (tile / tiles_x) * 16, x0 = (tile % tiles_x) * 16;
-    dacc16 acc[2][NB];
+    f32x16 acc[2][NB];
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.0f;
-    dh8 rb[WREG ? 1 : RING][NB][2];
+    f16x8 rb[WREG ? 1 : RING][NB][2];
     if constexpr (!WREG) {
 #pragma unroll
         for (int j = 0; j < RING; ++j)
@@ -183,10 +176,10 @@ __global__ __launch_bounds__(256, (WREG ? 2 : (NB == 1 ? 3 : 2))) void dec_conv3
                 }
                 dh4 hi, lo;
                 _Float16 h, l;
-                split_h(x.x, h, l); hi[0] = h; lo[0] = l;
-                split_h(x.y, h, l); hi[1] = h; lo[1] = l;
-                split_h(x.z, h, l); hi[2] = h; lo[2] = l;
-                split_h(x.w, h, l); hi[3] = h; lo[3] = l;
+                split1(x.x, h, l); hi[0] = h; lo[0] = l;
+                split1(x.y, h, l); hi[1] = h; lo[1] = l;
+                split1(x.z, h, l); hi[2] = h; lo[2] = l;
+                split1(x.w, h, l); hi[3] = h; lo[3] = l;
                 *reinterpret_cast<dh4 *>(lds + pix * DEC_PSTRIDE + cq * 8) = hi;
                 *reinterpret_cast<dh4 *>(lds + DEC_PLANE + pix * DEC_PSTRIDE + cq * 8) = lo;
             }
@@ -211,25 +204,25 @@ __global__ __launch_bounds__(256, (WREG ? 2 : (NB == 1 ? 3 : 2))) void dec_conv3
                     if (e >= 32 * DEC_PIX) continue;
                     const int c = e / DEC_PIX, pix = e % DEC_PIX;
                     _Float16 h, l;
-                    split_h(v[j], h, l);
+                    split1(v[j], h, l);
                     *reinterpret_cast<_Float16 *>(lds + pix * DEC_PSTRIDE + c * 2) = h;
                     *reinterpret_cast<_Float16 *>(lds + DEC_PLANE + pix * DEC_PSTRIDE + c * 2) = l;
                 }
             }
         }
         __syncthreads();
-        const dh8 *wf = wf0 + (size_t)(s * 18 + RING) * (NB * 2 * 64);          // the fragments RING steps ahead of this slab's step 0
+        const f16x8 *wf = wf0 + (size_t)(s * 18 + RING) * (NB * 2 * 64);        // the fragments RING steps ahead of this slab's step 0
 #pragma unroll
         for (int step = 0; step < 18; ++step) {
             const int tap = step >> 1, ks = step & 1, slot = step % RING;
             const int toff = ((tap / 3) * DEC_HALO + (tap % 3)) * DEC_PSTRIDE;
             // the three products of an accumulator are issued 2 NB MFMAs apart (every accumulator's chain is dependent: back to back
             // they wait for each other's passes)
-            dh8 ah[2], al[2];
+            f16x8 ah[2], al[2];
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb) {
-                ah[mb] = *reinterpret_cast<const dh8 *>(lds + a_off[mb] + toff + ks * 32);
-                al[mb] = *reinterpret_cast<const dh8 *>(lds + DEC_PLANE + a_off[mb] + toff + ks * 32);
+                ah[mb] = *reinterpret_cast<const f16x8 *>(lds + a_off[mb] + toff + ks * 32);
+                al[mb] = *reinterpret_cast<const f16x8 *>(lds + DEC_PLANE + a_off[mb] + toff + ks * 32);
             }
 #pragma unroll
             for (int part = 0; part < 3; ++part)
@@ -237,8 +230,8 @@ __global__ __launch_bounds__(256, (WREG ? 2 : (NB == 1 ? 3 : 2))) void dec_conv3
                 for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) {
-                        const dh8 bh = WREG ? wb[WREG ? step : 0][0] : rb[WREG ? 0 : slot][nb][0];
-                        const dh8 bl = WREG ? wb[WREG ? step : 0][1] : rb[WREG ? 0 : slot][nb][1];
+                        const f16x8 bh = WREG ? wb[WREG ? step : 0][0] : rb[WREG ? 0 : slot][nb][0];
+                        const f16x8 bl = WREG ? wb[WREG ? step : 0][1] : rb[WREG ? 0 : slot][nb][1];
                         acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(part == 0 ? al[mb] : ah[mb], part == 1 ? bl : bh, acc[mb][nb], 0, 0, 0);
                     }
             if constexpr (WREG) continue;
@@ -368,7 +361,7 @@ __global__ __launch_bounds__(64) void dec_gn_affine_kernel(const float *__restri
 // 32 channels); each accumulator row is one 128-byte run of the NHWC output.
 template <int KS, bool IN_NCHW, bool IN_GN>
 __global__ __launch_bounds__(256) void dec_upconv_kernel(const float *__restrict__ in, const float *__restrict__ affine, int Hin, int Win,
-                                                         int in_cstride, const dh8 *__restrict__ wimg, const float *__restrict__ bias,
+                                                         int in_cstride, const f16x8 *__restrict__ wimg, const float *__restrict__ bias,
                                                          float *__restrict__ out, int out_cstride, int cout, int nbp, unsigned *__restrict__ range_flag)
 {
     constexpr int CIN = KS * 16;
@@ -377,7 +370,7 @@ __global__ __launch_bounds__(256) void dec_upconv_kernel(const float *__restrict
     const int p0 = (blockIdx.x * 4 + wave) * 32;
     if (p0 >= Hin * Win) return;
     const int p = p0 + li;
-    dh8 ah[KS], al[KS];
+    f16x8 ah[KS], al[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         float x[8];
@@ -402,7 +395,7 @@ __global__ __launch_bounds__(256) void dec_upconv_kernel(const float *__restrict
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             _Float16 h, l;
-            split_h(x[e], h, l);
+            split1(x[e], h, l);
             ah[ks][e] = h;
             al[ks][e] = l;
         }
@@ -410,13 +403,13 @@ __global__ __launch_bounds__(256) void dec_upconv_kernel(const float *__restrict
     const int Hout = 2 * Hin, Wout = 2 * Win;
     unsigned x3m = 0u;
     for (int nb = 0; nb < 4 * nbp; ++nb) {
-        dacc16 acc;
+        f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-        const dh8 *wf = wimg + (size_t)nb * KS * 2 * 64 + lane;
+        const f16x8 *wf = wimg + (size_t)nb * KS * 2 * 64 + lane;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const dh8 bh = wf[(ks * 2 + 0) * 64], bl = wf[(ks * 2 + 1) * 64];
+            const f16x8 bh = wf[(ks * 2 + 0) * 64], bl = wf[(ks * 2 + 1) * 64];
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ks], bh, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ks], bl, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ks], bh, acc, 0, 0, 0);
@@ -492,7 +485,7 @@ __global__ __launch_bounds__(256) void dec_final_kernel(const float *__restrict_
 //     from global memory one tap ahead (all nine waves ask for the same fragments: L1 hits).  NHWC in, NHWC out.
 struct FusConv {
     const float *in;          // [n, 24, 24, cin]
-    const dh8 *wimg;          // fragments ((((slab * T + tap) * 2 + kstep) * (cout / 32) + nb) * 2 + part)
+    const f16x8 *wimg;        // fragments ((((slab * T + tap) * 2 + kstep) * (cout / 32) + nb) * 2 + part)
     const float *bias;        // [cout] or NULL
     float *out;               // [n, 24, 24, cout]
     int cin, cout, relu;
@@ -509,7 +502,7 @@ __global__ __launch_bounds__(576) void fus_conv24_kernel(const FusConv a)
     const int groups = a.cout / 64, nbt = a.cout / 32;
     const int img = blockIdx.x / groups, nb0 = (blockIdx.x % groups) * 2;
     const int slabs = (a.cin + 31) / 32;
-    dacc16 acc[2][2];
+    f32x16 acc[2][2];
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -522,7 +515,7 @@ __global__ __launch_bounds__(576) void fus_conv24_kernel(const FusConv a)
         const int p = (wave * 2 + mb) * 32 + li;
         a_off[mb] = ((p / S) * HWP + p % S) * DEC_PSTRIDE + kg * 16;        // halo coordinates of the pixel at tap (0, 0)
     }
-    const dh8 *wf = a.wimg + lane;
+    const f16x8 *wf = a.wimg + lane;
     auto frag = [&](int step, int nb, int part) { return wf[(((size_t)step * nbt + nb0 + nb) * 2 + part) * 64]; };
     for (int s = 0; s < slabs; ++s) {
         __syncthreads();
@@ -547,17 +540,17 @@ __global__ __launch_bounds__(576) void fus_conv24_kernel(const FusConv a)
                     if (p0 + j >= PASSES || pix >= HP) continue;
                     dh4 hi, lo;
                     _Float16 h, l;
-                    split_h(v[j].x, h, l); hi[0] = h; lo[0] = l;
-                    split_h(v[j].y, h, l); hi[1] = h; lo[1] = l;
-                    split_h(v[j].z, h, l); hi[2] = h; lo[2] = l;
-                    split_h(v[j].w, h, l); hi[3] = h; lo[3] = l;
+                    split1(v[j].x, h, l); hi[0] = h; lo[0] = l;
+                    split1(v[j].y, h, l); hi[1] = h; lo[1] = l;
+                    split1(v[j].z, h, l); hi[2] = h; lo[2] = l;
+                    split1(v[j].w, h, l); hi[3] = h; lo[3] = l;
                     *reinterpret_cast<dh4 *>(flds + pix * DEC_PSTRIDE + cq * 8) = hi;
                     *reinterpret_cast<dh4 *>(flds + PLANE + pix * DEC_PSTRIDE + cq * 8) = lo;
                 }
             }
         }
         __syncthreads();
-        dh8 cur[2][2][2], nxt[2][2][2];                        // [k-step][N block][hi | lo] of one tap
+        f16x8 cur[2][2][2], nxt[2][2][2];                      // [k-step][N block][hi | lo] of one tap
         const int step0 = s * T * 2;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
@@ -579,11 +572,11 @@ __global__ __launch_bounds__(576) void fus_conv24_kernel(const FusConv a)
             const int toff = ((tap / KS) * HWP + tap % KS) * DEC_PSTRIDE;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                dh8 ah[2], al[2];
+                f16x8 ah[2], al[2];
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb) {
-                    ah[mb] = *reinterpret_cast<const dh8 *>(flds + a_off[mb] + toff + ks * 32);
-                    al[mb] = *reinterpret_cast<const dh8 *>(flds + PLANE + a_off[mb] + toff + ks * 32);
+                    ah[mb] = *reinterpret_cast<const f16x8 *>(flds + a_off[mb] + toff + ks * 32);
+                    al[mb] = *reinterpret_cast<const f16x8 *>(flds + PLANE + a_off[mb] + toff + ks * 32);
                 }
 #pragma unroll
                 for (int part = 0; part < 3; ++part)
@@ -631,10 +624,10 @@ struct oryon_decoder {
     int device = 0;
     char *blob = nullptr;                   // one allocation: packed weight images + fp32 vectors
     // weight images
-    const dh8 *gp_img[2] = {nullptr, nullptr};
-    const dh8 *up_img[3] = {nullptr, nullptr, nullptr};
-    const dh8 *c1_img[3] = {nullptr, nullptr, nullptr};
-    const dh8 *c2_img[3] = {nullptr, nullptr, nullptr};
+    const f16x8 *gp_img[2] = {nullptr, nullptr};
+    const f16x8 *up_img[3] = {nullptr, nullptr, nullptr};
+    const f16x8 *c1_img[3] = {nullptr, nullptr, nullptr};
+    const f16x8 *c2_img[3] = {nullptr, nullptr, nullptr};
     // fp32 vectors (copies: the handle does not keep the caller's tensors alive)
     const float *gp_b[2], *up_b[3], *n1_g[3], *n1_b[3], *n2_g[3], *n2_b[3], *head_w, *head_b;
 };
@@ -715,7 +708,7 @@ int oryon_decoder_create(const oryon_decoder_weights_t *w, oryon_decoder_t **out
         const int64_t total = conv_img_halves(cin, NB);
         hipLaunchKernelGGL(dec_pack_conv3x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, cout, cin, NB,
                            reinterpret_cast<_Float16 *>(d->blob + o), total);
-        return reinterpret_cast<const dh8 *>(d->blob + o);
+        return reinterpret_cast<const f16x8 *>(d->blob + o);
     };
     for (int i = 0; i < 2; ++i) d->gp_img[i] = pack_conv(w->gp_w[i], D_G[i], D_GIN[i], o_gp[i]);
     float *vec = reinterpret_cast<float *>(d->blob + o_vec);
@@ -732,7 +725,7 @@ int oryon_decoder_create(const oryon_decoder_weights_t *w, oryon_decoder_t **out
         const int64_t total = up_img_halves(cin, nbp);
         hipLaunchKernelGGL(dec_pack_upconv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w->up_w[i], cin, cup, nbp,
                            reinterpret_cast<_Float16 *>(d->blob + o_up[i]), total);
-        d->up_img[i] = reinterpret_cast<const dh8 *>(d->blob + o_up[i]);
+        d->up_img[i] = reinterpret_cast<const f16x8 *>(d->blob + o_up[i]);
         d->up_b[i] = keep(w->up_b[i], cup);
         d->c1_img[i] = pack_conv(w->c1_w[i], D_OUT[i], D_CAT[i], o_c1[i]);
         d->c2_img[i] = pack_conv(w->c2_w[i], D_OUT[i], D_OUT[i], o_c2[i]);
@@ -893,7 +886,7 @@ int oryon_conv24_f16x3(const float *x, int n, int cin, const void *image, const 
     FusConv a{};
     a.range_flag = x3_range_flag(as_stream(stream));
     if (!a.range_flag) return ORYON_ERR_HIP;
-    a.in = x; a.wimg = reinterpret_cast<const dh8 *>(image); a.bias = bias; a.out = y; a.cin = cin; a.cout = cout; a.relu = relu ? 1 : 0;
+    a.in = x; a.wimg = reinterpret_cast<const f16x8 *>(image); a.bias = bias; a.out = y; a.cin = cin; a.cout = cout; a.relu = relu ? 1 : 0;
     const dim3 grid((unsigned)(n * (cout / 64)));
     if (ksize == 3) {
         constexpr int dyn = 2 * 26 * 26 * DEC_PSTRIDE;

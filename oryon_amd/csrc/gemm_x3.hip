@@ -1,11 +1,10 @@
 // B4: error-compensated fp16x3 linear layer for the frozen fp32 towers of Oryon.forward (net.py:142-167, models/vlm.py:43-61):
 //     C[M,N] = act(A[M,K] * W[N,K]^T + bias[N])      A, C fp32;  W given pre-split into two fp16 matrices W = Whi + Wlo
-// Every fp32 operand is split x = hi + lo (hi = half(x), lo = half(x - hi): 22 significant bits) and the product is accumulated in
-// fp32 as  Ahi*Whi + Ahi*Wlo + Alo*Whi  - three v_mfma_f32_32x32x16_f16 (16 k per 32 cycles) instead of eight fp32-input MFMAs
-// (2 k per 64 cycles); the dropped Alo*Wlo term is ~2^-22 |a||w|, the size of fp32's own accumulation error.  The split of the
-// activations happens on the way from HBM to LDS (the round-1 experiment split them with three torch passes per linear and lost
-// the gain to that traffic); weights are split once (oryon_split_f16x3) and cached by the caller.  Optional fused QuickGELU
-// (x * sigmoid(1.702 x), CLIP's activation) in the epilogue.
+// Every fp32 operand is split x = hi + lo and the product is accumulated in fp32 as  Alo*Whi + Ahi*Wlo + Ahi*Whi  (the fp16x3 scheme,
+// its split and its range rule: x3.h) - three v_mfma_f32_32x32x16_f16 (16 k per 32 cycles) instead of eight fp32-input MFMAs
+// (2 k per 64 cycles).  The split of the activations happens on the way from HBM to LDS (the round-1 experiment split them with
+// three torch passes per linear and lost the gain to that traffic); weights are split once (oryon_split_f16x3) and cached by the
+// caller.  Optional fused QuickGELU (x * sigmoid(1.702 x), CLIP's activation) in the epilogue.
 //
 // Two kernels: the persistent 256 x 256 x 32 stream kernel below (the one that runs; K >= 64), and a small-tile kernel for K = 32 and
 // as a cross-check (ORYON_GEMM_X3_VARIANT=1): tile 128 x 256 x 32, 4 waves (2 x 2, 64 x 128 each = eight 32x32 accumulators),
@@ -13,44 +12,17 @@
 // flight under the current tile's 48 MFMAs per wave.  Both accumulate every output in the same order (k ascending, per k-step
 // lo*hi, hi*lo, hi*hi), so their results are bit-identical.
 // Workgroups are dealt to the 8 XCDs in 8 x 8 super-tiles so that an XCD's concurrent workgroups share their A and W panels in its L2.
-// Range: magnitudes must stay below 65504 (fp16 range) or the split overflows to inf without a diagnostic; the random-init towers of
-// the tests have O(10) activations, released checkpoints may not - oryon_amd.backbone.enable_fp16x3(True, guard=True) validates every
-// call on the host first.  Precision: an operand below 2^-3 has its low half in float16's subnormal range (absolute split error
-// <= 2^-25 instead of the relative 2^-22).
+// Range (x3.h): the random-init towers of the tests have O(10) activations, released checkpoints may not -
+// oryon_amd.backbone.enable_fp16x3(True, guard=True) validates every call on the host first.
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 #include "common.h"
+#include "x3.h"
 
 namespace oryon {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f16acc __attribute__((ext_vector_type(16)));
-
 constexpr int GX_BM = 128, GX_BN = 256, GX_BK = 32;     // 4 waves as 2 (M) x 2 (N): 64 x 128 per wave = eight 32x32 accumulators
 constexpr int GX_LD = GX_BK + 8;                 // halves per LDS row (80 bytes)
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-// x = hi + lo with two packed conversions per pair (v_cvt_pk_f16_f32 on gfx950, round-to-nearest-even) and - round 6 - the residuals
-// x - float(hi) as one v_fma_mix_f32 each (hi's half read as the f16 source of an fp32 fma: the bits of the subtraction it replaces,
-// tools/probe_cvt_pk_f16.hip): four instructions per pair instead of six.  VALU and MFMA do not overlap on this part.
-__device__ __forceinline__ void split2(float x, float y, unsigned &hi, unsigned &lo)
-{
-    const f32x2 a = {x, y};
-    const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(a, f16x2));
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hb), "v"(x));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hb), "v"(y));
-    const f32x2 lv = {l0, l1};
-    hi = hb;
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(lv, f16x2));
-}
-__device__ __forceinline__ void split4(const float4 v, uint2 &hi, uint2 &lo)
-{
-    split2(v.x, v.y, hi.x, lo.x);
-    split2(v.z, v.w, hi.y, lo.y);
-}
 
 template <int ACT>
 __global__ __launch_bounds__(256, 2) void linear_f16x3_kernel(const float *__restrict__ A, int M, int K, const __half *__restrict__ Whi,
@@ -104,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void linear_f16x3_kernel(const float *__res
         }
     };
 
-    f16acc acc[2][4];
+    f32x16 acc[2][4];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -121,31 +93,26 @@ __global__ __launch_bounds__(256, 2) void linear_f16x3_kernel(const float *__res
         if (kt + 1 < nk) gload((kt + 1) * GX_BK);
 #pragma unroll
         for (int ks = 0; ks < GX_BK / 16; ++ks) {
-            h8 ah[2], al[2], wh[4], wl[4];
+            f16x8 ah[2], al[2], wh[4], wl[4];
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 const int off = (wm * 64 + a * 32 + l31) * GX_LD + ks * 16 + kh * 8;
-                ah[a] = *reinterpret_cast<const h8 *>(sAh + off);
-                al[a] = *reinterpret_cast<const h8 *>(sAl + off);
+                ah[a] = *reinterpret_cast<const f16x8 *>(sAh + off);
+                al[a] = *reinterpret_cast<const f16x8 *>(sAl + off);
             }
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const int off = (wn * 128 + b * 32 + l31) * GX_LD + ks * 16 + kh * 8;
-                wh[b] = *reinterpret_cast<const h8 *>(sWh + off);
-                wl[b] = *reinterpret_cast<const h8 *>(sWl + off);
+                wh[b] = *reinterpret_cast<const f16x8 *>(sWh + off);
+                wl[b] = *reinterpret_cast<const f16x8 *>(sWl + off);
             }
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    // smallest terms first
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[a], wh[b], acc[a][b], 0, 0, 0);
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[a], wl[b], acc[a][b], 0, 0, 0);
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[a], wh[b], acc[a][b], 0, 0, 0);
-                }
+                for (int b = 0; b < 4; ++b) mfma_x3(acc[a][b], ah[a], al[a], wh[b], wl[b]);
         }
     }
-    // epilogue: lane owns column l31 of each 32x32 block and rows (r & 3) + 8 (r >> 2) + 4 kh
+    // epilogue: lane owns column l31 of each 32x32 block and rows crow(r, kh)
     unsigned mag = 0u;                                   // range flag (common.h): largest magnitude among the raw accumulators of live rows
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
@@ -155,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void linear_f16x3_kernel(const float *__res
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int m = m0 + wm * 64 + a * 32 + crow(r, kh);
                 float v = acc[a][b][r] + bv;
                 if (m < M) mag = max(mag, x3_mag(v));             // pre-activation: what a later split would see is bounded by it
                 if (ACT == 1) v = v * (1.0f / (1.0f + __expf(-1.702f * v)));
@@ -192,7 +159,7 @@ constexpr int G2_STAGE = 2 * G2_A_BYTES + 2 * G2_W_BYTES;                       
 // Measured (M = 73856, CLIP ViT-L shapes): 1.0-1.13 PFLOP/s on the fp16 pipe (small-tile kernel: 0.55-0.6), socket power at the 1.4 kW cap with
 // sclk throttled to ~1.87 GHz: the kernel is power-limited, not stall-limited (a bare MFMA loop sustains ~1.7 PFLOP/s at the same cap,
 // tools/probe_mfma_peak.hip; LDS reads at twice this kernel's rate cost that loop nothing).
-struct G3Frags { h8 ah[2], wh[4]; };           // the hi halves are double-buffered; the lo halves (al, wl) are re-read in place
+struct G3Frags { f16x8 ah[2], wh[4]; };        // the hi halves are double-buffered; the lo halves (al, wl) are re-read in place
 
 // WEX ("weights exact"): every weight is exactly representable in fp16 (W_lo would be all zeros - what `clip.load` leaves in the
 // reference's CLIPEncoder, models/vlm.py:19-22: an fp16 checkpoint widened to fp32): the a_hi * w_lo term, its fragments and its DMA
@@ -286,16 +253,16 @@ __global__ __launch_bounds__(512, 2) void linear_f16x3_stream_kernel(const float
     // fragment offsets: row l31 of a 32-row block, slot (2 ks + kh) ^ ((row >> 2) & 3); blocks are 2048 bytes apart (same swizzle)
     const unsigned f_swz = (unsigned)((kh ^ ((l31 >> 2) & 3)) << 4);
     const unsigned fa0 = (unsigned)((wm * 64 + l31) * 64) + f_swz, fw0 = (unsigned)((wn * 128 + l31) * 64) + f_swz;
-    f16acc acc[2][4];
+    f32x16 acc[2][4];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 4; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-    h8 al[2], wl[4];
+    f16x8 al[2], wl[4];
 #define G3_MFMA(X, Y, a, b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(X, Y, acc[a][b], 0, 0, 0)
-#define G3_RD(p) (*reinterpret_cast<const h8 *>(p))
+#define G3_RD(p) (*reinterpret_cast<const f16x8 *>(p))
 #define G3_SB __builtin_amdgcn_sched_barrier(0)            // the compiler otherwise sinks every read to just before its first use
     // One k-step: 24 MFMAs on (cur.ah, al) x (cur.wh, wl), term-major; between them the NEXT k-step's fragments are requested from
     // `nbase` (k-step `nks`): the hi halves into `nxt`, al right after the last MFMA that reads it (end of term 1), wl likewise (end

@@ -1,45 +1,16 @@
 // Device building blocks of the fp16x3 PointDSC encoder kernels (pdsc_encoder.hip): one definition each of what pdsc_mlp3_x3_kernel,
 // pdsc_pcn_qkv_x3_kernel, pdsc_att_chain_x3_kernel and pdsc_attention_x3_img8_kernel share.  Everything is inlined into its kernel;
 // the order of the products (hi*hi, hi*lo, lo*hi, accumulators alternating), the sched_barriers and the layouts are part of each block.
+// The hi / lo split, the vector types and crow() are the fp16x3 family's: x3.h.
 #pragma once
 #include "common.h"
 #include "pdsc.h"
+#include "x3.h"
 
 namespace oryon {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 xhalf8 __attribute__((ext_vector_type(8)));
-typedef float xf32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 xf16x2 __attribute__((ext_vector_type(2)));
-
 // the attention kernels' tile: 128 queries per workgroup, key tiles of 64
 constexpr int ATT_Q = 128, ATT_KT = 64;
-
-// row index inside a 32x32 MFMA C/D block held by (register r, lane half hi)
-__device__ __forceinline__ int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-// x = hi + lo with hi = half(x), lo = half(x - hi): 22 significant bits together (see pdsc_attention_x3_kernel)
-__device__ __forceinline__ void split_half(float x, _Float16 &hi, _Float16 &lo)
-{
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
-
-// Two values at a time: packed conversions (v_cvt_pk_f16_f32 on gfx950, round-to-nearest-even) - same results as split_half.
-// Round 6: the residuals x - float(hi) come from v_fma_mix_f32 (hi's half read as the f16 source of an fp32 fma: float(hi) * -1 + x, one
-// rounding of an exactly representable difference - the bits of the subtraction it replaces), four instructions per pair instead of six.
-__device__ __forceinline__ void split_pair(float a, float b, unsigned &hi, unsigned &lo)
-{
-    const xf32x2 v = {a, b};
-    const xf16x2 h = __builtin_convertvector(v, xf16x2);
-    const unsigned hb = __builtin_bit_cast(unsigned, h);
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hb), "v"(a));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hb), "v"(b));
-    const xf32x2 lv = {l0, l1};
-    hi = hb;
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(lv, xf16x2));
-}
 
 // ---- LDS-DMA: PIECES pieces of 1 KB, global -> LDS, PER_WAVE per wave, lane-linear.  `wave_u` is the wave's index among the WAVES that
 // copy (wave-uniform: readfirstlane).  The caller waits (vmcnt) and synchronises.
@@ -81,20 +52,20 @@ __device__ __forceinline__ void dma_kv_tile(const char *pair_img, int j0, char *
 struct Frag256 {
     const char *lds;
     int l31, hi;
-    __device__ __forceinline__ xhalf8 operator()(int base, int rb, int s_) const
+    __device__ __forceinline__ f16x8 operator()(int base, int rb, int s_) const
     {
         const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(lds + base + o * 256 + (((2 * s_ + hi) ^ (o & 15)) << 4));
+        return *reinterpret_cast<const f16x8 *>(lds + base + o * 256 + (((2 * s_ + hi) ^ (o & 15)) << 4));
     }
 };
 // 128-byte rows (64 input channels: fc_message W2, W3): slot ^ ((row >> 1) & 7)
 struct Frag128 {
     const char *lds;
     int l31, hi;
-    __device__ __forceinline__ xhalf8 operator()(int base, int rb, int s_) const
+    __device__ __forceinline__ f16x8 operator()(int base, int rb, int s_) const
     {
         const int o = rb * 32 + l31;
-        return *reinterpret_cast<const xhalf8 *>(lds + base + o * 128 + (((2 * s_ + hi) ^ ((o >> 1) & 7)) << 4));
+        return *reinterpret_cast<const f16x8 *>(lds + base + o * 128 + (((2 * s_ + hi) ^ ((o >> 1) & 7)) << 4));
     }
 };
 
@@ -104,13 +75,13 @@ struct Frag128 {
 // SWAP = false: the weights are the A operand (accumulator: lane = point, registers = channels); SWAP = true: the activations are
 // (lane = channel, registers = points crow(r, hi)) - the same fragments either way, the 32x32x16 A and B register layouts are mirror images.
 template <int NS, bool SWAP, class Frag>
-__device__ __forceinline__ void two_blocks(const Frag &frag, int base_h, int base_l, int rb0, const xhalf8 *bh, const xhalf8 *bl, f32x16 (&acc)[2])
+__device__ __forceinline__ void two_blocks(const Frag &frag, int base_h, int base_l, int rb0, const f16x8 *bh, const f16x8 *bl, f32x16 (&acc)[2])
 {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
-    xhalf8 w[2][2][2];                            // [buffer][block][hi | lo]
+    f16x8 w[2][2][2];                             // [buffer][block][hi | lo]
 #pragma unroll
     for (int i = 0; i < 2; ++i) { w[0][i][0] = frag(base_h, rb0 + i, 0); w[0][i][1] = frag(base_l, rb0 + i, 0); }
     __builtin_amdgcn_sched_barrier(0);
@@ -176,7 +147,7 @@ struct BiasLds {
 // bias + ReLU + hi / lo split of two 32-channel accumulator blocks -> the 4 B fragments (k-steps) of the next layer;
 // the blocks' biases start at channel `off` of `bias`
 template <class Bias>
-__device__ __forceinline__ void next_operand(const f32x16 (&acc)[2], const Bias &bias, int off, int hi, xhalf8 (&oh)[4], xhalf8 (&ol)[4])
+__device__ __forceinline__ void next_operand(const f32x16 (&acc)[2], const Bias &bias, int off, int hi, f16x8 (&oh)[4], f16x8 (&ol)[4])
 {
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
@@ -190,17 +161,17 @@ __device__ __forceinline__ void next_operand(const f32x16 (&acc)[2], const Bias 
                 const int r0 = 8 * j + 4 * g2;
                 const float v0 = fmaxf(acc[rb][r0] + bv.x, 0.0f), v1 = fmaxf(acc[rb][r0 + 1] + bv.y, 0.0f);
                 const float v2 = fmaxf(acc[rb][r0 + 2] + bv.z, 0.0f), v3 = fmaxf(acc[rb][r0 + 3] + bv.w, 0.0f);
-                split_pair(v0, v1, ph[2 * g2], pl[2 * g2]);
-                split_pair(v2, v3, ph[2 * g2 + 1], pl[2 * g2 + 1]);
+                split2(v0, v1, ph[2 * g2], pl[2 * g2]);
+                split2(v2, v3, ph[2 * g2 + 1], pl[2 * g2 + 1]);
             }
-            oh[rb * 2 + j] = __builtin_bit_cast(xhalf8, uh);
-            ol[rb * 2 + j] = __builtin_bit_cast(xhalf8, ul);
+            oh[rb * 2 + j] = __builtin_bit_cast(f16x8, uh);
+            ol[rb * 2 + j] = __builtin_bit_cast(f16x8, ul);
         }
 }
 
 // The 128 floats of this lane's row as eight B-operand fragments: channels 16 s + 8 hi .. + 7 of k-step s, split into hi / lo.
 // All sixteen loads are issued before the first split.
-__device__ __forceinline__ void load_split_row(const float *row, int hi, xhalf8 (&xh)[8], xhalf8 (&xl)[8])
+__device__ __forceinline__ void load_split_row(const float *row, int hi, f16x8 (&xh)[8], f16x8 (&xl)[8])
 {
     const float4 *xp = reinterpret_cast<const float4 *>(row);
     float4 raw[16];
@@ -209,12 +180,12 @@ __device__ __forceinline__ void load_split_row(const float *row, int hi, xhalf8 
 #pragma unroll
     for (int s_ = 0; s_ < 8; ++s_) {
         uint4 uh, ul;
-        split_pair(raw[2 * s_].x, raw[2 * s_].y, uh.x, ul.x);
-        split_pair(raw[2 * s_].z, raw[2 * s_].w, uh.y, ul.y);
-        split_pair(raw[2 * s_ + 1].x, raw[2 * s_ + 1].y, uh.z, ul.z);
-        split_pair(raw[2 * s_ + 1].z, raw[2 * s_ + 1].w, uh.w, ul.w);
-        xh[s_] = __builtin_bit_cast(xhalf8, uh);
-        xl[s_] = __builtin_bit_cast(xhalf8, ul);
+        split2(raw[2 * s_].x, raw[2 * s_].y, uh.x, ul.x);
+        split2(raw[2 * s_].z, raw[2 * s_].w, uh.y, ul.y);
+        split2(raw[2 * s_ + 1].x, raw[2 * s_ + 1].y, uh.z, ul.z);
+        split2(raw[2 * s_ + 1].z, raw[2 * s_ + 1].w, uh.w, ul.w);
+        xh[s_] = __builtin_bit_cast(f16x8, uh);
+        xl[s_] = __builtin_bit_cast(f16x8, ul);
     }
 }
 
@@ -237,22 +208,22 @@ __device__ __forceinline__ void fetch_sc(const float4 *sc_q, bool q_live, int kb
     for (int v4 = 0; v4 < 4; ++v4) scv[v4] = q_live ? sp[(size_t)v4 * 64] : make_float4(-1.f, -1.f, -1.f, -1.f);
 }
 // K fragments (hi | lo) of key `key` of a tile image for k-step s_; V fragment of (key octet, channel) of a V plane
-__device__ __forceinline__ void read_k(const char *tile, int key, int s_, int hi, xhalf8 (&kf)[2])
+__device__ __forceinline__ void read_k(const char *tile, int key, int s_, int hi, f16x8 (&kf)[2])
 {
-    kf[0] = *reinterpret_cast<const xhalf8 *>(reinterpret_cast<const _Float16 *>(tile) + pdsc_k_img_elem(key, 2 * s_ + hi));
-    kf[1] = *reinterpret_cast<const xhalf8 *>(reinterpret_cast<const _Float16 *>(tile + PDSC_KV_KL) + pdsc_k_img_elem(key, 2 * s_ + hi));
+    kf[0] = *reinterpret_cast<const f16x8 *>(reinterpret_cast<const _Float16 *>(tile) + pdsc_k_img_elem(key, 2 * s_ + hi));
+    kf[1] = *reinterpret_cast<const f16x8 *>(reinterpret_cast<const _Float16 *>(tile + PDSC_KV_KL) + pdsc_k_img_elem(key, 2 * s_ + hi));
 }
-__device__ __forceinline__ xhalf8 read_v(const char *v_plane, int oct, int ch)
+__device__ __forceinline__ f16x8 read_v(const char *v_plane, int oct, int ch)
 {
-    return *reinterpret_cast<const xhalf8 *>(reinterpret_cast<const _Float16 *>(v_plane) + ((size_t)oct * 128 + ch) * 8);
+    return *reinterpret_cast<const f16x8 *>(reinterpret_cast<const _Float16 *>(v_plane) + ((size_t)oct * 128 + ch) * 8);
 }
 // ... and their writers (pdsc_pcn_qkv_x3_kernel, pdsc_att_chain_x3_kernel), already split into hi / lo:
 // k from the un-swapped product (lane = key): channels cc .. cc + 3 of `key` (0..63), one 8-byte piece per plane
 __device__ __forceinline__ void store_k(char *tile, float4 k, int key, int cc)
 {
     uint2 uh, ul;
-    split_pair(k.x, k.y, uh.x, ul.x);
-    split_pair(k.z, k.w, uh.y, ul.y);
+    split2(k.x, k.y, uh.x, ul.x);
+    split2(k.z, k.w, uh.y, ul.y);
     const size_t off = (size_t)pdsc_k_img_elem(key, cc >> 3) * 2 + (cc & 7) * 2;
     *reinterpret_cast<uint2 *>(tile + off) = uh;
     *reinterpret_cast<uint2 *>(tile + PDSC_KV_KL + off) = ul;
@@ -264,10 +235,10 @@ __device__ __forceinline__ void store_v(char *tile, const f32x16 &acc, float bv,
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
         uint4 uh, ul;
-        split_pair(acc[8 * t2 + 0] + bv, acc[8 * t2 + 1] + bv, uh.x, ul.x);
-        split_pair(acc[8 * t2 + 2] + bv, acc[8 * t2 + 3] + bv, uh.y, ul.y);
-        split_pair(acc[8 * t2 + 4] + bv, acc[8 * t2 + 5] + bv, uh.z, ul.z);
-        split_pair(acc[8 * t2 + 6] + bv, acc[8 * t2 + 7] + bv, uh.w, ul.w);
+        split2(acc[8 * t2 + 0] + bv, acc[8 * t2 + 1] + bv, uh.x, ul.x);
+        split2(acc[8 * t2 + 2] + bv, acc[8 * t2 + 3] + bv, uh.y, ul.y);
+        split2(acc[8 * t2 + 4] + bv, acc[8 * t2 + 5] + bv, uh.z, ul.z);
+        split2(acc[8 * t2 + 6] + bv, acc[8 * t2 + 7] + bv, uh.w, ul.w);
         const int oct = (kb * 2 + t2) * 2 + hi;
         *reinterpret_cast<uint4 *>(tile + PDSC_KV_VH + ((size_t)oct * 128 + ch) * 16) = uh;
         *reinterpret_cast<uint4 *>(tile + PDSC_KV_VL + ((size_t)oct * 128 + ch) * 16) = ul;

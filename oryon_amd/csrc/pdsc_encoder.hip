@@ -423,8 +423,8 @@ __global__ __launch_bounds__(256) void pdsc_attention_x3_kernel(const float *__r
         for (int i = 0; i < KF4; ++i) {
             const int e = t + 256 * i, row = e / (C / 4), c4 = e % (C / 4);
             uint2 ph, pl;
-            split_pair(kv[i].x, kv[i].y, ph.x, pl.x);
-            split_pair(kv[i].z, kv[i].w, ph.y, pl.y);
+            split2(kv[i].x, kv[i].y, ph.x, pl.x);
+            split2(kv[i].z, kv[i].w, ph.y, pl.y);
             *reinterpret_cast<uint2 *>(Kh + row * KLD + 4 * c4) = ph;
             *reinterpret_cast<uint2 *>(Kl + row * KLD + 4 * c4) = pl;
         }
@@ -432,17 +432,17 @@ __global__ __launch_bounds__(256) void pdsc_attention_x3_kernel(const float *__r
         for (int o = 0; o < VOCT; ++o) {
             const int oct = vgrp + GROUPS * o;
             uint4 ph, pl;
-            split_pair(vv[o * 8 + 0], vv[o * 8 + 1], ph.x, pl.x);
-            split_pair(vv[o * 8 + 2], vv[o * 8 + 3], ph.y, pl.y);
-            split_pair(vv[o * 8 + 4], vv[o * 8 + 5], ph.z, pl.z);
-            split_pair(vv[o * 8 + 6], vv[o * 8 + 7], ph.w, pl.w);
+            split2(vv[o * 8 + 0], vv[o * 8 + 1], ph.x, pl.x);
+            split2(vv[o * 8 + 2], vv[o * 8 + 3], ph.y, pl.y);
+            split2(vv[o * 8 + 4], vv[o * 8 + 5], ph.z, pl.z);
+            split2(vv[o * 8 + 6], vv[o * 8 + 7], ph.w, pl.w);
             *reinterpret_cast<uint4 *>(Vh + ((size_t)oct * C + vch) * 8) = ph;
             *reinterpret_cast<uint4 *>(Vl + ((size_t)oct * C + vch) * 8) = pl;
         }
     };
 
     // Q^T as B operand: lane (query l31, half hi), k16 step s -> channels 16s + 8hi .. +7, split once
-    xhalf8 qh[NS], ql[NS];
+    f16x8 qh[NS], ql[NS];
     {
         const float4 *qv = reinterpret_cast<const float4 *>(base + (size_t)qrow * 3 * C);
 #pragma unroll
@@ -452,7 +452,7 @@ __global__ __launch_bounds__(256) void pdsc_attention_x3_kernel(const float *__r
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 _Float16 h_, l_;
-                split_half(x[e], h_, l_);
+                split1(x[e], h_, l_);
                 qh[s_][e] = h_;
                 ql[s_][e] = l_;
             }
@@ -481,12 +481,12 @@ __global__ __launch_bounds__(256) void pdsc_attention_x3_kernel(const float *__r
         // One wave per SIMD: nobody hides an LDS read that is waited for right after its issue, and that is how the compiler orders
         // this loop when left alone (ds_read -> s_waitcnt lgkmcnt(0) -> 1-2 MFMAs, 32 times per tile).  The fragments of k16 step
         // s_+1 are therefore requested before the MFMAs of step s_, and sched_barrier keeps it that way.
-        xhalf8 kf[2][2][2];                           // [buffer][key block][hi | lo]
+        f16x8 kf[2][2][2];                            // [buffer][key block][hi | lo]
         auto read_k = [&](int s_, int buf) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
-                kf[buf][kb][0] = *reinterpret_cast<const xhalf8 *>(Kh + (kb * 32 + l31) * KLD + 16 * s_ + 8 * hi);
-                kf[buf][kb][1] = *reinterpret_cast<const xhalf8 *>(Kl + (kb * 32 + l31) * KLD + 16 * s_ + 8 * hi);
+                kf[buf][kb][0] = *reinterpret_cast<const f16x8 *>(Kh + (kb * 32 + l31) * KLD + 16 * s_ + 8 * hi);
+                kf[buf][kb][1] = *reinterpret_cast<const f16x8 *>(Kl + (kb * 32 + l31) * KLD + 16 * s_ + 8 * hi);
             }
         };
         read_k(0, 0);
@@ -522,7 +522,7 @@ __global__ __launch_bounds__(256) void pdsc_attention_x3_kernel(const float *__r
         const float m_new = fmaxf(m_run, m_tile);
         const float alpha = __expf(m_run - m_new);
         float l_tile = 0.0f;
-        xhalf8 ph[2][2], pl[2][2];                  // [kb][t2]: keys crow(8*t2 + e, hi)
+        f16x8 ph[2][2], pl[2][2];                   // [kb][t2]: keys crow(8*t2 + e, hi)
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -532,8 +532,8 @@ __global__ __launch_bounds__(256) void pdsc_attention_x3_kernel(const float *__r
                 l_tile += p0;
                 l_tile += p1;
                 unsigned uh, ul;
-                split_pair(p0, p1, uh, ul);
-                const xf16x2 h2 = __builtin_bit_cast(xf16x2, uh), l2 = __builtin_bit_cast(xf16x2, ul);
+                split2(p0, p1, uh, ul);
+                const f16x2 h2 = __builtin_bit_cast(f16x2, uh), l2 = __builtin_bit_cast(f16x2, ul);
                 ph[kb][r >> 3][r & 7] = h2[0]; ph[kb][r >> 3][(r & 7) + 1] = h2[1];
                 pl[kb][r >> 3][r & 7] = l2[0]; pl[kb][r >> 3][(r & 7) + 1] = l2[1];
             }
@@ -544,13 +544,13 @@ __global__ __launch_bounds__(256) void pdsc_attention_x3_kernel(const float *__r
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc_o[cb][r] *= alpha;
         // O^T += V^T P^T, the V fragments of key octet pair o+1 requested before the MFMAs of pair o (as above)
-        xhalf8 vf[2][CB][2];                          // [buffer][channel block][hi | lo]
+        f16x8 vf[2][CB][2];                           // [buffer][channel block][hi | lo]
         auto read_v = [&](int o, int buf) {           // o = kb * 2 + t2
             const int oct = o * 2 + hi;
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
-                vf[buf][cb][0] = *reinterpret_cast<const xhalf8 *>(Vh + ((size_t)oct * C + cb * 32 + l31) * 8);
-                vf[buf][cb][1] = *reinterpret_cast<const xhalf8 *>(Vl + ((size_t)oct * C + cb * 32 + l31) * 8);
+                vf[buf][cb][0] = *reinterpret_cast<const f16x8 *>(Vh + ((size_t)oct * C + cb * 32 + l31) * 8);
+                vf[buf][cb][1] = *reinterpret_cast<const f16x8 *>(Vl + ((size_t)oct * C + cb * 32 + l31) * 8);
             }
         };
         read_v(0, 0);
@@ -632,7 +632,7 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
     const float4 *sc_q = reinterpret_cast<const float4 *>(sc) + (((size_t)b * (n_cap / 32) + (q0 / 32 + wave)) * (n_cap / ATT_KT)) * 8 * 64 + lane;
     const bool q_live = q0 + wave * 32 < n;
     float4 scv[4];
-    xhalf8 qh[NS], ql[NS];
+    f16x8 qh[NS], ql[NS];
     {
         const float4 *qv = reinterpret_cast<const float4 *>(base + (size_t)qrow * 3 * C);
 #pragma unroll
@@ -642,7 +642,7 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 _Float16 h_, l_;
-                split_half(x[e], h_, l_);
+                split1(x[e], h_, l_);
                 qh[s_][e] = h_;
                 ql[s_][e] = l_;
             }
@@ -667,7 +667,7 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.0f;
-        xhalf8 kf[2][2];                              // [buffer][hi | lo]
+        f16x8 kf[2][2];                               // [buffer][hi | lo]
         read_k(tile, kb * 32 + l31, 0, hi, kf[0]);
 #pragma unroll
         for (int s_ = 0; s_ < NS; ++s_) {
@@ -693,7 +693,7 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
         // a block whose keys are all masked so far keeps m = -inf: exp(-inf - (-inf)) must not produce NaN
         const float alpha = m_new == -INFINITY ? 1.0f : __expf(m_run - m_new);
         float l_tile = 0.0f;
-        xhalf8 ph[2], pl[2];
+        f16x8 ph[2], pl[2];
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
             const float p0 = m_new == -INFINITY ? 0.0f : __expf(s[r] - m_new);
@@ -701,8 +701,8 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
             l_tile += p0;
             l_tile += p1;
             unsigned uh, ul;
-            split_pair(p0, p1, uh, ul);
-            const xf16x2 h2 = __builtin_bit_cast(xf16x2, uh), l2 = __builtin_bit_cast(xf16x2, ul);
+            split2(p0, p1, uh, ul);
+            const f16x2 h2 = __builtin_bit_cast(f16x2, uh), l2 = __builtin_bit_cast(f16x2, ul);
             ph[r >> 3][r & 7] = h2[0]; ph[r >> 3][(r & 7) + 1] = h2[1];
             pl[r >> 3][r & 7] = l2[0]; pl[r >> 3][(r & 7) + 1] = l2[1];
         }
@@ -720,7 +720,7 @@ __global__ __launch_bounds__(512) void pdsc_attention_x3_img8_kernel(const float
             const int oct = (kb * 2 + t2) * 2 + hi;
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
-                const xhalf8 vh = read_v(tile + PDSC_KV_VH, oct, cb * 32 + l31), vl = read_v(tile + PDSC_KV_VL, oct, cb * 32 + l31);
+                const f16x8 vh = read_v(tile + PDSC_KV_VH, oct, cb * 32 + l31), vl = read_v(tile + PDSC_KV_VL, oct, cb * 32 + l31);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[t2], acc_o[cb], 0, 0, 0);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[t2], acc_o[cb], 0, 0, 0);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[t2], acc_o[cb], 0, 0, 0);
@@ -802,8 +802,8 @@ __global__ __launch_bounds__(256) void pdsc_linear_x3_kernel(const float *__rest
         for (int i = 0; i < NX; ++i) {
             const int e = t + 256 * i, row = e >> 4, kk = (e & 15) * 2;
             union { _Float16 h[2]; unsigned u; } ph, pl;
-            split_half(xv[i].x, ph.h[0], pl.h[0]);
-            split_half(xv[i].y, ph.h[1], pl.h[1]);
+            split1(xv[i].x, ph.h[0], pl.h[0]);
+            split1(xv[i].y, ph.h[1], pl.h[1]);
             *reinterpret_cast<unsigned *>(Xh + row * XLD + kk) = ph.u;
             *reinterpret_cast<unsigned *>(Xl + row * XLD + kk) = pl.u;
         }
@@ -811,8 +811,8 @@ __global__ __launch_bounds__(256) void pdsc_linear_x3_kernel(const float *__rest
         for (int i = 0; i < NW; ++i) {
             const int e = t + 256 * i, col = e >> 4, kk = (e & 15) * 2;
             union { _Float16 h[2]; unsigned u; } ph, pl;
-            split_half(wv[i].x, ph.h[0], pl.h[0]);
-            split_half(wv[i].y, ph.h[1], pl.h[1]);
+            split1(wv[i].x, ph.h[0], pl.h[0]);
+            split1(wv[i].y, ph.h[1], pl.h[1]);
             *reinterpret_cast<unsigned *>(Wh + col * XLD + kk) = ph.u;
             *reinterpret_cast<unsigned *>(Wl + col * XLD + kk) = pl.u;
         }
@@ -820,12 +820,12 @@ __global__ __launch_bounds__(256) void pdsc_linear_x3_kernel(const float *__rest
 #pragma unroll
         for (int s_ = 0; s_ < LIN_BK / 16; ++s_) {
             const int ko = 16 * s_ + 8 * hi;
-            const xhalf8 ah = *reinterpret_cast<const xhalf8 *>(Xh + (wm * 32 + l31) * XLD + ko);
-            const xhalf8 al = *reinterpret_cast<const xhalf8 *>(Xl + (wm * 32 + l31) * XLD + ko);
+            const f16x8 ah = *reinterpret_cast<const f16x8 *>(Xh + (wm * 32 + l31) * XLD + ko);
+            const f16x8 al = *reinterpret_cast<const f16x8 *>(Xl + (wm * 32 + l31) * XLD + ko);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const xhalf8 bh = *reinterpret_cast<const xhalf8 *>(Wh + (wn * 64 + j * 32 + l31) * XLD + ko);
-                const xhalf8 bl = *reinterpret_cast<const xhalf8 *>(Wl + (wn * 64 + j * 32 + l31) * XLD + ko);
+                const f16x8 bh = *reinterpret_cast<const f16x8 *>(Wh + (wn * 64 + j * 32 + l31) * XLD + ko);
+                const f16x8 bl = *reinterpret_cast<const f16x8 *>(Wl + (wn * 64 + j * 32 + l31) * XLD + ko);
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[j], 0, 0, 0);
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[j], 0, 0, 0);
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[j], 0, 0, 0);
@@ -871,7 +871,7 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_mlp3_x3_kernel(const float *_
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     dma_mlp_image<WAVES>(img, mlp_lds, wave_u, lane);
     const size_t prow = ((size_t)b * n_cap + q0 + wave * 32 + l31) * C;       // this lane's point
-    xhalf8 xh[8], xl[8];
+    f16x8 xh[8], xl[8];
     load_split_row(msg + prow, hi, xh, xl);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -880,12 +880,12 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_mlp3_x3_kernel(const float *_
     // layer 1: [64, 128] x [128, points]
     f32x16 a1[2];
     two_blocks<8, false>(w1_frag, PDSC_MLP_W1H, PDSC_MLP_W1L, 0, xh, xl, a1);
-    xhalf8 h1h[4], h1l[4];
+    f16x8 h1h[4], h1l[4];
     next_operand(a1, BiasVector{b1}, 0, hi, h1h, h1l);
     // layer 2: [64, 64] x [64, points]
     f32x16 a2[2];
     two_blocks<4, false>(w23_frag, PDSC_MLP_W2H, PDSC_MLP_W2L, 0, h1h, h1l, a2);
-    xhalf8 h2h[4], h2l[4];
+    f16x8 h2h[4], h2l[4];
     next_operand(a2, BiasVector{b2}, 0, hi, h2h, h2l);
     // layer 3: [128, 64] x [64, points], + bias + residual, stored as float4 groups (channels rb*32 + 8 g + 4 hi + 0..3 of the lane's point)
 #pragma unroll
@@ -934,7 +934,7 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_pcn_qkv_x3_kernel(const float
     dma_pq_chunk<WAVES>(img, 0, pq_lds, wave_u, lane);
     dma_pq_chunk<WAVES>(img, 1, pq_lds + PDSC_PQ_CHUNK_BYTES, wave_u, lane);
     const size_t prow = (size_t)b * n_cap + q0 + wave * 32 + l31;
-    xhalf8 xh[8], xl[8];
+    f16x8 xh[8], xl[8];
     load_split_row(feat + prow * C, hi, xh, xl);
     // v's bias is per lane (lane = channel): fetched here, with the inputs, so that the wait below covers it - a load waited for between the
     // parts' stores would be waited for with vmcnt(0), i.e. behind every earlier store's acknowledgement
@@ -946,7 +946,7 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_pcn_qkv_x3_kernel(const float
     __syncthreads();
     const Frag256 frag{pq_lds, l31, hi};
     // layer 1 (PointCN, area 0): bias + ReLU, stored as feat1 and kept as the 8 B fragments of layer 2
-    xhalf8 fh[8], fl[8];
+    f16x8 fh[8], fl[8];
 #pragma unroll
     for (int rp = 0; rp < 2; ++rp) {
         f32x16 acc[2];
@@ -967,11 +967,11 @@ __global__ __launch_bounds__(64 * WAVES) void pdsc_pcn_qkv_x3_kernel(const float
                     v.z = fmaxf(acc[i][r0 + 2] + bv.z, 0.0f); v.w = fmaxf(acc[i][r0 + 3] + bv.w, 0.0f);
                     if (g4) reinterpret_cast<float4 *>(feat1 + (size_t)b * n_cap * C)[pdsc_g4_index(n_cap, q0 + wave * 32 + l31, c >> 2)] = v;
                     else *reinterpret_cast<float4 *>(feat1 + prow * C + c) = v;
-                    split_pair(v.x, v.y, ph[2 * g2], pl[2 * g2]);
-                    split_pair(v.z, v.w, ph[2 * g2 + 1], pl[2 * g2 + 1]);
+                    split2(v.x, v.y, ph[2 * g2], pl[2 * g2]);
+                    split2(v.z, v.w, ph[2 * g2 + 1], pl[2 * g2 + 1]);
                 }
-                fh[rb * 2 + j] = __builtin_bit_cast(xhalf8, uh);
-                fl[rb * 2 + j] = __builtin_bit_cast(xhalf8, ul);
+                fh[rb * 2 + j] = __builtin_bit_cast(f16x8, uh);
+                fl[rb * 2 + j] = __builtin_bit_cast(f16x8, ul);
             }
         }
     }
@@ -1088,7 +1088,7 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     // instructions of the split, their latency exposed in front of the first tile)
     dma_kv_tile(img, 0, att_lds, wave_u, lane);
     fetch_sc(sc_q, q_live, kb, 0, scv);
-    xhalf8 qh[NS], ql[NS];
+    f16x8 qh[NS], ql[NS];
     {
         // q in the G4 row-fragment layout (pdsc.h): the 8 channels of k-step s_ for lane half hi are the quads 4 s_ + 2 hi, + 1
         const float4 *qv = reinterpret_cast<const float4 *>(base);
@@ -1100,12 +1100,12 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
         for (int s_ = 0; s_ < NS; ++s_) {
             const float4 a = qv[pdsc_g4_index(n_cap, qrow, 4 * s_ + 2 * hi)], c = qv[pdsc_g4_index(n_cap, qrow, 4 * s_ + 2 * hi + 1)];
             uint4 uh, ul;
-            split_pair(a.x * qs, a.y * qs, uh.x, ul.x);
-            split_pair(a.z * qs, a.w * qs, uh.y, ul.y);
-            split_pair(c.x * qs, c.y * qs, uh.z, ul.z);
-            split_pair(c.z * qs, c.w * qs, uh.w, ul.w);
-            qh[s_] = __builtin_bit_cast(xhalf8, uh);
-            ql[s_] = __builtin_bit_cast(xhalf8, ul);
+            split2(a.x * qs, a.y * qs, uh.x, ul.x);
+            split2(a.z * qs, a.w * qs, uh.y, ul.y);
+            split2(c.x * qs, c.y * qs, uh.z, ul.z);
+            split2(c.z * qs, c.w * qs, uh.w, ul.w);
+            qh[s_] = __builtin_bit_cast(f16x8, uh);
+            ql[s_] = __builtin_bit_cast(f16x8, ul);
         }
     }
     f32x16 acc_o[CB];
@@ -1128,7 +1128,7 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.0f;
-        xhalf8 kf[2][2];                              // [buffer][hi | lo]
+        f16x8 kf[2][2];                               // [buffer][hi | lo]
         read_k(tile, kb * 32 + l31, 0, hi, kf[0]);
 #pragma unroll
         for (int s_ = 0; s_ < NS; ++s_) {
@@ -1139,7 +1139,7 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
             s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[bf][1], qh[s_], s, 0, 0, 0);
         }
         float m_tile = -INFINITY;
-        xhalf8 ph[2], pl[2];
+        f16x8 ph[2], pl[2];
         if (q_full && j0 + ATT_KT <= n) {
             // ---- full tile (round 6): every (query, key) of it exists - no mask, no -inf guards (m_new is finite; exp(-inf - m) = 0 on the
             // first tile).  Same arithmetic per element as the masked path below.
@@ -1163,8 +1163,8 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
                 l_tile += p0;
                 l_tile += p1;
                 unsigned uh, ul;
-                split_pair(p0, p1, uh, ul);
-                const xf16x2 h2 = __builtin_bit_cast(xf16x2, uh), l2 = __builtin_bit_cast(xf16x2, ul);
+                split2(p0, p1, uh, ul);
+                const f16x2 h2 = __builtin_bit_cast(f16x2, uh), l2 = __builtin_bit_cast(f16x2, ul);
                 ph[r >> 3][r & 7] = h2[0]; ph[r >> 3][(r & 7) + 1] = h2[1];
                 pl[r >> 3][r & 7] = l2[0]; pl[r >> 3][(r & 7) + 1] = l2[1];
             }
@@ -1199,8 +1199,8 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
             l_tile += p0;
             l_tile += p1;
             unsigned uh, ul;
-            split_pair(p0, p1, uh, ul);
-            const xf16x2 h2 = __builtin_bit_cast(xf16x2, uh), l2 = __builtin_bit_cast(xf16x2, ul);
+            split2(p0, p1, uh, ul);
+            const f16x2 h2 = __builtin_bit_cast(f16x2, uh), l2 = __builtin_bit_cast(f16x2, ul);
             ph[r >> 3][r & 7] = h2[0]; ph[r >> 3][(r & 7) + 1] = h2[1];
             pl[r >> 3][r & 7] = l2[0]; pl[r >> 3][(r & 7) + 1] = l2[1];
         }
@@ -1219,7 +1219,7 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
             const int oct = (kb * 2 + t2) * 2 + hi;
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
-                const xhalf8 vh = read_v(tile + PDSC_KV_VH, oct, cb * 32 + l31), vl = read_v(tile + PDSC_KV_VL, oct, cb * 32 + l31);
+                const f16x8 vh = read_v(tile + PDSC_KV_VH, oct, cb * 32 + l31), vl = read_v(tile + PDSC_KV_VL, oct, cb * 32 + l31);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[t2], acc_o[cb], 0, 0, 0);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[t2], acc_o[cb], 0, 0, 0);
                 acc_o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[t2], acc_o[cb], 0, 0, 0);
@@ -1243,7 +1243,7 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     __syncthreads();
     const bool live = kb == 0;
     const size_t prow = (size_t)b * n_cap + qrow;
-    xhalf8 xh[8], xl[8];                                              // the message as the chain's B fragments (k-step 2 cb + j: registers 8 j .. 8 j + 7 of block cb)
+    f16x8 xh[8], xl[8];                                               // the message as the chain's B fragments (k-step 2 cb + j: registers 8 j .. 8 j + 7 of block cb)
     if (live) {
         const float m_b = xo[(CB * 16) * 64 + lane], l_b = xo[(CB * 16 + 1) * 64 + lane];
         const float m = fmaxf(m_run, m_b);
@@ -1263,11 +1263,11 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
                     const float v1 = (wa * acc_o[cb][r0 + 1] + wb * xo[(cb * 16 + r0 + 1) * 64 + lane]) * inv_l;
                     const float v2 = (wa * acc_o[cb][r0 + 2] + wb * xo[(cb * 16 + r0 + 2) * 64 + lane]) * inv_l;
                     const float v3 = (wa * acc_o[cb][r0 + 3] + wb * xo[(cb * 16 + r0 + 3) * 64 + lane]) * inv_l;
-                    split_pair(v0, v1, ph[2 * g2], pl[2 * g2]);
-                    split_pair(v2, v3, ph[2 * g2 + 1], pl[2 * g2 + 1]);
+                    split2(v0, v1, ph[2 * g2], pl[2 * g2]);
+                    split2(v2, v3, ph[2 * g2 + 1], pl[2 * g2 + 1]);
                 }
-                xh[cb * 2 + j] = __builtin_bit_cast(xhalf8, uh);
-                xl[cb * 2 + j] = __builtin_bit_cast(xhalf8, ul);
+                xh[cb * 2 + j] = __builtin_bit_cast(f16x8, uh);
+                xl[cb * 2 + j] = __builtin_bit_cast(f16x8, ul);
             }
     }
     CLK(3);
@@ -1306,12 +1306,12 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     // ---- fc_message of layer l
     f32x16 a1[2];
     two_blocks<8, false>(w1_frag, PDSC_MLP_W1H, PDSC_MLP_W1L, 0, xh, xl, a1);
-    xhalf8 h1h[4], h1l[4];
+    f16x8 h1h[4], h1l[4];
     next_operand(a1, bias4l, SEG_B1, hi, h1h, h1l);
     CLK(5);
     f32x16 a2[2];
     two_blocks<4, false>(w23_frag, PDSC_MLP_W2H, PDSC_MLP_W2L, 0, h1h, h1l, a2);
-    xhalf8 h2h[4], h2l[4];
+    f16x8 h2h[4], h2l[4];
     next_operand(a2, bias4l, SEG_B2, hi, h2h, h2l);
     CLK(6);
     // layer 3 + bias + residual = the layer's output features, kept as the 8 B fragments (permuted K order) of the next layer's PointCN
@@ -1332,11 +1332,11 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
                     const float4 bv = bias4l(SEG_B3 + rb * 32 + 8 * g, hi);
                     const float v0 = a3[i][4 * g + 0] + bv.x + rv[rp][i][g].x, v1 = a3[i][4 * g + 1] + bv.y + rv[rp][i][g].y;
                     const float v2 = a3[i][4 * g + 2] + bv.z + rv[rp][i][g].z, v3 = a3[i][4 * g + 3] + bv.w + rv[rp][i][g].w;
-                    split_pair(v0, v1, ph[2 * g2], pl[2 * g2]);
-                    split_pair(v2, v3, ph[2 * g2 + 1], pl[2 * g2 + 1]);
+                    split2(v0, v1, ph[2 * g2], pl[2 * g2]);
+                    split2(v2, v3, ph[2 * g2 + 1], pl[2 * g2 + 1]);
                 }
-                xh[rb * 2 + j] = __builtin_bit_cast(xhalf8, uh);       // (the message fragments are dead: their registers take the features)
-                xl[rb * 2 + j] = __builtin_bit_cast(xhalf8, ul);
+                xh[rb * 2 + j] = __builtin_bit_cast(f16x8, uh);        // (the message fragments are dead: their registers take the features)
+                xl[rb * 2 + j] = __builtin_bit_cast(f16x8, ul);
             }
             if constexpr (!HAS_NEXT) {                                 // last layer: the features leave as fp32 rows
 #pragma unroll
@@ -1361,7 +1361,7 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     // ---- PointCN + q|k|v of layer l + 1.  The fc_message image is dead once every wave is here: q lands on top of it.
     __syncthreads();
     dma_chunk_idle(1, AREA1);
-    xhalf8 fh[8], fl[8];
+    f16x8 fh[8], fl[8];
     if (live) {
 #pragma unroll
     for (int rp = 0; rp < 2; ++rp) {
@@ -1382,11 +1382,11 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
                     v.x = fmaxf(acc[i][r0] + bv.x, 0.0f); v.y = fmaxf(acc[i][r0 + 1] + bv.y, 0.0f);
                     v.z = fmaxf(acc[i][r0 + 2] + bv.z, 0.0f); v.w = fmaxf(acc[i][r0 + 3] + bv.w, 0.0f);
                     if (live) reinterpret_cast<float4 *>(feat1 + (size_t)b * n_cap * C)[pdsc_g4_index(n_cap, qrow, c >> 2)] = v;
-                    split_pair(v.x, v.y, ph[2 * g2], pl[2 * g2]);
-                    split_pair(v.z, v.w, ph[2 * g2 + 1], pl[2 * g2 + 1]);
+                    split2(v.x, v.y, ph[2 * g2], pl[2 * g2]);
+                    split2(v.z, v.w, ph[2 * g2 + 1], pl[2 * g2 + 1]);
                 }
-                fh[rb * 2 + j] = __builtin_bit_cast(xhalf8, uh);
-                fl[rb * 2 + j] = __builtin_bit_cast(xhalf8, ul);
+                fh[rb * 2 + j] = __builtin_bit_cast(f16x8, uh);
+                fl[rb * 2 + j] = __builtin_bit_cast(f16x8, ul);
             }
         }
     }
@@ -1402,7 +1402,7 @@ __global__ __launch_bounds__(512) void pdsc_att_chain_x3_kernel(const float *__r
     __builtin_amdgcn_s_barrier();                                       // ... and every wave is done with the PointCN weights (area 0)
     asm volatile("" ::: "memory");
     {
-        xhalf8 *ex = reinterpret_cast<xhalf8 *>(att_lds + AREA0 + wave * 16384);
+        f16x8 *ex = reinterpret_cast<f16x8 *>(att_lds + AREA0 + wave * 16384);
         if (live) {
 #pragma unroll
             for (int f = 0; f < 8; ++f) { ex[f * 64 + lane] = fh[f]; ex[(8 + f) * 64 + lane] = fl[f]; }
@@ -1567,8 +1567,8 @@ __global__ __launch_bounds__(256) void pdsc_head_x3_kernel(const float *__restri
                 for (int i = 0; i < 4; ++i) {
                     const int e = t + 256 * i, row = e >> 4, kk = (e & 15) * 2;
                     union { _Float16 h[2]; unsigned u; } ph, pl;
-                    split_half(xv[i].x, ph.h[0], pl.h[0]);
-                    split_half(xv[i].y, ph.h[1], pl.h[1]);
+                    split1(xv[i].x, ph.h[0], pl.h[0]);
+                    split1(xv[i].y, ph.h[1], pl.h[1]);
                     *reinterpret_cast<unsigned *>(Xh + row * XLD + kk) = ph.u;
                     *reinterpret_cast<unsigned *>(Xl + row * XLD + kk) = pl.u;
                 }
@@ -1576,8 +1576,8 @@ __global__ __launch_bounds__(256) void pdsc_head_x3_kernel(const float *__restri
                 for (int i = 0; i < 2; ++i) {
                     const int e = t + 256 * i, col = e >> 4, kk = (e & 15) * 2;
                     union { _Float16 h[2]; unsigned u; } ph, pl;
-                    split_half(wv[i].x, ph.h[0], pl.h[0]);
-                    split_half(wv[i].y, ph.h[1], pl.h[1]);
+                    split1(wv[i].x, ph.h[0], pl.h[0]);
+                    split1(wv[i].y, ph.h[1], pl.h[1]);
                     *reinterpret_cast<unsigned *>(Wh + col * XLD + kk) = ph.u;
                     *reinterpret_cast<unsigned *>(Wl + col * XLD + kk) = pl.u;
                 }
@@ -1586,10 +1586,10 @@ __global__ __launch_bounds__(256) void pdsc_head_x3_kernel(const float *__restri
 #pragma unroll
                     for (int s_ = 0; s_ < LIN_BK / 16; ++s_) {
                         const int ko = 16 * s_ + 8 * hi;
-                        const xhalf8 ah = *reinterpret_cast<const xhalf8 *>(Xh + (wave * 32 + l31) * XLD + ko);
-                        const xhalf8 al = *reinterpret_cast<const xhalf8 *>(Xl + (wave * 32 + l31) * XLD + ko);
-                        const xhalf8 bh = *reinterpret_cast<const xhalf8 *>(Wh + l31 * XLD + ko);
-                        const xhalf8 bl = *reinterpret_cast<const xhalf8 *>(Wl + l31 * XLD + ko);
+                        const f16x8 ah = *reinterpret_cast<const f16x8 *>(Xh + (wave * 32 + l31) * XLD + ko);
+                        const f16x8 al = *reinterpret_cast<const f16x8 *>(Xl + (wave * 32 + l31) * XLD + ko);
+                        const f16x8 bh = *reinterpret_cast<const f16x8 *>(Wh + l31 * XLD + ko);
+                        const f16x8 bl = *reinterpret_cast<const f16x8 *>(Wl + l31 * XLD + ko);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);

@@ -5,6 +5,7 @@
 #include <math.h>
 #include "common.h"
 #include "pdsc.h"
+#include "x3.h"
 
 using namespace oryon;
 
@@ -247,7 +248,8 @@ extern "C" int oryon_pointdsc_finalize(oryon_pointdsc_t *h, void *stream)
     if (C == 128) {
         std::vector<char> img((size_t)2 * L * PDSC_MLP_IMG_BYTES, 0);       // [L] natural W1 | [L] W1 with the permuted K axis
         auto put_half = [](char *dst_hi, char *dst_lo, size_t byte, float x) {
-            const _Float16 hi = (_Float16)x, lo = (_Float16)(x - (float)hi);
+            _Float16 hi, lo;
+            split1(x, hi, lo);
             memcpy(dst_hi + byte, &hi, 2);
             memcpy(dst_lo + byte, &lo, 2);
         };

@@ -331,6 +331,22 @@ def test_shipped_library_reads_no_environment_variable():
         assert b"ORYON_AMB_X3" in open(dev, "rb").read()
 
 
+def test_fp16x3_split_is_defined_once():
+    """The hi / lo split of the fp16x3 kernels lives in csrc/x3.h alone: the v_fma_mix_f32 form is written nowhere else, and none of the
+    per-file names its copies and the vector typedefs used to carry is an identifier of any source or header."""
+    import glob, re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oryon_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    text = {os.path.basename(f): open(f).read() for f in files}
+    users = ("gemm_x3.hip", "attention_x3.hip", "backbone_ops.hip", "decoder.hip", "pdsc_blocks.h", "pointdsc.hip")
+    assert "x3.h" in text and all('#include "x3.h"' in text[f] for f in users)
+    assert [f for f, t in text.items() if "v_fma_mix_f32" in t] == ["x3.h"]
+    retired = ("split_h", "mha_split", "mha_split2", "split_half", "split_pair", "fwa_split8", "fwa_h8", "fwa_acc", "ahalf8", "af32x16",
+               "dh8", "dacc16", "f16acc", "xhalf8")
+    found = {(f, n) for f, t in text.items() for n in retired if re.search(rf"\b{n}\b", t)}
+    assert found == set(), sorted(found)
+
+
 def test_engine_config_struct_matches_the_library():
     """The ctypes mirror of oryon_engine_config_t has the size the library was built with (a field added on one side only would shift
     every later field silently)."""
