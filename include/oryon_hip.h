@@ -593,6 +593,12 @@ typedef struct {
                                 own process with oryon_engine_set_stream_roles (oryon_amd.engine.MatchPoseEngine.tune_stream_roles does).
                                 Results never
                                 depend on it */
+    int screen_cascade;      /* 1 (default in the Python binding): on the default route of the MX-fp6 screen (C <= 256, three 1024-anchor panels or
+                                more, not under sample_first) the matcher screens a probe of the anchors completely, learns per panel the band of
+                                query tiles its matches lie in, settles the validity of the other anchors inside that band and scans completely
+                                only the anchors left open and the sampled ones (DESIGN.md "default-route cascade").  Results are unchanged.
+                                0 = the plain full screen.  (It stands in front of the solver fields, whose place at the end of the struct is
+                                pinned; the matcher entries oryon_match_corrs_mx6[_araw] themselves always take the cascade where the shape has one) */
     int solver;              /* 0 = PointDSC (default: everything above), 1 = RANSAC: the registration stream calls oryon_ransac_register with
                                 the step's pair_key and cfg.seed instead of oryon_pointdsc_register; oryon_engine_arena_bytes /
                                 oryon_engine_create then accept a NULL PointDSC handle and the arena holds the RANSAC workspace in place of
@@ -635,6 +641,10 @@ int oryon_engine_gather_ms(oryon_engine_t *handle, int64_t step, float *ms);
 int oryon_engine_host_stats(const oryon_engine_t *handle, int64_t *n_submit, double *submit_ms_total, double *submit_ms_last);
 /* number of submits so far whose K0 pass wrote the hi / lo rows (cfg.x3_prefetch) */
 int oryon_engine_x3_steps(const oryon_engine_t *handle, int64_t *n_steps);
+/* the default-route cascade of the most recent submit (cfg.screen_cascade), read-only, for tests and tuning: out[B][4] (host memory) =
+ * per pair the probe rows, the rows settled inside their panel's band, the rows left open (scanned completely) and the band's query
+ * tiles summed over the pair's live panels.  All zero when that submit took another route.  Synchronises the device. */
+int oryon_engine_cascade_stats(oryon_engine_t *handle, int32_t *out);
 /* the engine's own feedback, for callers that want the statistic without queueing reads of slot buffers (round 5): sums of the newest
  * COMPLETED step's per-pair counts of anchors the screen left to the second level ("n_und") and of anchors ("n_a") - the pinned-memory
  * copies the x3_prefetch decision is made from (MX-fp6 screen only).  *step = that step's submit index, -1 when none has completed yet.

@@ -22,7 +22,7 @@ class OryonError(RuntimeError):
 class EngineConfig(ctypes.Structure):
     _fields_ = [("B", c_int), ("C", c_int), ("FH", c_int), ("FW", c_int), ("HA", c_int), ("WA", c_int), ("HQ", c_int), ("WQ", c_int),
                 ("layout", c_int), ("dist_th", c_float), ("n_corrs", c_int), ("src_sampling", c_int), ("seed", c_uint64),
-                ("round_f16", c_int), ("n_slots", c_int), ("overlap", c_int), ("gather_sets", c_int), ("reg_streams", c_int), ("reg_lag", c_int), ("screen", c_int), ("sample_first", c_int), ("x3_prefetch", c_int), ("stream_roles", c_int),
+                ("round_f16", c_int), ("n_slots", c_int), ("overlap", c_int), ("gather_sets", c_int), ("reg_streams", c_int), ("reg_lag", c_int), ("screen", c_int), ("sample_first", c_int), ("x3_prefetch", c_int), ("stream_roles", c_int), ("screen_cascade", c_int),
                 ("solver", c_int), ("ransac_max_iter", c_int), ("ransac_match_err", c_float), ("ransac_fix_percent", c_float)]
 
 
@@ -139,6 +139,7 @@ _PROTOS = {
     "oryon_engine_config_bytes": (c_size_t, []),
     "oryon_engine_host_stats": (c_int, [c_void_p, POINTER(c_int64), POINTER(ctypes.c_double), POINTER(ctypes.c_double)]),
     "oryon_engine_x3_steps": (c_int, [c_void_p, POINTER(c_int64)]),
+    "oryon_engine_cascade_stats": (c_int, [c_void_p, c_void_p]),
     "oryon_engine_feedback": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "oryon_fusion_window_attention_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "oryon_fusion_class_layer_f32": (c_int, [_P, _P, POINTER(FusionClassWeights), c_int, _P, _P]),

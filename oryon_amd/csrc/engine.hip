@@ -18,6 +18,7 @@
 #include <chrono>
 #include <new>
 #include <vector>
+#include <string.h>
 #include "common.h"
 #include "match_common.h"
 
@@ -233,7 +234,7 @@ int check_cfg(const oryon_engine_config_t *c)
     ORYON_CHECK_ARG((c->layout == ORYON_LAYOUT_NCHW || c->layout == ORYON_LAYOUT_NHWC) && (c->screen == 0 || c->screen == 1));
     ORYON_CHECK_ARG(c->overlap >= 0 && c->overlap <= 2 && (c->overlap == 0 || c->n_slots >= 2));      // results of step k live until submit k + n_slots
     ORYON_CHECK_ARG((size_t)c->C * (size_t)c->FH * (size_t)c->FW * 4u < (1ull << 32));
-    ORYON_CHECK_ARG(c->sample_first >= 0 && (c->x3_prefetch == 0 || c->x3_prefetch == 1));
+    ORYON_CHECK_ARG(c->sample_first >= 0 && (c->x3_prefetch == 0 || c->x3_prefetch == 1) && (c->screen_cascade == 0 || c->screen_cascade == 1));
     ORYON_CHECK_ARG(roles_valid(c->stream_roles));
     ORYON_CHECK_ARG(c->solver == 0 || (c->solver == 1 && c->ransac_max_iter > 0 && c->ransac_match_err >= 0.0f));
     return ORYON_OK;
@@ -659,6 +660,9 @@ extern "C" int oryon_engine_submit(oryon_engine_t *e, const float *feat_a, const
         m.workspace_bytes = e->L.match_ws_bytes;
         m.stream = sm;
         m.fmt = mx6 ? 1 : 0;
+        // the default route's validity cascade: not under the sample-first schedule (its first stage has one panel, its second runs for
+        // the few pairs that came up short: the cascade's extra launches would be all either of them sees of it)
+        m.cascade = (c.screen_cascade && !sf) ? 1 : 0;
         if (mx6 && x3_pre) {
             // hard route: K0 wrote g.a_hat and the hi / lo query rows on this step (see x3_pre above)
             m.a_hat = g.a_hat;
@@ -767,6 +771,16 @@ extern "C" int oryon_engine_x3_steps(const oryon_engine_t *e, int64_t *n_steps)
 {
     ORYON_CHECK_ARG(e && n_steps);
     *n_steps = e->n_x3;
+    return ORYON_OK;
+}
+
+extern "C" int oryon_engine_cascade_stats(oryon_engine_t *e, int32_t *out)
+{
+    ORYON_CHECK_ARG(e && out);
+    ORYON_CHECK_HIP(hipDeviceSynchronize());
+    const int32_t *stats = match_dc_stats(e->L.match_ws, e->cfg.B, e->L.c_pad, e->L.cap_a, e->L.cap_q, e->L.n_cap);
+    if (!stats) { memset(out, 0, (size_t)e->cfg.B * 4 * sizeof(int32_t)); return ORYON_OK; }        // the shape has no cascade
+    ORYON_CHECK_HIP(hipMemcpy(out, stats, (size_t)e->cfg.B * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
     return ORYON_OK;
 }
 

@@ -231,12 +231,14 @@ __global__ __launch_bounds__(256) void match_panel_settle_kernel(int cap_a, int 
 
 __global__ __launch_bounds__(256) void match_compact_rows_kernel(const uint8_t *__restrict__ rows, int row_bytes, int cap_a, int cap_c,
                                                                   const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
-                                                                  int idx_stride, uint8_t *__restrict__ out)
+                                                                  int idx_stride, uint8_t *__restrict__ out, int fill_mult)
 {
-    // 16 lanes per 256-byte row (uint4 each); rows [count, cap_c) are zero rows (exponent byte 0: finite scores nobody reads)
+    // 16 lanes per 256-byte row (uint4 each); rows [count, round_up(count, fill_mult)) - the rest of the last panel a screen launch
+    // reads - are zero rows (exponent byte 0: finite scores nobody reads)
     const int p = blockIdx.y, sl = blockIdx.x * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
     if (sl >= cap_c) return;
     const int n = count[p] < cap_c ? count[p] : cap_c;
+    if (sl >= (n + fill_mult - 1) / fill_mult * fill_mult) return;
     uint4 *d = reinterpret_cast<uint4 *>(out + ((size_t)p * cap_c + sl) * row_bytes);
     if (sl >= n) {
         for (int i = l; i < row_bytes / 16; i += 16) d[i] = make_uint4(0, 0, 0, 0);
@@ -253,7 +255,7 @@ __global__ __launch_bounds__(256) void match_decide_sampled_kernel(int cap_a, in
                                                                     const float *__restrict__ q_err, float *__restrict__ m_final,
                                                                     int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
                                                                     uint8_t *__restrict__ state, int32_t *__restrict__ mark,
-                                                                    int32_t *__restrict__ count_before)
+                                                                    int32_t *__restrict__ count_before, float *__restrict__ min_dist)
 {
     const int p = blockIdx.y, sl = blockIdx.x * 256 + threadIdx.x;
     const int n = count[p] < cap_c ? count[p] : cap_c;
@@ -275,10 +277,181 @@ __global__ __launch_bounds__(256) void match_decide_sampled_kernel(int cap_a, in
     m_final[arow] = m1;                                                // the complete scan's maximum (>= the partial one that settled validity)
     sid_final[arow] = sid;
     margin_out[arow] = margin;
+    // default-route cascade: the provisional distance of a settled row came from its witness inside the band; the estimate a sampled
+    // row reports is the complete scan's, as on the plain route
+    if (min_dist) min_dist[arow] = __fmaf_rn(-0.5f, m1, 0.5f);
     if (m1 - m2 > margin) {                                            // unambiguous after all: no second level for this row
         state[arow] = LZ_VALID;
         mark[arow] = 0;
     }
+}
+
+// ---- validity cascade of the DEFAULT route, at anchor granularity (oryon_match_corrs_mx6[_araw], C_pad 256; DESIGN "default-route cascade").
+// The result needs the validity of every anchor (one witness query within the threshold) and the complete (m1, slice, m2) of the sampled
+// ones only.  On descriptors without the hard route's smoothness no whole panel settles, but row-major neighbours still match row-major
+// neighbours, so the tiles a panel's matches lie in are LEARNED: a probe of every DC stride-th anchor gets the complete screen, the range
+// of the probe's winning tiles (+ slack) is the panel's band, the band pass settles the rows that find their witness there, and only the
+// rows left open (no counterpart at all, or a match outside the band) get the complete scan, compacted into dense 512-row panels.
+// A row is COMPLETE (true triple over all tiles: probe rows, rows of a panel whose band is "all tiles", open rows after their scan) or
+// SETTLED (partial maximum above match_decide_lite_kernel's line: valid for sure, m2 = +inf i.e. argmin open, as match_panel_settle_kernel
+// leaves the rows of a settled panel).  Scores of an (anchor, query) pair do not depend on the panel the anchor row sits in, and the
+// merged triple not on how the tiles are dealt to splits (ties go to the lowest slice either way): complete triples are today's.
+constexpr uint8_t DC_COMPLETE = 0, DC_SETTLED = 1, DC_OPEN = 2;
+constexpr int DC_SLACK = 2;             // tiles added at either end of a learned band (ORYON_DC_SLACK in the dev build)
+constexpr int DC_MIN_SURE = 8;          // a panel with fewer valid-for-sure probe rows scans all tiles
+constexpr int DC_BAND_CAP_NUM = 1, DC_BAND_CAP_DEN = 2;     // ... and so does one whose band exceeds this share of the pair's tiles
+
+__device__ __forceinline__ float dc_sure_line(const float *__restrict__ a_err, const float *__restrict__ q_err, int p, float cut0)
+{
+    const float ea = a_err[p], eq = q_err[p];
+    const float delta = ea + eq + ea * eq + 1.2e-4f;
+    return delta < 0.2f ? cut0 + delta + 2e-5f : INFINITY;        // (match_decide_lite_kernel: m1 > cut0 + delta + 1e-5)
+}
+
+// merge of one row's per-split triples (the loop of match_decide_lite_kernel); element (split s, row r) at (p S + s) cap + r
+__device__ __forceinline__ void dc_merge(const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1, const float *__restrict__ ws_m2,
+                                         int p, int S, int cap, int r, float &m1, int &sid, float &m2)
+{
+    m1 = -INFINITY;
+    m2 = -INFINITY;
+    sid = 0;
+    for (int s = 0; s < S; ++s) {
+        const size_t o = ((size_t)p * S + s) * cap + r;
+        const float x1 = ws_m1[o], x2 = ws_m2[o];
+        m2 = fmaxf(fminf(m1, x1), fmaxf(m2, x2));
+        if (x1 > m1) { m1 = x1; sid = ws_i1[o]; }
+    }
+}
+
+// the probe: rows 0, stride, 2 stride, .. of every pair (a shape-only pattern; <= MX6_SAMPLED_PANEL of them: stride >= cap_a / 512)
+__global__ __launch_bounds__(256) void match_dc_probe_list_kernel(int stride, const int32_t *__restrict__ n_a, int32_t *__restrict__ n_probe,
+                                                                   int32_t *__restrict__ probe_idx)
+{
+    const int p = blockIdx.x;
+    int n = (n_a[p] + stride - 1) / stride;
+    n = n < MX6_SAMPLED_PANEL ? n : MX6_SAMPLED_PANEL;
+    for (int k = threadIdx.x; k < n; k += 256) probe_idx[(size_t)p * MX6_SAMPLED_PANEL + k] = k * stride;
+    if (threadIdx.x == 0) n_probe[p] = n;
+}
+
+// one workgroup per (1024-row panel, pair): the panel's probe rows get their complete triples, and the panel its band [first, count)
+__global__ __launch_bounds__(256) void match_dc_probe_band_kernel(int cap_a, int T8, int stride, int S, const int32_t *__restrict__ n_a,
+                                                                   const int32_t *__restrict__ n_q, const float *__restrict__ cs_m1,
+                                                                   const int32_t *__restrict__ cs_i1, const float *__restrict__ cs_m2,
+                                                                   const float *__restrict__ a_err, const float *__restrict__ q_err, float cut0,
+                                                                   float *__restrict__ r_m1, int32_t *__restrict__ r_i1, float *__restrict__ r_m2,
+                                                                   int32_t *__restrict__ band, int32_t *__restrict__ stats, int slack)
+{
+    __shared__ int lo, hi, cnt;
+    const int p = blockIdx.y, panel = blockIdx.x, t = threadIdx.x;
+    const int na = n_a[p], a0 = panel * 1024;
+    if (a0 >= na) return;
+    if (t == 0) { lo = 0x7fffffff; hi = -1; cnt = 0; }
+    __syncthreads();
+    const int a1 = a0 + 1024 < na ? a0 + 1024 : na;
+    const int k_lo = (a0 + stride - 1) / stride;
+    int k_hi = (a1 + stride - 1) / stride;
+    k_hi = k_hi < MX6_SAMPLED_PANEL ? k_hi : MX6_SAMPLED_PANEL;
+    const float line = dc_sure_line(a_err, q_err, p, cut0);
+    for (int k = k_lo + t; k < k_hi; k += 256) {
+        float m1, m2;
+        int sid;
+        dc_merge(cs_m1, cs_i1, cs_m2, p, S, MX6_SAMPLED_PANEL, k, m1, sid, m2);
+        const size_t arow = (size_t)p * cap_a + (size_t)k * stride;
+        r_m1[arow] = m1;
+        r_i1[arow] = sid;
+        r_m2[arow] = m2;
+        if (m1 > line) {
+            atomicMin(&lo, sid >> 3);               // 8 slices of 16 rows per 128-row tile
+            atomicMax(&hi, sid >> 3);
+            atomicAdd(&cnt, 1);
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        const int nqt = (n_q[p] + 127) / 128;
+        int first = lo - slack < 0 ? 0 : lo - slack, end = hi + slack + 1 < nqt ? hi + slack + 1 : nqt;
+        if (cnt < DC_MIN_SURE || (long long)(end - first) * DC_BAND_CAP_DEN > (long long)nqt * DC_BAND_CAP_NUM) { first = 0; end = nqt; }
+        band[(p * T8 + panel) * 2] = first;
+        band[(p * T8 + panel) * 2 + 1] = end - first;
+        atomicAdd(&stats[p * 4 + 3], end - first);
+        if (panel == 0) stats[p * 4 + 0] = (na + stride - 1) / stride < MX6_SAMPLED_PANEL ? (na + stride - 1) / stride : MX6_SAMPLED_PANEL;
+    }
+}
+
+// one workgroup per pair, after the band pass: every row that is no probe row gets its class and (unless open) its triple; the open rows
+// are listed in ascending order (the single-scan ordered compaction of match_list_sampled_amb_kernel)
+__global__ __launch_bounds__(256) void match_dc_settle_rows_kernel(int cap_a, int T8, int stride, int S, const int32_t *__restrict__ n_a,
+                                                                    const int32_t *__restrict__ n_q, const float *__restrict__ ws_m1,
+                                                                    const int32_t *__restrict__ ws_i1, const float *__restrict__ ws_m2,
+                                                                    const float *__restrict__ a_err, const float *__restrict__ q_err, float cut0,
+                                                                    const int32_t *__restrict__ band, float *__restrict__ r_m1,
+                                                                    int32_t *__restrict__ r_i1, float *__restrict__ r_m2, uint8_t *__restrict__ cls,
+                                                                    int32_t *__restrict__ n_open, int32_t *__restrict__ open_idx,
+                                                                    int32_t *__restrict__ stats)
+{
+    __shared__ int wave_cnt[4], wave_settled[4];
+    const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int na = n_a[p], nqt = (n_q[p] + 127) / 128;
+    const float line = dc_sure_line(a_err, q_err, p, cut0);
+    const int R = (cap_a + 255) / 256;
+    uint8_t *cl = cls + (size_t)p * cap_a;
+    int mine = 0, settled = 0;
+    for (int i = 0; i < R; ++i) {
+        const int a = t * R + i;
+        if (a >= na || a >= cap_a) break;
+        const size_t arow = (size_t)p * cap_a + a;
+        if (a % stride == 0 && a / stride < MX6_SAMPLED_PANEL) { cl[a] = DC_COMPLETE; continue; }      // probe row: written by the probe
+        const int32_t *b = band + (p * T8 + (a >> 10)) * 2;
+        const bool all = b[0] == 0 && b[1] == nqt;
+        float m1, m2;
+        int sid;
+        dc_merge(ws_m1, ws_i1, ws_m2, p, S, cap_a, a, m1, sid, m2);
+        uint8_t c;
+        if (all) c = DC_COMPLETE;
+        else if (m1 > line) { c = DC_SETTLED; m2 = INFINITY; ++settled; }       // no margin: a partial scan rules nothing out
+        else { c = DC_OPEN; ++mine; }
+        cl[a] = c;
+        if (c != DC_OPEN) { r_m1[arow] = m1; r_i1[arow] = sid; r_m2[arow] = m2; }
+    }
+    int incl = mine, sett = settled;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+        sett += __shfl_xor(sett, off);
+    }
+    if (lane == 63) { wave_cnt[wave] = incl; wave_settled[wave] = sett; }
+    __syncthreads();
+    int off0 = incl - mine;
+    for (int w = 0; w < wave; ++w) off0 += wave_cnt[w];
+    for (int i = 0; i < R; ++i) {
+        const int a = t * R + i;
+        if (a >= na || a >= cap_a) break;
+        if (cl[a] == DC_OPEN) open_idx[(size_t)p * cap_a + off0++] = a;
+    }
+    if (t == 255) {
+        n_open[p] = off0;
+        stats[p * 4 + 1] = wave_settled[0] + wave_settled[1] + wave_settled[2] + wave_settled[3];
+        stats[p * 4 + 2] = off0;
+    }
+}
+
+// complete triples of the open rows (scanned as compacted rows: [B, S, cap_a] indexed by list slot) -> the rows' merged arrays
+__global__ __launch_bounds__(256) void match_dc_scatter_open_kernel(int cap_a, int S, const int32_t *__restrict__ n_open,
+                                                                     const int32_t *__restrict__ open_idx, const float *__restrict__ ws_m1,
+                                                                     const int32_t *__restrict__ ws_i1, const float *__restrict__ ws_m2,
+                                                                     float *__restrict__ r_m1, int32_t *__restrict__ r_i1, float *__restrict__ r_m2)
+{
+    const int p = blockIdx.y, sl = blockIdx.x * 256 + threadIdx.x;
+    if (sl >= n_open[p] || sl >= cap_a) return;
+    float m1, m2;
+    int sid;
+    dc_merge(ws_m1, ws_i1, ws_m2, p, S, cap_a, sl, m1, sid, m2);
+    const size_t arow = (size_t)p * cap_a + open_idx[(size_t)p * cap_a + sl];
+    r_m1[arow] = m1;
+    r_i1[arow] = sid;
+    r_m2[arow] = m2;
 }
 
 // Exact resolution of ONE unambiguous anchor by one wave: candidates = rows of the winning 16-row slice within the int8 margin of its
@@ -554,6 +727,16 @@ struct LazyWs : Screen8RawWs {
     float *cs_max, *cs_m2;
     int32_t *cs_i1;
     int32_t *n_ambv0, *cs_gate;
+    // validity cascade of the default route (C_pad 256, three panels or more): merged per-row triples and classes, the probe and open
+    // lists, the panels' bands, the open rows' operands as dense 512-row panels, the per-split triples of its band and open passes;
+    // counters (zeroed every call).  All of it lives INSIDE q16 - the fp16 query rows of the eager route's fall-back, which no lazy step
+    // touches - so the workspace's size and layout are what they were
+    bool dc_ok;                         // false where the shape has no such cascade (or q16 is too small for its buffers)
+    uint8_t *dc_rows;
+    float *dc_m1, *dc_m2, *dc_ws_m1, *dc_ws_m2;
+    int32_t *dc_i1, *dc_ws_i1, *dc_probe_idx, *dc_open_idx, *dc_band, *dc_n_probe, *dc_n_open, *dc_stats;
+    uint8_t *dc_cls;
+    size_t dc_zero_bytes;               // from dc_n_probe on
     size_t lazy_zero_off, lazy_zero_bytes;      // the second zeroed region (ScreenWs has the first)
 };
 
@@ -562,6 +745,53 @@ int sampled_cap(int corr_rows, int cap_a)
 {
     const int cap_s0 = (corr_rows + 127) / 128 * 128;
     return cap_s0 < cap_a ? cap_s0 : cap_a;
+}
+
+// The default route's cascade is chosen by shape alone: three 1024-row panels or more (below that the 512-row probe is no small
+// fraction of the anchors; the sample-first first stage has one panel), the second pass's 512-row panel large enough for the sample
+bool dc_shape(int C, int cap_a, int corr_rows) { return C == 256 && corr_rows <= MX6_SAMPLED_PANEL && mx6_panels_per_pair(cap_a) >= 3; }
+// (ORYON_DC_STRIDE / _SLACK / _BAND_SPLITS / _OPEN_SPLITS: the dev build's overrides, for sweeps; the shipped library reads none)
+int dc_probe_stride(int cap_a)
+{
+    static const int want = dev_env_int("ORYON_DC_STRIDE", 10);
+    const int s = (cap_a + MX6_SAMPLED_PANEL - 1) / MX6_SAMPLED_PANEL;
+    return s > want ? s : want;
+}
+// splits of the band pass (8-wave workgroups, one per CU: ~5 per CU) and of the open rows' scan (4-wave workgroups, two per CU)
+int dc_band_splits(int B, int cap_a)
+{
+    static const int force = dev_env_int("ORYON_DC_BAND_SPLITS", 0);
+    const int u = B * mx6_panels_per_pair(cap_a), s = force > 0 ? force : (1280 + u - 1) / u;
+    return s < 1 ? 1 : s > 16 ? 16 : s;
+}
+int dc_open_splits(int B)
+{
+    static const int force = dev_env_int("ORYON_DC_OPEN_SPLITS", 0);
+    const int s = force > 0 ? force : (1024 + B - 1) / B;
+    return s < 1 ? 1 : s > 16 ? 16 : s;
+}
+size_t carve_dc(void *base, LazyWs &w, int B, int C, int cap_a)
+{
+    Carver carve(base);
+    const size_t rows = (size_t)B * cap_a, pairs = (size_t)B;
+    const size_t S = 16;                                    // the most either pass uses (dc_band_splits, dc_open_splits)
+    carve(w.dc_rows, rows * C);
+    carve(w.dc_m1, rows);
+    carve(w.dc_m2, rows);
+    carve(w.dc_i1, rows);
+    carve(w.dc_cls, rows);
+    carve(w.dc_open_idx, rows);
+    carve(w.dc_probe_idx, pairs * MX6_SAMPLED_PANEL);
+    carve(w.dc_band, pairs * mx6_panels_per_pair(cap_a) * 2);
+    carve(w.dc_ws_m1, rows * S);
+    carve(w.dc_ws_m2, rows * S);
+    carve(w.dc_ws_i1, rows * S);
+    const size_t zero_off = carve.off;
+    carve(w.dc_n_probe, pairs);
+    carve(w.dc_n_open, pairs);
+    carve(w.dc_stats, pairs * 4);
+    w.dc_zero_bytes = carve.off - zero_off;
+    return carve.off;
 }
 
 size_t carve_lazy(void *base, LazyWs &w, int B, int C, int cap_a, int cap_q, int S, int corr_rows)
@@ -598,6 +828,15 @@ size_t carve_lazy(void *base, LazyWs &w, int B, int C, int cap_a, int cap_q, int
     carve(w.cs_i1, triples);
     carve(w.n_ambv0, pairs);
     carve(w.cs_gate, pairs * mx6_panels_per_pair(cap_a));
+    w.dc_ok = false;
+    w.dc_stats = nullptr;
+    if (dc_shape(C, cap_a, corr_rows)) {
+        LazyWs sized;
+        if (carve_dc(nullptr, sized, B, C, cap_a) <= (size_t)B * cap_q * C * sizeof(__half)) {
+            carve_dc(w.q16, w, B, C, cap_a);
+            w.dc_ok = true;
+        }
+    }
     w.lazy_zero_off = carve.off;
     carve(w.pair_eager, pairs);
     carve(w.n_unc, pairs);
@@ -616,6 +855,13 @@ extern "C" size_t oryon_match_corrs_i8_workspace_bytes(int B, int C, int cap_a, 
     if (B <= 0 || C <= 0 || cap_a <= 0 || cap_a % MT16 || cap_q <= 0 || corr_rows <= 0) return 0;
     LazyWs w;
     return carve_lazy(nullptr, w, B, C, cap_a, cap_q, pick_split16(B, cap_a / MT16), corr_rows);
+}
+
+int32_t *oryon::match_dc_stats(void *workspace, int B, int C, int cap_a, int cap_q, int corr_rows)
+{
+    LazyWs w;
+    carve_lazy(workspace, w, B, C, cap_a, cap_q, pick_split16(B, cap_a / MT16), corr_rows);
+    return w.dc_ok ? w.dc_stats : nullptr;
 }
 
 namespace {
@@ -655,7 +901,7 @@ void compact_anchors(const MatchCorrsArgs &m, const AnchorRaw &araw, const LazyW
                            st, araw, m.C_true, m.HW, m.round_f16, m.C, m.cap_a, cap_c, count, idx, idx_stride, w.a_hat_c);
 }
 
-int lazy_route(const MatchCorrsArgs &m, const LazyWs &w, hipStream_t st, int use_x3, bool cascade)
+int lazy_route(const MatchCorrsArgs &m, const LazyWs &w, hipStream_t st, int use_x3, bool cascade, bool dc)
 {
     const int B = m.B, C = m.C, cap_a = m.cap_a, cap_q = m.cap_q, corr_rows = m.corr_rows;
     const bool nhwc = m.layout == ORYON_LAYOUT_NHWC;
@@ -691,12 +937,12 @@ int lazy_route(const MatchCorrsArgs &m, const LazyWs &w, hipStream_t st, int use
         // second pass: the complete screen for the listed rows (one 512-row panel per pair), triples merged back, list rebuilt
         const int csS = mx6_sampled_splits(B);
         hipLaunchKernelGGL(match_compact_rows_kernel, dim3(MX6_SAMPLED_PANEL / 16, B), dim3(256), 0, st, reinterpret_cast<const uint8_t *>(m.a_i8),
-                           C, cap_a, MX6_SAMPLED_PANEL, w.n_ambv, w.ambv_idx, corr_rows, w.cs_panel);
+                           C, cap_a, MX6_SAMPLED_PANEL, w.n_ambv, w.ambv_idx, corr_rows, w.cs_panel, MX6_SAMPLED_PANEL);
         launch_screen_mx6_sampled(st, w.cs_panel, reinterpret_cast<const uint8_t *>(m.q_i8), B, cap_q, w.n_ambv, m.n_q, csS, w.cs_max, w.cs_i1,
                                   w.cs_m2, m.C_true);
         hipLaunchKernelGGL(match_decide_sampled_kernel, dim3((MX6_SAMPLED_PANEL + 255) / 256, B), dim3(256), 0, st, cap_a, MX6_SAMPLED_PANEL, csS,
                            w.n_ambv, w.ambv_idx, corr_rows, w.cs_max, w.cs_i1, w.cs_m2, m.a_scale, m.q_eps_max, w.m_final, w.sid_final,
-                           w.margin, w.state, w.mark, w.n_ambv0);
+                           w.margin, w.state, w.mark, w.n_ambv0, dc ? m.min_dist : nullptr);
         hipLaunchKernelGGL(match_list_sampled_amb_kernel, dim3(B), dim3(256), 0, st, cap_a, w.state, w.pair_eager, m.n_sel, w.sel_rows,
                            corr_rows, w.mark, w.n_ambv, w.ambv_idx);
         if ((rc = check_launch(IMPL))) return rc;
@@ -781,6 +1027,7 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
     ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(m.workspace) + w.zero_off, 0, w.zero_bytes, st));
     if (m.force_eager) ORYON_CHECK_HIP(hipMemsetAsync(w.need_f32, 0, (size_t)B * sizeof(int32_t), st));     // only the eager route reads it
     ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(m.workspace) + w.lazy_zero_off, 0, w.lazy_zero_bytes, st));
+    if (w.dc_ok && m.fmt == 1) ORYON_CHECK_HIP(hipMemsetAsync(w.dc_n_probe, 0, w.dc_zero_bytes, st));     // the cascade's counters read zero after any other route
     const float cut0 = 1.0f - 2.0f * m.threshold;
     // second level for the sampled anchors no screen can separate: fp16x3 two-sweep scan (K1x3, match_x3.hip; C_pad 256) instead of the
     // exact fp32 scan - same results, hard-descriptor step 9.8 -> 8.5 ms; ~30 us of empty launches per step when no anchor needs it.
@@ -791,6 +1038,11 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
     // the screen stops a panel whose anchors are all valid for sure, and a second, complete pass serves the sampled anchors only
     static const bool cascade_env = dev_env_int("ORYON_CASCADE", 1) != 0;
     const bool cascade = cascade_env && m.fmt == 1 && use_x3 && m.q_hi_lo != nullptr && w.cs_panel != nullptr;
+    // the default route's own cascade, at anchor granularity (kernels above: match_dc_*): by shape and the caller's knob alone
+    const bool dc = m.cascade != 0 && m.fmt == 1 && use_x3 && m.q_hi_lo == nullptr && w.cs_panel != nullptr && w.dc_ok;
+    int S_dec = S;                                                          // what match_decide_lite_kernel merges: the splits' triples ..
+    const float *dec_m1 = w.ws_max, *dec_m2 = w.ws_m2;
+    const int32_t *dec_i1 = w.ws_i1;
     if (m.fmt == 1) {
         const uint8_t *a6 = reinterpret_cast<const uint8_t *>(m.a_i8), *q6 = reinterpret_cast<const uint8_t *>(m.q_i8);
         const int groups = ((B * S + 7) / 8) * 8 * T;
@@ -803,6 +1055,36 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
             hipLaunchKernelGGL(match_panel_settle_kernel, dim3(T8, B), dim3(256), 0, st, cap_a, T8, S, m.n_a, w.ws_max, w.ws_m2, m.a_scale,
                                m.q_eps_max, cut0, w.cs_gate);
             launch_screen_mx6(C, groups, T, st, a6, q6, B, cap_a, cap_q, m.n_a, m.n_q, S, w.ws_max, w.ws_i1, w.ws_m2, m.C_true, 1, w.cs_gate, 0);
+        } else if (dc) {
+            const int T8 = mx6_panels_per_pair(cap_a), stride = dc_probe_stride(cap_a), csS = mx6_sampled_splits(B);
+            const int Sb = dc_band_splits(B, cap_a), So = dc_open_splits(B);
+            static const int slack = dev_env_int("ORYON_DC_SLACK", DC_SLACK);
+            static const int open_panel = dev_env_int("ORYON_DC_OPEN_PANEL", 0) == 1024 ? 1024 : MX6_SAMPLED_PANEL;
+            // (1) probe: every stride-th anchor, compacted into the second pass's panel, screened completely; triples and bands
+            hipLaunchKernelGGL(match_dc_probe_list_kernel, dim3(B), dim3(256), 0, st, stride, m.n_a, w.dc_n_probe, w.dc_probe_idx);
+            hipLaunchKernelGGL(match_compact_rows_kernel, dim3(MX6_SAMPLED_PANEL / 16, B), dim3(256), 0, st, a6, C, cap_a, MX6_SAMPLED_PANEL,
+                               w.dc_n_probe, w.dc_probe_idx, MX6_SAMPLED_PANEL, w.cs_panel, MX6_SAMPLED_PANEL);
+            launch_screen_mx6_sampled(st, w.cs_panel, q6, B, cap_q, w.dc_n_probe, m.n_q, csS, w.cs_max, w.cs_i1, w.cs_m2, m.C_true);
+            hipLaunchKernelGGL(match_dc_probe_band_kernel, dim3(T8, B), dim3(256), 0, st, cap_a, T8, stride, csS, m.n_a, m.n_q, w.cs_max, w.cs_i1,
+                               w.cs_m2, m.a_scale, m.q_eps_max, cut0, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_band, w.dc_stats, slack);
+            // (2) band pass over all rows, (3) classes, merged triples, ordered list of the open rows
+            launch_screen_mx6(C, ((B * Sb + 7) / 8) * 8 * T, T, st, a6, q6, B, cap_a, cap_q, m.n_a, m.n_q, Sb, w.dc_ws_m1, w.dc_ws_i1, w.dc_ws_m2, m.C_true,
+                              1, nullptr, 0, w.dc_band);
+            hipLaunchKernelGGL(match_dc_settle_rows_kernel, dim3(B), dim3(256), 0, st, cap_a, T8, stride, Sb, m.n_a, m.n_q, w.dc_ws_m1, w.dc_ws_i1,
+                               w.dc_ws_m2, m.a_scale, m.q_eps_max, cut0, w.dc_band, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_cls, w.dc_n_open, w.dc_open_idx,
+                               w.dc_stats);
+            // (4) complete scan of the open rows as dense 512-row panels (count-gated), triples scattered back
+            hipLaunchKernelGGL(match_compact_rows_kernel, dim3(cap_a / 16, B), dim3(256), 0, st, a6, C, cap_a, cap_a, w.dc_n_open, w.dc_open_idx,
+                               cap_a, w.dc_rows, open_panel);
+            if (open_panel == 1024)     // the sweep's alternative (dev build): the 8-wave kernel over 1024-row panels of the compacted rows
+                launch_screen_mx6(C, ((B * So + 7) / 8) * 8 * T, T, st, w.dc_rows, q6, B, cap_a, cap_q, w.dc_n_open, m.n_q, So, w.dc_ws_m1, w.dc_ws_i1,
+                                  w.dc_ws_m2, m.C_true);
+            else
+                launch_screen_mx6_rows512(st, w.dc_rows, q6, B, cap_a, cap_q, w.dc_n_open, m.n_q, So, w.dc_ws_m1, w.dc_ws_i1, w.dc_ws_m2, m.C_true);
+            hipLaunchKernelGGL(match_dc_scatter_open_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, So, w.dc_n_open, w.dc_open_idx,
+                               w.dc_ws_m1, w.dc_ws_i1, w.dc_ws_m2, w.dc_m1, w.dc_i1, w.dc_m2);
+            S_dec = 1;                                                      // .. or the rows' merged ones
+            dec_m1 = w.dc_m1; dec_i1 = w.dc_i1; dec_m2 = w.dc_m2;
         } else {
             launch_screen_mx6(C, groups, T, st, a6, q6, B, cap_a, cap_q, m.n_a, m.n_q, S, w.ws_max, w.ws_i1, w.ws_m2, m.C_true);
         }
@@ -811,13 +1093,13 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
         screen8_step(m, S, m.n_a, w);
     }
     ORYON_CHECK_LAUNCH();
-    hipLaunchKernelGGL(match_decide_lite_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, m.n_a, S, w.ws_max, w.ws_i1, w.ws_m2, m.a_scale,
+    hipLaunchKernelGGL(match_decide_lite_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, m.n_a, S_dec, dec_m1, dec_i1, dec_m2, m.a_scale,
                        m.q_eps_max, cut0, sqrtf((float)m.C_true), (float)m.C_true, m.force_eager, m.fmt, use_x3, w.m_final, w.sid_final, w.margin,
                        w.state, m.valid, m.min_dist, m.argmin, w.pair_eager, w.n_unc, w.unc_idx, w.n_ambu, w.ambu_idx, w.need_f32_lazy,
                        w.n_amb_total);
     hipLaunchKernelGGL(match_mask_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, m.n_a, w.pair_eager, w.n_a_eager, w.n_a_lazy);
     ORYON_CHECK_LAUNCH();
-    if (!m.force_eager) return lazy_route(m, w, st, use_x3, cascade);
+    if (!m.force_eager) return lazy_route(m, w, st, use_x3, cascade || dc, dc);
     const int rc = eager_route(m, w, S);
     if (rc) return rc;
     if (m.n_undecided) ORYON_CHECK_HIP(hipMemcpyAsync(m.n_undecided, w.n_amb, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));

@@ -438,11 +438,15 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
 //              their partial triples with m2 = +inf (no margin: argmin open, which is what every anchor of such maps is anyway), and
 //              the SAMPLED anchors get the complete screen in a second pass over one 512-row panel per pair (match_corrs_lazy_impl).
 // (An in-loop early exit was built first: the break cost the loop its register allocation - 161 spilled registers, six times slower per tile.)
+// The default route's cascade (round 10; match_corrs.hip, match_dc_*) uses a third placement:
+//   band     : every panel scans the tiles [first, first + count) its entry of `band` names - the range its probe rows' matches lie in,
+//              learned per pair and panel by match_dc_probe_band_kernel - dealt evenly to the S splits of the launch.
 template <int CP, int WAVES, int KL = CP / 64>
 __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_screen_w4_win_kernel(
     const uint8_t *__restrict__ a6, const uint8_t *__restrict__ q6, int B, int cap_a, int cap_q, const int32_t *__restrict__ n_a,
     const int32_t *__restrict__ n_q, int T, int S, float *__restrict__ ws_max, int32_t *__restrict__ ws_i1, float *__restrict__ ws_m2,
-    const int32_t *__restrict__ gate /* [B, T] or NULL: only panels with a non-zero entry run */, int win /* > 0: that many tiles of the split */)
+    const int32_t *__restrict__ gate /* [B, T] or NULL: only panels with a non-zero entry run */, int win /* > 0: that many tiles of the split */,
+    const int32_t *__restrict__ band /* [B, T, 2] or NULL: the panel scans tiles [first, first + count), dealt evenly to the S splits */)
 {
     static_assert(CP == 256 || (CP == 512 && WAVES == 4), "geometries: C_pad 256 with 4 / 8 waves, C_pad 512 with 4 waves");
     constexpr int RB = CP, NAB = 4;
@@ -479,6 +483,13 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
         k0 = k0 < 0 ? 0 : (k0 > cnt - win ? cnt - win : k0);
         qt_begin += k0;
         qt_end = qt_begin + win;
+    }
+    if (band) {
+        // default-route cascade: the band match_dc_probe_band_kernel learned for this panel from the probe rows' matches
+        const int first = band[(p * T + panel) * 2], cnt = band[(p * T + panel) * 2 + 1];
+        const int per = (cnt + S - 1) / S;
+        qt_begin = first + split * per;
+        qt_end = (qt_begin + per < first + cnt) ? qt_begin + per : first + cnt;
     }
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
     const char *qp = reinterpret_cast<const char *>(q6) + (size_t)p * cap_q * RB;
@@ -679,7 +690,7 @@ namespace {
 template <int CP>
 void launch_screen_mx6_t(int groups, int T, hipStream_t st, const uint8_t *a6, const uint8_t *q6, int B, int cap_a, int cap_q, const int32_t *n_a,
                        const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int kl = 0, bool gate_or_win = false,
-                       const int32_t *gate = nullptr, int win = 0)
+                       const int32_t *gate = nullptr, int win = 0, const int32_t *band = nullptr)
 {
     // C_pad 256: 512-anchor panels (8 waves; `groups` was sized for 256-anchor panels, T of them per unit).  C_pad 512: the stationary
     // operand is 128 registers, so 4 waves per workgroup and one workgroup per CU (512 registers per wave), as the int8 kernel
@@ -702,10 +713,10 @@ void launch_screen_mx6_t(int groups, int T, hipStream_t st, const uint8_t *a6, c
             if (dbg && !dbg_wg) (void)hipMalloc(&dbg_wg, (size_t)65536 * 4 * sizeof(long long));
             if (dbg && dbg_wg && g8 <= 65536) (void)hipMemsetAsync(dbg_wg, 0, (size_t)g8 * 4 * sizeof(long long), st);
             if (gate_or_win) {
-                // the cascade's launches: windowed (win > 0) or gated (gate != NULL) copy of the kernel
+                // the cascades' launches: windowed (win > 0), gated (gate != NULL) or banded (band != NULL) copy of the kernel
 #define ORYON_LAUNCH_WIN(KLV)                                                                                                         \
     hipLaunchKernelGGL((match_mx6_screen_w4_win_kernel<CP, 8, KLV>), dim3(g8), dim3(512), 0, st, a6, q6, B, cap_a, cap_q, n_a, n_q, T8, S,   \
-                       ws_max, ws_i1, ws_m2, gate, win)
+                       ws_max, ws_i1, ws_m2, gate, win, band)
                 if (kl == 1) ORYON_LAUNCH_WIN(1);
                 else if (kl == 2) ORYON_LAUNCH_WIN(2);
                 else ORYON_LAUNCH_WIN(4);
@@ -753,32 +764,41 @@ const char *screen_mx6_name(int C)
 
 void launch_screen_mx6(int C, int groups, int T, hipStream_t st, const uint8_t *a6, const uint8_t *q6, int B, int cap_a, int cap_q,
                        const int32_t *n_a, const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true,
-                       int cascade, const int32_t *gate, int win)
+                       int cascade, const int32_t *gate, int win, const int32_t *band)
 {
     // live k-steps of narrow maps (1 for C <= 64, 2 for C <= 128; otherwise all four): see match_mx6_screen_w4_kernel
     const int kl = (C == 256 && C_true > 0 && C_true <= 64) ? 1 : (C == 256 && C_true > 0 && C_true <= 128) ? 2 : 0;
     // cascade != 0 (C_pad 256 only): the windowed / gated launches of the validity cascade (match_mx6_screen_w4_win_kernel)
-    if (C == 256) launch_screen_mx6_t<256>(groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, ws_max, ws_i1, ws_m2, kl, cascade != 0, gate, win);
+    if (C == 256) launch_screen_mx6_t<256>(groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, ws_max, ws_i1, ws_m2, kl, cascade != 0, gate, win, band);
     else launch_screen_mx6_t<512>(groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, ws_max, ws_i1, ws_m2);
 }
 
-// Second pass of the validity cascade: the complete screen over ONE 512-row panel per pair (the sampled anchors whose argmin is open,
-// compacted by match_compact_rows_kernel), the query tiles of a pair dealt to S workgroups of four waves (two per CU): a tenth of the
-// first pass's multiply-accumulates, spread over the whole chip.  Same kernel, same scores, same slice ids as the full screen.
+// The complete screen over compacted anchor rows in 512-row panels (match_compact_rows_kernel): T = ceil(cap_rows / 512) panels per pair,
+// the query tiles of a pair dealt to S workgroups of four waves (two per CU) per panel; panels beyond a pair's row count return at once.
+// Same kernel, same scores, same slice ids as the full screen.  Triples come out as [B, S, cap_rows].
+void launch_screen_mx6_rows512(hipStream_t st, const uint8_t *a6_rows, const uint8_t *q6, int B, int cap_rows, int cap_q, const int32_t *n_rows,
+                               const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true)
+{
+    const int T = (cap_rows + 511) / 512;
+    const int groups = ((B * S + 7) / 8) * 8 * T;
+    const int kl = (C_true > 0 && C_true <= 64) ? 1 : (C_true > 0 && C_true <= 128) ? 2 : 0;
+    if (kl == 1)
+        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4, 1>), dim3(groups), dim3(256), 0, st, a6_rows, q6, B, cap_rows, cap_q, n_rows, n_q, T, S,
+                           ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
+    else if (kl == 2)
+        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4, 2>), dim3(groups), dim3(256), 0, st, a6_rows, q6, B, cap_rows, cap_q, n_rows, n_q, T, S,
+                           ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
+    else
+        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4>), dim3(groups), dim3(256), 0, st, a6_rows, q6, B, cap_rows, cap_q, n_rows, n_q, T, S,
+                           ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
+}
+
+// Second pass of the validity cascades: ONE 512-row panel per pair (the sampled anchors whose argmin is open): a tenth of the full
+// screen's multiply-accumulates, spread over the whole chip.
 void launch_screen_mx6_sampled(hipStream_t st, const uint8_t *a6_panel, const uint8_t *q6, int B, int cap_q, const int32_t *n_rows,
                                const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true)
 {
-    const int groups = ((B * S + 7) / 8) * 8;                      // T = 1 panel per (pair, split) unit
-    const int kl = (C_true > 0 && C_true <= 64) ? 1 : (C_true > 0 && C_true <= 128) ? 2 : 0;
-    if (kl == 1)
-        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4, 1>), dim3(groups), dim3(256), 0, st, a6_panel, q6, B, 512, cap_q, n_rows, n_q, 1, S,
-                           ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
-    else if (kl == 2)
-        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4, 2>), dim3(groups), dim3(256), 0, st, a6_panel, q6, B, 512, cap_q, n_rows, n_q, 1, S,
-                           ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
-    else
-        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4>), dim3(groups), dim3(256), 0, st, a6_panel, q6, B, 512, cap_q, n_rows, n_q, 1, S,
-                           ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
+    launch_screen_mx6_rows512(st, a6_panel, q6, B, MX6_SAMPLED_PANEL, cap_q, n_rows, n_q, S, ws_max, ws_i1, ws_m2, C_true);
 }
 
 }  // namespace oryon

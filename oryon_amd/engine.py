@@ -106,7 +106,7 @@ class NativeStep:
 
     def __init__(self, solver: Optional[PointDSC], cfg: "MatchPoseConfig", key: Tuple, dev: torch.device, overlap: int, n_slots: int = 6,
                  gather_sets: int = 2, reg_streams: int = 2, reg_lag: int = 0, screen: int = 1, x3_prefetch: int = 1,
-                 stream_roles: int = 0):
+                 stream_roles: int = 0, screen_cascade: int = 1):
         B, C, FH, FW, HA, WA, HQ, WQ, layout = key
         self.key, self.dev = key, dev
         if overlap >= 2:
@@ -124,7 +124,7 @@ class NativeStep:
                                       reg_lag=reg_lag if overlap else 0, screen=screen,
                                       sample_first=int(cfg.sample_first) if cfg.sample_first and cfg.sample_first > 0 else 0,
                                       x3_prefetch=int(bool(x3_prefetch)) if (C <= 256 and screen == 1) else 0,
-                                      stream_roles=int(stream_roles), solver=int(ransac), ransac_max_iter=int(cfg.ransac_max_iter),
+                                      stream_roles=int(stream_roles), screen_cascade=int(bool(screen_cascade)), solver=int(ransac), ransac_max_iter=int(cfg.ransac_max_iter),
                                       ransac_match_err=float(cfg.ransac_match_err), ransac_fix_percent=float(cfg.ransac_fix_percent))
         self.cfg_sig = _cfg_sig(cfg, overlap)
         need = lib().oryon_engine_arena_bytes(ctypes.byref(self.ecfg), handle)
@@ -206,6 +206,13 @@ class NativeStep:
         check(lib().oryon_engine_x3_steps(self._h, ctypes.byref(n)))
         return n.value
 
+    def cascade_stats(self) -> Tensor:
+        """[B, 4] int32 (host): per pair the probe rows, settled rows, open rows and band tiles of the most recent submit's default-route
+        validity cascade (oryon_engine_config_t.screen_cascade); zeros when it took another route.  Synchronises the device."""
+        out = torch.zeros((self.geo["B"], 4), dtype=torch.int32)
+        check(lib().oryon_engine_cascade_stats(self._h, out.data_ptr()), "oryon_engine_cascade_stats")
+        return out
+
     def feedback(self) -> Optional[Tuple[int, int, int]]:
         """(step, undecided anchors, anchors) of the newest completed step from the engine's own pinned-memory feedback (MX-fp6 screen),
         or None - no device copy, no read of a slot buffer, never waits."""
@@ -261,7 +268,7 @@ class MatchPoseEngine:
         self.result_views = result_views
         self._native: Optional[NativeStep] = None
         self._inflight: Dict[int, Dict[str, Tensor]] = {}       # slot -> result dict of the native step that last used it
-        self.native_geometry = dict(n_slots=6, gather_sets=2, reg_streams=2, reg_lag=0, screen=1, x3_prefetch=1, stream_roles=0)      # NativeStep's pipeline depth / placement (see oryon_engine_config_t)
+        self.native_geometry = dict(n_slots=6, gather_sets=2, reg_streams=2, reg_lag=0, screen=1, x3_prefetch=1, stream_roles=0, screen_cascade=1)      # NativeStep's pipeline depth / placement (see oryon_engine_config_t)
         self.native_timing = False          # bracket the sections of every native step with HIP events (NativeStep.timing)
         self._reg_stream = None
         self.reg_streams = 2

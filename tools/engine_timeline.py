@@ -24,7 +24,7 @@ inp["cam"] = inp["cam"].reshape(B, 9).float().contiguous()
 ser = bool(os.environ.get("ENG_SERIAL"))
 eng = MatchPoseEngine(bench.build_solver(dev), MatchPoseConfig(), overlap_registration=not ser, overlap_gather=not ser, native=True, result_views=True)
 eng.native_timing = not os.environ.get("ENG_NO_TIMING")
-for k_ in ("n_slots", "gather_sets", "reg_streams", "reg_lag", "screen", "x3_prefetch"):
+for k_ in ("n_slots", "gather_sets", "reg_streams", "reg_lag", "screen", "x3_prefetch", "screen_cascade"):
     if os.environ.get("ENG_" + k_.upper()):
         eng.native_geometry[k_] = int(os.environ["ENG_" + k_.upper()])
 if os.environ.get("ENG_PYTHON"):
@@ -93,3 +93,9 @@ print("absolute ms since the gather start of step", first, ": step  G[begin end]
 for k in range(first, nat.steps):
     ts = [nat.elapsed(first, 0, k, ev) for ev in range(8)]
     print(f"{k:4d}  G[{ts[0]:7.2f} {ts[1]:7.2f}]  M[{ts[2]:7.2f} {ts[3]:7.2f}] ({ts[4]:7.2f} {ts[5]:7.2f})  R[{ts[6]:7.2f} {ts[7]:7.2f}]")
+st = nat.cascade_stats().double()
+if st.any():
+    tiles = (inp["mask_q"].reshape(B, -1).sum(1).cpu().double() + 127) // 128
+    panels = (inp["mask_a"].reshape(B, -1).sum(1).cpu().double().clamp(max=MatchPoseConfig().src_sampling) + 1023) // 1024
+    print(f"default-route cascade, mean per pair: probe {st[:, 0].mean():.0f}  settled {st[:, 1].mean():.0f}  open {st[:, 2].mean():.0f} "
+          f"(max {st[:, 2].max():.0f})  band share of the tiles {(st[:, 3] / (panels * tiles)).mean():.3f} (max {(st[:, 3] / (panels * tiles)).max():.3f})")
