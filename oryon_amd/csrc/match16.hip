@@ -25,6 +25,7 @@
 #include <type_traits>
 #include "common.h"
 #include "match_common.h"
+#include "screen_tile.h"
 
 namespace oryon {
 
@@ -242,23 +243,8 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_f16_screen_kerne
             if (hi == 0) ws_max[((size_t)p * S + split) * cap_a + a] = m;
         }
     }
-    if (MODE == 2) {
-#pragma unroll
-        for (int ab = 0; ab < NAB; ++ab) {
-            const float om1 = __shfl_xor(runmax[ab], 32), om2 = __shfl_xor(run2[ab], 32);
-            const int oi1 = __shfl_xor(runidx[ab], 32);
-            const float m1 = fmaxf(runmax[ab], om1);
-            const float m2 = fmaxf(fminf(runmax[ab], om1), fmaxf(run2[ab], om2));
-            const int i1 = (om1 > runmax[ab]) ? oi1 : runidx[ab];
-            const int a = a0 + wave * 64 + ab * 32 + l31;
-            if (hi == 0) {
-                const size_t o = ((size_t)p * S + split) * cap_a + a;
-                ws_max[o] = m1;
-                ws_i1[o] = i1;
-                ws_m2[o] = m2;
-            }
-        }
-    }
+    // (cap_a is a multiple of this kernel's 256-anchor panels: the helper's a < cap_a holds for every lane)
+    if (MODE == 2) screen_merge_store<NAB>(runmax, run2, runidx, a0 + wave * 64 + l31, hi, (size_t)p * S + split, cap_a, ws_max, ws_i1, ws_m2);
 }
 
 // Single-pass strategy, step 2 (one wave per anchor): merge the per-split (m1, slice of m1, m2) triples and decide
@@ -587,9 +573,7 @@ __global__ void match_need_f32_kernel(int B, const int32_t *__restrict__ n_amb, 
 //                                  fp32 re-scoring (unchanged)
 //   otherwise                   -> the anchor is handed to the fp16 screening (compacted set, complete K1s pipeline), so the int8
 //                                  stage can only ever lose time, never exactness.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
-constexpr int screen8_tile_bytes(int CP) { return CP * 128; }     // 128 query rows per tile
 
 template <int CP>
 __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_i8_screen_kernel(
@@ -599,11 +583,9 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_i8_screen_kernel
 {
     constexpr int RB = CP;                       // row bytes
     constexpr int TILE_BYTES = screen8_tile_bytes(CP);
-    constexpr int ROWS = 128, NQB = 4, NAB = 2;
+    constexpr int NQB = 4, NAB = 2;
     constexpr int NKS = CP / 32;                 // MFMA k-steps
     constexpr int NI = TILE_BYTES / 4096;
-    constexpr int LPR = RB / 256;
-    static_assert(LPR >= 1, "rows are whole 256-byte lines");
     char *smem;
     if constexpr (2 * TILE_BYTES > 65536) {
         extern __shared__ __attribute__((aligned(256))) char smem_dyn8[];
@@ -612,18 +594,11 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_i8_screen_kernel
         __shared__ __attribute__((aligned(256))) char smem_st8[2 * TILE_BYTES];
         smem = smem_st8;
     }
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int unit = (slot / T) * 8 + xcd;
-    if (unit >= B * S) return;
-    const int panel = slot % T;
-    const int p = unit / S, split = unit % S;
-    const int na = n_a[p], nq = n_q[p];
-    const int a0 = panel * MT16;
-    if (a0 >= na) return;
-    const int nqt = (nq + ROWS - 1) / ROWS;
-    const int qt_per = (nqt + S - 1) / S;
-    const int qt_begin = split * qt_per;
-    const int qt_end = (qt_begin + qt_per < nqt) ? qt_begin + qt_per : nqt;
+    ScreenUnit u;
+    if (!screen_unit_decode(u, MT16, B, T, S, n_a, n_q)) return;
+    const int p = u.p, split = u.split, a0 = u.a0;
+    int qt_begin, qt_end;
+    screen_split_tiles(u, S, qt_begin, qt_end);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
     const char *qp = reinterpret_cast<const char *>(q8) + (size_t)p * cap_q * RB;
     const float2 *qs = reinterpret_cast<const float2 *>(q_scale + (size_t)p * (cap_q / 16));    // (h = 0, h = 1) per 32-row block
@@ -637,13 +612,7 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_i8_screen_kernel
         for (int s = 0; s < NKS; ++s) breg[ab][s] = *reinterpret_cast<const i32x4 *>(arow + 32 * s);
     }
     unsigned dma_off[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int line = (wave * NI + j) * 4 + (lane >> 4), sl = lane & 15;
-        const int row = line / LPR;
-        const int cc = sl ^ (row & 15);
-        dma_off[j] = (unsigned)(row * RB + ((line % LPR) * 16 + cc) * 16);
-    }
+    screen_dma_offsets<RB>(dma_off, wave * NI, lane);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     auto issue = [&](int qt, int buf) {
         const char *qb = qp + (size_t)qt * TILE_BYTES;
@@ -723,21 +692,8 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_i8_screen_kernel
         __syncthreads();
         buf ^= 1;
     }
-#pragma unroll
-    for (int ab = 0; ab < NAB; ++ab) {
-        const float om1 = __shfl_xor(runmax[ab], 32), om2 = __shfl_xor(run2[ab], 32);
-        const int oi1 = __shfl_xor(runidx[ab], 32);
-        const float m1 = fmaxf(runmax[ab], om1);
-        const float m2 = fmaxf(fminf(runmax[ab], om1), fmaxf(run2[ab], om2));
-        const int i1 = (om1 > runmax[ab]) ? oi1 : runidx[ab];
-        const int a = a0 + wave * 64 + ab * 32 + l31;
-        if (hi == 0) {
-            const size_t o = ((size_t)p * S + split) * cap_a + a;
-            ws_max[o] = m1;
-            ws_i1[o] = i1;
-            ws_m2[o] = m2;
-        }
-    }
+    // (cap_a is a multiple of this kernel's 256-anchor panels: the helper's a < cap_a holds for every lane)
+    screen_merge_store<NAB>(runmax, run2, runidx, a0 + wave * 64 + l31, hi, (size_t)p * S + split, cap_a, ws_max, ws_i1, ws_m2);
 }
 
 // Round-2 restructuring of the int8 screening loop (same operands, same outputs, same tiles as match_i8_screen_kernel).
@@ -761,10 +717,9 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_i8_screen
 {
     constexpr int RB = CP;
     constexpr int TILE_BYTES = screen8_tile_bytes(CP);
-    constexpr int ROWS = 128, NQB = 4, NAB = 2;
+    constexpr int NQB = 4, NAB = 2;
     constexpr int NKS = CP / 32;
     constexpr int NI = TILE_BYTES / (1024 * WAVES);
-    constexpr int LPR = RB / 256;
     char *smem;
     if constexpr (2 * TILE_BYTES > 65536) {
         extern __shared__ __attribute__((aligned(256))) char smem_dyn8b[];
@@ -773,18 +728,11 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_i8_screen
         __shared__ __attribute__((aligned(256))) char smem_st8b[2 * TILE_BYTES];
         smem = smem_st8b;
     }
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int unit = (slot / T) * 8 + xcd;
-    if (unit >= B * S) return;
-    const int panel = slot % T;
-    const int p = unit / S, split = unit % S;
-    const int na = n_a[p], nq = n_q[p];
-    const int a0 = panel * (64 * WAVES);
-    if (a0 >= na) return;
-    const int nqt = (nq + ROWS - 1) / ROWS;
-    const int qt_per = (nqt + S - 1) / S;
-    const int qt_begin = split * qt_per;
-    const int qt_end = (qt_begin + qt_per < nqt) ? qt_begin + qt_per : nqt;
+    ScreenUnit u;
+    if (!screen_unit_decode(u, 64 * WAVES, B, T, S, n_a, n_q)) return;
+    const int p = u.p, split = u.split, a0 = u.a0;
+    int qt_begin, qt_end;
+    screen_split_tiles(u, S, qt_begin, qt_end);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
     const unsigned hi_mask = 0u - (unsigned)hi;
     const char *qp = reinterpret_cast<const char *>(q8) + (size_t)p * cap_q * RB;
@@ -799,13 +747,7 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_i8_screen
         for (int s = 0; s < NKS; ++s) breg[ab][s] = *reinterpret_cast<const i32x4 *>(arow + 32 * s);
     }
     unsigned dma_off[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int line = (wave * NI + j) * 4 + (lane >> 4), sl = lane & 15;
-        const int row = line / LPR;
-        const int cc = sl ^ (row & 15);
-        dma_off[j] = (unsigned)(row * RB + ((line % LPR) * 16 + cc) * 16);
-    }
+    screen_dma_offsets<RB>(dma_off, wave * NI, lane);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     auto issue_one = [&](int qt, int buf, int j) {
         const char *qb = qp + (size_t)qt * TILE_BYTES;
@@ -923,21 +865,7 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_i8_screen
     }
 #pragma unroll
     for (int ab = 0; ab < NAB; ++ab) reduce_block(prev[ab], prev_sc, prev_sid, ab);
-#pragma unroll
-    for (int ab = 0; ab < NAB; ++ab) {
-        const float om1 = __shfl_xor(runmax[ab], 32), om2 = __shfl_xor(run2[ab], 32);
-        const int oi1 = __shfl_xor(runidx[ab], 32);
-        const float m1 = fmaxf(runmax[ab], om1);
-        const float m2 = fmaxf(fminf(runmax[ab], om1), fmaxf(run2[ab], om2));
-        const int i1 = (om1 > runmax[ab]) ? oi1 : runidx[ab];
-        const int a = a0 + wave * 64 + ab * 32 + l31;
-        if (hi == 0 && a < cap_a) {
-            const size_t o = ((size_t)p * S + split) * cap_a + a;
-            ws_max[o] = m1;
-            ws_i1[o] = i1;
-            ws_m2[o] = m2;
-        }
-    }
+    screen_merge_store<NAB>(runmax, run2, runidx, a0 + wave * 64 + l31, hi, (size_t)p * S + split, cap_a, ws_max, ws_i1, ws_m2);
 }
 
 

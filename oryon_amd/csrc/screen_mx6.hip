@@ -11,11 +11,9 @@
 #include <type_traits>
 #include "common.h"
 #include "match_common.h"
+#include "screen_tile.h"
 
 namespace oryon {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-constexpr int screen8_tile_bytes(int CP) { return CP * 128; }     // 128 query rows per tile (as the int8 screen, match16.hip)
 
 // ------------------------------------------------------------------------------------------------ K1s6: MX-fp6 screen (round 3)
 // The same single-pass (m1, slice, m2) screening on v_mfma_scale_f32_32x32x64_f8f6f4 with fp6 (e2m3) operands: 64 channels per
@@ -41,10 +39,9 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
 {
     constexpr int RB = CP;
     constexpr int TILE_BYTES = screen8_tile_bytes(CP);
-    constexpr int ROWS = 128, NQB = 4, NAB = 2;
+    constexpr int NQB = 4, NAB = 2;
     constexpr int NKS = CP / 64;                          // k-steps of 64 channels (two 32-channel blocks, one per lane half)
     constexpr int NI = TILE_BYTES / (1024 * WAVES);
-    constexpr int LPR = RB / 256;
     char *smem;
     if constexpr (2 * TILE_BYTES > 65536) {
         extern __shared__ __attribute__((aligned(256))) char smem_dyn6[];
@@ -53,18 +50,11 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
         __shared__ __attribute__((aligned(256))) char smem_st6[2 * TILE_BYTES];
         smem = smem_st6;
     }
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int unit = (slot / T) * 8 + xcd;
-    if (unit >= B * S) return;
-    const int panel = slot % T;
-    const int p = unit / S, split = unit % S;
-    const int na = n_a[p], nq = n_q[p];
-    const int a0 = panel * (64 * WAVES);
-    if (a0 >= na) return;
-    const int nqt = (nq + ROWS - 1) / ROWS;
-    const int qt_per = (nqt + S - 1) / S;
-    const int qt_begin = split * qt_per;
-    const int qt_end = (qt_begin + qt_per < nqt) ? qt_begin + qt_per : nqt;
+    ScreenUnit u;
+    if (!screen_unit_decode(u, 64 * WAVES, B, T, S, n_a, n_q)) return;
+    const int p = u.p, split = u.split, a0 = u.a0;
+    int qt_begin, qt_end;
+    screen_split_tiles(u, S, qt_begin, qt_end);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
     const char *qp = reinterpret_cast<const char *>(q6) + (size_t)p * cap_q * RB;
 
@@ -81,13 +71,7 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
         }
     }
     unsigned dma_off[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int line = (wave * NI + j) * 4 + (lane >> 4), sl = lane & 15;
-        const int row = line / LPR;
-        const int cc = sl ^ (row & 15);
-        dma_off[j] = (unsigned)(row * RB + ((line % LPR) * 16 + cc) * 16);
-    }
+    screen_dma_offsets<RB>(dma_off, wave * NI, lane);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     auto issue_one = [&](int qt, int buf, int j) {
         const char *qb = qp + (size_t)qt * TILE_BYTES;
@@ -187,21 +171,7 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
     }
 #pragma unroll
     for (int ab = 0; ab < NAB; ++ab) reduce_block(prev[ab], prev_sid, ab);
-#pragma unroll
-    for (int ab = 0; ab < NAB; ++ab) {
-        const float om1 = __shfl_xor(runmax[ab], 32), om2 = __shfl_xor(run2[ab], 32);
-        const int oi1 = __shfl_xor(runidx[ab], 32);
-        const float m1 = fmaxf(runmax[ab], om1);
-        const float m2 = fmaxf(fminf(runmax[ab], om1), fmaxf(run2[ab], om2));
-        const int i1 = (om1 > runmax[ab]) ? oi1 : runidx[ab];
-        const int a = a0 + wave * 64 + ab * 32 + l31;
-        if (hi == 0 && a < cap_a) {
-            const size_t o = ((size_t)p * S + split) * cap_a + a;
-            ws_max[o] = m1;
-            ws_i1[o] = i1;
-            ws_m2[o] = m2;
-        }
-    }
+    screen_merge_store<NAB>(runmax, run2, runidx, a0 + wave * 64 + l31, hi, (size_t)p * S + split, cap_a, ws_max, ws_i1, ws_m2);
 }
 
 // K1s6 at C_pad = 256, second cut (round 3): 128 anchors per wave.  The kernel above feeds every 32x32x64 MFMA one kilobyte of LDS reads
@@ -217,8 +187,9 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
 // C_pad = 512 (cfg4): the same loop with 8 k-steps, 4 waves and one wave per SIMD (192 code + 8 exponent registers stationary, 482 VGPRs incl. AGPRs,
 // 2 x 64 KB of LDS): 19.7 ms per cfg4 launch against 21.7 ms for the two-block kernel, cfg4 shard 3.57 k -> 3.84 k pairs/s.
 // Outputs and slice meaning unchanged.
-typedef int i32x3 __attribute__((ext_vector_type(3)));
-typedef int i32x6 __attribute__((ext_vector_type(6)));
+//
+// The loop is written once, in mx6_screen_w4_tiles below: the plain kernel (all tiles of the split) and the cascades' kernel (a window, a
+// band or the gated panels: match_mx6_screen_w4_win_kernel) decode their workgroup, choose the tile range [qt_begin, qt_end) and call it.
 
 // compile-time loop over the k-steps (the step index is an instruction operand: the op_sel byte of the packed exponents)
 template <int S0, int N, class F>
@@ -230,45 +201,27 @@ __device__ __forceinline__ void mx6_static_for(F &&f)
     }
 }
 
+// The loop: tiles [qt_begin, qt_end) of pair p against the panel's anchors a0 .. a0 + 128 WAVES - 1, everything from the stationary-operand
+// load to the store of the (m1, slice, m2) triples of (p, split).  smem: the workgroup's two tile buffers.
 // C_pad = 512: WAVES = 4, one wave per SIMD (192 code + 8 exponent registers of stationary operands), 2 x 64 KB of dynamic LDS
 // KL = live k-steps of 64 channels (round 4: narrow maps - the reference's own C = 32 - are zero-padded to the 256-channel rows; their dead
 // k-steps hold zero codes and contribute exactly 0, so they are simply not multiplied: same results, a quarter of the MFMAs at C <= 64)
-template <int CP, int WAVES, int KL = CP / 64>
-__global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_screen_w4_kernel(
-    const uint8_t *__restrict__ a6, const uint8_t *__restrict__ q6, int B, int cap_a, int cap_q, const int32_t *__restrict__ n_a,
-    const int32_t *__restrict__ n_q, int T, int S, float *__restrict__ ws_max, int32_t *__restrict__ ws_i1, float *__restrict__ ws_m2,
-    long long *__restrict__ dbg_wg /* ORYON_MX6_DEBUG: per-workgroup (start, end, hw_id, xcc_id), else NULL */)
+// No early exit: one was built into the loop for the cascade first, and the break cost the loop its register allocation - 161 spilled
+// registers, six times slower per tile.  A caller bounds the work by the range it passes.
+template <int CP, int WAVES, int KL>
+__device__ __forceinline__ void mx6_screen_w4_tiles(char *smem, const uint8_t *__restrict__ a6, const uint8_t *__restrict__ q6, int p, int split,
+                                                    int a0, int cap_a, int cap_q, int S, int qt_begin, int qt_end, float *__restrict__ ws_max,
+                                                    int32_t *__restrict__ ws_i1, float *__restrict__ ws_m2)
 {
     static_assert(CP == 256 || (CP == 512 && WAVES == 4), "geometries: C_pad 256 with 4 / 8 waves, C_pad 512 with 4 waves");
     constexpr int RB = CP, NAB = 4;
     constexpr int TILE_BYTES = screen8_tile_bytes(CP);
-    constexpr int ROWS = 128, NQB = 4;
+    constexpr int NQB = 4;
     constexpr int NKS = CP / 64;
     constexpr int NI = TILE_BYTES / (1024 * WAVES);
     constexpr int LPR = RB / 256;
-    char *smem;
-    if constexpr (2 * TILE_BYTES > 65536) {
-        extern __shared__ __attribute__((aligned(256))) char smem_dyn_w4[];
-        smem = smem_dyn_w4;
-    } else {
-        __shared__ __attribute__((aligned(256))) char smem_st_w4[2 * TILE_BYTES];
-        smem = smem_st_w4;
-    }
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int unit = (slot / T) * 8 + xcd;
-    if (unit >= B * S) return;
-    const int panel = slot % T;
-    const int p = unit / S, split = unit % S;
-    const int na = n_a[p], nq = n_q[p];
-    const int a0 = panel * (32 * NAB * WAVES);
-    if (a0 >= na) return;
-    const int nqt = (nq + ROWS - 1) / ROWS;
-    const int qt_per = (nqt + S - 1) / S;
-    const int qt_begin = split * qt_per;
-    const int qt_end = (qt_begin + qt_per < nqt) ? qt_begin + qt_per : nqt;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
     const char *qp = reinterpret_cast<const char *>(q6) + (size_t)p * cap_q * RB;
-    const long long tk0 = dbg_wg ? wall_clock64() : 0;
 
     // stationary B operands: slot (2 s + hi) of k-step s of the lane's anchor row in each of the four blocks; the four exponent bytes of a
     // block packed into one register (the instruction picks the byte by op_sel)
@@ -295,12 +248,7 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
     constexpr int DJ = 4 * LPR;
     static_assert(NI % DJ == 0 || NI == DJ, "DMA instructions per wave and tile");
     unsigned dma_off[DJ];
-#pragma unroll
-    for (int j = 0; j < DJ; ++j) {
-        const int line = (wave * NI + j) * 4 + (lane >> 4), sl = lane & 15;
-        const int row = line / LPR;
-        dma_off[j] = (unsigned)(row * RB + (((line % LPR) * 16 + (sl ^ (row & 15))) << 4));
-    }
+    screen_dma_offsets<RB>(dma_off, wave * NI, lane);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     auto issue_one = [&](int qt, int buf, int j) {
         const char *qb = qp + (size_t)qt * TILE_BYTES + (j / DJ) * (16 * RB);
@@ -351,7 +299,7 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
     for (int ab = 0; ab < NAB; ++ab)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[ab][r] = -3.0e38f;           // "previous block" of the pairs before the first one: never wins
-    int sid01 = 0, sid23 = 0;                                         // slice ids of the blocks acc[0..1] / acc[2..3] currently hold
+    int sid23 = 0;                                                    // slice id of the block acc[2..3] currently hold
 
     // one MFMA: k-step SC (a compile-time constant: it is also the op_sel byte of the packed B exponents) of anchor block ab
     auto mfma = [&](f32x16s &d, int ab, auto SC) {
@@ -394,7 +342,6 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
                 __builtin_amdgcn_sched_group_barrier(0x002, 16 / KL, 0);
                 if (qb + 1 < NQB && (i & 1)) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
             }
-            sid01 = sid;
             sid23 = sid;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -403,25 +350,34 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
 #pragma unroll
         for (int s = 0; s < KL; ++s) areg[s] = rd(s, 0, buf * TILE_BYTES);
     }
-    (void)sid01;
     reduce_block(acc[2], sid23, 2);
     reduce_block(acc[3], sid23, 3);
-#pragma unroll
-    for (int ab = 0; ab < NAB; ++ab) {
-        const float om1 = __shfl_xor(runmax[ab], 32), om2 = __shfl_xor(run2[ab], 32);
-        const int oi1 = __shfl_xor(runidx[ab], 32);
-        const float m1 = fmaxf(runmax[ab], om1);
-        const float m2 = fmaxf(fminf(runmax[ab], om1), fmaxf(run2[ab], om2));
-        const int i1 = (om1 > runmax[ab]) ? oi1 : runidx[ab];
-        const int a = a0 + wave * (32 * NAB) + ab * 32 + l31;
-        if (hi == 0 && a < cap_a) {
-            const size_t o = ((size_t)p * S + split) * cap_a + a;
-            ws_max[o] = m1;
-            ws_i1[o] = i1;
-            ws_m2[o] = m2;
-        }
+    screen_merge_store<NAB>(runmax, run2, runidx, a0 + wave * (32 * NAB) + l31, hi, (size_t)p * S + split, cap_a, ws_max, ws_i1, ws_m2);
+}
+
+// The full screen: every tile of the workgroup's query split.
+template <int CP, int WAVES, int KL = CP / 64>
+__global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_screen_w4_kernel(
+    const uint8_t *__restrict__ a6, const uint8_t *__restrict__ q6, int B, int cap_a, int cap_q, const int32_t *__restrict__ n_a,
+    const int32_t *__restrict__ n_q, int T, int S, float *__restrict__ ws_max, int32_t *__restrict__ ws_i1, float *__restrict__ ws_m2,
+    long long *__restrict__ dbg_wg /* ORYON_MX6_DEBUG: per-workgroup (start, end, hw_id, xcc_id), else NULL */)
+{
+    constexpr int TILE_BYTES = screen8_tile_bytes(CP);
+    char *smem;
+    if constexpr (2 * TILE_BYTES > 65536) {
+        extern __shared__ __attribute__((aligned(256))) char smem_dyn_w4[];
+        smem = smem_dyn_w4;
+    } else {
+        __shared__ __attribute__((aligned(256))) char smem_st_w4[2 * TILE_BYTES];
+        smem = smem_st_w4;
     }
-    if (dbg_wg && t == 0) {
+    ScreenUnit u;
+    if (!screen_unit_decode(u, 128 * WAVES, B, T, S, n_a, n_q)) return;
+    int qt_begin, qt_end;
+    screen_split_tiles(u, S, qt_begin, qt_end);
+    const long long tk0 = dbg_wg ? wall_clock64() : 0;
+    mx6_screen_w4_tiles<CP, WAVES, KL>(smem, a6, q6, u.p, u.split, u.a0, cap_a, cap_q, S, qt_begin, qt_end, ws_max, ws_i1, ws_m2);
+    if (dbg_wg && threadIdx.x == 0) {
         dbg_wg[(size_t)blockIdx.x * 4 + 0] = tk0;
         dbg_wg[(size_t)blockIdx.x * 4 + 1] = wall_clock64();
         dbg_wg[(size_t)blockIdx.x * 4 + 2] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);        // HW_REG_HW_ID
@@ -429,15 +385,14 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
     }
 }
 
-// The validity cascade of the hard route (round 6; oryon_match_corrs_mx6_x3) runs the screen in two launches of this copy of the kernel
-// above (same loop, two more scalar arguments; the headline's kernel itself is untouched):
+// The cascades' launches: the same loop over a part of the split's tiles, or for a part of the panels.
+// The validity cascade of the hard route (round 6; oryon_match_corrs_mx6_x3) runs the screen in two launches of this kernel:
 //   win > 0  : every (panel, split) multiplies only `win` query tiles, placed in its split where the panel sits in its own map - on smooth
 //              maps (every anchor matches a near-by query and its neighbours almost as well) that settles the VALIDITY of every anchor
 //              of the panel ("some query within the threshold" needs one witness) at a few percent of the multiply-accumulates;
 //   gate     : the complete scan, for the panels match_panel_settle_kernel found an unsettled anchor in; panels that were settled keep
 //              their partial triples with m2 = +inf (no margin: argmin open, which is what every anchor of such maps is anyway), and
 //              the SAMPLED anchors get the complete screen in a second pass over one 512-row panel per pair (match_corrs_lazy_impl).
-// (An in-loop early exit was built first: the break cost the loop its register allocation - 161 spilled registers, six times slower per tile.)
 // The default route's cascade (round 10; match_corrs.hip, match_dc_*) uses a third placement:
 //   band     : every panel scans the tiles [first, first + count) its entry of `band` names - the range its probe rows' matches lie in,
 //              learned per pair and panel by match_dc_probe_band_kernel - dealt evenly to the S splits of the launch.
@@ -448,13 +403,7 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
     const int32_t *__restrict__ gate /* [B, T] or NULL: only panels with a non-zero entry run */, int win /* > 0: that many tiles of the split */,
     const int32_t *__restrict__ band /* [B, T, 2] or NULL: the panel scans tiles [first, first + count), dealt evenly to the S splits */)
 {
-    static_assert(CP == 256 || (CP == 512 && WAVES == 4), "geometries: C_pad 256 with 4 / 8 waves, C_pad 512 with 4 waves");
-    constexpr int RB = CP, NAB = 4;
     constexpr int TILE_BYTES = screen8_tile_bytes(CP);
-    constexpr int ROWS = 128, NQB = 4;
-    constexpr int NKS = CP / 64;
-    constexpr int NI = TILE_BYTES / (1024 * WAVES);
-    constexpr int LPR = RB / 256;
     char *smem;
     if constexpr (2 * TILE_BYTES > 65536) {
         extern __shared__ __attribute__((aligned(256))) char smem_dyn_w4w[];
@@ -463,188 +412,27 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
         __shared__ __attribute__((aligned(256))) char smem_st_w4w[2 * TILE_BYTES];
         smem = smem_st_w4w;
     }
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int unit = (slot / T) * 8 + xcd;
-    if (unit >= B * S) return;
-    const int panel = slot % T;
-    const int p = unit / S, split = unit % S;
-    const int na = n_a[p], nq = n_q[p];
-    const int a0 = panel * (32 * NAB * WAVES);
-    if (a0 >= na) return;
-    if (gate && gate[p * T + panel] == 0) return;
-    const int nqt = (nq + ROWS - 1) / ROWS;
-    const int qt_per = (nqt + S - 1) / S;
-    int qt_begin = split * qt_per;
-    int qt_end = (qt_begin + qt_per < nqt) ? qt_begin + qt_per : nqt;
+    ScreenUnit u;
+    if (!screen_unit_decode(u, 128 * WAVES, B, T, S, n_a, n_q)) return;
+    if (gate && gate[u.p * T + u.panel] == 0) return;
+    int qt_begin, qt_end;
+    screen_split_tiles(u, S, qt_begin, qt_end);
     if (win > 0 && qt_end - qt_begin > win) {
         // the window sits in the split where the panel sits among the pair's panels (smooth maps match near-by pixels)
-        const int cnt = qt_end - qt_begin, panels = (na + 32 * NAB * WAVES - 1) / (32 * NAB * WAVES);
-        int k0 = (int)(((long long)(2 * panel + 1) * cnt) / (2 * panels)) - win / 2;
+        const int cnt = qt_end - qt_begin, panels = (u.na + 128 * WAVES - 1) / (128 * WAVES);
+        int k0 = (int)(((long long)(2 * u.panel + 1) * cnt) / (2 * panels)) - win / 2;
         k0 = k0 < 0 ? 0 : (k0 > cnt - win ? cnt - win : k0);
         qt_begin += k0;
         qt_end = qt_begin + win;
     }
     if (band) {
         // default-route cascade: the band match_dc_probe_band_kernel learned for this panel from the probe rows' matches
-        const int first = band[(p * T + panel) * 2], cnt = band[(p * T + panel) * 2 + 1];
+        const int first = band[(u.p * T + u.panel) * 2], cnt = band[(u.p * T + u.panel) * 2 + 1];
         const int per = (cnt + S - 1) / S;
-        qt_begin = first + split * per;
+        qt_begin = first + u.split * per;
         qt_end = (qt_begin + per < first + cnt) ? qt_begin + per : first + cnt;
     }
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
-    const char *qp = reinterpret_cast<const char *>(q6) + (size_t)p * cap_q * RB;
-
-    // stationary B operands: slot (2 s + hi) of k-step s of the lane's anchor row in each of the four blocks; the four exponent bytes of a
-    // block packed into one register (the instruction picks the byte by op_sel)
-    i32x8 breg[NAB][NKS];
-    int bsc[NAB][NKS / 4];
-#pragma unroll
-    for (int ab = 0; ab < NAB; ++ab) {
-        const int arow_i = a0 + wave * (32 * NAB) + ab * 32 + l31;
-        const char *arow = reinterpret_cast<const char *>(a6) + ((size_t)p * cap_a + (arow_i < cap_a ? arow_i : cap_a - 1)) * RB + 32 * hi;
-        unsigned sc[NKS / 4];
-#pragma unroll
-        for (int w = 0; w < NKS / 4; ++w) sc[w] = 0;
-#pragma unroll
-        for (int s = 0; s < KL; ++s) {
-            const i32x4 lo = *reinterpret_cast<const i32x4 *>(arow + 64 * s), up = *reinterpret_cast<const i32x4 *>(arow + 64 * s + 16);
-            breg[ab][s] = __builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, -1, -1);   // the fp6 format reads six dwords
-            sc[s >> 2] |= ((unsigned)up[2] & 0xffu) << (8 * (s & 3));
-        }
-#pragma unroll
-        for (int w = 0; w < NKS / 4; ++w) bsc[ab][w] = (int)sc[w];
-    }
-    // DMA instruction j of a wave moves the four 256-byte lines (wave NI + j) 4 .. + 3 of the tile (4 / LPR rows); rows 16 apart share the
-    // swizzle, so instructions j and j + DJ (DJ = 4 LPR) differ by 16 rows - in the scalar base, not in another pair of address registers
-    constexpr int DJ = 4 * LPR;
-    static_assert(NI % DJ == 0 || NI == DJ, "DMA instructions per wave and tile");
-    unsigned dma_off[DJ];
-#pragma unroll
-    for (int j = 0; j < DJ; ++j) {
-        const int line = (wave * NI + j) * 4 + (lane >> 4), sl = lane & 15;
-        const int row = line / LPR;
-        dma_off[j] = (unsigned)(row * RB + (((line % LPR) * 16 + (sl ^ (row & 15))) << 4));
-    }
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    auto issue_one = [&](int qt, int buf, int j) {
-        const char *qb = qp + (size_t)qt * TILE_BYTES + (j / DJ) * (16 * RB);
-        char *dst = smem + buf * TILE_BYTES + (wave_u * NI + j) * 1024;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(qb + dma_off[j % DJ]),
-                                         (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
-    };
-    unsigned koff[4][2];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int e = 0; e < 2; ++e) koff[c][e] = (unsigned)(l31 * RB) + ((((unsigned)(4 * c + 2 * hi + e)) ^ (unsigned)(l31 & 15)) << 4);
-    // A operand of one k-step: 16 + 12 bytes of the lane's slot (dword 6 = exponent byte, the scale operand)
-    auto rd = [&](int s, int qb, unsigned tile) -> i32x8 {
-        const unsigned base = tile + (unsigned)(qb * 32 * RB + (s >> 2) * 256);
-        const i32x4 lo = *reinterpret_cast<const i32x4 *>(smem + koff[s & 3][0] + base);
-        const i32x4 up = *reinterpret_cast<const i32x4 *>(smem + koff[s & 3][1] + base);
-        return __builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, 6, -1);
-    };
-
-    float runmax[NAB], run2[NAB];
-    int runidx[NAB];
-#pragma unroll
-    for (int ab = 0; ab < NAB; ++ab) { runmax[ab] = -INFINITY; run2[ab] = -INFINITY; runidx[ab] = 0; }
-    auto reduce_block = [&](const f32x16s &c, int sid, int ab) {
-        const float m0 = fmaxf(fmaxf(c[0], c[1]), c[2]), m1 = fmaxf(fmaxf(c[3], c[4]), c[5]), m2 = fmaxf(fmaxf(c[6], c[7]), c[8]);
-        const float m3 = fmaxf(fmaxf(c[9], c[10]), c[11]), m4 = fmaxf(fmaxf(c[12], c[13]), c[14]);
-        const float x = fmaxf(fmaxf(fmaxf(m0, m1), m2), fmaxf(fmaxf(m3, m4), c[15]));
-        const bool improved = x > runmax[ab];
-        run2[ab] = __builtin_amdgcn_fmed3f(runmax[ab], run2[ab], x);              // run2 <= runmax: the median is the second largest
-        runmax[ab] = __builtin_amdgcn_fmed3f(runmax[ab], x, INFINITY);           // = max (no NaNs here); as the intrinsic it needs no operand
-        runidx[ab] = improved ? sid : runidx[ab];                                // canonicalisation (v_max x, x) of the loop-carried state
-    };
-    const f32x16s zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-    if (qt_end > qt_begin) {
-#pragma unroll
-        for (int j = 0; j < NI; ++j) issue_one(qt_begin, 0, j);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    i32x8 areg[NKS];
-#pragma unroll
-    for (int s = 0; s < KL; ++s) areg[s] = rd(s, 0, 0u);
-    f32x16s acc[NAB];
-#pragma unroll
-    for (int ab = 0; ab < NAB; ++ab)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[ab][r] = -3.0e38f;           // "previous block" of the pairs before the first one: never wins
-    int sid01 = 0, sid23 = 0;                                         // slice ids of the blocks acc[0..1] / acc[2..3] currently hold
-
-    // one MFMA: k-step SC (a compile-time constant: it is also the op_sel byte of the packed B exponents) of anchor block ab
-    auto mfma = [&](f32x16s &d, int ab, auto SC) {
-        constexpr int s_ = decltype(SC)::value;
-        d = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(areg[s_], breg[ab][s_], s_ == 0 ? zero16 : d, 2, 2, 0, areg[s_][6], s_ & 3,
-                                                            bsc[ab][s_ >> 2]);
-    };
-    int buf = 0;
-    for (int qt = qt_begin; qt < qt_end; ++qt) {
-        const unsigned tile = buf * TILE_BYTES;
-        const int qt_next = qt + 1 < qt_end ? qt + 1 : qt;
-#pragma unroll
-        for (int qb = 0; qb < NQB; ++qb) {
-            const int sid = (qt * NQB + qb) * 2 + hi;
-            if (qb == 0) {
-#pragma unroll
-                for (int j = 0; j < NI; ++j) issue_one(qt_next, buf ^ 1, j);
-            }
-            // first half: the VALU reduces the previous block of anchor blocks 2 / 3, the matrix pipe starts this block for 0 / 1
-            reduce_block(acc[2], sid23, 2);
-            reduce_block(acc[3], sid23, 3);
-            // (the reductions read acc[2..3] before the second half overwrites them: program order)
-            mx6_static_for<0, KL>([&](auto SC) { mfma(acc[0], 0, SC); mfma(acc[1], 1, SC); });
-#pragma unroll
-            for (int i = 0; i < 2 * KL; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 16 / KL, 0);
-            }
-            // second half: this block for 2 / 3 while the VALU reduces what 0 / 1 just finished; next A operand behind its last use
-            mx6_static_for<0, KL>([&](auto SC) {
-                constexpr int s_ = decltype(SC)::value;
-                mfma(acc[2], 2, SC); mfma(acc[3], 3, SC);
-                if (qb + 1 < NQB) areg[s_] = rd(s_, qb + 1, tile);
-            });
-            reduce_block(acc[0], sid, 0);
-            reduce_block(acc[1], sid, 1);
-#pragma unroll
-            for (int i = 0; i < 2 * KL; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 16 / KL, 0);
-                if (qb + 1 < NQB && (i & 1)) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-            }
-            sid01 = sid;
-            sid23 = sid;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        buf ^= 1;
-#pragma unroll
-        for (int s = 0; s < KL; ++s) areg[s] = rd(s, 0, buf * TILE_BYTES);
-    }
-    (void)sid01;
-    reduce_block(acc[2], sid23, 2);
-    reduce_block(acc[3], sid23, 3);
-#pragma unroll
-    for (int ab = 0; ab < NAB; ++ab) {
-        const float om1 = __shfl_xor(runmax[ab], 32), om2 = __shfl_xor(run2[ab], 32);
-        const int oi1 = __shfl_xor(runidx[ab], 32);
-        const float m1 = fmaxf(runmax[ab], om1);
-        const float m2 = fmaxf(fminf(runmax[ab], om1), fmaxf(run2[ab], om2));
-        const int i1 = (om1 > runmax[ab]) ? oi1 : runidx[ab];
-        const int a = a0 + wave * (32 * NAB) + ab * 32 + l31;
-        if (hi == 0 && a < cap_a) {
-            const size_t o = ((size_t)p * S + split) * cap_a + a;
-            ws_max[o] = m1;
-            ws_i1[o] = i1;
-            ws_m2[o] = m2;
-        }
-    }
+    mx6_screen_w4_tiles<CP, WAVES, KL>(smem, a6, q6, u.p, u.split, u.a0, cap_a, cap_q, S, qt_begin, qt_end, ws_max, ws_i1, ws_m2);
 }
 
 // ORYON_MX6_DEBUG=1 (development aid; synchronises): per-workgroup wall-clock records of the screen launch -> how many workgroups were
@@ -687,9 +475,20 @@ static int mx6_var()
 }
 
 namespace {
+// live k-steps of a C_pad 256 launch: narrow maps multiply 1 (C <= 64) or 2 (C <= 128) of the four (see mx6_screen_w4_tiles) ...
+int mx6_live_ksteps(int C_true) { return (C_true > 0 && C_true <= 64) ? 1 : (C_true > 0 && C_true <= 128) ? 2 : 4; }
+// ... as the template argument KL: f(std::integral_constant<int, kl>)
+template <class F>
+void mx6_with_kl(int kl, F &&f)
+{
+    if (kl == 1) f(std::integral_constant<int, 1>{});
+    else if (kl == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 4>{});
+}
+
 template <int CP>
 void launch_screen_mx6_t(int groups, int T, hipStream_t st, const uint8_t *a6, const uint8_t *q6, int B, int cap_a, int cap_q, const int32_t *n_a,
-                       const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int kl = 0, bool gate_or_win = false,
+                       const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int kl = 4, bool gate_or_win = false,
                        const int32_t *gate = nullptr, int win = 0, const int32_t *band = nullptr)
 {
     // C_pad 256: 512-anchor panels (8 waves; `groups` was sized for 256-anchor panels, T of them per unit).  C_pad 512: the stationary
@@ -713,25 +512,17 @@ void launch_screen_mx6_t(int groups, int T, hipStream_t st, const uint8_t *a6, c
             if (dbg && !dbg_wg) (void)hipMalloc(&dbg_wg, (size_t)65536 * 4 * sizeof(long long));
             if (dbg && dbg_wg && g8 <= 65536) (void)hipMemsetAsync(dbg_wg, 0, (size_t)g8 * 4 * sizeof(long long), st);
             if (gate_or_win) {
-                // the cascades' launches: windowed (win > 0), gated (gate != NULL) or banded (band != NULL) copy of the kernel
-#define ORYON_LAUNCH_WIN(KLV)                                                                                                         \
-    hipLaunchKernelGGL((match_mx6_screen_w4_win_kernel<CP, 8, KLV>), dim3(g8), dim3(512), 0, st, a6, q6, B, cap_a, cap_q, n_a, n_q, T8, S,   \
-                       ws_max, ws_i1, ws_m2, gate, win, band)
-                if (kl == 1) ORYON_LAUNCH_WIN(1);
-                else if (kl == 2) ORYON_LAUNCH_WIN(2);
-                else ORYON_LAUNCH_WIN(4);
-#undef ORYON_LAUNCH_WIN
+                // the cascades' launches: a window (win > 0), the gated panels (gate != NULL) or a band (band != NULL) of the same loop
+                mx6_with_kl(kl, [&](auto KLC) {
+                    hipLaunchKernelGGL((match_mx6_screen_w4_win_kernel<CP, 8, decltype(KLC)::value>), dim3(g8), dim3(512), 0, st, a6, q6, B, cap_a,
+                                       cap_q, n_a, n_q, T8, S, ws_max, ws_i1, ws_m2, gate, win, band);
+                });
                 return;
             }
-            if (kl == 1)
-                hipLaunchKernelGGL((match_mx6_screen_w4_kernel<CP, 8, 1>), dim3(g8), dim3(512), 0, st, a6, q6, B, cap_a, cap_q, n_a, n_q, T8, S,
-                                   ws_max, ws_i1, ws_m2, (dbg && g8 <= 65536) ? dbg_wg : nullptr);
-            else if (kl == 2)
-                hipLaunchKernelGGL((match_mx6_screen_w4_kernel<CP, 8, 2>), dim3(g8), dim3(512), 0, st, a6, q6, B, cap_a, cap_q, n_a, n_q, T8, S,
-                                   ws_max, ws_i1, ws_m2, (dbg && g8 <= 65536) ? dbg_wg : nullptr);
-            else
-            hipLaunchKernelGGL((match_mx6_screen_w4_kernel<CP, 8>), dim3(g8), dim3(512), 0, st, a6, q6, B, cap_a, cap_q, n_a, n_q, T8, S,
-                               ws_max, ws_i1, ws_m2, (dbg && g8 <= 65536) ? dbg_wg : nullptr);
+            mx6_with_kl(kl, [&](auto KLC) {
+                hipLaunchKernelGGL((match_mx6_screen_w4_kernel<CP, 8, decltype(KLC)::value>), dim3(g8), dim3(512), 0, st, a6, q6, B, cap_a, cap_q,
+                                   n_a, n_q, T8, S, ws_max, ws_i1, ws_m2, (dbg && g8 <= 65536) ? dbg_wg : nullptr);
+            });
             if (dbg && dbg_wg && g8 <= 65536) mx6_debug_report(dbg_wg, g8, st);
             return;
         }
@@ -766,10 +557,10 @@ void launch_screen_mx6(int C, int groups, int T, hipStream_t st, const uint8_t *
                        const int32_t *n_a, const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true,
                        int cascade, const int32_t *gate, int win, const int32_t *band)
 {
-    // live k-steps of narrow maps (1 for C <= 64, 2 for C <= 128; otherwise all four): see match_mx6_screen_w4_kernel
-    const int kl = (C == 256 && C_true > 0 && C_true <= 64) ? 1 : (C == 256 && C_true > 0 && C_true <= 128) ? 2 : 0;
-    // cascade != 0 (C_pad 256 only): the windowed / gated launches of the validity cascade (match_mx6_screen_w4_win_kernel)
-    if (C == 256) launch_screen_mx6_t<256>(groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, ws_max, ws_i1, ws_m2, kl, cascade != 0, gate, win, band);
+    // cascade != 0 (C_pad 256 only): the windowed / gated / banded launches of the validity cascades (match_mx6_screen_w4_win_kernel)
+    if (C == 256)
+        launch_screen_mx6_t<256>(groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, ws_max, ws_i1, ws_m2, mx6_live_ksteps(C_true), cascade != 0,
+                                 gate, win, band);
     else launch_screen_mx6_t<512>(groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, ws_max, ws_i1, ws_m2);
 }
 
@@ -781,16 +572,10 @@ void launch_screen_mx6_rows512(hipStream_t st, const uint8_t *a6_rows, const uin
 {
     const int T = (cap_rows + 511) / 512;
     const int groups = ((B * S + 7) / 8) * 8 * T;
-    const int kl = (C_true > 0 && C_true <= 64) ? 1 : (C_true > 0 && C_true <= 128) ? 2 : 0;
-    if (kl == 1)
-        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4, 1>), dim3(groups), dim3(256), 0, st, a6_rows, q6, B, cap_rows, cap_q, n_rows, n_q, T, S,
-                           ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
-    else if (kl == 2)
-        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4, 2>), dim3(groups), dim3(256), 0, st, a6_rows, q6, B, cap_rows, cap_q, n_rows, n_q, T, S,
-                           ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
-    else
-        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4>), dim3(groups), dim3(256), 0, st, a6_rows, q6, B, cap_rows, cap_q, n_rows, n_q, T, S,
-                           ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
+    mx6_with_kl(mx6_live_ksteps(C_true), [&](auto KLC) {
+        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4, decltype(KLC)::value>), dim3(groups), dim3(256), 0, st, a6_rows, q6, B, cap_rows, cap_q,
+                           n_rows, n_q, T, S, ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
+    });
 }
 
 // Second pass of the validity cascades: ONE 512-row panel per pair (the sampled anchors whose argmin is open): a tenth of the full

@@ -347,6 +347,31 @@ def test_fp16x3_split_is_defined_once():
     assert found == set(), sorted(found)
 
 
+def test_mx6_w4_loop_is_written_once():
+    """The MX-fp6 screen's tile loop exists once (mx6_screen_w4_tiles: the plain and the cascade kernel call it), and what the screen
+    kernels share lives in csrc/screen_tile.h alone: the merge of the two lane halves' (m1, slice, m2) and the tile size.
+    `__shfl_xor(runmax` also opens the two max-only merges of kernels that keep no slice and no runner-up (pass 0 of the fp16 screen in
+    match16.hip, the fp16x3 scan in match_x3.hip): one line each, pinned here; the triple merge is told apart by `__shfl_xor(run2`."""
+    import glob, re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oryon_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    text = {os.path.basename(f): open(f).read() for f in files}
+    mx6 = text["screen_mx6.hip"]
+    mfma = "__builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4"
+    assert mx6.count(mfma) == 2
+    body = mx6[mx6.index("void mx6_screen_w4_tiles("):mx6.index("void match_mx6_screen_w4_kernel(")]
+    two_block = mx6[mx6.index("void match_mx6_screen_kernel("):mx6.index("void mx6_screen_w4_tiles(")]
+    assert body.count(mfma) == 1 and two_block.count(mfma) == 1
+    assert mx6.count("mx6_screen_w4_tiles<CP, WAVES, KL>(") == 2                      # the two kernels' calls
+    assert all('#include "screen_tile.h"' in text[f] for f in ("match16.hip", "screen_mx6.hip"))
+    assert {f: t.count("__shfl_xor(run2") for f, t in text.items() if "__shfl_xor(run2" in t} == {"screen_tile.h": 1}
+    max_only = "fmaxf(runmax[ab], __shfl_xor(runmax[ab], 32))"
+    merges = {f: t.count("__shfl_xor(runmax") for f, t in text.items() if "__shfl_xor(runmax" in t}
+    assert merges == {"screen_tile.h": 1, "match16.hip": 1, "match_x3.hip": 1}, merges
+    assert text["match16.hip"].count(max_only) == 1 and text["match_x3.hip"].count(max_only) == 1
+    assert [f for f, t in text.items() if re.search(r"constexpr\s+int\s+screen8_tile_bytes\s*\(", t)] == ["screen_tile.h"]
+
+
 def test_engine_config_struct_matches_the_library():
     """The ctypes mirror of oryon_engine_config_t has the size the library was built with (a field added on one side only would shift
     every later field silently)."""
