@@ -795,6 +795,56 @@ int oryon_gt_corrs(const float *depth_a, const float *depth_q, int B, int HA, in
                    const double *cam_q, const double *pose_aq, double threshold, const int32_t *status_in, void *workspace,
                    size_t workspace_bytes, int32_t *corrs, int32_t *n_corr, int32_t *idx, double *d2, void *stream);
 
+/* g2  ICP pose refinement of B pairs of object clouds (csrc/icp.hip; test.refine = icp): the reference's utils/geo6d.py:157-208 `icp`
+ *     over nearest_neighbor (:22-38, sklearn's NearestNeighbors) and best_fit_transform_icp (:122-155), batched, with nothing read back.
+ * DEFINITION.  For each pair: a source cloud src [n_s,3] and a target cloud dst [n_d,3], float64 metres, of ANY two sizes (the
+ * reference asserts equal sizes but does not need them); an initial pose T_0 [4,4], which arrives as fp32 and is widened; max_iter,
+ * tolerance and max_dist (+inf = the reference's behaviour).  All arithmetic is float64 without contraction;
+ * tests/icp_restatement.py is its numpy statement.  State: T_k, prev = 0.0, not done.  For k = 0 .. max_iter - 1, while not done:
+ *   1 move      s_i = ((R0 x + R1 y) + R2 z) + t per coordinate, [R | t] of T_k, applied to src_i.
+ *   2 nearest   d2_ij = ((dx dx + dy dy) + dz dz); j_i = the FIRST minimiser over j ascending (strict <; a NaN never wins, and a row
+ *               whose every distance is NaN has no neighbour, j_i = -1); dist_i = sqrt(d2_i).
+ *   3 keep      row i is kept when it has a neighbour and dist_i <= max_dist; m = the number kept.  m < 3 (or n_d = 0): the pair is
+ *               done and T_k stays.  Otherwise mean_k = the mean of dist_i over the kept rows.
+ *   4 fit       dT = best_fit_transform_icp(s_kept, dst[j]_kept): plain means c_s, c_d as centroids, H = sum (s - c_s)(d - c_d)^T,
+ *               R = V diag(1, 1, det(V U^T)) U^T for H = U S V^T, t = c_d - R c_s.
+ *   5 update    T_{k+1} = dT T_k.
+ *   6 converge  |prev - mean_k| < tolerance: the pair is done, with this iteration's update applied (as in the reference); otherwise
+ *               prev = mean_k.
+ * The result is T_K.  The reference carries the moved cloud along and ends with best_fit_transform_icp(A, moved A); as the moved
+ * cloud is a rigid image of A the two agree to rounding (tests/golden/icp_*.npz: 3.4e-15) - provided T_0 is rigid: the reference's last
+ * fit returns the nearest rigid transform, so it differs from T_K by as much as an fp32-rounded T_0 is off a rigid one (~6e-8).
+ * A pair with status_in != 0, n_s < 3 or n_d = 0 returns T_0 unchanged with iters = 0.
+ * The ORDER of the sums over rows is not part of the definition, but it is fixed (rows of a 256-row block by an xor butterfly in each
+ * wave, waves then blocks ascending; moments taken about the target's centroid): no float atomics, outputs bit-stable across runs,
+ * streams and batch position.  Against the restatement the pose agrees to ~1e-13 (bar 1e-9), indices and iters exactly
+ * wherever best and second-best neighbour and |prev - mean| and the tolerance are further apart than rounding.
+ *
+ * oryon_icp_refine: src [B,cap_src,3], dst [B,cap_dst,3] float64; n_src, n_dst [B] DEVICE counts: a count above its capacity is read
+ *   as the capacity (below 0 as 0) and rows beyond the count are never read.  1 <= cap_src, cap_dst <= ORYON_ICP_MAX_ROWS, B <= 65535,
+ *   1 <= max_iter <= ORYON_ICP_MAX_ITER (two launches per iteration, all enqueued at once; a finished pair's workgroups return at
+ *   once), tolerance >= 0, max_dist >= 0.  T_init [B,16] fp32 row-major 4x4.  status_in [B] or NULL.
+ *   workspace: oryon_icp_workspace_bytes(B, cap_src, cap_dst) bytes (0 = unsupported shape), 256-byte aligned
+ *     = align256(B * ORYON_ICP_STATE_BYTES) + align256(B * ceil(cap_src / 256) * 17 * 8).
+ *   T [B,16] fp32: rows 0-2 exactly float32(T64), row 3 T_init's.  T64 [B,12] float64 rows of [R | t], or NULL.  iters [B]: updates
+ *   applied.  mean_err [B]: mean_k of the last update applied (0.0 when none).  n_kept [B]: m of the last executed iteration (0 when
+ *   none).  idx [B,cap_src] or NULL: the last executed iteration's neighbours, -1 for a row without one, beyond n_s or of a pair
+ *   that never iterated.  status_out [B] = status_in (0 when NULL).  float64 pointers must be 8-byte aligned. */
+#define ORYON_ICP_MAX_ROWS 8192
+#define ORYON_ICP_MAX_ITER 1000
+#define ORYON_ICP_STATE_BYTES 136
+size_t oryon_icp_workspace_bytes(int B, int cap_src, int cap_dst);
+int oryon_icp_refine(const double *src, const int32_t *n_src, int cap_src, const double *dst, const int32_t *n_dst, int cap_dst, int B,
+                     const float *T_init, int max_iter, double tolerance, double max_dist, const int32_t *status_in, void *workspace,
+                     size_t workspace_bytes, float *T, double *T64, int32_t *iters, double *mean_err, int32_t *n_kept, int32_t *idx,
+                     int32_t *status_out, void *stream);
+/* oryon_icp_best_fit: step 4 alone over the CALLER's correspondences (best_fit_transform_icp, geo6d.py:122-155): row i of A [B,cap,3]
+ *   corresponds to row i of Bp [B,cap,3], float64, n [B] device counts -> T [B,16] fp32 (= float32(T64), last row 0 0 0 1), T64 [B,12] or
+ *   NULL, fitted [B] = 1, or 0 with the identity when n < 3; mean_err [B] = the mean distance of the pairs BEFORE the fit.  One
+ *   iteration of the same kernels with the neighbour search replaced by j_i = i.  workspace: oryon_icp_workspace_bytes(B, cap, cap). */
+int oryon_icp_best_fit(const double *A, const double *Bp, const int32_t *n, int cap, int B, void *workspace, size_t workspace_bytes, float *T,
+                       double *T64, int32_t *fitted, double *mean_err, void *stream);
+
 /* a5  StandardDecoder.forward (models/decoder.py:82-108) on the device, fp32 in / fp32 out, for the decoder the reference builds
  *     (get_decoder, models/decoder.py:119-125: input_dim 128, decoder_dims [64, 32], extra_upsampling, guidance projections 256->32 and
  *     128->16): three Up blocks (ConvTranspose2d 2x2 s2 -> cat guidance -> (conv3x3 - GroupNorm(C/16) - ReLU) x 2, :9-42), the two

@@ -178,6 +178,10 @@ _PROTOS = {
     "oryon_gt_corrs_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "oryon_gt_corrs": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, _P, _P, _P, ctypes.c_double, _P,
                                _P, c_size_t, _P, _P, _P, _P, _P]),
+    "oryon_icp_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "oryon_icp_refine": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, _P, c_int, ctypes.c_double, ctypes.c_double, _P, _P, c_size_t,
+                                 _P, _P, _P, _P, _P, _P, _P, _P]),
+    "oryon_icp_best_fit": (c_int, [_P, _P, _P, c_int, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_PROTOS)

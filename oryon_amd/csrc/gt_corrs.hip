@@ -16,13 +16,14 @@
 //   nearest    d2_j = ((dx dx + dy dy) + dz dz), j ascending, strict <: the first minimiser (torch.argmin).  NaN never wins.
 //   keep       sqrt(d2) <= threshold, rows written in anchor order.
 #include "common.h"
+#include "nn_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace oryon {
 
 constexpr int GTC_THREADS = 256;
-constexpr int GTC_TILE = 1024;               // query points per LDS tile: 3 x 1024 float64 = 24 KB
+constexpr int GTC_TILE = NN_TILE;            // query points per LDS tile (nn_tile.h): 3 x 1024 float64 = 24 KB
 constexpr int GTC_KEEP_THREADS = 1024;
 constexpr int GTC_KEEP_WAVES = GTC_KEEP_THREADS / 64;
 
@@ -63,9 +64,8 @@ __global__ __launch_bounds__(GTC_THREADS) void gtc_lift_kernel(const float *__re
 }
 
 // The hot path.  A workgroup owns GTC_THREADS * PPL anchor points of one pair (PPL per lane, in registers) and walks the pair's query
-// cloud in order through LDS tiles of GTC_TILE points, float64 structure-of-arrays: in the inner loop every lane of a wave reads the
-// SAME address, which the LDS serves as a broadcast (no bank conflicts).  Tiles and the points inside them are visited in ascending
-// order with a strict <, so the first minimiser wins.  idx = -1 and d2 = +inf when no query point compares below +inf (n_dst = 0).
+// cloud in order through LDS tiles of GTC_TILE points (nearest_walk_f64, nn_tile.h: broadcast LDS reads, ascending order, strict <, so
+// the first minimiser wins).  idx = -1 and d2 = +inf when no query point compares below +inf (n_dst = 0).
 template <int PPL>
 __global__ __launch_bounds__(GTC_THREADS) void pcd_nearest_f64_kernel(const double *__restrict__ src, const int32_t *__restrict__ n_src, int cap_src,
                                                                       const double *__restrict__ dst, const int32_t *__restrict__ n_dst, int cap_dst,
@@ -73,7 +73,6 @@ __global__ __launch_bounds__(GTC_THREADS) void pcd_nearest_f64_kernel(const doub
                                                                       double *__restrict__ d2)
 {
     extern __shared__ __align__(16) double gtc_tile[];       // [3][GTC_TILE]: x | y | z
-    double *sx = gtc_tile, *sy = gtc_tile + GTC_TILE, *sz = gtc_tile + 2 * GTC_TILE;
     const int b = blockIdx.y;
     if (gtc_skip(status, b)) return;
     const int na = min(n_src[b], cap_src), nq = min(n_dst[b], cap_dst);
@@ -89,30 +88,8 @@ __global__ __launch_bounds__(GTC_THREADS) void pcd_nearest_f64_kernel(const doub
         ax[u] = live ? A[(size_t)r * 3 + 0] : 0.0;
         ay[u] = live ? A[(size_t)r * 3 + 1] : 0.0;
         az[u] = live ? A[(size_t)r * 3 + 2] : 0.0;
-        best[u] = __longlong_as_double(0x7ff0000000000000ll);
-        bi[u] = -1;
     }
-    for (int t0 = 0; t0 < nq; t0 += GTC_TILE) {
-        const int m = min(GTC_TILE, nq - t0);
-        __syncthreads();                                     // the previous tile has been consumed
-        for (int e = threadIdx.x; e < 3 * m; e += GTC_THREADS) {
-            const int pnt = e / 3, c = e - pnt * 3;          // coalesced read of the [m,3] rows, transposed into the three planes
-            gtc_tile[c * GTC_TILE + pnt] = Q[(size_t)t0 * 3 + e];
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int j = 0; j < m; ++j) {
-            const double qx = sx[j], qy = sy[j], qz = sz[j];
-#pragma unroll
-            for (int u = 0; u < PPL; ++u) {
-                const double dx = ax[u] - qx, dy = ay[u] - qy, dz = az[u] - qz;
-                const double d = ((dx * dx + dy * dy) + dz * dz);
-                const bool lt = d < best[u];
-                best[u] = lt ? d : best[u];
-                bi[u] = lt ? t0 + j : bi[u];
-            }
-        }
-    }
+    nearest_walk_f64<PPL, GTC_THREADS>(Q, nq, gtc_tile, ax, ay, az, best, bi);
 #pragma unroll
     for (int u = 0; u < PPL; ++u) {
         const int r = row0 + u * GTC_THREADS + (int)threadIdx.x;

@@ -1,10 +1,11 @@
-"""Drop-in counterpart of the used half of the reference's utils/geo6d.py (lines 40-120): `best_fit_transform` and
-`best_fit_transform_with_RANSAC`, same names, argument order and defaults, numpy in / numpy out.
+"""Drop-in counterpart of the reference's utils/geo6d.py: `best_fit_transform` and `best_fit_transform_with_RANSAC` (lines 40-120),
+`best_fit_transform_icp` and `icp` (lines 122-208), same names, argument order and defaults, numpy in / numpy out.
 
     from oryon_amd.geo6d import best_fit_transform_with_RANSAC      # instead of: from utils.geo6d import ...
 
 The arithmetic runs in liboryon_hip.so (csrc/ransac.hip: every hypothesis of a call is scored in ONE launch); this module only
-moves the arrays and keeps numpy's global generator where the reference leaves it.  The points are handed to the kernel as
+moves the arrays and keeps numpy's global generator where the reference leaves it.  `icp` and `best_fit_transform_icp` run in
+csrc/icp.hip (ops.icp_refine: float64 throughout, the clouds need not be of equal length).  The points are handed to the kernel as
 float32 (what pipeline.py:459-463 passes); fits and the inlier test are float64, as numpy computes them for float64 input.
 """
 from __future__ import annotations
@@ -77,3 +78,34 @@ def best_fit_transform_with_RANSAC(A, B, max_iter=20, match_err=0.015, fix_perce
         if k > 0:
             np.random.randint(0, n, (k, 4))
     return out["T"][0, :3, :].double().cpu().numpy()
+
+
+def _cloud(x: np.ndarray, device) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))[None].to(device)
+
+
+def best_fit_transform_icp(A, B, *, device="cuda") -> np.ndarray:
+    """utils/geo6d.py:122-155: least-squares rigid transform of A onto B (row i of A corresponds to row i of B), [4,4] float64."""
+    A, B = _as_points(A), _as_points(B)
+    assert A.shape == B.shape and A.shape[0] >= 3, "two [n,3] arrays of one length, n >= 3"
+    dev = torch.device(device)
+    out = ops.icp_best_fit(_cloud(A, dev), _cloud(B, dev), torch.tensor([A.shape[0]], dtype=torch.int32, device=dev))
+    T = np.identity(4)
+    T[:3, :] = out["T64"][0].cpu().numpy()
+    return T
+
+
+def icp(A, B, init_pose=None, max_iterations=20, tolerance=0.001, *, max_dist=float("inf"), device="cuda") -> np.ndarray:
+    """utils/geo6d.py:157-208: iterative closest point of A [n,3] onto B [m,3] from init_pose ([4,4], None = identity) -> [3,4] float64.
+    The clouds need not be of equal length; max_dist drops source rows further than that from the target (inf: none, the reference).
+    init_pose reaches the kernel as float32, as the solvers' poses do; the result is the composed T_K of the definition
+    (include/oryon_hip.h, oryon_icp_refine), which the reference's closing fit of A onto the moved cloud equals to rounding."""
+    A, B = _as_points(A), _as_points(B)
+    dev = torch.device(device)
+    T0 = np.eye(4, dtype=np.float32) if init_pose is None else np.asarray(init_pose, dtype=np.float32).reshape(4, 4)
+    if A.shape[0] < 3 or B.shape[0] == 0:                  # the definition: such a pair returns T_0
+        return T0[:3, :].astype(np.float64)
+    out = ops.icp_refine(_cloud(A, dev), _cloud(B, dev), torch.tensor([A.shape[0]], dtype=torch.int32, device=dev),
+                         torch.tensor([B.shape[0]], dtype=torch.int32, device=dev), torch.from_numpy(np.ascontiguousarray(T0))[None].to(dev),
+                         max_iter=int(max_iterations), tolerance=float(tolerance), max_dist=float(max_dist))
+    return out["T64"][0].cpu().numpy()

@@ -1034,6 +1034,89 @@ def gt_corrs(depth_a: torch.Tensor, depth_q: torch.Tensor, pix_a: torch.Tensor, 
     return dict(corrs=corrs, n_corr=n_corr, idx=idx, d2=d2)
 
 
+ICP_MAX_ROWS, ICP_MAX_ITER = 8192, 1000      # ORYON_ICP_MAX_ROWS, ORYON_ICP_MAX_ITER (include/oryon_hip.h)
+
+
+def _icp_require(cond: bool, check_name: str, detail: str = "") -> None:
+    if not cond:
+        raise ValueError(f"icp_refine: {check_name}" + (f" ({detail})" if detail else ""))
+
+
+def icp_refine(src: torch.Tensor, dst: torch.Tensor, n_src: torch.Tensor, n_dst: torch.Tensor, T_init: torch.Tensor, max_iter: int = 20,
+               tolerance: float = 1e-3, max_dist: float = float("inf"), status: Optional[torch.Tensor] = None, want_idx: bool = False,
+               workspace: Optional[torch.Tensor] = None):
+    """ICP refinement of B poses (g2, csrc/icp.hip; definition: include/oryon_hip.h, oryon_icp_refine).  src [B,cap_src,3], dst
+    [B,cap_dst,3] float64 metres, n_src / n_dst [B] int32, T_init [B,4,4] fp32, status [B] int32 or None - all contiguous device tensors
+    of exactly these dtypes: nothing is converted or copied here, a tensor that does not fit is rejected with the name of the check.
+    Runs on the current stream with no host round trip -> dict(T [B,4,4] fp32, T64 [B,3,4] float64, iters [B] int32, mean_err [B]
+    float64, n_kept [B] int32, idx [B,cap_src] int32 | None, status [B] int32)."""
+    for name, t in (("src", src), ("dst", dst), ("n_src", n_src), ("n_dst", n_dst), ("T_init", T_init)):
+        _icp_require(isinstance(t, torch.Tensor) and t.is_cuda, f"{name}.is_cuda")
+    _icp_require(src.dtype == torch.float64, "src.dtype == float64", str(src.dtype))
+    _icp_require(dst.dtype == torch.float64, "dst.dtype == float64", str(dst.dtype))
+    _icp_require(src.dim() == 3 and src.shape[2] == 3 and src.shape[1] >= 1, "src.shape == [B,cap_src,3]", str(tuple(src.shape)))
+    B = src.shape[0]
+    _icp_require(B >= 1, "B >= 1")
+    _icp_require(dst.dim() == 3 and dst.shape[2] == 3 and dst.shape[1] >= 1 and dst.shape[0] == B, "dst.shape == [B,cap_dst,3]",
+                 str(tuple(dst.shape)))
+    cap_src, cap_dst = src.shape[1], dst.shape[1]
+    _icp_require(src.is_contiguous(), "src.is_contiguous")
+    _icp_require(dst.is_contiguous(), "dst.is_contiguous")
+    for name, t in (("n_src", n_src), ("n_dst", n_dst)) + ((("status", status),) if status is not None else ()):
+        _icp_require(t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (B,), f"{name} is [B] int32", f"{tuple(t.shape)} {t.dtype}")
+        _icp_require(t.is_contiguous(), f"{name}.is_contiguous")
+    _icp_require(T_init.dtype == torch.float32, "T_init.dtype == float32", str(T_init.dtype))
+    _icp_require(tuple(T_init.shape) == (B, 4, 4), "T_init.shape == [B,4,4]", str(tuple(T_init.shape)))
+    _icp_require(T_init.is_contiguous(), "T_init.is_contiguous")
+    _icp_require(all(t.device == src.device for t in (dst, n_src, n_dst, T_init) + ((status,) if status is not None else ())), "one device")
+    max_iter = int(max_iter)
+    _icp_require(1 <= max_iter <= ICP_MAX_ITER, f"1 <= max_iter <= {ICP_MAX_ITER}", str(max_iter))
+    _icp_require(float(tolerance) >= 0.0, "tolerance >= 0", str(tolerance))
+    _icp_require(float(max_dist) >= 0.0, "max_dist >= 0", str(max_dist))
+    _icp_require(cap_src <= ICP_MAX_ROWS and cap_dst <= ICP_MAX_ROWS, f"cap <= {ICP_MAX_ROWS}", f"{cap_src}, {cap_dst}")
+    dev = _lib.require_gpu(src.device)
+    with torch.cuda.device(dev):
+        need = lib().oryon_icp_workspace_bytes(B, cap_src, cap_dst)
+        if need == 0 and B > 0:
+            raise _lib.OryonError(f"oryon_icp_workspace_bytes({B}, {cap_src}, {cap_dst}): shape not supported")
+        ws = workspace if workspace is not None else torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+        T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+        T64 = torch.empty((B, 3, 4), dtype=torch.float64, device=dev)
+        iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        mean_err = torch.empty((B,), dtype=torch.float64, device=dev)
+        n_kept = torch.empty((B,), dtype=torch.int32, device=dev)
+        idx = torch.empty((B, cap_src), dtype=torch.int32, device=dev) if want_idx else None
+        st_out = torch.empty((B,), dtype=torch.int32, device=dev)
+        check(lib().oryon_icp_refine(ptr(src), ptr(n_src), cap_src, ptr(dst), ptr(n_dst), cap_dst, B, ptr(T_init), max_iter, float(tolerance),
+                                     float(max_dist), ptr(status), ptr(ws), ws.numel(), ptr(T), ptr(T64), ptr(iters), ptr(mean_err),
+                                     ptr(n_kept), ptr(idx), ptr(st_out), stream_ptr(dev)), "oryon_icp_refine")
+    return dict(T=T, T64=T64, iters=iters, mean_err=mean_err, n_kept=n_kept, idx=idx, status=st_out)
+
+
+def icp_best_fit(A: torch.Tensor, Bp: torch.Tensor, n: torch.Tensor):
+    """The rigid fit of ICP's step 4 over given correspondences (g2, oryon_icp_best_fit): A, Bp [B,cap,3] float64 (row i of A corresponds
+    to row i of Bp), n [B] int32, contiguous device tensors -> dict(T [B,4,4] fp32, T64 [B,3,4] float64, fitted [B] int32,
+    mean_err [B] float64 = the pairs' mean distance before the fit)."""
+    for name, t in (("A", A), ("Bp", Bp)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 3 and t.shape[2] == 3 and t.is_contiguous()):
+            raise ValueError(f"icp_best_fit: {name} is a contiguous [B,cap,3] float64 device tensor")
+    B, cap = A.shape[0], A.shape[1]
+    if tuple(Bp.shape) != tuple(A.shape) or not (1 <= cap <= ICP_MAX_ROWS) or B < 1:
+        raise ValueError(f"icp_best_fit: A {tuple(A.shape)} / Bp {tuple(Bp.shape)}: one shape, 1 <= cap <= {ICP_MAX_ROWS}")
+    if not (n.is_cuda and n.dtype == torch.int32 and tuple(n.shape) == (B,) and n.is_contiguous()):
+        raise ValueError("icp_best_fit: n is [B] int32")
+    dev = _lib.require_gpu(A.device)
+    with torch.cuda.device(dev):
+        ws = torch.empty((max(lib().oryon_icp_workspace_bytes(B, cap, cap), 256),), dtype=torch.uint8, device=dev)
+        T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+        T64 = torch.empty((B, 3, 4), dtype=torch.float64, device=dev)
+        fitted = torch.empty((B,), dtype=torch.int32, device=dev)
+        mean_err = torch.empty((B,), dtype=torch.float64, device=dev)
+        check(lib().oryon_icp_best_fit(ptr(A), ptr(Bp), ptr(n), cap, B, ptr(ws), ws.numel(), ptr(T), ptr(T64), ptr(fitted), ptr(mean_err),
+                                       stream_ptr(dev)), "oryon_icp_best_fit")
+    return dict(T=T, T64=T64, fitted=fitted, mean_err=mean_err)
+
+
 _x3_weights = {}
 # Validation mode of the fp16x3 path (backbone.enable_fp16x3(True, guard=True)): every call first checks max|activation| against the
 # float16 range (one reduction + a host sync per linear - for a first run with a real checkpoint, not for throughput) and evaluates

@@ -8,6 +8,10 @@
     test_step(batch, batch_idx)                       # per-sample loop, host RNG: reference semantics
     test_step_batched(batch, first_pair_index=0)      # same work for the whole batch with no host sync
 
+`test.refine = icp` (absent or `none`: nothing changes) refines every solved pose by ICP of the anchor's object cloud onto the query's
+(utils/geo6d.py:157-208 `icp`, csrc/icp.hip) in both routes; flags test.refine_points / refine_max_iter / refine_tolerance /
+refine_max_dist.
+
 and the validation step (pipeline.py:196-247, 579-590):
 
     on_validation_start(objects=None) / validation_step(batch, batch_idx) -> (loss, log) / on_validation_end() -> dict
@@ -37,6 +41,23 @@ from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK
 from .geo6d import best_fit_transform_with_RANSAC
 from .pcd import nn_correspondences
 from .pointdsc import PointDSC, get_pointdsc_pose
+
+
+REFINEMENTS = ("none", "icp")
+_default_refine = "none"
+
+
+def set_default_refine(name: str) -> None:
+    """The process-wide default of test.refine: what a Pipeline does when its args name no refinement ('none' unless set).  A driver
+    sets it once, before it builds pipelines (run_pose.py --refine does, as --solver does through engine.set_default_solver)."""
+    global _default_refine
+    if name not in REFINEMENTS:
+        raise ValueError(f"Refinement {name} not implemented")
+    _default_refine = name
+
+
+def default_refine() -> str:
+    return _default_refine
 
 
 def default_args(**overrides) -> SimpleNamespace:
@@ -107,6 +128,8 @@ class Pipeline:
         self._valid_log: List[Dict[str, float]] = []
         self._valid_fmr: List[float] = []
         self.last_validation: Optional[Dict] = None      # the latest validation_step's {'poses', 'status', 'results', 'losses'}
+        self.last_refine: Optional[Dict] = None          # the latest ops.icp_refine result (test.refine = icp)
+        self.refine_mode()                               # an unknown test.refine raises here, not at the first pose
 
     # ------------------------------------------------------------------ mask post-processing (losses.py:56-60)
     def mask_results(self, batch: Dict, outputs: Dict) -> Dict[str, Tensor]:
@@ -157,8 +180,59 @@ class Pipeline:
             pos_a, pos_q = None, None
         return pred_corrs, pos_a, pos_q
 
+    # ------------------------------------------------------------------ ICP refinement (test.refine = icp; utils/geo6d.py:157-208)
+    REFINE_SEED_A, REFINE_SEED_Q = 0x1C9A0A, 0x1C9A0B       # the two sides' subsamples draw from streams of their own
+
+    def refine_mode(self) -> str:
+        """test.refine: 'none' (absent = the process-wide default, 'none' unless a driver set it) or 'icp' - ICP of the anchor's object cloud onto the query's, started at the solver's pose."""
+        mode = getattr(self.args.test, "refine", default_refine())
+        if mode not in REFINEMENTS:
+            raise RuntimeError(f"Refinement {mode} not implemented")
+        return mode
+
+    def refine_clouds(self, mask_a: Tensor, mask_q: Tensor, depth_a: Tensor, depth_q: Tensor, cam_a: Tensor, cam_q: Tensor,
+                      pair_key: Tensor) -> Dict[str, Tensor]:
+        """The object clouds ICP runs on, per side: the mask ([B,h,w], the masks the matcher saw - test.mask) resized to the depth map's
+        size (nearest), AND depth > 0, compacted to a pixel list, thinned to test.refine_points pixels by the device RNG keyed by
+        (seed, pair key) - so a pair's cloud does not depend on the batch it arrives in - and lifted in float64 (ops.gtc_lift).
+        depth_* [B,H,W] fp32 millimetres, cam_* [B,9] or [B,3,3], pair_key [B] int64 -> src, dst [B,cap,3] float64 metres (anchor,
+        query) and n_src, n_dst [B] int32, all on the device, nothing read back."""
+        points = int(getattr(self.args.test, "refine_points", 2048))
+        seed = self.args.seed if self.args.seed is not None else 1
+        out = {}
+        for side, mask, depth, cam, salt in (("src", mask_a, depth_a, cam_a, self.REFINE_SEED_A), ("dst", mask_q, depth_q, cam_q, self.REFINE_SEED_Q)):
+            B, H, W = depth.shape
+            m = ops.mask_resize_nearest(mask, (H, W)) if tuple(mask.shape[-2:]) != (H, W) else mask.to(torch.int32)
+            m = ((m == 1) & (depth > 0)).to(torch.int32)
+            roi, count = ops.roi_compact(m)
+            ops.roi_subsample_(roi, count, points, seed ^ salt, pair_key)
+            cap = min(points, H * W)
+            pix = roi[:, :cap].contiguous()
+            count = torch.clamp(count, max=cap)
+            # the intrinsics as both solver routes see them: fp32 values, widened
+            xyz, _ = ops.gtc_lift(depth, pix, count, cam.to(depth.device, torch.float32).to(torch.float64).reshape(B, 9))
+            out[side], out["n_" + side] = xyz, count
+        return out
+
+    def refine_poses(self, pose: Tensor, status: Optional[Tensor], clouds: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        """ops.icp_refine with the flags test.refine_max_iter / refine_tolerance / refine_max_dist: pose [B,4,4] fp32 (the solver's) ->
+        the refined poses and the iteration counts; a pair with a failure status keeps its pose."""
+        t = self.args.test
+        return ops.icp_refine(clouds["src"], clouds["dst"], clouds["n_src"], clouds["n_dst"], pose.to(torch.float32).contiguous(),
+                              max_iter=int(getattr(t, "refine_max_iter", 20)), tolerance=float(getattr(t, "refine_tolerance", 1e-3)),
+                              max_dist=float(getattr(t, "refine_max_dist", float("inf"))), status=status)
+
+    def _refine_masks(self, batch: Dict, results: Optional[Dict], dev) -> Tuple[Tensor, Tensor]:
+        if self.args.test.mask != "predicted":
+            return batch["anchor"]["mask"].to(dev), batch["query"]["mask"].to(dev)
+        if results is None or "mask_a" not in results:
+            raise KeyError("test.refine='icp' with test.mask='predicted' needs the predicted masks (results['mask_a'], results['mask_q'])")
+        return results["mask_a"], results["mask_q"]
+
     # ------------------------------------------------------------------ pipeline.py:429-472
-    def get_pose(self, batch: Dict, corrs: Tensor, idx: int) -> Tensor:
+    def get_pose(self, batch: Dict, corrs: Tensor, idx: int, results: Optional[Dict] = None, pair_key: Optional[int] = None) -> Tensor:
+        """results: the masks' post-processing (mask_results), needed by test.refine = icp with predicted masks only; pair_key: the
+        pair's global index (default idx), which keys the refinement's subsample."""
         dev = _lib.require_gpu(self.device)
         depth_a = batch["anchor"]["orig_depth"][idx].squeeze().to(dev, torch.float32)
         depth_q = batch["query"]["orig_depth"][idx].squeeze().to(dev, torch.float32)
@@ -182,6 +256,13 @@ class Pipeline:
             pose4 = torch.tensor(pose4)
         else:
             pose4 = get_pointdsc_pose(self.pointdsc_solver, pcd_a[0, :m], pcd_q[0, :m], self.device)
+        if self.refine_mode() == "icp":
+            mask_a, mask_q = self._refine_masks(batch, results, dev)
+            key = torch.tensor([idx if pair_key is None else pair_key], dtype=torch.int64, device=dev)
+            clouds = self.refine_clouds(mask_a[idx:idx + 1], mask_q[idx:idx + 1], depth_a[None].contiguous(), depth_q[None].contiguous(),
+                                        camera_a, camera_q, key)
+            self.last_refine = self.refine_poses(pose4.to(torch.float32)[None].to(dev), None, clouds)
+            return self.last_refine["T"][0].cpu()
         return pose4.to(torch.float32)
 
     # ------------------------------------------------------------------ pipeline.py:490-497
@@ -223,7 +304,7 @@ class Pipeline:
         return n
 
     # ------------------------------------------------------------------ pipeline.py:306-355
-    def test_step(self, batch: Dict, batch_idx: int = 0) -> List[Dict]:
+    def test_step(self, batch: Dict, batch_idx: int = 0, first_pair_index: int = 0) -> List[Dict]:
         outputs = self.model.forward(batch)
         BS = outputs["featmap_a"].shape[0]
         self.feature_loss_rng_draws(batch, outputs)          # generator state as after pipeline.py:311
@@ -242,7 +323,7 @@ class Pipeline:
             if self.is_detection_valid(results, batch, i_b):
                 pred_corrs, _, _ = self.get_featmap_corrs(batch, outputs, results, idx=i_b)
                 if pred_corrs is not None:
-                    pred_pose = self.get_pose(batch, pred_corrs, idx=i_b)
+                    pred_pose = self.get_pose(batch, pred_corrs, idx=i_b, results=results, pair_key=first_pair_index + i_b)
                     pred_q = pred_pose @ batch["anchor"]["pose"][i_b].cpu().detach().to(torch.float32)
                 else:
                     status, pred_pose = PAIR_NO_CORR, torch.eye(4)
@@ -254,6 +335,8 @@ class Pipeline:
             iou_q = results["iou_q"][i_b].cpu().numpy()
             self.add_pred_pose(id_a, id_q, iou_a, iou_q, pred_pose.cpu().numpy())
             records.append(dict(status=status, pred_pose_rel=pred_pose, pred_pose=pred_q))
+            if status == PAIR_OK and self.refine_mode() == "icp":
+                records[-1]["refine_iters"] = int(self.last_refine["iters"][0])
         return records
 
     # ------------------------------------------------------------------ batched device path
@@ -285,6 +368,11 @@ class Pipeline:
         key = torch.arange(first_pair_index, first_pair_index + BS, dtype=torch.int64, device=dev)
         out = self._engine.run(outputs["featmap_a"].float().contiguous(), outputs["featmap_q"].float().contiguous(), mask_a,
                                mask_q, depth_a, depth_q, batch["anchor"]["camera"].to(dev), batch["query"]["camera"].to(dev), key)
+        if self.refine_mode() == "icp":                          # same stream, no host round trip; failed pairs keep their identity
+            rmask_a, rmask_q = self._refine_masks(batch, res, dev)
+            self.last_refine = self.refine_poses(out["pose"], out["status"], self.refine_clouds(
+                rmask_a, rmask_q, depth_a, depth_q, batch["anchor"]["camera"].to(dev), batch["query"]["camera"].to(dev), key))
+            out["pose_unrefined"], out["pose"], out["refine_iters"] = out["pose"], self.last_refine["T"], self.last_refine["iters"]
         anchor_pose = batch["anchor"]["pose"].to(dev, torch.float32)
         out["pred_q"] = torch.bmm(out["pose"], anchor_pose)
         if res is not None:
@@ -404,13 +492,13 @@ class Pipeline:
             st, pred_pose = PAIR_OK, torch.eye(4)
             if self.args.debug_valid:
                 if int(batch["valid"][i_b]) == 1:
-                    pred_pose = self.get_pose(batch, self.gt_featmap_corrs(batch, outputs, i_b), idx=i_b)
+                    pred_pose = self.get_pose(batch, self.gt_featmap_corrs(batch, outputs, i_b), idx=i_b, results=results)
                 else:
                     st = PAIR_NO_CORR
             elif self.is_detection_valid(results, batch, i_b):
                 pred_corrs, _, _ = self.get_featmap_corrs(batch, outputs, results, idx=i_b)
                 if pred_corrs is not None:
-                    pred_pose = self.get_pose(batch, pred_corrs, idx=i_b)
+                    pred_pose = self.get_pose(batch, pred_corrs, idx=i_b, results=results)
                 else:
                     st = PAIR_NO_CORR
             else:

@@ -10,6 +10,12 @@
 engine - then selects it.  Everything else goes to run_test.py unchanged.  With `ransac` (best_fit_transform_with_RANSAC,
 utils/geo6d.py:75-120, max_iter=10000, fix_percent=0.9999, match_err=0.001 as pipeline.py:463) no PointDSC weights take part in a pose.
 
+    python run_pose.py --solver ransac --refine icp --pairs 8
+
+`--refine {none,icp}` (default none; test.refine) becomes the process-wide default refinement (oryon_amd.pipeline.set_default_refine),
+which every Pipeline that run_test.py builds then applies: every solved pose is refined by ICP of the anchor's object cloud onto the
+query's (utils/geo6d.py:157-208 `icp`, csrc/icp.hip), in the per-sample loop and behind the batched engine alike.
+
     python run_pose.py --vsd --data-root /data --dataset nocs --ckpt ... --out preds/nocs.csv
 
 `--vsd` (real-asset mode only) also reports VSD and AR = (VSD + MSSD + MSPD) / 3, the reference's headline column
@@ -26,11 +32,20 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+def take_refine(argv=None):
+    """-> (test.refine: 'none' or 'icp', argv without `--refine ...`); an unknown refinement exits like an unknown solver."""
+    ap = argparse.ArgumentParser(add_help=False)
+    ap.add_argument("--refine", choices=["none", "icp"], default="none")
+    a, rest = ap.parse_known_args(argv)
+    return a.refine, rest
+
+
 def parse(argv=None):
-    """-> (solver, the arguments left for run_test.py)."""
+    """-> (solver, the arguments left for run_test.py).  `--refine` is checked and taken out as well (take_refine returns it)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
     ap.add_argument("--solver", choices=["pointdsc", "ransac"], default="pointdsc",
                     help="test.solver: PointDSC registration, or best_fit_transform_with_RANSAC (needs no PointDSC weights)")
+    ap.add_argument("--refine", choices=["none", "icp"], default="none", help="test.refine: ICP refinement of every solved pose (see above)")
     ap.add_argument("-h", "--help", action="store_true")
     a, rest = ap.parse_known_args(argv)
     if a.help:
@@ -64,11 +79,14 @@ def add_vsd(summary: dict, rest) -> dict:
 
 def main(argv=None):
     vsd, argv = take_vsd(argv)
+    refine, _ = take_refine(argv)
     solver, rest = parse(argv)
     if vsd and "--data-root" not in rest and not any(r.startswith("--data-root=") for r in rest):
         raise SystemExit("run_pose.py --vsd needs real-asset mode (--data-root ...): the synthetic pairs have no object mesh")
     from oryon_amd.engine import set_default_solver
     set_default_solver(solver)
+    from oryon_amd.pipeline import set_default_refine
+    set_default_refine(refine)
     import run_test
     summary = run_test.main(rest)
     return add_vsd(summary, rest) if vsd and summary.get("pairs") else summary

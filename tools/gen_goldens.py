@@ -21,6 +21,7 @@ Reference entry points executed here:
   losses.py                   FeatureLoss.forward (sample_positives, sample_hardest_negatives, sample_negatives, mask_loss) and
                               utils/metrics.py compute_fmr (gen_feature_loss; `python tools/gen_goldens.py floss`); the same forward
                               followed by torch's backward (gen_feature_loss_grad; `python tools/gen_goldens.py floss_grad`)
+  utils/geo6d.py              icp over nearest_neighbor + best_fit_transform_icp (gen_icp; `python tools/gen_goldens.py icp`)
   scripts/data/make_toyl_test.py  pcd_correspondences (gen_gt_corrs; `python tools/gen_goldens.py gt_corrs`): recorded results only
 """
 import json
@@ -1105,7 +1106,65 @@ def gen_gt_corrs():
         assert os.path.getsize(os.path.join(OUT, f"gtcorr_{name}.npz")) <= 256 * 1024
 
 
+def gen_icp():
+    """utils/geo6d.py:157-208 `icp` on the seeded clouds of tests/icp_restatement.py, on the CPU (sklearn's NearestNeighbors).  The
+    reference returns no iteration count: its `nearest_neighbor` is called once per executed iteration, so the calls are counted.
+    Asserted for every fixture and every iteration, so that neither the neighbour indices nor the iteration count can turn on a
+    rounding: the relative gap between a row's best and second-best squared distance is >= 1e-9, | |prev - mean| - tolerance | >= 1e-9,
+    and the second singular value of every H is >= 1e-2 of the first.  A seed that misses one is replaced in GOLDEN_CASES."""
+    sys.modules["cv2"].imshow = sys.modules["cv2"].waitKey = lambda *a, **k: None
+    if "numpy.lib.function_base" not in sys.modules:
+        try:
+            import numpy.lib.function_base  # noqa: F401
+        except ImportError:
+            fb = types.ModuleType("numpy.lib.function_base")
+            fb.append = np.append
+            sys.modules["numpy.lib.function_base"] = fb
+    from utils import geo6d as ref_geo6d  # noqa: E402  (reference)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import icp_restatement as R  # noqa: E402  (ours)
+
+    calls = [0]
+    ref_nn = ref_geo6d.nearest_neighbor
+
+    def counted(src, dst):
+        calls[0] += 1
+        return ref_nn(src, dst)
+    ref_geo6d.nearest_neighbor = counted
+    try:
+        for name, c in R.GOLDEN_CASES.items():
+            A, B, init, tol = R.golden_case(name)
+            rec = {}
+            # every fixture is recorded at its own tolerance AND at both TOLERANCE and FINE_TOLERANCE: tolerance is an argument of the
+            # call, not of the pair, and the GPU test runs all fixtures as one batch
+            for tag, t in (("", tol), ("_coarse", R.TOLERANCE), ("_fine", R.FINE_TOLERANCE)):
+                calls[0] = 0
+                T_ref = ref_geo6d.icp(A.copy(), B.copy(), init_pose=None if init is None else init.copy(), max_iterations=R.MAX_ITER, tolerance=t)
+                iters = calls[0]
+                r = R.icp(A, B, init, R.MAX_ITER, t)
+                gap = float(np.abs(r["T"][:3] - T_ref).max())
+                print(f"icp_{name} tolerance {t:g}: n {A.shape[0]}, iters {iters} (restatement {r['iters']}), |T - T_ref| <= {gap:.1e}, nn gap "
+                      f"{r['nn_gap']:.1e}, convergence gap {r['conv_gap']:.1e}, s2/s1 >= {r['sv_ratio']:.2e}, det < 0 in {r['det_negative']} fits")
+                assert r["nn_gap"] >= 1e-9 and r["conv_gap"] >= 1e-9 and r["sv_ratio"] >= 1e-2, name
+                assert iters == r["iters"] and gap <= 1e-12, name
+                if c["kind"] == "mirrored":
+                    assert r["det_negative"] >= 1, name
+                if c["kind"] == "far" and t == 1e-6:
+                    assert iters == R.MAX_ITER, name
+                if c["kind"] == "identity":
+                    assert iters < R.MAX_ITER, name
+                rec["T" + tag], rec["iters" + tag] = T_ref, np.int64(iters)
+            save(f"icp_{name}", case=np.array(name), seed=np.int64(c["seed"]), A=A, B=B, has_init=np.int64(init is not None),
+                 init_pose=np.eye(4) if init is None else init, tolerance=np.float64(tol), tolerance_coarse=np.float64(R.TOLERANCE), tolerance_fine=np.float64(R.FINE_TOLERANCE),
+                 max_iterations=np.int64(R.MAX_ITER), **rec)
+            assert os.path.getsize(os.path.join(OUT, f"icp_{name}.npz")) <= 64 * 1024
+    finally:
+        ref_geo6d.nearest_neighbor = ref_nn
+
+
 if __name__ == "__main__":
+    if "icp" in sys.argv[1:]:
+        gen_icp()
     which = sys.argv[1:] or ["matcher", "lift", "kabsch", "pointdsc", "e2e", "backbone", "metrics", "bop", "tokenizer", "data"]
     if "data" in which:
         gen_data()
