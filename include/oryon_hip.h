@@ -845,6 +845,54 @@ int oryon_icp_refine(const double *src, const int32_t *n_src, int cap_src, const
 int oryon_icp_best_fit(const double *A, const double *Bp, const int32_t *n, int cap, int B, void *workspace, size_t workspace_bytes, float *T,
                        double *T64, int32_t *fitted, double *mean_err, void *stream);
 
+/* g3  Point-to-plane ICP of B source clouds onto the queries' depth maps (csrc/icp_plane.hip; test.refine = icp_plane): projective
+ *     association and a point-to-plane error.  The target is never a loose cloud here but an organised depth map, so a normal is two
+ *     central differences and the neighbour of a moved source point is the pixel it projects to: no search, O(n) per iteration.
+ * DEFINITION.  All arithmetic is float64 without contraction; only + - * / sqrt (and floor) are used, so the device and
+ * tests/icp_plane_restatement.py, its numpy statement, differ by the order of the sums over rows alone.  Per pair: a source cloud
+ * src [n_s,3] float64 metres (the anchor's object cloud); the target as an organised map, depth [H,W] fp32 millimetres, mask [H,W] int32
+ * (1 = object) and cam9 float64 (fx = cam9[0], cx = cam9[2], fy = cam9[4], cy = cam9[5]); T_0, fp32 4x4, widened; max_iter, tolerance,
+ * max_dist and normal_jump, the last two in metres.  The lift V(x, y) of pixel (x, y) with depth z is exactly g1's:
+ *   X = ((double(float(x) - float(cx)) z) / fx) / 1000, Y alike with (y, cy, fy), Z = z / 1000.
+ * State: T_k, prev = 0.0, not done.  The origin o is the mean of the source rows moved by T_0 (a non-finite coordinate counts as 0),
+ * computed once: the 6 x 6 system is formed about it, which keeps it well conditioned at coordinates around 1 m.  A pair with
+ * status_in != 0 or n_s < 6 returns T_0 with iters = 0.  For k = 0 .. max_iter - 1, while not done:
+ *   1 move       s = ((R0 x + R1 y) + R2 z) + t per coordinate, [R | t] of T_k.
+ *   2 associate  the row is dropped unless s.z > 0.  u = (fx s.x) / s.z + cx, v = (fy s.y) / s.z + cy, px = floor(u + 0.5),
+ *                py = floor(v + 0.5).  Dropped unless 1 <= px <= W - 2, 1 <= py <= H - 2, mask[py,px] == 1 and depth[py,px] > 0.
+ *   3 normal     each of the four neighbours (px +- 1, py), (px, py +- 1) must have depth > 0 and |z_nb - z_c| <= normal_jump * 1000,
+ *                otherwise the row is dropped.  a = V(px+1,py) - V(px-1,py), b = V(px,py+1) - V(px,py-1), c = a x b,
+ *                l = sqrt((cx^2 + cy^2) + cz^2); dropped unless l > 0 and finite; n = c / l.  Nothing below depends on the sign of n.
+ *   4 gate       d = V(px,py), e = s - d, dist = sqrt((ex^2 + ey^2) + ez^2); the row is kept when dist <= max_dist; m rows are kept.
+ *                m < 6: the pair is done and T_k stays.
+ *   5 sums       r = (nx ex + ny ey) + nz ez, J = [(s - o) x n, n]; A = sum J J^T (21 unique sums), g = sum J r (6), sum |r| and the
+ *                count: 29 sums.  mean_k = sum |r| / m.
+ *   6 solve      A x = -g by an unblocked Cholesky written out in a fixed order (column j: d = A_jj - sum_{q<j} L_jq^2, q ascending;
+ *                L_ij = (A_ij - sum_{q<j} L_iq L_jq) / L_jj; forward then backward substitution, each sum ascending).  A pivot d
+ *                that is not > 1e-12 max_i A_ii: the pair is done and T_k stays.  omega = x[0:3], v = x[3:6].  The rotation is the
+ *                Cayley map - no sin, no cos: a = omega / 2, R = I + 2 / (1 + a.a) ([a]x + [a]x^2) with [a]x^2 = a a^T - (a.a) I.
+ *                dT: p -> R (p - o) + o + v, i.e. t = (o - R o) + v; T_{k+1} = dT T_k.  |prev - mean_k| < tolerance: the pair is
+ *                done, with this update applied (as g2 does); otherwise prev = mean_k.
+ * The ORDER of the sums over rows is not part of the definition, but it is fixed exactly as g2's is: no atomics, outputs bit-stable
+ * across runs, streams and batch position.
+ *
+ * oryon_icp_plane_refine: src [B,cap_src,3] float64; n_src [B] DEVICE counts (above the capacity: read as the capacity; rows beyond the
+ *   count are never read); depth [B,H,W] fp32, mask [B,H,W] int32, cam9 [B,9] float64; T_init [B,16] fp32; status_in [B] or NULL.
+ *   1 <= cap_src <= ORYON_ICP_MAX_ROWS, 1 <= max_iter <= ORYON_ICP_MAX_ITER (two launches per iteration, all enqueued at once; a
+ *   finished pair's workgroups return at once), B <= 65535, H, W >= 3, H W < 2^31, tolerance, max_dist, normal_jump >= 0.
+ *   workspace: oryon_icp_plane_workspace_bytes(B, cap_src) bytes (0 = unsupported shape), 256-byte aligned
+ *     = align256(B * ORYON_ICP_STATE_BYTES) + align256(B * ceil(cap_src / 256) * ORYON_ICP_PLANE_REC * 8).
+ *   Outputs as oryon_icp_refine's: T [B,16] fp32, rows 0-2 exactly float32(T64), row 3 T_init's; T64 [B,12] or NULL; iters [B] updates
+ *   applied; mean_err [B] mean_k of the last update applied (0.0 when none); n_kept [B] m of the last executed iteration; idx
+ *   [B,cap_src] or NULL: py W + px of the last executed iteration for a kept row, -1 otherwise; status_out [B] = status_in (0 when
+ *   NULL).  float64 pointers must be 8-byte aligned. */
+#define ORYON_ICP_PLANE_REC 29
+size_t oryon_icp_plane_workspace_bytes(int B, int cap_src);
+int oryon_icp_plane_refine(const double *src, const int32_t *n_src, int cap_src, const float *depth, const int32_t *mask, int H, int W,
+                           const double *cam9, int B, const float *T_init, int max_iter, double tolerance, double max_dist,
+                           double normal_jump, const int32_t *status_in, void *workspace, size_t workspace_bytes, float *T, double *T64,
+                           int32_t *iters, double *mean_err, int32_t *n_kept, int32_t *idx, int32_t *status_out, void *stream);
+
 /* a5  StandardDecoder.forward (models/decoder.py:82-108) on the device, fp32 in / fp32 out, for the decoder the reference builds
  *     (get_decoder, models/decoder.py:119-125: input_dim 128, decoder_dims [64, 32], extra_upsampling, guidance projections 256->32 and
  *     128->16): three Up blocks (ConvTranspose2d 2x2 s2 -> cat guidance -> (conv3x3 - GroupNorm(C/16) - ReLU) x 2, :9-42), the two

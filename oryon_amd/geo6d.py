@@ -5,7 +5,8 @@
 
 The arithmetic runs in liboryon_hip.so (csrc/ransac.hip: every hypothesis of a call is scored in ONE launch); this module only
 moves the arrays and keeps numpy's global generator where the reference leaves it.  `icp` and `best_fit_transform_icp` run in
-csrc/icp.hip (ops.icp_refine: float64 throughout, the clouds need not be of equal length).  The points are handed to the kernel as
+csrc/icp.hip (ops.icp_refine: float64 throughout, the clouds need not be of equal length); `icp_point_to_plane`, which the reference
+does not have, runs point-to-plane ICP of a cloud onto a depth map (csrc/icp_plane.hip, ops.icp_plane_refine).  The points are handed to the kernel as
 float32 (what pipeline.py:459-463 passes); fits and the inlier test are float64, as numpy computes them for float64 input.
 """
 from __future__ import annotations
@@ -108,4 +109,25 @@ def icp(A, B, init_pose=None, max_iterations=20, tolerance=0.001, *, max_dist=fl
     out = ops.icp_refine(_cloud(A, dev), _cloud(B, dev), torch.tensor([A.shape[0]], dtype=torch.int32, device=dev),
                          torch.tensor([B.shape[0]], dtype=torch.int32, device=dev), torch.from_numpy(np.ascontiguousarray(T0))[None].to(dev),
                          max_iter=int(max_iterations), tolerance=float(tolerance), max_dist=float(max_dist))
+    return out["T64"][0].cpu().numpy()
+
+
+def icp_point_to_plane(A, depth_mm, mask, K, init_pose=None, max_iterations=20, tolerance=1e-5, *, max_dist=0.02, normal_jump=0.02,
+                       device="cuda") -> np.ndarray:
+    """Point-to-plane ICP of the cloud A [n,3] (metres) onto a depth map: depth_mm [H,W] millimetres, mask [H,W] (1 = object), K the
+    [3,3] intrinsics; from init_pose ([4,4], None = identity) -> [3,4] float64.  Projective association against the map's own normals
+    (include/oryon_hip.h, oryon_icp_plane_refine; csrc/icp_plane.hip); max_dist and normal_jump in metres.  init_pose and K reach the
+    kernel as float32 values, as the solvers' poses and the pipeline's intrinsics do.  The reference has no counterpart."""
+    A = _as_points(A)
+    dev = torch.device(device)
+    T0 = np.eye(4, dtype=np.float32) if init_pose is None else np.asarray(init_pose, dtype=np.float32).reshape(4, 4)
+    depth_mm, mask = np.asarray(depth_mm), np.asarray(mask)
+    assert depth_mm.ndim == 2 and mask.shape == depth_mm.shape, "depth_mm and mask are [H, W]"
+    if A.shape[0] < 6:                                      # the definition: such a pair returns T_0
+        return T0[:3, :].astype(np.float64)
+    t = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dtype=dt))[None].to(dev)
+    cam9 = np.asarray(K, dtype=np.float32).reshape(9).astype(np.float64)
+    out = ops.icp_plane_refine(_cloud(A, dev), torch.tensor([A.shape[0]], dtype=torch.int32, device=dev), t(depth_mm, np.float32),
+                               t(mask == 1, np.int32), t(cam9, np.float64), t(T0, np.float32), max_iter=int(max_iterations),
+                               tolerance=float(tolerance), max_dist=float(max_dist), normal_jump=float(normal_jump))
     return out["T64"][0].cpu().numpy()

@@ -1117,6 +1117,72 @@ def icp_best_fit(A: torch.Tensor, Bp: torch.Tensor, n: torch.Tensor):
     return dict(T=T, T64=T64, fitted=fitted, mean_err=mean_err)
 
 
+def _icp_plane_require(cond: bool, check_name: str, detail: str = "") -> None:
+    if not cond:
+        raise ValueError(f"icp_plane_refine: {check_name}" + (f" ({detail})" if detail else ""))
+
+
+def icp_plane_refine(src: torch.Tensor, n_src: torch.Tensor, depth: torch.Tensor, mask: torch.Tensor, cam9: torch.Tensor,
+                     T_init: torch.Tensor, max_iter: int = 20, tolerance: float = 1e-5, max_dist: float = 0.02, normal_jump: float = 0.02,
+                     status: Optional[torch.Tensor] = None, want_idx: bool = False, workspace: Optional[torch.Tensor] = None):
+    """Point-to-plane ICP of B source clouds onto the queries' depth maps (g3, csrc/icp_plane.hip; definition: include/oryon_hip.h,
+    oryon_icp_plane_refine).  src [B,cap_src,3] float64 metres, n_src [B] int32, depth [B,H,W] fp32 millimetres, mask [B,H,W] int32
+    (1 = object), cam9 [B,9] float64, T_init [B,4,4] fp32, status [B] int32 or None - all contiguous device tensors of exactly these
+    dtypes: nothing is converted or copied here, a tensor that does not fit is rejected with the name of the check.  max_dist and
+    normal_jump in metres.  Runs on the current stream with no host round trip -> dict(T [B,4,4] fp32, T64 [B,3,4] float64, iters [B]
+    int32, mean_err [B] float64, n_kept [B] int32, idx [B,cap_src] int32 | None (py W + px of a kept row, -1 otherwise), status [B])."""
+    req = _icp_plane_require
+    for name, t in (("src", src), ("n_src", n_src), ("depth", depth), ("mask", mask), ("cam9", cam9), ("T_init", T_init)):
+        req(isinstance(t, torch.Tensor) and t.is_cuda, f"{name}.is_cuda")
+    req(src.dtype == torch.float64, "src.dtype == float64", str(src.dtype))
+    req(src.dim() == 3 and src.shape[2] == 3 and src.shape[1] >= 1, "src.shape == [B,cap_src,3]", str(tuple(src.shape)))
+    B, cap_src = src.shape[0], src.shape[1]
+    req(B >= 1, "B >= 1")
+    req(src.is_contiguous(), "src.is_contiguous")
+    for name, t in (("n_src", n_src),) + ((("status", status),) if status is not None else ()):
+        req(t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (B,), f"{name} is [B] int32", f"{tuple(t.shape)} {t.dtype}")
+        req(t.is_contiguous(), f"{name}.is_contiguous")
+    req(depth.dtype == torch.float32, "depth.dtype == float32", str(depth.dtype))
+    req(depth.dim() == 3 and depth.shape[0] == B, "depth.shape == [B,H,W]", str(tuple(depth.shape)))
+    H, W = depth.shape[1], depth.shape[2]
+    req(H >= 3 and W >= 3 and H * W < 2 ** 31, "H, W >= 3 and H W < 2^31", f"{H} x {W}")
+    req(depth.is_contiguous(), "depth.is_contiguous")
+    req(mask.dtype == torch.int32, "mask.dtype == int32", str(mask.dtype))
+    req(tuple(mask.shape) == (B, H, W), "mask.shape == depth.shape", str(tuple(mask.shape)))
+    req(mask.is_contiguous(), "mask.is_contiguous")
+    req(cam9.dtype == torch.float64, "cam9.dtype == float64", str(cam9.dtype))
+    req(tuple(cam9.shape) == (B, 9), "cam9.shape == [B,9]", str(tuple(cam9.shape)))
+    req(cam9.is_contiguous(), "cam9.is_contiguous")
+    req(T_init.dtype == torch.float32, "T_init.dtype == float32", str(T_init.dtype))
+    req(tuple(T_init.shape) == (B, 4, 4), "T_init.shape == [B,4,4]", str(tuple(T_init.shape)))
+    req(T_init.is_contiguous(), "T_init.is_contiguous")
+    req(all(t.device == src.device for t in (n_src, depth, mask, cam9, T_init) + ((status,) if status is not None else ())), "one device")
+    max_iter = int(max_iter)
+    req(1 <= max_iter <= ICP_MAX_ITER, f"1 <= max_iter <= {ICP_MAX_ITER}", str(max_iter))
+    req(float(tolerance) >= 0.0, "tolerance >= 0", str(tolerance))
+    req(float(max_dist) >= 0.0, "max_dist >= 0", str(max_dist))
+    req(float(normal_jump) >= 0.0, "normal_jump >= 0", str(normal_jump))
+    req(cap_src <= ICP_MAX_ROWS, f"cap_src <= {ICP_MAX_ROWS}", str(cap_src))
+    dev = _lib.require_gpu(src.device)
+    with torch.cuda.device(dev):
+        need = lib().oryon_icp_plane_workspace_bytes(B, cap_src)
+        if need == 0:
+            raise _lib.OryonError(f"oryon_icp_plane_workspace_bytes({B}, {cap_src}): shape not supported")
+        ws = workspace if workspace is not None else torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+        T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+        T64 = torch.empty((B, 3, 4), dtype=torch.float64, device=dev)
+        iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        mean_err = torch.empty((B,), dtype=torch.float64, device=dev)
+        n_kept = torch.empty((B,), dtype=torch.int32, device=dev)
+        idx = torch.empty((B, cap_src), dtype=torch.int32, device=dev) if want_idx else None
+        st_out = torch.empty((B,), dtype=torch.int32, device=dev)
+        check(lib().oryon_icp_plane_refine(ptr(src), ptr(n_src), cap_src, ptr(depth), ptr(mask), H, W, ptr(cam9), B, ptr(T_init), max_iter,
+                                           float(tolerance), float(max_dist), float(normal_jump), ptr(status), ptr(ws), ws.numel(), ptr(T),
+                                           ptr(T64), ptr(iters), ptr(mean_err), ptr(n_kept), ptr(idx), ptr(st_out), stream_ptr(dev)),
+              "oryon_icp_plane_refine")
+    return dict(T=T, T64=T64, iters=iters, mean_err=mean_err, n_kept=n_kept, idx=idx, status=st_out)
+
+
 _x3_weights = {}
 # Validation mode of the fp16x3 path (backbone.enable_fp16x3(True, guard=True)): every call first checks max|activation| against the
 # float16 range (one reduction + a host sync per linear - for a first run with a real checkpoint, not for throughput) and evaluates

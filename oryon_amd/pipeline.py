@@ -10,7 +10,9 @@
 
 `test.refine = icp` (absent or `none`: nothing changes) refines every solved pose by ICP of the anchor's object cloud onto the query's
 (utils/geo6d.py:157-208 `icp`, csrc/icp.hip) in both routes; flags test.refine_points / refine_max_iter / refine_tolerance /
-refine_max_dist.
+refine_max_dist.  `test.refine = icp_plane` refines it by point-to-plane ICP of the anchor's object cloud onto the query's DEPTH MAP
+(projective association, csrc/icp_plane.hip; no counterpart in the reference): the same flags with defaults of their own
+(REFINE_DEFAULTS) and test.refine_normal_jump.
 
 and the validation step (pipeline.py:196-247, 579-590):
 
@@ -43,7 +45,13 @@ from .pcd import nn_correspondences
 from .pointdsc import PointDSC, get_pointdsc_pose
 
 
-REFINEMENTS = ("none", "icp")
+REFINEMENTS = ("none", "icp", "icp_plane")
+# test.refine_tolerance / refine_max_dist / refine_normal_jump (metres) where the args do not name them.  icp: the reference's.
+# icp_plane: design choices, not tuned on data - the 1 mm tolerance of icp stops point-to-plane too early (its mean |r| is a distance
+# along the normal, far smaller than a point-to-point distance: fixture 4 of tests/icp_plane_restatement.py stops after two iterations,
+# 8.2 degrees off, where 1e-5 takes seven to 0.05 degrees), and the gates are the scale of a solver's error (2 cm) and of a depth step
+# between neighbouring pixels that is an edge rather than a slope (2 cm).
+REFINE_DEFAULTS = {"icp": dict(tolerance=1e-3, max_dist=float("inf")), "icp_plane": dict(tolerance=1e-5, max_dist=0.02, normal_jump=0.02)}
 _default_refine = "none"
 
 
@@ -128,7 +136,7 @@ class Pipeline:
         self._valid_log: List[Dict[str, float]] = []
         self._valid_fmr: List[float] = []
         self.last_validation: Optional[Dict] = None      # the latest validation_step's {'poses', 'status', 'results', 'losses'}
-        self.last_refine: Optional[Dict] = None          # the latest ops.icp_refine result (test.refine = icp)
+        self.last_refine: Optional[Dict] = None          # the latest ops.icp_refine / ops.icp_plane_refine result (test.refine)
         self.refine_mode()                               # an unknown test.refine raises here, not at the first pose
 
     # ------------------------------------------------------------------ mask post-processing (losses.py:56-60)
@@ -184,7 +192,8 @@ class Pipeline:
     REFINE_SEED_A, REFINE_SEED_Q = 0x1C9A0A, 0x1C9A0B       # the two sides' subsamples draw from streams of their own
 
     def refine_mode(self) -> str:
-        """test.refine: 'none' (absent = the process-wide default, 'none' unless a driver set it) or 'icp' - ICP of the anchor's object cloud onto the query's, started at the solver's pose."""
+        """test.refine: 'none' (absent = the process-wide default, 'none' unless a driver set it), 'icp' - ICP of the anchor's object
+        cloud onto the query's - or 'icp_plane' - point-to-plane ICP of that cloud onto the query's depth map - started at the solver's pose."""
         mode = getattr(self.args.test, "refine", default_refine())
         if mode not in REFINEMENTS:
             raise RuntimeError(f"Refinement {mode} not implemented")
@@ -197,36 +206,70 @@ class Pipeline:
         (seed, pair key) - so a pair's cloud does not depend on the batch it arrives in - and lifted in float64 (ops.gtc_lift).
         depth_* [B,H,W] fp32 millimetres, cam_* [B,9] or [B,3,3], pair_key [B] int64 -> src, dst [B,cap,3] float64 metres (anchor,
         query) and n_src, n_dst [B] int32, all on the device, nothing read back."""
-        points = int(getattr(self.args.test, "refine_points", 2048))
-        seed = self.args.seed if self.args.seed is not None else 1
         out = {}
         for side, mask, depth, cam, salt in (("src", mask_a, depth_a, cam_a, self.REFINE_SEED_A), ("dst", mask_q, depth_q, cam_q, self.REFINE_SEED_Q)):
-            B, H, W = depth.shape
-            m = ops.mask_resize_nearest(mask, (H, W)) if tuple(mask.shape[-2:]) != (H, W) else mask.to(torch.int32)
-            m = ((m == 1) & (depth > 0)).to(torch.int32)
-            roi, count = ops.roi_compact(m)
-            ops.roi_subsample_(roi, count, points, seed ^ salt, pair_key)
-            cap = min(points, H * W)
-            pix = roi[:, :cap].contiguous()
-            count = torch.clamp(count, max=cap)
-            # the intrinsics as both solver routes see them: fp32 values, widened
-            xyz, _ = ops.gtc_lift(depth, pix, count, cam.to(depth.device, torch.float32).to(torch.float64).reshape(B, 9))
-            out[side], out["n_" + side] = xyz, count
+            out[side], out["n_" + side] = self._refine_cloud(mask, depth, cam, salt, pair_key)
         return out
 
+    @staticmethod
+    def _object_mask(mask: Tensor, depth: Tensor) -> Tensor:
+        """The object's pixels of one side: the mask resized (nearest) to the depth map's size, AND depth > 0 -> [B,H,W] int32."""
+        H, W = depth.shape[-2:]
+        m = ops.mask_resize_nearest(mask, (H, W)) if tuple(mask.shape[-2:]) != (H, W) else mask.to(torch.int32)
+        return ((m == 1) & (depth > 0)).to(torch.int32)
+
+    def _refine_cloud(self, mask: Tensor, depth: Tensor, cam: Tensor, salt: int, pair_key: Tensor) -> Tuple[Tensor, Tensor]:
+        """One side of refine_clouds -> (xyz [B,cap,3] float64 metres, count [B] int32)."""
+        points = int(getattr(self.args.test, "refine_points", 2048))
+        seed = self.args.seed if self.args.seed is not None else 1
+        B, H, W = depth.shape
+        roi, count = ops.roi_compact(self._object_mask(mask, depth))
+        ops.roi_subsample_(roi, count, points, seed ^ salt, pair_key)
+        cap = min(points, H * W)
+        pix = roi[:, :cap].contiguous()
+        count = torch.clamp(count, max=cap)
+        # the intrinsics as both solver routes see them: fp32 values, widened
+        xyz, _ = ops.gtc_lift(depth, pix, count, cam.to(depth.device, torch.float32).to(torch.float64).reshape(B, 9))
+        return xyz, count
+
+    def refine_target(self, mask_q: Tensor, depth_q: Tensor, cam_q: Tensor) -> Dict[str, Tensor]:
+        """The target of test.refine = icp_plane: the query's depth map as it is ([B,H,W] fp32 millimetres), its object mask (resized
+        with nearest to the depth map's size, AND depth > 0; int32) and the intrinsics as fp32 values, widened ([B,9] float64)."""
+        B = depth_q.shape[0]
+        return dict(depth=depth_q.contiguous(), mask=self._object_mask(mask_q, depth_q).contiguous(),
+                    cam9=cam_q.to(depth_q.device, torch.float32).to(torch.float64).reshape(B, 9).contiguous())
+
+    def refine_inputs(self, mask_a: Tensor, mask_q: Tensor, depth_a: Tensor, depth_q: Tensor, cam_a: Tensor, cam_q: Tensor,
+                      pair_key: Tensor) -> Dict[str, Tensor]:
+        """What refine_poses runs on in the pipeline's mode: refine_clouds (icp), or the anchor's cloud - the very cloud refine_clouds
+        builds for it - and refine_target (icp_plane)."""
+        if self.refine_mode() == "icp_plane":
+            src, n_src = self._refine_cloud(mask_a, depth_a, cam_a, self.REFINE_SEED_A, pair_key)
+            return dict(self.refine_target(mask_q, depth_q, cam_q), src=src, n_src=n_src)
+        return self.refine_clouds(mask_a, mask_q, depth_a, depth_q, cam_a, cam_q, pair_key)
+
     def refine_poses(self, pose: Tensor, status: Optional[Tensor], clouds: Dict[str, Tensor]) -> Dict[str, Tensor]:
-        """ops.icp_refine with the flags test.refine_max_iter / refine_tolerance / refine_max_dist: pose [B,4,4] fp32 (the solver's) ->
-        the refined poses and the iteration counts; a pair with a failure status keeps its pose."""
+        """ops.icp_refine (clouds of refine_clouds) or ops.icp_plane_refine (clouds of refine_inputs in mode icp_plane: they hold a depth
+        map) with the flags test.refine_max_iter / refine_tolerance / refine_max_dist / refine_normal_jump (defaults: REFINE_DEFAULTS of
+        the mode): pose [B,4,4] fp32 (the solver's) -> the refined poses and the iteration counts; a pair with a failure status keeps
+        its pose."""
         t = self.args.test
+        plane = "depth" in clouds
+        d = REFINE_DEFAULTS["icp_plane" if plane else "icp"]
+        max_iter, tolerance = int(getattr(t, "refine_max_iter", 20)), float(getattr(t, "refine_tolerance", d["tolerance"]))
+        max_dist = float(getattr(t, "refine_max_dist", d["max_dist"]))
+        if plane:
+            return ops.icp_plane_refine(clouds["src"], clouds["n_src"], clouds["depth"], clouds["mask"], clouds["cam9"],
+                                        pose.to(torch.float32).contiguous(), max_iter=max_iter, tolerance=tolerance, max_dist=max_dist,
+                                        normal_jump=float(getattr(t, "refine_normal_jump", d["normal_jump"])), status=status)
         return ops.icp_refine(clouds["src"], clouds["dst"], clouds["n_src"], clouds["n_dst"], pose.to(torch.float32).contiguous(),
-                              max_iter=int(getattr(t, "refine_max_iter", 20)), tolerance=float(getattr(t, "refine_tolerance", 1e-3)),
-                              max_dist=float(getattr(t, "refine_max_dist", float("inf"))), status=status)
+                              max_iter=max_iter, tolerance=tolerance, max_dist=max_dist, status=status)
 
     def _refine_masks(self, batch: Dict, results: Optional[Dict], dev) -> Tuple[Tensor, Tensor]:
         if self.args.test.mask != "predicted":
             return batch["anchor"]["mask"].to(dev), batch["query"]["mask"].to(dev)
         if results is None or "mask_a" not in results:
-            raise KeyError("test.refine='icp' with test.mask='predicted' needs the predicted masks (results['mask_a'], results['mask_q'])")
+            raise KeyError(f"test.refine='{self.refine_mode()}' with test.mask='predicted' needs the predicted masks (results['mask_a'], results['mask_q'])")
         return results["mask_a"], results["mask_q"]
 
     # ------------------------------------------------------------------ pipeline.py:429-472
@@ -256,10 +299,10 @@ class Pipeline:
             pose4 = torch.tensor(pose4)
         else:
             pose4 = get_pointdsc_pose(self.pointdsc_solver, pcd_a[0, :m], pcd_q[0, :m], self.device)
-        if self.refine_mode() == "icp":
+        if self.refine_mode() != "none":
             mask_a, mask_q = self._refine_masks(batch, results, dev)
             key = torch.tensor([idx if pair_key is None else pair_key], dtype=torch.int64, device=dev)
-            clouds = self.refine_clouds(mask_a[idx:idx + 1], mask_q[idx:idx + 1], depth_a[None].contiguous(), depth_q[None].contiguous(),
+            clouds = self.refine_inputs(mask_a[idx:idx + 1], mask_q[idx:idx + 1], depth_a[None].contiguous(), depth_q[None].contiguous(),
                                         camera_a, camera_q, key)
             self.last_refine = self.refine_poses(pose4.to(torch.float32)[None].to(dev), None, clouds)
             return self.last_refine["T"][0].cpu()
@@ -335,7 +378,7 @@ class Pipeline:
             iou_q = results["iou_q"][i_b].cpu().numpy()
             self.add_pred_pose(id_a, id_q, iou_a, iou_q, pred_pose.cpu().numpy())
             records.append(dict(status=status, pred_pose_rel=pred_pose, pred_pose=pred_q))
-            if status == PAIR_OK and self.refine_mode() == "icp":
+            if status == PAIR_OK and self.refine_mode() != "none":
                 records[-1]["refine_iters"] = int(self.last_refine["iters"][0])
         return records
 
@@ -368,9 +411,9 @@ class Pipeline:
         key = torch.arange(first_pair_index, first_pair_index + BS, dtype=torch.int64, device=dev)
         out = self._engine.run(outputs["featmap_a"].float().contiguous(), outputs["featmap_q"].float().contiguous(), mask_a,
                                mask_q, depth_a, depth_q, batch["anchor"]["camera"].to(dev), batch["query"]["camera"].to(dev), key)
-        if self.refine_mode() == "icp":                          # same stream, no host round trip; failed pairs keep their identity
+        if self.refine_mode() != "none":                         # same stream, no host round trip; failed pairs keep their identity
             rmask_a, rmask_q = self._refine_masks(batch, res, dev)
-            self.last_refine = self.refine_poses(out["pose"], out["status"], self.refine_clouds(
+            self.last_refine = self.refine_poses(out["pose"], out["status"], self.refine_inputs(
                 rmask_a, rmask_q, depth_a, depth_q, batch["anchor"]["camera"].to(dev), batch["query"]["camera"].to(dev), key))
             out["pose_unrefined"], out["pose"], out["refine_iters"] = out["pose"], self.last_refine["T"], self.last_refine["iters"]
         anchor_pose = batch["anchor"]["pose"].to(dev, torch.float32)

@@ -12,9 +12,10 @@ utils/geo6d.py:75-120, max_iter=10000, fix_percent=0.9999, match_err=0.001 as pi
 
     python run_pose.py --solver ransac --refine icp --pairs 8
 
-`--refine {none,icp}` (default none; test.refine) becomes the process-wide default refinement (oryon_amd.pipeline.set_default_refine),
+`--refine {none,icp,icp_plane}` (default none; test.refine) becomes the process-wide default refinement (oryon_amd.pipeline.set_default_refine),
 which every Pipeline that run_test.py builds then applies: every solved pose is refined by ICP of the anchor's object cloud onto the
-query's (utils/geo6d.py:157-208 `icp`, csrc/icp.hip), in the per-sample loop and behind the batched engine alike.
+query's (utils/geo6d.py:157-208 `icp`, csrc/icp.hip), in the per-sample loop and behind the batched engine alike; `icp_plane` refines it
+by point-to-plane ICP of that cloud onto the query's depth map instead (projective association, csrc/icp_plane.hip).
 
     python run_pose.py --vsd --data-root /data --dataset nocs --ckpt ... --out preds/nocs.csv
 
@@ -32,10 +33,13 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+REFINE_CHOICES = ["none", "icp", "icp_plane"]          # oryon_amd.pipeline.REFINEMENTS
+
+
 def take_refine(argv=None):
-    """-> (test.refine: 'none' or 'icp', argv without `--refine ...`); an unknown refinement exits like an unknown solver."""
+    """-> (test.refine: 'none', 'icp' or 'icp_plane', argv without `--refine ...`); an unknown refinement exits like an unknown solver."""
     ap = argparse.ArgumentParser(add_help=False)
-    ap.add_argument("--refine", choices=["none", "icp"], default="none")
+    ap.add_argument("--refine", choices=REFINE_CHOICES, default="none")
     a, rest = ap.parse_known_args(argv)
     return a.refine, rest
 
@@ -45,7 +49,7 @@ def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
     ap.add_argument("--solver", choices=["pointdsc", "ransac"], default="pointdsc",
                     help="test.solver: PointDSC registration, or best_fit_transform_with_RANSAC (needs no PointDSC weights)")
-    ap.add_argument("--refine", choices=["none", "icp"], default="none", help="test.refine: ICP refinement of every solved pose (see above)")
+    ap.add_argument("--refine", choices=REFINE_CHOICES, default="none", help="test.refine: ICP refinement of every solved pose (see above)")
     ap.add_argument("-h", "--help", action="store_true")
     a, rest = ap.parse_known_args(argv)
     if a.help:

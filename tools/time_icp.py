@@ -1,7 +1,10 @@
 """ICP refinement time (ops.icp_refine, csrc/icp.hip): B pairs of N x N points, ITERS forced iterations (tolerance = 0: no pair
 finishes early), device events after a warm-up.  GPU box.
 
-    python tools/time_icp.py [B=64] [N=2048] [ITERS=20]
+    python tools/time_icp.py [B=64] [N=2048] [ITERS=20] [--mode icp|plane]
+
+`--mode plane`: point-to-plane ICP on the depth map instead (ops.icp_plane_refine, csrc/icp_plane.hip): B pairs of N source rows onto
+480 x 640 depth maps, ITERS forced iterations - 2 ITERS + 1 small launches, no candidate search.
 
 Prints one JSON line: ms per call (median and spread over the repeats), the candidate evaluations per second, and - for scale - the
 estimate DESIGN.md "ICP refinement" started from (B ITERS N^2 candidates at ~8 float64 VALU instructions each at the unpacked vector
@@ -33,8 +36,71 @@ def clouds(B, N, dev, seed=0):
     return t(src), t(dst)
 
 
+def plane_inputs(B, N, dev, H=480, W=640, seed=0):
+    """A smooth bumpy surface ~0.9 m away filling the map, an elliptic object mask, and N sub-pixel samples of the object as the source;
+    the start pose is 2 degrees and 5 mm off and every row is kept at every forced iteration: the full cost of a row, every time."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    surf = lambda x, y: 900.0 + 30.0 * np.sin(0.02 * x + 0.3) * np.cos(0.017 * y) + 0.05 * x + 15.0 * np.cos(0.03 * (x + y))
+    depth = surf(xx, yy).astype(np.float32)
+    mask = (((xx - W / 2) / (0.3 * W)) ** 2 + ((yy - H / 2) / (0.3 * H)) ** 2 <= 1.0).astype(np.int32)
+    f, cx, cy = 600.0, W / 2 - 0.5, H / 2 - 0.5
+    r, a = np.sqrt(rng.uniform(0, 1, (B, N))) * 0.29, rng.uniform(0, 2 * np.pi, (B, N))
+    x, y = W / 2 + r * W * np.cos(a), H / 2 + r * H * np.sin(a)
+    z = surf(x, y)
+    src = np.stack([(x - cx) * z / f / 1000.0, (y - cy) * z / f / 1000.0, z / 1000.0], axis=-1)
+    c = src.reshape(-1, 3).mean(axis=0)
+    ang = np.deg2rad(2.0)
+    T0 = np.eye(4)
+    T0[:3, :3] = np.array([[np.cos(ang), 0.0, np.sin(ang)], [0.0, 1.0, 0.0], [-np.sin(ang), 0.0, np.cos(ang)]])
+    T0[:3, 3] = c - T0[:3, :3] @ c + np.array([0.003, -0.003, 0.003])
+    t = lambda v, dt: torch.from_numpy(np.ascontiguousarray(v)).to(dt).to(dev)
+    cam9 = np.tile(np.array([f, 0.0, cx, 0.0, f, cy, 0.0, 0.0, 1.0]), (B, 1))
+    return (t(src, torch.float64), t(np.tile(depth, (B, 1, 1)), torch.float32), t(np.tile(mask, (B, 1, 1)), torch.int32), t(cam9, torch.float64),
+            t(np.tile(T0, (B, 1, 1)), torch.float32))
+
+
+def main_plane(B, N, iters):
+    dev = torch.device("cuda", 0)
+    src, depth, mask, cam9, T0 = plane_inputs(B, N, dev)
+    n = torch.full((B,), N, dtype=torch.int32, device=dev)
+    ws = torch.empty((max(ops.lib().oryon_icp_plane_workspace_bytes(B, N), 256),), dtype=torch.uint8, device=dev)
+    call = lambda: ops.icp_plane_refine(src, n, depth, mask, cam9, T0, max_iter=iters, tolerance=0.0, workspace=ws)
+    for _ in range(3):
+        out = call()
+    torch.cuda.synchronize()
+    assert int(out["iters"].min()) == iters, "tolerance = 0 forces every iteration"
+    ms = timed(call)
+    med = ms[len(ms) // 2]
+    print(json.dumps({"mode": "plane", "B": B, "N": N, "map": [480, 640], "iters": iters, "launches": 2 * iters + 1, "ms_per_call": round(med, 4),
+                      "ms_min": round(ms[0], 4), "ms_max": round(ms[-1], 4), "us_per_pair": round(1e3 * med / B, 2),
+                      "us_per_launch": round(1e3 * med / (2 * iters + 1), 2), "n_kept_first_pair": int(out["n_kept"][0]),
+                      "mean_err_first_pair": float(out["mean_err"][0])}))
+
+
+def timed(call, reps=7, per=10):
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(per):
+            call()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / per)
+    return sorted(ms)
+
+
 def main(argv):
+    mode = "icp"
+    if "--mode" in argv:
+        at = argv.index("--mode")
+        mode, argv = argv[at + 1], argv[:at] + argv[at + 2:]
+    if mode not in ("icp", "plane"):
+        raise SystemExit("--mode icp|plane")
     B, N, iters = (int(a) for a in (argv + ["64", "2048", "20"][len(argv):])[:3])
+    if mode == "plane":
+        return main_plane(B, N, iters)
     dev = torch.device("cuda", 0)
     src, dst = clouds(B, N, dev)
     n = torch.full((B,), N, dtype=torch.int32, device=dev)
@@ -46,17 +112,7 @@ def main(argv):
         out = call()
     torch.cuda.synchronize()
     assert int(out["iters"].min()) == iters, "tolerance = 0 forces every iteration"
-    reps, per = 7, 10
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(per):
-            call()
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1) / per)
-    ms.sort()
+    ms = timed(call)
     med = ms[len(ms) // 2]
     print(json.dumps({"B": B, "N": N, "iters": iters, "ms_per_call": round(med, 4), "ms_min": round(ms[0], 4), "ms_max": round(ms[-1], 4),
                       "us_per_pair": round(1e3 * med / B, 2), "candidates_per_s": round(B * iters * N * N / (med * 1e-3), -6),
