@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void match_decide_lite_kernel(
         // this pair's fp32 query rows get materialised (device-gated launch) - with the fp16x3 second level (x3) only when an
         // ambiguous anchor's VALIDITY is open too: the sampled valid ones are then resolved from hi / lo half rows made later
         if (st == LZ_AMB_UNCERTAIN || !x3) need_f32_lazy[p] = 1;
-        atomicAdd(&n_amb_total[p], 1);
+        atomicAdd(&n_amb_total[p], 1);      // (the compiler already issues one add per wave: a ballot count written by hand measured no faster)
     }
 }
 
@@ -290,7 +290,8 @@ __global__ __launch_bounds__(256) void match_decide_sampled_kernel(int cap_a, in
 // The result needs the validity of every anchor (one witness query within the threshold) and the complete (m1, slice, m2) of the sampled
 // ones only.  On descriptors without the hard route's smoothness no whole panel settles, but row-major neighbours still match row-major
 // neighbours, so the tiles a panel's matches lie in are LEARNED: a probe of every DC stride-th anchor gets the complete screen, the range
-// of the probe's winning tiles (+ slack) is the panel's band, the band pass settles the rows that find their witness there, and only the
+// of the probe's winning tiles (+ slack) is the panel's band - narrowed per 512-row half to the range of the half's own probe rows -, the
+// band pass settles the rows that find their witness there, and only the
 // rows left open (no counterpart at all, or a match outside the band) get the complete scan, compacted into dense 512-row panels.
 // A row is COMPLETE (true triple over all tiles: probe rows, rows of a panel whose band is "all tiles", open rows after their scan) or
 // SETTLED (partial maximum above match_decide_lite_kernel's line: valid for sure, m2 = +inf i.e. argmin open, as match_panel_settle_kernel
@@ -334,19 +335,24 @@ __global__ __launch_bounds__(256) void match_dc_probe_list_kernel(int stride, co
     if (threadIdx.x == 0) n_probe[p] = n;
 }
 
-// one workgroup per (1024-row panel, pair): the panel's probe rows get their complete triples, and the panel its band [first, count)
+// one workgroup per (1024-row panel, pair): the panel's probe rows get their complete triples, the panel its band [first, count) and
+// each of its two 512-row halves a sub-band inside it: band[p][2 panel + h] (what the band pass scans and the settle pass looks up).
+// The panel's band - and with it the decision to scan all tiles - is formed from all its sure probe rows as before the halves existed:
+// stats[p][3] is the sum of these parent widths.  A half of an "all tiles" panel, or one with fewer than DC_MIN_SURE sure probe rows of
+// its own, takes the panel's band; every other half the range of its own rows' winning tiles + slack, clipped to the panel's band.
+// sub_stats (dev build's sweeps): stats[p][3] sums the halves' widths instead.
 __global__ __launch_bounds__(256) void match_dc_probe_band_kernel(int cap_a, int T8, int stride, int S, const int32_t *__restrict__ n_a,
                                                                    const int32_t *__restrict__ n_q, const float *__restrict__ cs_m1,
                                                                    const int32_t *__restrict__ cs_i1, const float *__restrict__ cs_m2,
                                                                    const float *__restrict__ a_err, const float *__restrict__ q_err, float cut0,
                                                                    float *__restrict__ r_m1, int32_t *__restrict__ r_i1, float *__restrict__ r_m2,
-                                                                   int32_t *__restrict__ band, int32_t *__restrict__ stats, int slack)
+                                                                   int32_t *__restrict__ band, int32_t *__restrict__ stats, int slack, int sub_stats)
 {
-    __shared__ int lo, hi, cnt;
+    __shared__ int lo[2], hi[2], cnt[2];
     const int p = blockIdx.y, panel = blockIdx.x, t = threadIdx.x;
     const int na = n_a[p], a0 = panel * 1024;
     if (a0 >= na) return;
-    if (t == 0) { lo = 0x7fffffff; hi = -1; cnt = 0; }
+    if (t < 2) { lo[t] = 0x7fffffff; hi[t] = -1; cnt[t] = 0; }
     __syncthreads();
     const int a1 = a0 + 1024 < na ? a0 + 1024 : na;
     const int k_lo = (a0 + stride - 1) / stride;
@@ -362,26 +368,41 @@ __global__ __launch_bounds__(256) void match_dc_probe_band_kernel(int cap_a, int
         r_i1[arow] = sid;
         r_m2[arow] = m2;
         if (m1 > line) {
-            atomicMin(&lo, sid >> 3);               // 8 slices of 16 rows per 128-row tile
-            atomicMax(&hi, sid >> 3);
-            atomicAdd(&cnt, 1);
+            const int h = (k * stride - a0) >> 9;       // the row's 512-row half of the panel
+            atomicMin(&lo[h], sid >> 3);                // 8 slices of 16 rows per 128-row tile
+            atomicMax(&hi[h], sid >> 3);
+            atomicAdd(&cnt[h], 1);
         }
     }
     __syncthreads();
     if (t == 0) {
         const int nqt = (n_q[p] + 127) / 128;
-        int first = lo - slack < 0 ? 0 : lo - slack, end = hi + slack + 1 < nqt ? hi + slack + 1 : nqt;
-        if (cnt < DC_MIN_SURE || (long long)(end - first) * DC_BAND_CAP_DEN > (long long)nqt * DC_BAND_CAP_NUM) { first = 0; end = nqt; }
-        band[(p * T8 + panel) * 2] = first;
-        band[(p * T8 + panel) * 2 + 1] = end - first;
-        atomicAdd(&stats[p * 4 + 3], end - first);
+        const int plo = lo[0] < lo[1] ? lo[0] : lo[1], phi = hi[0] > hi[1] ? hi[0] : hi[1];
+        int first = plo - slack < 0 ? 0 : plo - slack, end = phi + slack + 1 < nqt ? phi + slack + 1 : nqt;
+        const bool all = cnt[0] + cnt[1] < DC_MIN_SURE || (long long)(end - first) * DC_BAND_CAP_DEN > (long long)nqt * DC_BAND_CAP_NUM;
+        if (all) { first = 0; end = nqt; }
+        int sub_sum = 0;
+        for (int h = 0; h < 2; ++h) {
+            int f = first, e = end;
+            if (!all && cnt[h] >= DC_MIN_SURE) {
+                f = lo[h] - slack > first ? lo[h] - slack : first;
+                e = hi[h] + slack + 1 < end ? hi[h] + slack + 1 : end;
+            }
+            band[((p * T8 + panel) * 2 + h) * 2] = f;
+            band[((p * T8 + panel) * 2 + h) * 2 + 1] = e - f;
+            if (a0 + 512 * h < na) sub_sum += e - f;
+        }
+        atomicAdd(&stats[p * 4 + 3], sub_stats ? sub_sum : end - first);
         if (panel == 0) stats[p * 4 + 0] = (na + stride - 1) / stride < MX6_SAMPLED_PANEL ? (na + stride - 1) / stride : MX6_SAMPLED_PANEL;
     }
 }
 
 // one workgroup per pair, after the band pass: every row that is no probe row gets its class and (unless open) its triple; the open rows
-// are listed in ascending order (the single-scan ordered compaction of match_list_sampled_amb_kernel)
-__global__ __launch_bounds__(256) void match_dc_settle_rows_kernel(int cap_a, int T8, int stride, int S, const int32_t *__restrict__ n_a,
+// are listed in ascending order.  A lane owns one row per iteration (a = i blockDim + t: the [B, S, cap_a] triples are read coalesced),
+// and a block-wide ordered scan of the iteration's open flags (the scan of block_scan_counts_sel, post.hip, on wave ballots) places them
+// behind the earlier iterations'.  The next iteration's triple and band are loaded before this one's barrier.
+constexpr int DC_SETTLE_THREADS = 1024;
+__global__ __launch_bounds__(DC_SETTLE_THREADS) void match_dc_settle_rows_kernel(int cap_a, int T8, int stride, int S, const int32_t *__restrict__ n_a,
                                                                     const int32_t *__restrict__ n_q, const float *__restrict__ ws_m1,
                                                                     const int32_t *__restrict__ ws_i1, const float *__restrict__ ws_m2,
                                                                     const float *__restrict__ a_err, const float *__restrict__ q_err, float cut0,
@@ -390,50 +411,63 @@ __global__ __launch_bounds__(256) void match_dc_settle_rows_kernel(int cap_a, in
                                                                     int32_t *__restrict__ n_open, int32_t *__restrict__ open_idx,
                                                                     int32_t *__restrict__ stats)
 {
-    __shared__ int wave_cnt[4], wave_settled[4];
+    constexpr int NW = DC_SETTLE_THREADS / 64;
+    __shared__ int wave_cnt[2][NW], wave_settled[NW];
     const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int na = n_a[p], nqt = (n_q[p] + 127) / 128;
+    const int na = n_a[p] < cap_a ? n_a[p] : cap_a, nqt = (n_q[p] + 127) / 128;
     const float line = dc_sure_line(a_err, q_err, p, cut0);
-    const int R = (cap_a + 255) / 256;
     uint8_t *cl = cls + (size_t)p * cap_a;
-    int mine = 0, settled = 0;
-    for (int i = 0; i < R; ++i) {
-        const int a = t * R + i;
-        if (a >= na || a >= cap_a) break;
-        const size_t arow = (size_t)p * cap_a + a;
-        if (a % stride == 0 && a / stride < MX6_SAMPLED_PANEL) { cl[a] = DC_COMPLETE; continue; }      // probe row: written by the probe
-        const int32_t *b = band + (p * T8 + (a >> 10)) * 2;
-        const bool all = b[0] == 0 && b[1] == nqt;
-        float m1, m2;
-        int sid;
+    // merged triple of row a over the band pass's splits, and whether its half's band is "all tiles" (its parent panel's then: a learned
+    // band is at most DC_BAND_CAP of the tiles)
+    auto fetch = [&](int a, float &m1, int &sid, float &m2, bool &all) {
+        if (a >= na) return;
+        const int32_t *b = band + ((size_t)p * T8 * 2 + (a >> 9)) * 2;
+        all = b[0] == 0 && b[1] == nqt;
         dc_merge(ws_m1, ws_i1, ws_m2, p, S, cap_a, a, m1, sid, m2);
-        uint8_t c;
-        if (all) c = DC_COMPLETE;
-        else if (m1 > line) { c = DC_SETTLED; m2 = INFINITY; ++settled; }       // no margin: a partial scan rules nothing out
-        else { c = DC_OPEN; ++mine; }
-        cl[a] = c;
-        if (c != DC_OPEN) { r_m1[arow] = m1; r_i1[arow] = sid; r_m2[arow] = m2; }
-    }
-    int incl = mine, sett = settled;
+    };
+    float m1 = 0.0f, m2 = 0.0f, m1_n = 0.0f, m2_n = 0.0f;
+    int sid = 0, sid_n = 0, base = 0, settled = 0;
+    bool all = false, all_n = false;
+    fetch(t, m1, sid, m2, all);
+    for (int a0 = 0, it = 0; a0 < na; a0 += DC_SETTLE_THREADS, ++it) {
+        const int a = a0 + t;
+        fetch(a + DC_SETTLE_THREADS, m1_n, sid_n, m2_n, all_n);
+        bool open = false, sett = false;
+        if (a < na) {
+            const size_t arow = (size_t)p * cap_a + a;
+            uint8_t c = DC_COMPLETE;
+            const bool probe = a % stride == 0 && a / stride < MX6_SAMPLED_PANEL;       // probe row: triple written by the probe
+            if (!probe) {
+                if (all) c = DC_COMPLETE;
+                else if (m1 > line) { c = DC_SETTLED; m2 = INFINITY; sett = true; }     // no margin: a partial scan rules nothing out
+                else { c = DC_OPEN; open = true; }
+                if (c != DC_OPEN) { r_m1[arow] = m1; r_i1[arow] = sid; r_m2[arow] = m2; }
+            }
+            cl[a] = c;
+        }
+        const unsigned long long open_lanes = __ballot(open);
+        settled += __popcll(__ballot(sett));
+        if (lane == 0) wave_cnt[it & 1][wave] = __popcll(open_lanes);
+        __syncthreads();                        // (two buffers: the writes of iteration it + 2 lie behind the barrier of it + 1)
+        int before = 0, tot = 0;
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-        sett += __shfl_xor(sett, off);
+        for (int w = 0; w < NW; ++w) {
+            const int c = wave_cnt[it & 1][w];
+            before += w < wave ? c : 0;
+            tot += c;
+        }
+        if (open) open_idx[(size_t)p * cap_a + base + before + __popcll(open_lanes & ((1ull << lane) - 1ull))] = a;
+        base += tot;
+        m1 = m1_n; sid = sid_n; m2 = m2_n; all = all_n;
     }
-    if (lane == 63) { wave_cnt[wave] = incl; wave_settled[wave] = sett; }
+    if (lane == 0) wave_settled[wave] = settled;
     __syncthreads();
-    int off0 = incl - mine;
-    for (int w = 0; w < wave; ++w) off0 += wave_cnt[w];
-    for (int i = 0; i < R; ++i) {
-        const int a = t * R + i;
-        if (a >= na || a >= cap_a) break;
-        if (cl[a] == DC_OPEN) open_idx[(size_t)p * cap_a + off0++] = a;
-    }
-    if (t == 255) {
-        n_open[p] = off0;
-        stats[p * 4 + 1] = wave_settled[0] + wave_settled[1] + wave_settled[2] + wave_settled[3];
-        stats[p * 4 + 2] = off0;
+    if (t == 0) {
+        int s = 0;
+        for (int w = 0; w < NW; ++w) s += wave_settled[w];
+        n_open[p] = base;
+        stats[p * 4 + 1] = s;
+        stats[p * 4 + 2] = base;
     }
 }
 
@@ -757,11 +791,11 @@ int dc_probe_stride(int cap_a)
     const int s = (cap_a + MX6_SAMPLED_PANEL - 1) / MX6_SAMPLED_PANEL;
     return s > want ? s : want;
 }
-// splits of the band pass (8-wave workgroups, one per CU: ~5 per CU) and of the open rows' scan (4-wave workgroups, two per CU)
+// splits of the band pass (4-wave workgroups over 512-row halves, two per CU: ~2.5 per place) and of the open rows' scan (the same kernel geometry)
 int dc_band_splits(int B, int cap_a)
 {
     static const int force = dev_env_int("ORYON_DC_BAND_SPLITS", 0);
-    const int u = B * mx6_panels_per_pair(cap_a), s = force > 0 ? force : (1280 + u - 1) / u;
+    const int u = B * 2 * mx6_panels_per_pair(cap_a), s = force > 0 ? force : (1280 + u - 1) / u;
     return s < 1 ? 1 : s > 16 ? 16 : s;
 }
 int dc_open_splits(int B)
@@ -782,7 +816,7 @@ size_t carve_dc(void *base, LazyWs &w, int B, int C, int cap_a)
     carve(w.dc_cls, rows);
     carve(w.dc_open_idx, rows);
     carve(w.dc_probe_idx, pairs * MX6_SAMPLED_PANEL);
-    carve(w.dc_band, pairs * mx6_panels_per_pair(cap_a) * 2);
+    carve(w.dc_band, pairs * mx6_panels_per_pair(cap_a) * 2 * 2);         // [first, count) per 512-row half of every 1024-row panel
     carve(w.dc_ws_m1, rows * S);
     carve(w.dc_ws_m2, rows * S);
     carve(w.dc_ws_i1, rows * S);
@@ -1060,17 +1094,17 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
             const int Sb = dc_band_splits(B, cap_a), So = dc_open_splits(B);
             static const int slack = dev_env_int("ORYON_DC_SLACK", DC_SLACK);
             static const int open_panel = dev_env_int("ORYON_DC_OPEN_PANEL", 0) == 1024 ? 1024 : MX6_SAMPLED_PANEL;
+            static const int sub_stats = dev_env_int("ORYON_DC_SUB_STATS", 0);     // stats[3] = the halves' widths (sweeps: the sub-bands' share)
             // (1) probe: every stride-th anchor, compacted into the second pass's panel, screened completely; triples and bands
             hipLaunchKernelGGL(match_dc_probe_list_kernel, dim3(B), dim3(256), 0, st, stride, m.n_a, w.dc_n_probe, w.dc_probe_idx);
             hipLaunchKernelGGL(match_compact_rows_kernel, dim3(MX6_SAMPLED_PANEL / 16, B), dim3(256), 0, st, a6, C, cap_a, MX6_SAMPLED_PANEL,
                                w.dc_n_probe, w.dc_probe_idx, MX6_SAMPLED_PANEL, w.cs_panel, MX6_SAMPLED_PANEL);
             launch_screen_mx6_sampled(st, w.cs_panel, q6, B, cap_q, w.dc_n_probe, m.n_q, csS, w.cs_max, w.cs_i1, w.cs_m2, m.C_true);
             hipLaunchKernelGGL(match_dc_probe_band_kernel, dim3(T8, B), dim3(256), 0, st, cap_a, T8, stride, csS, m.n_a, m.n_q, w.cs_max, w.cs_i1,
-                               w.cs_m2, m.a_scale, m.q_eps_max, cut0, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_band, w.dc_stats, slack);
-            // (2) band pass over all rows, (3) classes, merged triples, ordered list of the open rows
-            launch_screen_mx6(C, ((B * Sb + 7) / 8) * 8 * T, T, st, a6, q6, B, cap_a, cap_q, m.n_a, m.n_q, Sb, w.dc_ws_m1, w.dc_ws_i1, w.dc_ws_m2, m.C_true,
-                              1, nullptr, 0, w.dc_band);
-            hipLaunchKernelGGL(match_dc_settle_rows_kernel, dim3(B), dim3(256), 0, st, cap_a, T8, stride, Sb, m.n_a, m.n_q, w.dc_ws_m1, w.dc_ws_i1,
+                               w.cs_m2, m.a_scale, m.q_eps_max, cut0, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_band, w.dc_stats, slack, sub_stats);
+            // (2) band pass over all rows, each 512-row half in its own sub-band, (3) classes, merged triples, ordered list of the open rows
+            launch_screen_mx6_band512(st, a6, q6, B, cap_a, cap_q, m.n_a, m.n_q, Sb, w.dc_ws_m1, w.dc_ws_i1, w.dc_ws_m2, m.C_true, w.dc_band, 2 * T8);
+            hipLaunchKernelGGL(match_dc_settle_rows_kernel, dim3(B), dim3(DC_SETTLE_THREADS), 0, st, cap_a, T8, stride, Sb, m.n_a, m.n_q, w.dc_ws_m1, w.dc_ws_i1,
                                w.dc_ws_m2, m.a_scale, m.q_eps_max, cut0, w.dc_band, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_cls, w.dc_n_open, w.dc_open_idx,
                                w.dc_stats);
             // (4) complete scan of the open rows as dense 512-row panels (count-gated), triples scattered back

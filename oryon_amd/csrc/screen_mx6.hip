@@ -395,13 +395,15 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
 //              the SAMPLED anchors get the complete screen in a second pass over one 512-row panel per pair (match_corrs_lazy_impl).
 // The default route's cascade (round 10; match_corrs.hip, match_dc_*) uses a third placement:
 //   band     : every panel scans the tiles [first, first + count) its entry of `band` names - the range its probe rows' matches lie in,
-//              learned per pair and panel by match_dc_probe_band_kernel - dealt evenly to the S splits of the launch.
+//              learned per pair and 512-row panel by match_dc_probe_band_kernel - dealt evenly to the S splits of the launch.  This is
+//              the 4-wave instantiation (launch_screen_mx6_band512): two workgroups per CU, each with a band of its own.
 template <int CP, int WAVES, int KL = CP / 64>
 __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_screen_w4_win_kernel(
     const uint8_t *__restrict__ a6, const uint8_t *__restrict__ q6, int B, int cap_a, int cap_q, const int32_t *__restrict__ n_a,
     const int32_t *__restrict__ n_q, int T, int S, float *__restrict__ ws_max, int32_t *__restrict__ ws_i1, float *__restrict__ ws_m2,
     const int32_t *__restrict__ gate /* [B, T] or NULL: only panels with a non-zero entry run */, int win /* > 0: that many tiles of the split */,
-    const int32_t *__restrict__ band /* [B, T, 2] or NULL: the panel scans tiles [first, first + count), dealt evenly to the S splits */)
+    const int32_t *__restrict__ band /* [B, band_T, 2] or NULL: the panel scans tiles [first, first + count), dealt evenly to the S splits */,
+    int band_T /* entries of `band` per pair (>= T), indexed by this launch's panels */)
 {
     constexpr int TILE_BYTES = screen8_tile_bytes(CP);
     char *smem;
@@ -427,7 +429,7 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
     }
     if (band) {
         // default-route cascade: the band match_dc_probe_band_kernel learned for this panel from the probe rows' matches
-        const int first = band[(u.p * T + u.panel) * 2], cnt = band[(u.p * T + u.panel) * 2 + 1];
+        const int first = band[(u.p * band_T + u.panel) * 2], cnt = band[(u.p * band_T + u.panel) * 2 + 1];
         const int per = (cnt + S - 1) / S;
         qt_begin = first + u.split * per;
         qt_end = (qt_begin + per < first + cnt) ? qt_begin + per : first + cnt;
@@ -489,7 +491,7 @@ void mx6_with_kl(int kl, F &&f)
 template <int CP>
 void launch_screen_mx6_t(int groups, int T, hipStream_t st, const uint8_t *a6, const uint8_t *q6, int B, int cap_a, int cap_q, const int32_t *n_a,
                        const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int kl = 4, bool gate_or_win = false,
-                       const int32_t *gate = nullptr, int win = 0, const int32_t *band = nullptr)
+                       const int32_t *gate = nullptr, int win = 0)
 {
     // C_pad 256: 512-anchor panels (8 waves; `groups` was sized for 256-anchor panels, T of them per unit).  C_pad 512: the stationary
     // operand is 128 registers, so 4 waves per workgroup and one workgroup per CU (512 registers per wave), as the int8 kernel
@@ -512,10 +514,10 @@ void launch_screen_mx6_t(int groups, int T, hipStream_t st, const uint8_t *a6, c
             if (dbg && !dbg_wg) (void)hipMalloc(&dbg_wg, (size_t)65536 * 4 * sizeof(long long));
             if (dbg && dbg_wg && g8 <= 65536) (void)hipMemsetAsync(dbg_wg, 0, (size_t)g8 * 4 * sizeof(long long), st);
             if (gate_or_win) {
-                // the cascades' launches: a window (win > 0), the gated panels (gate != NULL) or a band (band != NULL) of the same loop
+                // the hard route's cascade launches: a window (win > 0) or the gated panels (gate != NULL) of the same loop
                 mx6_with_kl(kl, [&](auto KLC) {
                     hipLaunchKernelGGL((match_mx6_screen_w4_win_kernel<CP, 8, decltype(KLC)::value>), dim3(g8), dim3(512), 0, st, a6, q6, B, cap_a,
-                                       cap_q, n_a, n_q, T8, S, ws_max, ws_i1, ws_m2, gate, win, band);
+                                       cap_q, n_a, n_q, T8, S, ws_max, ws_i1, ws_m2, gate, win, static_cast<const int32_t *>(nullptr), 0);
                 });
                 return;
             }
@@ -555,12 +557,12 @@ const char *screen_mx6_name(int C)
 
 void launch_screen_mx6(int C, int groups, int T, hipStream_t st, const uint8_t *a6, const uint8_t *q6, int B, int cap_a, int cap_q,
                        const int32_t *n_a, const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true,
-                       int cascade, const int32_t *gate, int win, const int32_t *band)
+                       int cascade, const int32_t *gate, int win)
 {
-    // cascade != 0 (C_pad 256 only): the windowed / gated / banded launches of the validity cascades (match_mx6_screen_w4_win_kernel)
+    // cascade != 0 (C_pad 256 only): the windowed / gated launches of the hard route's validity cascade (match_mx6_screen_w4_win_kernel)
     if (C == 256)
         launch_screen_mx6_t<256>(groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, ws_max, ws_i1, ws_m2, mx6_live_ksteps(C_true), cascade != 0,
-                                 gate, win, band);
+                                 gate, win);
     else launch_screen_mx6_t<512>(groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, ws_max, ws_i1, ws_m2);
 }
 
@@ -575,6 +577,20 @@ void launch_screen_mx6_rows512(hipStream_t st, const uint8_t *a6_rows, const uin
     mx6_with_kl(mx6_live_ksteps(C_true), [&](auto KLC) {
         hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4, decltype(KLC)::value>), dim3(groups), dim3(256), 0, st, a6_rows, q6, B, cap_rows, cap_q,
                            n_rows, n_q, T, S, ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
+    });
+}
+
+// Band pass of the default route's cascade: the same 512-row panels over the anchors in place, every panel over the tiles its entry of
+// `band` names (match_dc_probe_band_kernel: one sub-band per 512-row half of a 1024-row panel, band_T entries per pair).  A band is
+// ~13 tiles at cfg2, so a workgroup's stationary operand (128 KB) is a large part of what it moves: few splits (dc_band_splits).
+void launch_screen_mx6_band512(hipStream_t st, const uint8_t *a6, const uint8_t *q6, int B, int cap_a, int cap_q, const int32_t *n_a,
+                               const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true, const int32_t *band, int band_T)
+{
+    const int T = (cap_a + 511) / 512;
+    const int groups = ((B * S + 7) / 8) * 8 * T;
+    mx6_with_kl(mx6_live_ksteps(C_true), [&](auto KLC) {
+        hipLaunchKernelGGL((match_mx6_screen_w4_win_kernel<256, 4, decltype(KLC)::value>), dim3(groups), dim3(256), 0, st, a6, q6, B, cap_a, cap_q,
+                           n_a, n_q, T, S, ws_max, ws_i1, ws_m2, static_cast<const int32_t *>(nullptr), 0, band, band_T);
     });
 }
 
