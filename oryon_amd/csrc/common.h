@@ -83,6 +83,41 @@ __host__ __device__ static inline uint32_t rng_u32(uint64_t seed, uint64_t key, 
     return (uint32_t)(mix64(mix64(seed ^ (key * 0xD1B54A32D192ED03ull)) + ((uint64_t)stream << 32 | i)) >> 32);
 }
 
+// The bin walk of a radix select over a 256-bin histogram, by ONE complete wave (all 64 lanes call it, after the barrier that closes the
+// histogram): the first bin b with hist[0] + .. + hist[b] >= remaining, and `below` = hist[0] + .. + hist[b - 1].  What the serial walk
+//     for (b = 0; b < 256; ++b) { if (cum + hist[b] >= remaining) break; cum += hist[b]; }
+// leaves in (b, cum) for every histogram - b = 256 and the whole sum where no bin gets there.  Four bins per lane, a wave prefix sum of
+// the lanes' totals, a ballot for the first lane whose inclusive sum reaches `remaining`, and that lane's four bins walked in order.
+// Every lane returns the same pair.  hist must be 16-byte aligned.
+#ifdef __HIPCC__
+__device__ __forceinline__ int radix_pick(const unsigned *hist, unsigned remaining, unsigned &below)
+{
+    const int lane = threadIdx.x & 63;
+    const uint4 h = *reinterpret_cast<const uint4 *>(hist + lane * 4);
+    const unsigned tot = h.x + h.y + h.z + h.w;
+    unsigned incl = tot;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = __shfl_up(incl, o);
+        incl += (lane >= o) ? v : 0u;
+    }
+    const unsigned long long reach = __ballot(incl >= remaining);
+    if (reach == 0ull) {                                   // no bin gets there: the walk runs off the end with the whole sum
+        below = __shfl(incl, 63);
+        return 256;
+    }
+    const int src = __ffsll(reach) - 1;
+    unsigned cum = incl - tot;
+    int j = 3;
+    if (cum + h.x >= remaining) j = 0;
+    else if ((cum += h.x) + h.y >= remaining) j = 1;
+    else if ((cum += h.y) + h.z >= remaining) j = 2;
+    else cum += h.z;                                       // lane `src` reaches it in its last bin at the latest
+    below = __shfl(cum, src);
+    return src * 4 + __shfl(j, src);
+}
+#endif
+
 // Raise a kernel's dynamic-LDS limit once per (kernel, device): thread-safe, and right when one process drives several GPUs
 // (the attribute belongs to the device's copy of the function).
 inline void allow_dynamic_lds(const void *kernel, int bytes)

@@ -746,9 +746,10 @@ void launch_g8(hipStream_t st, const float *feat, int n_maps, int C, int HW, con
     const int chunk_tiles = (T + chunks_per_map - 1) / chunks_per_map;
     const int units = n_maps * chunks_per_map;
     const int groups = ((units + 7) / 8) * 8 * chunk_tiles;
-    // (the hi / lo pass of K1x3 stays one tile per block: it does real work on every step of smooth inputs and the tile loop costs it 20 %:
-    // 1.53 against 1.27 ms; the fp32-row passes are rare fall-backs)
-    if (map_enable && FMT != 2 && FMT != 3) {
+    // (the hi / lo rows of a step that expects the second level for every pair come from K0's own pass, FMT 3, one tile per block: the
+    // tile loop cost that pass 20 %, 1.53 against 1.27 ms.  The gated FMT 2 pass of match_x3_resolve is what is left for the steps that
+    // do not expect it - a few pairs at most, usually none: ~50 k workgroups that only exit; the fp32-row passes are rare fall-backs)
+    if (map_enable && FMT != 3) {
         auto gk = gather_q8_v3_gated_kernel<CP, LPR, NHWC, FMT>;
         allow_dynamic_lds(reinterpret_cast<const void *>(gk), 4 * G8_STAGE_BYTES);
         const int grid = groups < 2048 ? groups : 2048;

@@ -22,17 +22,15 @@ namespace oryon {
 // fp32 scan (K1) on a compacted list of just those anchor rows against the pair's materialised fp32 query rows.
 constexpr uint8_t LZ_INVALID = 0, LZ_VALID = 1, LZ_UNCERTAIN = 2, LZ_AMB_VALID = 3, LZ_RESOLVED = 4, LZ_AMB_UNCERTAIN = 5;
 
-// one THREAD per anchor: merge the per-split (m1, slice, m2) triples and classify
-__global__ __launch_bounds__(256) void match_decide_lite_kernel(
-    int cap_a, const int32_t *__restrict__ n_a, int S, const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
+// one anchor row: merge the per-split (m1, slice, m2) triples and classify; -> the row is ambiguous (lazy route only)
+__device__ __forceinline__ bool decide_lite_row(
+    int cap_a, int p, int a, int S, const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
     const float *__restrict__ ws_m2, const float *__restrict__ a_scale8, const float *__restrict__ eps_q8, float cut0, float sqrt_c,
     float c_true, int force_eager, int fmt, int x3, float *__restrict__ m_final, int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
     uint8_t *__restrict__ state, uint8_t *__restrict__ valid, float *__restrict__ min_dist, int32_t *__restrict__ argmin,
     int32_t *__restrict__ pair_eager, int32_t *__restrict__ n_unc, int32_t *__restrict__ unc_idx, int32_t *__restrict__ n_ambu,
-    int32_t *__restrict__ ambu_idx, int32_t *__restrict__ need_f32_lazy, int32_t *__restrict__ n_amb_total)
+    int32_t *__restrict__ ambu_idx, int32_t *__restrict__ need_f32_lazy)
 {
-    const int p = blockIdx.y, a = blockIdx.x * 256 + threadIdx.x;
-    if (a >= n_a[p]) return;
     const size_t arow = (size_t)p * cap_a + a;
     float m1 = -INFINITY, m2 = -INFINITY;
     int sid = 0;
@@ -71,15 +69,49 @@ __global__ __launch_bounds__(256) void match_decide_lite_kernel(
     min_dist[arow] = __fmaf_rn(-0.5f, m1, 0.5f);
     argmin[arow] = 0;
     valid[arow] = (st == LZ_VALID || st == LZ_AMB_VALID) ? 1 : 0;
-    if (force_eager) { pair_eager[p] = 1; return; }
+    if (force_eager) { pair_eager[p] = 1; return false; }
     if (st == LZ_UNCERTAIN) unc_idx[(size_t)p * cap_a + atomicAdd(&n_unc[p], 1)] = a;
     if (st == LZ_AMB_UNCERTAIN) ambu_idx[(size_t)p * cap_a + atomicAdd(&n_ambu[p], 1)] = a;
     if (st == LZ_AMB_VALID || st == LZ_AMB_UNCERTAIN) {
         // this pair's fp32 query rows get materialised (device-gated launch) - with the fp16x3 second level (x3) only when an
         // ambiguous anchor's VALIDITY is open too: the sampled valid ones are then resolved from hi / lo half rows made later
         if (st == LZ_AMB_UNCERTAIN || !x3) need_f32_lazy[p] = 1;
-        atomicAdd(&n_amb_total[p], 1);      // (the compiler already issues one add per wave: a ballot count written by hand measured no faster)
+        return true;
     }
+    return false;
+}
+
+// one THREAD per anchor.  n_amb_part [B, gridDim.x]: every workgroup's count of ambiguous rows, one plain store each (zero for a
+// workgroup past n_a), summed by the two readers.  One add per wave on a word per pair - ~80 adds on one address, since round 10 made
+// most rows ambiguous-valid - was 26 of this kernel's 32 us at 64 x 5000 rows (round 13: 31.9 us with the add, 5.9 us with it compiled
+// out).  n_unc / n_ambu keep their returning adds: they index lists, and such rows are rare
+__global__ __launch_bounds__(256) void match_decide_lite_kernel(
+    int cap_a, const int32_t *__restrict__ n_a, int S, const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
+    const float *__restrict__ ws_m2, const float *__restrict__ a_scale8, const float *__restrict__ eps_q8, float cut0, float sqrt_c,
+    float c_true, int force_eager, int fmt, int x3, float *__restrict__ m_final, int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
+    uint8_t *__restrict__ state, uint8_t *__restrict__ valid, float *__restrict__ min_dist, int32_t *__restrict__ argmin,
+    int32_t *__restrict__ pair_eager, int32_t *__restrict__ n_unc, int32_t *__restrict__ unc_idx, int32_t *__restrict__ n_ambu,
+    int32_t *__restrict__ ambu_idx, int32_t *__restrict__ need_f32_lazy, int32_t *__restrict__ n_amb_part)
+{
+    __shared__ int s_amb[4];
+    const int p = blockIdx.y, a = blockIdx.x * 256 + threadIdx.x;
+    bool amb = false;
+    if (a < n_a[p])
+        amb = decide_lite_row(cap_a, p, a, S, ws_m1, ws_i1, ws_m2, a_scale8, eps_q8, cut0, sqrt_c, c_true, force_eager, fmt, x3, m_final, sid_final,
+                              margin_out, state, valid, min_dist, argmin, pair_eager, n_unc, unc_idx, n_ambu, ambu_idx, need_f32_lazy);
+    if (force_eager) return;                                    // (the eager route reads no such count)
+    const unsigned long long amb_lanes = __ballot(amb);
+    if ((threadIdx.x & 63) == 0) s_amb[threadIdx.x >> 6] = __popcll(amb_lanes);
+    __syncthreads();
+    if (threadIdx.x == 0) n_amb_part[(size_t)p * gridDim.x + blockIdx.x] = s_amb[0] + s_amb[1] + s_amb[2] + s_amb[3];
+}
+
+// sum of a pair's parts (match_decide_lite_kernel)
+__device__ __forceinline__ int amb_total(const int32_t *__restrict__ n_amb_part, int n_parts, int p)
+{
+    int tot = 0;
+    for (int i = 0; i < n_parts; ++i) tot += n_amb_part[(size_t)p * n_parts + i];
+    return tot;
 }
 
 __global__ void match_mask_counts_kernel(int B, const int32_t *__restrict__ n_a, const int32_t *__restrict__ pair_eager,
@@ -91,19 +123,20 @@ __global__ void match_mask_counts_kernel(int B, const int32_t *__restrict__ n_a,
     n_a_lazy[p] = pair_eager[p] ? 0 : n_a[p];
 }
 
-__global__ void match_cascade_counts_kernel(int B, const int32_t *__restrict__ n_amb_total, const int32_t *__restrict__ n_after,
+__global__ void match_cascade_counts_kernel(int B, const int32_t *__restrict__ n_amb_part, int n_parts, const int32_t *__restrict__ n_after,
                                             const int32_t *__restrict__ n_before, int32_t *__restrict__ out)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= B) return;
-    const long long tot = n_amb_total[p], nb = n_before[p], na = n_after[p];
+    const long long tot = amb_total(n_amb_part, n_parts, p), nb = n_before[p], na = n_after[p];
     out[p] = nb > 0 ? (int32_t)(tot * na / nb) : (int32_t)tot;
 }
 
-__global__ void match_sum_counts_kernel(int B, const int32_t *__restrict__ a, const int32_t *__restrict__ b, int32_t *__restrict__ out)
+__global__ void match_sum_counts_kernel(int B, const int32_t *__restrict__ a, const int32_t *__restrict__ n_amb_part, int n_parts,
+                                        int32_t *__restrict__ out)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < B) out[p] = a[p] + b[p];
+    if (p < B) out[p] = a[p] + amb_total(n_amb_part, n_parts, p);
 }
 
 // fp32 anchor rows of a work list -> dense panels for the exact scan (rows [count, round_up(count, 128)) zero-filled)
@@ -231,20 +264,26 @@ __global__ __launch_bounds__(256) void match_panel_settle_kernel(int cap_a, int 
 
 __global__ __launch_bounds__(256) void match_compact_rows_kernel(const uint8_t *__restrict__ rows, int row_bytes, int cap_a, int cap_c,
                                                                   const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
-                                                                  int idx_stride, uint8_t *__restrict__ out, int fill_mult)
+                                                                  int idx_stride, uint8_t *__restrict__ out, int fill_mult,
+                                                                  int32_t *__restrict__ n_out)
 {
     // 16 lanes per 256-byte row (uint4 each); rows [count, round_up(count, fill_mult)) - the rest of the last panel a screen launch
-    // reads - are zero rows (exponent byte 0: finite scores nobody reads)
+    // reads - are zero rows (exponent byte 0: finite scores nobody reads).
+    // idx == nullptr: the list is "every idx_stride-th row of the pair's count[p] rows" (the default-route cascade's probe: rows 0,
+    // stride, 2 stride, .. - a shape-only pattern, <= cap_c of them), and n_out[p] receives its length for the screen launch behind
     const int p = blockIdx.y, sl = blockIdx.x * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
     if (sl >= cap_c) return;
-    const int n = count[p] < cap_c ? count[p] : cap_c;
+    const int listed = idx ? count[p] : (count[p] + idx_stride - 1) / idx_stride;
+    const int n = listed < cap_c ? listed : cap_c;
+    if (!idx && blockIdx.x == 0 && threadIdx.x == 0) n_out[p] = n;
     if (sl >= (n + fill_mult - 1) / fill_mult * fill_mult) return;
     uint4 *d = reinterpret_cast<uint4 *>(out + ((size_t)p * cap_c + sl) * row_bytes);
     if (sl >= n) {
         for (int i = l; i < row_bytes / 16; i += 16) d[i] = make_uint4(0, 0, 0, 0);
         return;
     }
-    const uint4 *src = reinterpret_cast<const uint4 *>(rows + ((size_t)p * cap_a + idx[(size_t)p * idx_stride + sl]) * row_bytes);
+    const int row = idx ? idx[(size_t)p * idx_stride + sl] : sl * idx_stride;
+    const uint4 *src = reinterpret_cast<const uint4 *>(rows + ((size_t)p * cap_a + row) * row_bytes);
     for (int i = l; i < row_bytes / 16; i += 16) d[i] = src[i];
 }
 
@@ -324,16 +363,7 @@ __device__ __forceinline__ void dc_merge(const float *__restrict__ ws_m1, const 
     }
 }
 
-// the probe: rows 0, stride, 2 stride, .. of every pair (a shape-only pattern; <= MX6_SAMPLED_PANEL of them: stride >= cap_a / 512)
-__global__ __launch_bounds__(256) void match_dc_probe_list_kernel(int stride, const int32_t *__restrict__ n_a, int32_t *__restrict__ n_probe,
-                                                                   int32_t *__restrict__ probe_idx)
-{
-    const int p = blockIdx.x;
-    int n = (n_a[p] + stride - 1) / stride;
-    n = n < MX6_SAMPLED_PANEL ? n : MX6_SAMPLED_PANEL;
-    for (int k = threadIdx.x; k < n; k += 256) probe_idx[(size_t)p * MX6_SAMPLED_PANEL + k] = k * stride;
-    if (threadIdx.x == 0) n_probe[p] = n;
-}
+// (the probe - rows 0, stride, 2 stride, .. of every pair - has no list: match_compact_rows_kernel's stride mode forms it and its count)
 
 // one workgroup per (1024-row panel, pair): the panel's probe rows get their complete triples, the panel its band [first, count) and
 // each of its two 512-row halves a sub-band inside it: band[p][2 panel + h] (what the band pass scans and the settle pass looks up).
@@ -746,7 +776,9 @@ namespace {
 struct LazyWs : Screen8RawWs {
     float *margin;
     int32_t *sid_final, *pair_eager, *n_unc, *unc_idx, *n_a_eager, *n_a_lazy, *sel_rows, *scratch;
-    int32_t *n_ambu, *ambu_idx, *n_ambv, *ambv_idx, *need_f32_lazy, *n_amb_total, *mark;
+    int32_t *n_ambu, *ambu_idx, *n_ambv, *ambv_idx, *need_f32_lazy, *n_amb_room, *mark;
+    int32_t *n_amb_part;                // [B, cap_a / 256] ambiguous rows per workgroup of match_decide_lite_kernel: ScreenWs' panel_flag
+                                        // ([B, cap_a / 128], zeroed every call), which only the eager route's exact recomputation uses
     void *exact_ws;
     size_t exact_ws_bytes;
     // K1x3 (C_pad 256): hi / lo anchor rows, the overflow fall-back's compact rows and outputs, candidate lists
@@ -768,10 +800,11 @@ struct LazyWs : Screen8RawWs {
     bool dc_ok;                         // false where the shape has no such cascade (or q16 is too small for its buffers)
     uint8_t *dc_rows;
     float *dc_m1, *dc_m2, *dc_ws_m1, *dc_ws_m2;
-    int32_t *dc_i1, *dc_ws_i1, *dc_probe_idx, *dc_open_idx, *dc_band, *dc_n_probe, *dc_n_open, *dc_stats;
+    int32_t *dc_i1, *dc_ws_i1, *dc_probe_room, *dc_open_idx, *dc_band, *dc_n_probe, *dc_n_open, *dc_stats;
     uint8_t *dc_cls;
-    size_t dc_zero_bytes;               // from dc_n_probe on
-    size_t lazy_zero_off, lazy_zero_bytes;      // the second zeroed region (ScreenWs has the first)
+    size_t dc_zero_bytes;               // the counters, at the start of q16
+    size_t lazy_zero_off, lazy_zero_bytes;      // the second zeroed region (ScreenWs has the first) ..
+    size_t x3_zero_bytes;                       // .. which the head of x3_scratch continues when the second level is K1x3
 };
 
 // list capacity of the second level: distinct sampled rows <= min(max_corrs, n_a)
@@ -809,22 +842,22 @@ size_t carve_dc(void *base, LazyWs &w, int B, int C, int cap_a)
     Carver carve(base);
     const size_t rows = (size_t)B * cap_a, pairs = (size_t)B;
     const size_t S = 16;                                    // the most either pass uses (dc_band_splits, dc_open_splits)
+    // the counters first: q16 begins where ScreenWs' zeroed region ends, so one fill clears both (match_corrs_lazy_impl)
+    carve(w.dc_n_probe, pairs);
+    carve(w.dc_n_open, pairs);
+    carve(w.dc_stats, pairs * 4);
+    w.dc_zero_bytes = carve.off;
     carve(w.dc_rows, rows * C);
     carve(w.dc_m1, rows);
     carve(w.dc_m2, rows);
     carve(w.dc_i1, rows);
     carve(w.dc_cls, rows);
     carve(w.dc_open_idx, rows);
-    carve(w.dc_probe_idx, pairs * MX6_SAMPLED_PANEL);
+    carve(w.dc_probe_room, pairs * MX6_SAMPLED_PANEL);                    // (the probe's index list until round 13: the shape gate's sum stays)
     carve(w.dc_band, pairs * mx6_panels_per_pair(cap_a) * 2 * 2);         // [first, count) per 512-row half of every 1024-row panel
     carve(w.dc_ws_m1, rows * S);
     carve(w.dc_ws_m2, rows * S);
     carve(w.dc_ws_i1, rows * S);
-    const size_t zero_off = carve.off;
-    carve(w.dc_n_probe, pairs);
-    carve(w.dc_n_open, pairs);
-    carve(w.dc_stats, pairs * 4);
-    w.dc_zero_bytes = carve.off - zero_off;
     return carve.off;
 }
 
@@ -852,7 +885,6 @@ size_t carve_lazy(void *base, LazyWs &w, int B, int C, int cap_a, int cap_q, int
     carve(w.x3_md_o, pairs * cap_s);
     carve(w.x3_am_o, pairs * cap_s);
     carve(w.x3_va_o, pairs * cap_s);
-    carve(w.x3_scratch, match_x3_scratch_bytes(B, (int)cap_s, 8, cap_q));
     const bool cascade = C == 256 && corr_rows <= MX6_SAMPLED_PANEL;
     const size_t triples = cascade ? pairs * mx6_sampled_splits(B) * MX6_SAMPLED_PANEL : 4;      // 16-byte placeholders without it
     carve(w.cs_panel, cascade ? pairs * MX6_SAMPLED_PANEL * C : 16);
@@ -877,9 +909,13 @@ size_t carve_lazy(void *base, LazyWs &w, int B, int C, int cap_a, int cap_q, int
     carve(w.n_ambu, pairs);
     carve(w.n_ambv, pairs);
     carve(w.need_f32_lazy, pairs);
-    carve(w.n_amb_total, pairs);
+    carve(w.n_amb_room, pairs);                                            // (the per-pair count until round 13: the size is pinned)
+    w.n_amb_part = w.panel_flag;
     carve(w.mark, rows);
     w.lazy_zero_bytes = carve.off - w.lazy_zero_off;
+    // the second level's scratch last: what it needs zeroed is at its start (match_x3_zero_bytes), i.e. right behind `mark` - one fill
+    w.x3_zero_bytes = match_x3_zero_bytes(B, (int)cap_s, 8);
+    carve(w.x3_scratch, match_x3_scratch_bytes(B, (int)cap_s, 8, cap_q));
     return carve.off;
 }
 }  // namespace
@@ -971,7 +1007,8 @@ int lazy_route(const MatchCorrsArgs &m, const LazyWs &w, hipStream_t st, int use
         // second pass: the complete screen for the listed rows (one 512-row panel per pair), triples merged back, list rebuilt
         const int csS = mx6_sampled_splits(B);
         hipLaunchKernelGGL(match_compact_rows_kernel, dim3(MX6_SAMPLED_PANEL / 16, B), dim3(256), 0, st, reinterpret_cast<const uint8_t *>(m.a_i8),
-                           C, cap_a, MX6_SAMPLED_PANEL, w.n_ambv, w.ambv_idx, corr_rows, w.cs_panel, MX6_SAMPLED_PANEL);
+                           C, cap_a, MX6_SAMPLED_PANEL, w.n_ambv, w.ambv_idx, corr_rows, w.cs_panel, MX6_SAMPLED_PANEL,
+                           static_cast<int32_t *>(nullptr));
         launch_screen_mx6_sampled(st, w.cs_panel, reinterpret_cast<const uint8_t *>(m.q_i8), B, cap_q, w.n_ambv, m.n_q, csS, w.cs_max, w.cs_i1,
                                   w.cs_m2, m.C_true);
         hipLaunchKernelGGL(match_decide_sampled_kernel, dim3((MX6_SAMPLED_PANEL + 255) / 256, B), dim3(256), 0, st, cap_a, MX6_SAMPLED_PANEL, csS,
@@ -1022,12 +1059,13 @@ int lazy_route(const MatchCorrsArgs &m, const LazyWs &w, hipStream_t st, int use
     if (m.n_undecided && cascade) {
         // cascade: the first pass calls every anchor of a panel that stopped early "ambiguous"; the feedback the engine steers by is that
         // count scaled by the share of the SAMPLED ambiguous rows which the complete second pass left ambiguous
-        hipLaunchKernelGGL(match_cascade_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, w.n_amb_total, w.n_ambv, w.n_ambv0,
+        hipLaunchKernelGGL(match_cascade_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, w.n_amb_part, cap_a / 256, w.n_ambv, w.n_ambv0,
                            m.n_undecided);
         if ((rc = check_launch(IMPL))) return rc;
     } else if (m.n_undecided) {
         // anchors the int8 stage could not fully decide: the fp16-stage anchors of eager pairs + the ambiguous anchors of lazy pairs
-        hipLaunchKernelGGL(match_sum_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, w.n_amb, w.n_amb_total, m.n_undecided);
+        hipLaunchKernelGGL(match_sum_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, w.n_amb, w.n_amb_part, cap_a / 256,
+                           m.n_undecided);
         if ((rc = check_launch(IMPL))) return rc;
     }
     return ORYON_OK;
@@ -1058,16 +1096,17 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
         return ORYON_ERR_WORKSPACE;
     }
     hipStream_t st = as_stream(m.stream);
-    ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(m.workspace) + w.zero_off, 0, w.zero_bytes, st));
-    if (m.force_eager) ORYON_CHECK_HIP(hipMemsetAsync(w.need_f32, 0, (size_t)B * sizeof(int32_t), st));     // only the eager route reads it
-    ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(m.workspace) + w.lazy_zero_off, 0, w.lazy_zero_bytes, st));
-    if (w.dc_ok && m.fmt == 1) ORYON_CHECK_HIP(hipMemsetAsync(w.dc_n_probe, 0, w.dc_zero_bytes, st));     // the cascade's counters read zero after any other route
     const float cut0 = 1.0f - 2.0f * m.threshold;
     // second level for the sampled anchors no screen can separate: fp16x3 two-sweep scan (K1x3, match_x3.hip; C_pad 256) instead of the
     // exact fp32 scan - same results, hard-descriptor step 9.8 -> 8.5 ms; ~30 us of empty launches per step when no anchor needs it.
     // ORYON_AMB_X3=0 keeps the exact scan (the tests run both settings).
     static const bool x3_env = dev_env_int("ORYON_AMB_X3", 1) != 0;
     const int use_x3 = (x3_env && C == 256 && !m.force_eager) ? 1 : 0;
+    // Two fills per call.  ScreenWs' zeroed region runs on into the cascade's counters at the start of q16 (carve_dc; on fmt 1 they read
+    // zero after any other route), the lazy tail's into what match_x3_resolve wants zeroed at the head of its scratch (carve_lazy)
+    ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(m.workspace) + w.zero_off, 0, w.zero_bytes + (w.dc_ok && m.fmt == 1 ? w.dc_zero_bytes : 0), st));
+    if (m.force_eager) ORYON_CHECK_HIP(hipMemsetAsync(w.need_f32, 0, (size_t)B * sizeof(int32_t), st));     // only the eager route reads it
+    ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(m.workspace) + w.lazy_zero_off, 0, w.lazy_zero_bytes + (use_x3 ? w.x3_zero_bytes : 0), st));
     // validity cascade (round 6): on the route the engine takes once its feedback says "hard" (q_hi_lo given: K0 wrote the hi / lo rows),
     // the screen stops a panel whose anchors are all valid for sure, and a second, complete pass serves the sampled anchors only
     static const bool cascade_env = dev_env_int("ORYON_CASCADE", 1) != 0;
@@ -1096,9 +1135,9 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
             static const int open_panel = dev_env_int("ORYON_DC_OPEN_PANEL", 0) == 1024 ? 1024 : MX6_SAMPLED_PANEL;
             static const int sub_stats = dev_env_int("ORYON_DC_SUB_STATS", 0);     // stats[3] = the halves' widths (sweeps: the sub-bands' share)
             // (1) probe: every stride-th anchor, compacted into the second pass's panel, screened completely; triples and bands
-            hipLaunchKernelGGL(match_dc_probe_list_kernel, dim3(B), dim3(256), 0, st, stride, m.n_a, w.dc_n_probe, w.dc_probe_idx);
+            //     (rows 0, stride, 2 stride, ..: <= MX6_SAMPLED_PANEL of them, stride >= cap_a / 512; the compaction writes dc_n_probe)
             hipLaunchKernelGGL(match_compact_rows_kernel, dim3(MX6_SAMPLED_PANEL / 16, B), dim3(256), 0, st, a6, C, cap_a, MX6_SAMPLED_PANEL,
-                               w.dc_n_probe, w.dc_probe_idx, MX6_SAMPLED_PANEL, w.cs_panel, MX6_SAMPLED_PANEL);
+                               m.n_a, static_cast<const int32_t *>(nullptr), stride, w.cs_panel, MX6_SAMPLED_PANEL, w.dc_n_probe);
             launch_screen_mx6_sampled(st, w.cs_panel, q6, B, cap_q, w.dc_n_probe, m.n_q, csS, w.cs_max, w.cs_i1, w.cs_m2, m.C_true);
             hipLaunchKernelGGL(match_dc_probe_band_kernel, dim3(T8, B), dim3(256), 0, st, cap_a, T8, stride, csS, m.n_a, m.n_q, w.cs_max, w.cs_i1,
                                w.cs_m2, m.a_scale, m.q_eps_max, cut0, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_band, w.dc_stats, slack, sub_stats);
@@ -1109,7 +1148,7 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
                                w.dc_stats);
             // (4) complete scan of the open rows as dense 512-row panels (count-gated), triples scattered back
             hipLaunchKernelGGL(match_compact_rows_kernel, dim3(cap_a / 16, B), dim3(256), 0, st, a6, C, cap_a, cap_a, w.dc_n_open, w.dc_open_idx,
-                               cap_a, w.dc_rows, open_panel);
+                               cap_a, w.dc_rows, open_panel, static_cast<int32_t *>(nullptr));
             if (open_panel == 1024)     // the sweep's alternative (dev build): the 8-wave kernel over 1024-row panels of the compacted rows
                 launch_screen_mx6(C, ((B * So + 7) / 8) * 8 * T, T, st, w.dc_rows, q6, B, cap_a, cap_q, w.dc_n_open, m.n_q, So, w.dc_ws_m1, w.dc_ws_i1,
                                   w.dc_ws_m2, m.C_true);
@@ -1130,8 +1169,9 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
     hipLaunchKernelGGL(match_decide_lite_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, m.n_a, S_dec, dec_m1, dec_i1, dec_m2, m.a_scale,
                        m.q_eps_max, cut0, sqrtf((float)m.C_true), (float)m.C_true, m.force_eager, m.fmt, use_x3, w.m_final, w.sid_final, w.margin,
                        w.state, m.valid, m.min_dist, m.argmin, w.pair_eager, w.n_unc, w.unc_idx, w.n_ambu, w.ambu_idx, w.need_f32_lazy,
-                       w.n_amb_total);
-    hipLaunchKernelGGL(match_mask_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, m.n_a, w.pair_eager, w.n_a_eager, w.n_a_lazy);
+                       w.n_amb_part);
+    if (m.force_eager)      // n_a_eager / n_a_lazy: read by eager_route alone
+        hipLaunchKernelGGL(match_mask_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, m.n_a, w.pair_eager, w.n_a_eager, w.n_a_lazy);
     ORYON_CHECK_LAUNCH();
     if (!m.force_eager) return lazy_route(m, w, st, use_x3, cascade || dc, dc);
     const int rc = eager_route(m, w, S);

@@ -506,6 +506,8 @@ __global__ __launch_bounds__(256, 1) void match_x3_sweep2_kernel(const __half *_
     const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
     if constexpr (!NARROW) kc = CP / 64;                        // every chunk is live: the compiler sees a constant
     const int n_jobs = __atomic_load_n(njobs, __ATOMIC_RELAXED);
+    // nothing posted (the usual step): leave without a pull - the 1024 waves' returning adds on next_job were most of the empty launch
+    if (n_jobs <= 0 && !dbg) return;
     // DMA source: lane L of instruction j lands at LDS (row j*8 + L/8, 16-byte slot L%8); slots are XOR-swizzled with (row >> 1) & 7 so
     // that the 16 lanes of a ds_read_b128 phase (rows r .. r+15 at one logical slot) cover all 64 banks
     unsigned src2[NJ];
@@ -835,6 +837,13 @@ size_t match_x3_scratch_bytes(int B, int cap_s, int S, int cap_q)
            owners * x3_jobs_per_owner(cap_q, S) * sizeof(uint2) /* jobs */ + 1024;
 }
 
+// what match_x3_resolve needs zeroed at the head of its scratch before every call: cnt | n_ovf | ql_max | queue
+size_t match_x3_zero_bytes(int B, int cap_s, int S)
+{
+    const size_t cnt_block = ((size_t)B * sizeof(int32_t) + 255) / 256 * 256;
+    return ((size_t)B * S * cap_s * 2 * sizeof(int32_t) + 255) / 256 * 256 + 2 * cnt_block + 256;
+}
+
 // a_c [B, cap_s, 256] fp32 compact anchor rows (k-permuted), n_c [B] -> md_c / am_c / va_c [B, cap_s]; n_ovf / ovf_idx: anchors whose
 // lists overflowed (to be redone by the exact scan).  qh / ql: room for [B, cap_q, 256] halves each; ah / al: [B, cap_s, 256] halves;
 // scratch: match_x3_scratch_bytes.  Every launch is gated on the device by n_c.
@@ -851,18 +860,20 @@ int match_x3_resolve(const float *a_c, const int32_t *n_c, int cap_s, const floa
     const int G = T * x3_waves;                                  // 64-anchor groups per (pair, split)
     const int S = 8;
     char *sp = static_cast<char *>(scratch);
+    // cnt | n_ovf | ql_max | queue: the head of the scratch, match_x3_zero_bytes of it - zeroed by the CALLER's fill before this call
+    // (sweep 2 appends to cnt with atomics)
     int32_t *cnt = reinterpret_cast<int32_t *>(sp);
     size_t off = ((size_t)B * S * cap_s * 2 * sizeof(int32_t) + 255) / 256 * 256;
-    uint2 *cand = reinterpret_cast<uint2 *>(sp + off);
-    off += ((size_t)B * S * cap_s * 2 * X3_CAPH * sizeof(uint2) + 255) / 256 * 256;
-    int32_t *n_ovf = reinterpret_cast<int32_t *>(sp + off);             // n_ovf | ql_max: adjacent, zeroed by ONE memset
+    int32_t *n_ovf = reinterpret_cast<int32_t *>(sp + off);
     const size_t cnt_block = ((size_t)B * sizeof(int32_t) + 255) / 256 * 256;
     off += cnt_block;
     float *ql_max = reinterpret_cast<float *>(sp + off);
     off += cnt_block;
     int32_t *queue = reinterpret_cast<int32_t *>(sp + off);            // sweep 1's per-XCD item counters [0..7], njobs [8], next_job [9]
-    int32_t *njobs = queue + 8, *next_job = queue + 9;                  // (zeroed by the same memset)
+    int32_t *njobs = queue + 8, *next_job = queue + 9;
     off += 256;
+    uint2 *cand = reinterpret_cast<uint2 *>(sp + off);
+    off += ((size_t)B * S * cap_s * 2 * X3_CAPH * sizeof(uint2) + 255) / 256 * 256;
     int32_t *ovf_idx = reinterpret_cast<int32_t *>(sp + off);
     off += ((size_t)B * cap_s * sizeof(int32_t) + 255) / 256 * 256;
     float *al_norm = reinterpret_cast<float *>(sp + off);
@@ -877,8 +888,6 @@ int match_x3_resolve(const float *a_c, const int32_t *n_c, int cap_s, const floa
     uint2 *jobs = reinterpret_cast<uint2 *>(sp + off);
     *n_ovf_out = n_ovf;
     *ovf_idx_out = ovf_idx;
-    if (hipMemsetAsync(n_ovf, 0, 2 * cnt_block + 256, st) != hipSuccess) return ORYON_ERR_HIP;
-    if (hipMemsetAsync(cnt, 0, (size_t)B * S * cap_s * 2 * sizeof(int32_t), st) != hipSuccess) return ORYON_ERR_HIP;     // sweep 2 appends with atomics
     // query rows as hi / lo halves, only for pairs that have listed anchors (the gather's per-map gate reads the counts themselves) -
     // unless the caller's K0 pass already wrote them for every pair (oryon_gather_mx6_x3: the step engine does when recent steps came here)
     int rc = ORYON_OK;

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_corrs_kernel(
     // sel_rows != NULL (lazy matcher, match_corrs.hip): also record WHICH anchor row fills every slot; for pairs whose argmin column is
     // not materialised yet (pair_eager[p] == 0) the query half of the row is left to match_resolve_selected_kernel
     __shared__ int s_wave[SEL_WAVES];
-    __shared__ unsigned s_hist[256];
+    __shared__ __align__(16) unsigned s_hist[256];
     __shared__ unsigned s_prefix, s_remaining;
     const int p = blockIdx.x;
     const int na = n_a[p], nq = n_q[p];
@@ -135,15 +135,14 @@ __global__ __launch_bounds__(SEL_THREADS) void select_corrs_kernel(
             if ((k & hi_mask) == prefix) atomicAdd(&s_hist[(k >> shift) & 0xFFu], 1u);
         }
         __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned rem = s_remaining, cum = 0u;
-            int b = 0;
-            for (; b < 256; ++b) {
-                if (cum + s_hist[b] >= rem) break;
-                cum += s_hist[b];
+        if (threadIdx.x < 64) {                                     // the bin walk, by the first wave (common.h)
+            const unsigned rem = s_remaining;
+            unsigned cum;
+            const int b = radix_pick(s_hist, rem, cum);
+            if (threadIdx.x == 0) {
+                s_remaining = rem - cum;
+                s_prefix = prefix | ((unsigned)b << shift);
             }
-            s_remaining = rem - cum;
-            s_prefix = prefix | ((unsigned)b << shift);
         }
         __syncthreads();
     }

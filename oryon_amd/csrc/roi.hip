@@ -118,7 +118,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void roi_subsample_kernel(int32_t *__
                                                                       const int64_t *__restrict__ map_key)
 {
     __shared__ int s_wave[SCAN_WAVES];
-    __shared__ unsigned s_hist[256];
+    __shared__ __align__(16) unsigned s_hist[256];
     __shared__ unsigned s_prefix, s_remaining;
     const int m = blockIdx.x;
     const int n = count[m];
@@ -139,15 +139,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void roi_subsample_kernel(int32_t *__
             if ((k & hi_mask) == prefix) atomicAdd(&s_hist[(k >> shift) & 0xFFu], 1u);
         }
         __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned rem = s_remaining, cum = 0u;
-            int b = 0;
-            for (; b < 256; ++b) {
-                if (cum + s_hist[b] >= rem) break;
-                cum += s_hist[b];
+        if (threadIdx.x < 64) {                                     // the bin walk, by the first wave (common.h)
+            const unsigned rem = s_remaining;
+            unsigned cum;
+            const int b = radix_pick(s_hist, rem, cum);
+            if (threadIdx.x == 0) {
+                s_remaining = rem - cum;
+                s_prefix = prefix | ((unsigned)b << shift);
             }
-            s_remaining = rem - cum;
-            s_prefix = prefix | ((unsigned)b << shift);
         }
         __syncthreads();
     }
