@@ -359,7 +359,7 @@ int oryon_select_corrs(const int32_t *roi_a, const int32_t *roi_q, int roi_strid
 
 /* K2  scale (y,x) to the original image, keep rows inside both images, truncate, gather depth, pin-hole
  *     lift, /1000.  Replaces pipeline.py:447-460 + utils/coordinates.py:5-48 + utils/pcd.py:44-74.
- * corrs [B, n_cap, 4] int32; n_corr [B] or NULL (then n_cap rows each); depth_* [B,H*,W*] fp32 millimetres;
+ * corrs [B, n_cap, 4] int32; n_corr [B] (clamped to [0, n_cap]) or NULL (then n_cap rows each); depth_* [B,H*,W*] fp32 millimetres;
  * cam_* [B,9] fp32 (row-major K, already rounded from the reference's fp64); status [B] may be NULL
  * (pairs whose status != ORYON_PAIR_OK are skipped and get n_out = 0).
  * pcd_a/pcd_q [B, n_cap, 3] fp32 metres, compacted over valid rows in order, rows >= n_out zeroed; n_out [B]. */

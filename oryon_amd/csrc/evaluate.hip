@@ -22,10 +22,18 @@ __device__ __forceinline__ float3 move_f16(const float *P, float x, float y, flo
 {
     const float px = h16(x), py = h16(y), pz = h16(z);
     float3 o;
-    // np.dot(pcd16, R16.T): fp32 accumulation in k order, one rounding to half at the end; then + t16, rounded again
-    o.x = h16(h16(__fmaf_rn(pz, h16(P[2]), __fmaf_rn(py, h16(P[1]), __fmul_rn(px, h16(P[0]))))) + h16(P[3]));
-    o.y = h16(h16(__fmaf_rn(pz, h16(P[6]), __fmaf_rn(py, h16(P[5]), __fmul_rn(px, h16(P[4]))))) + h16(P[7]));
-    o.z = h16(h16(__fmaf_rn(pz, h16(P[10]), __fmaf_rn(py, h16(P[9]), __fmul_rn(px, h16(P[8]))))) + h16(P[11]));
+    // np.dot(pcd16, R16.T): fp32 accumulation in k order, one rounding to half at the end; then + t16, rounded again.
+    // The fp32 sum is pinned in a register: left alone, the compiler folds the last fma and the conversion into one
+    // v_fma_mixlo_f16, which rounds the exact sum to half ONCE - another half than numpy's fp32 sum gives wherever that sum is a
+    // rounding tie of the half grid (one value in 2^13; tests/test_gpu_plumbing.py, M = 2500).
+    auto row = [&](int r) {
+        float acc = __fmaf_rn(pz, h16(P[r + 2]), __fmaf_rn(py, h16(P[r + 1]), __fmul_rn(px, h16(P[r]))));
+        asm volatile("" : "+v"(acc));
+        return h16(h16(acc) + h16(P[r + 3]));
+    };
+    o.x = row(0);
+    o.y = row(4);
+    o.z = row(8);
     return o;
 }
 

@@ -194,7 +194,8 @@ __global__ __launch_bounds__(512) void lift_pairs_kernel(
         zero_from(0);
         return;
     }
-    const int n = n_corr ? n_corr[p] : n_cap;
+    // a count outside [0, n_cap] would read the next pair's rows and write past this pair's clouds
+    const int n = n_corr ? min(max(n_corr[p], 0), n_cap) : n_cap;
     const int32_t *c = corrs + (size_t)p * n_cap * 4;
     const float *da = depth_a + (size_t)p * HA * WA, *dq = depth_q + (size_t)p * HQ * WQ;
     const float fxa = cam_a[p * 9 + 0], cxa = cam_a[p * 9 + 2], fya = cam_a[p * 9 + 4], cya = cam_a[p * 9 + 5];

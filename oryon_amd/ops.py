@@ -662,6 +662,8 @@ def lift_points(depth: torch.Tensor, cam9: torch.Tensor, x_idx: torch.Tensor, y_
     dev = _lib.require_gpu(depth.device)
     n = x_idx.shape[0]
     out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if n == 0:                                   # empty tensors have no storage: the C entry refuses their NULL pointers
+        return out
     xi = x_idx.to(torch.int32).contiguous()
     yi = y_idx.to(torch.int32).contiguous()
     check(lib().oryon_lift_points(ptr(depth), depth.shape[0], depth.shape[1], ptr(cam9.contiguous()), ptr(xi), ptr(yi), n,
