@@ -69,6 +69,9 @@ __device__ __forceinline__ void x3_raise(unsigned *flag, unsigned mag_max)
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// workspace carving: every block starts on a 256-byte boundary; float64 / int64 arguments must be 8-byte aligned (NULL is)
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 // 64-bit mix (splitmix64 finaliser): the counter-based RNG of the batched sampling kernels.
 __host__ __device__ static inline uint64_t mix64(uint64_t x)

@@ -9,14 +9,14 @@
 // The arithmetic is DEFINED (include/oryon_hip.h, oryon_gt_corrs; DESIGN.md "Ground-truth correspondences"): float64, no contraction,
 // sums left to right, so that tests/gt_corrs_restatement.py - the same sequence of correctly rounded operations in numpy - agrees bit
 // for bit.  No kernel here allocates, synchronises or uses an atomic: every output is bit-stable.
-//   lift       X = (double(fp32(x) - fp32(cx)) * z) / fx / 1000, Y alike with (y, cy, fy), Z = z / 1000;  z = double(depth[pixel]) in
-//              millimetres.  The pixel-minus-centre difference is taken in fp32: the reference's xmap / ymap are float32 tensors and cx
-//              a 0-dim float64 one, which torch's promotion rules leave in float32.  Zero depth lifts to the origin and is kept.
+//   lift       depth_lift.h: X = (double(fp32(x) - fp32(cx)) * z) / fx / 1000, Y alike with (y, cy, fy), Z = z / 1000;
+//              z = double(depth[pixel]) in millimetres.  Zero depth lifts to the origin and is kept.
 //   transform  p' = ((R0 x + R1 y) + R2 z) + t per output coordinate (anchor side only).
 //   nearest    d2_j = ((dx dx + dy dy) + dz dz), j ascending, strict <: the first minimiser (torch.argmin).  NaN never wins.
 //   keep       sqrt(d2) <= threshold, rows written in anchor order.
 #include "common.h"
 #include "nn_tile.h"
+#include "depth_lift.h"
 
 #pragma clang fp contract(off)
 
@@ -46,10 +46,9 @@ __global__ __launch_bounds__(GTC_THREADS) void gtc_lift_kernel(const float *__re
     const double z = inside ? (double)depth[(size_t)b * HW + p] : 0.0;
     const double *K = cam9 + (size_t)b * 9;
     const double fx = K[0], cx = K[2], fy = K[4], cy = K[5];
-    const float dxf = (float)x - (float)cx, dyf = (float)y - (float)cy;
-    double X = (((double)dxf * z) / fx) / 1000.0;
-    double Y = (((double)dyf * z) / fy) / 1000.0;
-    double Z = z / 1000.0;
+    double V[3];
+    depth_lift_f64(x, y, z, fx, (float)cx, fy, (float)cy, V);
+    double X = V[0], Y = V[1], Z = V[2];
     if (pose) {
         const double *T = pose + (size_t)b * 12;
         const double x2 = ((T[0] * X + T[1] * Y) + T[2] * Z) + T[3];
@@ -147,8 +146,6 @@ __global__ __launch_bounds__(GTC_KEEP_THREADS) void gtc_keep_kernel(const int32_
     if (threadIdx.x == 0) n_corr[b] = base;
 }
 
-static inline size_t gtc_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline bool gtc_aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 static void launch_lift(const float *depth, int B, int H, int W, const int32_t *pix, const int32_t *n, int cap, const double *cam9,
                         const double *pose, const int32_t *status, double *xyz, int32_t *yx, hipStream_t st)
@@ -186,7 +183,7 @@ static GtcWorkspace gtc_carve(void *workspace, int B, int cap_a, int cap_q)
     GtcWorkspace w;
     char *p = static_cast<char *>(workspace);
     size_t at = 0;
-    auto take = [&](size_t n) { char *r = p ? p + at : nullptr; at += gtc_align256(n); return r; };
+    auto take = [&](size_t n) { char *r = p ? p + at : nullptr; at += align256(n); return r; };
     w.xyz_a = reinterpret_cast<double *>(take((size_t)B * cap_a * 3 * sizeof(double)));
     w.xyz_q = reinterpret_cast<double *>(take((size_t)B * cap_q * 3 * sizeof(double)));
     w.d2 = reinterpret_cast<double *>(take((size_t)B * cap_a * sizeof(double)));
@@ -205,7 +202,7 @@ extern "C" int oryon_gtc_lift(const float *depth, int B, int H, int W, const int
                               const double *pose, double *xyz, int32_t *yx, void *stream)
 {
     ORYON_CHECK_ARG(depth && pix && n && cam9 && xyz && yx);                          // pose may be NULL: no transform
-    ORYON_CHECK_ARG(gtc_aligned8(cam9) && gtc_aligned8(pose) && gtc_aligned8(xyz));
+    ORYON_CHECK_ARG(aligned8(cam9) && aligned8(pose) && aligned8(xyz));
     ORYON_CHECK_ARG(B >= 0 && B <= 65535 && H >= 1 && W >= 1 && (int64_t)H * W <= 0x7fffffff && cap >= 1);
     if (B == 0) return ORYON_OK;
     launch_lift(depth, B, H, W, pix, n, cap, cam9, pose, nullptr, xyz, yx, as_stream(stream));
@@ -217,7 +214,7 @@ extern "C" int oryon_pcd_nearest_f64(const double *src, const int32_t *n_src, co
                                      int cap_dst, int32_t *idx, double *d2, void *stream)
 {
     ORYON_CHECK_ARG(src && n_src && dst && n_dst && idx && d2);
-    ORYON_CHECK_ARG(gtc_aligned8(src) && gtc_aligned8(dst) && gtc_aligned8(d2));
+    ORYON_CHECK_ARG(aligned8(src) && aligned8(dst) && aligned8(d2));
     ORYON_CHECK_ARG(B >= 0 && B <= 65535 && cap_src >= 1 && cap_dst >= 1);
     if (B == 0) return ORYON_OK;
     launch_nearest(src, n_src, dst, n_dst, B, cap_src, cap_dst, nullptr, idx, d2, as_stream(stream));
@@ -237,7 +234,7 @@ extern "C" int oryon_gt_corrs(const float *depth_a, const float *depth_q, int B,
                               size_t workspace_bytes, int32_t *corrs, int32_t *n_corr, int32_t *idx, double *d2, void *stream)
 {
     ORYON_CHECK_ARG(depth_a && depth_q && pix_a && n_a && pix_q && n_q && cam_a && cam_q && pose_aq && workspace && corrs && n_corr);
-    ORYON_CHECK_ARG(gtc_aligned8(cam_a) && gtc_aligned8(cam_q) && gtc_aligned8(pose_aq) && gtc_aligned8(d2));   // idx / d2 may be NULL
+    ORYON_CHECK_ARG(aligned8(cam_a) && aligned8(cam_q) && aligned8(pose_aq) && aligned8(d2));   // idx / d2 may be NULL
     ORYON_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0);
     ORYON_CHECK_ARG(threshold >= 0.0);                                                // NaN fails
     ORYON_CHECK_ARG(B >= 0 && B <= 65535 && cap_a >= 1 && cap_q >= 1);

@@ -9,42 +9,21 @@
 //   fit       dT = best_fit_transform_icp(s_kept, dst[j]_kept): plain means, H = sum (s - c_s)(d - c_d)^T,
 //             R = V diag(1, 1, det(V U^T)) U^T (kabsch.h), t = c_d - R c_s
 //   update    T_{k+1} = dT T_k; done when |prev - mean(dist_kept)| < tolerance (this update applied), else prev = mean
-// The order of the sums over rows is not part of the definition but it is FIXED: a workgroup's rows are reduced by an xor butterfly
-// inside each wave and over the waves in ascending order, the workgroups' records in ascending block order.  No float atomics: every
-// output is bit-stable across runs, streams and batch position.
+// The state, the FIXED order of the sums over rows (no float atomics: every output is bit-stable across runs, streams and batch
+// position), the done flag and the end of an update are icp_common.h's, shared with icp_plane.hip.
 //
-// Two launches per iteration, all max_iter iterations enqueued by the host.  A pair that is done has its workgroups return at once.  No
-// workgroup waits on another inside a launch: launch boundaries are the only cross-workgroup ordering.
-#include "common.h"
-#include "kabsch.h"
+// Two launches per iteration, all max_iter iterations enqueued by the host.  A pair that is done has its workgroups return at once.
+#include "icp_common.h"                  // first: kabsch.h stays under the default contraction
 #include "nn_tile.h"
-
-#pragma clang fp contract(off)
 
 namespace oryon {
 
-constexpr int ICP_THREADS = 256;             // source rows of a workgroup, one per lane: 64 pairs x 2048 rows = 512 workgroups on 256 CUs
-constexpr int ICP_WAVES = ICP_THREADS / 64;
-constexpr int ICP_MAX_ROWS = 8192;           // ORYON_ICP_MAX_ROWS: the derived error bar of the row sums assumes it
-constexpr int ICP_MAX_ITER = 1000;           // ORYON_ICP_MAX_ITER: two launches each
 constexpr int ICP_REC = 17;                  // a partial record: sum s' [3] | sum d' [3] | sum s' d'^T [9] | sum dist | count
-static_assert(ICP_MAX_ROWS == ORYON_ICP_MAX_ROWS && ICP_MAX_ITER == ORYON_ICP_MAX_ITER, "include/oryon_hip.h states the caps");
 static_assert(ICP_WAVES * ICP_REC <= 3 * NN_TILE, "the waves' records reuse the tile");
 
-// Per-pair state, in the workspace.  origin: the target's centroid, computed once - the moments are accumulated about it (s' = s - origin,
-// d' = d - origin), so that H = sum s' d'^T - m c_s' c_d'^T does not cancel at coordinates around 1 m with a spread of around 5 cm.
-struct IcpState {
-    double T[12];                            // rows of [R | t] of T_k
-    double prev;
-    double origin[3];
-    int32_t done, pad;
-};
-static_assert(sizeof(IcpState) == ORYON_ICP_STATE_BYTES, "include/oryon_hip.h states the workspace formula");
-
-__device__ __forceinline__ int icp_count(const int32_t *__restrict__ n, int b, int cap) { return max(0, min(n[b], cap)); }
-
-// One wave per pair: T_0 widened (and written out, so a pair that never iterates returns it), the done flag of pairs that do not start,
-// the target's centroid (lane-strided sums, xor butterfly: a fixed order), idx = -1.
+// One wave per pair: the done flag of pairs that do not start, the origin (lane-strided sums, xor butterfly: a fixed order) and
+// icp_init_tail.  origin: the target's centroid - the moments are accumulated about it (s' = s - origin, d' = d - origin), so that
+// H = sum s' d'^T - m c_s' c_d'^T does not cancel at coordinates around 1 m with a spread of around 5 cm.
 __global__ __launch_bounds__(64) void icp_init_kernel(const double *__restrict__ dst, const int32_t *__restrict__ n_src, int cap_src,
                                                       const int32_t *__restrict__ n_dst, int cap_dst, const float *__restrict__ T_init,
                                                       const int32_t *__restrict__ status_in, IcpState *__restrict__ state, float *__restrict__ T,
@@ -68,27 +47,7 @@ __global__ __launch_bounds__(64) void icp_init_kernel(const double *__restrict__
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[c] = wave_sum(o[c]) / (double)nd;
     }
-    if (idx)
-        for (int i = lane; i < cap_src; i += 64) idx[(size_t)b * cap_src + i] = -1;
-    if (lane < 16) {
-        const float v = T_init ? T_init[(size_t)b * 16 + lane] : ((lane & 3) == (lane >> 2) ? 1.0f : 0.0f);    // NULL: the identity
-        T[(size_t)b * 16 + lane] = v;                                                 // the last row stays T_init's
-        if (lane < 12) {
-            state[b].T[lane] = (double)v;
-            if (T64) T64[(size_t)b * 12 + lane] = (double)v;
-        }
-    }
-    if (lane == 0) {
-        IcpState &S = state[b];
-        S.prev = 0.0;
-        S.origin[0] = o[0]; S.origin[1] = o[1]; S.origin[2] = o[2];
-        S.done = done ? 1 : 0;
-        S.pad = 0;
-        iters[b] = 0;
-        mean_err[b] = 0.0;
-        if (n_kept) n_kept[b] = 0;
-        if (status_out) status_out[b] = st;
-    }
+    icp_init_tail(b, lane, cap_src, done, st, o, T_init, state, T, T64, iters, mean_err, n_kept, idx, status_out);
 }
 
 // grid (row blocks, B).  A workgroup moves its ICP_THREADS source rows by T_k once, into registers, walks the pair's target cloud
@@ -113,9 +72,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_nearest_kernel(const double *
     const bool live = r < ns;                                // rows beyond n are never read
     const double x = live ? A[(size_t)r * 3 + 0] : 0.0, y = live ? A[(size_t)r * 3 + 1] : 0.0, z = live ? A[(size_t)r * 3 + 2] : 0.0;
     const double *T = S.T;
-    const double ax[1] = {((T[0] * x + T[1] * y) + T[2] * z) + T[3]};
-    const double ay[1] = {((T[4] * x + T[5] * y) + T[6] * z) + T[7]};
-    const double az[1] = {((T[8] * x + T[9] * y) + T[10] * z) + T[11]};
+    const double ax[1] = {icp_move(T, x, y, z)}, ay[1] = {icp_move(T + 4, x, y, z)}, az[1] = {icp_move(T + 8, x, y, z)};
     double best[1];
     int bi[1];
     if (PAIRED) {
@@ -146,21 +103,8 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_nearest_kernel(const double *
         v[15] = dist;
         v[16] = 1.0;
     }
-#pragma unroll
-    for (int q = 0; q < ICP_REC; ++q) v[q] = wave_sum(v[q]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __syncthreads();                                         // every wave has left the last tile
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < ICP_REC; ++q) icp_tile[wave * ICP_REC + q] = v[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < ICP_REC) {
-        double a = icp_tile[threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < ICP_WAVES; ++w) a += icp_tile[w * ICP_REC + threadIdx.x];
-        partials[((size_t)b * gridDim.x + blockIdx.x) * ICP_REC + threadIdx.x] = a;
-    }
+    icp_block_record<ICP_REC>(v, icp_tile, partials, b);
 }
 
 // One wave per pair: the records summed in ascending block order (lane q sums entry q), then lane 0 fits dT (kabsch.h), composes
@@ -174,13 +118,7 @@ __global__ __launch_bounds__(64) void icp_update_kernel(const int32_t *__restric
     const int b = blockIdx.x;
     IcpState &S = state[b];
     if (S.done) return;                                      // uniform: only lane 0 writes it, after the barrier
-    const int used = (icp_count(n_src, b, cap_src) + ICP_THREADS - 1) / ICP_THREADS;
-    if (threadIdx.x < ICP_REC) {
-        double a = 0.0;
-        for (int blk = 0; blk < used; ++blk) a += partials[((size_t)b * n_blocks + blk) * ICP_REC + threadIdx.x];
-        acc[threadIdx.x] = a;
-    }
-    __syncthreads();
+    icp_sum_records<ICP_REC>(partials, b, n_blocks, n_src, cap_src, acc);
     if (threadIdx.x != 0) return;
     const double m = acc[16];
     if (n_kept) n_kept[b] = (int32_t)m;
@@ -201,47 +139,13 @@ __global__ __launch_bounds__(64) void icp_update_kernel(const int32_t *__restric
     for (int c = 0; c < 3; ++c) { cs[c] += S.origin[c]; cd[c] += S.origin[c]; }
 #pragma unroll
     for (int c = 0; c < 3; ++c) t[c] = cd[c] - ((R[c * 3] * cs[0] + R[c * 3 + 1] * cs[1]) + R[c * 3 + 2] * cs[2]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) Tn[c * 4 + e] = (R[c * 3] * S.T[e] + R[c * 3 + 1] * S.T[4 + e]) + R[c * 3 + 2] * S.T[8 + e];
-        Tn[c * 4 + 3] += t[c];
-    }
-#pragma unroll
-    for (int q = 0; q < 12; ++q) {
-        S.T[q] = Tn[q];
-        if (T64) T64[(size_t)b * 12 + q] = Tn[q];
-        T_out[(size_t)b * 16 + q] = (float)Tn[q];
-    }
-    iters[b] = k + 1;
-    mean_err[b] = mean;
-    if (fabs(S.prev - mean) < tolerance) S.done = 1;
-    else S.prev = mean;
+    icp_compose(R, t, S.T, Tn);
+    icp_commit(S, b, k, Tn, mean, tolerance, T_out, T64, iters, mean_err);
 }
 
-static inline size_t icp_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline bool icp_aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 static inline bool icp_shape_ok(int B, int cap_src, int cap_dst)
 {
     return B >= 1 && B <= 65535 && cap_src >= 1 && cap_src <= ICP_MAX_ROWS && cap_dst >= 1 && cap_dst <= ICP_MAX_ROWS;
-}
-
-struct IcpWorkspace {
-    IcpState *state;
-    double *partials;
-    size_t bytes;
-};
-
-static IcpWorkspace icp_carve(void *workspace, int B, int cap_src)
-{
-    IcpWorkspace w;
-    char *p = static_cast<char *>(workspace);
-    size_t at = 0;
-    auto take = [&](size_t n) { char *r = p ? p + at : nullptr; at += icp_align256(n); return r; };
-    w.state = reinterpret_cast<IcpState *>(take((size_t)B * sizeof(IcpState)));
-    w.partials = reinterpret_cast<double *>(take((size_t)B * ceil_div(cap_src, ICP_THREADS) * ICP_REC * sizeof(double)));
-    w.bytes = at;
-    return w;
 }
 
 }  // namespace oryon
@@ -251,7 +155,7 @@ using namespace oryon;
 extern "C" size_t oryon_icp_workspace_bytes(int B, int cap_src, int cap_dst)
 {
     if (!icp_shape_ok(B, cap_src, cap_dst)) return 0;
-    return icp_carve(nullptr, B, cap_src).bytes;
+    return icp_carve(nullptr, B, cap_src, ICP_REC).bytes;
 }
 
 // The launches of both entries.  paired: one iteration over the caller's correspondences.
@@ -288,7 +192,7 @@ extern "C" int oryon_icp_refine(const double *src, const int32_t *n_src, int cap
 {
     ORYON_CHECK_ARG(src && n_src && dst && n_dst && T_init && workspace);
     ORYON_CHECK_ARG(T && iters && mean_err && n_kept && status_out);                  // T64, idx and status_in may be NULL
-    ORYON_CHECK_ARG(icp_aligned8(src) && icp_aligned8(dst) && icp_aligned8(T64) && icp_aligned8(mean_err));
+    ORYON_CHECK_ARG(aligned8(src) && aligned8(dst) && aligned8(T64) && aligned8(mean_err));
     ORYON_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0);
     ORYON_CHECK_ARG(max_iter >= 1 && max_iter <= ICP_MAX_ITER);
     ORYON_CHECK_ARG(tolerance >= 0.0);                                                // NaN fails
@@ -296,7 +200,7 @@ extern "C" int oryon_icp_refine(const double *src, const int32_t *n_src, int cap
     ORYON_CHECK_ARG(B >= 0 && B <= 65535);
     ORYON_CHECK_ARG(cap_src >= 1 && cap_src <= ICP_MAX_ROWS && cap_dst >= 1 && cap_dst <= ICP_MAX_ROWS);
     if (B == 0) return ORYON_OK;
-    const IcpWorkspace w = icp_carve(workspace, B, cap_src);
+    const IcpWorkspace w = icp_carve(workspace, B, cap_src, ICP_REC);
     ORYON_CHECK_ARG(workspace_bytes >= w.bytes);
     return icp_enqueue(__func__, false, src, n_src, cap_src, dst, n_dst, cap_dst, B, T_init, max_iter, tolerance, max_dist, status_in, w, T, T64,
                        iters, mean_err, n_kept, idx, status_out, as_stream(stream));
@@ -306,11 +210,11 @@ extern "C" int oryon_icp_best_fit(const double *A, const double *Bp, const int32
                                   float *T, double *T64, int32_t *fitted, double *mean_err, void *stream)
 {
     ORYON_CHECK_ARG(A && Bp && n && workspace && T && fitted && mean_err);            // T64 may be NULL
-    ORYON_CHECK_ARG(icp_aligned8(A) && icp_aligned8(Bp) && icp_aligned8(T64) && icp_aligned8(mean_err));
+    ORYON_CHECK_ARG(aligned8(A) && aligned8(Bp) && aligned8(T64) && aligned8(mean_err));
     ORYON_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0);
     ORYON_CHECK_ARG(B >= 0 && B <= 65535 && cap >= 1 && cap <= ICP_MAX_ROWS);
     if (B == 0) return ORYON_OK;
-    const IcpWorkspace w = icp_carve(workspace, B, cap);
+    const IcpWorkspace w = icp_carve(workspace, B, cap, ICP_REC);
     ORYON_CHECK_ARG(workspace_bytes >= w.bytes);
     return icp_enqueue(__func__, true, A, n, cap, Bp, n, cap, B, nullptr, 1, 0.0, __builtin_inf(), nullptr, w, T, T64, fitted, mean_err, nullptr,
                        nullptr, nullptr, as_stream(stream));

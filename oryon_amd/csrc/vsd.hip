@@ -248,8 +248,6 @@ __global__ __launch_bounds__(256) void vsd_score_kernel(const uint32_t *__restri
     }
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static size_t render_workspace_bytes(int N, int max_faces) { return VSD_HEADER_BYTES + (size_t)N * max_faces * sizeof(uint2); }
 
 // z-buffer cleared and filled; zbuf [N,H,W] holds depth bit patterns, VSD_EMPTY where nothing was drawn

@@ -1039,9 +1039,42 @@ def gt_corrs(depth_a: torch.Tensor, depth_q: torch.Tensor, pix_a: torch.Tensor, 
 ICP_MAX_ROWS, ICP_MAX_ITER = 8192, 1000      # ORYON_ICP_MAX_ROWS, ORYON_ICP_MAX_ITER (include/oryon_hip.h)
 
 
-def _icp_require(cond: bool, check_name: str, detail: str = "") -> None:
-    if not cond:
-        raise ValueError(f"icp_refine: {check_name}" + (f" ({detail})" if detail else ""))
+def _icp_requirer(who: str):
+    def require(cond: bool, check_name: str, detail: str = "") -> None:
+        if not cond:
+            raise ValueError(f"{who}: {check_name}" + (f" ({detail})" if detail else ""))
+    return require
+
+
+def _icp_check_counts(req, B: int, n_src=None, n_dst=None, status=None) -> None:
+    """The [B] int32 tensors of a refiner, in the order given; None: not passed."""
+    for name, t in (("n_src", n_src), ("n_dst", n_dst), ("status", status)):
+        if t is not None:
+            req(t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (B,), f"{name} is [B] int32", f"{tuple(t.shape)} {t.dtype}")
+            req(t.is_contiguous(), f"{name}.is_contiguous")
+
+
+def _icp_check_start(req, B: int, T_init, device, others, max_iter, tolerance, max_dist) -> int:
+    """T_init, one device over `others` (status may be None among them), and the scalars both refiners share -> int(max_iter)."""
+    req(T_init.dtype == torch.float32, "T_init.dtype == float32", str(T_init.dtype))
+    req(tuple(T_init.shape) == (B, 4, 4), "T_init.shape == [B,4,4]", str(tuple(T_init.shape)))
+    req(T_init.is_contiguous(), "T_init.is_contiguous")
+    req(all(t.device == device for t in others + (T_init,) if t is not None), "one device")
+    max_iter = int(max_iter)
+    req(1 <= max_iter <= ICP_MAX_ITER, f"1 <= max_iter <= {ICP_MAX_ITER}", str(max_iter))
+    req(float(tolerance) >= 0.0, "tolerance >= 0", str(tolerance))
+    req(float(max_dist) >= 0.0, "max_dist >= 0", str(max_dist))
+    return max_iter
+
+
+def _icp_outputs(dev, B: int, cap_src: int, need: int, workspace=None, want_idx: bool = False):
+    """What every refiner call writes: dict(T, T64, iters, mean_err, n_kept, idx | None, status), and the workspace."""
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    ws = workspace if workspace is not None else new((max(need, 256),), torch.uint8)
+    out = dict(T=new((B, 4, 4), torch.float32), T64=new((B, 3, 4), torch.float64), iters=new((B,), torch.int32),
+               mean_err=new((B,), torch.float64), n_kept=new((B,), torch.int32), idx=new((B, cap_src), torch.int32) if want_idx else None,
+               status=new((B,), torch.int32))
+    return out, ws
 
 
 def icp_refine(src: torch.Tensor, dst: torch.Tensor, n_src: torch.Tensor, n_dst: torch.Tensor, T_init: torch.Tensor, max_iter: int = 20,
@@ -1052,47 +1085,31 @@ def icp_refine(src: torch.Tensor, dst: torch.Tensor, n_src: torch.Tensor, n_dst:
     of exactly these dtypes: nothing is converted or copied here, a tensor that does not fit is rejected with the name of the check.
     Runs on the current stream with no host round trip -> dict(T [B,4,4] fp32, T64 [B,3,4] float64, iters [B] int32, mean_err [B]
     float64, n_kept [B] int32, idx [B,cap_src] int32 | None, status [B] int32)."""
+    req = _icp_requirer("icp_refine")
     for name, t in (("src", src), ("dst", dst), ("n_src", n_src), ("n_dst", n_dst), ("T_init", T_init)):
-        _icp_require(isinstance(t, torch.Tensor) and t.is_cuda, f"{name}.is_cuda")
-    _icp_require(src.dtype == torch.float64, "src.dtype == float64", str(src.dtype))
-    _icp_require(dst.dtype == torch.float64, "dst.dtype == float64", str(dst.dtype))
-    _icp_require(src.dim() == 3 and src.shape[2] == 3 and src.shape[1] >= 1, "src.shape == [B,cap_src,3]", str(tuple(src.shape)))
+        req(isinstance(t, torch.Tensor) and t.is_cuda, f"{name}.is_cuda")
+    req(src.dtype == torch.float64, "src.dtype == float64", str(src.dtype))
+    req(dst.dtype == torch.float64, "dst.dtype == float64", str(dst.dtype))
+    req(src.dim() == 3 and src.shape[2] == 3 and src.shape[1] >= 1, "src.shape == [B,cap_src,3]", str(tuple(src.shape)))
     B = src.shape[0]
-    _icp_require(B >= 1, "B >= 1")
-    _icp_require(dst.dim() == 3 and dst.shape[2] == 3 and dst.shape[1] >= 1 and dst.shape[0] == B, "dst.shape == [B,cap_dst,3]",
-                 str(tuple(dst.shape)))
+    req(B >= 1, "B >= 1")
+    req(dst.dim() == 3 and dst.shape[2] == 3 and dst.shape[1] >= 1 and dst.shape[0] == B, "dst.shape == [B,cap_dst,3]", str(tuple(dst.shape)))
     cap_src, cap_dst = src.shape[1], dst.shape[1]
-    _icp_require(src.is_contiguous(), "src.is_contiguous")
-    _icp_require(dst.is_contiguous(), "dst.is_contiguous")
-    for name, t in (("n_src", n_src), ("n_dst", n_dst)) + ((("status", status),) if status is not None else ()):
-        _icp_require(t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (B,), f"{name} is [B] int32", f"{tuple(t.shape)} {t.dtype}")
-        _icp_require(t.is_contiguous(), f"{name}.is_contiguous")
-    _icp_require(T_init.dtype == torch.float32, "T_init.dtype == float32", str(T_init.dtype))
-    _icp_require(tuple(T_init.shape) == (B, 4, 4), "T_init.shape == [B,4,4]", str(tuple(T_init.shape)))
-    _icp_require(T_init.is_contiguous(), "T_init.is_contiguous")
-    _icp_require(all(t.device == src.device for t in (dst, n_src, n_dst, T_init) + ((status,) if status is not None else ())), "one device")
-    max_iter = int(max_iter)
-    _icp_require(1 <= max_iter <= ICP_MAX_ITER, f"1 <= max_iter <= {ICP_MAX_ITER}", str(max_iter))
-    _icp_require(float(tolerance) >= 0.0, "tolerance >= 0", str(tolerance))
-    _icp_require(float(max_dist) >= 0.0, "max_dist >= 0", str(max_dist))
-    _icp_require(cap_src <= ICP_MAX_ROWS and cap_dst <= ICP_MAX_ROWS, f"cap <= {ICP_MAX_ROWS}", f"{cap_src}, {cap_dst}")
+    req(src.is_contiguous(), "src.is_contiguous")
+    req(dst.is_contiguous(), "dst.is_contiguous")
+    _icp_check_counts(req, B, n_src, n_dst, status)
+    max_iter = _icp_check_start(req, B, T_init, src.device, (dst, n_src, n_dst, status), max_iter, tolerance, max_dist)
+    req(cap_src <= ICP_MAX_ROWS and cap_dst <= ICP_MAX_ROWS, f"cap <= {ICP_MAX_ROWS}", f"{cap_src}, {cap_dst}")
     dev = _lib.require_gpu(src.device)
     with torch.cuda.device(dev):
         need = lib().oryon_icp_workspace_bytes(B, cap_src, cap_dst)
         if need == 0 and B > 0:
             raise _lib.OryonError(f"oryon_icp_workspace_bytes({B}, {cap_src}, {cap_dst}): shape not supported")
-        ws = workspace if workspace is not None else torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
-        T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
-        T64 = torch.empty((B, 3, 4), dtype=torch.float64, device=dev)
-        iters = torch.empty((B,), dtype=torch.int32, device=dev)
-        mean_err = torch.empty((B,), dtype=torch.float64, device=dev)
-        n_kept = torch.empty((B,), dtype=torch.int32, device=dev)
-        idx = torch.empty((B, cap_src), dtype=torch.int32, device=dev) if want_idx else None
-        st_out = torch.empty((B,), dtype=torch.int32, device=dev)
+        o, ws = _icp_outputs(dev, B, cap_src, need, workspace, want_idx)
         check(lib().oryon_icp_refine(ptr(src), ptr(n_src), cap_src, ptr(dst), ptr(n_dst), cap_dst, B, ptr(T_init), max_iter, float(tolerance),
-                                     float(max_dist), ptr(status), ptr(ws), ws.numel(), ptr(T), ptr(T64), ptr(iters), ptr(mean_err),
-                                     ptr(n_kept), ptr(idx), ptr(st_out), stream_ptr(dev)), "oryon_icp_refine")
-    return dict(T=T, T64=T64, iters=iters, mean_err=mean_err, n_kept=n_kept, idx=idx, status=st_out)
+                                     float(max_dist), ptr(status), ptr(ws), ws.numel(), ptr(o["T"]), ptr(o["T64"]), ptr(o["iters"]),
+                                     ptr(o["mean_err"]), ptr(o["n_kept"]), ptr(o["idx"]), ptr(o["status"]), stream_ptr(dev)), "oryon_icp_refine")
+    return o
 
 
 def icp_best_fit(A: torch.Tensor, Bp: torch.Tensor, n: torch.Tensor):
@@ -1109,19 +1126,10 @@ def icp_best_fit(A: torch.Tensor, Bp: torch.Tensor, n: torch.Tensor):
         raise ValueError("icp_best_fit: n is [B] int32")
     dev = _lib.require_gpu(A.device)
     with torch.cuda.device(dev):
-        ws = torch.empty((max(lib().oryon_icp_workspace_bytes(B, cap, cap), 256),), dtype=torch.uint8, device=dev)
-        T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
-        T64 = torch.empty((B, 3, 4), dtype=torch.float64, device=dev)
-        fitted = torch.empty((B,), dtype=torch.int32, device=dev)
-        mean_err = torch.empty((B,), dtype=torch.float64, device=dev)
-        check(lib().oryon_icp_best_fit(ptr(A), ptr(Bp), ptr(n), cap, B, ptr(ws), ws.numel(), ptr(T), ptr(T64), ptr(fitted), ptr(mean_err),
-                                       stream_ptr(dev)), "oryon_icp_best_fit")
-    return dict(T=T, T64=T64, fitted=fitted, mean_err=mean_err)
-
-
-def _icp_plane_require(cond: bool, check_name: str, detail: str = "") -> None:
-    if not cond:
-        raise ValueError(f"icp_plane_refine: {check_name}" + (f" ({detail})" if detail else ""))
+        o, ws = _icp_outputs(dev, B, cap, lib().oryon_icp_workspace_bytes(B, cap, cap))
+        check(lib().oryon_icp_best_fit(ptr(A), ptr(Bp), ptr(n), cap, B, ptr(ws), ws.numel(), ptr(o["T"]), ptr(o["T64"]), ptr(o["iters"]),
+                                       ptr(o["mean_err"]), stream_ptr(dev)), "oryon_icp_best_fit")
+    return dict(T=o["T"], T64=o["T64"], fitted=o["iters"], mean_err=o["mean_err"])
 
 
 def icp_plane_refine(src: torch.Tensor, n_src: torch.Tensor, depth: torch.Tensor, mask: torch.Tensor, cam9: torch.Tensor,
@@ -1133,7 +1141,7 @@ def icp_plane_refine(src: torch.Tensor, n_src: torch.Tensor, depth: torch.Tensor
     dtypes: nothing is converted or copied here, a tensor that does not fit is rejected with the name of the check.  max_dist and
     normal_jump in metres.  Runs on the current stream with no host round trip -> dict(T [B,4,4] fp32, T64 [B,3,4] float64, iters [B]
     int32, mean_err [B] float64, n_kept [B] int32, idx [B,cap_src] int32 | None (py W + px of a kept row, -1 otherwise), status [B])."""
-    req = _icp_plane_require
+    req = _icp_requirer("icp_plane_refine")
     for name, t in (("src", src), ("n_src", n_src), ("depth", depth), ("mask", mask), ("cam9", cam9), ("T_init", T_init)):
         req(isinstance(t, torch.Tensor) and t.is_cuda, f"{name}.is_cuda")
     req(src.dtype == torch.float64, "src.dtype == float64", str(src.dtype))
@@ -1141,9 +1149,7 @@ def icp_plane_refine(src: torch.Tensor, n_src: torch.Tensor, depth: torch.Tensor
     B, cap_src = src.shape[0], src.shape[1]
     req(B >= 1, "B >= 1")
     req(src.is_contiguous(), "src.is_contiguous")
-    for name, t in (("n_src", n_src),) + ((("status", status),) if status is not None else ()):
-        req(t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (B,), f"{name} is [B] int32", f"{tuple(t.shape)} {t.dtype}")
-        req(t.is_contiguous(), f"{name}.is_contiguous")
+    _icp_check_counts(req, B, n_src=n_src, status=status)
     req(depth.dtype == torch.float32, "depth.dtype == float32", str(depth.dtype))
     req(depth.dim() == 3 and depth.shape[0] == B, "depth.shape == [B,H,W]", str(tuple(depth.shape)))
     H, W = depth.shape[1], depth.shape[2]
@@ -1155,14 +1161,7 @@ def icp_plane_refine(src: torch.Tensor, n_src: torch.Tensor, depth: torch.Tensor
     req(cam9.dtype == torch.float64, "cam9.dtype == float64", str(cam9.dtype))
     req(tuple(cam9.shape) == (B, 9), "cam9.shape == [B,9]", str(tuple(cam9.shape)))
     req(cam9.is_contiguous(), "cam9.is_contiguous")
-    req(T_init.dtype == torch.float32, "T_init.dtype == float32", str(T_init.dtype))
-    req(tuple(T_init.shape) == (B, 4, 4), "T_init.shape == [B,4,4]", str(tuple(T_init.shape)))
-    req(T_init.is_contiguous(), "T_init.is_contiguous")
-    req(all(t.device == src.device for t in (n_src, depth, mask, cam9, T_init) + ((status,) if status is not None else ())), "one device")
-    max_iter = int(max_iter)
-    req(1 <= max_iter <= ICP_MAX_ITER, f"1 <= max_iter <= {ICP_MAX_ITER}", str(max_iter))
-    req(float(tolerance) >= 0.0, "tolerance >= 0", str(tolerance))
-    req(float(max_dist) >= 0.0, "max_dist >= 0", str(max_dist))
+    max_iter = _icp_check_start(req, B, T_init, src.device, (n_src, depth, mask, cam9, status), max_iter, tolerance, max_dist)
     req(float(normal_jump) >= 0.0, "normal_jump >= 0", str(normal_jump))
     req(cap_src <= ICP_MAX_ROWS, f"cap_src <= {ICP_MAX_ROWS}", str(cap_src))
     dev = _lib.require_gpu(src.device)
@@ -1170,19 +1169,12 @@ def icp_plane_refine(src: torch.Tensor, n_src: torch.Tensor, depth: torch.Tensor
         need = lib().oryon_icp_plane_workspace_bytes(B, cap_src)
         if need == 0:
             raise _lib.OryonError(f"oryon_icp_plane_workspace_bytes({B}, {cap_src}): shape not supported")
-        ws = workspace if workspace is not None else torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
-        T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
-        T64 = torch.empty((B, 3, 4), dtype=torch.float64, device=dev)
-        iters = torch.empty((B,), dtype=torch.int32, device=dev)
-        mean_err = torch.empty((B,), dtype=torch.float64, device=dev)
-        n_kept = torch.empty((B,), dtype=torch.int32, device=dev)
-        idx = torch.empty((B, cap_src), dtype=torch.int32, device=dev) if want_idx else None
-        st_out = torch.empty((B,), dtype=torch.int32, device=dev)
+        o, ws = _icp_outputs(dev, B, cap_src, need, workspace, want_idx)
         check(lib().oryon_icp_plane_refine(ptr(src), ptr(n_src), cap_src, ptr(depth), ptr(mask), H, W, ptr(cam9), B, ptr(T_init), max_iter,
-                                           float(tolerance), float(max_dist), float(normal_jump), ptr(status), ptr(ws), ws.numel(), ptr(T),
-                                           ptr(T64), ptr(iters), ptr(mean_err), ptr(n_kept), ptr(idx), ptr(st_out), stream_ptr(dev)),
-              "oryon_icp_plane_refine")
-    return dict(T=T, T64=T64, iters=iters, mean_err=mean_err, n_kept=n_kept, idx=idx, status=st_out)
+                                           float(tolerance), float(max_dist), float(normal_jump), ptr(status), ptr(ws), ws.numel(), ptr(o["T"]),
+                                           ptr(o["T64"]), ptr(o["iters"]), ptr(o["mean_err"]), ptr(o["n_kept"]), ptr(o["idx"]),
+                                           ptr(o["status"]), stream_ptr(dev)), "oryon_icp_plane_refine")
+    return o
 
 
 _x3_weights = {}
