@@ -25,6 +25,7 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 #include "common.h"
+#include "match_exact.h"
 
 namespace oryon {
 
@@ -367,10 +368,10 @@ __device__ __forceinline__ void gather_q8_v3_tile(
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
                     float4 q;
-                    q.x = __fdiv_rn(VG(64 * c + 8 * g + 0 + hh), d);
-                    q.y = __fdiv_rn(VG(64 * c + 8 * g + 2 + hh), d);
-                    q.z = __fdiv_rn(VG(64 * c + 8 * g + 4 + hh), d);
-                    q.w = __fdiv_rn(VG(64 * c + 8 * g + 6 + hh), d);
+                    q.x = __fdiv_rn(VG(64 * c + kperm_k(g, hh, 0)), d);
+                    q.y = __fdiv_rn(VG(64 * c + kperm_k(g, hh, 1)), d);
+                    q.z = __fdiv_rn(VG(64 * c + kperm_k(g, hh, 2)), d);
+                    q.w = __fdiv_rn(VG(64 * c + kperm_k(g, hh, 3)), d);
                     *reinterpret_cast<float4 *>(stage + stage_addr(lane, 2 * g + hh, 256)) = q;
                 }
             WAVE_LDS_ORDER();
@@ -597,10 +598,10 @@ __global__ __launch_bounds__(256, X3 ? 3 : 4) void gather_mx6_v4_kernel(
             for (int sl = 0; sl < 8; ++sl) {
                 const int g = 4 * P + (sl >> 1), hh = sl & 1;
                 float4 q;
-                q.x = __fdiv_rn(R.get(8 * g + 0 + hh), d);
-                q.y = __fdiv_rn(R.get(8 * g + 2 + hh), d);
-                q.z = __fdiv_rn(R.get(8 * g + 4 + hh), d);
-                q.w = __fdiv_rn(R.get(8 * g + 6 + hh), d);
+                q.x = __fdiv_rn(R.get(kperm_k(g, hh, 0)), d);
+                q.y = __fdiv_rn(R.get(kperm_k(g, hh, 1)), d);
+                q.z = __fdiv_rn(R.get(kperm_k(g, hh, 2)), d);
+                q.w = __fdiv_rn(R.get(kperm_k(g, hh, 3)), d);
                 *reinterpret_cast<float4 *>(my_st + ((sl ^ (lane & 7)) << 4)) = q;
             }
             WAVE_LDS_ORDER();

@@ -26,6 +26,7 @@
 #include "common.h"
 #include "match_common.h"
 #include "screen_tile.h"
+#include "match_exact.h"
 
 namespace oryon {
 
@@ -268,8 +269,8 @@ __global__ __launch_bounds__(256) void match_decide_kernel(const __half *__restr
                                                             const float *__restrict__ q_scale8)
 {
     // a_scale8 != nullptr: the (m1, slice, m2) triples come from the INT8 screening pass (K1s8) in units of 2^-E_a per anchor
-    // slice; margin and validity cut then follow the per-anchor int8 bound DELTA8 (see the header of the int8 kernel).
-    constexpr int NQB = ROWS_TILE / 32;
+    // slice; margin and validity cut then follow the per-anchor int8 bound DELTA8 (match_exact.h: i8_bound).  The slice ids do not
+    // depend on ROWS_TILE: sid >> 1 = tile * (ROWS_TILE / 32) + block is the 32-row query block either way (slice_row).
     // 16 anchors per wave: an empty launch (the fp16 stage behind K1s8 usually has nothing to do) costs 5 k workgroups, not 80 k
     const int p = blockIdx.y, lane = threadIdx.x & 63;
     const int n_anchors = n_a[p];
@@ -277,27 +278,18 @@ __global__ __launch_bounds__(256) void match_decide_kernel(const __half *__restr
     auto one_anchor = [&](const int a) {
     float valid_cut = valid_cut_in;
     const size_t arow = (size_t)p * cap_a + a;
-    float m1 = -INFINITY, m2 = -INFINITY;
-    int sid = 0;
-    for (int s = 0; s < S; ++s) {
-        const size_t o = ((size_t)p * S + s) * cap_a + a;
-        const float x1 = ws_m1[o], x2 = ws_m2[o];
-        m2 = fmaxf(fminf(m1, x1), fmaxf(m2, x2));
-        if (x1 > m1) { m1 = x1; sid = ws_i1[o]; }
-    }
+    float m1, m2;
+    int sid;
+    merge_split_triples(ws_m1, ws_i1, ws_m2, p, S, cap_a, a, m1, sid, m2);
     float margin = SCREEN_MARGIN, sa = 1.0f;
     if (a_scale8) {
-        sa = a_scale8[(size_t)p * (cap_a / 16) + (a >> 5) * 2 + ((a >> 2) & 1)];   // 2^-E of the anchor's slice
+        sa = a_scale8[(size_t)p * (cap_a / 16) + anchor_scale_slot(a)];           // 2^-E of the anchor's slice
         m1 *= sa;                                             // exact: power of two
         m2 *= sa;
-        // K0's rounding: |q 2^-E - x^| <= 2^-(E+1) * (1 + 4.6e-5)  (gather8.hip: q = rint(x * RN(2^E / d)))
-        const float ea = 0.50003f * sa, eq = 1.00006f * eps_q8[p];
         (void)eps_a8;
-        // |s8 - a^.q^| <= ea*|q^|_1 + eq*|a^|_1 + C*ea*eq <= (ea + eq)*sqrt(C) + C*ea*eq   (+ fp32 accumulation slack of the exact scan)
-        const float delta = (ea + eq) * sqrt_c + c_true * ea * eq + 4e-5f;
-        margin = 2.0f * delta + 2e-7f;
-        valid_cut = cut0 - delta - 1e-6f;
-        if (!(delta < 0.2f)) { margin = INFINITY; valid_cut = -INFINITY; }     // degenerate scales: leave it to the fp16 pass
+        const ScreenBound b = i8_bound(sa, eps_q8[p], sqrt_c, c_true);
+        margin = b.margin();                                  // degenerate scales (not usable): +inf, -inf - left to the fp16 pass
+        valid_cut = b.usable() ? b.cannot_line(cut0) : -INFINITY;
     }
     if (lane == 0) m_final[arow] = m1;
     if (!(m1 >= valid_cut)) {
@@ -311,63 +303,20 @@ __global__ __launch_bounds__(256) void match_decide_kernel(const __half *__restr
         }
         return;
     }
-    // slice sid = (tile*NQB + qb)*2 + half: rows tile*ROWS + qb*32 + (r&3) + 8*(r>>2) + 4*half, r = 0..15
-    const int half = sid & 1, qb = (sid >> 1) % NQB, tile = (sid >> 1) / NQB;
-    const int r = lane >> 2, seg = lane & 3;                   // 4 lanes per row, each a quarter of K
-    const int q = tile * ROWS_TILE + qb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+    // the 16 rows of the winning slice re-scored by the wave (match_exact.h: 4 lanes per row), the hits become the candidates
+    const int seg = lane & 3;
+    const int q = slice_row(sid, lane >> 2);
     const int nq = n_q[p];
+    bool hit;
     if (a_scale8) {
-        // int8 mode: the slice is re-scored from the int8 rows (the very integers the screening pass accumulated, so the slice
-        // maximum reproduces m1 exactly); every row within the int8 margin of it goes to the exact fp32 re-scoring
-        int idot = 0;
-        if (q < nq) {
-            const uint4 *ar = reinterpret_cast<const uint4 *>(a8 + arow * Cp) + seg * (Cp / 64);
-            const uint4 *qr = reinterpret_cast<const uint4 *>(q8 + ((size_t)p * cap_q + q) * Cp) + seg * (Cp / 64);
-            for (int i0 = 0; i0 < Cp / 64; i0 += 4) {
-                uint4 av[4], qv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { av[u] = ar[i0 + u]; qv[u] = qr[i0 + u]; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    idot = __builtin_amdgcn_sdot4((int)av[u].x, (int)qv[u].x, idot, false);
-                    idot = __builtin_amdgcn_sdot4((int)av[u].y, (int)qv[u].y, idot, false);
-                    idot = __builtin_amdgcn_sdot4((int)av[u].z, (int)qv[u].z, idot, false);
-                    idot = __builtin_amdgcn_sdot4((int)av[u].w, (int)qv[u].w, idot, false);
-                }
-            }
-        }
-        idot += __shfl_xor(idot, 1);
-        idot += __shfl_xor(idot, 2);
-        const float s8 = (float)idot * q_scale8[(size_t)p * (cap_q / 16) + (sid >> 1) * 2 + half] * sa;
-        const bool hit8 = (seg == 0) && (q < nq) && (s8 >= m1 - margin);
-        const unsigned long long b8 = __ballot(hit8);
-        if (hit8) cand[arow * SCREEN_CAP + __popcll(b8 & ((1ull << lane) - 1ull))] = q;
-        if (lane == 0) cnt[arow] = __popcll(b8);
-        return;
+        // int8 mode: every row within the int8 margin of the slice maximum (= m1 exactly) goes to the exact fp32 re-scoring
+        const int idot = slice_score_i8(a8 + arow * Cp, q8 + (size_t)p * cap_q * Cp, q, Cp, q < nq);
+        const float s8 = (float)idot * q_scale8[(size_t)p * (cap_q / 16) + sid] * sa;
+        hit = (seg == 0) && (q < nq) && (s8 >= m1 - margin);
+    } else {
+        const float sdot = slice_score_f16(a16 + arow * Cp, q16 + (size_t)p * cap_q * Cp, q, Cp, q < nq);
+        hit = (seg == 0) && (q < nq) && (sdot >= m1 - SCREEN_MARGIN - 4e-5f);
     }
-    float sdot = 0.0f;
-    if (q < nq) {
-        const uint4 *ar = reinterpret_cast<const uint4 *>(a16 + arow * Cp) + seg * (Cp / 32);
-        const uint4 *qr = reinterpret_cast<const uint4 *>(q16 + ((size_t)p * cap_q + q) * Cp) + seg * (Cp / 32);
-        for (int i0 = 0; i0 < Cp / 32; i0 += 4) {
-            uint4 av[4], qv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { av[u] = ar[i0 + u]; qv[u] = qr[i0 + u]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const __half2 *ah = reinterpret_cast<const __half2 *>(&av[u]), *qh = reinterpret_cast<const __half2 *>(&qv[u]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float2 x = __half22float2(ah[e]), y = __half22float2(qh[e]);
-                    sdot = fmaf(x.x, y.x, sdot);
-                    sdot = fmaf(x.y, y.y, sdot);
-                }
-            }
-        }
-    }
-    sdot += __shfl_xor(sdot, 1);
-    sdot += __shfl_xor(sdot, 2);
-    const bool hit = (seg == 0) && (q < nq) && (sdot >= m1 - SCREEN_MARGIN - 4e-5f);
     const unsigned long long b = __ballot(hit);
     if (hit) cand[arow * SCREEN_CAP + __popcll(b & ((1ull << lane) - 1ull))] = q;
     if (lane == 0) cnt[arow] = __popcll(b);
@@ -401,6 +350,59 @@ __global__ __launch_bounds__(256) void match_compact_kernel(const __half *__rest
 // pass 2: L lanes per anchor row, candidates strided over them; canonical fp32 chain on the k-permuted fp32 rows.  Almost
 // every anchor has ONE candidate and the chain is a serial 256-step fmaf per (anchor, candidate): few lanes per anchor keep
 // more lanes of a wave busy.
+// The body of both entries, which differ in cand_dot(ar, jj): the canonical dot product of the anchor row at ar with query row jj.  CUT
+// (the fp16 screen): rows whose screening maximum screen_max(arow, a) lies below valid_cut are not re-scored; behind the int8 screen the
+// count -1 carries that and the maximum is read for the estimate only.  need_f32 (may be null): raised for the pair with an overflow.
+template <int L, bool CUT, class ScreenMax, class CandDot>
+__device__ __forceinline__ void rescore_rows(const float *__restrict__ a_hat, int Cp, int cap_a, const int32_t *__restrict__ n_a,
+                                             const int32_t *__restrict__ n_q, float thr, float valid_cut, const int32_t *__restrict__ cnt,
+                                             const int32_t *__restrict__ cand, float *__restrict__ min_dist, int32_t *__restrict__ argmin,
+                                             uint8_t *__restrict__ valid, uint8_t *__restrict__ row_flag, int32_t *__restrict__ panel_flag,
+                                             int32_t *__restrict__ need_f32, ScreenMax screen_max, CandDot cand_dot)
+{
+    const int p = blockIdx.y;
+    const int a = blockIdx.x * (256 / L) + (threadIdx.x / L), sub = threadIdx.x % L;
+    const bool live = a < n_a[p];
+    const size_t arow = (size_t)p * cap_a + (live ? a : 0);
+    float m16 = -INFINITY;
+    if (CUT && live) m16 = screen_max(arow, a);
+    const int c_raw = live ? cnt[arow] : 0;
+    const bool possible = live && (!CUT || m16 >= valid_cut) && c_raw >= 0;      // count -1: ruled out by the int8 stage
+    const int c = possible ? c_raw : 0;
+    const bool overflow = c > SCREEN_CAP;
+    float d = INFINITY;
+    int j = 0x7fffffff;
+    if (!overflow) {
+        const float *ar = a_hat + arow * Cp;
+        const int nq_p = n_q[p];
+        for (int ci = sub; ci < c; ci += L) {
+            const int jj = cand[arow * SCREEN_CAP + ci];
+            if (jj >= nq_p) continue;                     // zero-padded query rows can never be the answer
+            lex_min(d, j, dist_from_dot(cand_dot(ar, jj)), jj);
+        }
+    }
+#pragma unroll
+    for (int off = L / 2; off > 0; off >>= 1) {
+        const float od = __shfl_xor(d, off);
+        const int oj = __shfl_xor(j, off);
+        lex_min(d, j, od, oj);
+    }
+    if (!live || sub != 0) return;
+    if (!possible) {                    // cannot reach the threshold: report the screening estimate, valid = 0
+        min_dist[arow] = dist_from_dot(CUT ? m16 : screen_max(arow, a));
+        argmin[arow] = 0;
+        valid[arow] = 0;
+    } else if (overflow) {              // list overflow: the exact fp32 kernel recomputes this anchor's panel
+        row_flag[arow] = 1;
+        panel_flag[(size_t)p * (cap_a / ORYON_MATCH_TILE) + a / ORYON_MATCH_TILE] = 1;
+        if (need_f32) need_f32[p] = 1;
+    } else {
+        min_dist[arow] = d;
+        argmin[arow] = j;
+        valid[arow] = (d < thr) ? 1 : 0;
+    }
+}
+
 template <int L>
 __global__ __launch_bounds__(256) void match_rescore_kernel(const float *__restrict__ a_hat, const float *__restrict__ q_hat,
                                                              int Cp, int cap_a, int cap_q, const int32_t *__restrict__ n_a,
@@ -412,60 +414,25 @@ __global__ __launch_bounds__(256) void match_rescore_kernel(const float *__restr
                                                              uint8_t *__restrict__ row_flag, int32_t *__restrict__ panel_flag)
 {
     const int p = blockIdx.y;
-    const int a = blockIdx.x * (256 / L) + (threadIdx.x / L), sub = threadIdx.x % L;
-    const bool live = a < n_a[p];
-    const size_t arow = (size_t)p * cap_a + (live ? a : 0);
-    float m16 = -INFINITY;
-    if (live) {
-        if (m_final) m16 = m_final[arow];
-        else
+    rescore_rows<L, true>(
+        a_hat, Cp, cap_a, n_a, n_q, thr, valid_cut, cnt, cand, min_dist, argmin, valid, row_flag, panel_flag, nullptr,
+        [&](size_t arow, int a) {
+            if (m_final) return m_final[arow];
+            float m16 = -INFINITY;
             for (int s = 0; s < S; ++s) m16 = fmaxf(m16, ws_max[((size_t)p * S + s) * cap_a + a]);
-    }
-    const int c_raw = live ? cnt[arow] : 0;
-    const bool possible = live && (m16 >= valid_cut) && c_raw >= 0;      // count -1: ruled out by the int8 stage
-    const int c = possible ? c_raw : 0;
-    const bool overflow = c > SCREEN_CAP;
-    float d = INFINITY;
-    int j = 0x7fffffff;
-    if (!overflow) {
-        const float *ar = a_hat + arow * Cp;
-        const int nq_p = n_q[p];
-        for (int ci = sub; ci < c; ci += L) {
-            const int jj = cand[arow * SCREEN_CAP + ci];
-            if (jj >= nq_p) continue;                     // zero-padded query rows can never be the answer
+            return m16;
+        },
+        [&](const float *ar, int jj) {                    // materialised query rows, k-permuted like the anchors'
             const float *qr = q_hat + ((size_t)p * cap_q + jj) * Cp;
             float dot = 0.0f;
             for (int g = 0; g < Cp; g += 8) {
                 const float4 a0 = *reinterpret_cast<const float4 *>(ar + g), a1 = *reinterpret_cast<const float4 *>(ar + g + 4);
-                const float4 q0 = *reinterpret_cast<const float4 *>(qr + g), q1 = *reinterpret_cast<const float4 *>(qr + g + 4);
-                // positions 0..3 hold k = 8g+0,2,4,6 and 4..7 hold k = 8g+1,3,5,7: accumulate in natural k order
-                dot = __fmaf_rn(a0.x, q0.x, dot); dot = __fmaf_rn(a1.x, q1.x, dot);
-                dot = __fmaf_rn(a0.y, q0.y, dot); dot = __fmaf_rn(a1.y, q1.y, dot);
-                dot = __fmaf_rn(a0.z, q0.z, dot); dot = __fmaf_rn(a1.z, q1.z, dot);
-                dot = __fmaf_rn(a0.w, q0.w, dot); dot = __fmaf_rn(a1.w, q1.w, dot);
+                float x[8];
+                kperm_group_natural(*reinterpret_cast<const float4 *>(qr + g), *reinterpret_cast<const float4 *>(qr + g + 4), x);
+                dot = chain_step8(a0, a1, x, dot);
             }
-            lex_min(d, j, __fmaf_rn(-0.5f, dot, 0.5f), jj);
-        }
-    }
-#pragma unroll
-    for (int off = L / 2; off > 0; off >>= 1) {
-        const float od = __shfl_xor(d, off);
-        const int oj = __shfl_xor(j, off);
-        lex_min(d, j, od, oj);
-    }
-    if (!live || sub != 0) return;
-    if (!possible) {                    // cannot reach the threshold: report the screening estimate, valid = 0
-        min_dist[arow] = __fmaf_rn(-0.5f, m16, 0.5f);
-        argmin[arow] = 0;
-        valid[arow] = 0;
-    } else if (overflow) {              // list overflow: the exact fp32 kernel recomputes this anchor's panel
-        row_flag[arow] = 1;
-        panel_flag[(size_t)p * (cap_a / ORYON_MATCH_TILE) + a / ORYON_MATCH_TILE] = 1;
-    } else {
-        min_dist[arow] = d;
-        argmin[arow] = j;
-        valid[arow] = (d < thr) ? 1 : 0;
-    }
+            return dot;
+        });
 }
 
 // pass 2 for the K1s8 path fed by K0v3 (gather8.hip), which writes NO fp32 copy of the query rows: a candidate's canonical unit
@@ -482,27 +449,15 @@ __global__ __launch_bounds__(256) void match_rescore_raw_kernel(
     uint8_t *__restrict__ row_flag, int32_t *__restrict__ panel_flag, int32_t *__restrict__ need_f32, int round_f16)
 {
     const int p = blockIdx.y;
-    const int a = blockIdx.x * (256 / L) + (threadIdx.x / L), sub = threadIdx.x % L;
-    const bool live = a < n_a[p];
-    const size_t arow = (size_t)p * cap_a + (live ? a : 0);
-    const int c_raw = live ? cnt[arow] : 0;
-    const bool possible = live && c_raw >= 0;                 // count -1: ruled out by the int8 stage
-    const int c = possible ? c_raw : 0;
-    const bool overflow = c > SCREEN_CAP;
-    float d = INFINITY;
-    int j = 0x7fffffff;
-    if (!overflow) {
-        const float *ar = a_hat + arow * Cp;
-        const int nq_p = n_q[p];
-        const float *fq = feat_q + (size_t)p * C_true * HW;
-        for (int ci = sub; ci < c; ci += L) {
-            const int jj = cand[arow * SCREEN_CAP + ci];
-            if (jj >= nq_p) continue;
+    const float *fq = feat_q + (size_t)p * C_true * HW;
+    rescore_rows<L, false>(
+        a_hat, Cp, cap_a, n_a, n_q, thr, 0.0f, cnt, cand, min_dist, argmin, valid, row_flag, panel_flag, need_f32,
+        [&](size_t arow, int) { return m_final[arow]; },
+        [&](const float *ar, int jj) {
             const int pix = roi_q[(size_t)p * roi_stride + jj];
             const float dq = norm_q[(size_t)p * cap_q + jj];
             float dot = 0.0f;
             for (int g = 0; g < C_true; g += 8) {
-                // anchor positions 0..3 of a group hold k = 8g+0,2,4,6 and 4..7 hold k = 8g+1,3,5,7
                 const float4 a0 = *reinterpret_cast<const float4 *>(ar + g), a1 = *reinterpret_cast<const float4 *>(ar + g + 4);
                 float x[8];
                 if constexpr (NHWC) {
@@ -519,36 +474,12 @@ __global__ __launch_bounds__(256) void match_rescore_raw_kernel(
                     for (int e = 0; e < 8; ++e) x[e] = g + e < C_true ? fq[(size_t)(g + e) * HW + pix] : 0.0f;
                 }
 #pragma unroll
-                for (int e = 0; e < 8; ++e) x[e] = __fdiv_rn(round_f16 ? __half2float(__float2half_rn(x[e])) : x[e], dq);
-                dot = __fmaf_rn(a0.x, x[0], dot); dot = __fmaf_rn(a1.x, x[1], dot);
-                dot = __fmaf_rn(a0.y, x[2], dot); dot = __fmaf_rn(a1.y, x[3], dot);
-                dot = __fmaf_rn(a0.z, x[4], dot); dot = __fmaf_rn(a1.z, x[5], dot);
-                dot = __fmaf_rn(a0.w, x[6], dot); dot = __fmaf_rn(a1.w, x[7], dot);
+                for (int e = 0; e < 8; ++e) x[e] = unit_value(x[e], dq, round_f16);
+                dot = chain_step8(a0, a1, x, dot);
             }
             // channels C_true .. Cp-1 are zero on both sides: fma(0, 0, dot) leaves dot unchanged, nothing to add
-            lex_min(d, j, __fmaf_rn(-0.5f, dot, 0.5f), jj);
-        }
-    }
-#pragma unroll
-    for (int off = L / 2; off > 0; off >>= 1) {
-        const float od = __shfl_xor(d, off);
-        const int oj = __shfl_xor(j, off);
-        lex_min(d, j, od, oj);
-    }
-    if (!live || sub != 0) return;
-    if (!possible) {
-        min_dist[arow] = __fmaf_rn(-0.5f, m_final[arow], 0.5f);
-        argmin[arow] = 0;
-        valid[arow] = 0;
-    } else if (overflow) {
-        row_flag[arow] = 1;
-        panel_flag[(size_t)p * (cap_a / ORYON_MATCH_TILE) + a / ORYON_MATCH_TILE] = 1;
-        need_f32[p] = 1;
-    } else {
-        min_dist[arow] = d;
-        argmin[arow] = j;
-        valid[arow] = (d < thr) ? 1 : 0;
-    }
+            return dot;
+        });
 }
 
 // pairs that need materialised fp32 query rows: undecided anchors (fp16 stage) or an overflowed candidate list (exact panel scan)

@@ -1,5 +1,4 @@
 // Shared bits of the matcher translation units (match.hip, match16.hip, match_corrs.hip, screen_mx6.hip, match_x3.hip).
-// Where a comment elsewhere says resolve_anchor of match16.hip (screen_mx6.hip does): it lives in match_corrs.hip with the lazy tail.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <type_traits>

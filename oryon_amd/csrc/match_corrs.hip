@@ -4,6 +4,7 @@
 #include <hip/hip_fp16.h>
 #include "common.h"
 #include "match_common.h"
+#include "match_exact.h"
 
 // ------------------------------------------------------------------------------------------------ lazy tail: K1s8 -> sampled correspondences
 // The batched engine consumes the matcher through oryon_select_corrs only: it needs the VALID FLAG of every anchor and the argmin of the
@@ -32,41 +33,31 @@ __device__ __forceinline__ bool decide_lite_row(
     int32_t *__restrict__ ambu_idx, int32_t *__restrict__ need_f32_lazy)
 {
     const size_t arow = (size_t)p * cap_a + a;
-    float m1 = -INFINITY, m2 = -INFINITY;
-    int sid = 0;
-    for (int s = 0; s < S; ++s) {
-        const size_t o = ((size_t)p * S + s) * cap_a + a;
-        const float x1 = ws_m1[o], x2 = ws_m2[o];
-        m2 = fmaxf(fminf(m1, x1), fmaxf(m2, x2));
-        if (x1 > m1) { m1 = x1; sid = ws_i1[o]; }
-    }
-    float delta;
-    if (fmt == 1) {
-        // mx6 screen: scores are dequantised dot products; a_scale8 / eps_q8 hold the pair's largest measured row error |e|_2 of the
-        // anchor / query rows (K0, FMT = 1): |s6 - a^.q^| <= |ea| + |eq| + |ea||eq| + fp32 accumulation slack
-        const float ea = a_scale8[p], eq = eps_q8[p];
-        delta = ea + eq + ea * eq + 1.2e-4f;       // + fp32 accumulation of <= 512 products in the MFMA and in the canonical chain (<= 7e-5)
-    } else {
-        const float sa = a_scale8[(size_t)p * (cap_a / 16) + (a >> 5) * 2 + ((a >> 2) & 1)];
+    float m1, m2;
+    int sid;
+    merge_split_triples(ws_m1, ws_i1, ws_m2, p, S, cap_a, a, m1, sid, m2);
+    ScreenBound b;
+    if (fmt == 1) b = mx6_bound(a_scale8[p], eps_q8[p]);      // the pair's largest anchor / query row error
+    else {
+        const float sa = a_scale8[(size_t)p * (cap_a / 16) + anchor_scale_slot(a)];
         m1 *= sa;
         m2 *= sa;
-        const float ea = 0.50003f * sa, eq = 1.00006f * eps_q8[p];
-        delta = (ea + eq) * sqrt_c + c_true * ea * eq + 4e-5f;
+        b = i8_bound(sa, eps_q8[p], sqrt_c, c_true);
     }
-    const bool usable = delta < 0.2f;
-    const float margin = usable ? 2.0f * delta + 2e-7f : INFINITY;
+    const bool usable = b.usable();
+    const float margin = b.margin();
     m_final[arow] = m1;
     sid_final[arow] = sid;
     margin_out[arow] = margin;
     uint8_t st;
-    const bool certain_valid = usable && m1 > cut0 + delta + 1e-5f;
-    if (usable && !(m1 >= cut0 - delta - 1e-6f)) st = LZ_INVALID;
+    const bool certain_valid = usable && m1 > b.sure_line(cut0);
+    if (usable && !(m1 >= b.cannot_line(cut0))) st = LZ_INVALID;
     else if (!(m1 - m2 > margin)) st = certain_valid ? LZ_AMB_VALID : LZ_AMB_UNCERTAIN;
     else if (certain_valid) st = LZ_VALID;
     else st = LZ_UNCERTAIN;
     state[arow] = st;
     // provisional outputs: the distance is the screening estimate until (unless) the row is resolved exactly
-    min_dist[arow] = __fmaf_rn(-0.5f, m1, 0.5f);
+    min_dist[arow] = dist_from_dot(m1);
     argmin[arow] = 0;
     valid[arow] = (st == LZ_VALID || st == LZ_AMB_VALID) ? 1 : 0;
     if (force_eager) { pair_eager[p] = 1; return false; }
@@ -230,8 +221,15 @@ __global__ __launch_bounds__(256) void match_list_sampled_amb_kernel(int cap_a, 
 // the same kernel over all query tiles, and the (m1, slice, m2) triples merged back into the per-anchor arrays - a row whose winner turns
 // out unambiguous becomes LZ_VALID (resolved from its winning slice like any other), the others keep LZ_AMB_VALID with their true winning
 // slice as the second level's seed.
+// the line a partial maximum must exceed to settle its row as valid for sure (match_exact.h); a_err / q_err: K0's (FMT = 1) per pair
+__device__ __forceinline__ float dc_sure_line(const float *__restrict__ a_err, const float *__restrict__ q_err, int p, float cut0)
+{
+    const ScreenBound b = mx6_bound(a_err[p], q_err[p]);
+    return b.usable() ? b.settled_line(cut0) : INFINITY;
+}
+
 // after the windowed first launch: is every live anchor of a 1024-row panel valid for sure already (its best score over the splits' windows
-// above match_decide_lite_kernel's line)?  Then gate = 0 and its runner-ups read +inf (no margin: a partial scan rules nothing out);
+// above dc_sure_line)?  Then gate = 0 and its runner-ups read +inf (no margin: a partial scan rules nothing out);
 // otherwise gate = 1: the gated launch scans everything for this panel and overwrites the triples.
 __global__ __launch_bounds__(256) void match_panel_settle_kernel(int cap_a, int T8, int S, const int32_t *__restrict__ n_a,
                                                                   const float *__restrict__ ws_m1, float *__restrict__ ws_m2,
@@ -244,9 +242,7 @@ __global__ __launch_bounds__(256) void match_panel_settle_kernel(int cap_a, int 
     if (a0 >= na) return;
     if (t == 0) bad = 0;
     __syncthreads();
-    const float ea = a_err[p], eq = q_err[p];
-    const float delta = ea + eq + ea * eq + 1.2e-4f;
-    const float thr = delta < 0.2f ? cut0 + delta + 2e-5f : INFINITY;      // (match_decide_lite_kernel: m1 > cut0 + delta + 1e-5)
+    const float thr = dc_sure_line(a_err, q_err, p, cut0);
     int mine = 0;
     for (int a = a0 + t; a < a0 + 1024 && a < na; a += 256) {
         float m1 = -INFINITY;
@@ -301,24 +297,17 @@ __global__ __launch_bounds__(256) void match_decide_sampled_kernel(int cap_a, in
     if (sl == 0) count_before[p] = n;
     if (sl >= n) return;
     const int a = idx[(size_t)p * idx_stride + sl];
-    float m1 = -INFINITY, m2 = -INFINITY;
-    int sid = 0;
-    for (int s = 0; s < S; ++s) {
-        const size_t o = ((size_t)p * S + s) * cap_c + sl;
-        const float x1 = ws_m1[o], x2 = ws_m2[o];
-        m2 = fmaxf(fminf(m1, x1), fmaxf(m2, x2));
-        if (x1 > m1) { m1 = x1; sid = ws_i1[o]; }
-    }
-    const float ea = a_err[p], eq = q_err[p];
-    const float delta = ea + eq + ea * eq + 1.2e-4f;                  // match_decide_lite_kernel, fmt 1
-    const float margin = delta < 0.2f ? 2.0f * delta + 2e-7f : INFINITY;
+    float m1, m2;
+    int sid;
+    merge_split_triples(ws_m1, ws_i1, ws_m2, p, S, cap_c, sl, m1, sid, m2);
+    const float margin = mx6_bound(a_err[p], q_err[p]).margin();
     const size_t arow = (size_t)p * cap_a + a;
     m_final[arow] = m1;                                                // the complete scan's maximum (>= the partial one that settled validity)
     sid_final[arow] = sid;
     margin_out[arow] = margin;
     // default-route cascade: the provisional distance of a settled row came from its witness inside the band; the estimate a sampled
     // row reports is the complete scan's, as on the plain route
-    if (min_dist) min_dist[arow] = __fmaf_rn(-0.5f, m1, 0.5f);
+    if (min_dist) min_dist[arow] = dist_from_dot(m1);
     if (m1 - m2 > margin) {                                            // unambiguous after all: no second level for this row
         state[arow] = LZ_VALID;
         mark[arow] = 0;
@@ -333,35 +322,13 @@ __global__ __launch_bounds__(256) void match_decide_sampled_kernel(int cap_a, in
 // band pass settles the rows that find their witness there, and only the
 // rows left open (no counterpart at all, or a match outside the band) get the complete scan, compacted into dense 512-row panels.
 // A row is COMPLETE (true triple over all tiles: probe rows, rows of a panel whose band is "all tiles", open rows after their scan) or
-// SETTLED (partial maximum above match_decide_lite_kernel's line: valid for sure, m2 = +inf i.e. argmin open, as match_panel_settle_kernel
+// SETTLED (partial maximum above dc_sure_line: valid for sure, m2 = +inf i.e. argmin open, as match_panel_settle_kernel
 // leaves the rows of a settled panel).  Scores of an (anchor, query) pair do not depend on the panel the anchor row sits in, and the
 // merged triple not on how the tiles are dealt to splits (ties go to the lowest slice either way): complete triples are today's.
 constexpr uint8_t DC_COMPLETE = 0, DC_SETTLED = 1, DC_OPEN = 2;
 constexpr int DC_SLACK = 2;             // tiles added at either end of a learned band (ORYON_DC_SLACK in the dev build)
 constexpr int DC_MIN_SURE = 8;          // a panel with fewer valid-for-sure probe rows scans all tiles
 constexpr int DC_BAND_CAP_NUM = 1, DC_BAND_CAP_DEN = 2;     // ... and so does one whose band exceeds this share of the pair's tiles
-
-__device__ __forceinline__ float dc_sure_line(const float *__restrict__ a_err, const float *__restrict__ q_err, int p, float cut0)
-{
-    const float ea = a_err[p], eq = q_err[p];
-    const float delta = ea + eq + ea * eq + 1.2e-4f;
-    return delta < 0.2f ? cut0 + delta + 2e-5f : INFINITY;        // (match_decide_lite_kernel: m1 > cut0 + delta + 1e-5)
-}
-
-// merge of one row's per-split triples (the loop of match_decide_lite_kernel); element (split s, row r) at (p S + s) cap + r
-__device__ __forceinline__ void dc_merge(const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1, const float *__restrict__ ws_m2,
-                                         int p, int S, int cap, int r, float &m1, int &sid, float &m2)
-{
-    m1 = -INFINITY;
-    m2 = -INFINITY;
-    sid = 0;
-    for (int s = 0; s < S; ++s) {
-        const size_t o = ((size_t)p * S + s) * cap + r;
-        const float x1 = ws_m1[o], x2 = ws_m2[o];
-        m2 = fmaxf(fminf(m1, x1), fmaxf(m2, x2));
-        if (x1 > m1) { m1 = x1; sid = ws_i1[o]; }
-    }
-}
 
 // (the probe - rows 0, stride, 2 stride, .. of every pair - has no list: match_compact_rows_kernel's stride mode forms it and its count)
 
@@ -392,7 +359,7 @@ __global__ __launch_bounds__(256) void match_dc_probe_band_kernel(int cap_a, int
     for (int k = k_lo + t; k < k_hi; k += 256) {
         float m1, m2;
         int sid;
-        dc_merge(cs_m1, cs_i1, cs_m2, p, S, MX6_SAMPLED_PANEL, k, m1, sid, m2);
+        merge_split_triples(cs_m1, cs_i1, cs_m2, p, S, MX6_SAMPLED_PANEL, k, m1, sid, m2);
         const size_t arow = (size_t)p * cap_a + (size_t)k * stride;
         r_m1[arow] = m1;
         r_i1[arow] = sid;
@@ -453,7 +420,7 @@ __global__ __launch_bounds__(DC_SETTLE_THREADS) void match_dc_settle_rows_kernel
         if (a >= na) return;
         const int32_t *b = band + ((size_t)p * T8 * 2 + (a >> 9)) * 2;
         all = b[0] == 0 && b[1] == nqt;
-        dc_merge(ws_m1, ws_i1, ws_m2, p, S, cap_a, a, m1, sid, m2);
+        merge_split_triples(ws_m1, ws_i1, ws_m2, p, S, cap_a, a, m1, sid, m2);
     };
     float m1 = 0.0f, m2 = 0.0f, m1_n = 0.0f, m2_n = 0.0f;
     int sid = 0, sid_n = 0, base = 0, settled = 0;
@@ -511,7 +478,7 @@ __global__ __launch_bounds__(256) void match_dc_scatter_open_kernel(int cap_a, i
     if (sl >= n_open[p] || sl >= cap_a) return;
     float m1, m2;
     int sid;
-    dc_merge(ws_m1, ws_i1, ws_m2, p, S, cap_a, sl, m1, sid, m2);
+    merge_split_triples(ws_m1, ws_i1, ws_m2, p, S, cap_a, sl, m1, sid, m2);
     const size_t arow = (size_t)p * cap_a + open_idx[(size_t)p * cap_a + sl];
     r_m1[arow] = m1;
     r_i1[arow] = sid;
@@ -519,41 +486,16 @@ __global__ __launch_bounds__(256) void match_dc_scatter_open_kernel(int cap_a, i
 }
 
 // Exact resolution of ONE unambiguous anchor by one wave: candidates = rows of the winning 16-row slice within the int8 margin of its
-// maximum (re-scored from the int8 rows, as match_decide_kernel does), then the canonical fp32 chain per candidate on x_k / d read
-// from the raw map (as match_rescore_raw_kernel does).  Returns (distance, first index of the minimum) in lane 0.
-typedef float f32x32r __attribute__((ext_vector_type(32)));
-typedef unsigned u32x6r __attribute__((ext_vector_type(6)));
-
-// dequantised dot product of two mx6 slots (32 channels): codes decoded by the conversion instruction (exact: multiples of 1/8 up to
-// 7.5), 32 exact products summed in fp32 (every partial sum is a multiple of 1/64 below 2^11: exact), times both block exponents
-__device__ __forceinline__ float mx6_block_dot(const uint4 a_lo, const uint4 a_up, const uint4 q_lo, const uint4 q_up)
-{
-    const u32x6r ca = {a_lo.x, a_lo.y, a_lo.z, a_lo.w, a_up.x, a_up.y}, cq = {q_lo.x, q_lo.y, q_lo.z, q_lo.w, q_up.x, q_up.y};
-    const f32x32r fa = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(ca, 1.0f), fq = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(cq, 1.0f);
-    float sum = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) sum = __fmaf_rn(fa[i], fq[i], sum);
-    return sum * ldexpf(1.0f, (int)(a_up.z & 255u) + (int)(q_up.z & 255u) - 254);
-}
-
+// maximum (slice_score_* of match_exact.h on the screen's own operand rows), then the canonical fp32 chain per candidate on x_k / d read
+// from the raw map (wave_exact_dist).  Returns (distance, first index of the minimum) in lane 0.
 // Anchor rows on demand (the `_araw` entries): where K0 wrote no fp32 unit rows (a_hat == nullptr), a consumer forms the row itself from
-// the raw anchor map, exactly as K0 does - x_k at the anchor's pixel (rounded to float16 first under round_f16, zero beyond C_true),
-// divided by the norm K0 left in a_norm: __fdiv_rn(x_k, d), bit for bit the value K0 would have stored.
+// the raw anchor map with K0's norm in a_norm (match_exact.h: raw_unit), bit for bit the value K0 would have stored.
 struct AnchorRaw {
     const float *feat_a;        // [B, C_true, HW] (or channels-last), the map K0 gathered the anchors from
     const int32_t *roi_a;       // [B, roi_stride] pixel of every anchor row
     const float *a_norm;        // [B, cap_a] K0's row norms
     int roi_stride;
 };
-
-template <bool NHWC>
-__device__ __forceinline__ float anchor_raw_unit(const float *__restrict__ fa, int pix, float d, int k, int C_true, int HW, int round_f16)
-{
-    float x = 0.0f;
-    if (k < C_true) x = NHWC ? fa[(size_t)pix * C_true + k] : fa[(size_t)k * HW + pix];
-    if (round_f16) x = __half2float(__float2half_rn(x));
-    return __fdiv_rn(x, d);
-}
 
 template <bool NHWC, bool NEED_DIST = true, int FMT = 0>
 __device__ __forceinline__ void resolve_anchor(int p, int a, const float *__restrict__ a_hat, const AnchorRaw &araw, const int8_t *__restrict__ a8,
@@ -565,47 +507,22 @@ __device__ __forceinline__ void resolve_anchor(int p, int a, const float *__rest
 {
     const int lane = threadIdx.x & 63;
     const size_t arow = (size_t)p * cap_a + a;
-    const int half = sid & 1, blk = sid >> 1;
-    const int r = lane >> 2, seg = lane & 3;
-    const int q = blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+    const int seg = lane & 3;
+    const int q = slice_row(sid, lane >> 2);
     bool hit;
     if constexpr (FMT == 1) {
-        // mx6 rows: the 16 rows of the winning slice re-scored from the very operands the screen multiplied (software sum: the order of
-        // the additions differs from the MFMA's, inside the bound's slack); candidates = rows within the margin of the SLICE maximum
-        // (every exact minimiser lies in this slice and scores at least max - 2 delta)
-        float s6 = 0.0f;
-        if (q < nq) {
-            const uint4 *ar = reinterpret_cast<const uint4 *>(a8 + arow * Cp) + seg * (Cp / 64);
-            const uint4 *qr = reinterpret_cast<const uint4 *>(q8 + ((size_t)p * cap_q + q) * Cp) + seg * (Cp / 64);
-            for (int b = 0; b < Cp / 128; ++b) s6 += mx6_block_dot(ar[2 * b], ar[2 * b + 1], qr[2 * b], qr[2 * b + 1]);
-        }
-        s6 += __shfl_xor(s6, 1);
-        s6 += __shfl_xor(s6, 2);
+        // mx6 rows: candidates = rows within the margin of the SLICE maximum (every exact minimiser is one and scores >= max - 2 delta)
+        const float s6 = slice_score_mx6(a8 + arow * Cp, q8 + (size_t)p * cap_q * Cp, q, Cp, q < nq);
         float mx = (q < nq) ? s6 : -INFINITY;
-        mx = fmaxf(mx, __shfl_xor(mx, 4));
-        mx = fmaxf(mx, __shfl_xor(mx, 8));
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+#pragma unroll
+        for (int off = 4; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
         hit = (seg == 0) && (q < nq) && (s6 >= mx - margin - 4e-5f);
         (void)m1;
     } else {
-    const float sa = a_scale8[(size_t)p * (cap_a / 16) + (a >> 5) * 2 + ((a >> 2) & 1)];
-    int idot = 0;
-    if (q < nq) {
-        const uint4 *ar = reinterpret_cast<const uint4 *>(a8 + arow * Cp) + seg * (Cp / 64);
-        const uint4 *qr = reinterpret_cast<const uint4 *>(q8 + ((size_t)p * cap_q + q) * Cp) + seg * (Cp / 64);
-        for (int i0 = 0; i0 < Cp / 64; ++i0) {
-            const uint4 av = ar[i0], qv = qr[i0];
-            idot = __builtin_amdgcn_sdot4((int)av.x, (int)qv.x, idot, false);
-            idot = __builtin_amdgcn_sdot4((int)av.y, (int)qv.y, idot, false);
-            idot = __builtin_amdgcn_sdot4((int)av.z, (int)qv.z, idot, false);
-            idot = __builtin_amdgcn_sdot4((int)av.w, (int)qv.w, idot, false);
-        }
-    }
-    idot += __shfl_xor(idot, 1);
-    idot += __shfl_xor(idot, 2);
-    const float s8 = (float)idot * q_scale8[(size_t)p * (cap_q / 16) + sid] * sa;
-    hit = (seg == 0) && (q < nq) && (s8 >= m1 - margin);
+        const float sa = a_scale8[(size_t)p * (cap_a / 16) + anchor_scale_slot(a)];
+        const int idot = slice_score_i8(a8 + arow * Cp, q8 + (size_t)p * cap_q * Cp, q, Cp, q < nq);
+        const float s8 = (float)idot * q_scale8[(size_t)p * (cap_q / 16) + sid] * sa;
+        hit = (seg == 0) && (q < nq) && (s8 >= m1 - margin);
     }
     unsigned long long hits = __ballot(hit);
     if (!NEED_DIST && __popcll(hits) == 1) {
@@ -615,19 +532,16 @@ __device__ __forceinline__ void resolve_anchor(int p, int a, const float *__rest
         d_out = __builtin_nanf("");
         return;
     }
-    // anchor row (k-permuted: position 8g + 4h + j holds k = 8g + 2j + h) -> natural order in LDS
+    // anchor row (k-permuted) -> natural order in LDS
     float *A = lds, *Q = lds + Cp;
     if (a_hat) {
-        for (int pos = lane; pos < Cp; pos += 64) {
-            const int g = pos >> 3, hh = (pos >> 2) & 1, jj = pos & 3;
-            A[8 * g + 2 * jj + hh] = a_hat[arow * Cp + pos];
-        }
+        wave_unpermute_row(A, a_hat + arow * Cp, Cp);
     } else {
         // no materialised row: the same values from the raw map (one pass, Cp / 64 independent loads per lane), natural order as they come
         const float *fa = araw.feat_a + (size_t)p * C_true * HW;
         const int pix_a = araw.roi_a[(size_t)p * araw.roi_stride + a];
         const float da = araw.a_norm[arow];
-        for (int k = lane; k < Cp; k += 64) A[k] = anchor_raw_unit<NHWC>(fa, pix_a, da, k, C_true, HW, round_f16);
+        for (int k = lane; k < Cp; k += 64) A[k] = raw_unit<NHWC>(fa, pix_a, da, k, C_true, HW, round_f16);
     }
     float d = INFINITY;
     int j = 0x7fffffff;
@@ -638,34 +552,14 @@ __device__ __forceinline__ void resolve_anchor(int p, int a, const float *__rest
         const int jj = __shfl(q, src);
         const int pix = roi_q[(size_t)p * roi_stride + jj];
         const float dq = norm_q[(size_t)p * cap_q + jj];
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int k = lane; k < Cp; k += 64) {
-            float x = 0.0f;
-            if (k < C_true) x = NHWC ? fq[(size_t)pix * C_true + k] : fq[(size_t)k * HW + pix];
-            if (round_f16) x = __half2float(__float2half_rn(x));
-            Q[k] = __fdiv_rn(x, dq);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        float dot = 0.0f;                               // every lane runs the same chain on broadcast LDS reads
-        for (int k = 0; k < C_true; k += 8) {
-            float av[8], qv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { av[e] = A[k + e]; qv[e] = Q[k + e]; }
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                if (k + e < C_true) dot = __fmaf_rn(av[e], qv[e], dot);
-        }
-        lex_min(d, j, __fmaf_rn(-0.5f, dot, 0.5f), jj);
+        lex_min(d, j, wave_exact_dist<NHWC>(A, Q, fq, pix, dq, Cp, C_true, HW, round_f16), jj);
     }
     d_out = d;
     j_out = j;
 }
 
-// match_compact_f32_kernel for the `_araw` entries: the listed anchors' fp32 unit rows formed from the raw map (anchor_raw_unit) and
-// written in the k-permuted order K0's rows have (position 8g + 4h + j holds k = 8g + 2j + h), which is what K1 / K1x3 read.  One wave
+// match_compact_f32_kernel for the `_araw` entries: the listed anchors' fp32 unit rows formed from the raw map (raw_unit) and
+// written in the k-permuted order K0's rows have (match_exact.h: kperm_k), which is what K1 / K1x3 read.  One wave
 // per row, one 16-byte store per lane: lane i of a pass owns positions 4i .. 4i + 3 = (g, h) = (i >> 1, i & 1), j = 0 .. 3.
 template <bool NHWC>
 __global__ __launch_bounds__(256) void match_compact_raw_kernel(const AnchorRaw araw, int C_true, int HW, int round_f16, int Cp, int cap_a,
@@ -688,12 +582,12 @@ __global__ __launch_bounds__(256) void match_compact_raw_kernel(const AnchorRaw 
         const int pix = araw.roi_a[(size_t)p * araw.roi_stride + a];
         const float da = araw.a_norm[(size_t)p * cap_a + a];
         for (int i = lane; i < Cp / 4; i += 64) {
-            const int k0 = 8 * (i >> 1) + (i & 1);
+            const int g = i >> 1, hh = i & 1;
             float4 q;
-            q.x = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 0, C_true, HW, round_f16);
-            q.y = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 2, C_true, HW, round_f16);
-            q.z = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 4, C_true, HW, round_f16);
-            q.w = anchor_raw_unit<NHWC>(fa, pix, da, k0 + 6, C_true, HW, round_f16);
+            q.x = raw_unit<NHWC>(fa, pix, da, kperm_k(g, hh, 0), C_true, HW, round_f16);
+            q.y = raw_unit<NHWC>(fa, pix, da, kperm_k(g, hh, 1), C_true, HW, round_f16);
+            q.z = raw_unit<NHWC>(fa, pix, da, kperm_k(g, hh, 2), C_true, HW, round_f16);
+            q.w = raw_unit<NHWC>(fa, pix, da, kperm_k(g, hh, 3), C_true, HW, round_f16);
             d[i] = q;
         }
     }

@@ -28,6 +28,7 @@
 #include <type_traits>
 #include "common.h"
 #include "match_common.h"
+#include "match_exact.h"
 
 namespace oryon {
 
@@ -43,7 +44,7 @@ __host__ __device__ __forceinline__ size_t x3_q_off(int q, int b) { return (size
 constexpr int X3_JOB_TILES = 16;           // tiles per sweep-2 job (one reload of the 64 anchors' operands per job: 64 KB against 512 KB of tiles)
 constexpr int X3_SURV = 256;               // survivors of the first filter kept per anchor (more: exact-scan route)
 
-// fp32 anchor rows (k-permuted inside groups of 8: position 8g + 4h + j holds k = 8g + 2j + h) -> hi / lo half rows in natural k order
+// fp32 anchor rows (k-permuted inside groups of 8, match_exact.h) -> hi / lo half rows in natural k order
 // + al_norm [B, cap_s]: an upper bound of |lo|_2 of every row (Cp = 256: the 32 groups of a row are 32 consecutive lanes)
 __global__ __launch_bounds__(256) void match_x3_split_anchors_kernel(const float *__restrict__ a_c, int Cp, int cap_s,
                                                                       const int32_t *__restrict__ n_c, __half *__restrict__ ah,
@@ -63,8 +64,8 @@ __global__ __launch_bounds__(256) void match_x3_split_anchors_kernel(const float
             lo.u = make_uint4(0, 0, 0, 0);
         } else if (row < n) {
             const float4 *src = reinterpret_cast<const float4 *>(a_c + ((size_t)p * cap_s + row) * Cp) + 2 * gi;
-            const float4 x = src[0], y = src[1];                // x = k 8g+{0,2,4,6}, y = k 8g+{1,3,5,7}
-            const float v[8] = {x.x, y.x, x.y, y.y, x.z, y.z, x.w, y.w};
+            float v[8];
+            kperm_group_natural(src[0], src[1], v);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 hi.h[i] = __float2half_rn(v[i]);
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(256) void match_x3_split_anchors_kernel(const float
 }
 
 // Seed of the scan's running maxima (round 4): s_hi of the 16 query rows of the anchor's WINNING SLICE of the low-precision screen
-// (sid_final: slice (blk, half) = rows blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, r = 0..15).  On smooth fields the screen cannot tell
+// (sid_final; its rows: slice_row of match_exact.h).  On smooth fields the screen cannot tell
 // which row of the neighbourhood wins, but its winning slice sits at the peak: the best hi.hi score there is within ~1e-3 of the anchor's
 // true maximum.  It is the score of a real row, so it is a valid start for the running maximum of EVERY query split of the anchor:
 // sweep 1's tile flags (tested against the running maximum) then single out the few tiles around the peak from the first tile on instead
@@ -103,9 +104,8 @@ __global__ __launch_bounds__(256) void match_x3_seed_kernel(const __half *__rest
     if (row >= nc) return;
     const int nq = n_q[p];
     const int sid = sid_final[(size_t)p * cap_a + orig_idx[(size_t)p * orig_stride + row]];
-    const int half = sid & 1, blk = sid >> 1;
-    const int r = lane >> 2, seg = lane & 3;
-    const int q = blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+    const int seg = lane & 3;
+    const int q = slice_row(sid, lane >> 2);
     float s = 0.0f;
     if (q < nq && seg < kc) {                                   // (chunks beyond the map's channels are never written: zero by definition)
         const uint4 *ar = reinterpret_cast<const uint4 *>(ah + ((size_t)p * cap_s + row) * Cp) + seg * (Cp / 32);
@@ -664,7 +664,7 @@ __global__ __launch_bounds__(256, 1) void match_x3_sweep2_kernel(const __half *_
 }
 
 // one wave per compacted anchor: final maximum over the lists of all query splits, stale entries dropped, canonical fp32 chain on the raw
-// map for the rest (as resolve_anchor in match_corrs.hip), result -> md_c / am_c / va_c; overflowed lists -> the pair's overflow list
+// map for the rest (wave_exact_dist of match_exact.h, as resolve_anchor in match_corrs.hip), result -> md_c / am_c / va_c; overflowed lists -> the pair's overflow list
 template <bool NHWC>
 __global__ __launch_bounds__(256) void match_x3_rescore_kernel(const float *__restrict__ a_c, int Cp, int cap_s, const int32_t *__restrict__ n_c,
                                                                 const float *__restrict__ feat_q, int C_true, int HW,
@@ -707,10 +707,7 @@ __global__ __launch_bounds__(256) void match_x3_rescore_kernel(const float *__re
         if (lane == 0) ovf_idx[(size_t)p * cap_s + atomicAdd(&n_ovf[p], 1)] = row;
         return;
     }
-    for (int pos = lane; pos < Cp; pos += 64) {            // anchor row -> natural k order
-        const int g = pos >> 3, hh = (pos >> 2) & 1, jj = pos & 3;
-        A[8 * g + 2 * jj + hh] = a_c[crow * Cp + pos];
-    }
+    wave_unpermute_row(A, a_c + crow * Cp, Cp);            // anchor row -> natural k order
     // second filter: entries within MARGIN3 of the best listed s3 get a REFINED score from the hi / lo rows - the exact products
     // (ah + al)(qh + ql) summed in fp64 - which is within DELTA_R = 1.63e-5 of the canonical fp32 chain (256 roundings of the chain:
     // 1.53e-5; split residuals, lo parts being subnormal halves: 9.6e-7; the score's own rounding to float), a quarter of the s3 bound
@@ -775,31 +772,9 @@ __global__ __launch_bounds__(256) void match_x3_rescore_kernel(const float *__re
     for (int i = 0; i < ns; ++i) {
         if (!(sref[i] >= ref_max - X3_MARGIN_R)) continue;  // wave-uniform (LDS broadcast)
         const int jj = sj[i];
-        {
-            const int pix = roi_q[(size_t)p * roi_stride + jj];
-            const float dq = norm_q[(size_t)p * cap_q + jj];
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            for (int k = lane; k < Cp; k += 64) {
-                float x = 0.0f;
-                if (k < C_true) x = NHWC ? fq[(size_t)pix * C_true + k] : fq[(size_t)k * HW + pix];
-                if (round_f16) x = __half2float(__float2half_rn(x));
-                Q[k] = __fdiv_rn(x, dq);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            float dot = 0.0f;                               // every lane runs the same canonical chain on broadcast LDS reads
-            for (int k = 0; k < C_true; k += 8) {
-                float av[8], qv[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { av[e] = A[k + e]; qv[e] = Q[k + e]; }
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if (k + e < C_true) dot = __fmaf_rn(av[e], qv[e], dot);
-            }
-            lex_min(d, j, __fmaf_rn(-0.5f, dot, 0.5f), jj);
-        }
+        const int pix = roi_q[(size_t)p * roi_stride + jj];
+        const float dq = norm_q[(size_t)p * cap_q + jj];
+        lex_min(d, j, wave_exact_dist<NHWC>(A, Q, fq, pix, dq, Cp, C_true, HW, round_f16), jj);
     }
     if (lane == 0) {
         md_c[crow] = d;

@@ -5,6 +5,7 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 #include "common.h"
+#include "match_exact.h"
 
 namespace oryon {
 
@@ -224,13 +225,13 @@ __global__ __launch_bounds__(GN_ROWS) void gather_normalise_kernel(const float *
         for (int i = 0; i < (GN_ROWS * GN_KT / 4) / GN_ROWS; ++i) {
             const int fidx = t + GN_ROWS * i;
             const int r = fidx / (GN_KT / 4), c4 = fidx % (GN_KT / 4);
-            // k-permuted row layout consumed by K1: position 8g + 4h + j holds k = 8g + 2j + h  (c4 = 2g + h)
-            const int kb = 8 * (c4 >> 1) + (c4 & 1);
+            // k-permuted row layout consumed by K1 (match_exact.h: kperm_k), c4 = 2g + h
+            const int kg = c4 >> 1, kh = c4 & 1;
             float4 v;
-            v.x = tile[r * (GN_KT + 1) + kb + 0];
-            v.y = tile[r * (GN_KT + 1) + kb + 2];
-            v.z = tile[r * (GN_KT + 1) + kb + 4];
-            v.w = tile[r * (GN_KT + 1) + kb + 6];
+            v.x = tile[r * (GN_KT + 1) + kperm_k(kg, kh, 0)];
+            v.y = tile[r * (GN_KT + 1) + kperm_k(kg, kh, 1)];
+            v.z = tile[r * (GN_KT + 1) + kperm_k(kg, kh, 2)];
+            v.w = tile[r * (GN_KT + 1) + kperm_k(kg, kh, 3)];
             *reinterpret_cast<float4 *>(o + (size_t)r * Cp + k0 + c4 * 4) = v;
         }
         if (out16) {
@@ -320,13 +321,13 @@ __global__ __launch_bounds__(256) void gather_normalise_v2_kernel(const float *_
     for (int rg = wave % NRG; rg < NRG; rg += 4) {
         const int r = rg * 8 + (lane >> 3), c4 = lane & 7;
         const float d = sd[r];
-        const int kb = 8 * (c4 >> 1) + (c4 & 1);
+        const int kg = c4 >> 1, kh = c4 & 1;        // the chunk's (g, h) of the k-permuted format (match_exact.h)
         for (int k0 = 32 * (wave / NRG); k0 < Cp; k0 += 32 * KSPLIT) {
             float4 q;
-            q.x = __fdiv_rn(raw[(k0 + kb + 0) * LD + r], d);
-            q.y = __fdiv_rn(raw[(k0 + kb + 2) * LD + r], d);
-            q.z = __fdiv_rn(raw[(k0 + kb + 4) * LD + r], d);
-            q.w = __fdiv_rn(raw[(k0 + kb + 6) * LD + r], d);
+            q.x = __fdiv_rn(raw[(k0 + kperm_k(kg, kh, 0)) * LD + r], d);
+            q.y = __fdiv_rn(raw[(k0 + kperm_k(kg, kh, 1)) * LD + r], d);
+            q.z = __fdiv_rn(raw[(k0 + kperm_k(kg, kh, 2)) * LD + r], d);
+            q.w = __fdiv_rn(raw[(k0 + kperm_k(kg, kh, 3)) * LD + r], d);
             *reinterpret_cast<float4 *>(o + (size_t)r * Cp + k0 + c4 * 4) = q;
         }
     }
@@ -426,18 +427,18 @@ __global__ __launch_bounds__(256) void gather_normalise_q8_kernel(const float *_
     {
         const int r = wave * 8 + (lane >> 3), c4 = lane & 7;
         const float d = sd[r];
-        const int kb = 8 * (c4 >> 1) + (c4 & 1);
+        const int kg = c4 >> 1, kh = c4 & 1;        // the chunk's (g, h) of the k-permuted format (match_exact.h)
         float mx = 0.0f;
         for (int k0 = 0; k0 < Cp; k0 += 32) {
             float4 q;
-            q.x = __fdiv_rn(raw[(k0 + kb + 0) * LD + r], d);
-            q.y = __fdiv_rn(raw[(k0 + kb + 2) * LD + r], d);
-            q.z = __fdiv_rn(raw[(k0 + kb + 4) * LD + r], d);
-            q.w = __fdiv_rn(raw[(k0 + kb + 6) * LD + r], d);
-            raw[(k0 + kb + 0) * LD + r] = q.x;
-            raw[(k0 + kb + 2) * LD + r] = q.y;
-            raw[(k0 + kb + 4) * LD + r] = q.z;
-            raw[(k0 + kb + 6) * LD + r] = q.w;
+            q.x = __fdiv_rn(raw[(k0 + kperm_k(kg, kh, 0)) * LD + r], d);
+            q.y = __fdiv_rn(raw[(k0 + kperm_k(kg, kh, 1)) * LD + r], d);
+            q.z = __fdiv_rn(raw[(k0 + kperm_k(kg, kh, 2)) * LD + r], d);
+            q.w = __fdiv_rn(raw[(k0 + kperm_k(kg, kh, 3)) * LD + r], d);
+            raw[(k0 + kperm_k(kg, kh, 0)) * LD + r] = q.x;
+            raw[(k0 + kperm_k(kg, kh, 1)) * LD + r] = q.y;
+            raw[(k0 + kperm_k(kg, kh, 2)) * LD + r] = q.z;
+            raw[(k0 + kperm_k(kg, kh, 3)) * LD + r] = q.w;
             mx = fmaxf(fmaxf(mx, fmaxf(fabsf(q.x), fabsf(q.y))), fmaxf(fabsf(q.z), fabsf(q.w)));
             *reinterpret_cast<float4 *>(o + (size_t)r * Cp + k0 + c4 * 4) = q;
         }

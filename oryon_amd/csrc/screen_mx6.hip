@@ -4,7 +4,8 @@
 // that push match_mx6_screen_w4_kernel<256, 8> from 246 VGPRs to 52 spilled registers (266 MB of scratch writes per launch in the
 // WRITE_SIZE counter, +12 % time).  No NaN can occur here: fp6 e2m3 has no NaN / Inf codes, the E8M0 exponents K0 writes are finite
 // (dead rows of a tile are zero rows with exponent byte 0), and a garbage anchor row beyond the pair's count only feeds its own,
-// ignored, output column.  match16.hip, which uses a NaN as a marker (resolve_anchor), keeps the default semantics.
+// ignored, output column.  The decision side keeps the default semantics (match_corrs.hip's resolve_anchor uses a NaN as a marker, and
+// match_exact.h's merges rely on fmaxf / fminf of infinities): match_exact.h is not included here.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>

@@ -348,7 +348,8 @@ def gather_normalise(feat: torch.Tensor, roi: torch.Tensor, count: torch.Tensor,
 
 def unpermute_k(x: torch.Tensor) -> torch.Tensor:
     """K0 stores every descriptor row with k permuted inside groups of 8 (position 8g+4h+j holds k = 8g+2j+h, the order
-    the MFMA A/B operands consume 16-byte chunks in).  Returns the rows in natural k order (tests / debugging only)."""
+    the MFMA A/B operands consume 16-byte chunks in; the format's definition is kperm_k in csrc/match_exact.h).  Returns the rows in
+    natural k order (tests / debugging only)."""
     Cp = x.shape[-1]
     pos = torch.arange(Cp, device=x.device)
     g, r = pos // 8, pos % 8

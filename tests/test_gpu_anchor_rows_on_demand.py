@@ -269,3 +269,45 @@ def test_variants(variant):
     fa, fq, ma, mq = _stack(_mixed(64, C, "cuda"))
     res, _ = _old_vs_new(fa, fq, ma, mq, 256, ("mx6", "i8", "x3"), channels_last=variant == "channels_last", round_f16=variant == "round_f16")
     assert int(res["mx6"][1][1]) > 100 and int(res["mx6"][1][2]) > 0                  # the smooth and the near-duplicate pair were ambiguous
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("C,channels_last,round_f16", [(100, False, False), (100, True, True), (36, True, False)])
+def test_entries_vs_c_oracle_at_odd_widths(C, channels_last, round_f16):
+    """Widths that are no multiple of 8, where the canonical chain's k + e < C predicate and the channels-last tail are live: every route's
+    `_araw` entry (equal to the a_hat entry inside _old_vs_new) against the C oracle's exact scan of the same ROI rows - an independent
+    chain, which the old-against-new comparison above is not.  Every anchor row and every sampled row is checked."""
+    import numpy as np
+    from oracle import c_oracle
+    from oryon_amd import ops
+    H, n_corrs = 48, 256
+    pairs = _mixed(H, C, "cuda")
+    fa, fq, ma, mq = _stack(pairs)
+    res, (roi_a, na, W) = _old_vs_new(fa, fq, ma, mq, 256, ("mx6", "i8", "x3"), max_corrs=n_corrs, channels_last=channels_last,
+                                      round_f16=round_f16)
+    roi_q, nq = ops.roi_compact(mq)
+    roi_a, roi_q, na, nq = roi_a.cpu().numpy(), roi_q.cpu().numpy(), na.tolist(), nq.tolist()
+    # under round_f16 the entries round the raw values to float16 first: the oracle gets the maps rounded to half and back
+    as_seen = (lambda x: x.half().float()) if round_f16 else (lambda x: x)
+    ref = [c_oracle.match_lin(as_seen(fa[b]).cpu().numpy(), as_seen(fq[b]).cpu().numpy(), roi_a[b, : na[b]], roi_q[b, : nq[b]], 0.25)
+           for b in range(len(pairs))]
+    for route in ("mx6", "i8", "x3"):
+        (corrs, n_valid, n_sel, status, md, am, va), und = res[route]
+        corrs, md, am, va = corrs.cpu().numpy().astype(np.int64), md.cpu().numpy(), am.cpu().numpy(), va.cpu().numpy()
+        assert n_sel.tolist() == [n_corrs] * len(pairs) and status.tolist() == [0] * len(pairs), (route, n_sel.tolist(), status.tolist())
+        for b, (md0, am0, va0) in enumerate(ref):
+            n, what = na[b], f"{route}, pair {b}"
+            assert np.array_equal(va[b, :n].astype(bool), va0.astype(bool)), f"{what}: valid set differs from the C oracle"
+            assert int(n_valid[b]) == int(va0.sum()), what
+            lin_a = corrs[b, :n_corrs, 0] * W + corrs[b, :n_corrs, 1]
+            row = np.searchsorted(roi_a[b, :n], lin_a)
+            assert np.array_equal(roi_a[b, :n][row], lin_a), f"{what}: a sampled anchor pixel is not in the anchor ROI"
+            assert np.array_equal(am[b, row], am0[row]), f"{what}: argmin of a sampled row differs from the oracle"
+            assert np.array_equal(corrs[b, :n_corrs, 2] * W + corrs[b, :n_corrs, 3], roi_q[b, : nq[b]][am0[row]]), \
+                f"{what}: a sampled correspondence's query pixel is not the oracle's argmin"
+            # exact, or (rows the bound settled alone carry the screen's estimate) within the screens' bound of the truth: the rule of
+            # _check_pair in test_gpu_default_route_vs_oracle.py
+            exact = md[b, row].view(np.uint32) == md0[row].view(np.uint32)
+            assert np.all(exact | (np.abs(md[b, row] - md0[row]) < 0.05)), f"{what}: min_dist of a sampled row is off"
+        if route != "i8":
+            assert int(und[1]) > 0, f"{route}: the smooth pair had nothing for the second level"
