@@ -451,6 +451,49 @@ int oryon_ransac_register(const float *src, const float *tgt, const int32_t *n, 
                           int32_t *exited, int32_t *counts, int32_t *status_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Spectral pose solver (test.solver = spectral): no weights, no random numbers.  PointDSC's learned confidence and neighbour lists are
+ *         replaced by spectral matching on the spatial-compatibility matrix and by second-order spatial compatibility (SC^2, Chen et
+ *         al., CVPR 2022); seeds, per-seed power iteration, weighted Kabsch, scoring and refinement are PointDSC's kernels.  The
+ *         definition, stage by stage (S1-S9), is the header comment of csrc/spectral.hip; in short, per pair:
+ *         C_ij = | |s_i - s_j| - |t_i - t_j| | < inlier_threshold in float64 (bit-packed, zero diagonal); conf = the iterate after
+ *         EXACTLY num_iterations steps v <- M v / (|M v| + 1e-6) from v = 1, M_ij = max(0, 1 - (|s_i - s_j| - |t_i - t_j|)^2 / sigma_d^2)
+ *         in fp32 (no early exit: the bits do not depend on a near-tie); NMS seeds on conf, S = int(n ratio); the set of seed s = s, then
+ *         the k' - 1 rows j != s of the highest C_sj popcount(row_s & row_j), ties by ascending j, k' = min(k, n - 1); the k' x k' matrix
+ *         of M between its members; then PointDSC's hypotheses and its refinement with tau = inlier_threshold.
+ * The defaults below are object-scale (metres) and come from one synthetic experiment (planted motions of a 0.3 m cube of points, 1 mm
+ *         noise, 50-90 % outliers), not from real data.
+ * No allocation, no synchronisation, no float atomics; every output is the same bytes in every run, batch position and stream. */
+typedef struct {
+    int num_iterations;     /* 10 (1..16): power-iteration steps of the confidence (exact) and cap of the per-seed iteration */
+    float ratio;            /* 0.1: seeds = int(n * ratio) */
+    float inlier_threshold; /* 0.01 */
+    float sigma_d;          /* 0.01 */
+    int k;                  /* 40 (2..63) */
+    float nms_radius;       /* 0.02 */
+} oryon_spectral_config_t;
+/* 0 for unsupported shapes; supported: B >= 1, n_cap % 128 == 0, n_cap <= 2048, 2 <= k <= 63, 1 <= num_iterations <= 16 (and
+ * 0 < ratio <= 1, positive thresholds). */
+size_t oryon_spectral_workspace_bytes(const oryon_spectral_config_t *cfg, int B, int n_cap);
+/* The contract of oryon_pointdsc_register: src,tgt [B,n_cap,3] fp32 metres (rows >= n[b] are never read); n [B] int32; status_in [B] or
+ * NULL: pairs with a non-zero status get the identity and pass the status on; a pair without a seed (int(n ratio) == 0) or with n < 2
+ * gets the identity and ORYON_PAIR_NO_CORR.  T [B,16] fp32, labels [B,n_cap] uint8 or NULL (inliers of the best hypothesis),
+ * status_out [B] or NULL. */
+int oryon_spectral_register(const oryon_spectral_config_t *cfg, const float *src, const float *tgt, const int32_t *n, int B, int n_cap,
+                            const int32_t *status_in, void *workspace, size_t workspace_bytes, float *T, uint8_t *labels,
+                            int32_t *status_out, void *stream);
+/* The same kernels with every intermediate as an optional output (NULL = not wanted), S_cap = int(n_cap ratio) + 1:
+ *   compat [B,n_cap,n_cap/32] uint32 (bit j & 31 of word j >> 5 of row i); conf [B,n_cap] (rows >= n: 0); seeds [B,S_cap], n_seeds [B];
+ *   sets [B,S_cap,k] (entries >= k': -1); scores [B,S_cap,n_cap] int32 (0 at the seed and at columns >= n); Mmat [B,S_cap,k,k] (zero
+ *   outside k' x k'); close [B,S_cap,num_iterations] int32: the per-seed closeness flags of the power iteration (the hypotheses use
+ *   the first iteration at which every seed of the pair is close, else the last); seed_T [B,S_cap,16], fitness [B,S_cap], best [B]
+ *   (-1: no seed), T0 [B,16] (the best hypothesis, before the refinement), T [B,16], status_out [B].  Of the per-seed outputs (seeds,
+ *   sets, scores, Mmat, close, seed_T, fitness) only the first n_seeds[b] entries of pair b are specified. */
+int oryon_spectral_stages(const oryon_spectral_config_t *cfg, const float *src, const float *tgt, const int32_t *n, int B, int n_cap,
+                          const int32_t *status_in, void *workspace, size_t workspace_bytes, uint32_t *compat, float *conf,
+                          int32_t *seeds, int32_t *n_seeds, int32_t *sets, int32_t *scores, float *Mmat, int32_t *close, float *seed_T,
+                          float *fitness, int32_t *best, float *T0, float *T, int32_t *status_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Validation step: the contrastive terms of FeatureLoss.forward (losses.py:64-141) for B pairs in three launches, no allocation, no
  *         synchronisation, no float atomics (every output is bit-stable across runs, streams and batch shapes).  fp32 throughout, as the
  *         reference runs on the CPU; cosine in the matcher's form (rows / max(|x|, 1e-8), then a dot product).

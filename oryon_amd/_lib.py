@@ -44,6 +44,12 @@ class PointDSCConfig(ctypes.Structure):
                 ("nms_radius", c_float)]
 
 
+class SpectralConfig(ctypes.Structure):
+    """oryon_spectral_config_t (include/oryon_hip.h); the defaults are object-scale, from one synthetic experiment (csrc/spectral.hip)."""
+    _fields_ = [("num_iterations", c_int), ("ratio", c_float), ("inlier_threshold", c_float), ("sigma_d", c_float), ("k", c_int),
+                ("nms_radius", c_float)]
+
+
 _P = c_void_p
 _PROTOS = {
     "oryon_version": (c_char_p, []),
@@ -160,6 +166,10 @@ _PROTOS = {
     "oryon_ransac_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "oryon_ransac_register": (c_int, [_P, _P, _P, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, _P, c_uint64, _P, _P, _P, c_size_t,
                                       _P, _P, _P, _P, _P, _P]),
+    "oryon_spectral_workspace_bytes": (c_size_t, [POINTER(SpectralConfig), c_int, c_int]),
+    "oryon_spectral_register": (c_int, [POINTER(SpectralConfig), _P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P, _P, _P, _P]),
+    "oryon_spectral_stages": (c_int, [POINTER(SpectralConfig), _P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P, _P, _P, _P, _P, _P, _P, _P,
+                                      _P, _P, _P, _P, _P, _P, _P]),
     "oryon_feature_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "oryon_feature_loss": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, c_int, c_float, c_float, c_float, _P, c_size_t,
                                    _P, _P, _P, _P, _P, _P]),

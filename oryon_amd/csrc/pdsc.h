@@ -110,4 +110,13 @@ int pdsc_run_refine(const PdscModel &M, const float *src, const float *tgt, cons
                     const float *T_in, const int32_t *status_in, const int32_t *n_seeds, float *T_out, int32_t *status_out,
                     hipStream_t st);
 
+// the stages behind a (neighbour list [B,S_cap,k], matrix [B,S_cap,k,k]) pair per seed, callable on their own (spectral.hip):
+// power iteration + weighted Kabsch / fitness + first-argmax (v_hist [B,S_cap,16,64], close_hist [B,S_cap,16]), and the refinement
+// with the caller's tau
+int pdsc_run_tail(const float *src, const float *tgt, const int32_t *n_rows, const int32_t *n_seeds, int B, int n_cap, int S_cap, int k,
+                  int num_iterations, float inlier_thr, const int32_t *knn, const float *Mmat, float *v_hist, int32_t *close_hist,
+                  float *seed_T, float *fitness, int32_t *best, float *T_best, uint8_t *labels, hipStream_t st);
+int pdsc_run_refine_tau(const float *src, const float *tgt, const int32_t *n_rows, int B, int n_cap, float tau, const float *T_in,
+                        const int32_t *status_in, const int32_t *n_seeds, float *T_out, int32_t *status_out, hipStream_t st);
+
 }  // namespace oryon

@@ -945,6 +945,21 @@ int pdsc_run_seeds(const PdscModel &M, const float *src, const float *conf, cons
     return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
 }
 
+// K7b + K8 + K9 on their own: everything behind a (neighbour list, k x k matrix) pair per seed depends on nothing learned, so the
+// spectral solver (spectral.hip) runs the same three launches on its own lists and matrices.
+int pdsc_run_tail(const float *src, const float *tgt, const int32_t *n_rows, const int32_t *n_seeds, int B, int n_cap, int S_cap, int k,
+                  int num_iterations, float inlier_thr, const int32_t *knn, const float *Mmat, float *v_hist, int32_t *close_hist,
+                  float *seed_T, float *fitness, int32_t *best, float *T_best, uint8_t *labels, hipStream_t st)
+{
+    const int nit = num_iterations < HYP_MAX_IT ? num_iterations : HYP_MAX_IT;
+    hipLaunchKernelGGL(pdsc_power_kernel, dim3(S_cap, B), dim3(64), 0, st, n_rows, n_seeds, S_cap, k, nit, Mmat, v_hist, close_hist);
+    hipLaunchKernelGGL(pdsc_seed_solve_kernel, dim3(S_cap, B), dim3(64), 0, st, src, tgt, n_rows, n_cap, n_seeds, S_cap, k, nit,
+                       inlier_thr, knn, v_hist, close_hist, seed_T, fitness);
+    hipLaunchKernelGGL(pdsc_seed_select_kernel, dim3(B), dim3(256), 0, st, src, tgt, n_rows, n_cap, n_seeds, S_cap, inlier_thr,
+                       seed_T, fitness, best, T_best, labels);
+    return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
+}
+
 int pdsc_run_hypotheses(const PdscModel &M, const PdscWorkspace &ws, const float *src, const float *tgt, const float *feat_n,
                         const int32_t *n_rows, const int32_t *seeds, const int32_t *n_seeds, int B, int n_cap, float *seed_T,
                         float *fitness, int32_t *best, float *T_best, uint8_t *labels, hipStream_t st)
@@ -976,7 +991,6 @@ int pdsc_run_hypotheses(const PdscModel &M, const PdscWorkspace &ws, const float
             hipLaunchKernelGGL(pdsc_hyp_fused_kernel<4>, grid, dim3(256), shf, st, feat_n, src, tgt, n_rows, n_cap, ws.seed_dist, n_seeds, S_cap, k,
                                1.0f / (M.sigma * M.sigma), 1.0f / (M.sigma_d * M.sigma_d), ws.knn, ws.Mmat, B);
         if (hipGetLastError() != hipSuccess) return ORYON_ERR_HIP;
-        hipLaunchKernelGGL(pdsc_power_kernel, dim3(S_cap, B), dim3(64), 0, st, n_rows, n_seeds, S_cap, k, nit, ws.Mmat, ws.v_hist, ws.close_hist);
     } else {
     const float *dist_pre = nullptr;
     if (C == 128 && (size_t)S_cap * 128 * sizeof(float) <= 64 * 1024) {
@@ -998,13 +1012,9 @@ int pdsc_run_hypotheses(const PdscModel &M, const PdscWorkspace &ws, const float
     hipLaunchKernelGGL(pdsc_knn_matrix_kernel, dim3(S_cap, (B + 7) / 8 * 8), dim3(256), sh1, st, feat_n, src, tgt, n_rows, n_cap, C, seeds,
                        n_seeds, S_cap, k, 1.0f / (M.sigma * M.sigma), 1.0f / (M.sigma_d * M.sigma_d), ws.knn, ws.Mmat, dist_pre, B);
     if (hipGetLastError() != hipSuccess) return ORYON_ERR_HIP;
-    hipLaunchKernelGGL(pdsc_power_kernel, dim3(S_cap, B), dim3(64), 0, st, n_rows, n_seeds, S_cap, k, nit, ws.Mmat, ws.v_hist, ws.close_hist);
     }
-    hipLaunchKernelGGL(pdsc_seed_solve_kernel, dim3(S_cap, B), dim3(64), 0, st, src, tgt, n_rows, n_cap, n_seeds, S_cap, k, nit,
-                       M.cfg.inlier_threshold, ws.knn, ws.v_hist, ws.close_hist, seed_T, fitness);
-    hipLaunchKernelGGL(pdsc_seed_select_kernel, dim3(B), dim3(256), 0, st, src, tgt, n_rows, n_cap, n_seeds, S_cap, M.cfg.inlier_threshold,
-                       seed_T, fitness, best, T_best, labels);
-    return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
+    return pdsc_run_tail(src, tgt, n_rows, n_seeds, B, n_cap, S_cap, k, nit, M.cfg.inlier_threshold, ws.knn, ws.Mmat, ws.v_hist, ws.close_hist,
+                         seed_T, fitness, best, T_best, labels, st);
 }
 
 int pdsc_run_refine(const PdscModel &M, const float *src, const float *tgt, const int32_t *n_rows, int B, int n_cap,
@@ -1012,6 +1022,12 @@ int pdsc_run_refine(const PdscModel &M, const float *src, const float *tgt, cons
                     hipStream_t st)
 {
     const float tau = (M.cfg.inlier_threshold == 0.10f) ? 0.10f : 1.2f;   // PointDSC.py:415-418
+    return pdsc_run_refine_tau(src, tgt, n_rows, B, n_cap, tau, T_in, status_in, n_seeds, T_out, status_out, st);
+}
+
+int pdsc_run_refine_tau(const float *src, const float *tgt, const int32_t *n_rows, int B, int n_cap, float tau, const float *T_in,
+                        const int32_t *status_in, const int32_t *n_seeds, float *T_out, int32_t *status_out, hipStream_t st)
+{
     hipLaunchKernelGGL(pdsc_refine_kernel, dim3(B), dim3(256), 0, st, src, tgt, n_rows, n_cap, tau, T_in, status_in, n_seeds,
                        T_out, status_out);
     return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;

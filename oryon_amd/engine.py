@@ -25,7 +25,7 @@ from ._lib import check, lib
 from .pointdsc import PointDSC
 
 PAIR_OK, PAIR_NO_MASK, PAIR_NO_CORR = 0, 1, 2
-SOLVERS = ("pointdsc", "ransac")
+SOLVERS = ("pointdsc", "ransac", "spectral")
 _default_solver = "pointdsc"
 
 
@@ -69,10 +69,20 @@ class MatchPoseConfig:
     ransac_max_iter: int = 10000
     ransac_match_err: float = 0.001
     ransac_fix_percent: float = 0.9999
+    # "spectral" (csrc/spectral.hip): spectral matching + second-order spatial compatibility in front of PointDSC's hypothesis and
+    # refinement kernels - no weights (solver=None is accepted), no random numbers.  The fields of oryon_spectral_config_t; the three
+    # lengths are object-scale defaults chosen from one synthetic experiment, not from real data.  It runs on the per-call schedule
+    # (the native C step engine does not know it yet).
+    spectral_num_iterations: int = 10
+    spectral_ratio: float = 0.1
+    spectral_inlier_threshold: float = 0.01
+    spectral_sigma_d: float = 0.01
+    spectral_k: int = 40
+    spectral_nms_radius: float = 0.02
 
 
 def _check_solver(cfg: "MatchPoseConfig", solver) -> bool:
-    """True for the RANSAC solver; a PointDSC model is required by the other one only."""
+    """True for the RANSAC solver; a PointDSC model is required by 'pointdsc' only ('ransac' and 'spectral' need no weights)."""
     if cfg.solver not in SOLVERS:
         raise ValueError(f"Solver {cfg.solver} not implemented")
     if cfg.solver == "pointdsc" and solver is None:
@@ -80,10 +90,22 @@ def _check_solver(cfg: "MatchPoseConfig", solver) -> bool:
     return cfg.solver == "ransac"
 
 
+def _f32(x: float) -> float:
+    """x rounded through float32: what a C configuration struct carries."""
+    return ctypes.c_float(x).value
+
+
+def _spectral_cfg(cfg: "MatchPoseConfig") -> Dict[str, float]:
+    """The spectral_* fields as ops.spectral_register takes them, the floats rounded through float32 (as the RANSAC thresholds are)."""
+    return dict(num_iterations=int(cfg.spectral_num_iterations), ratio=_f32(cfg.spectral_ratio),
+                inlier_threshold=_f32(cfg.spectral_inlier_threshold), sigma_d=_f32(cfg.spectral_sigma_d), k=int(cfg.spectral_k),
+                nms_radius=_f32(cfg.spectral_nms_radius))
+
+
 def _cfg_sig(cfg: "MatchPoseConfig", overlap: int) -> Tuple:
     """What a NativeStep bakes into its C engine: a change of any of these rebuilds it."""
     return (cfg.dist_th, cfg.n_corrs, cfg.src_sampling, cfg.seed, cfg.half_descriptors, overlap, int(cfg.sample_first), cfg.solver,
-            cfg.ransac_max_iter, cfg.ransac_match_err, cfg.ransac_fix_percent)
+            cfg.ransac_max_iter, cfg.ransac_match_err, cfg.ransac_fix_percent) + tuple(_spectral_cfg(cfg).values())
 
 
 class NativeStep:
@@ -113,6 +135,8 @@ class NativeStep:
             from . import configure
             configure()                 # no-op when the host program configured the process; warns when HIP started with too few queues
         ransac = _check_solver(cfg, solver)
+        if cfg.solver == "spectral":
+            raise ValueError("the native step engine has no spectral solver: MatchPoseEngine.run takes the per-call schedule for it")
         if not ransac:
             solver._ensure_handle(dev)
         self._solver = solver                                   # keeps the C handle alive
@@ -418,6 +442,9 @@ class MatchPoseEngine:
             out = ops.ransac_register(pcd_a, pcd_q, n_lift, cfg.ransac_max_iter, f32(cfg.ransac_match_err), f32(cfg.ransac_fix_percent), None,
                                       cfg.seed, pair_key, status)
             return out["T"], out["status"]
+        if cfg.solver == "spectral":
+            out = ops.spectral_register(pcd_a, pcd_q, n_lift, status, **_spectral_cfg(cfg))
+            return out["T"], out["status"]
         pose, _, status_out = self.solver.register(pcd_a, pcd_q, n_lift, status, ws_slot=ws_slot)
         return pose, status_out
 
@@ -517,7 +544,7 @@ class MatchPoseEngine:
         # the native step engine serves every width up to 512 on the screened route (narrow maps zero-padded to 256 channels by K0);
         # the per-call schedule below keeps its own choice per width (exact scan for C <= 64, fp16 screen for C <= 128)
         native_ok = cfg.match_mode == "screened" and C <= 512 and 0.0 < cfg.dist_th <= 0.5 and (use_i8 or C <= 128)
-        if native_ok and self.native:
+        if native_ok and self.native and cfg.solver != "spectral":       # the C step engine does not know the spectral solver
             return self._run_native(feat_a, feat_q, mask_a, mask_q, depth_a, depth_q, cam_a, cam_q, pair_key, keep, inputs_event,
                                     inputs_resident, dev)
         if pair_key is None:

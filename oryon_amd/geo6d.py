@@ -6,7 +6,8 @@
 The arithmetic runs in liboryon_hip.so (csrc/ransac.hip: every hypothesis of a call is scored in ONE launch); this module only
 moves the arrays and keeps numpy's global generator where the reference leaves it.  `icp` and `best_fit_transform_icp` run in
 csrc/icp.hip (ops.icp_refine: float64 throughout, the clouds need not be of equal length); `icp_point_to_plane`, which the reference
-does not have, runs point-to-plane ICP of a cloud onto a depth map (csrc/icp_plane.hip, ops.icp_plane_refine).  The points are handed to the kernel as
+does not have, runs point-to-plane ICP of a cloud onto a depth map (csrc/icp_plane.hip, ops.icp_plane_refine); `spectral_pose`, which
+the reference does not have either, is the per-sample facade of the spectral solver (csrc/spectral.hip).  The points are handed to the kernel as
 float32 (what pipeline.py:459-463 passes); fits and the inlier test are float64, as numpy computes them for float64 input.
 """
 from __future__ import annotations
@@ -79,6 +80,25 @@ def best_fit_transform_with_RANSAC(A, B, max_iter=20, match_err=0.015, fix_perce
         if k > 0:
             np.random.randint(0, n, (k, 4))
     return out["T"][0, :3, :].double().cpu().numpy()
+
+
+def spectral_pose(pcd_a, pcd_q, device="cuda", **cfg) -> torch.Tensor:
+    """The per-sample facade of the spectral solver (test.solver = spectral), shaped like pointdsc.get_pointdsc_pose: pcd_a, pcd_q
+    [N,3] corresponding points (metres) -> [4,4] fp32 on the CPU.  No weights, no random numbers (csrc/spectral.hip); cfg: the fields of
+    oryon_spectral_config_t, whose defaults (ops.SPECTRAL_DEFAULTS) are object-scale and come from a synthetic experiment only.  Fewer
+    than int(1 / ratio) points give no seed: the identity, as the batched route reports with ORYON_PAIR_NO_CORR."""
+    A, B = _as_points(pcd_a), _as_points(pcd_q)
+    assert A.shape == B.shape
+    n = A.shape[0]
+    if n > MAX_ROWS:
+        raise ValueError(f"at most {MAX_ROWS} correspondences per call ({n} given)")
+    n_cap = ops.round_up(max(n, 1), 128)
+    src = torch.zeros((1, n_cap, 3), dtype=torch.float32, device=device)
+    tgt = torch.zeros((1, n_cap, 3), dtype=torch.float32, device=device)
+    src[0, :n] = torch.from_numpy(np.ascontiguousarray(A, dtype=np.float32))
+    tgt[0, :n] = torch.from_numpy(np.ascontiguousarray(B, dtype=np.float32))
+    out = ops.spectral_register(src, tgt, torch.tensor([n], dtype=torch.int32, device=device), **cfg)
+    return out["T"][0].cpu()
 
 
 def _cloud(x: np.ndarray, device) -> torch.Tensor:

@@ -715,6 +715,75 @@ def ransac_register(src: torch.Tensor, tgt: torch.Tensor, n: torch.Tensor, max_i
     return dict(T=T, winner=winner, exited=exited, status=st_out, counts=counts)
 
 
+# oryon_spectral_config_t's defaults: object-scale (metres), chosen from one synthetic experiment, not from real data (csrc/spectral.hip)
+SPECTRAL_DEFAULTS = dict(num_iterations=10, ratio=0.1, inlier_threshold=0.01, sigma_d=0.01, k=40, nms_radius=0.02)
+
+
+def spectral_config(**cfg) -> "_lib.SpectralConfig":
+    unknown = set(cfg) - set(SPECTRAL_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown spectral solver option(s): {sorted(unknown)}")
+    c = dict(SPECTRAL_DEFAULTS, **cfg)
+    return _lib.SpectralConfig(num_iterations=int(c["num_iterations"]), ratio=float(c["ratio"]), inlier_threshold=float(c["inlier_threshold"]),
+                               sigma_d=float(c["sigma_d"]), k=int(c["k"]), nms_radius=float(c["nms_radius"]))
+
+
+def _spectral_args(src, tgt, n, status, workspace, cfg):
+    dev = _lib.require_gpu(src.device)
+    assert src.dtype == torch.float32 and tgt.dtype == torch.float32 and src.shape == tgt.shape and src.dim() == 3 and src.shape[2] == 3
+    assert n.dtype == torch.int32 and (status is None or status.dtype == torch.int32)
+    B, n_cap = src.shape[0], src.shape[1]
+    c = spectral_config(**cfg)
+    need = lib().oryon_spectral_workspace_bytes(ctypes.byref(c), B, n_cap)
+    if need == 0 and B > 0:
+        raise _lib.OryonError(f"oryon_spectral_workspace_bytes(B={B}, n_cap={n_cap}): shape or configuration not supported "
+                              "(n_cap % 128 == 0, n_cap <= 2048, 2 <= k <= 63, 1 <= num_iterations <= 16)")
+    ws = workspace if workspace is not None else torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    return dev, B, n_cap, c, ws
+
+
+@_on_tensor_device
+def spectral_register(src: torch.Tensor, tgt: torch.Tensor, n: torch.Tensor, status: Optional[torch.Tensor] = None,
+                      want_labels: bool = False, workspace: Optional[torch.Tensor] = None, **cfg):
+    """src, tgt [B,n_cap,3] fp32 (metres; n_cap a multiple of 128, <= 2048), n [B] int32 -> dict(T [B,4,4], status [B],
+    labels [B,n_cap] uint8 | None).  cfg: the fields of oryon_spectral_config_t (SPECTRAL_DEFAULTS).  No weights, no random numbers;
+    definition: csrc/spectral.hip."""
+    dev, B, n_cap, c, ws = _spectral_args(src, tgt, n, status, workspace, cfg)
+    T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+    st_out = torch.empty((B,), dtype=torch.int32, device=dev)
+    labels = torch.empty((B, n_cap), dtype=torch.uint8, device=dev) if want_labels else None
+    check(lib().oryon_spectral_register(ctypes.byref(c), ptr(src), ptr(tgt), ptr(n), B, n_cap, ptr(status), ptr(ws), ws.numel(), ptr(T),
+                                        ptr(labels), ptr(st_out), stream_ptr(dev)), "oryon_spectral_register")
+    return dict(T=T, status=st_out, labels=labels)
+
+
+SPECTRAL_STAGES = ("compat", "conf", "seeds", "n_seeds", "sets", "scores", "Mmat", "close", "seed_T", "fitness", "best", "T0", "T", "status")
+
+
+@_on_tensor_device
+def spectral_stages(src: torch.Tensor, tgt: torch.Tensor, n: torch.Tensor, status: Optional[torch.Tensor] = None,
+                    out: Optional[dict] = None, workspace: Optional[torch.Tensor] = None, **cfg):
+    """oryon_spectral_stages: the kernels of spectral_register with every intermediate returned (shapes: include/oryon_hip.h).
+    out: name -> caller's buffer for any of SPECTRAL_STAGES (contiguous, the stage's dtype and shape); the rest are allocated."""
+    dev, B, n_cap, c, ws = _spectral_args(src, tgt, n, status, workspace, cfg)
+    S_cap, k, nit = int(float(n_cap) * float(c.ratio)) + 1, c.k, c.num_iterations
+    i32, f32 = torch.int32, torch.float32
+    spec = dict(compat=(i32, (B, n_cap, n_cap // 32)), conf=(f32, (B, n_cap)), seeds=(i32, (B, S_cap)), n_seeds=(i32, (B,)),
+                sets=(i32, (B, S_cap, k)), scores=(i32, (B, S_cap, n_cap)), Mmat=(f32, (B, S_cap, k, k)), close=(i32, (B, S_cap, nit)),
+                seed_T=(f32, (B, S_cap, 4, 4)), fitness=(f32, (B, S_cap)), best=(i32, (B,)), T0=(f32, (B, 4, 4)), T=(f32, (B, 4, 4)),
+                status=(i32, (B,)))
+    r = {}
+    for name, (dt, shape) in spec.items():
+        t = (out or {}).get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device=dev)
+        assert t.dtype == dt and tuple(t.shape) == shape, name
+        r[name] = t
+    check(lib().oryon_spectral_stages(ctypes.byref(c), ptr(src), ptr(tgt), ptr(n), B, n_cap, ptr(status), ptr(ws), ws.numel(),
+                                      *(ptr(r[k_]) for k_ in SPECTRAL_STAGES), stream_ptr(dev)), "oryon_spectral_stages")
+    return r
+
+
 @_on_tensor_device
 def feature_loss(feat_a: torch.Tensor, feat_q: torch.Tensor, corrs: torch.Tensor, valid: torch.Tensor, pool: Optional[torch.Tensor] = None,
                  pos_margin: float = 0.2, neg_margin: float = 0.9, neg_kernel: float = 5.0, pool_per_positive: bool = False,

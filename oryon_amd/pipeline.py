@@ -30,6 +30,7 @@ names of configs/config.yaml.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
@@ -39,8 +40,8 @@ import torch
 from torch import Tensor
 
 from . import _lib, ops
-from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK, PAIR_OK, default_solver
-from .geo6d import best_fit_transform_with_RANSAC
+from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK, PAIR_OK, SOLVERS, default_solver
+from .geo6d import best_fit_transform_with_RANSAC, spectral_pose
 from .pcd import nn_correspondences
 from .pointdsc import PointDSC, get_pointdsc_pose
 
@@ -75,7 +76,11 @@ def default_args(**overrides) -> SimpleNamespace:
         dataset=SimpleNamespace(img_size=[224, 224], max_corrs=500),
         model=SimpleNamespace(image_encoder=SimpleNamespace(img_size=[192, 192], out_channels=32)),
         test=SimpleNamespace(mask="predicted", src_sampling=5000, solver=default_solver(), n_corrs=500, dist_th=0.25,
-                             mask_threshold=0.5),
+                             mask_threshold=0.5,
+                             # test.solver = spectral (csrc/spectral.hip; the reference has no counterpart): the fields of
+                             # oryon_spectral_config_t.  Object-scale lengths chosen from one synthetic experiment, not from real data
+                             spectral_num_iterations=10, spectral_ratio=0.1, spectral_inlier_threshold=0.01, spectral_sigma_d=0.01,
+                             spectral_k=40, spectral_nms_radius=0.02),
         loss=SimpleNamespace(hard_negatives=True, pos_margin=0.2, neg_margin=0.9, neg_kernel_size=5, mask_type="dice",
                              w={"mask": 1.0, "pos": 0.5, "neg": 0.5}),
         optimization=SimpleNamespace(optim_type="Adam", scheduler_type="cosine", lr=0.001, momentum=0.0, w_decay=0.0005, gamma=0.1),
@@ -112,7 +117,7 @@ def mask_iou(gt: Tensor, pred: Tensor) -> Tensor:
 
 class Pipeline:
     def __init__(self, args: SimpleNamespace, model=None, pointdsc_solver: Optional[PointDSC] = None):
-        """pointdsc_solver may be None with test.solver = 'ransac' (the solver that needs no pretrained weights).
+        """pointdsc_solver may be None with test.solver = 'ransac' or 'spectral' (the solvers that need no pretrained weights).
         The solver is a property of the pipeline, read from args.test.solver HERE: `pointdsc_solver` is handed in for it, and the
         batched engine bakes it into its arena and registration stream.  The reference reads the flag at every call; this class has
         always refused `args.test.solver = "ransac"` set on a pipeline that was built for PointDSC (the suite pins that), and still
@@ -282,7 +287,7 @@ class Pipeline:
         camera_a = batch["anchor"]["camera"][idx].reshape(1, 9).to(torch.float32).to(dev)
         camera_q = batch["query"]["camera"][idx].reshape(1, 9).to(torch.float32).to(dev)
         HO, WO = self.args.model.image_encoder.img_size
-        if self.args.test.solver not in ("pointdsc", "ransac"):
+        if self.args.test.solver not in SOLVERS:
             raise RuntimeError(f"Solver {self.args.test.solver} not implemented")
         if self.args.test.solver != self.solver:
             raise RuntimeError(f"test.solver was changed from '{self.solver}' to '{self.args.test.solver}' after this Pipeline was built: "
@@ -297,6 +302,8 @@ class Pipeline:
             pose4 = np.eye(4)
             pose4[:3, :] = pose
             pose4 = torch.tensor(pose4)
+        elif self.args.test.solver == "spectral":
+            pose4 = spectral_pose(pcd_a[0, :m], pcd_q[0, :m], dev, **self._spectral_cfg())
         else:
             pose4 = get_pointdsc_pose(self.pointdsc_solver, pcd_a[0, :m], pcd_q[0, :m], self.device)
         if self.refine_mode() != "none":
@@ -307,6 +314,15 @@ class Pipeline:
             self.last_refine = self.refine_poses(pose4.to(torch.float32)[None].to(dev), None, clouds)
             return self.last_refine["T"][0].cpu()
         return pose4.to(torch.float32)
+
+    _SPECTRAL_FIELDS = ("num_iterations", "ratio", "inlier_threshold", "sigma_d", "k", "nms_radius")
+
+    def _spectral_cfg(self) -> Dict[str, float]:
+        """test.spectral_* (absent = the defaults of MatchPoseConfig) under the names of oryon_spectral_config_t, the floats rounded
+        through float32 as the engine carries them: both routes hand the kernels the same numbers."""
+        d = MatchPoseConfig(solver="spectral")
+        vals = {f: getattr(self.args.test, "spectral_" + f, getattr(d, "spectral_" + f)) for f in self._SPECTRAL_FIELDS}
+        return {f: (int(v) if f in ("num_iterations", "k") else ctypes.c_float(float(v)).value) for f, v in vals.items()}
 
     # ------------------------------------------------------------------ pipeline.py:490-497
     def add_pred_pose(self, id_a: str, id_q: str, mask_a_iou, mask_q_iou, pred_pose: np.ndarray) -> str:
@@ -403,7 +419,8 @@ class Pipeline:
         if self._engine is None:
             self._engine = MatchPoseEngine(self.pointdsc_solver, MatchPoseConfig(
                 dist_th=self.args.test.dist_th, n_corrs=self.args.test.n_corrs, src_sampling=self.args.test.src_sampling,
-                seed=self.args.seed if self.args.seed is not None else 1, solver=self.solver))
+                seed=self.args.seed if self.args.seed is not None else 1, solver=self.solver,
+                **{"spectral_" + f: v for f, v in self._spectral_cfg().items()}))
 
         def stack(x):
             return (torch.stack([d.squeeze() for d in x]) if isinstance(x, (list, tuple)) else x).to(dev, torch.float32).contiguous()

@@ -5,11 +5,16 @@
     python run_pose.py --solver ransac --pairs 8 --batch 4
     python run_pose.py --solver ransac --data-root /data --dataset nocs --ckpt ... --bpe ...       # no --pointdsc snapshot needed
 
-`--solver {pointdsc,ransac}` (default pointdsc) becomes the process-wide default solver (oryon_amd.engine.set_default_solver): every
+`--solver {pointdsc,ransac,spectral}` (default pointdsc) becomes the process-wide default solver (oryon_amd.engine.set_default_solver): every
 `default_args()` and `MatchPoseConfig()` that run_test.py builds - the per-sample loop, the batched engine, its --half-descriptors
 engine - then selects it.  Everything else goes to run_test.py unchanged.  With `ransac` (best_fit_transform_with_RANSAC,
 utils/geo6d.py:75-120, max_iter=10000, fix_percent=0.9999, match_err=0.001 as pipeline.py:463) no PointDSC weights take part in a pose.
 
+With `spectral` (csrc/spectral.hip: spectral matching and second-order spatial compatibility in front of PointDSC's hypothesis and
+refinement kernels) no weights and no random numbers take part either; its thresholds (test.spectral_*) are object-scale defaults
+chosen on synthetic data only.
+
+    python run_pose.py --solver spectral --pairs 8 --batch 4
     python run_pose.py --solver ransac --refine icp --pairs 8
 
 `--refine {none,icp,icp_plane}` (default none; test.refine) becomes the process-wide default refinement (oryon_amd.pipeline.set_default_refine),
@@ -47,8 +52,9 @@ def take_refine(argv=None):
 def parse(argv=None):
     """-> (solver, the arguments left for run_test.py).  `--refine` is checked and taken out as well (take_refine returns it)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
-    ap.add_argument("--solver", choices=["pointdsc", "ransac"], default="pointdsc",
-                    help="test.solver: PointDSC registration, or best_fit_transform_with_RANSAC (needs no PointDSC weights)")
+    ap.add_argument("--solver", choices=["pointdsc", "ransac", "spectral"], default="pointdsc",
+                    help="test.solver: PointDSC registration, best_fit_transform_with_RANSAC, or the spectral solver (the last two need no "
+                         "PointDSC weights)")
     ap.add_argument("--refine", choices=REFINE_CHOICES, default="none", help="test.refine: ICP refinement of every solved pose (see above)")
     ap.add_argument("-h", "--help", action="store_true")
     a, rest = ap.parse_known_args(argv)
