@@ -539,10 +539,20 @@ extern "C" int oryon_engine_submit(oryon_engine_t *e, const float *feat_a, const
     const int ablate = e->n_submit >= (int64_t)(c.n_slots + c.gather_sets) ? ablate_env : 0;
     // ---- K0 on the gather stream
     if (timing) ORYON_CHECK_HIP(hipEventRecord(tev[0], sg));
-    if ((rc = oryon_roi_compact(mask_a, B, HW, b.roi_a, b.n_a, sg))) return rc;
-    if ((rc = oryon_roi_compact(mask_q, B, HW, b.roi_q, b.n_q, sg))) return rc;
-    if (c.src_sampling > 0 && (rc = oryon_roi_subsample(b.roi_a, b.n_a, B, HW, c.src_sampling, c.seed, pair_key, sg))) return rc;
     const bool mx6 = c.screen == 1 && !force_eager;           // the eager route (complete min_dist / argmin arrays) keeps the int8 operands
+    // both mask sets in one launch; on the MX-fp6 route its workgroups also clear the per-map error norms that this step's two gathers
+    // raise with atomic maxima (the anchors' under sample-first are those of the first-stage subset), so the gathers are issued without a
+    // fill of their own.  Every wait of the gather stream for the last reader of this buffer set is already queued above.
+    {
+        const bool clear = mx6 && !(ablate & 1);              // an ablated K0 leaves the stale operands AND their norms
+        const bool sf_k0 = e->L.cap_a1 > 0 && !force_eager;
+        if ((rc = roi_compact_pair_launch(mask_a, mask_q, B, HW, b.roi_a, b.roi_q, b.n_a, b.n_q, clear ? (sf_k0 ? g.a_eps_1 : g.a_eps) : nullptr,
+                                          clear ? g.q_eps : nullptr, sg))) {
+            set_error("oryon_engine_submit: roi_compact launch failed");
+            return rc;
+        }
+    }
+    if (c.src_sampling > 0 && (rc = oryon_roi_subsample(b.roi_a, b.n_a, B, HW, c.src_sampling, c.seed, pair_key, sg))) return rc;
     // "sample first" (cfg.sample_first = N, oryon_sample_first_gate): the matcher first sees a uniformly random N-anchor subset of every pair
     // (second-level device-RNG subsample, row order kept); only pairs whose subset holds fewer than n_corrs valid rows are redone on all
     // anchors - gated on the device, so the second K0 pass and the second matcher call see zero anchors for every other pair
@@ -589,10 +599,11 @@ extern "C" int oryon_engine_submit(oryon_engine_t *e, const float *feat_a, const
                                           g.q_eps, g.q_norm, g.q_hilo, g.q_lo_max, c.round_f16, sg))) return rc;
             e->n_x3 += 1;
         } else
-        if ((rc = oryon_gather_mx6(feat_q, B, c.C, HW, c.layout, b.roi_q, HW, b.n_q, e->L.cap_q, e->L.c_pad, reinterpret_cast<uint8_t *>(g.q8),
-                                   g.q_eps, g.q_norm, nullptr, c.round_f16, sg))) return rc;
-        if ((rc = oryon_gather_mx6(feat_a, B, c.C, HW, c.layout, roi_a_k0, HW, n_a_k0, cap_a_k0, e->L.c_pad, reinterpret_cast<uint8_t *>(a8_k0),
-                                   a_eps_k0, a_norm_k0, a_hat_k0, c.round_f16, sg))) return rc;
+        if ((rc = gather_mx6_prezeroed(feat_q, B, c.C, HW, c.layout, b.roi_q, HW, b.n_q, e->L.cap_q, e->L.c_pad, reinterpret_cast<uint8_t *>(g.q8),
+                                       g.q_eps, g.q_norm, nullptr, c.round_f16, sg))) return rc;
+        // (g.q_eps and a_eps_k0 were cleared by this step's roi_compact launch)
+        if ((rc = gather_mx6_prezeroed(feat_a, B, c.C, HW, c.layout, roi_a_k0, HW, n_a_k0, cap_a_k0, e->L.c_pad, reinterpret_cast<uint8_t *>(a8_k0),
+                                       a_eps_k0, a_norm_k0, a_hat_k0, c.round_f16, sg))) return rc;
     } else {
     if ((rc = oryon_gather_q8(feat_q, B, c.C, HW, c.layout, b.roi_q, HW, b.n_q, e->L.cap_q, e->L.c_pad, g.q8, g.q_sc, g.q_eps, g.q_norm,
                               nullptr, c.round_f16, sg))) return rc;

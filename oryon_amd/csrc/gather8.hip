@@ -25,6 +25,7 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 #include "common.h"
+#include "match_common.h"
 #include "match_exact.h"
 
 namespace oryon {
@@ -859,13 +860,29 @@ extern "C" int oryon_gather_mx6(const float *feat, int n_maps, int C, int HW, in
     ORYON_CHECK_ARG(rows_cap > 0 && rows_cap % 256 == 0 && (size_t)C * (size_t)HW * 4u < (1ull << 32));
     if (n_maps == 0) return ORYON_OK;
     hipStream_t st = as_stream(stream);
+    // the public entry clears err_max itself: its callers give no guarantee about the words' contents
     ORYON_CHECK_HIP(hipMemsetAsync(err_max, 0, (size_t)n_maps * sizeof(float), st));
+    return gather_mx6_prezeroed(feat, n_maps, C, HW, layout, roi, roi_stride, count, rows_cap, C_pad, out_mx6, err_max, row_norm, out_f32,
+                                round_f16, st);
+}
+
+namespace oryon {
+int gather_mx6_prezeroed(const float *feat, int n_maps, int C, int HW, int layout, const int32_t *roi, int roi_stride, const int32_t *count,
+                         int rows_cap, int C_pad, uint8_t *out_mx6, float *err_max, float *row_norm, float *out_f32, int round_f16,
+                         hipStream_t st)
+{
+    ORYON_CHECK_ARG(feat && roi && count && out_mx6 && err_max);
+    ORYON_CHECK_ARG(n_maps >= 0 && C > 0 && HW > 0 && roi_stride > 0 && C_pad >= C && (C_pad == 256 || C_pad == 512));
+    ORYON_CHECK_ARG(layout == ORYON_LAYOUT_NCHW || layout == ORYON_LAYOUT_NHWC);
+    ORYON_CHECK_ARG(rows_cap > 0 && rows_cap % 256 == 0 && (size_t)C * (size_t)HW * 4u < (1ull << 32));
+    if (n_maps == 0) return ORYON_OK;
     static const int lpr_env = dev_env_int("ORYON_GATHER8_LPR", 1);
     const int rc = gather_q8_launch(feat, n_maps, C, HW, layout, roi, roi_stride, count, nullptr, rows_cap, C_pad,
                                     reinterpret_cast<int8_t *>(out_mx6), nullptr, err_max, row_norm, out_f32, lpr_env, round_f16, st, 1, nullptr);
     if (rc) { set_error("oryon_gather_mx6: launch failed"); return rc; }
     return ORYON_OK;
 }
+}  // namespace oryon
 
 extern "C" int oryon_gather_mx6_x3(const float *feat, int n_maps, int C, int HW, int layout, const int32_t *roi, int roi_stride,
                                    const int32_t *count, int rows_cap, int C_pad, uint8_t *out_mx6, float *err_max, float *row_norm,

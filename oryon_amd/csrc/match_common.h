@@ -39,12 +39,13 @@ void launch_screen_mx6(int C, int groups, int T, hipStream_t st, const uint8_t *
                        const int32_t *n_a, const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true,
                        int cascade = 0, const int32_t *gate = nullptr, int win = 0);
 inline int mx6_panels_per_pair(int cap_a) { return (cap_a + 1023) / 1024; }     // panels of the 8-wave C_pad 256 screen (the cascade's gate is [B, that])
-// second pass of the validity cascade: one 512-row panel of compacted anchor rows per pair, S query splits (C_pad 256)
-void launch_screen_mx6_sampled(hipStream_t st, const uint8_t *a6_panel, const uint8_t *q6, int B, int cap_q, const int32_t *n_rows,
-                               const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true);
-// the same over T = ceil(cap_rows / 512) panels of compacted rows per pair (the open rows of the default route's cascade)
-void launch_screen_mx6_rows512(hipStream_t st, const uint8_t *a6_rows, const uint8_t *q6, int B, int cap_rows, int cap_q, const int32_t *n_rows,
-                               const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true);
+// the complete screen of a LIST of a pair's cap_src anchor rows, read in place (C_pad 256): list slot i is row idx[p idx_stride + i] with
+// count[p] rows listed, or (idx == nullptr) row i stride with ceil(count[p] / stride) rows; at most cap_list rows, T = ceil(cap_list / 512)
+// panels per pair, S query splits; triples come out as [B, S, cap_list] by list slot.  The cascades' probe (stride), open rows (cap_list
+// = cap_a) and sampled rows (cap_list = MX6_SAMPLED_PANEL: the second pass of either validity cascade)
+void launch_screen_mx6_list512(hipStream_t st, const uint8_t *a6, const uint8_t *q6, int B, int cap_src, int cap_list, int cap_q,
+                               const int32_t *count, const int32_t *idx, int idx_stride, int stride, const int32_t *n_q, int S, float *ws_max,
+                               int32_t *ws_i1, float *ws_m2, int C_true);
 // band pass of the default route's cascade: the anchors in 512-row panels, panel k of pair p over the tiles [first, first + count) that
 // band[(p band_T + k) 2 ..] names, dealt evenly to S four-wave workgroups; triples come out as [B, S, cap_a]
 void launch_screen_mx6_band512(hipStream_t st, const uint8_t *a6, const uint8_t *q6, int B, int cap_a, int cap_q, const int32_t *n_a,
@@ -99,11 +100,85 @@ size_t carve_screen8_raw(void *base, Screen8RawWs &w, int B, int C, int cap_a, i
 int gather_q8_launch(const float *feat, int n_maps, int C, int HW, int layout, const int32_t *roi, int roi_stride, const int32_t *count,
                      const int32_t *map_enable, int rows_cap, int C_pad, int8_t *out8, float *scale, float *eps, float *norm,
                      float *out32, int lanes_per_row, int round_f16, hipStream_t st, int fmt = 0, void *aux = nullptr);
-// post.hip: the sampler; sel_rows / pair_eager as the lazy matcher uses them
+// gather8.hip: oryon_gather_mx6 without its fill of err_max - for a caller whose stream has already cleared those n_maps words
+int gather_mx6_prezeroed(const float *feat, int n_maps, int C, int HW, int layout, const int32_t *roi, int roi_stride, const int32_t *count,
+                         int rows_cap, int C_pad, uint8_t *out_mx6, float *err_max, float *row_norm, float *out_f32, int round_f16,
+                         hipStream_t st);
+// roi.hip: oryon_roi_compact on the anchor and the query masks of a step in ONE launch (grid 2 n_maps); the workgroup of map m also stores
+// 0 to zero_a[m] / zero_q[m] (either may be NULL): the err_max words of the gathers that follow on the same stream
+int roi_compact_pair_launch(const int32_t *mask_a, const int32_t *mask_q, int n_maps, int HW, int32_t *roi_a, int32_t *roi_q,
+                            int32_t *n_a, int32_t *n_q, float *zero_a, float *zero_q, hipStream_t st);
+// The sampled slots whose anchor row is in state `want` (ambiguous-valid: argmin still unknown) -> work list of the second level
+// (K1x3 / exact scan), built by the one workgroup of pair p that holds the data: the sampler right after it wrote sel_rows, the sampled
+// rows' decide pass right after it wrote their states.  state == nullptr: no list.
+// The list comes out in ASCENDING anchor-row order, i.e. in image order: neighbouring anchors share a wave of match_x3_scan_kernel,
+// their matches are neighbours in the query map, and the scan can skip the query tiles none of a wave's anchors can match (it is also
+// deterministic).  A row drawn several times (sampling with replacement) is marked - and listed - once.
+struct SampledAmbList {
+    const uint8_t *state = nullptr;     // [B, cap_a]
+    uint8_t want = 0;
+    int32_t *mark = nullptr;            // [B, cap_a], zero where no earlier list of this call marked the row
+    int32_t *n_list = nullptr;          // [B]
+    int32_t *list = nullptr;            // [B, corr_rows]
+};
+// Called by ALL threads of the workgroup (blockDim.x a multiple of 64, at most 1024; s_wave holds blockDim.x / 64 words).  What the
+// workgroup itself wrote before the call (sel_rows, state, mark) is read behind a barrier.
+__device__ __forceinline__ void list_sampled_amb(const SampledAmbList &L, int p, int cap_a, int n, const int32_t *sel_rows, int corr_rows,
+                                                 int *s_wave)
+{
+    const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6;
+    const uint8_t *st = L.state + (size_t)p * cap_a;
+    int32_t *mk = L.mark + (size_t)p * cap_a;
+    __threadfence_block();
+    __syncthreads();
+    for (int s = t; s < n; s += nt) {
+        const int a = sel_rows[(size_t)p * corr_rows + s];
+        if (st[a] == L.want) mk[a] = 1;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // ordered compaction in ONE scan: thread t owns the consecutive rows [t R, (t + 1) R), R a multiple of four (its mark words are
+    // 16-byte loads), counts its marks, the block scans the counts
+    const int R = ((cap_a + nt - 1) / nt + 3) / 4 * 4;
+    const bool vec = cap_a % 4 == 0 && (reinterpret_cast<uintptr_t>(mk) & 15) == 0;
+    auto marks4 = [&](int a) -> unsigned {          // bit e: row a + e is marked
+        if (vec && a + 4 <= cap_a) {
+            const int4 v = *reinterpret_cast<const int4 *>(mk + a);
+            return (v.x != 0 ? 1u : 0u) | (v.y != 0 ? 2u : 0u) | (v.z != 0 ? 4u : 0u) | (v.w != 0 ? 8u : 0u);
+        }
+        unsigned b = 0u;
+        for (int e = 0; e < 4; ++e) b |= (a + e < cap_a && mk[a + e] != 0 ? 1u : 0u) << e;
+        return b;
+    };
+    int mine = 0;
+    for (int i = 0; i < R; i += 4) mine += __popc(marks4(t * R + i));
+    int incl = mine;                                            // inclusive scan inside the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int off0 = incl - mine;
+    for (int w = 0; w < wave; ++w) off0 += s_wave[w];
+    if (mine)
+        for (int i = 0; i < R; i += 4) {
+            const unsigned b = marks4(t * R + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (b & (1u << e)) L.list[(size_t)p * corr_rows + off0++] = t * R + i + e;
+        }
+    if (t == nt - 1) L.n_list[p] = off0;
+}
+
+// post.hip: the sampler; sel_rows / pair_eager as the lazy matcher uses them; amb (lazy route only): the sampler's workgroups also build
+// the list of list_sampled_amb from the rows they just drew
 int select_corrs_launch(const int32_t *roi_a, const int32_t *roi_q, int roi_stride_a, int roi_stride_q, const int32_t *n_a,
                         const int32_t *n_q, const int32_t *argmin, const uint8_t *valid, int cap_a, int B, int W, int max_corrs,
                         int corr_rows, uint64_t seed, const int64_t *pair_key, int32_t *scratch, int32_t *corrs, int32_t *n_valid,
-                        int32_t *n_sel, int32_t *status, int32_t *sel_rows, const int32_t *pair_eager, hipStream_t st);
+                        int32_t *n_sel, int32_t *status, int32_t *sel_rows, const int32_t *pair_eager, hipStream_t st,
+                        const SampledAmbList &amb = SampledAmbList());
 
 // ------------------------------------------------------------------------------------------------ host steps of K1s8 (match16.hip)
 // What the steps below read: oryon_match_screened8 and oryon_match_screened8_raw fill one, MatchCorrsArgs extends it.

@@ -22,11 +22,29 @@ namespace oryon {
 // only if the row gets sampled.  AMB_UNCERTAIN: neither settled - resolved before the sampling.  Both AMB kinds are resolved by the EXACT
 // fp32 scan (K1) on a compacted list of just those anchor rows against the pair's materialised fp32 query rows.
 constexpr uint8_t LZ_INVALID = 0, LZ_VALID = 1, LZ_UNCERTAIN = 2, LZ_AMB_VALID = 3, LZ_RESOLVED = 4, LZ_AMB_UNCERTAIN = 5;
+// row classes of the default route's cascade (described in front of its kernels, further down)
+constexpr uint8_t DC_COMPLETE = 0, DC_SETTLED = 1, DC_OPEN = 2;
+
+// The default-route cascade's open rows, for the decide pass: a row of class DC_OPEN has its list slot in r_i1 (written by
+// match_dc_settle_rows_kernel) and its complete triples per split in the [B, S, cap_a] arrays m1 / i1 / m2, indexed by that slot (the
+// open rows' scan).  The decide pass merges them - as every other merge here: the maximum, the second-largest slice maximum, ties to
+// the lowest slice id - and stores the merged triple to r_m1 / r_i1 / r_m2, the rows' merged arrays, for the later readers.
+// cls == nullptr: no such rows.  r_* are the arrays the decide pass reads its S = 1 triples from: no __restrict__ on either side.
+struct DcOpenRows {
+    const uint8_t *cls = nullptr;
+    int S = 0;
+    const float *m1 = nullptr;
+    const int32_t *i1 = nullptr;
+    const float *m2 = nullptr;
+    float *r_m1 = nullptr;
+    int32_t *r_i1 = nullptr;
+    float *r_m2 = nullptr;
+};
 
 // one anchor row: merge the per-split (m1, slice, m2) triples and classify; -> the row is ambiguous (lazy route only)
 __device__ __forceinline__ bool decide_lite_row(
-    int cap_a, int p, int a, int S, const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
-    const float *__restrict__ ws_m2, const float *__restrict__ a_scale8, const float *__restrict__ eps_q8, float cut0, float sqrt_c,
+    int cap_a, int p, int a, int S, const float *ws_m1, const int32_t *ws_i1,
+    const float *ws_m2, const DcOpenRows &open, const float *__restrict__ a_scale8, const float *__restrict__ eps_q8, float cut0, float sqrt_c,
     float c_true, int force_eager, int fmt, int x3, float *__restrict__ m_final, int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
     uint8_t *__restrict__ state, uint8_t *__restrict__ valid, float *__restrict__ min_dist, int32_t *__restrict__ argmin,
     int32_t *__restrict__ pair_eager, int32_t *__restrict__ n_unc, int32_t *__restrict__ unc_idx, int32_t *__restrict__ n_ambu,
@@ -35,7 +53,13 @@ __device__ __forceinline__ bool decide_lite_row(
     const size_t arow = (size_t)p * cap_a + a;
     float m1, m2;
     int sid;
-    merge_split_triples(ws_m1, ws_i1, ws_m2, p, S, cap_a, a, m1, sid, m2);
+    if (open.cls && open.cls[arow] == DC_OPEN) {
+        merge_split_triples(open.m1, open.i1, open.m2, p, open.S, cap_a, open.r_i1[arow], m1, sid, m2);
+        open.r_m1[arow] = m1;
+        open.r_i1[arow] = sid;
+        open.r_m2[arow] = m2;
+    } else
+        merge_split_triples(ws_m1, ws_i1, ws_m2, p, S, cap_a, a, m1, sid, m2);
     ScreenBound b;
     if (fmt == 1) b = mx6_bound(a_scale8[p], eps_q8[p]);      // the pair's largest anchor / query row error
     else {
@@ -77,8 +101,8 @@ __device__ __forceinline__ bool decide_lite_row(
 // most rows ambiguous-valid - was 26 of this kernel's 32 us at 64 x 5000 rows (round 13: 31.9 us with the add, 5.9 us with it compiled
 // out).  n_unc / n_ambu keep their returning adds: they index lists, and such rows are rare
 __global__ __launch_bounds__(256) void match_decide_lite_kernel(
-    int cap_a, const int32_t *__restrict__ n_a, int S, const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
-    const float *__restrict__ ws_m2, const float *__restrict__ a_scale8, const float *__restrict__ eps_q8, float cut0, float sqrt_c,
+    int cap_a, const int32_t *__restrict__ n_a, int S, const float *ws_m1, const int32_t *ws_i1,
+    const float *ws_m2, const DcOpenRows open, const float *__restrict__ a_scale8, const float *__restrict__ eps_q8, float cut0, float sqrt_c,
     float c_true, int force_eager, int fmt, int x3, float *__restrict__ m_final, int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
     uint8_t *__restrict__ state, uint8_t *__restrict__ valid, float *__restrict__ min_dist, int32_t *__restrict__ argmin,
     int32_t *__restrict__ pair_eager, int32_t *__restrict__ n_unc, int32_t *__restrict__ unc_idx, int32_t *__restrict__ n_ambu,
@@ -88,7 +112,7 @@ __global__ __launch_bounds__(256) void match_decide_lite_kernel(
     const int p = blockIdx.y, a = blockIdx.x * 256 + threadIdx.x;
     bool amb = false;
     if (a < n_a[p])
-        amb = decide_lite_row(cap_a, p, a, S, ws_m1, ws_i1, ws_m2, a_scale8, eps_q8, cut0, sqrt_c, c_true, force_eager, fmt, x3, m_final, sid_final,
+        amb = decide_lite_row(cap_a, p, a, S, ws_m1, ws_i1, ws_m2, open, a_scale8, eps_q8, cut0, sqrt_c, c_true, force_eager, fmt, x3, m_final, sid_final,
                               margin_out, state, valid, min_dist, argmin, pair_eager, n_unc, unc_idx, n_ambu, ambu_idx, need_f32_lazy);
     if (force_eager) return;                                    // (the eager route reads no such count)
     const unsigned long long amb_lanes = __ballot(amb);
@@ -169,55 +193,12 @@ __global__ __launch_bounds__(256) void match_scatter_exact_kernel(int cap_a, int
     state[dst] = LZ_RESOLVED;
 }
 
-// the sampled slots whose anchor row is AMB_VALID (argmin still unknown) -> work list for the second level (K1x3 / exact scan).  One
-// workgroup per pair.  The list comes out in ASCENDING anchor-row order, i.e. in image order: neighbouring anchors share a wave of
-// match_x3_scan_kernel, their matches are neighbours in the query map, and the scan can skip the query tiles none of a wave's anchors
-// can match (it is also deterministic; the first version appended in atomic order).
-__global__ __launch_bounds__(256) void match_list_sampled_amb_kernel(int cap_a, const uint8_t *__restrict__ state,
-                                                                      const int32_t *__restrict__ pair_eager, const int32_t *__restrict__ n_sel,
-                                                                      const int32_t *__restrict__ sel_rows, int corr_rows,
-                                                                      int32_t *__restrict__ mark, int32_t *__restrict__ n_list,
-                                                                      int32_t *__restrict__ list)
-{
-    __shared__ int wave_cnt[4];
-    const int p = blockIdx.x;
-    if (pair_eager[p]) return;
-    const int n = n_sel[p], t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    // a row drawn several times (sampling with replacement) is marked once
-    for (int s = t; s < n; s += 256) {
-        const int a = sel_rows[(size_t)p * corr_rows + s];
-        if (state[(size_t)p * cap_a + a] == LZ_AMB_VALID) mark[(size_t)p * cap_a + a] = 1;
-    }
-    __threadfence_block();
-    __syncthreads();
-    // ordered compaction in ONE scan: thread t owns the consecutive rows [t R, (t + 1) R), counts its marks, the block scans the 256 counts
-    const int R = (cap_a + 255) / 256;
-    const int32_t *mk = mark + (size_t)p * cap_a;
-    int mine = 0;
-    for (int i = 0; i < R; ++i) {
-        const int a = t * R + i;
-        mine += (a < cap_a && mk[a] != 0) ? 1 : 0;
-    }
-    int incl = mine;                                            // inclusive scan inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wave_cnt[wave] = incl;
-    __syncthreads();
-    int off0 = incl - mine;
-    for (int w = 0; w < wave; ++w) off0 += wave_cnt[w];
-    for (int i = 0; i < R; ++i) {
-        const int a = t * R + i;
-        if (a < cap_a && mk[a] != 0) list[(size_t)p * corr_rows + off0++] = a;
-    }
-    if (t == 255) n_list[p] = off0;
-}
+// (the sampled slots whose anchor row is AMB_VALID - argmin still unknown - are listed for the second level by the kernels that hold the
+// data: list_sampled_amb, match_common.h, called by the sampler and by match_decide_sampled_kernel)
 
 // ---- validity cascade, second pass (round 6; oryon_match_corrs_mx6_x3).  The first screening pass stops a panel once its anchors are all
 // valid for sure and leaves their runner-up open (match_mx6_screen_w4_kernel<.., EXIT>); the sampled ones among them (the list of
-// match_list_sampled_amb_kernel, <= corr_rows per pair) get the COMPLETE screen here: their operand rows compacted into one panel per pair,
+// list_sampled_amb, <= corr_rows per pair) get the COMPLETE screen here: their operand rows compacted into one panel per pair,
 // the same kernel over all query tiles, and the (m1, slice, m2) triples merged back into the per-anchor arrays - a row whose winner turns
 // out unambiguous becomes LZ_VALID (resolved from its winning slice like any other), the others keep LZ_AMB_VALID with their true winning
 // slice as the second level's seed.
@@ -258,60 +239,65 @@ __global__ __launch_bounds__(256) void match_panel_settle_kernel(int cap_a, int 
             for (int s_ = 0; s_ < S; ++s_) ws_m2[((size_t)p * S + s_) * cap_a + a] = INFINITY;
 }
 
+// the listed rows as dense panels (the dev build's sweep of the open rows' scan with the 8-wave kernel: ORYON_DC_OPEN_PANEL=1024; every
+// shipped route reads its lists in place, launch_screen_mx6_list512)
 __global__ __launch_bounds__(256) void match_compact_rows_kernel(const uint8_t *__restrict__ rows, int row_bytes, int cap_a, int cap_c,
                                                                   const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
-                                                                  int idx_stride, uint8_t *__restrict__ out, int fill_mult,
-                                                                  int32_t *__restrict__ n_out)
+                                                                  int idx_stride, uint8_t *__restrict__ out, int fill_mult)
 {
     // 16 lanes per 256-byte row (uint4 each); rows [count, round_up(count, fill_mult)) - the rest of the last panel a screen launch
-    // reads - are zero rows (exponent byte 0: finite scores nobody reads).
-    // idx == nullptr: the list is "every idx_stride-th row of the pair's count[p] rows" (the default-route cascade's probe: rows 0,
-    // stride, 2 stride, .. - a shape-only pattern, <= cap_c of them), and n_out[p] receives its length for the screen launch behind
+    // reads - are zero rows (exponent byte 0: finite scores nobody reads)
     const int p = blockIdx.y, sl = blockIdx.x * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
     if (sl >= cap_c) return;
-    const int listed = idx ? count[p] : (count[p] + idx_stride - 1) / idx_stride;
-    const int n = listed < cap_c ? listed : cap_c;
-    if (!idx && blockIdx.x == 0 && threadIdx.x == 0) n_out[p] = n;
+    const int n = count[p] < cap_c ? count[p] : cap_c;
     if (sl >= (n + fill_mult - 1) / fill_mult * fill_mult) return;
     uint4 *d = reinterpret_cast<uint4 *>(out + ((size_t)p * cap_c + sl) * row_bytes);
     if (sl >= n) {
         for (int i = l; i < row_bytes / 16; i += 16) d[i] = make_uint4(0, 0, 0, 0);
         return;
     }
-    const int row = idx ? idx[(size_t)p * idx_stride + sl] : sl * idx_stride;
-    const uint4 *src = reinterpret_cast<const uint4 *>(rows + ((size_t)p * cap_a + row) * row_bytes);
+    const uint4 *src = reinterpret_cast<const uint4 *>(rows + ((size_t)p * cap_a + idx[(size_t)p * idx_stride + sl]) * row_bytes);
     for (int i = l; i < row_bytes / 16; i += 16) d[i] = src[i];
 }
 
-__global__ __launch_bounds__(256) void match_decide_sampled_kernel(int cap_a, int cap_c, int S, const int32_t *__restrict__ count,
-                                                                    const int32_t *__restrict__ idx, int idx_stride,
-                                                                    const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
-                                                                    const float *__restrict__ ws_m2, const float *__restrict__ a_err,
-                                                                    const float *__restrict__ q_err, float *__restrict__ m_final,
-                                                                    int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
-                                                                    uint8_t *__restrict__ state, int32_t *__restrict__ mark,
-                                                                    int32_t *__restrict__ count_before, float *__restrict__ min_dist)
+// One workgroup per pair, a thread per row of the sampled panel: the rows' decisions, then - behind a barrier - the second level's list of
+// the rows that stay ambiguous (list_sampled_amb; count / idx are that list's own n_list / list, rebuilt in place).
+constexpr int DS_THREADS = 512;
+__global__ __launch_bounds__(DS_THREADS) void match_decide_sampled_kernel(int cap_a, int cap_c, int S, const int32_t *count,
+                                                                           const int32_t *idx, int idx_stride,
+                                                                           const float *__restrict__ ws_m1, const int32_t *__restrict__ ws_i1,
+                                                                           const float *__restrict__ ws_m2, const float *__restrict__ a_err,
+                                                                           const float *__restrict__ q_err, float *__restrict__ m_final,
+                                                                           int32_t *__restrict__ sid_final, float *__restrict__ margin_out,
+                                                                           uint8_t *state, int32_t *mark,
+                                                                           int32_t *__restrict__ count_before, float *__restrict__ min_dist,
+                                                                           const int32_t *__restrict__ pair_eager, const int32_t *__restrict__ n_sel,
+                                                                           const int32_t *__restrict__ sel_rows, const SampledAmbList amb)
 {
-    const int p = blockIdx.y, sl = blockIdx.x * 256 + threadIdx.x;
+    __shared__ int s_wave[DS_THREADS / 64];
+    const int p = blockIdx.x;
     const int n = count[p] < cap_c ? count[p] : cap_c;
-    if (sl == 0) count_before[p] = n;
-    if (sl >= n) return;
-    const int a = idx[(size_t)p * idx_stride + sl];
-    float m1, m2;
-    int sid;
-    merge_split_triples(ws_m1, ws_i1, ws_m2, p, S, cap_c, sl, m1, sid, m2);
-    const float margin = mx6_bound(a_err[p], q_err[p]).margin();
-    const size_t arow = (size_t)p * cap_a + a;
-    m_final[arow] = m1;                                                // the complete scan's maximum (>= the partial one that settled validity)
-    sid_final[arow] = sid;
-    margin_out[arow] = margin;
-    // default-route cascade: the provisional distance of a settled row came from its witness inside the band; the estimate a sampled
-    // row reports is the complete scan's, as on the plain route
-    if (min_dist) min_dist[arow] = dist_from_dot(m1);
-    if (m1 - m2 > margin) {                                            // unambiguous after all: no second level for this row
-        state[arow] = LZ_VALID;
-        mark[arow] = 0;
+    if (threadIdx.x == 0) count_before[p] = n;
+    for (int sl = threadIdx.x; sl < n; sl += DS_THREADS) {
+        const int a = idx[(size_t)p * idx_stride + sl];
+        float m1, m2;
+        int sid;
+        merge_split_triples(ws_m1, ws_i1, ws_m2, p, S, cap_c, sl, m1, sid, m2);
+        const float margin = mx6_bound(a_err[p], q_err[p]).margin();
+        const size_t arow = (size_t)p * cap_a + a;
+        m_final[arow] = m1;                                            // the complete scan's maximum (>= the partial one that settled validity)
+        sid_final[arow] = sid;
+        margin_out[arow] = margin;
+        // default-route cascade: the provisional distance of a settled row came from its witness inside the band; the estimate a sampled
+        // row reports is the complete scan's, as on the plain route
+        if (min_dist) min_dist[arow] = dist_from_dot(m1);
+        if (m1 - m2 > margin) {                                        // unambiguous after all: no second level for this row
+            state[arow] = LZ_VALID;
+            mark[arow] = 0;
+        }
     }
+    if (pair_eager[p]) return;
+    list_sampled_amb(amb, p, cap_a, n_sel[p], sel_rows, idx_stride, s_wave);
 }
 
 // ---- validity cascade of the DEFAULT route, at anchor granularity (oryon_match_corrs_mx6[_araw], C_pad 256; DESIGN "default-route cascade").
@@ -325,12 +311,12 @@ __global__ __launch_bounds__(256) void match_decide_sampled_kernel(int cap_a, in
 // SETTLED (partial maximum above dc_sure_line: valid for sure, m2 = +inf i.e. argmin open, as match_panel_settle_kernel
 // leaves the rows of a settled panel).  Scores of an (anchor, query) pair do not depend on the panel the anchor row sits in, and the
 // merged triple not on how the tiles are dealt to splits (ties go to the lowest slice either way): complete triples are today's.
-constexpr uint8_t DC_COMPLETE = 0, DC_SETTLED = 1, DC_OPEN = 2;
-constexpr int DC_SLACK = 2;             // tiles added at either end of a learned band (ORYON_DC_SLACK in the dev build)
+// (DC_COMPLETE / DC_SETTLED / DC_OPEN: at the head of the file, for the decide pass)
+constexpr int DC_SLACK = 2;            // tiles added at either end of a learned band (ORYON_DC_SLACK in the dev build)
 constexpr int DC_MIN_SURE = 8;          // a panel with fewer valid-for-sure probe rows scans all tiles
 constexpr int DC_BAND_CAP_NUM = 1, DC_BAND_CAP_DEN = 2;     // ... and so does one whose band exceeds this share of the pair's tiles
 
-// (the probe - rows 0, stride, 2 stride, .. of every pair - has no list: match_compact_rows_kernel's stride mode forms it and its count)
+// (the probe - rows 0, stride, 2 stride, .. of every pair - has no list: the list screen's stride mode forms it and its count)
 
 // one workgroup per (1024-row panel, pair): the panel's probe rows get their complete triples, the panel its band [first, count) and
 // each of its two 512-row halves a sub-band inside it: band[p][2 panel + h] (what the band pass scans and the settle pass looks up).
@@ -453,7 +439,12 @@ __global__ __launch_bounds__(DC_SETTLE_THREADS) void match_dc_settle_rows_kernel
             before += w < wave ? c : 0;
             tot += c;
         }
-        if (open) open_idx[(size_t)p * cap_a + base + before + __popcll(open_lanes & ((1ull << lane) - 1ull))] = a;
+        if (open) {
+            // the row's slot also goes where its slice id will stand (DcOpenRows): the decide pass merges the open rows' scan from there
+            const int slot = base + before + __popcll(open_lanes & ((1ull << lane) - 1ull));
+            open_idx[(size_t)p * cap_a + slot] = a;
+            r_i1[(size_t)p * cap_a + a] = slot;
+        }
         base += tot;
         m1 = m1_n; sid = sid_n; m2 = m2_n; all = all_n;
     }
@@ -468,22 +459,8 @@ __global__ __launch_bounds__(DC_SETTLE_THREADS) void match_dc_settle_rows_kernel
     }
 }
 
-// complete triples of the open rows (scanned as compacted rows: [B, S, cap_a] indexed by list slot) -> the rows' merged arrays
-__global__ __launch_bounds__(256) void match_dc_scatter_open_kernel(int cap_a, int S, const int32_t *__restrict__ n_open,
-                                                                     const int32_t *__restrict__ open_idx, const float *__restrict__ ws_m1,
-                                                                     const int32_t *__restrict__ ws_i1, const float *__restrict__ ws_m2,
-                                                                     float *__restrict__ r_m1, int32_t *__restrict__ r_i1, float *__restrict__ r_m2)
-{
-    const int p = blockIdx.y, sl = blockIdx.x * 256 + threadIdx.x;
-    if (sl >= n_open[p] || sl >= cap_a) return;
-    float m1, m2;
-    int sid;
-    merge_split_triples(ws_m1, ws_i1, ws_m2, p, S, cap_a, sl, m1, sid, m2);
-    const size_t arow = (size_t)p * cap_a + open_idx[(size_t)p * cap_a + sl];
-    r_m1[arow] = m1;
-    r_i1[arow] = sid;
-    r_m2[arow] = m2;
-}
+// (the complete triples of the open rows - scanned as compacted rows: [B, S, cap_a] indexed by list slot - reach the rows' merged arrays
+// in match_decide_lite_kernel, the next reader of every row: DcOpenRows)
 
 // Exact resolution of ONE unambiguous anchor by one wave: candidates = rows of the winning 16-row slice within the int8 margin of its
 // maximum (slice_score_* of match_exact.h on the screen's own operand rows), then the canonical fp32 chain per candidate on x_k / d read
@@ -831,11 +808,23 @@ int32_t *oryon::match_dc_stats(void *workspace, int B, int C, int cap_a, int cap
 namespace {
 constexpr const char *IMPL = "match_corrs_lazy_impl";       // the name launch failures of its two routes are reported under
 
-int select_step(const MatchCorrsArgs &m, const LazyWs &w, hipStream_t st)
+// the second level's list of the sampled rows that are ambiguous-valid: what the sampler (lazy route) and the sampled rows' decide pass build
+SampledAmbList sampled_amb_list(const LazyWs &w)
+{
+    SampledAmbList L;
+    L.state = w.state;
+    L.want = LZ_AMB_VALID;
+    L.mark = w.mark;
+    L.n_list = w.n_ambv;
+    L.list = w.ambv_idx;
+    return L;
+}
+
+int select_step(const MatchCorrsArgs &m, const LazyWs &w, hipStream_t st, const SampledAmbList &amb = SampledAmbList())
 {
     const int rc = select_corrs_launch(m.roi_a, m.roi_q, m.roi_stride_a, m.roi_stride_q, m.n_a, m.n_q, m.argmin, m.valid, m.cap_a, m.B, m.W,
                                        m.max_corrs, m.corr_rows, m.seed, m.pair_key, w.scratch, m.corrs, m.n_valid, m.n_sel, m.status,
-                                       w.sel_rows, w.pair_eager, st);
+                                       w.sel_rows, w.pair_eager, st, amb);
     if (rc) set_error("oryon_match_corrs_i8: select launch failed");
     return rc;
 }
@@ -891,25 +880,20 @@ int lazy_route(const MatchCorrsArgs &m, const LazyWs &w, hipStream_t st, int use
                        m.C_true, m.HW, m.roi_q, m.roi_stride_q, m.q_norm, C, cap_a, cap_q, m.n_q, m.threshold, w.m_final, w.sid_final, w.margin,
                        w.n_unc, w.unc_idx, w.pair_eager, w.state, m.valid, m.min_dist, m.argmin, m.round_f16);
     if ((rc = check_launch(IMPL))) return rc;
-    // (4) the sampling, on the exact valid set
-    if ((rc = select_step(m, w, st))) return rc;
+    // (4) the sampling, on the exact valid set; its workgroups also list the sampled rows that are ambiguous (n_ambv, ambv_idx)
+    const SampledAmbList amb = sampled_amb_list(w);
+    if ((rc = select_step(m, w, st, amb))) return rc;
     // (5) sampled rows that are ambiguous (valid for sure, argmin open): exact fp32 scan of just those <= max_corrs rows per pair
     const int cap_s = sampled_cap(corr_rows, cap_a);
-    hipLaunchKernelGGL(match_list_sampled_amb_kernel, dim3(B), dim3(256), 0, st, cap_a, w.state, w.pair_eager, m.n_sel, w.sel_rows, corr_rows,
-                       w.mark, w.n_ambv, w.ambv_idx);
     if (cascade) {
         // second pass: the complete screen for the listed rows (one 512-row panel per pair), triples merged back, list rebuilt
         const int csS = mx6_sampled_splits(B);
-        hipLaunchKernelGGL(match_compact_rows_kernel, dim3(MX6_SAMPLED_PANEL / 16, B), dim3(256), 0, st, reinterpret_cast<const uint8_t *>(m.a_i8),
-                           C, cap_a, MX6_SAMPLED_PANEL, w.n_ambv, w.ambv_idx, corr_rows, w.cs_panel, MX6_SAMPLED_PANEL,
-                           static_cast<int32_t *>(nullptr));
-        launch_screen_mx6_sampled(st, w.cs_panel, reinterpret_cast<const uint8_t *>(m.q_i8), B, cap_q, w.n_ambv, m.n_q, csS, w.cs_max, w.cs_i1,
-                                  w.cs_m2, m.C_true);
-        hipLaunchKernelGGL(match_decide_sampled_kernel, dim3((MX6_SAMPLED_PANEL + 255) / 256, B), dim3(256), 0, st, cap_a, MX6_SAMPLED_PANEL, csS,
+        // (the screen reads the listed rows in place, through the list: cs_panel keeps its room, unused)
+        launch_screen_mx6_list512(st, reinterpret_cast<const uint8_t *>(m.a_i8), reinterpret_cast<const uint8_t *>(m.q_i8), B, cap_a, MX6_SAMPLED_PANEL,
+                                  cap_q, w.n_ambv, w.ambv_idx, corr_rows, 0, m.n_q, csS, w.cs_max, w.cs_i1, w.cs_m2, m.C_true);
+        hipLaunchKernelGGL(match_decide_sampled_kernel, dim3(B), dim3(DS_THREADS), 0, st, cap_a, MX6_SAMPLED_PANEL, csS,
                            w.n_ambv, w.ambv_idx, corr_rows, w.cs_max, w.cs_i1, w.cs_m2, m.a_scale, m.q_eps_max, w.m_final, w.sid_final,
-                           w.margin, w.state, w.mark, w.n_ambv0, dc ? m.min_dist : nullptr);
-        hipLaunchKernelGGL(match_list_sampled_amb_kernel, dim3(B), dim3(256), 0, st, cap_a, w.state, w.pair_eager, m.n_sel, w.sel_rows,
-                           corr_rows, w.mark, w.n_ambv, w.ambv_idx);
+                           w.margin, w.state, w.mark, w.n_ambv0, dc ? m.min_dist : nullptr, w.pair_eager, m.n_sel, w.sel_rows, amb);
         if ((rc = check_launch(IMPL))) return rc;
     }
     compact_anchors(m, araw, w, st, cap_s, w.n_ambv, w.ambv_idx, corr_rows);
@@ -1010,6 +994,7 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
     int S_dec = S;                                                          // what match_decide_lite_kernel merges: the splits' triples ..
     const float *dec_m1 = w.ws_max, *dec_m2 = w.ws_m2;
     const int32_t *dec_i1 = w.ws_i1;
+    DcOpenRows dc_open;
     if (m.fmt == 1) {
         const uint8_t *a6 = reinterpret_cast<const uint8_t *>(m.a_i8), *q6 = reinterpret_cast<const uint8_t *>(m.q_i8);
         const int groups = ((B * S + 7) / 8) * 8 * T;
@@ -1028,11 +1013,11 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
             static const int slack = dev_env_int("ORYON_DC_SLACK", DC_SLACK);
             static const int open_panel = dev_env_int("ORYON_DC_OPEN_PANEL", 0) == 1024 ? 1024 : MX6_SAMPLED_PANEL;
             static const int sub_stats = dev_env_int("ORYON_DC_SUB_STATS", 0);     // stats[3] = the halves' widths (sweeps: the sub-bands' share)
-            // (1) probe: every stride-th anchor, compacted into the second pass's panel, screened completely; triples and bands
-            //     (rows 0, stride, 2 stride, ..: <= MX6_SAMPLED_PANEL of them, stride >= cap_a / 512; the compaction writes dc_n_probe)
-            hipLaunchKernelGGL(match_compact_rows_kernel, dim3(MX6_SAMPLED_PANEL / 16, B), dim3(256), 0, st, a6, C, cap_a, MX6_SAMPLED_PANEL,
-                               m.n_a, static_cast<const int32_t *>(nullptr), stride, w.cs_panel, MX6_SAMPLED_PANEL, w.dc_n_probe);
-            launch_screen_mx6_sampled(st, w.cs_panel, q6, B, cap_q, w.dc_n_probe, m.n_q, csS, w.cs_max, w.cs_i1, w.cs_m2, m.C_true);
+            // (1) probe: every stride-th anchor, read in place as one list panel per pair, screened completely; triples and bands
+            //     (rows 0, stride, 2 stride, ..: <= MX6_SAMPLED_PANEL of them, stride >= cap_a / 512; the screen forms the list's length
+            //     from n_a itself, as match_dc_probe_band_kernel does: dc_n_probe keeps its room, unwritten)
+            launch_screen_mx6_list512(st, a6, q6, B, cap_a, MX6_SAMPLED_PANEL, cap_q, m.n_a, nullptr, 0, stride, m.n_q, csS, w.cs_max, w.cs_i1,
+                                      w.cs_m2, m.C_true);
             hipLaunchKernelGGL(match_dc_probe_band_kernel, dim3(T8, B), dim3(256), 0, st, cap_a, T8, stride, csS, m.n_a, m.n_q, w.cs_max, w.cs_i1,
                                w.cs_m2, m.a_scale, m.q_eps_max, cut0, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_band, w.dc_stats, slack, sub_stats);
             // (2) band pass over all rows, each 512-row half in its own sub-band, (3) classes, merged triples, ordered list of the open rows
@@ -1040,18 +1025,22 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
             hipLaunchKernelGGL(match_dc_settle_rows_kernel, dim3(B), dim3(DC_SETTLE_THREADS), 0, st, cap_a, T8, stride, Sb, m.n_a, m.n_q, w.dc_ws_m1, w.dc_ws_i1,
                                w.dc_ws_m2, m.a_scale, m.q_eps_max, cut0, w.dc_band, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_cls, w.dc_n_open, w.dc_open_idx,
                                w.dc_stats);
-            // (4) complete scan of the open rows as dense 512-row panels (count-gated), triples scattered back
-            hipLaunchKernelGGL(match_compact_rows_kernel, dim3(cap_a / 16, B), dim3(256), 0, st, a6, C, cap_a, cap_a, w.dc_n_open, w.dc_open_idx,
-                               cap_a, w.dc_rows, open_panel, static_cast<int32_t *>(nullptr));
-            if (open_panel == 1024)     // the sweep's alternative (dev build): the 8-wave kernel over 1024-row panels of the compacted rows
+            // (4) complete scan of the open rows in 512-row list panels, read in place through open_idx (count-gated); their triples are
+            //     merged by the decide pass.  dc_rows keeps its room for the sweep's alternative
+            if (open_panel == 1024) {   // (dev build): the 8-wave kernel over 1024-row panels of the rows compacted into dc_rows
+                hipLaunchKernelGGL(match_compact_rows_kernel, dim3(cap_a / 16, B), dim3(256), 0, st, a6, C, cap_a, cap_a, w.dc_n_open, w.dc_open_idx,
+                                   cap_a, w.dc_rows, open_panel);
                 launch_screen_mx6(C, ((B * So + 7) / 8) * 8 * T, T, st, w.dc_rows, q6, B, cap_a, cap_q, w.dc_n_open, m.n_q, So, w.dc_ws_m1, w.dc_ws_i1,
                                   w.dc_ws_m2, m.C_true);
-            else
-                launch_screen_mx6_rows512(st, w.dc_rows, q6, B, cap_a, cap_q, w.dc_n_open, m.n_q, So, w.dc_ws_m1, w.dc_ws_i1, w.dc_ws_m2, m.C_true);
-            hipLaunchKernelGGL(match_dc_scatter_open_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, So, w.dc_n_open, w.dc_open_idx,
-                               w.dc_ws_m1, w.dc_ws_i1, w.dc_ws_m2, w.dc_m1, w.dc_i1, w.dc_m2);
-            S_dec = 1;                                                      // .. or the rows' merged ones
-            dec_m1 = w.dc_m1; dec_i1 = w.dc_i1; dec_m2 = w.dc_m2;
+            } else
+                launch_screen_mx6_list512(st, a6, q6, B, cap_a, cap_a, cap_q, w.dc_n_open, w.dc_open_idx, cap_a, 0, m.n_q, So, w.dc_ws_m1, w.dc_ws_i1,
+                                          w.dc_ws_m2, m.C_true);
+            S_dec = 1;                                                      // .. or the rows' merged ones; the open rows' So triples are
+            dec_m1 = w.dc_m1; dec_i1 = w.dc_i1; dec_m2 = w.dc_m2;           //    merged by the decide pass itself, from their list slots
+            dc_open.cls = w.dc_cls;
+            dc_open.S = So;
+            dc_open.m1 = w.dc_ws_m1; dc_open.i1 = w.dc_ws_i1; dc_open.m2 = w.dc_ws_m2;
+            dc_open.r_m1 = w.dc_m1; dc_open.r_i1 = w.dc_i1; dc_open.r_m2 = w.dc_m2;
         } else {
             launch_screen_mx6(C, groups, T, st, a6, q6, B, cap_a, cap_q, m.n_a, m.n_q, S, w.ws_max, w.ws_i1, w.ws_m2, m.C_true);
         }
@@ -1060,7 +1049,7 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
         screen8_step(m, S, m.n_a, w);
     }
     ORYON_CHECK_LAUNCH();
-    hipLaunchKernelGGL(match_decide_lite_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, m.n_a, S_dec, dec_m1, dec_i1, dec_m2, m.a_scale,
+    hipLaunchKernelGGL(match_decide_lite_kernel, dim3(cap_a / 256, B), dim3(256), 0, st, cap_a, m.n_a, S_dec, dec_m1, dec_i1, dec_m2, dc_open, m.a_scale,
                        m.q_eps_max, cut0, sqrtf((float)m.C_true), (float)m.C_true, m.force_eager, m.fmt, use_x3, w.m_final, w.sid_final, w.margin,
                        w.state, m.valid, m.min_dist, m.argmin, w.pair_eager, w.n_unc, w.unc_idx, w.n_ambu, w.ambu_idx, w.need_f32_lazy,
                        w.n_amb_part);

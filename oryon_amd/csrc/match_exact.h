@@ -112,13 +112,16 @@ __device__ __forceinline__ void merge_split_triples(const float *__restrict__ ws
                                                     const float *__restrict__ ws_m2, int p, int S, int cap, int row, float &m1, int &sid, float &m2)
 {
     m1 = m2 = -INFINITY;
-    sid = 0;
+    int s_best = -1;
+    // (the slice id is fetched once, from the split that won: the 2 S loads of the loop do not depend on one another)
+#pragma unroll 4
     for (int s = 0; s < S; ++s) {
         const size_t o = ((size_t)p * S + s) * cap + row;
         const float x1 = ws_m1[o], x2 = ws_m2[o];
         m2 = fmaxf(fminf(m1, x1), fmaxf(m2, x2));
-        if (x1 > m1) { m1 = x1; sid = ws_i1[o]; }
+        if (x1 > m1) { m1 = x1; s_best = s; }
     }
+    sid = s_best >= 0 ? ws_i1[((size_t)p * S + s_best) * cap + row] : 0;
 }
 
 // ------------------------------------------------------------------------------------------------ bounds

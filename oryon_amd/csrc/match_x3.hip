@@ -223,7 +223,7 @@ __device__ __forceinline__ void match_x3_scan_item(const int xcd, const int slot
     // has s_hi >= max_hi - 2 e_hi - 2 DELTA3 for any of the wave's anchors holds no candidate for this wave.  Sweep 1 flags the tiles that
     // pass against the RUNNING maximum (a superset of those that pass against the final one) - started from the seed, i.e. close to the
     // final maximum from the first tile on; sweep 2 multiplies only flagged tiles.  The anchors arrive in image order
-    // (match_list_sampled_amb_kernel), so a wave's 64 anchors - and their matches - cover a band of the image (hard cfg2 step: 19 % of
+    // (list_sampled_amb, match_common.h), so a wave's 64 anchors - and their matches - cover a band of the image (hard cfg2 step: 19 % of
     // the (wave, tile) pairs flagged with the seed, 46 % without).
     constexpr int FLAG_BASE = NS1 * PART;                       // behind the ring: 4 x X3_MAX_TILES flag bytes, 4 x X3_MAX_TILES list entries
     unsigned char *tile_flag = reinterpret_cast<unsigned char *>(smem + FLAG_BASE) + wave * X3_MAX_TILES;

@@ -5,6 +5,7 @@
 // H.cpu() -> LAPACK -> .to(device) per Kabsch call).
 #include "common.h"
 #include "kabsch.h"
+#include "match_common.h"
 
 namespace oryon {
 
@@ -62,10 +63,12 @@ __global__ __launch_bounds__(SEL_THREADS) void select_corrs_kernel(
     const uint8_t *__restrict__ valid, int cap_a, int W, int max_corrs, int corr_rows, uint64_t seed,
     const int64_t *__restrict__ pair_key, int32_t *__restrict__ scratch, int32_t *__restrict__ corrs,
     int32_t *__restrict__ n_valid, int32_t *__restrict__ n_sel, int32_t *__restrict__ status,
-    int32_t *__restrict__ sel_rows, const int32_t *__restrict__ pair_eager)
+    int32_t *sel_rows, const int32_t *__restrict__ pair_eager, const SampledAmbList amb)
 {
     // sel_rows != NULL (lazy matcher, match_corrs.hip): also record WHICH anchor row fills every slot; for pairs whose argmin column is
-    // not materialised yet (pair_eager[p] == 0) the query half of the row is left to match_resolve_selected_kernel
+    // not materialised yet (pair_eager[p] == 0) the query half of the row is left to match_resolve_selected_kernel.
+    // amb.state != NULL (its lazy route): the workgroup then lists the drawn rows that are still ambiguous (list_sampled_amb) - a pair
+    // that draws nothing leaves its zeroed count and marks as they are
     __shared__ int s_wave[SEL_WAVES];
     __shared__ __align__(16) unsigned s_hist[256];
     __shared__ unsigned s_prefix, s_remaining;
@@ -113,6 +116,10 @@ __global__ __launch_bounds__(SEL_THREADS) void select_corrs_kernel(
         *reinterpret_cast<int4 *>(out + (size_t)slot * 4) = c;
         if (sel_rows) sel_rows[(size_t)p * corr_rows + slot] = row;
     };
+    // behind either way of drawing, by all threads: the drawn rows that are still ambiguous (lazy pairs only, as their query halves)
+    auto list_amb = [&]() {
+        if (amb.state && sel_rows && !query_known) list_sampled_amb(amb, p, cap_a, max_corrs, sel_rows, corr_rows, s_wave);
+    };
     if (nv < max_corrs) {
         // with replacement (utils/misc.py:251-252): max_corrs independent uniform draws
         for (int j = threadIdx.x; j < max_corrs; j += SEL_THREADS) {
@@ -120,6 +127,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_corrs_kernel(
             const int pick = (int)(((uint64_t)u * (uint64_t)nv) >> 32);
             emit(j, list[pick]);
         }
+        list_amb();
         return;
     }
     // without replacement: the max_corrs smallest keys among the nv valid rows, emitted in row order
@@ -172,6 +180,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_corrs_kernel(
         kept += keep_total;
         ties_seen += tie_total;
     }
+    list_amb();
 }
 
 // K2.  One workgroup per pair; fp32 operation order is the reference's, with explicit _rn intrinsics so the
@@ -305,10 +314,11 @@ __global__ __launch_bounds__(256) void sample_first_merge_kernel(int corr_rows, 
 int select_corrs_launch(const int32_t *roi_a, const int32_t *roi_q, int roi_stride_a, int roi_stride_q, const int32_t *n_a,
                         const int32_t *n_q, const int32_t *argmin, const uint8_t *valid, int cap_a, int B, int W, int max_corrs,
                         int corr_rows, uint64_t seed, const int64_t *pair_key, int32_t *scratch, int32_t *corrs, int32_t *n_valid,
-                        int32_t *n_sel, int32_t *status, int32_t *sel_rows, const int32_t *pair_eager, hipStream_t st)
+                        int32_t *n_sel, int32_t *status, int32_t *sel_rows, const int32_t *pair_eager, hipStream_t st,
+                        const SampledAmbList &amb)
 {
     hipLaunchKernelGGL(select_corrs_kernel, dim3(B), dim3(SEL_THREADS), 0, st, roi_a, roi_q, roi_stride_a, roi_stride_q, n_a, n_q, argmin,
-                       valid, cap_a, W, max_corrs, corr_rows, seed, pair_key, scratch, corrs, n_valid, n_sel, status, sel_rows, pair_eager);
+                       valid, cap_a, W, max_corrs, corr_rows, seed, pair_key, scratch, corrs, n_valid, n_sel, status, sel_rows, pair_eager, amb);
     return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
 }
 }  // namespace oryon
@@ -324,7 +334,7 @@ extern "C" int oryon_select_corrs(const int32_t *roi_a, const int32_t *roi_q, in
     if (B == 0) return ORYON_OK;
     hipLaunchKernelGGL(select_corrs_kernel, dim3(B), dim3(SEL_THREADS), 0, as_stream(stream), roi_a, roi_q, roi_stride_a,
                        roi_stride_q, n_a, n_q, argmin, valid, cap_a, W, max_corrs, corr_rows, seed, pair_key, scratch, corrs,
-                       n_valid, n_sel, status, static_cast<int32_t *>(nullptr), static_cast<const int32_t *>(nullptr));
+                       n_valid, n_sel, status, static_cast<int32_t *>(nullptr), static_cast<const int32_t *>(nullptr), SampledAmbList());
     ORYON_CHECK_LAUNCH();
     return ORYON_OK;
 }

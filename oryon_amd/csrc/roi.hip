@@ -5,6 +5,7 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 #include "common.h"
+#include "match_common.h"
 #include "match_exact.h"
 
 namespace oryon {
@@ -57,38 +58,112 @@ __device__ __forceinline__ int block_scan_counts(int cnt, int *s_wave /*[SCAN_WA
     return base + incl - cnt;
 }
 
-// One workgroup per map, EIGHT consecutive pixels per thread and scan step (two 16-byte loads): 7 block scans for a 224 x 224 map
-// instead of 49 - the kernel is bound by the latency of its scan steps (55 -> ~12 us per launch at 64 maps), not by the 200 KB it reads.
-__global__ __launch_bounds__(SCAN_THREADS) void roi_compact_kernel(const int32_t *__restrict__ mask, int HW,
-                                                                    int32_t *__restrict__ roi, int32_t *__restrict__ count)
+// `chunks` workgroups per map, EIGHT consecutive pixels per thread and scan step (two 16-byte loads), and RC_STEPS scan steps settled
+// behind ONE pair of barriers: a 224 x 224 map (7 steps of 8192 pixels) has all its loads in flight at once and one hand-over of the
+// wave totals through LDS instead of seven dependent load -> scan -> barrier rounds.
+// Chunk c of a map compacts the pixels [c CL, (c + 1) CL) (CL = ceil(HW / chunks) rounded up to eight); where its entries start in the
+// map's list it counts for itself, with a store-free pass over the pixels in front of its own: the ROI stores (up to 64 predicated
+// 4-byte stores per thread) are what the kernel's time goes to, a second read of half a mask costs a few microseconds.  The launches
+// deal 256 workgroups or fewer: the 64 + 64 maps of a cfg2 step get two chunks each.
+// Up to two mask sets per launch: the workgroups of the second half of the grid take the second one (the engine's K0 section compacts
+// the anchor and the query masks of a step with one launch).  zero0 / zero1 (may be NULL): one word per map that the map's first
+// workgroup clears - the error-norm word of the gather that follows on the same stream.
+constexpr int RC_STEPS = 8;
+inline int roi_compact_chunks(int maps) { return maps >= 256 ? 1 : (256 / maps < 4 ? 256 / maps : 4); }
+__global__ __launch_bounds__(SCAN_THREADS) void roi_compact_kernel(const int32_t *__restrict__ mask0, const int32_t *__restrict__ mask1,
+                                                                    int n_maps, int chunks, int HW, int32_t *__restrict__ roi0,
+                                                                    int32_t *__restrict__ roi1, int32_t *__restrict__ count0,
+                                                                    int32_t *__restrict__ count1, float *__restrict__ zero0,
+                                                                    float *__restrict__ zero1)
 {
-    __shared__ int s_wave[SCAN_WAVES];
-    const int m = blockIdx.x;
-    const int32_t *mk = mask + (size_t)m * HW;
-    int32_t *out = roi + (size_t)m * HW;
+    __shared__ __align__(16) int s_wave[RC_STEPS][SCAN_WAVES];
+    const int chunk = (int)blockIdx.x % chunks, map = (int)blockIdx.x / chunks;
+    const bool second = map >= n_maps;
+    const int m = second ? map - n_maps : map;
+    const int32_t *mk = (second ? mask1 : mask0) + (size_t)m * HW;
+    int32_t *out = (second ? roi1 : roi0) + (size_t)m * HW;
+    float *zero = second ? zero1 : zero0;
+    const int CL = ((HW + chunks - 1) / chunks + 7) / 8 * 8;
+    const int first = chunk * CL < HW ? chunk * CL : HW, end = first + CL < HW ? first + CL : HW;
     const bool vec = (HW % 4 == 0) && ((reinterpret_cast<uintptr_t>(mk) & 15) == 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int base = 0;
-    for (int p0 = 0; p0 < HW; p0 += SCAN_THREADS * 8) {
-        const int p = p0 + (int)threadIdx.x * 8;
-        int v[8];
-        if (vec && p + 8 <= HW) {
-            const int4 a = *reinterpret_cast<const int4 *>(mk + p), b = *reinterpret_cast<const int4 *>(mk + p + 4);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        } else {
+    if (first > 0) {
+        // ROI pixels in front of this chunk (first is a multiple of eight, or HW for a chunk that lies beyond a small map's end)
+        int mine = 0;
+        for (int p = (int)threadIdx.x * 8; p < first; p += SCAN_THREADS * 8) {
+            if (vec && p + 8 <= first) {
+                const int4 a = *reinterpret_cast<const int4 *>(mk + p), b = *reinterpret_cast<const int4 *>(mk + p + 4);
+                mine += (a.x == 1) + (a.y == 1) + (a.z == 1) + (a.w == 1) + (b.x == 1) + (b.y == 1) + (b.z == 1) + (b.w == 1);
+            } else {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (p + e < HW) ? mk[p + e] : 0;
+                for (int e = 0; e < 8; ++e) mine += (p + e < first && mk[p + e] == 1) ? 1 : 0;
+            }
         }
-        unsigned bits = 0u;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) bits |= (v[e] == 1 ? 1u : 0u) << e;
-        int total;
-        int o = base + block_scan_counts(__popc(bits), s_wave, total);
+        for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+        if (lane == 0) s_wave[0][wave] = mine;
+        __syncthreads();
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
-            if (bits & (1u << e)) out[o++] = p + e;
-        base += total;
+        for (int w = 0; w < SCAN_WAVES; ++w) base += s_wave[0][w];
     }
-    if (threadIdx.x == 0) count[m] = base;
+    for (int p0 = first; p0 < end; p0 += RC_STEPS * SCAN_THREADS * 8) {
+        unsigned bits[RC_STEPS];
+#pragma unroll
+        for (int s = 0; s < RC_STEPS; ++s) {
+            const int p = p0 + (s * SCAN_THREADS + (int)threadIdx.x) * 8;
+            int v[8];
+            if (vec && p + 8 <= end) {
+                const int4 a = *reinterpret_cast<const int4 *>(mk + p), b = *reinterpret_cast<const int4 *>(mk + p + 4);
+                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = (p + e < end) ? mk[p + e] : 0;
+            }
+            unsigned bt = 0u;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) bt |= (v[e] == 1 ? 1u : 0u) << e;
+            bits[s] = bt;
+        }
+        // inclusive scan inside the wave, every step on its own (independent chains)
+        int incl[RC_STEPS];
+#pragma unroll
+        for (int s = 0; s < RC_STEPS; ++s) incl[s] = __popc(bits[s]);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+#pragma unroll
+            for (int s = 0; s < RC_STEPS; ++s) {
+                const int v = __shfl_up(incl[s], o);
+                incl[s] += (lane >= o) ? v : 0;
+            }
+        }
+        __syncthreads();                       // the previous group's readers of s_wave are done
+        if (lane == 63) {
+#pragma unroll
+            for (int s = 0; s < RC_STEPS; ++s) s_wave[s][wave] = incl[s];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < RC_STEPS; ++s) {
+            int before = 0, tot = 0;
+#pragma unroll
+            for (int w4 = 0; w4 < SCAN_WAVES; w4 += 4) {
+                const int4 c = *reinterpret_cast<const int4 *>(&s_wave[s][w4]);
+                before += (w4 + 0 < wave ? c.x : 0) + (w4 + 1 < wave ? c.y : 0) + (w4 + 2 < wave ? c.z : 0) + (w4 + 3 < wave ? c.w : 0);
+                tot += c.x + c.y + c.z + c.w;
+            }
+            const int p = p0 + (s * SCAN_THREADS + (int)threadIdx.x) * 8;
+            int o = base + before + incl[s] - __popc(bits[s]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if (bits[s] & (1u << e)) out[o++] = p + e;
+            base += tot;
+        }
+    }
+    if (threadIdx.x == 0) {
+        if (chunk == chunks - 1) (second ? count1 : count0)[m] = base;
+        if (zero && chunk == 0) zero[m] = 0.0f;
+    }
 }
 
 __global__ void mask_from_logits_kernel(const float *__restrict__ logits, int64_t n, float thr, int32_t *__restrict__ mask)
@@ -485,6 +560,17 @@ __global__ __launch_bounds__(256) void gather_normalise_q8_kernel(const float *_
     }
 }
 
+// the engine's K0 section (match_common.h): both mask sets of a step in one launch; zero_a / zero_q as the kernel's zero0 / zero1
+int roi_compact_pair_launch(const int32_t *mask_a, const int32_t *mask_q, int n_maps, int HW, int32_t *roi_a, int32_t *roi_q,
+                            int32_t *n_a, int32_t *n_q, float *zero_a, float *zero_q, hipStream_t st)
+{
+    if (n_maps == 0) return ORYON_OK;
+    const int chunks = roi_compact_chunks(2 * n_maps);
+    hipLaunchKernelGGL(roi_compact_kernel, dim3(2 * n_maps * chunks), dim3(SCAN_THREADS), 0, st, mask_a, mask_q, n_maps, chunks, HW, roi_a, roi_q,
+                       n_a, n_q, zero_a, zero_q);
+    return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
+}
+
 }  // namespace oryon
 
 using namespace oryon;
@@ -493,7 +579,9 @@ extern "C" int oryon_roi_compact(const int32_t *mask, int n_maps, int HW, int32_
 {
     ORYON_CHECK_ARG(mask && roi && count && n_maps >= 0 && HW > 0);
     if (n_maps == 0) return ORYON_OK;
-    hipLaunchKernelGGL(roi_compact_kernel, dim3(n_maps), dim3(SCAN_THREADS), 0, as_stream(stream), mask, HW, roi, count);
+    const int chunks = roi_compact_chunks(n_maps);
+    hipLaunchKernelGGL(roi_compact_kernel, dim3(n_maps * chunks), dim3(SCAN_THREADS), 0, as_stream(stream), mask, nullptr, n_maps, chunks, HW, roi,
+                       nullptr, count, nullptr, nullptr, nullptr);
     ORYON_CHECK_LAUNCH();
     return ORYON_OK;
 }

@@ -209,10 +209,21 @@ __device__ __forceinline__ void mx6_static_for(F &&f)
 // k-steps hold zero codes and contribute exactly 0, so they are simply not multiplied: same results, a quarter of the MFMAs at C <= 64)
 // No early exit: one was built into the loop for the cascade first, and the break cost the loop its register allocation - 161 spilled
 // registers, six times slower per tile.  A caller bounds the work by the range it passes.
-template <int CP, int WAVES, int KL>
+// Row source of the index-fed panels (IDX; the 4-wave kernel only): the panel is a LIST of rows of the pair's cap_src anchor rows - panel row
+// i is row idx[p * idx_stride + i], or row i * stride where idx == nullptr (the default-route cascade's probe) - read in place by the
+// prologue instead of from a dense copy; list rows i >= n are zero codes with exponent byte 0 (finite scores nobody reads).
+struct Mx6RowList {
+    const int32_t *idx;
+    int idx_stride, stride, cap_src;
+    int n;                              // live rows of this pair's list: set by the kernel
+};
+struct Mx6RowsInPlace {};               // IDX = false: panel row i is row i of the pair's cap_a rows
+
+template <int CP, int WAVES, int KL, bool IDX = false>
 __device__ __forceinline__ void mx6_screen_w4_tiles(char *smem, const uint8_t *__restrict__ a6, const uint8_t *__restrict__ q6, int p, int split,
                                                     int a0, int cap_a, int cap_q, int S, int qt_begin, int qt_end, float *__restrict__ ws_max,
-                                                    int32_t *__restrict__ ws_i1, float *__restrict__ ws_m2)
+                                                    int32_t *__restrict__ ws_i1, float *__restrict__ ws_m2,
+                                                    const std::conditional_t<IDX, Mx6RowList, Mx6RowsInPlace> &rows = {})
 {
     static_assert(CP == 256 || (CP == 512 && WAVES == 4), "geometries: C_pad 256 with 4 / 8 waves, C_pad 512 with 4 waves");
     constexpr int RB = CP, NAB = 4;
@@ -231,13 +242,25 @@ __device__ __forceinline__ void mx6_screen_w4_tiles(char *smem, const uint8_t *_
 #pragma unroll
     for (int ab = 0; ab < NAB; ++ab) {
         const int arow_i = a0 + wave * (32 * NAB) + ab * 32 + l31;
-        const char *arow = reinterpret_cast<const char *>(a6) + ((size_t)p * cap_a + (arow_i < cap_a ? arow_i : cap_a - 1)) * RB + 32 * hi;
+        const char *arow;
+        bool live = true;
+        if constexpr (IDX) {
+            live = arow_i < rows.n;
+            const int src = !live ? 0 : rows.idx ? rows.idx[(size_t)p * rows.idx_stride + arow_i] : arow_i * rows.stride;
+            arow = reinterpret_cast<const char *>(a6) + ((size_t)p * rows.cap_src + src) * RB + 32 * hi;
+        } else
+            arow = reinterpret_cast<const char *>(a6) + ((size_t)p * cap_a + (arow_i < cap_a ? arow_i : cap_a - 1)) * RB + 32 * hi;
         unsigned sc[NKS / 4];
 #pragma unroll
         for (int w = 0; w < NKS / 4; ++w) sc[w] = 0;
 #pragma unroll
         for (int s = 0; s < KL; ++s) {
-            const i32x4 lo = *reinterpret_cast<const i32x4 *>(arow + 64 * s), up = *reinterpret_cast<const i32x4 *>(arow + 64 * s + 16);
+            i32x4 lo = *reinterpret_cast<const i32x4 *>(arow + 64 * s), up = *reinterpret_cast<const i32x4 *>(arow + 64 * s + 16);
+            if constexpr (IDX) {
+                const i32x4 z = {0, 0, 0, 0};
+                lo = live ? lo : z;
+                up = live ? up : z;
+            }
             breg[ab][s] = __builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, -1, -1);   // the fp6 format reads six dwords
             sc[s >> 2] |= ((unsigned)up[2] & 0xffu) << (8 * (s & 3));
         }
@@ -384,6 +407,27 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
         dbg_wg[(size_t)blockIdx.x * 4 + 2] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);        // HW_REG_HW_ID
         dbg_wg[(size_t)blockIdx.x * 4 + 3] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 20);       // HW_REG_XCC_ID
     }
+}
+
+// The full screen of a LIST of a pair's anchor rows, 512 list rows per workgroup (Mx6RowList): what the cascades' probe, open-row and
+// sampled-row passes run.  count[p] rows are listed (idx), or every stride-th of the pair's count[p] rows (idx == nullptr); at most
+// cap_list, the rows the triples [B, S, cap_list] have room for.
+template <int KL>
+__global__ __launch_bounds__(256, 2) void match_mx6_screen_w4_list_kernel(
+    const uint8_t *__restrict__ a6, const uint8_t *__restrict__ q6, int B, int cap_src, int cap_list, int cap_q, const int32_t *__restrict__ count,
+    const int32_t *__restrict__ idx, int idx_stride, int stride, const int32_t *__restrict__ n_q, int T, int S, float *__restrict__ ws_max,
+    int32_t *__restrict__ ws_i1, float *__restrict__ ws_m2)
+{
+    __shared__ __attribute__((aligned(256))) char smem_st_w4l[2 * screen8_tile_bytes(256)];
+    ScreenUnit u;
+    if (!screen_unit_decode(u, 512, B, T, S, count, n_q)) return;
+    Mx6RowList rows = {idx, idx_stride, stride, cap_src, 0};
+    const int listed = idx ? u.na : (u.na + stride - 1) / stride;
+    rows.n = listed < cap_list ? listed : cap_list;
+    if (u.a0 >= rows.n) return;
+    int qt_begin, qt_end;
+    screen_split_tiles(u, S, qt_begin, qt_end);
+    mx6_screen_w4_tiles<256, 4, KL, true>(smem_st_w4l, a6, q6, u.p, u.split, u.a0, cap_list, cap_q, S, qt_begin, qt_end, ws_max, ws_i1, ws_m2, rows);
 }
 
 // The cascades' launches: the same loop over a part of the split's tiles, or for a part of the panels.
@@ -567,17 +611,19 @@ void launch_screen_mx6(int C, int groups, int T, hipStream_t st, const uint8_t *
     else launch_screen_mx6_t<512>(groups, T, st, a6, q6, B, cap_a, cap_q, n_a, n_q, S, ws_max, ws_i1, ws_m2);
 }
 
-// The complete screen over compacted anchor rows in 512-row panels (match_compact_rows_kernel): T = ceil(cap_rows / 512) panels per pair,
-// the query tiles of a pair dealt to S workgroups of four waves (two per CU) per panel; panels beyond a pair's row count return at once.
-// Same kernel, same scores, same slice ids as the full screen.  Triples come out as [B, S, cap_rows].
-void launch_screen_mx6_rows512(hipStream_t st, const uint8_t *a6_rows, const uint8_t *q6, int B, int cap_rows, int cap_q, const int32_t *n_rows,
-                               const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true)
+// The complete screen of a LIST of a pair's anchor rows, read in place, in 512-row panels (match_mx6_screen_w4_list_kernel): T =
+// ceil(cap_list / 512) panels per pair, the query tiles of a pair dealt to S workgroups of four waves (two per CU) per panel; panels
+// beyond a pair's list return at once.  Same loop, same scores, same slice ids as the full screen.  idx == nullptr: every stride-th row.
+// Triples come out as [B, S, cap_list], indexed by list slot.
+void launch_screen_mx6_list512(hipStream_t st, const uint8_t *a6, const uint8_t *q6, int B, int cap_src, int cap_list, int cap_q,
+                               const int32_t *count, const int32_t *idx, int idx_stride, int stride, const int32_t *n_q, int S, float *ws_max,
+                               int32_t *ws_i1, float *ws_m2, int C_true)
 {
-    const int T = (cap_rows + 511) / 512;
+    const int T = (cap_list + 511) / 512;
     const int groups = ((B * S + 7) / 8) * 8 * T;
     mx6_with_kl(mx6_live_ksteps(C_true), [&](auto KLC) {
-        hipLaunchKernelGGL((match_mx6_screen_w4_kernel<256, 4, decltype(KLC)::value>), dim3(groups), dim3(256), 0, st, a6_rows, q6, B, cap_rows, cap_q,
-                           n_rows, n_q, T, S, ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
+        hipLaunchKernelGGL((match_mx6_screen_w4_list_kernel<decltype(KLC)::value>), dim3(groups), dim3(256), 0, st, a6, q6, B, cap_src, cap_list,
+                           cap_q, count, idx, idx_stride, stride, n_q, T, S, ws_max, ws_i1, ws_m2);
     });
 }
 
@@ -593,14 +639,6 @@ void launch_screen_mx6_band512(hipStream_t st, const uint8_t *a6, const uint8_t 
         hipLaunchKernelGGL((match_mx6_screen_w4_win_kernel<256, 4, decltype(KLC)::value>), dim3(groups), dim3(256), 0, st, a6, q6, B, cap_a, cap_q,
                            n_a, n_q, T, S, ws_max, ws_i1, ws_m2, static_cast<const int32_t *>(nullptr), 0, band, band_T);
     });
-}
-
-// Second pass of the validity cascades: ONE 512-row panel per pair (the sampled anchors whose argmin is open): a tenth of the full
-// screen's multiply-accumulates, spread over the whole chip.
-void launch_screen_mx6_sampled(hipStream_t st, const uint8_t *a6_panel, const uint8_t *q6, int B, int cap_q, const int32_t *n_rows,
-                               const int32_t *n_q, int S, float *ws_max, int32_t *ws_i1, float *ws_m2, int C_true)
-{
-    launch_screen_mx6_rows512(st, a6_panel, q6, B, MX6_SAMPLED_PANEL, cap_q, n_rows, n_q, S, ws_max, ws_i1, ws_m2, C_true);
 }
 
 }  // namespace oryon
