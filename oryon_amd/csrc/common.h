@@ -46,6 +46,8 @@ void profile_end(hipStream_t st);
 
 // Development switches.  The SHIPPED library (make all) reads no environment variable: dev_env_* return their defaults.  The dev build
 // (make dev -> liboryon_hip_dev.so, -DORYON_DEV; what the A/B scripts under tools/ load) reads them.
+// A switch exists only while a test, a tool without a round number in its name, or README / DESIGN / INTEGRATION.md sets or documents it
+// (tests/test_dev_switches.py holds the list); one that nothing uses any more goes, together with the code only it reached.
 #ifdef ORYON_DEV
 static inline int dev_env_int(const char *name, int dflt) { const char *s = getenv(name); return s ? atoi(s) : dflt; }
 static inline bool dev_env_set(const char *name) { return getenv(name) != nullptr; }

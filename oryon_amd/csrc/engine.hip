@@ -373,11 +373,10 @@ extern "C" int oryon_engine_create(oryon_engine_t **handle, const oryon_engine_c
     // has one) registration 0 on pool stream 0 loses the pipeline (2301: 1.47 -> 2.42 ms), 2345 / 2341 / 6345 / 6341 stay at 1.44-1.47 in
     // both cases; in a plain process the gather on pool stream 7 costs 13 %.  Hence the default 2345.  cfg.stream_roles names the placement
     // (0 = that default); oryon_engine_set_stream_roles changes it on a live engine, which is how a host measures the candidates on ITS
-    // process (oryon_amd.engine.MatchPoseEngine.tune_stream_roles).  (dev build: ORYON_ENGINE_ROLES overrides the default)
-    static const int default_roles = dev_env_int("ORYON_ENGINE_ROLES", DEFAULT_ROLES);
+    // process (oryon_amd.engine.MatchPoseEngine.tune_stream_roles).
     e->n_reg_streams = cfg->reg_streams;
     for (int s = 0; s < MAX_REG_STREAMS; ++s) e->sr[s] = nullptr;
-    if (assign_roles(e, cfg->stream_roles > 0 ? cfg->stream_roles : (roles_valid(default_roles) ? default_roles : DEFAULT_ROLES)) != ORYON_OK)
+    if (assign_roles(e, cfg->stream_roles > 0 ? cfg->stream_roles : DEFAULT_ROLES) != ORYON_OK)
         err = hipErrorUnknown;
     for (int s = 0; s < MAX_SLOTS; ++s) {
         e->used[s] = false;

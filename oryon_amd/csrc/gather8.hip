@@ -777,8 +777,7 @@ int gather_q8_launch(const float *feat, int n_maps, int C, int HW, int layout, c
     // K0v4 (round 5): the MX-fp6 passes over channel-planar maps of up to 256 channels - narrow maps (the reference's C = 32) included:
     // waves whose 64 channels lie beyond C load nothing and contribute zero blocks (smooth C = 32 @ 192 x 192 step 2.89 -> 2.77 ms);
     // channels_last, C_pad 512 and the device-gated fall-back passes stay on K0v3
-    static const int v4 = dev_env_int("ORYON_K0V4", 1);
-    if ((fmt == 1 || (fmt == 3 && aux && scale && !out32)) && v4 && C_pad == 256 && layout == ORYON_LAYOUT_NCHW && !map_enable &&
+    if ((fmt == 1 || (fmt == 3 && aux && scale && !out32)) && C_pad == 256 && layout == ORYON_LAYOUT_NCHW && !map_enable &&
         (lanes_per_row != 2 || fmt == 3)) {
         const int T = (rows_cap + 63) / 64;
         const int chunks_per_map = n_maps >= 8 ? 1 : (8 + n_maps - 1) / n_maps;

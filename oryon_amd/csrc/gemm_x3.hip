@@ -7,7 +7,7 @@
 // caller.  Optional fused QuickGELU (x * sigmoid(1.702 x), CLIP's activation) in the epilogue.
 //
 // Two kernels: the persistent 256 x 256 x 32 stream kernel below (the one that runs; K >= 64), and a small-tile kernel for K = 32 and
-// as a cross-check (ORYON_GEMM_X3_VARIANT=1): tile 128 x 256 x 32, 4 waves (2 x 2, 64 x 128 each = eight 32x32 accumulators),
+// for N * K >= 2^30: tile 128 x 256 x 32, 4 waves (2 x 2, 64 x 128 each = eight 32x32 accumulators),
 // operands in padded LDS rows (40 halves: conflict-free ds_read_b128 for the 32x32x16 fragment layout), next tile's global loads in
 // flight under the current tile's 48 MFMAs per wave.  Both accumulate every output in the same order (k ascending, per k-step
 // lo*hi, hi*lo, hi*hi), so their results are bit-identical.
@@ -537,8 +537,7 @@ static int linear_f16x3_impl(const float *A, int M, int K, const void *W_hi, con
     ORYON_CHECK_ARG(K % GX_BK == 0 && act >= 0 && act <= 2);
     ORYON_CHECK_ARG(N % GX_BN == 0 || (N % 128 == 0 && K >= 2 * G2_BK && (size_t)N * (size_t)K < (1ull << 30)));   // half-wide last column tile: stream kernel only
     if (M == 0) return ORYON_OK;
-    static const int variant = dev_env_int("ORYON_GEMM_X3_VARIANT", 2);      // dev: 1 = small-tile kernel
-    if ((variant != 1 || N % GX_BN != 0 || !W_lo || accumulate) && K >= 2 * G2_BK && (size_t)N * (size_t)K < (1ull << 30)) {
+    if (K >= 2 * G2_BK && (size_t)N * (size_t)K < (1ull << 30)) {          // the stream kernel; else the small-tile kernel
         const int tiles_m = (M + G2_BM - 1) / G2_BM, tiles_n = (N + G2_BN - 1) / G2_BN;
         const int sup_n = (tiles_n + 7) / 8;
         const int sup_cols = (tiles_n + sup_n - 1) / sup_n;

@@ -208,7 +208,7 @@ __global__ __launch_bounds__(MATCH_THREADS, 2) void match_f32_kernel(
 //   * Work units: (pair, query split) units are dealt round-robin to the 8 XCDs (blockIdx & 7) and all anchor
 //     panels of a unit sit on ONE XCD, so a unit's query stream is fetched once per XCD and shared through
 //     that XCD's L2; several splits per pair keep the tail of the launch short.
-template <int CP, int VAR = 0>   // VAR != 0: timing ablations only (ORYON_MATCH_VARIANT), results are then meaningless
+template <int CP>
 __global__ __launch_bounds__(MATCH_THREADS, 2) void match_f32_regb_kernel(
     const float *__restrict__ a_hat, const float *__restrict__ q_hat, int B, int cap_a, int cap_q,
     const int32_t *__restrict__ n_a, const int32_t *__restrict__ n_q, float thr, int T, int S,
@@ -309,21 +309,19 @@ __global__ __launch_bounds__(MATCH_THREADS, 2) void match_f32_regb_kernel(
     for (int qt = qt_begin; qt < qt_end; ++qt) {
 #pragma unroll
         for (int kp = 0; kp < KP; ++kp) {
-            if (!(VAR & 2)) {
-                if (kp + 1 < KP) issue(qt, kp + 1, buf ^ 1);
-                else if (qt + 1 < qt_end) issue(qt + 1, 0, buf ^ 1);
-            }
+            if (kp + 1 < KP) issue(qt, kp + 1, buf ^ 1);
+            else if (qt + 1 < qt_end) issue(qt + 1, 0, buf ^ 1);
             const unsigned tile = buf * TILE_BYTES;
             float4 ring[RG][NACC];
 #pragma unroll
             for (int g = 0; g < RG - 1; ++g)
 #pragma unroll
-                for (int m = 0; m < NACC; ++m) ring[g][m] = (VAR & 4) ? make_float4(1.f, 2.f, 3.f, 4.f) : rd(g, m, tile);
+                for (int m = 0; m < NACC; ++m) ring[g][m] = rd(g, m, tile);
 #pragma unroll
             for (int g = 0; g < NGT; ++g) {
                 // reads of group g+RG-1 go out first (their ring slot was freed by group g-1), then the 4*NACC MFMAs of
                 // group g, accumulators round-robin so consecutive MFMAs are independent
-                if (!(VAR & 4) && g + RG - 1 < NGT) {
+                if (g + RG - 1 < NGT) {
 #pragma unroll
                     for (int m = 0; m < NACC; ++m) ring[(g + RG - 1) % RG][m] = rd(g + RG - 1, m, tile);
                 }
@@ -339,48 +337,38 @@ __global__ __launch_bounds__(MATCH_THREADS, 2) void match_f32_regb_kernel(
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (kp == KP - 1) {
-                if (VAR & 1) {
+                const int qlane = qt * ROWS + 4 * hi;
+                const bool full = (qt + 1) * ROWS <= nq;
+                // dist = fma(-0.5, dot, 0.5) is monotone in dot, so the tile's smallest distance is the image of its
+                // largest dot product: one max tree + one fma decide whether ANY lane of the wave improves.  Only then
+                // (ever rarer as the running minimum settles) is the exact first-index search below executed.
+                float mx = acc[0][0];
+#pragma unroll
+                for (int m = 0; m < NACC; ++m)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, acc[m][r]);
+                const bool improves = __fmaf_rn(-0.5f, mx, 0.5f) < best;
+                if (!full || __any(improves)) {
 #pragma unroll
                     for (int m = 0; m < NACC; ++m)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(acc[m][r]));
-                    if (qt == qt_end - 1) best = acc[0][0];
-                } else {
-                    const int qlane = qt * ROWS + 4 * hi;
-                    const bool full = (qt + 1) * ROWS <= nq;
-                    // dist = fma(-0.5, dot, 0.5) is monotone in dot, so the tile's smallest distance is the image of its
-                    // largest dot product: one max tree + one fma decide whether ANY lane of the wave improves.  Only then
-                    // (ever rarer as the running minimum settles) is the exact first-index search below executed.
-                    float mx = acc[0][0];
-#pragma unroll
-                    for (int m = 0; m < NACC; ++m)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, acc[m][r]);
-                    const bool improves = __fmaf_rn(-0.5f, mx, 0.5f) < best;
-                    if (!full || __any(improves)) {
-#pragma unroll
-                        for (int m = 0; m < NACC; ++m)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                const int q = qlane + m * 32 + (r & 3) + 8 * (r >> 2);
-                                float d = __fmaf_rn(-0.5f, acc[m][r], 0.5f);
-                                if (!full) d = (q < nq) ? d : INFINITY;
-                                const bool better = d < best;     // strict: first (smallest) query index wins ties
-                                best = better ? d : best;
-                                bidx = better ? q : bidx;
-                            }
-                    }
-#pragma unroll
-                    for (int m = 0; m < NACC; ++m)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[m][r] = 0.0f;
+                        for (int r = 0; r < 16; ++r) {
+                            const int q = qlane + m * 32 + (r & 3) + 8 * (r >> 2);
+                            float d = __fmaf_rn(-0.5f, acc[m][r], 0.5f);
+                            if (!full) d = (q < nq) ? d : INFINITY;
+                            const bool better = d < best;     // strict: first (smallest) query index wins ties
+                            best = better ? d : best;
+                            bidx = better ? q : bidx;
+                        }
                 }
+#pragma unroll
+                for (int m = 0; m < NACC; ++m)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[m][r] = 0.0f;
             }
-            if (!(VAR & 2)) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                buf ^= 1;
-            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            buf ^= 1;
         }
     }
     {
@@ -494,15 +482,7 @@ extern "C" int oryon_match_f32(const float *a_hat, const float *q_hat, int B, in
     if (C == 32) LAUNCH_REGB(32);
     else if (C == 64) LAUNCH_REGB(64);
     else if (C == 128) LAUNCH_REGB(128);
-    else if (C == 256) {
-        static const int var = dev_env_int("ORYON_MATCH_VARIANT", 0);
-#define LAUNCH_VAR(V) hipLaunchKernelGGL((match_f32_regb_kernel<256, V>), dim3(groups_regb), dim3(MATCH_THREADS), 0, st, a_hat, q_hat, B, cap_a, cap_q, n_a, n_q, threshold, T, S, min_dist, argmin, valid, ws_dist, ws_idx, nullptr, nullptr)
-        switch (var) {
-            case 1: LAUNCH_VAR(1); break; case 2: LAUNCH_VAR(2); break; case 3: LAUNCH_VAR(3); break; case 4: LAUNCH_VAR(4); break;
-            case 5: LAUNCH_VAR(5); break; case 6: LAUNCH_VAR(6); break; case 7: LAUNCH_VAR(7); break; default: LAUNCH_REGB(256);
-        }
-#undef LAUNCH_VAR
-    }
+    else if (C == 256) LAUNCH_REGB(256);
     else   // wide descriptors (e.g. C = 512): operands do not fit the register file, stage both through LDS
         hipLaunchKernelGGL(match_f32_kernel, dim3(groups), dim3(MATCH_THREADS), 0, st, a_hat, q_hat, B, C, cap_a, cap_q, n_a, n_q,
                            threshold, T, S, min_dist, argmin, valid, ws_dist, ws_idx, nullptr, nullptr);

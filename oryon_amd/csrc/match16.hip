@@ -3,10 +3,12 @@
 // Same contract as K1 (utils/pcd.py:202-205: dist = 0.5*(1-cos), row amin/argmin, < threshold) for every
 // anchor row that can possibly be valid, at a fraction of the fp32-MFMA cost:
 //
-//   pass 0  s16_ij = a16_i . q16_j on v_mfma_f32_32x32x16_f16 (IEEE-half copies of the unit rows, fp32 accumulate);
-//           per anchor only max_j s16_ij is kept.
-//   pass 1  the same products again; every j with s16_ij >= max_i - MARGIN is appended to anchor i's candidate list.
-//           Rows with max_i < (1 - 2*threshold) - DELTA can never pass the threshold: no candidates, valid = 0.
+//   screen  s16_ij = a16_i . q16_j on v_mfma_f32_32x32x16_f16 (IEEE-half copies of the unit rows, fp32 accumulate);
+//           per anchor the maximum max_i, the 16-row slice it lies in and the best maximum of any other slice are kept (MODE 2).
+//   pass 1  every j with s16_ij >= max_i - MARGIN goes to anchor i's candidate list: from the winning slice alone where the
+//           runner-up slice is further than MARGIN away (match_decide_kernel), else by the same products again over the compacted
+//           ambiguous anchors (MODE 1).  Rows with max_i < (1 - 2*threshold) - DELTA can never pass the threshold: no candidates,
+//           valid = 0.
 //   pass 2  candidates are re-scored with the canonical fp32 fmaf chain of K1 (bit-exact vs the oracle) and the first
 //           index of the smallest distance wins.  Lists that overflow (duplicate-heavy inputs) flag their anchor panel,
 //           which is then recomputed by the exact fp32 kernel (match_f32_regb_kernel) - still no host round trip.
@@ -50,7 +52,7 @@ __device__ __noinline__ void emit_candidates(const float *vals, float thr, int q
         }
 }
 
-template <int CP, int MODE, int VAR = 0>   // VAR != 0: timing ablations only (ORYON_MATCH16_VARIANT)
+template <int CP, int MODE>   // MODE 2: the pass over all anchors (slice maxima); MODE 1: the candidate pass over the ambiguous ones
 __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_f16_screen_kernel(
     const __half *__restrict__ a16, const __half *__restrict__ q16, int B, int cap_a, int cap_q,
     const int32_t *__restrict__ n_a, const int32_t *__restrict__ n_q, int T, int S, float valid_cut,
@@ -157,7 +159,7 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_f16_screen_kerne
 
     int buf = 0;
     for (int qt = qt_begin; qt < qt_end; ++qt) {
-        if (!(VAR & 2) && qt + 1 < qt_end) issue(qt + 1, buf ^ 1);
+        if (qt + 1 < qt_end) issue(qt + 1, buf ^ 1);
         const unsigned tile = buf * TILE_BYTES;
         half8 ring[2][NQB];
 #pragma unroll
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_f16_screen_kerne
         for (int s = 0; s < NKS; ++s) {
             if (s + 1 < NKS) {
 #pragma unroll
-                for (int qb = 0; qb < NQB; ++qb) ring[(s + 1) & 1][qb] = (VAR & 4) ? ring[s & 1][qb] : rd(s + 1, qb, tile);
+                for (int qb = 0; qb < NQB; ++qb) ring[(s + 1) & 1][qb] = rd(s + 1, qb, tile);
             }
 #pragma unroll
             for (int qb = 0; qb < NQB; ++qb)
@@ -174,17 +176,6 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_f16_screen_kerne
                 for (int ab = 0; ab < NAB; ++ab)
                     acc[qb][ab] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ring[s & 1][qb], breg[ab][s], acc[qb][ab], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-        }
-        if (VAR & 1) {
-#pragma unroll
-            for (int qb = 0; qb < NQB; ++qb)
-#pragma unroll
-                for (int ab = 0; ab < NAB; ++ab)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(acc[qb][ab][r]));
-            if (qt == qt_end - 1) runmax[0] = acc[0][0][0];
-            if (!(VAR & 2)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); buf ^= 1; }
-            continue;
         }
         // epilogue: lane owns anchor column (ab, l31); rows of the C/D block are queries.
         // Rows >= n_q of the last tile need no masking: K0 zero-fills them, so they score exactly 0, which can neither
@@ -199,9 +190,7 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_f16_screen_kerne
 #pragma unroll
                     for (int r = 0; r < 16; ++r) m = fmaxf(m, acc[qb][ab][r]);
             }
-            if (MODE == 0) {
-                runmax[ab] = fmaxf(runmax[ab], m);
-            } else if (MODE == 2) {
+            if (MODE == 2) {
                 // per (tile, query block) SLICE maxima only: running (m1, slice id of m1, m2 = best slice maximum other than
                 // m1's slice).  16 rows of one lane half form a slice; what happens INSIDE the winning slice is resolved by
                 // match_decide_kernel, which re-scores just those 16 rows.
@@ -215,7 +204,7 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_f16_screen_kerne
                     runmax[ab] = fmaxf(runmax[ab], x);
                     runidx[ab] = improved ? ((qt * NQB + qb) * 2 + hi) : runidx[ab];
                 }
-            } else if (!(VAR & 8) && __any(m >= thr[ab])) {
+            } else if (__any(m >= thr[ab])) {
                 float vals[NQB * 16];
 #pragma unroll
                 for (int qb = 0; qb < NQB; ++qb)
@@ -230,19 +219,9 @@ __global__ __launch_bounds__(256, CP == 512 ? 1 : 2) void match_f16_screen_kerne
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[qb][ab][r] = 0.0f;
         }
-        if (!(VAR & 2)) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            buf ^= 1;
-        }
-    }
-    if (MODE == 0) {
-#pragma unroll
-        for (int ab = 0; ab < NAB; ++ab) {
-            const float m = fmaxf(runmax[ab], __shfl_xor(runmax[ab], 32));
-            const int a = a0 + wave * 64 + ab * 32 + l31;
-            if (hi == 0) ws_max[((size_t)p * S + split) * cap_a + a] = m;
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        buf ^= 1;
     }
     // (cap_a is a multiple of this kernel's 256-anchor panels: the helper's a < cap_a holds for every lane)
     if (MODE == 2) screen_merge_store<NAB>(runmax, run2, runidx, a0 + wave * 64 + l31, hi, (size_t)p * S + split, cap_a, ws_max, ws_i1, ws_m2);
@@ -872,8 +851,7 @@ __global__ __launch_bounds__(256) void match_scatter8_kernel(int cap_a, const in
 
 int pick_split16(int B, int T)
 {
-    static const int target = dev_env_int("ORYON_SCREEN_WGS", 8192);     // timing experiments only
-    int S = (target + B * T - 1) / (B * T);
+    int S = (8192 + B * T - 1) / (B * T);
     if (S < 1) S = 1;
     if (S > 16) S = 16;
     return S;
@@ -953,12 +931,12 @@ struct Screen16Args {       // the arguments of match_f16_screen_kernel
 };
 
 // one launcher per descriptor width; C = 512 needs 2 x 64 KB of dynamic LDS (opt-in above 64 KB)
-template <int CP, int MODE, int VAR = 0>
+template <int CP, int MODE>
 void launch_screen(int groups, hipStream_t st, const Screen16Args &k)
 {
     constexpr size_t dyn = 2 * screen_tile_bytes(CP) > 65536 ? 2 * screen_tile_bytes(CP) : 0;
-    if (dyn) allow_dynamic_lds(reinterpret_cast<const void *>(&match_f16_screen_kernel<CP, MODE, VAR>), (int)dyn);
-    hipLaunchKernelGGL((match_f16_screen_kernel<CP, MODE, VAR>), dim3(groups), dim3(256), dyn, st, k.a16, k.q16, k.B, k.cap_a, k.cap_q, k.n_a,
+    if (dyn) allow_dynamic_lds(reinterpret_cast<const void *>(&match_f16_screen_kernel<CP, MODE>), (int)dyn);
+    hipLaunchKernelGGL((match_f16_screen_kernel<CP, MODE>), dim3(groups), dim3(256), dyn, st, k.a16, k.q16, k.B, k.cap_a, k.cap_q, k.n_a,
                        k.n_q, k.T, k.S, k.valid_cut, k.ws_max, k.cnt, k.cand, k.S_thr, k.row_map, k.ws_i1, k.ws_m2);
 }
 
@@ -966,10 +944,10 @@ using Screen16Fn = void (*)(int, hipStream_t, const Screen16Args &);
 
 void launch_screen16(int C, int mode, int groups, hipStream_t st, const Screen16Args &k)
 {
-    static const Screen16Fn by_width[3][3] = {{launch_screen<128, 0>, launch_screen<128, 1>, launch_screen<128, 2>},
-                                              {launch_screen<256, 0>, launch_screen<256, 1>, launch_screen<256, 2>},
-                                              {launch_screen<512, 0>, launch_screen<512, 1>, launch_screen<512, 2>}};
-    by_width[C == 128 ? 0 : C == 256 ? 1 : 2][mode](groups, st, k);
+    static const Screen16Fn by_width[3][2] = {{launch_screen<128, 1>, launch_screen<128, 2>},
+                                              {launch_screen<256, 1>, launch_screen<256, 2>},
+                                              {launch_screen<512, 1>, launch_screen<512, 2>}};
+    by_width[C == 128 ? 0 : C == 256 ? 1 : 2][mode - 1](groups, st, k);
 }
 }  // namespace
 
@@ -1013,47 +991,30 @@ extern "C" int oryon_match_screened(const float *a_hat, const float *q_hat, cons
     all.row_map = nullptr;
     all.ws_i1 = w.ws_i1;
     all.ws_m2 = w.ws_m2;
-    static const int var16 = dev_env_int("ORYON_MATCH16_VARIANT", 0);
-    static const bool two_pass = dev_env_set("ORYON_SCREEN_TWOPASS");
-    const float *m_final = nullptr;
-    if (C == 256 && var16 == 8) {
-        launch_screen<256, 0>(groups, st, all);
-        launch_screen<256, 1, 8>(groups, st, all);
-    } else if (C == 256 && var16) {
-        static const Screen16Fn variant[7] = {launch_screen<256, 0, 1>, launch_screen<256, 0, 2>, launch_screen<256, 0, 3>, launch_screen<256, 0, 4>,
-                                              launch_screen<256, 0, 5>, launch_screen<256, 0, 6>, launch_screen<256, 0, 7>};
-        variant[(var16 >= 1 && var16 <= 6 ? var16 : 7) - 1](groups, st, all);
-        launch_screen<256, 1>(groups, st, all);
-    } else if (two_pass || var16) {
-        launch_screen16(C, 0, groups, st, all);
-        launch_screen16(C, 1, groups, st, all);
-    } else {
-        // single screening pass keeping (max, argmax, second max) per anchor; anchors whose runner-up is within MARGIN of the
-        // maximum (duplicates, smooth descriptor fields) go through a second, compacted candidate pass
-        profile_begin(st, C == 256 ? "match_f16_screen_kernel<256, 2>" : C == 512 ? "match_f16_screen_kernel<512, 2>" : "match_f16_screen_kernel<128, 2>");
-        launch_screen16(C, 2, groups, st, all);
-        profile_end(st);
-        ORYON_CHECK_LAUNCH();
-        hipLaunchKernelGGL(C >= 256 ? match_decide_kernel<64> : match_decide_kernel<128>, dim3(cap_a / 64, B), dim3(256), 0, st, a16, q16, C,
-                           cap_a, cap_q, n_a, n_q, S, valid_cut, w.ws_max, w.ws_i1, w.ws_m2, w.m_final, w.cnt, w.cand, w.n_amb, w.amb_idx,
-                           nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr);
-        hipLaunchKernelGGL(match_compact_kernel, dim3(cap_a / 64, B), dim3(256), 0, st, a16, C, cap_a, w.n_amb, w.amb_idx, w.m_final,
-                           w.a16c, w.amb_max);
-        Screen16Args amb = all;     // the candidate pass over the compacted ambiguous anchors
-        amb.a16 = w.a16c;
-        amb.n_a = w.n_amb;
-        amb.ws_max = w.amb_max;
-        amb.S_thr = 1;
-        amb.row_map = w.amb_idx;
-        amb.ws_i1 = nullptr;
-        amb.ws_m2 = nullptr;
-        launch_screen16(C, 1, groups, st, amb);
-        m_final = w.m_final;
-    }
+    // single screening pass keeping (max, argmax, second max) per anchor; anchors whose runner-up is within MARGIN of the
+    // maximum (duplicates, smooth descriptor fields) go through a second, compacted candidate pass
+    profile_begin(st, C == 256 ? "match_f16_screen_kernel<256, 2>" : C == 512 ? "match_f16_screen_kernel<512, 2>" : "match_f16_screen_kernel<128, 2>");
+    launch_screen16(C, 2, groups, st, all);
+    profile_end(st);
+    ORYON_CHECK_LAUNCH();
+    hipLaunchKernelGGL(C >= 256 ? match_decide_kernel<64> : match_decide_kernel<128>, dim3(cap_a / 64, B), dim3(256), 0, st, a16, q16, C,
+                       cap_a, cap_q, n_a, n_q, S, valid_cut, w.ws_max, w.ws_i1, w.ws_m2, w.m_final, w.cnt, w.cand, w.n_amb, w.amb_idx,
+                       nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(match_compact_kernel, dim3(cap_a / 64, B), dim3(256), 0, st, a16, C, cap_a, w.n_amb, w.amb_idx, w.m_final,
+                       w.a16c, w.amb_max);
+    Screen16Args amb = all;     // the candidate pass over the compacted ambiguous anchors
+    amb.a16 = w.a16c;
+    amb.n_a = w.n_amb;
+    amb.ws_max = w.amb_max;
+    amb.S_thr = 1;
+    amb.row_map = w.amb_idx;
+    amb.ws_i1 = nullptr;
+    amb.ws_m2 = nullptr;
+    launch_screen16(C, 1, groups, st, amb);
     ORYON_CHECK_LAUNCH();
     // 4 lanes per anchor: 16 -> 394 us, 8 -> 230, 4 -> 184, 2 -> 175, 1 -> 200 us at cfg2 (almost every anchor has one candidate)
     hipLaunchKernelGGL((match_rescore_kernel<4>), dim3(cap_a / 64, B), dim3(256), 0, st, a_hat, q_hat, C, cap_a, cap_q, n_a, n_q, S,
-                       threshold, valid_cut, w.ws_max, m_final, w.cnt, w.cand, min_dist, argmin, valid, w.row_flag, w.panel_flag);
+                       threshold, valid_cut, w.ws_max, w.m_final, w.cnt, w.cand, min_dist, argmin, valid, w.row_flag, w.panel_flag);
     ORYON_CHECK_LAUNCH();
     // exact recomputation of the (rare) panels whose candidate lists overflowed; exits immediately elsewhere
     return match_f32_flagged(a_hat, q_hat, B, C, cap_a, cap_q, n_a, n_q, threshold, min_dist, argmin, valid, w.panel_flag,

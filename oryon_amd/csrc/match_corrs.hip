@@ -239,27 +239,6 @@ __global__ __launch_bounds__(256) void match_panel_settle_kernel(int cap_a, int 
             for (int s_ = 0; s_ < S; ++s_) ws_m2[((size_t)p * S + s_) * cap_a + a] = INFINITY;
 }
 
-// the listed rows as dense panels (the dev build's sweep of the open rows' scan with the 8-wave kernel: ORYON_DC_OPEN_PANEL=1024; every
-// shipped route reads its lists in place, launch_screen_mx6_list512)
-__global__ __launch_bounds__(256) void match_compact_rows_kernel(const uint8_t *__restrict__ rows, int row_bytes, int cap_a, int cap_c,
-                                                                  const int32_t *__restrict__ count, const int32_t *__restrict__ idx,
-                                                                  int idx_stride, uint8_t *__restrict__ out, int fill_mult)
-{
-    // 16 lanes per 256-byte row (uint4 each); rows [count, round_up(count, fill_mult)) - the rest of the last panel a screen launch
-    // reads - are zero rows (exponent byte 0: finite scores nobody reads)
-    const int p = blockIdx.y, sl = blockIdx.x * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
-    if (sl >= cap_c) return;
-    const int n = count[p] < cap_c ? count[p] : cap_c;
-    if (sl >= (n + fill_mult - 1) / fill_mult * fill_mult) return;
-    uint4 *d = reinterpret_cast<uint4 *>(out + ((size_t)p * cap_c + sl) * row_bytes);
-    if (sl >= n) {
-        for (int i = l; i < row_bytes / 16; i += 16) d[i] = make_uint4(0, 0, 0, 0);
-        return;
-    }
-    const uint4 *src = reinterpret_cast<const uint4 *>(rows + ((size_t)p * cap_a + idx[(size_t)p * idx_stride + sl]) * row_bytes);
-    for (int i = l; i < row_bytes / 16; i += 16) d[i] = src[i];
-}
-
 // One workgroup per pair, a thread per row of the sampled panel: the rows' decisions, then - behind a barrier - the second level's list of
 // the rows that stay ambiguous (list_sampled_amb; count / idx are that list's own n_list / list, rebuilt in place).
 constexpr int DS_THREADS = 512;
@@ -312,7 +291,7 @@ __global__ __launch_bounds__(DS_THREADS) void match_decide_sampled_kernel(int ca
 // leaves the rows of a settled panel).  Scores of an (anchor, query) pair do not depend on the panel the anchor row sits in, and the
 // merged triple not on how the tiles are dealt to splits (ties go to the lowest slice either way): complete triples are today's.
 // (DC_COMPLETE / DC_SETTLED / DC_OPEN: at the head of the file, for the decide pass)
-constexpr int DC_SLACK = 2;            // tiles added at either end of a learned band (ORYON_DC_SLACK in the dev build)
+constexpr int DC_SLACK = 2;            // tiles added at either end of a learned band
 constexpr int DC_MIN_SURE = 8;          // a panel with fewer valid-for-sure probe rows scans all tiles
 constexpr int DC_BAND_CAP_NUM = 1, DC_BAND_CAP_DEN = 2;     // ... and so does one whose band exceeds this share of the pair's tiles
 
@@ -688,24 +667,21 @@ int sampled_cap(int corr_rows, int cap_a)
 // The default route's cascade is chosen by shape alone: three 1024-row panels or more (below that the 512-row probe is no small
 // fraction of the anchors; the sample-first first stage has one panel), the second pass's 512-row panel large enough for the sample
 bool dc_shape(int C, int cap_a, int corr_rows) { return C == 256 && corr_rows <= MX6_SAMPLED_PANEL && mx6_panels_per_pair(cap_a) >= 3; }
-// (ORYON_DC_STRIDE / _SLACK / _BAND_SPLITS / _OPEN_SPLITS: the dev build's overrides, for sweeps; the shipped library reads none)
+// the probe takes every 10th anchor, fewer where they would not fit its one 512-row panel
 int dc_probe_stride(int cap_a)
 {
-    static const int want = dev_env_int("ORYON_DC_STRIDE", 10);
     const int s = (cap_a + MX6_SAMPLED_PANEL - 1) / MX6_SAMPLED_PANEL;
-    return s > want ? s : want;
+    return s > 10 ? s : 10;
 }
 // splits of the band pass (4-wave workgroups over 512-row halves, two per CU: ~2.5 per place) and of the open rows' scan (the same kernel geometry)
 int dc_band_splits(int B, int cap_a)
 {
-    static const int force = dev_env_int("ORYON_DC_BAND_SPLITS", 0);
-    const int u = B * 2 * mx6_panels_per_pair(cap_a), s = force > 0 ? force : (1280 + u - 1) / u;
+    const int u = B * 2 * mx6_panels_per_pair(cap_a), s = (1280 + u - 1) / u;
     return s < 1 ? 1 : s > 16 ? 16 : s;
 }
 int dc_open_splits(int B)
 {
-    static const int force = dev_env_int("ORYON_DC_OPEN_SPLITS", 0);
-    const int s = force > 0 ? force : (1024 + B - 1) / B;
+    const int s = (1024 + B - 1) / B;
     return s < 1 ? 1 : s > 16 ? 16 : s;
 }
 size_t carve_dc(void *base, LazyWs &w, int B, int C, int cap_a)
@@ -987,8 +963,7 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
     ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(m.workspace) + w.lazy_zero_off, 0, w.lazy_zero_bytes + (use_x3 ? w.x3_zero_bytes : 0), st));
     // validity cascade (round 6): on the route the engine takes once its feedback says "hard" (q_hi_lo given: K0 wrote the hi / lo rows),
     // the screen stops a panel whose anchors are all valid for sure, and a second, complete pass serves the sampled anchors only
-    static const bool cascade_env = dev_env_int("ORYON_CASCADE", 1) != 0;
-    const bool cascade = cascade_env && m.fmt == 1 && use_x3 && m.q_hi_lo != nullptr && w.cs_panel != nullptr;
+    const bool cascade = m.fmt == 1 && use_x3 && m.q_hi_lo != nullptr && w.cs_panel != nullptr;
     // the default route's own cascade, at anchor granularity (kernels above: match_dc_*): by shape and the caller's knob alone
     const bool dc = m.cascade != 0 && m.fmt == 1 && use_x3 && m.q_hi_lo == nullptr && w.cs_panel != nullptr && w.dc_ok;
     int S_dec = S;                                                          // what match_decide_lite_kernel merges: the splits' triples ..
@@ -1010,8 +985,6 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
         } else if (dc) {
             const int T8 = mx6_panels_per_pair(cap_a), stride = dc_probe_stride(cap_a), csS = mx6_sampled_splits(B);
             const int Sb = dc_band_splits(B, cap_a), So = dc_open_splits(B);
-            static const int slack = dev_env_int("ORYON_DC_SLACK", DC_SLACK);
-            static const int open_panel = dev_env_int("ORYON_DC_OPEN_PANEL", 0) == 1024 ? 1024 : MX6_SAMPLED_PANEL;
             static const int sub_stats = dev_env_int("ORYON_DC_SUB_STATS", 0);     // stats[3] = the halves' widths (sweeps: the sub-bands' share)
             // (1) probe: every stride-th anchor, read in place as one list panel per pair, screened completely; triples and bands
             //     (rows 0, stride, 2 stride, ..: <= MX6_SAMPLED_PANEL of them, stride >= cap_a / 512; the screen forms the list's length
@@ -1019,22 +992,16 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
             launch_screen_mx6_list512(st, a6, q6, B, cap_a, MX6_SAMPLED_PANEL, cap_q, m.n_a, nullptr, 0, stride, m.n_q, csS, w.cs_max, w.cs_i1,
                                       w.cs_m2, m.C_true);
             hipLaunchKernelGGL(match_dc_probe_band_kernel, dim3(T8, B), dim3(256), 0, st, cap_a, T8, stride, csS, m.n_a, m.n_q, w.cs_max, w.cs_i1,
-                               w.cs_m2, m.a_scale, m.q_eps_max, cut0, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_band, w.dc_stats, slack, sub_stats);
+                               w.cs_m2, m.a_scale, m.q_eps_max, cut0, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_band, w.dc_stats, DC_SLACK, sub_stats);
             // (2) band pass over all rows, each 512-row half in its own sub-band, (3) classes, merged triples, ordered list of the open rows
             launch_screen_mx6_band512(st, a6, q6, B, cap_a, cap_q, m.n_a, m.n_q, Sb, w.dc_ws_m1, w.dc_ws_i1, w.dc_ws_m2, m.C_true, w.dc_band, 2 * T8);
             hipLaunchKernelGGL(match_dc_settle_rows_kernel, dim3(B), dim3(DC_SETTLE_THREADS), 0, st, cap_a, T8, stride, Sb, m.n_a, m.n_q, w.dc_ws_m1, w.dc_ws_i1,
                                w.dc_ws_m2, m.a_scale, m.q_eps_max, cut0, w.dc_band, w.dc_m1, w.dc_i1, w.dc_m2, w.dc_cls, w.dc_n_open, w.dc_open_idx,
                                w.dc_stats);
             // (4) complete scan of the open rows in 512-row list panels, read in place through open_idx (count-gated); their triples are
-            //     merged by the decide pass.  dc_rows keeps its room for the sweep's alternative
-            if (open_panel == 1024) {   // (dev build): the 8-wave kernel over 1024-row panels of the rows compacted into dc_rows
-                hipLaunchKernelGGL(match_compact_rows_kernel, dim3(cap_a / 16, B), dim3(256), 0, st, a6, C, cap_a, cap_a, w.dc_n_open, w.dc_open_idx,
-                                   cap_a, w.dc_rows, open_panel);
-                launch_screen_mx6(C, ((B * So + 7) / 8) * 8 * T, T, st, w.dc_rows, q6, B, cap_a, cap_q, w.dc_n_open, m.n_q, So, w.dc_ws_m1, w.dc_ws_i1,
-                                  w.dc_ws_m2, m.C_true);
-            } else
-                launch_screen_mx6_list512(st, a6, q6, B, cap_a, cap_a, cap_q, w.dc_n_open, w.dc_open_idx, cap_a, 0, m.n_q, So, w.dc_ws_m1, w.dc_ws_i1,
-                                          w.dc_ws_m2, m.C_true);
+            //     merged by the decide pass.  dc_rows keeps its room, unused
+            launch_screen_mx6_list512(st, a6, q6, B, cap_a, cap_a, cap_q, w.dc_n_open, w.dc_open_idx, cap_a, 0, m.n_q, So, w.dc_ws_m1, w.dc_ws_i1,
+                                      w.dc_ws_m2, m.C_true);
             S_dec = 1;                                                      // .. or the rows' merged ones; the open rows' So triples are
             dec_m1 = w.dc_m1; dec_i1 = w.dc_i1; dec_m2 = w.dc_m2;           //    merged by the decide pass itself, from their list slots
             dc_open.cls = w.dc_cls;

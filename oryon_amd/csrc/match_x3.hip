@@ -23,8 +23,6 @@
 #include <hip/hip_fp16.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <vector>
-#include <algorithm>
 #include <type_traits>
 #include "common.h"
 #include "match_common.h"
@@ -137,8 +135,7 @@ __device__ __forceinline__ void match_x3_scan_item(const int xcd, const int slot
                                                    int cap_s, int cap_q, const int32_t *__restrict__ n_c, const int32_t *__restrict__ n_q, int T, int S,
                                                    const float *__restrict__ al_norm, const float *__restrict__ ql_max,
                                                    const float *__restrict__ seed, float *__restrict__ smax, unsigned short *__restrict__ tl,
-                                                   uint2 *__restrict__ jobs, int32_t *__restrict__ njobs, int kc, int32_t *__restrict__ dbg,
-                                                   long long *__restrict__ dbg_wg)
+                                                   uint2 *__restrict__ jobs, int32_t *__restrict__ njobs, int kc)
 {
     constexpr int RB = CP * 2;                 // bytes per half row
     constexpr int ROWS = 32;
@@ -164,7 +161,6 @@ __device__ __forceinline__ void match_x3_scan_item(const int xcd, const int slot
     const int qt_begin = split * qt_per;
     const int qt_end = (qt_begin + qt_per < nqt) ? qt_begin + qt_per : nqt;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
-    long long tk0 = dbg ? wall_clock64() : 0;
     half8x bh[NAB][NKS];                                    // sweep 1 multiplies hi parts only
 #pragma unroll
     for (int ab = 0; ab < NAB; ++ab) {
@@ -191,7 +187,7 @@ __device__ __forceinline__ void match_x3_scan_item(const int xcd, const int slot
         return *reinterpret_cast<const half8x *>(smem + koff[s & 7] + tile + (unsigned)(part * PART + (s >> 3) * 256));
     };
 
-    // Round 4 (measured with ORYON_X3_DEBUG's phase clocks: sweep 1 took 1.0 us per tile against 0.5 us of MFMAs, sweep 2 2.3 us per visited
+    // Round 4 (measured with per-phase clocks: sweep 1 took 1.0 us per tile against 0.5 us of MFMAs, sweep 2 2.3 us per visited
     // tile with 1.2 of the 4 waves multiplying on average - both were waiting, not computing):
     //  * sweep 1 moves hi parts only, so the 128 KB ring holds EIGHT 16 KB tiles: requests run 7 tiles ahead instead of 3;
     //  * sweep 2 is wave-private.  A wave's anchors cover a band of the image, so the tiles that can hold its candidates are mostly not
@@ -231,7 +227,6 @@ __device__ __forceinline__ void match_x3_scan_item(const int xcd, const int slot
     for (int i = t; i < WAVES * X3_MAX_TILES; i += 64 * WAVES) reinterpret_cast<unsigned char *>(smem + FLAG_BASE)[i] = 0;
     const int ntl = qt_end - qt_begin;
     const bool flags_ok = ntl <= X3_MAX_TILES;
-    long long tk1 = dbg ? wall_clock64() : 0;
     // ---- sweep 1: hi.hi only (a third of the MFMAs, half of the tile bytes) -> a lower bound of every anchor's maximum over this split's rows
     float runmax[NAB];
 #pragma unroll
@@ -353,13 +348,6 @@ __device__ __forceinline__ void match_x3_scan_item(const int xcd, const int slot
         }
     }
     __syncthreads();                         // the ring is free: sweep 2's private regions overlay it
-    long long tk2 = dbg ? wall_clock64() : 0;
-    if (dbg && lane == 0) {                                  // ORYON_X3_DEBUG: flagged / all (wave, tile) pairs
-        int f = 0;
-        for (int i = 0; i < ntl && i < X3_MAX_TILES; ++i) f += tile_flag[i] != 0;
-        atomicAdd(&dbg[0], f);
-        atomicAdd(&dbg[1], ntl);
-    }
     // this wave's flagged tiles, in order (every tile when the split is too long for the flag array)
     int n_t2 = 0;
     if (flags_ok) {
@@ -409,29 +397,11 @@ __device__ __forceinline__ void match_x3_scan_item(const int xcd, const int slot
         }
     }
 #undef X3_WAIT
-    if (dbg && t == 0) {                                     // phase times (100 MHz ticks) summed over workgroups, sweep-2 tiles visited
-        const long long tk3 = wall_clock64();
-        atomicAdd(&dbg[2], (int)(tk1 - tk0));
-        atomicAdd(&dbg[3], (int)(tk2 - tk1));
-        atomicAdd(&dbg[4], (int)(tk3 - tk2));
-        atomicAdd(&dbg[5], n_t2);
-        atomicAdd(&dbg[6], 1);
-        atomicMin(reinterpret_cast<unsigned long long *>(dbg + 8), (unsigned long long)tk0);
-        atomicMax(reinterpret_cast<unsigned long long *>(dbg + 10), (unsigned long long)tk3);
-        // slowest workgroup
-        atomicMax(&dbg[7], (int)(tk3 - tk0));
-        if (dbg_wg) {
-            dbg_wg[(size_t)(slot * 8 + xcd) * 4 + 0] = tk0;
-            dbg_wg[(size_t)(slot * 8 + xcd) * 4 + 1] = tk3;
-            dbg_wg[(size_t)(slot * 8 + xcd) * 4 + 2] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);        // HW_REG_HW_ID
-            dbg_wg[(size_t)(slot * 8 + xcd) * 4 + 3] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 20);       // HW_REG_XCC_ID
-        }
-    }
 }
 
 #undef X3_ANCHOR
 // Persistent launch (round 4).  Launched one block per work item (1024 blocks of ~220 us, one per CU at a time: 512 registers per lane,
-// 130 KB of LDS) the scan took 2.4 ms although its workgroups' own times summed to 0.9 ms per CU: ORYON_X3_DEBUG's per-workgroup clocks
+// 130 KB of LDS) the scan took 2.4 ms although its workgroups' own times summed to 0.9 ms per CU: per-workgroup clocks
 // showed the dispatcher leaving most CUs empty after the first round (256 running, then 30-180).  So the grid is one workgroup per CU and
 // the workgroups pull items themselves: one queue per XCD (an item's two anchor panels and its query rows stay in that XCD's L2), in the
 // order the one-block-per-item grid used; a workgroup whose XCD has run dry takes items of the others.
@@ -443,7 +413,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void match_x3_scan_kernel(const __ha
                                                                const float *__restrict__ seed, float *__restrict__ smax,
                                                                unsigned short *__restrict__ tl, uint2 *__restrict__ jobs,
                                                                int32_t *__restrict__ njobs, int32_t *__restrict__ queue /*[8], zeroed*/,
-                                                               int items_per_xcd, int kc, int32_t *__restrict__ dbg, long long *__restrict__ dbg_wg)
+                                                               int items_per_xcd, int kc)
 {
     extern __shared__ __attribute__((aligned(256))) char smem[];
     __shared__ int item_s;
@@ -470,7 +440,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void match_x3_scan_kernel(const __ha
         __syncthreads();
         const int it = item_s;
         if (it < 0) return;
-        match_x3_scan_item<CP, WAVES, NARROW>(it & 7, it >> 3, smem, ah, al, qh, ql, B, cap_s, cap_q, n_c, n_q, T, S, al_norm, ql_max, seed, smax, tl, jobs, njobs, kc, dbg, dbg_wg);
+        match_x3_scan_item<CP, WAVES, NARROW>(it & 7, it >> 3, smem, ah, al, qh, ql, B, cap_s, cap_q, n_c, n_q, T, S, al_norm, ql_max, seed, smax, tl, jobs, njobs, kc);
     }
 }
 
@@ -487,13 +457,9 @@ __global__ __launch_bounds__(256, 1) void match_x3_sweep2_kernel(const __half *_
                                                                 const float *__restrict__ smax, const unsigned short *__restrict__ tl,
                                                                 const uint2 *__restrict__ jobs, const int32_t *__restrict__ njobs,
                                                                 int32_t *__restrict__ next_job, int32_t *__restrict__ cnt, uint2 *__restrict__ cand,
-                                                                int kc /* live 64-channel chunks: ceil(C_true / 64); the rest of a row is zero */,
-                                                                int32_t *__restrict__ dbg)
+                                                                int kc /* live 64-channel chunks: ceil(C_true / 64); the rest of a row is zero */)
 {
     constexpr int RB = CP * 2, ROWS = 32, PART = ROWS * RB, NKS = CP / 16, NAB = 2;
-    const long long tw0 = dbg ? wall_clock64() : 0;
-    long long t_load = 0;
-    int n_tiles_done = 0, n_jobs_done = 0;
     constexpr int CH = 64;                                  // channels per chunk
     constexpr int NCH = CP / CH;                            // 4 chunks per tile = the 4 slots of the region
     constexpr int CHB = 2 * ROWS * CH * 2;                  // 8 KB: [part][row][128 B]
@@ -507,7 +473,7 @@ __global__ __launch_bounds__(256, 1) void match_x3_sweep2_kernel(const __half *_
     if constexpr (!NARROW) kc = CP / 64;                        // every chunk is live: the compiler sees a constant
     const int n_jobs = __atomic_load_n(njobs, __ATOMIC_RELAXED);
     // nothing posted (the usual step): leave without a pull - the 1024 waves' returning adds on next_job were most of the empty launch
-    if (n_jobs <= 0 && !dbg) return;
+    if (n_jobs <= 0) return;
     // DMA source: lane L of instruction j lands at LDS (row j*8 + L/8, 16-byte slot L%8); slots are XOR-swizzled with (row >> 1) & 7 so
     // that the 16 lanes of a ds_read_b128 phase (rows r .. r+15 at one logical slot) cover all 64 banks
     unsigned src2[NJ];
@@ -524,19 +490,7 @@ __global__ __launch_bounds__(256, 1) void match_x3_sweep2_kernel(const __half *_
         int jx = 0;
         if (lane == 0) jx = atomicAdd(next_job, 1);
         jx = __builtin_amdgcn_readfirstlane(jx);
-        if (jx >= n_jobs) {
-            if (dbg && lane == 0) {                          // ORYON_X3_DEBUG: per-wave totals
-                const long long tw1 = wall_clock64();
-                atomicAdd(&dbg[12], (int)(tw1 - tw0));       // busy ticks of this wave (start to its last job's end)
-                atomicAdd(&dbg[13], (int)t_load);            // of which: operand loads
-                atomicAdd(&dbg[14], n_tiles_done);
-                atomicAdd(&dbg[15], n_jobs_done);
-                atomicMax(&dbg[16], (int)(tw1 - tw0));
-                atomicAdd(&dbg[17], 1);
-            }
-            return;
-        }
-        const long long tj0 = dbg ? wall_clock64() : 0;
+        if (jx >= n_jobs) return;
         const uint2 jb = jobs[jx];
         const int owner = (int)jb.x, first = (int)((jb.y >> 8) & 0x7fffffu), n_t = (int)(jb.y & 0xffu);
         const bool dense = (jb.y >> 31) != 0;
@@ -568,7 +522,6 @@ __global__ __launch_bounds__(256, 1) void match_x3_sweep2_kernel(const __half *_
             lim[ab] = gm - e_hi - 0.5f * X3_MARGIN;
             run3[ab] = -INFINITY;
         }
-        if (dbg) { t_load += wall_clock64() - tj0; n_tiles_done += n_t; n_jobs_done += 1; }
         auto tile_at = [&](int i) { return qt_begin + (dense ? first + i : (int)(gl[i] & 0x3fffu)); };
         auto issue2 = [&](int g) {                               // chunk g = (tile g / kc of the job, k-chunk g % kc), into slot g % 4
             const int ti = g / kc, c = g - ti * kc;
@@ -829,10 +782,9 @@ int match_x3_resolve(const float *a_c, const int32_t *n_c, int cap_s, const floa
                      const __half *q_hi_lo_pre, const float *q_lo_sq_max_pre, hipStream_t st)
 {
     constexpr int CP = 256;
-    // sweep 1 as 8-wave workgroups (512 anchors, two waves per SIMD) unless ORYON_X3_WAVES=4 (256 anchors, one wave per SIMD)
-    static const int x3_waves = (dev_env_int("ORYON_X3_WAVES", 8) == 4) ? 4 : 8;
-    const int T = (cap_s + 64 * x3_waves - 1) / (64 * x3_waves);
-    const int G = T * x3_waves;                                  // 64-anchor groups per (pair, split)
+    constexpr int X3_WAVES = 8;                                  // sweep 1 as 8-wave workgroups: 512 anchors, two waves per SIMD
+    const int T = (cap_s + 64 * X3_WAVES - 1) / (64 * X3_WAVES);
+    const int G = T * X3_WAVES;                                  // 64-anchor groups per (pair, split)
     const int S = 8;
     char *sp = static_cast<char *>(scratch);
     // cnt | n_ovf | ql_max | queue: the head of the scratch, match_x3_zero_bytes of it - zeroed by the CALLER's fill before this call
@@ -854,7 +806,7 @@ int match_x3_resolve(const float *a_c, const int32_t *n_c, int cap_s, const floa
     float *al_norm = reinterpret_cast<float *>(sp + off);
     off += ((size_t)B * cap_s * sizeof(float) + 255) / 256 * 256;
     float *seed = reinterpret_cast<float *>(sp + off);
-    off += ((size_t)B * cap_s * sizeof(float) + 255) / 256 * 256 + 8192;                    // + the debug counters' slack
+    off += ((size_t)B * cap_s * sizeof(float) + 255) / 256 * 256 + 8192;                    // + 8 KB of slack (unused; kept so that no offset moves)
     float *smax = reinterpret_cast<float *>(sp + off);
     off += ((size_t)B * S * cap_s * sizeof(float) + 255) / 256 * 256;
     const size_t owners = (size_t)B * S * G;
@@ -877,29 +829,16 @@ int match_x3_resolve(const float *a_c, const int32_t *n_c, int cap_s, const floa
     }
     hipLaunchKernelGGL(match_x3_split_anchors_kernel, dim3(64, B), dim3(256), 0, st, a_c, CP, cap_s, n_c, ah, al, al_norm);
     const int groups = ((B * S + 7) / 8) * 8 * T;
-    static const bool dbg = dev_env_set("ORYON_X3_DEBUG");          // development aid: list statistics of this call on stderr
-    int32_t *dbg_dev = nullptr;
-    if (dbg) {
-        dbg_dev = reinterpret_cast<int32_t *>(seed + (size_t)B * cap_s + 64);         // in the scratch's 8 KB of slack
-        (void)hipMemsetAsync(dbg_dev, 0, 96, st);
-        (void)hipMemsetAsync(dbg_dev + 8, 0xff, 8, st);
-    }
-    // seeds of the running maxima from the screen's winning slices (ORYON_X3_SEED=0: the round-3 scan, for A/B timing; same results)
-    static const bool use_seed = dev_env_int("ORYON_X3_SEED", 1) != 0;
+    // seeds of the running maxima from the screen's winning slices, where the caller has them
     const float *seed_arg = nullptr;
-    if (use_seed && orig_idx && sid_final) {
+    if (orig_idx && sid_final) {
         hipLaunchKernelGGL(match_x3_seed_kernel, dim3((cap_s + 3) / 4, B), dim3(256), 0, st, ah, qh, CP, cap_s, cap_q, n_c, n_q, orig_idx, orig_stride,
                            sid_final, cap_a, (C_true + 63) / 64, seed);
         seed_arg = seed;
     }
-    static long long *dbg_wg = nullptr;
-    if (dbg && !dbg_wg) (void)hipMalloc(&dbg_wg, (size_t)65536 * 4 * sizeof(long long));
-    if (dbg && dbg_wg) (void)hipMemsetAsync(dbg_wg, 0, (size_t)(groups < 65536 ? groups : 65536) * 4 * sizeof(long long), st);
     constexpr int X3_SCAN_LDS = 4 * 2 * 32 * CP * 2 + 8 * X3_MAX_TILES + 8 * 2 * X3_MAX_TILES + 64;   // 128 KB of tile ring + tile flags + the waves' tile lists
-    allow_dynamic_lds(reinterpret_cast<const void *>(&match_x3_scan_kernel<CP, 4, false>), X3_SCAN_LDS);
-    allow_dynamic_lds(reinterpret_cast<const void *>(&match_x3_scan_kernel<CP, 8, false>), X3_SCAN_LDS);
-    allow_dynamic_lds(reinterpret_cast<const void *>(&match_x3_scan_kernel<CP, 4, true>), X3_SCAN_LDS);
-    allow_dynamic_lds(reinterpret_cast<const void *>(&match_x3_scan_kernel<CP, 8, true>), X3_SCAN_LDS);
+    allow_dynamic_lds(reinterpret_cast<const void *>(&match_x3_scan_kernel<CP, X3_WAVES, false>), X3_SCAN_LDS);
+    allow_dynamic_lds(reinterpret_cast<const void *>(&match_x3_scan_kernel<CP, X3_WAVES, true>), X3_SCAN_LDS);
     // one workgroup per CU, items pulled from per-XCD queues (see the kernel)
     static int n_cus = 0;
     if (!n_cus) {
@@ -909,16 +848,15 @@ int match_x3_resolve(const float *a_c, const int32_t *n_c, int cap_s, const floa
     }
     const int grid = groups < n_cus ? groups : n_cus / 8 * 8;
     const int kc = (C_true + 63) / 64;                          // live 64-channel chunks of a row (narrow maps are zero-padded to 256)
-#define X3_SCAN_LAUNCH(WV, NR)                                                                                                   \
-    hipLaunchKernelGGL((match_x3_scan_kernel<CP, WV, NR>), dim3(grid), dim3(64 * WV), X3_SCAN_LDS, st, ah, al, qh, ql, B, cap_s, cap_q, n_c, n_q, T, \
-                       S, al_norm, ql_max, seed_arg, smax, tl, jobs, njobs, queue, groups / 8, kc, dbg_dev, dbg_wg)
-    if (x3_waves == 8) { if (kc < 4) X3_SCAN_LAUNCH(8, true); else X3_SCAN_LAUNCH(8, false); }
-    else { if (kc < 4) X3_SCAN_LAUNCH(4, true); else X3_SCAN_LAUNCH(4, false); }
+#define X3_SCAN_LAUNCH(NR)                                                                                                       \
+    hipLaunchKernelGGL((match_x3_scan_kernel<CP, X3_WAVES, NR>), dim3(grid), dim3(64 * X3_WAVES), X3_SCAN_LDS, st, ah, al, qh, ql, B, cap_s, cap_q, n_c, \
+                       n_q, T, S, al_norm, ql_max, seed_arg, smax, tl, jobs, njobs, queue, groups / 8, kc)
+    if (kc < 4) X3_SCAN_LAUNCH(true); else X3_SCAN_LAUNCH(false);
 #undef X3_SCAN_LAUNCH
     // sweep 2: four independent waves per CU pull the jobs sweep 1 posted (none posted: they exit at once)
 #define X3_SWEEP2_LAUNCH(NR)                                                                                                     \
     hipLaunchKernelGGL((match_x3_sweep2_kernel<CP, NR>), dim3(n_cus), dim3(256), 4 * 32768, st, ah, al, qh, ql, cap_s, cap_q, n_c, n_q, G, S, al_norm, \
-                       ql_max, smax, tl, jobs, njobs, next_job, cnt, cand, kc, dbg_dev)
+                       ql_max, smax, tl, jobs, njobs, next_job, cnt, cand, kc)
     allow_dynamic_lds(reinterpret_cast<const void *>(&match_x3_sweep2_kernel<CP, true>), 4 * 32768);
     allow_dynamic_lds(reinterpret_cast<const void *>(&match_x3_sweep2_kernel<CP, false>), 4 * 32768);
     if (kc < 4) X3_SWEEP2_LAUNCH(true); else X3_SWEEP2_LAUNCH(false);
@@ -930,74 +868,6 @@ int match_x3_resolve(const float *a_c, const int32_t *n_c, int cap_s, const floa
     else
         hipLaunchKernelGGL((match_x3_rescore_kernel<false>), dim3(cap_s / 4, B), dim3(256), lds, st, a_c, CP, cap_s, n_c, feat_q, C_true, HW, roi_q,
                            roi_stride_q, q_norm, cap_q, n_q, S, threshold, cnt, cand, ah, al, qh, ql, round_f16, md_c, am_c, va_c, n_ovf, ovf_idx);
-    if (dbg) {
-        (void)hipStreamSynchronize(st);
-        std::vector<int32_t> hc((size_t)B * S * cap_s * 2), hn(B), hov(B);
-        std::vector<float> hq(B), ha((size_t)B * cap_s);
-        (void)hipMemcpy(hc.data(), cnt, hc.size() * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(hn.data(), n_c, (size_t)B * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(hov.data(), n_ovf, (size_t)B * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(hq.data(), ql_max, (size_t)B * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(ha.data(), al_norm, ha.size() * 4, hipMemcpyDeviceToHost);
-        long tot = 0, nl = 0, over = 0, mx = 0, anchors = 0, novf = 0;
-        double amax = 0, qmax = 0;
-        for (int p = 0; p < B; ++p) {
-            const int n = hn[p] < cap_s ? hn[p] : cap_s;
-            anchors += n; novf += hov[p];
-            qmax = sqrtf(hq[p]) > qmax ? sqrtf(hq[p]) : qmax;
-            for (int a = 0; a < n; ++a) {
-                amax = ha[(size_t)p * cap_s + a] > amax ? ha[(size_t)p * cap_s + a] : amax;
-                for (int sp = 0; sp < S; ++sp)
-                    for (int h = 0; h < 2; ++h) {
-                        const int c = hc[((((size_t)p * S + sp) * cap_s + a) * 2) + h];
-                        tot += c; nl += 1; over += c > X3_CAPH; mx = c > mx ? c : mx;
-                    }
-            }
-        }
-        int32_t hd[24] = {0};
-        (void)hipMemcpy(hd, dbg_dev, 96, hipMemcpyDeviceToHost);
-        if (hd[17] > 0)
-            fprintf(stderr, "[x3] sweep 2: %d waves, mean alive %.1f us (longest %.1f us), operand loads %.1f us per wave, %d jobs, %d tiles (%.2f us of wave time per tile)\n",
-                    hd[17], hd[12] * 0.01 / hd[17], hd[16] * 0.01, hd[13] * 0.01 / hd[17], hd[15], hd[14], hd[14] ? (hd[12] - hd[13]) * 0.01 / hd[14] : 0.0);
-        {
-            unsigned long long t_lo, t_hi;
-            memcpy(&t_lo, hd + 8, 8);
-            memcpy(&t_hi, hd + 10, 8);
-            fprintf(stderr, "[x3] scan span %.1f us (first start to last end), slowest workgroup %.1f us\n", (double)(t_hi - t_lo) * 0.01, hd[7] * 0.01);
-        }
-        fprintf(stderr, "[x3] sweep-2 (wave, tile) pairs flagged: %d of %d\n", hd[0], hd[1]);
-        if (dbg_wg && groups <= 65536) {
-            std::vector<long long> w((size_t)groups * 4);
-            (void)hipMemcpy(w.data(), dbg_wg, w.size() * sizeof(long long), hipMemcpyDeviceToHost);
-            long long t0 = -1;
-            for (int g = 0; g < groups; ++g) if (w[4 * g + 1] && (t0 < 0 || w[4 * g] < t0)) t0 = w[4 * g];
-            std::vector<unsigned long long> ids;
-            for (int g = 0; g < groups; ++g) if (w[4 * g + 1]) ids.push_back(((unsigned long long)(w[4 * g + 3] & 0xf) << 32) | (unsigned long long)(w[4 * g + 2] & 0xff00));
-            std::sort(ids.begin(), ids.end());
-            const size_t distinct = std::unique(ids.begin(), ids.end()) - ids.begin();
-            fprintf(stderr, "[x3] workgroups ran on %zu distinct (xcc, se, sh, cu) places\n", distinct);
-            // concurrency profile: workgroups running at 10 sample times, and the start time of every 128th workgroup in launch order
-            long long t1 = 0;
-            for (int g = 0; g < groups; ++g) if (w[4 * g + 1] > t1) t1 = w[4 * g + 1];
-            fprintf(stderr, "[x3] running at 5%%..95%% of the span:");
-            for (int k = 0; k < 10; ++k) {
-                const long long ts = t0 + (t1 - t0) * (2 * k + 1) / 20;
-                int r = 0;
-                for (int g = 0; g < groups; ++g) r += w[4 * g + 1] && w[4 * g] <= ts && ts < w[4 * g + 1];
-                fprintf(stderr, " %d", r);
-            }
-            fprintf(stderr, "\n[x3] start (us) of block 0, 128, 256, ...:");
-            for (int g = 0; g < groups; g += 128) fprintf(stderr, " %.0f", w[4 * g + 1] ? (w[4 * g] - t0) * 0.01 : -1.0);
-            fprintf(stderr, "\n[x3] raw ids of blocks 0..11 (hw_id, xcc_id):");
-            for (int g = 0; g < 12 && g < groups; ++g) fprintf(stderr, " (%llx,%llx)", (unsigned long long)w[4 * g + 2], (unsigned long long)w[4 * g + 3]);
-            fprintf(stderr, "\n");
-        }
-        if (hd[6] > 0)
-            fprintf(stderr, "[x3] per workgroup (%d ran): operand load %.1f us, sweep 1 %.1f us, list + sweep 2 %.1f us; sweep-2 tiles visited %.1f of %.1f\n", hd[6],
-                    hd[2] * 0.01 / hd[6], hd[3] * 0.01 / hd[6], hd[4] * 0.01 / hd[6], (double)hd[5] / hd[6], (double)hd[1] / (4.0 * hd[6]));
-        fprintf(stderr, "[x3] anchors %ld, lists %ld, entries %ld (%.1f per anchor), longest %ld, overflowed lists %ld, overflowed anchors %ld, max|al| %.3g, max|ql| %.3g\n",
-                anchors, nl, tot, anchors ? (double)tot / anchors : 0.0, mx, over, novf, amax, qmax);
-    }
     return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
 }
 

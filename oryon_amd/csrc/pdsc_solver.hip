@@ -930,8 +930,7 @@ __global__ __launch_bounds__(256) void pdsc_refine_kernel(const float *__restric
 int pdsc_run_seeds(const PdscModel &M, const float *src, const float *conf, const int32_t *n_rows, int B, int n_cap, int S_cap,
                    int32_t *seeds, int32_t *n_seeds, float *key_scratch /* [B,n_cap] */, hipStream_t st)
 {
-    static const bool fused_seeds = dev_env_int("ORYON_PDSC_FUSED_SEEDS", 1) != 0;      // dev build: 0 = keys + bitonic rank kernels
-    if (fused_seeds && n_cap <= 2048) {
+    if (n_cap <= 2048) {
         hipLaunchKernelGGL(pdsc_seeds_fused_kernel, dim3(B), dim3(1024), (size_t)7 * n_cap * sizeof(float), st, src, conf, n_rows, n_cap,
                            M.cfg.nms_radius, S_cap, M.cfg.ratio, key_scratch, seeds, n_seeds);
         return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
@@ -969,18 +968,12 @@ int pdsc_run_hypotheses(const PdscModel &M, const PdscWorkspace &ws, const float
     while (P < (size_t)n_cap) P <<= 1;
     const size_t sh1 = (2 * P + C + (size_t)KNN_MAX_K * (C + 4) + KNN_MAX_K * 6 + KNN_MAX_K) * sizeof(float);
     const int nit = M.cfg.num_iterations < HYP_MAX_IT ? M.cfg.num_iterations : HYP_MAX_IT;
-    // round 5: distances + kNN (rank counting) + compatibility matrix + power iteration in ONE launch (0 = the separate kernels, dev build)
-    static const bool fused_hyp = dev_env_int("ORYON_PDSC_FUSED_HYP", 1) != 0;
-    if (fused_hyp && C == 128 && n_cap <= 1024 && k <= KNN_MAX_K - 1 && (size_t)S_cap * 128 * sizeof(float) <= 64 * 1024) {
-        static const bool dist_mfma = dev_env_int("ORYON_PDSC_DIST_MFMA", 1) != 0;          // dev build: 0 = the VALU kernel
-        if (dist_mfma) {
-            const size_t shd = (size_t)((S_cap + 31) / 32 * 32) * 129 * sizeof(float);
-            allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_seed_dist_mfma_kernel), (int)shd);
-            hipLaunchKernelGGL(pdsc_seed_dist_mfma_kernel, dim3(n_cap / 64, B), dim3(256), shd, st, feat_n, n_rows, n_cap, seeds, n_seeds, S_cap,
-                               ws.seed_dist);
-        } else
-        hipLaunchKernelGGL((pdsc_seed_dist_kernel<128>), dim3(n_cap / 64, B), dim3(256), (size_t)S_cap * 128 * sizeof(float), st, feat_n, n_rows,
-                           n_cap, seeds, n_seeds, S_cap, ws.seed_dist);
+    // round 5: distances + kNN (rank counting) + compatibility matrix + power iteration in ONE launch where the shape allows
+    if (C == 128 && n_cap <= 1024 && k <= KNN_MAX_K - 1 && (size_t)S_cap * 128 * sizeof(float) <= 64 * 1024) {
+        const size_t shd = (size_t)((S_cap + 31) / 32 * 32) * 129 * sizeof(float);
+        allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_seed_dist_mfma_kernel), (int)shd);
+        hipLaunchKernelGGL(pdsc_seed_dist_mfma_kernel, dim3(n_cap / 64, B), dim3(256), shd, st, feat_n, n_rows, n_cap, seeds, n_seeds, S_cap,
+                           ws.seed_dist);
         const int ept = n_cap <= 512 ? 2 : 4;
         const size_t shf = ((size_t)512 + (size_t)k * (C + 4) + k * 6 + KNN_MAX_K) * sizeof(float);
         const dim3 grid(S_cap, (B + 7) / 8 * 8);

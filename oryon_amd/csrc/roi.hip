@@ -646,8 +646,7 @@ extern "C" int oryon_gather_normalise_f32(const float *feat, int n_maps, int C, 
     ORYON_CHECK_ARG(rows_cap > 0 && rows_cap % GN_ROWS == 0);
     if (n_maps == 0) return ORYON_OK;
     if (C_pad <= 512) {
-        static const int rows_env = dev_env_int("ORYON_GATHER_ROWS", 0);
-        const int rows = rows_env ? rows_env : 32;
+        constexpr int rows = 32;
         const size_t sh = ((size_t)C_pad * (rows + 1) + 64) * sizeof(float);
 #define LAUNCH_G2(NLV, RV)                                                                                                 \
     do {                                                                                                                   \
@@ -655,7 +654,7 @@ extern "C" int oryon_gather_normalise_f32(const float *feat, int n_maps, int C, 
         hipLaunchKernelGGL((gather_normalise_v2_kernel<NLV, RV>), dim3(rows_cap / RV, n_maps), dim3(256), sh, as_stream(stream), feat, \
                            C, HW, roi, roi_stride, count, rows_cap, C_pad, out, static_cast<__half *>(out_f16));          \
     } while (0)
-        if (rows == 64) LAUNCH_G2(16, 64); else LAUNCH_G2(16, 32);
+        LAUNCH_G2(16, rows);
 #undef LAUNCH_G2
     } else {
         hipLaunchKernelGGL(gather_normalise_kernel, dim3(rows_cap / GN_ROWS, n_maps), dim3(GN_ROWS), 0, as_stream(stream), feat,

@@ -384,7 +384,8 @@ template <int CP, int WAVES, int KL = CP / 64>
 __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_screen_w4_kernel(
     const uint8_t *__restrict__ a6, const uint8_t *__restrict__ q6, int B, int cap_a, int cap_q, const int32_t *__restrict__ n_a,
     const int32_t *__restrict__ n_q, int T, int S, float *__restrict__ ws_max, int32_t *__restrict__ ws_i1, float *__restrict__ ws_m2,
-    long long *__restrict__ dbg_wg /* ORYON_MX6_DEBUG: per-workgroup (start, end, hw_id, xcc_id), else NULL */)
+    long long *__restrict__ dbg_wg /* per-workgroup (start, end, hw_id, xcc_id) records; the library passes NULL.  Kept, with the lines
+                                      that use it: without them the tile loop comes out with other registers (profiles/r17) */)
 {
     constexpr int TILE_BYTES = screen8_tile_bytes(CP);
     char *smem;
@@ -482,38 +483,6 @@ __global__ __launch_bounds__(64 * WAVES, CP == 512 ? 1 : 2) void match_mx6_scree
     mx6_screen_w4_tiles<CP, WAVES, KL>(smem, a6, q6, u.p, u.split, u.a0, cap_a, cap_q, S, qt_begin, qt_end, ws_max, ws_i1, ws_m2);
 }
 
-// ORYON_MX6_DEBUG=1 (development aid; synchronises): per-workgroup wall-clock records of the screen launch -> how many workgroups were
-// resident over the launch, i.e. whether the dispatcher keeps the CUs full (the K1x3 scan's were not: match_x3.hip)
-static void mx6_debug_report(const long long *dbg_dev, int groups, hipStream_t st)
-{
-    (void)hipStreamSynchronize(st);
-    long long *w = static_cast<long long *>(malloc((size_t)groups * 4 * sizeof(long long)));
-    (void)hipMemcpy(w, dbg_dev, (size_t)groups * 4 * sizeof(long long), hipMemcpyDeviceToHost);
-    long long t0 = -1, t1 = 0;
-    double sum = 0;
-    int ran = 0;
-    long long longest = 0;
-    for (int g = 0; g < groups; ++g)
-        if (w[4 * g + 1]) {
-            if (t0 < 0 || w[4 * g] < t0) t0 = w[4 * g];
-            if (w[4 * g + 1] > t1) t1 = w[4 * g + 1];
-            sum += (double)(w[4 * g + 1] - w[4 * g]);
-            if (w[4 * g + 1] - w[4 * g] > longest) longest = w[4 * g + 1] - w[4 * g];
-            ++ran;
-        }
-    fprintf(stderr, "[mx6] %d of %d workgroups ran: span %.1f us, mean %.1f us, longest %.1f us, mean residency %.1f workgroups\n", ran, groups,
-            (t1 - t0) * 0.01, ran ? sum * 0.01 / ran : 0.0, longest * 0.01, t1 > t0 ? sum / (double)(t1 - t0) : 0.0);
-    fprintf(stderr, "[mx6] resident at 5%%..95%% of the span:");
-    for (int k = 0; k < 10; ++k) {
-        const long long ts = t0 + (t1 - t0) * (2 * k + 1) / 20;
-        int r = 0;
-        for (int g = 0; g < groups; ++g) r += w[4 * g + 1] && w[4 * g] <= ts && ts < w[4 * g + 1];
-        fprintf(stderr, " %d", r);
-    }
-    fprintf(stderr, "\n");
-    free(w);
-}
-
 static int mx6_var()
 {
     // 0: default; 1: diagnostic build of the 8-wave loop (wrong results); 2: the first 8-wave kernel at C_pad 256; 3: 4-wave workgroups
@@ -553,11 +522,7 @@ void launch_screen_mx6_t(int groups, int T, hipStream_t st, const uint8_t *a6, c
     if constexpr (CP == 256) {
         if (var == 0) {                                          // default: 8 waves x 128 anchors (1024-anchor panels, one workgroup per CU)
             const int T8 = (cap_a + 1023) / 1024;
-            static const bool dbg = dev_env_set("ORYON_MX6_DEBUG");
-            static long long *dbg_wg = nullptr;
             const int g8 = groups / T * T8;
-            if (dbg && !dbg_wg) (void)hipMalloc(&dbg_wg, (size_t)65536 * 4 * sizeof(long long));
-            if (dbg && dbg_wg && g8 <= 65536) (void)hipMemsetAsync(dbg_wg, 0, (size_t)g8 * 4 * sizeof(long long), st);
             if (gate_or_win) {
                 // the hard route's cascade launches: a window (win > 0) or the gated panels (gate != NULL) of the same loop
                 mx6_with_kl(kl, [&](auto KLC) {
@@ -568,9 +533,8 @@ void launch_screen_mx6_t(int groups, int T, hipStream_t st, const uint8_t *a6, c
             }
             mx6_with_kl(kl, [&](auto KLC) {
                 hipLaunchKernelGGL((match_mx6_screen_w4_kernel<CP, 8, decltype(KLC)::value>), dim3(g8), dim3(512), 0, st, a6, q6, B, cap_a, cap_q,
-                                   n_a, n_q, T8, S, ws_max, ws_i1, ws_m2, (dbg && g8 <= 65536) ? dbg_wg : nullptr);
+                                   n_a, n_q, T8, S, ws_max, ws_i1, ws_m2, static_cast<long long *>(nullptr));
             });
-            if (dbg && dbg_wg && g8 <= 65536) mx6_debug_report(dbg_wg, g8, st);
             return;
         }
         if (var == 3) {                                          // 4 waves x 128 anchors (512-anchor panels, two workgroups per CU)

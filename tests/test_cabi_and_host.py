@@ -350,8 +350,8 @@ def test_fp16x3_split_is_defined_once():
 def test_mx6_w4_loop_is_written_once():
     """The MX-fp6 screen's tile loop exists once (mx6_screen_w4_tiles: the plain and the cascade kernel call it), and what the screen
     kernels share lives in csrc/screen_tile.h alone: the merge of the two lane halves' (m1, slice, m2) and the tile size.
-    `__shfl_xor(runmax` also opens the two max-only merges of kernels that keep no slice and no runner-up (pass 0 of the fp16 screen in
-    match16.hip, the fp16x3 scan in match_x3.hip): one line each, pinned here; the triple merge is told apart by `__shfl_xor(run2`."""
+    `__shfl_xor(runmax` also opens the max-only merge of the one kernel that keeps no slice and no runner-up (the fp16x3 scan in
+    match_x3.hip): one line, pinned here; the triple merge is told apart by `__shfl_xor(run2`."""
     import glob, re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oryon_amd", "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
@@ -367,8 +367,8 @@ def test_mx6_w4_loop_is_written_once():
     assert {f: t.count("__shfl_xor(run2") for f, t in text.items() if "__shfl_xor(run2" in t} == {"screen_tile.h": 1}
     max_only = "fmaxf(runmax[ab], __shfl_xor(runmax[ab], 32))"
     merges = {f: t.count("__shfl_xor(runmax") for f, t in text.items() if "__shfl_xor(runmax" in t}
-    assert merges == {"screen_tile.h": 1, "match16.hip": 1, "match_x3.hip": 1}, merges
-    assert text["match16.hip"].count(max_only) == 1 and text["match_x3.hip"].count(max_only) == 1
+    assert merges == {"screen_tile.h": 1, "match_x3.hip": 1}, merges
+    assert text["match_x3.hip"].count(max_only) == 1
     assert [f for f, t in text.items() if re.search(r"constexpr\s+int\s+screen8_tile_bytes\s*\(", t)] == ["screen_tile.h"]
 
 
