@@ -235,6 +235,17 @@ def ptr(t) -> int | None:
     return t.data_ptr()
 
 
+def workspace(device, need: int, what: str | None = None, given=None, unsupported: str = "shape not supported"):
+    """The workspace of one C call that asked for `need` bytes (its *_workspace_bytes): the caller's own tensor `given`, else a fresh
+    uint8 tensor of at least 16 bytes (never an empty one: the entries refuse a NULL workspace).  what (the size call, as text): a
+    `need` of 0 then means the entry refuses the shape, and raises."""
+    if what and need == 0:
+        raise OryonError(f"{what}: {unsupported}")
+    if given is not None:
+        return given
+    return torch.empty((max(int(need), 16),), dtype=torch.uint8, device=device)
+
+
 def stream_ptr(device=None) -> int:
     """The current torch HIP stream of `device` as a raw hipStream_t."""
     return torch.cuda.current_stream(device).cuda_stream

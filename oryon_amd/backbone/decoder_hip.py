@@ -67,7 +67,7 @@ class HipDecoder:
             if nbytes <= 0:
                 raise ValueError(f"oryon_decoder_forward: unsupported shape n={n}, h={h}, w={w} (h, w multiples of 8)")
             self._ws.clear()                                  # one shape at a time: the buffers are ~14 MB per image at 24 x 24
-            self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._ws[key] = _lib.workspace(self.device, nbytes)
         return self._ws[key]
 
     def layout(self, n: int, h: int, w: int) -> List[int]:

@@ -7,6 +7,7 @@
 #include <string.h>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 #include "../../include/oryon_hip.h"
 
@@ -23,6 +24,16 @@ void profile_end(hipStream_t st);
         if (!(cond)) {                                                                  \
             oryon::set_error("%s: invalid argument: %s", __func__, #cond);              \
             return ORYON_ERR_INVALID_ARG;                                               \
+        }                                                                               \
+    } while (0)
+
+// the one refusal of a missing or short caller-provided workspace: prefix (a literal; its own format arguments follow `need`) + the common text
+#define ORYON_CHECK_WORKSPACE(prefix, ptr, given, need, ...)                            \
+    do {                                                                                \
+        const size_t given_ = (given), need_ = (need);                                  \
+        if (!(ptr) || given_ < need_) {                                                 \
+            oryon::set_error(prefix "workspace too small (%zu < %zu)", ##__VA_ARGS__, given_, need_); \
+            return ORYON_ERR_WORKSPACE;                                                 \
         }                                                                               \
     } while (0)
 
@@ -74,6 +85,23 @@ static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 // workspace carving: every block starts on a 256-byte boundary; float64 / int64 arguments must be 8-byte aligned (NULL is)
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// ------------------------------------------------------------------------------------------------ caller-provided workspaces
+// One allocation, 256-byte aligned buffers, one line per buffer: carve(w.ws_max, B * S * cap_a) assigns the pointer (typed by it) and
+// advances to the next multiple of 256; a buffer of zero elements gets the next buffer's address and leaves the offset where it is.
+// The carve_* functions are walked twice with the same code: on a null base every pointer comes out null and only the size (off, or
+// end where the site does not pad its last buffer) is of interest.  A nested workspace starts its Carver at the inner one's size.
+struct Carver {
+    char *base;
+    size_t off, end;                    // start of the next buffer; unpadded end of the last one
+    explicit Carver(void *b, size_t start = 0) : base(static_cast<char *>(b)), off(start), end(start) {}
+    template <class T> void operator()(T *&p, size_t count)             // count elements (bytes for a void pointer)
+    {
+        p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        end = off + count * sizeof(std::conditional_t<std::is_void<T>::value, char, T>);
+        off = align256(end);
+    }
+};
 
 // 64-bit mix (splitmix64 finaliser): the counter-based RNG of the batched sampling kernels.
 __host__ __device__ static inline uint64_t mix64(uint64_t x)

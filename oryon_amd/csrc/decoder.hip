@@ -642,7 +642,6 @@ constexpr int D_GIN[2] = {256, 128};                      // Swin guidance chann
 inline int64_t conv_img_halves(int cin, int NB) { return ((int64_t)(cin / 32) * 18 + DEC_RING) * NB * 2 * 64 * 8; }   // + RING steps of zeros
 inline int64_t up_img_halves(int cin, int nbp) { return (int64_t)(4 * nbp) * (cin / 16) * 2 * 64 * 8; }
 inline int nb_of(int cout) { return (cout + 31) / 32; }
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 struct WsLayout {
     int64_t R[3], stats, affine[6], total;
@@ -650,11 +649,11 @@ struct WsLayout {
 WsLayout ws_layout(int n, int h, int w)
 {
     WsLayout L;
-    const int64_t big = align256((int64_t)n * (8 * h) * (8 * w) * 32 * 4);
+    const int64_t big = (int64_t)align256((size_t)n * (8 * h) * (8 * w) * 32 * 4);       // common.h's, on size_t: every size here is positive
     int64_t off = 0;
     for (int i = 0; i < 3; ++i) { L.R[i] = off; off += big; }
-    L.stats = off; off += align256((int64_t)n * ((8 * h / 16) * (8 * w / 16)) * 4 * 2 * 4);
-    for (int i = 0; i < 6; ++i) { L.affine[i] = off; off += align256((int64_t)n * 64 * 2 * 4); }
+    L.stats = off; off += (int64_t)align256((size_t)n * ((8 * h / 16) * (8 * w / 16)) * 4 * 2 * 4);
+    for (int i = 0; i < 6; ++i) { L.affine[i] = off; off += (int64_t)align256((size_t)n * 64 * 2 * 4); }
     L.total = off;
     return L;
 }

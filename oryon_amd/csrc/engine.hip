@@ -140,87 +140,76 @@ int carve_engine(const oryon_engine_config_t &c, const oryon_pointdsc_t *solver,
     // the registration workspace of a slot: PointDSC's, or with cfg.solver == 1 the RANSAC solver's in its place
     L.pdsc_ws_bytes = c.solver == 1 ? oryon_ransac_workspace_bytes(c.B, L.n_cap, c.ransac_max_iter) : oryon_pointdsc_workspace_bytes(solver, c.B, L.n_cap);
     if (!L.match_ws_bytes || !L.pdsc_ws_bytes) return ORYON_ERR_INVALID_ARG;
-    size_t off = 0;
+    Carver carve(base);
     for (int g = 0; g < c.gather_sets; ++g) {
         GatherBuf &b = L.gbuf[g];
-        auto take = [&](size_t n) {
-            const size_t o = off;
-            off = up(off + n, 256);
-            return base ? base + o : nullptr;
-        };
-#define TAKE(field, type, count) b.field = reinterpret_cast<type *>(take((size_t)(count) * sizeof(type)))
-        TAKE(a8, int8_t, B * L.cap_a * L.c_pad);
-        TAKE(q8, int8_t, B * L.cap_q * L.c_pad);
-        TAKE(a_sc, float, B * (L.cap_a / 16));
-        TAKE(q_sc, float, B * (L.cap_q / 16));
-        TAKE(a_eps, float, B);
-        TAKE(q_eps, float, B);
-        TAKE(a_norm, float, B * L.cap_a);
-        TAKE(q_norm, float, B * L.cap_q);
-        TAKE(a_hat, float, B * L.cap_a * L.c_pad);
+        carve(b.a8, B * L.cap_a * L.c_pad);
+        carve(b.q8, B * L.cap_q * L.c_pad);
+        carve(b.a_sc, B * (L.cap_a / 16));
+        carve(b.q_sc, B * (L.cap_q / 16));
+        carve(b.a_eps, B);
+        carve(b.q_eps, B);
+        carve(b.a_norm, B * L.cap_a);
+        carve(b.q_norm, B * L.cap_q);
+        carve(b.a_hat, B * L.cap_a * L.c_pad);
         b.q_hilo = nullptr;
         b.q_lo_max = nullptr;
         if (c.x3_prefetch && L.c_pad == 256) {
-            b.q_hilo = take((size_t)2 * B * L.cap_q * L.c_pad * 2);
-            TAKE(q_lo_max, float, B);
+            carve(b.q_hilo, 2 * B * L.cap_q * L.c_pad * 2);
+            carve(b.q_lo_max, B);
         }
         b.a8_1 = nullptr;
         b.a_sc_1 = b.a_eps_1 = b.a_norm_1 = nullptr;
         if (L.cap_a1) {
-            TAKE(a8_1, int8_t, B * L.cap_a1 * L.c_pad);
-            TAKE(a_sc_1, float, B * (L.cap_a1 / 16));
-            TAKE(a_eps_1, float, B);
-            TAKE(a_norm_1, float, B * L.cap_a1);
+            carve(b.a8_1, B * L.cap_a1 * L.c_pad);
+            carve(b.a_sc_1, B * (L.cap_a1 / 16));
+            carve(b.a_eps_1, B);
+            carve(b.a_norm_1, B * L.cap_a1);
         }
-#undef TAKE
     }
     for (int s = 0; s < c.n_slots; ++s) {
         SlotBuf &b = L.slot[s];
         L.names[s].clear();
-        b.base = off;
-        auto take = [&](const char *name, size_t n) {
-            const size_t o = off;
-            off = up(off + n, 256);
-            L.names[s].push_back({name, o, n});
-            return base ? base + o : nullptr;
+        b.base = carve.off;
+        auto named = [&](const char *name, auto *&p, size_t count) {       // carve + the {name, offset, bytes} oryon_engine_buffer reports
+            const size_t o = carve.off;
+            carve(p, count);
+            L.names[s].push_back({name, o, carve.end - o});
         };
-#define TAKE(field, type, count) b.field = reinterpret_cast<type *>(take(#field, (size_t)(count) * sizeof(type)))
-        TAKE(roi_a, int32_t, B * HW);
-        TAKE(roi_q, int32_t, B * HW);
-        TAKE(n_a, int32_t, B);
-        TAKE(n_q, int32_t, B);
-        TAKE(min_dist, float, B * L.cap_a);
-        TAKE(argmin, int32_t, B * L.cap_a);
-        TAKE(valid, uint8_t, B * L.cap_a);
-        TAKE(corrs, int32_t, B * L.n_cap * 4);
-        TAKE(n_valid, int32_t, B);
-        TAKE(n_sel, int32_t, B);
-        TAKE(status, int32_t, B);
-        TAKE(n_und, int32_t, B);
+        named("roi_a", b.roi_a, B * HW);
+        named("roi_q", b.roi_q, B * HW);
+        named("n_a", b.n_a, B);
+        named("n_q", b.n_q, B);
+        named("min_dist", b.min_dist, B * L.cap_a);
+        named("argmin", b.argmin, B * L.cap_a);
+        named("valid", b.valid, B * L.cap_a);
+        named("corrs", b.corrs, B * L.n_cap * 4);
+        named("n_valid", b.n_valid, B);
+        named("n_sel", b.n_sel, B);
+        named("status", b.status, B);
+        named("n_und", b.n_und, B);
         b.roi_a1 = b.n_a1 = b.n_a2 = b.corrs2 = b.n_valid2 = b.n_sel2 = b.status2 = nullptr;
         if (L.cap_a1) {
-            TAKE(roi_a1, int32_t, B * HW);
-            TAKE(n_a1, int32_t, B);
-            TAKE(n_a2, int32_t, B);
-            TAKE(corrs2, int32_t, B * L.n_cap * 4);
-            TAKE(n_valid2, int32_t, B);
-            TAKE(n_sel2, int32_t, B);
-            TAKE(status2, int32_t, B);
+            named("roi_a1", b.roi_a1, B * HW);
+            named("n_a1", b.n_a1, B);
+            named("n_a2", b.n_a2, B);
+            named("corrs2", b.corrs2, B * L.n_cap * 4);
+            named("n_valid2", b.n_valid2, B);
+            named("n_sel2", b.n_sel2, B);
+            named("status2", b.status2, B);
         }
-        TAKE(pcd_a, float, B * L.n_cap * 3);
-        TAKE(pcd_q, float, B * L.n_cap * 3);
-        TAKE(n_lift, int32_t, B);
-        TAKE(pose, float, B * 16);
-        TAKE(status_out, int32_t, B);
-        TAKE(n_valid_out, int32_t, B);
-        TAKE(n_lift_out, int32_t, B);
-#undef TAKE
-        b.pdsc_ws = take("pdsc_ws", L.pdsc_ws_bytes);
-        b.bytes = off - b.base;
+        named("pcd_a", b.pcd_a, B * L.n_cap * 3);
+        named("pcd_q", b.pcd_q, B * L.n_cap * 3);
+        named("n_lift", b.n_lift, B);
+        named("pose", b.pose, B * 16);
+        named("status_out", b.status_out, B);
+        named("n_valid_out", b.n_valid_out, B);
+        named("n_lift_out", b.n_lift_out, B);
+        named("pdsc_ws", b.pdsc_ws, L.pdsc_ws_bytes);
+        b.bytes = carve.off - b.base;
     }
-    L.match_ws = base ? base + off : nullptr;
-    off = up(off + L.match_ws_bytes, 256);
-    L.bytes = off;
+    carve(L.match_ws, L.match_ws_bytes);
+    L.bytes = carve.off;
     return ORYON_OK;
 }
 

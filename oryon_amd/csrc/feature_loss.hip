@@ -34,8 +34,6 @@ constexpr int FL_TJ = 64;                  // pool candidates per LDS tile
 constexpr int FL_MAX_C = 256;              // dynamic LDS = 2 * 64 * C floats = 128 KB at C = 256
 constexpr int MD_THREADS = 512;
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
 // 64 rows of the NCHW map `f` at the pixels pix[0..63] (-1: a row of zeros) -> dst [C][64] as unit rows.  Called by the whole block.
 __device__ __forceinline__ void load_unit_rows(const float *__restrict__ f, int C, size_t HW, const int *pix, float *dst, float *s_d)
 {
@@ -331,7 +329,7 @@ using namespace oryon;
 extern "C" size_t oryon_feature_loss_workspace_bytes(int B, int n_corr, int n_pool)
 {
     if (B <= 0 || B > 65535 || n_corr <= 0 || n_pool < 0) return 0;
-    return up256((size_t)B * 3 * sizeof(double));           // the pairs' float64 means between the finish and the batch kernel
+    return align256((size_t)B * 3 * sizeof(double));           // the pairs' float64 means between the finish and the batch kernel
 }
 
 extern "C" int oryon_feature_loss(const float *feat_a, const float *feat_q, int B, int C, int FH, int FW, const int32_t *corrs, int n_corr,
@@ -352,11 +350,7 @@ extern "C" int oryon_feature_loss(const float *feat_a, const float *feat_q, int 
         return ORYON_OK;
     }
     ORYON_CHECK_ARG(feat_a && feat_q && corrs && valid && d_pos && d_neg && neg_idx && pair_terms);
-    const size_t need = up256((size_t)B * 3 * sizeof(double));
-    if (!workspace || workspace_bytes < need) {
-        set_error("feature-loss workspace too small (%zu < %zu)", workspace_bytes, need);
-        return ORYON_ERR_WORKSPACE;
-    }
+    ORYON_CHECK_WORKSPACE("feature-loss ", workspace, workspace_bytes, oryon_feature_loss_workspace_bytes(B, n_corr, n_pool));
     double *pair_sums = static_cast<double *>(workspace);
     const size_t dyn = (size_t)C * (FL_TP + FL_TJ) * sizeof(float);
     // the opt-in is made once per (kernel, device), so it is for the largest C, not for this call's: the next call may have more channels

@@ -28,8 +28,6 @@ constexpr int FG_MAX_C = 256;
 constexpr int FG_MAX_N = 4096;             // 2 N keys + 2 N links in LDS: 16 N bytes = 64 KB
 constexpr double FG_EPS = 1e-8;
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
 __device__ __forceinline__ int clamped_pixel(const int32_t *c, int FH, int FW)
 {
     return min(max(c[0], 0), FH - 1) * FW + min(max(c[1], 0), FW - 1);
@@ -174,7 +172,7 @@ using namespace oryon;
 extern "C" size_t oryon_feature_loss_grad_workspace_bytes(int B, int C, int n_corr)
 {
     if (B <= 0 || B > 65535 || C <= 0 || C > FG_MAX_C || n_corr <= 0 || n_corr > FG_MAX_N) return 0;
-    return up256((size_t)B * 2 * C * 2 * n_corr * sizeof(float));      // the 2 N contribution vectors of every (pair, side)
+    return align256((size_t)B * 2 * C * 2 * n_corr * sizeof(float));      // the 2 N contribution vectors of every (pair, side)
 }
 
 extern "C" int oryon_feature_loss_grad(const float *feat_a, const float *feat_q, int B, int C, int FH, int FW, const int32_t *corrs, int n_corr,
@@ -188,11 +186,7 @@ extern "C" int oryon_feature_loss_grad(const float *feat_a, const float *feat_q,
     if (n_corr > FG_MAX_N) { set_error("%s: n_corr = %d exceeds %d correspondences (LDS budget of the pixel keys)", __func__, n_corr, FG_MAX_N); return ORYON_ERR_INVALID_ARG; }
     if (B == 0) return ORYON_OK;
     ORYON_CHECK_ARG(feat_a && feat_q && corrs && valid && neg_idx && d_pos && d_neg && g && grad_a && grad_q);
-    const size_t need = up256((size_t)B * 2 * C * 2 * n_corr * sizeof(float));
-    if (!workspace || workspace_bytes < need) {
-        set_error("feature-loss gradient workspace too small (%zu < %zu)", workspace_bytes, need);
-        return ORYON_ERR_WORKSPACE;
-    }
+    ORYON_CHECK_WORKSPACE("feature-loss gradient ", workspace, workspace_bytes, oryon_feature_loss_grad_workspace_bytes(B, C, n_corr));
     hipStream_t st = as_stream(stream);
     const size_t map_bytes = (size_t)B * C * FH * FW * sizeof(float);
     ORYON_CHECK_HIP(hipMemsetAsync(grad_a, 0, map_bytes, st));

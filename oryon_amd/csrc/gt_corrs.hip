@@ -181,16 +181,14 @@ struct GtcWorkspace {
 static GtcWorkspace gtc_carve(void *workspace, int B, int cap_a, int cap_q)
 {
     GtcWorkspace w;
-    char *p = static_cast<char *>(workspace);
-    size_t at = 0;
-    auto take = [&](size_t n) { char *r = p ? p + at : nullptr; at += align256(n); return r; };
-    w.xyz_a = reinterpret_cast<double *>(take((size_t)B * cap_a * 3 * sizeof(double)));
-    w.xyz_q = reinterpret_cast<double *>(take((size_t)B * cap_q * 3 * sizeof(double)));
-    w.d2 = reinterpret_cast<double *>(take((size_t)B * cap_a * sizeof(double)));
-    w.yx_a = reinterpret_cast<int32_t *>(take((size_t)B * cap_a * 2 * sizeof(int32_t)));
-    w.yx_q = reinterpret_cast<int32_t *>(take((size_t)B * cap_q * 2 * sizeof(int32_t)));
-    w.idx = reinterpret_cast<int32_t *>(take((size_t)B * cap_a * sizeof(int32_t)));
-    w.bytes = at;
+    Carver carve(workspace);
+    carve(w.xyz_a, (size_t)B * cap_a * 3);
+    carve(w.xyz_q, (size_t)B * cap_q * 3);
+    carve(w.d2, (size_t)B * cap_a);
+    carve(w.yx_a, (size_t)B * cap_a * 2);
+    carve(w.yx_q, (size_t)B * cap_q * 2);
+    carve(w.idx, (size_t)B * cap_a);
+    w.bytes = carve.off;
     return w;
 }
 

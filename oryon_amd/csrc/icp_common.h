@@ -147,12 +147,10 @@ struct IcpWorkspace {
 static IcpWorkspace icp_carve(void *workspace, int B, int cap_src, int rec)
 {
     IcpWorkspace w;
-    char *p = static_cast<char *>(workspace);
-    size_t at = 0;
-    auto take = [&](size_t n) { char *r = p ? p + at : nullptr; at += align256(n); return r; };
-    w.state = reinterpret_cast<IcpState *>(take((size_t)B * sizeof(IcpState)));
-    w.partials = reinterpret_cast<double *>(take((size_t)B * ceil_div(cap_src, ICP_THREADS) * rec * sizeof(double)));
-    w.bytes = at;
+    Carver carve(workspace);
+    carve(w.state, B);
+    carve(w.partials, (size_t)B * ceil_div(cap_src, ICP_THREADS) * rec);
+    w.bytes = carve.off;
     return w;
 }
 

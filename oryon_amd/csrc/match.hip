@@ -464,10 +464,7 @@ extern "C" int oryon_match_f32(const float *a_hat, const float *q_hat, int B, in
     int32_t *ws_idx = nullptr;
     if (S > 1) {
         const size_t need = (size_t)B * S * cap_a * (sizeof(float) + sizeof(int32_t));
-        if (!workspace || workspace_bytes < need) {
-            set_error("oryon_match_f32: workspace too small (%zu < %zu)", workspace_bytes, need);
-            return ORYON_ERR_WORKSPACE;
-        }
+        ORYON_CHECK_WORKSPACE("oryon_match_f32: ", workspace, workspace_bytes, need);
         ws_dist = static_cast<float *>(workspace);
         ws_idx = reinterpret_cast<int32_t *>(ws_dist + (size_t)B * S * cap_a);
     }

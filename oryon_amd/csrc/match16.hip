@@ -963,10 +963,7 @@ extern "C" int oryon_match_screened(const float *a_hat, const float *q_hat, cons
     const int S = pick_split16(B, T);
     ScreenWs w;
     const size_t need = carve_screen(workspace, w, B, C, cap_a, S);
-    if (!workspace || workspace_bytes < need) {
-        set_error("oryon_match_screened: workspace too small (%zu < %zu)", workspace_bytes, need);
-        return ORYON_ERR_WORKSPACE;
-    }
+    ORYON_CHECK_WORKSPACE("oryon_match_screened: ", workspace, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     ORYON_CHECK_HIP(hipMemsetAsync(static_cast<char *>(workspace) + w.zero_off, 0, w.zero_bytes, st));
     // rows whose best fp16 score is below this can never satisfy 0.5*(1-dot) < threshold
@@ -1150,10 +1147,7 @@ extern "C" int oryon_match_screened8(const float *a_hat, const float *q_hat, con
     const int S = pick_split16(B, cap_a / MT16);
     Screen8Ws w;
     const size_t need = carve_screen8(workspace, w, B, C, cap_a, cap_q, S);
-    if (!workspace || workspace_bytes < need) {
-        set_error("oryon_match_screened8: workspace too small (%zu < %zu)", workspace_bytes, need);
-        return ORYON_ERR_WORKSPACE;
-    }
+    ORYON_CHECK_WORKSPACE("oryon_match_screened8: ", workspace, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     Screen8Args m;                 // the query rows are fp32 rows here (q_hat): no raw map
     m.a_hat = a_hat;
@@ -1211,10 +1205,7 @@ extern "C" int oryon_match_screened8_raw(const float *a_hat, const int8_t *a_i8,
     const int S = pick_split16(B, cap_a / MT16);
     Screen8RawWs w;
     const size_t need = carve_screen8_raw(workspace, w, B, C, cap_a, cap_q, S);
-    if (!workspace || workspace_bytes < need) {
-        set_error("oryon_match_screened8_raw: workspace too small (%zu < %zu)", workspace_bytes, need);
-        return ORYON_ERR_WORKSPACE;
-    }
+    ORYON_CHECK_WORKSPACE("oryon_match_screened8_raw: ", workspace, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     Screen8Args m;
     m.a_hat = a_hat;

@@ -1,7 +1,6 @@
 // Shared bits of the matcher translation units (match.hip, match16.hip, match_corrs.hip, screen_mx6.hip, match_x3.hip).
 #pragma once
 #include <hip/hip_fp16.h>
-#include <type_traits>
 #include "common.h"
 
 namespace oryon {
@@ -54,20 +53,7 @@ constexpr int MX6_SAMPLED_PANEL = 512;        // rows of that panel (>= the samp
 inline int mx6_sampled_splits(int B) { int s = (512 + B - 1) / B; return s < 1 ? 1 : s > 16 ? 16 : s; }      // ~512 four-wave workgroups
 
 // ------------------------------------------------------------------------------------------------ workspaces of the screened matchers
-// One allocation, 256-byte aligned buffers, one line per buffer: carve(w.ws_max, B * S * cap_a) assigns the pointer (typed by it) and
-// advances.  The carve_* functions are walked twice with the same code: on a null base every pointer comes out null and only the
-// size (their return value) is of interest.
-struct Carver {
-    char *base;
-    size_t off;
-    explicit Carver(void *b, size_t start = 0) : base(static_cast<char *>(b)), off(start) {}
-    template <class T> void operator()(T *&p, size_t count)             // count elements (bytes for a void pointer)
-    {
-        p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off = (off + count * sizeof(std::conditional_t<std::is_void<T>::value, char, T>) + 255) / 256 * 256;
-    }
-};
-
+// (carved with common.h's Carver; the carve_* functions return the size)
 constexpr int MT16 = 256;               // anchors per workgroup of the screens (4 waves x 2 blocks of 32)
 
 // K1s (oryon_match_screened).  [zero_off, zero_off + zero_bytes) of the allocation is zeroed at the start of every call

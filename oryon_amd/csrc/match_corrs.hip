@@ -945,10 +945,7 @@ int oryon::match_corrs_lazy_impl(const MatchCorrsArgs &m)
     const int S = pick_split16(B, T);
     LazyWs w;
     const size_t need = carve_lazy(m.workspace, w, B, C, cap_a, cap_q, S, m.corr_rows);
-    if (!m.workspace || m.workspace_bytes < need) {
-        set_error("oryon_match_corrs_i8: workspace too small (%zu < %zu)", m.workspace_bytes, need);
-        return ORYON_ERR_WORKSPACE;
-    }
+    ORYON_CHECK_WORKSPACE("oryon_match_corrs_i8: ", m.workspace, m.workspace_bytes, need);
     hipStream_t st = as_stream(m.stream);
     const float cut0 = 1.0f - 2.0f * m.threshold;
     // second level for the sampled anchors no screen can separate: fp16x3 two-sweep scan (K1x3, match_x3.hip; C_pad 256) instead of the

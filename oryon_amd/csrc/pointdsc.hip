@@ -23,60 +23,45 @@ struct oryon_pointdsc {
 
 namespace {
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-struct Carver {
-    char *base;
-    size_t off = 0;
-    explicit Carver(void *p) : base(static_cast<char *>(p)) {}
-    template <typename T> T *take(size_t count)
-    {
-        off = align_up(off, 256);
-        T *r = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += count * sizeof(T);
-        return r;
-    }
-};
-
 size_t carve(const oryon_pointdsc_config_t &cfg, int B, int n_cap, void *ws_ptr, PdscWorkspace *ws)
 {
     const int C = cfg.num_channels, Hh = (C / 2 > 32) ? C / 2 : 32;
     const int S_cap = pdsc_seed_cap(cfg, n_cap), k = cfg.k;
-    Carver c(ws_ptr);
+    Carver c(ws_ptr);                   // a buffer the configuration does not have is carved with zero elements
     PdscWorkspace w;
     const size_t rows = (size_t)B * n_cap;
-    w.corr_pos = c.take<float>(rows * 8);
-    w.feat = c.take<float>(rows * C);
-    w.feat1 = c.take<float>(rows * C);
-    w.qkv = c.take<float>(rows * 3 * C);
-    w.msg = c.take<float>(rows * C);
-    w.kv_img = c.take<char>(C == 128 ? rows / 64 * PDSC_KV_TILE_BYTES : 0);
-    w.kv_img2 = c.take<char>(C == 128 ? rows / 64 * PDSC_KV_TILE_BYTES : 0);
-    w.sc = c.take<float>(rows * n_cap);
+    c(w.corr_pos, rows * 8);
+    c(w.feat, rows * C);
+    c(w.feat1, rows * C);
+    c(w.qkv, rows * 3 * C);
+    c(w.msg, rows * C);
+    c(w.kv_img, C == 128 ? rows / 64 * PDSC_KV_TILE_BYTES : 0);
+    c(w.kv_img2, C == 128 ? rows / 64 * PDSC_KV_TILE_BYTES : 0);
+    c(w.sc, rows * n_cap);
     w.att_splits = pdsc_attention_splits(B, n_cap);
-    w.att_o = c.take<float>(w.att_splits > 1 ? rows * C * w.att_splits : 0);
-    w.att_ml = c.take<float>(w.att_splits > 1 ? rows * 2 * w.att_splits : 0);
-    w.h1 = c.take<float>(rows * Hh);
-    w.h2 = c.take<float>(rows * Hh);
-    w.feat_n = c.take<float>(rows * C);
-    w.conf = c.take<float>(rows);
-    w.seed_key = c.take<float>(rows);
-    w.seeds = c.take<int32_t>((size_t)B * S_cap);
-    w.n_seeds = c.take<int32_t>(B);
-    w.knn = c.take<int32_t>((size_t)B * S_cap * k);
-    w.Mmat = c.take<float>((size_t)B * S_cap * k * k);
-    w.seed_w = c.take<float>((size_t)B * S_cap * k);
-    w.seed_dist = c.take<float>((size_t)B * S_cap * n_cap);
-    w.v_hist = c.take<float>((size_t)B * S_cap * 16 * 64);
-    w.close_hist = c.take<int32_t>((size_t)B * S_cap * 16);
-    w.seed_T = c.take<float>((size_t)B * S_cap * 16);
-    w.fitness = c.take<float>((size_t)B * S_cap);
-    w.best = c.take<int32_t>(B);
-    w.T0 = c.take<float>((size_t)B * 16);
+    c(w.att_o, w.att_splits > 1 ? rows * C * w.att_splits : 0);
+    c(w.att_ml, w.att_splits > 1 ? rows * 2 * w.att_splits : 0);
+    c(w.h1, rows * Hh);
+    c(w.h2, rows * Hh);
+    c(w.feat_n, rows * C);
+    c(w.conf, rows);
+    c(w.seed_key, rows);
+    c(w.seeds, (size_t)B * S_cap);
+    c(w.n_seeds, B);
+    c(w.knn, (size_t)B * S_cap * k);
+    c(w.Mmat, (size_t)B * S_cap * k * k);
+    c(w.seed_w, (size_t)B * S_cap * k);
+    c(w.seed_dist, (size_t)B * S_cap * n_cap);
+    c(w.v_hist, (size_t)B * S_cap * 16 * 64);
+    c(w.close_hist, (size_t)B * S_cap * 16);
+    c(w.seed_T, (size_t)B * S_cap * 16);
+    c(w.fitness, (size_t)B * S_cap);
+    c(w.best, B);
+    c(w.T0, (size_t)B * 16);
     w.S_cap = S_cap;
     w.k = k;
     if (ws) *ws = w;
-    return align_up(c.off, 256);
+    return c.off;
 }
 
 bool expected_numel(const oryon_pointdsc_config_t &cfg, const std::string &name, int64_t *numel)
@@ -352,11 +337,7 @@ extern "C" size_t oryon_pointdsc_workspace_bytes(const oryon_pointdsc_t *h, int 
 
 static int get_ws(oryon_pointdsc_t *h, int B, int n_cap, void *workspace, size_t workspace_bytes, PdscWorkspace *ws)
 {
-    const size_t need = carve(h->cfg, B, n_cap, nullptr, nullptr);
-    if (!workspace || workspace_bytes < need) {
-        set_error("pointdsc workspace too small (%zu < %zu)", workspace_bytes, need);
-        return ORYON_ERR_WORKSPACE;
-    }
+    ORYON_CHECK_WORKSPACE("pointdsc ", workspace, workspace_bytes, carve(h->cfg, B, n_cap, nullptr, nullptr));
     carve(h->cfg, B, n_cap, workspace, ws);
     return ORYON_OK;
 }

@@ -38,23 +38,19 @@ struct RansacWs {
     double *rt_best, *rt_exit;      // [B, nblk, 12]  the 3x4 transform behind each block's key / exit candidate
 };
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 inline int n_blocks(int max_iter) { return (max_iter + RS_THREADS - 1) / RS_THREADS; }
 
 size_t carve_ransac(int B, int max_iter, void *base, RansacWs *ws)
 {
-    const size_t per = (size_t)B * n_blocks(max_iter) * 12 * sizeof(double);
-    char *p = static_cast<char *>(base);
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        const size_t o = off;
-        off = up256(off + n);
-        return p ? p + o : nullptr;
-    };
-    void *best = take((size_t)B * sizeof(unsigned long long)), *fe = take((size_t)B * sizeof(unsigned));
-    void *rb = take(per), *re = take(per);
-    if (ws) *ws = RansacWs{static_cast<unsigned long long *>(best), static_cast<unsigned *>(fe), static_cast<double *>(rb), static_cast<double *>(re)};
-    return off;
+    const size_t per = (size_t)B * n_blocks(max_iter) * 12;
+    Carver carve(base);
+    RansacWs w;
+    carve(w.best, B);
+    carve(w.first_exit, B);
+    carve(w.rt_best, per);
+    carve(w.rt_exit, per);
+    if (ws) *ws = w;
+    return carve.off;
 }
 
 // Squared float64 residual of one correspondence under RT (3x4 row-major).  Explicit fma: the scoring kernel's fallback and the
@@ -354,11 +350,7 @@ extern "C" int oryon_ransac_register(const float *src, const float *tgt, const i
     if (B == 0) return ORYON_OK;
     ORYON_CHECK_ARG(src && tgt && n && T);
     RansacWs ws;
-    const size_t need = carve_ransac(B, max_iter, nullptr, nullptr);
-    if (!workspace || workspace_bytes < need) {
-        set_error("ransac workspace too small (%zu < %zu)", workspace_bytes, need);
-        return ORYON_ERR_WORKSPACE;
-    }
+    ORYON_CHECK_WORKSPACE("ransac ", workspace, workspace_bytes, carve_ransac(B, max_iter, nullptr, nullptr));
     carve_ransac(B, max_iter, workspace, &ws);
     hipStream_t st = as_stream(stream);
     const int nblk = n_blocks(max_iter);

@@ -84,34 +84,28 @@ int seed_cap(const oryon_spectral_config_t &c, int n_cap) { return (int)((double
 
 size_t carve_spectral(const oryon_spectral_config_t &c, int B, int n_cap, void *base, SpectralWs *ws)
 {
-    char *p = static_cast<char *>(base);
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        const size_t o = off;
-        off = align256(off + n);
-        return p ? static_cast<void *>(p + o) : nullptr;
-    };
+    Carver carve(base);
     const size_t rows = (size_t)B * n_cap, S_cap = (size_t)seed_cap(c, n_cap), seeds = (size_t)B * S_cap, k = (size_t)c.k;
     SpectralWs w;
-    w.compat = static_cast<uint32_t *>(take(rows * (n_cap / 32) * sizeof(uint32_t)));
-    w.u0 = static_cast<float *>(take(rows * sizeof(float)));
-    w.u1 = static_cast<float *>(take(rows * sizeof(float)));
-    w.conf = static_cast<float *>(take(rows * sizeof(float)));
-    w.seed_key = static_cast<float *>(take(rows * sizeof(float)));
-    w.seeds = static_cast<int32_t *>(take(seeds * sizeof(int32_t)));
-    w.n_seeds = static_cast<int32_t *>(take((size_t)B * sizeof(int32_t)));
-    w.sets = static_cast<int32_t *>(take(seeds * k * sizeof(int32_t)));
-    w.Mmat = static_cast<float *>(take(seeds * k * k * sizeof(float)));
-    w.v_hist = static_cast<float *>(take(seeds * SP_MAX_IT * 64 * sizeof(float)));
-    w.close_hist = static_cast<int32_t *>(take(seeds * SP_MAX_IT * sizeof(int32_t)));
-    w.seed_T = static_cast<float *>(take(seeds * 16 * sizeof(float)));
-    w.fitness = static_cast<float *>(take(seeds * sizeof(float)));
-    w.best = static_cast<int32_t *>(take((size_t)B * sizeof(int32_t)));
-    w.T0 = static_cast<float *>(take((size_t)B * 16 * sizeof(float)));
-    w.T = static_cast<float *>(take((size_t)B * 16 * sizeof(float)));
+    carve(w.compat, rows * (n_cap / 32));
+    carve(w.u0, rows);
+    carve(w.u1, rows);
+    carve(w.conf, rows);
+    carve(w.seed_key, rows);
+    carve(w.seeds, seeds);
+    carve(w.n_seeds, (size_t)B);
+    carve(w.sets, seeds * k);
+    carve(w.Mmat, seeds * k * k);
+    carve(w.v_hist, seeds * SP_MAX_IT * 64);
+    carve(w.close_hist, seeds * SP_MAX_IT);
+    carve(w.seed_T, seeds * 16);
+    carve(w.fitness, seeds);
+    carve(w.best, (size_t)B);
+    carve(w.T0, (size_t)B * 16);
+    carve(w.T, (size_t)B * 16);
     w.S_cap = (int)S_cap;
     if (ws) *ws = w;
-    return off;
+    return carve.off;
 }
 
 __device__ __forceinline__ int rows_of(const int32_t *__restrict__ n_rows, int b, int n_cap)
@@ -411,14 +405,8 @@ extern "C" size_t oryon_spectral_workspace_bytes(const oryon_spectral_config_t *
     if (B == 0) return ORYON_OK;                                                                                                     \
     ORYON_CHECK_ARG(src && tgt && n);                                                                                                \
     SpectralWs ws;                                                                                                                   \
-    {                                                                                                                                \
-        const size_t need = carve_spectral(*cfg, B, n_cap, nullptr, nullptr);                                                        \
-        if (!workspace || workspace_bytes < need) {                                                                                  \
-            set_error("%s: spectral workspace too small (%zu < %zu)", __func__, workspace_bytes, need);                              \
-            return ORYON_ERR_WORKSPACE;                                                                                              \
-        }                                                                                                                            \
-        carve_spectral(*cfg, B, n_cap, workspace, &ws);                                                                              \
-    }
+    ORYON_CHECK_WORKSPACE("%s: spectral ", workspace, workspace_bytes, carve_spectral(*cfg, B, n_cap, nullptr, nullptr), __func__);  \
+    carve_spectral(*cfg, B, n_cap, workspace, &ws);
 
 extern "C" int oryon_spectral_register(const oryon_spectral_config_t *cfg, const float *src, const float *tgt, const int32_t *n, int B,
                                        int n_cap, const int32_t *status_in, void *workspace, size_t workspace_bytes, float *T,

@@ -248,14 +248,22 @@ __global__ __launch_bounds__(256) void vsd_score_kernel(const uint32_t *__restri
     }
 }
 
-static size_t render_workspace_bytes(int N, int max_faces) { return VSD_HEADER_BYTES + (size_t)N * max_faces * sizeof(uint2); }
+// render workspace: header (the counters) | queue of the large triangles [N, max_faces], which is not padded
+static size_t carve_render(void *base, int N, int max_faces, uint32_t *&counters, uint2 *&queue)
+{
+    Carver carve(base);
+    carve(counters, VSD_HEADER_BYTES / sizeof(uint32_t));
+    carve(queue, (size_t)N * max_faces);
+    return carve.end;
+}
 
 // z-buffer cleared and filled; zbuf [N,H,W] holds depth bit patterns, VSD_EMPTY where nothing was drawn
 static int rasterise(const float *pose, const float *K, int N, const Mesh &mesh, int max_faces, int H, int W, void *workspace, uint32_t *zbuf,
                      hipStream_t st)
 {
-    uint32_t *counters = static_cast<uint32_t *>(workspace);
-    uint2 *queue = reinterpret_cast<uint2 *>(static_cast<char *>(workspace) + VSD_HEADER_BYTES);
+    uint32_t *counters;
+    uint2 *queue;
+    carve_render(workspace, N, max_faces, counters, queue);
     ORYON_CHECK_HIP(hipMemsetAsync(counters, 0, VSD_HEADER_BYTES, st));
     ORYON_CHECK_HIP(hipMemsetAsync(zbuf, 0xff, (size_t)N * H * W * sizeof(uint32_t), st));
     hipLaunchKernelGGL(vsd_raster_setup_kernel, dim3(ceil_div(max_faces, 256), N), dim3(256), 0, st, pose, K, mesh, H, W, zbuf, counters, queue);
@@ -266,11 +274,37 @@ static int rasterise(const float *pose, const float *K, int N, const Mesh &mesh,
     return ORYON_OK;
 }
 
+// workspace of oryon_vsd_counts: render workspace (header first) | fp32 poses [2B,16] | fp32 K [2B,9] | model_of_image [2B] | z-buffers [2B,H,W]
+struct VsdWs {
+    void *render;
+    float *pose32, *K32;
+    int32_t *model_of_image;
+    uint32_t *zbuf;
+};
+static size_t carve_vsd(void *base, VsdWs &w, int B, int H, int W, int max_faces)
+{
+    const size_t N = 2 * (size_t)B;
+    uint32_t *counters;
+    uint2 *queue;
+    Carver carve(base);
+    carve(w.render, carve_render(nullptr, (int)N, max_faces, counters, queue));
+    carve(w.pose32, N * 16);
+    carve(w.K32, N * 9);
+    carve(w.model_of_image, N);
+    carve(w.zbuf, N * H * W);
+    return carve.off;
+}
+
 }  // namespace oryon
 
 using namespace oryon;
 
-extern "C" size_t oryon_render_depth_workspace_bytes(int N, int max_faces) { return N > 0 && max_faces > 0 ? render_workspace_bytes(N, max_faces) : 0; }
+extern "C" size_t oryon_render_depth_workspace_bytes(int N, int max_faces)
+{
+    uint32_t *counters;
+    uint2 *queue;
+    return N > 0 && max_faces > 0 ? carve_render(nullptr, N, max_faces, counters, queue) : 0;
+}
 
 extern "C" int oryon_render_depth(const float *pose, const float *K, int N, const float *verts_mm, const int32_t *vert_offset, const int32_t *faces,
                                   const int32_t *face_offset, int n_models, int max_faces, const int32_t *model_of_image, int H, int W,
@@ -290,13 +324,11 @@ extern "C" int oryon_render_depth(const float *pose, const float *K, int N, cons
     return ORYON_OK;
 }
 
-// workspace of oryon_vsd_counts: render workspace (header first) | fp32 poses [2B,16] | fp32 K [2B,9] | model_of_image [2B] | z-buffers [2B,H,W]
 extern "C" size_t oryon_vsd_workspace_bytes(int B, int H, int W, int max_faces)
 {
     if (B <= 0 || H <= 0 || W <= 0 || max_faces <= 0) return 0;
-    const size_t N = 2 * (size_t)B;
-    return align256(render_workspace_bytes((int)N, max_faces)) + align256(N * 16 * sizeof(float)) + align256(N * 9 * sizeof(float)) +
-           align256(N * sizeof(int32_t)) + align256(N * H * W * sizeof(uint32_t));
+    VsdWs w;
+    return carve_vsd(nullptr, w, B, H, W, max_faces);
 }
 
 extern "C" int oryon_vsd_counts(const double *pred_pose, const double *gt_pose, const double *K, const float *depth_test, int B, int H, int W,
@@ -310,20 +342,16 @@ extern "C" int oryon_vsd_counts(const double *pred_pose, const double *gt_pose, 
     if (B == 0) return ORYON_OK;
     hipStream_t st = as_stream(stream);
     const int N = 2 * B;
-    char *w = static_cast<char *>(workspace);
-    void *render_ws = w;                  w += align256(render_workspace_bytes(N, max_faces));
-    float *pose32 = (float *)w;           w += align256((size_t)N * 16 * sizeof(float));
-    float *K32 = (float *)w;              w += align256((size_t)N * 9 * sizeof(float));
-    int32_t *model_of_image = (int32_t *)w; w += align256((size_t)N * sizeof(int32_t));
-    uint32_t *zbuf = (uint32_t *)w;
-    hipLaunchKernelGGL(vsd_prepare_kernel, dim3(ceil_div(N, 128)), dim3(128), 0, st, B, pred_pose, gt_pose, K, model_of_pair, pose32, K32,
-                       model_of_image);
-    const Mesh mesh{verts_mm, vert_offset, faces, face_offset, model_of_image, n_models, max_faces};
-    const int rc = rasterise(pose32, K32, N, mesh, max_faces, H, W, render_ws, zbuf, st);
+    VsdWs w;
+    carve_vsd(workspace, w, B, H, W, max_faces);
+    hipLaunchKernelGGL(vsd_prepare_kernel, dim3(ceil_div(N, 128)), dim3(128), 0, st, B, pred_pose, gt_pose, K, model_of_pair, w.pose32, w.K32,
+                       w.model_of_image);
+    const Mesh mesh{verts_mm, vert_offset, faces, face_offset, w.model_of_image, n_models, max_faces};
+    const int rc = rasterise(w.pose32, w.K32, N, mesh, max_faces, H, W, w.render, w.zbuf, st);
     if (rc != ORYON_OK) return rc;
     ORYON_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * (2 + n_tau) * sizeof(int32_t), st));
     const int blocks = min(ceil_div(H * W, 1024), 256);
-    hipLaunchKernelGGL(vsd_score_kernel, dim3(blocks, B), dim3(256), 0, st, zbuf, depth_test, K, H, W, diameter_mm, (float)delta, taus, n_tau,
+    hipLaunchKernelGGL(vsd_score_kernel, dim3(blocks, B), dim3(256), 0, st, w.zbuf, depth_test, K, H, W, diameter_mm, (float)delta, taus, n_tau,
                        counts);
     ORYON_CHECK_LAUNCH();
     return ORYON_OK;

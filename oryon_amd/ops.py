@@ -154,7 +154,6 @@ def fusion_class_layer(x_nhwc: torch.Tensor, text_guidance: torch.Tensor, params
     shapes = [(128,), (128,), (128, 256), (128,), (128, 256), (128,), (128, 128), (128,), (128,), (128,), (512, 128), (512,), (128, 512), (128,)]
     assert [tuple(p.shape) for p in ps] == shapes, [tuple(p.shape) for p in ps]
     w = _lib.FusionClassWeights(*[ptr(p) for p in ps])
-    import ctypes
     check(lib().oryon_fusion_class_layer_f32(ptr(x), ptr(tg), ctypes.byref(w), B, ptr(out), stream_ptr(dev)), "oryon_fusion_class_layer_f32")
     return out
 
@@ -255,7 +254,7 @@ def rgb_augment_resize(rgb_hwc: torch.Tensor, table: torch.Tensor, out_hw: Tuple
     table = _flip_table(table, n, rgb_hwc.device)
     out = torch.empty((n, 3, int(out_hw[0]), int(out_hw[1])), dtype=torch.float32, device=rgb_hwc.device)
     ws_bytes = int(lib().oryon_rgb_augment_workspace_bytes(n))
-    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=rgb_hwc.device)
+    ws = _lib.workspace(rgb_hwc.device, ws_bytes)
     check(lib().oryon_rgb_augment_resize(ptr(rgb_hwc), ptr(table), n, HI, WI, int(out_hw[0]), int(out_hw[1]), ptr(ws), ws_bytes, ptr(out),
                                          stream_ptr(rgb_hwc.device)), "oryon_rgb_augment_resize")
     return out
@@ -370,7 +369,7 @@ def match(a_hat: torch.Tensor, q_hat: torch.Tensor, n_a: torch.Tensor, n_q: torc
     argmin = torch.empty((B, cap_a), dtype=torch.int32, device=dev)
     valid = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
     wsb = lib().oryon_match_workspace_bytes(B, cap_a)
-    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(dev, wsb)
     check(lib().oryon_match_f32(ptr(a_hat), ptr(q_hat), B, Cp, cap_a, cap_q, ptr(n_a), ptr(n_q), float(threshold),
                                 ptr(min_dist), ptr(argmin), ptr(valid), ptr(ws), wsb, stream_ptr(dev)), "oryon_match_f32")
     return min_dist, argmin, valid
@@ -387,7 +386,7 @@ def match_screened(a_hat, q_hat, a16, q16, n_a, n_q, threshold: float):
     argmin = torch.empty((B, cap_a), dtype=torch.int32, device=dev)
     valid = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
     wsb = lib().oryon_match_screened_workspace_bytes(B, Cp, cap_a)
-    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(dev, wsb)
     check(lib().oryon_match_screened(ptr(a_hat), ptr(q_hat), ptr(a16), ptr(q16), B, Cp, cap_a, cap_q, ptr(n_a), ptr(n_q),
                                      float(threshold), ptr(min_dist), ptr(argmin), ptr(valid), ptr(ws), wsb, stream_ptr(dev)),
           "oryon_match_screened")
@@ -482,8 +481,7 @@ def _cached_raw_ws(dev, wsb: int):
     key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
     ws = _raw_ws.get(key)
     if ws is None or ws.numel() < wsb:
-        ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
-        _raw_ws[key] = ws
+        ws = _raw_ws[key] = _lib.workspace(dev, wsb)
     return ws
 
 
@@ -528,7 +526,7 @@ def _match_corrs(entry: str, a_hat, feat_a, a_norm, a_rows, a_aux, feat_q, roi_a
         with _raw_ws_lock:
             call(_cached_raw_ws(dev, wsb))
     else:
-        call(torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev))
+        call(_lib.workspace(dev, wsb))
     return corrs, n_valid, n_sel, status, min_dist, argmin, valid
 
 
@@ -612,7 +610,7 @@ def match_screened8(a_hat, q_hat, a8, q8, a_scale, q_scale, q_eps, n_a, n_q, thr
     argmin = torch.empty((B, cap_a), dtype=torch.int32, device=dev)
     valid = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
     wsb = lib().oryon_match_screened8_workspace_bytes(B, Cp, cap_a, cap_q)
-    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(dev, wsb)
     check(lib().oryon_match_screened8(ptr(a_hat), ptr(q_hat), ptr(a8), ptr(q8), ptr(a_scale), ptr(q_scale), ptr(q_eps),
                                       B, int(c_true), Cp, cap_a, cap_q, ptr(n_a), ptr(n_q), float(threshold), ptr(min_dist), ptr(argmin),
                                       ptr(valid), ptr(n_undecided), ptr(ws), wsb, stream_ptr(dev)), "oryon_match_screened8")
@@ -700,10 +698,9 @@ def ransac_register(src: torch.Tensor, tgt: torch.Tensor, n: torch.Tensor, max_i
     max_iter = int(max_iter)
     if sample_idx is not None:
         assert sample_idx.dtype == torch.int32 and tuple(sample_idx.shape) == (B, max_iter, 4)
-    need = lib().oryon_ransac_workspace_bytes(B, n_cap, max_iter)
-    if need == 0 and B > 0:
-        raise _lib.OryonError(f"oryon_ransac_workspace_bytes({B}, {n_cap}, {max_iter}): shape not supported (n_cap <= 2048, max_iter > 0)")
-    ws = workspace if workspace is not None else torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(dev, lib().oryon_ransac_workspace_bytes(B, n_cap, max_iter),
+                        f"oryon_ransac_workspace_bytes({B}, {n_cap}, {max_iter})" if B > 0 else None, workspace,
+                        "shape not supported (n_cap <= 2048, max_iter > 0)")
     T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
     winner = torch.empty((B,), dtype=torch.int32, device=dev)
     exited = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -734,11 +731,9 @@ def _spectral_args(src, tgt, n, status, workspace, cfg):
     assert n.dtype == torch.int32 and (status is None or status.dtype == torch.int32)
     B, n_cap = src.shape[0], src.shape[1]
     c = spectral_config(**cfg)
-    need = lib().oryon_spectral_workspace_bytes(ctypes.byref(c), B, n_cap)
-    if need == 0 and B > 0:
-        raise _lib.OryonError(f"oryon_spectral_workspace_bytes(B={B}, n_cap={n_cap}): shape or configuration not supported "
-                              "(n_cap % 128 == 0, n_cap <= 2048, 2 <= k <= 63, 1 <= num_iterations <= 16)")
-    ws = workspace if workspace is not None else torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(dev, lib().oryon_spectral_workspace_bytes(ctypes.byref(c), B, n_cap),
+                        f"oryon_spectral_workspace_bytes(B={B}, n_cap={n_cap})" if B > 0 else None, workspace,
+                        "shape or configuration not supported (n_cap % 128 == 0, n_cap <= 2048, 2 <= k <= 63, 1 <= num_iterations <= 16)")
     return dev, B, n_cap, c, ws
 
 
@@ -802,10 +797,8 @@ def feature_loss(feat_a: torch.Tensor, feat_q: torch.Tensor, corrs: torch.Tensor
     if pool is not None:
         assert pool.dtype == torch.int32 and pool.dim() == 3 and tuple(pool.shape[:2]) == (B, 2)
         n_pool = pool.shape[2]
-    need = lib().oryon_feature_loss_workspace_bytes(B, N, n_pool)
-    if need == 0 and B > 0:
-        raise _lib.OryonError(f"oryon_feature_loss_workspace_bytes({B}, {N}, {n_pool}): shape not supported")
-    ws = workspace if workspace is not None else torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(dev, lib().oryon_feature_loss_workspace_bytes(B, N, n_pool),
+                        f"oryon_feature_loss_workspace_bytes({B}, {N}, {n_pool})" if B > 0 else None, workspace)
     d_pos = torch.empty((B, N), dtype=torch.float32, device=dev)
     d_neg = torch.empty((B, 2, N), dtype=torch.float32, device=dev)
     neg_idx = torch.empty((B, 2, N), dtype=torch.int32, device=dev)
@@ -850,10 +843,9 @@ def feature_loss_grad(feat_a: torch.Tensor, feat_q: torch.Tensor, corrs: torch.T
     assert neg_idx.dtype == torch.int32 and tuple(neg_idx.shape) == (B, 2, N)
     assert d_pos.dtype == torch.float32 and tuple(d_pos.shape) == (B, N) and d_neg.dtype == torch.float32 and tuple(d_neg.shape) == (B, 2, N)
     assert g.dtype == torch.float32 and g.numel() == 3 and g.device == feat_a.device
-    need = lib().oryon_feature_loss_grad_workspace_bytes(B, C, N)
-    if need == 0 and B > 0:
-        raise _lib.OryonError(f"oryon_feature_loss_grad_workspace_bytes({B}, {C}, {N}): shape not supported (C <= 256, n_corr <= 4096)")
-    ws = workspace if workspace is not None else torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(dev, lib().oryon_feature_loss_grad_workspace_bytes(B, C, N),
+                        f"oryon_feature_loss_grad_workspace_bytes({B}, {C}, {N})" if B > 0 else None, workspace,
+                        "shape not supported (C <= 256, n_corr <= 4096)")
     if out is None:
         out = (torch.empty((B, C, FH, FW), dtype=torch.float32, device=dev), torch.empty((B, C, FH, FW), dtype=torch.float32, device=dev))
     grad_a, grad_q = out
@@ -922,7 +914,7 @@ def pose_bop_errors(pred_pose: torch.Tensor, gt_pose: torch.Tensor, K: torch.Ten
     po, so = pts_offset.to(torch.int32).cpu(), sym_offset.to(torch.int32).cpu()
     n_models = po.numel() - 1
     max_syms = int((so[1:] - so[:-1]).max())
-    ws = torch.empty((max(1, lib().oryon_pose_bop_workspace_bytes(B, max_syms) // 8),), dtype=torch.float64, device=dev)
+    ws = _lib.workspace(dev, lib().oryon_pose_bop_workspace_bytes(B, max_syms))
     out = torch.empty((B, 2), dtype=torch.float64, device=dev)
     mop = None if model_of_pair is None else model_of_pair.to(dev, torch.int32).contiguous()
     po_d, so_d = po.to(dev), so.to(dev)               # named: a temporary would be freed (and its block re-used) before the launch
@@ -959,7 +951,7 @@ def render_depth(pose: torch.Tensor, K: torch.Tensor, verts_mm: torch.Tensor, fa
     Kc = K.to(dev, torch.float32).reshape(N, 9).contiguous()
     verts, fc, vo_d, fo_d, n_models, max_faces = _mesh_args(dev, verts_mm, faces, vert_offset, face_offset)
     moi = None if model_of_image is None else model_of_image.to(dev, torch.int32).contiguous()
-    ws = torch.empty((max(8, lib().oryon_render_depth_workspace_bytes(N, max_faces)),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(dev, lib().oryon_render_depth_workspace_bytes(N, max_faces))
     depth = torch.empty((N, int(H), int(W)), dtype=torch.float32, device=dev)
     check(lib().oryon_render_depth(ptr(P), ptr(Kc), N, ptr(verts), ptr(vo_d), ptr(fc), ptr(fo_d), n_models, max_faces, ptr(moi), int(H),
                                    int(W), ptr(ws), ptr(depth), stream_ptr(dev)), "oryon_render_depth")
@@ -990,7 +982,7 @@ def vsd_counts(pred_pose: torch.Tensor, gt_pose: torch.Tensor, K: torch.Tensor, 
     n_tau = taus_d.numel()
     verts, fc, vo_d, fo_d, n_models, max_faces = _mesh_args(dev, verts_mm, faces, vert_offset, face_offset)
     mop = None if model_of_pair is None else model_of_pair.to(dev, torch.int32).contiguous()
-    ws = torch.empty((max(8, lib().oryon_vsd_workspace_bytes(B, H, W, max_faces)),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(dev, lib().oryon_vsd_workspace_bytes(B, H, W, max_faces))
     counts = torch.empty((B, 2 + n_tau), dtype=torch.int32, device=dev)
     check(lib().oryon_vsd_counts(ptr(pred), ptr(gt), ptr(Kc), ptr(dt), B, H, W, ptr(verts), ptr(vo_d), ptr(fc), ptr(fo_d), n_models, max_faces,
                                  ptr(mop), ptr(diam), float(delta), ptr(taus_d), n_tau, ptr(ws), ptr(counts), stream_ptr(dev)),
@@ -1092,10 +1084,8 @@ def gt_corrs(depth_a: torch.Tensor, depth_q: torch.Tensor, pix_a: torch.Tensor, 
         T = pose.to(dev, torch.float64).contiguous()
         na, nq = na.to(dev).contiguous(), nq.to(dev).contiguous()
         st = None if status is None else status.to(dev, torch.int32).contiguous()
-        need = lib().oryon_gt_corrs_workspace_bytes(B, cap_a, cap_q)
-        if need == 0 and B > 0:
-            raise _lib.OryonError(f"oryon_gt_corrs_workspace_bytes({B}, {cap_a}, {cap_q}): shape not supported")
-        ws = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(dev, lib().oryon_gt_corrs_workspace_bytes(B, cap_a, cap_q),
+                            f"oryon_gt_corrs_workspace_bytes({B}, {cap_a}, {cap_q})" if B > 0 else None)
         corrs = torch.empty((B, cap_a, 4), dtype=torch.int32, device=dev)
         n_corr = torch.empty((B,), dtype=torch.int32, device=dev)
         idx = torch.empty((B, cap_a), dtype=torch.int32, device=dev) if want_nn else None
@@ -1137,10 +1127,10 @@ def _icp_check_start(req, B: int, T_init, device, others, max_iter, tolerance, m
     return max_iter
 
 
-def _icp_outputs(dev, B: int, cap_src: int, need: int, workspace=None, want_idx: bool = False):
+def _icp_outputs(dev, B: int, cap_src: int, need: int, what: str, workspace=None, want_idx: bool = False):
     """What every refiner call writes: dict(T, T64, iters, mean_err, n_kept, idx | None, status), and the workspace."""
     new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
-    ws = workspace if workspace is not None else new((max(need, 256),), torch.uint8)
+    ws = _lib.workspace(dev, need, what, workspace)
     out = dict(T=new((B, 4, 4), torch.float32), T64=new((B, 3, 4), torch.float64), iters=new((B,), torch.int32),
                mean_err=new((B,), torch.float64), n_kept=new((B,), torch.int32), idx=new((B, cap_src), torch.int32) if want_idx else None,
                status=new((B,), torch.int32))
@@ -1172,10 +1162,8 @@ def icp_refine(src: torch.Tensor, dst: torch.Tensor, n_src: torch.Tensor, n_dst:
     req(cap_src <= ICP_MAX_ROWS and cap_dst <= ICP_MAX_ROWS, f"cap <= {ICP_MAX_ROWS}", f"{cap_src}, {cap_dst}")
     dev = _lib.require_gpu(src.device)
     with torch.cuda.device(dev):
-        need = lib().oryon_icp_workspace_bytes(B, cap_src, cap_dst)
-        if need == 0 and B > 0:
-            raise _lib.OryonError(f"oryon_icp_workspace_bytes({B}, {cap_src}, {cap_dst}): shape not supported")
-        o, ws = _icp_outputs(dev, B, cap_src, need, workspace, want_idx)
+        o, ws = _icp_outputs(dev, B, cap_src, lib().oryon_icp_workspace_bytes(B, cap_src, cap_dst),
+                             f"oryon_icp_workspace_bytes({B}, {cap_src}, {cap_dst})", workspace, want_idx)
         check(lib().oryon_icp_refine(ptr(src), ptr(n_src), cap_src, ptr(dst), ptr(n_dst), cap_dst, B, ptr(T_init), max_iter, float(tolerance),
                                      float(max_dist), ptr(status), ptr(ws), ws.numel(), ptr(o["T"]), ptr(o["T64"]), ptr(o["iters"]),
                                      ptr(o["mean_err"]), ptr(o["n_kept"]), ptr(o["idx"]), ptr(o["status"]), stream_ptr(dev)), "oryon_icp_refine")
@@ -1196,7 +1184,7 @@ def icp_best_fit(A: torch.Tensor, Bp: torch.Tensor, n: torch.Tensor):
         raise ValueError("icp_best_fit: n is [B] int32")
     dev = _lib.require_gpu(A.device)
     with torch.cuda.device(dev):
-        o, ws = _icp_outputs(dev, B, cap, lib().oryon_icp_workspace_bytes(B, cap, cap))
+        o, ws = _icp_outputs(dev, B, cap, lib().oryon_icp_workspace_bytes(B, cap, cap), None)
         check(lib().oryon_icp_best_fit(ptr(A), ptr(Bp), ptr(n), cap, B, ptr(ws), ws.numel(), ptr(o["T"]), ptr(o["T64"]), ptr(o["iters"]),
                                        ptr(o["mean_err"]), stream_ptr(dev)), "oryon_icp_best_fit")
     return dict(T=o["T"], T64=o["T64"], fitted=o["iters"], mean_err=o["mean_err"])
@@ -1236,10 +1224,8 @@ def icp_plane_refine(src: torch.Tensor, n_src: torch.Tensor, depth: torch.Tensor
     req(cap_src <= ICP_MAX_ROWS, f"cap_src <= {ICP_MAX_ROWS}", str(cap_src))
     dev = _lib.require_gpu(src.device)
     with torch.cuda.device(dev):
-        need = lib().oryon_icp_plane_workspace_bytes(B, cap_src)
-        if need == 0:
-            raise _lib.OryonError(f"oryon_icp_plane_workspace_bytes({B}, {cap_src}): shape not supported")
-        o, ws = _icp_outputs(dev, B, cap_src, need, workspace, want_idx)
+        o, ws = _icp_outputs(dev, B, cap_src, lib().oryon_icp_plane_workspace_bytes(B, cap_src),
+                             f"oryon_icp_plane_workspace_bytes({B}, {cap_src})", workspace, want_idx)
         check(lib().oryon_icp_plane_refine(ptr(src), ptr(n_src), cap_src, ptr(depth), ptr(mask), H, W, ptr(cam9), B, ptr(T_init), max_iter,
                                            float(tolerance), float(max_dist), float(normal_jump), ptr(status), ptr(ws), ws.numel(), ptr(o["T"]),
                                            ptr(o["T64"]), ptr(o["iters"]), ptr(o["mean_err"]), ptr(o["n_kept"]), ptr(o["idx"]),

@@ -157,8 +157,7 @@ class PointDSC(nn.Module):
             self._ws = {}
         ws = self._ws.get(slot)
         if ws is None or ws.numel() < need or ws.device != dev:
-            ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-            self._ws[slot] = ws
+            ws = self._ws[slot] = _lib.workspace(dev, need)
         return ws
 
     # ---- batched registration (the product path) ----------------------------------------------

@@ -82,6 +82,20 @@ def test_matcher_workspace_sizes_are_the_layout_contract():
     assert L.oryon_match_screened_workspace_bytes(64, 256, 5000) == 0 and L.oryon_match_corrs_i8_workspace_bytes(64, 256, 5120, 50176, 0) == 0
 
 
+def test_every_workspace_size_is_pinned():
+    """Every other workspace-size entry, the decoder's offset table and the engine's arena size, over the shapes of
+    tests/workspace_size_cases.py.  The numbers in tests/golden/workspace_sizes.json were recorded from a build of the commit BEFORE the
+    carving code moved onto common.h's Carver (never from the code under test): a layout that drifts by one alignment shows here."""
+    import json
+    import workspace_size_cases
+    from oryon_amd import _lib
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "workspace_sizes.json")))
+    got = workspace_size_cases.sizes(_lib.lib(), _lib)
+    assert len(want) == 72 and set(got) == set(want)
+    assert got == want, {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    assert all(v > 0 for k, v in want.items() if not k.startswith("oryon_decoder_workspace_layout[0]"))
+
+
 def test_no_cpu_fallback():
     from oryon_amd import pcd
     from oryon_amd._lib import OryonError

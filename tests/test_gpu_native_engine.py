@@ -260,3 +260,29 @@ def test_validity_cascade_with_unsettled_panels_gives_identical_results():
             assert torch.equal(outs[0][i][k], outs[1][i][k]), (i, k)
     # the Gaussian pair has anchors without a counterpart: fewer valid rows than anchors, i.e. its panels could not settle in the window
     assert int(outs[1][5]["n_valid"][2]) < int(outs[1][5]["n_valid"][0])
+
+
+def test_slot_layout_is_pinned():
+    """oryon_engine_buffer's (offset, bytes) of every slot buffer NativeStep.view knows, the registration workspace and the
+    sample_first buffers, for both slots of a small engine with and without the sample-first schedule.  tests/golden/
+    engine_slot_layout.json was recorded from a build of the commit BEFORE carve_engine moved onto common.h's Carver, never from the
+    code under test; None = the library has no buffer of that name in that configuration.  No step is submitted."""
+    import json
+    import os
+    from oryon_amd._lib import lib
+    from oryon_amd.engine import MatchPoseConfig, NativeStep
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "engine_slot_layout.json")))
+    solver = _solver()
+    names = list(NativeStep._SLOT_VIEWS) + ["pdsc_ws", "roi_a1", "n_a1", "n_a2", "corrs2", "n_valid2", "n_sel2", "status2"]
+    assert len(want) == 2 * (2 * len(names) + 1)
+    for sf in (0, 64):
+        nat = NativeStep(solver, MatchPoseConfig(n_corrs=128, sample_first=sf), (2, 32, 16, 16, 16, 16, 16, 16, 0), torch.device("cuda", 0),
+                         overlap=2, n_slots=2, gather_sets=2)
+        assert nat.arena.numel() == want[f"{sf}/arena"]
+        for slot in (0, 1):
+            for name in names:
+                off, nbytes = ctypes.c_size_t(), ctypes.c_size_t()
+                rc = lib().oryon_engine_buffer(nat._h, slot, name.encode(), ctypes.byref(off), ctypes.byref(nbytes))
+                assert ([off.value, nbytes.value] if rc == 0 else None) == want[f"{sf}/{slot}/{name}"], (sf, slot, name)
+            assert (want[f"{sf}/{slot}/roi_a1"] is not None) == (sf > 0)
+
