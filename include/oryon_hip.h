@@ -180,6 +180,26 @@ int oryon_match_f32(const float *a_hat, const float *q_hat, int B, int C, int ca
                     const int32_t *n_a, const int32_t *n_q, float threshold, float *min_dist, int32_t *argmin,
                     uint8_t *valid, void *workspace, size_t workspace_bytes, void *stream);
 
+/* K1m mutual nearest neighbours: both directions of K1 from ONE all-pairs scan (csrc/match_mutual.hip).
+ *     min_dist / argmin / valid [B,cap_a]: exactly what oryon_match_f32(a_hat, q_hat, ...) writes (rows < n_a).
+ *     rev_min_dist / rev_argmin [B,cap_q]: exactly what oryon_match_f32(q_hat, a_hat, ...) - the roles swapped - writes for
+ *     row j < n_q: the minimum over the n_a anchor rows passed in (first anchor index on ties).
+ *     mutual [B,cap_a] uint8: valid[i] && rev_argmin[argmin[i]] == i.  The argmin of a pair's mutual rows are pairwise distinct,
+ *     and on a mutual row rev_min_dist[argmin[i]] has the bits of min_dist[i].
+ * Pairs with n_a == 0 or n_q == 0 get what the two calls leave (INFINITY, index 0, valid 0) and mutual 0; rows >= n_a / >= n_q of
+ * the outputs are not written, rows >= n_a / >= n_q of the INPUTS are never used (masked by index in both directions).
+ * C a multiple of 32, caps multiples of ORYON_MATCH_TILE (cap_q of 256 when C == 32), B <= 65535.
+ * workspace: oryon_match_mutual_workspace_bytes(B, cap_a, cap_q) = ORYON_MATCH_MUTUAL_KEY_WORDS 8-byte words per query row
+ * (B cap_q of them: the (distance, index) keys the anchor panels meet in with a 64-bit atomic minimum) + oryon_match_workspace_bytes(B,
+ * cap_a) for K1's query splits; no per-panel slab. */
+#define ORYON_MATCH_MUTUAL_KEY_WORDS 1
+size_t oryon_match_mutual_workspace_bytes(int B, int cap_a, int cap_q);
+int oryon_match_mutual_f32(const float *a_hat, const float *q_hat, int B, int C, int cap_a, int cap_q,
+                           const int32_t *n_a, const int32_t *n_q, float threshold,
+                           float *min_dist, int32_t *argmin, uint8_t *valid,
+                           float *rev_min_dist, int32_t *rev_argmin, uint8_t *mutual,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* K1s same contract as oryon_match_f32 for every anchor row that can reach the threshold, computed as an fp16-MFMA
  *     screening pass (v_mfma_f32_32x32x16_f16 on the IEEE-half copies written by oryon_gather_normalise_f32) followed by
  *     an exact fp32 re-scoring of the surviving candidates with K1's canonical fmaf chain.  A proven error bound on the

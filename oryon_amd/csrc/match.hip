@@ -420,6 +420,8 @@ static int pick_split(int B, int T)
     return S;
 }
 
+int match_f32_split(int B, int T) { return pick_split(B, T); }
+
 int match_f32_flagged(const float *a_hat, const float *q_hat, int B, int C, int cap_a, int cap_q, const int32_t *n_a,
                       const int32_t *n_q, float threshold, float *min_dist, int32_t *argmin, uint8_t *valid,
                       const int32_t *panel_flag, const uint8_t *row_flag, void *stream)

@@ -21,6 +21,9 @@ int match_f32_flagged(const float *a_hat, const float *q_hat, int B, int C, int 
                       const int32_t *n_q, float threshold, float *min_dist, int32_t *argmin, uint8_t *valid,
                       const int32_t *panel_flag, const uint8_t *row_flag, void *stream);
 
+// K1's query splits S for a call with T anchor panels per pair (match.hip; K1m sizes its split buffers by the same rule)
+int match_f32_split(int B, int T);
+
 // K1x3 (match_x3.hip): fp32-grade scan of a compacted anchor list on the fp16 matrix pipe; see the file's header
 size_t match_x3_scratch_bytes(int B, int cap_s, int S, int cap_q);
 size_t match_x3_zero_bytes(int B, int cap_s, int S);         // the head of that scratch the caller zeroes before match_x3_resolve

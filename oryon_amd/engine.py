@@ -42,6 +42,20 @@ def default_solver() -> str:
     return _default_solver
 
 
+_default_mutual = False
+
+
+def set_default_mutual(on: bool) -> None:
+    """The process-wide default of test.mutual: what `MatchPoseConfig()` and `pipeline.default_args()` choose when the caller does not
+    say (False unless set).  A driver sets it once, before it builds pipelines (run_pose.py --mutual does, as --solver does)."""
+    global _default_mutual
+    _default_mutual = bool(on)
+
+
+def default_mutual() -> bool:
+    return _default_mutual
+
+
 @dataclass
 class MatchPoseConfig:
     """Flag names follow configs/config.yaml of the reference (test.* section)."""
@@ -79,6 +93,22 @@ class MatchPoseConfig:
     spectral_sigma_d: float = 0.01
     spectral_k: int = 40
     spectral_nms_radius: float = 0.02
+    # test.mutual: keep only the MUTUAL nearest neighbours (csrc/match_mutual.hip; the reference matches in one direction only).  One
+    # fused exact scan gives both directions; the sampler then draws from the rows with valid && rev_argmin[argmin] == row, n_valid
+    # counts those rows and a pair with at most one of them ends ORYON_PAIR_NO_CORR.  The reverse minimum runs over the anchors the
+    # matcher was GIVEN - the src_sampling subsample, not the whole mask.  Runs on the per-call schedule with the exact gather (the
+    # screened routes carry no reverse screen, the native C step engine does not know it); half_descriptors composes (the rounding
+    # happens before the gather), sample_first does not (a ValueError).
+    mutual: bool = field(default_factory=default_mutual)
+
+    def __post_init__(self):
+        _check_mutual(self)
+
+
+def _check_mutual(cfg: "MatchPoseConfig") -> None:
+    if cfg.mutual and cfg.sample_first and cfg.sample_first > 0:
+        raise ValueError("mutual=True does not combine with sample_first > 0: the reverse minimum of a first-stage subset of the anchors "
+                         "is not the reverse minimum of the pair")
 
 
 def _check_solver(cfg: "MatchPoseConfig", solver) -> bool:
@@ -525,10 +555,12 @@ class MatchPoseEngine:
         everything queued on the caller's stream so far (always correct, but then it cannot overlap the previous batch's matching)."""
         dev = _lib.require_gpu(feat_a.device)
         cfg = self.cfg
+        _check_mutual(cfg)
         B, C, FH, FW = feat_a.shape
         main = torch.cuda.current_stream(dev)
-        # the screens' validity cut is 1 - 2*dist_th: thresholds above 0.5 (or non-positive) take the exact scan
-        screened = cfg.match_mode in ("screened", "screened16") and 64 < C <= 512 and 0.0 < cfg.dist_th <= 0.5
+        # the screens' validity cut is 1 - 2*dist_th: thresholds above 0.5 (or non-positive) take the exact scan; so does mutual (no
+        # reverse screen exists)
+        screened = cfg.match_mode in ("screened", "screened16") and 64 < C <= 512 and 0.0 < cfg.dist_th <= 0.5 and not cfg.mutual
         use_i8 = screened and cfg.match_mode == "screened" and C > 128
         if use_i8:
             if self._i8_pending is not None and self._i8_pending[1].query():
@@ -544,7 +576,7 @@ class MatchPoseEngine:
         # the native step engine serves every width up to 512 on the screened route (narrow maps zero-padded to 256 channels by K0);
         # the per-call schedule below keeps its own choice per width (exact scan for C <= 64, fp16 screen for C <= 128)
         native_ok = cfg.match_mode == "screened" and C <= 512 and 0.0 < cfg.dist_th <= 0.5 and (use_i8 or C <= 128)
-        if native_ok and self.native and cfg.solver != "spectral":       # the C step engine does not know the spectral solver
+        if native_ok and self.native and cfg.solver != "spectral" and not cfg.mutual:   # the C step engine knows neither spectral nor mutual
             return self._run_native(feat_a, feat_q, mask_a, mask_q, depth_a, depth_q, cam_a, cam_q, pair_key, keep, inputs_event,
                                     inputs_resident, dev)
         if pair_key is None:
@@ -573,7 +605,7 @@ class MatchPoseEngine:
         else:
             cap_a = ops.round_up(FH * FW, ops.ROW_PAD)
         cap_q = ops.round_up(FH * FW, ops.ROW_PAD)
-        a16 = q16 = a8 = q8 = a_sc = q_sc = q_eps = q_norm = q_hat = roi_a1 = n_a1 = None
+        a16 = q16 = a8 = q8 = a_sc = q_sc = q_eps = q_norm = q_hat = roi_a1 = n_a1 = mutual = rev_argmin = rev_min_dist = None
         stage1 = use_i8 and cfg.sample_first > 0 and not keep
         if use_i8:
             # K0v3: anchors -> fp32 + int8 rows, queries -> int8 rows + row norms only (the re-scoring pass reads its few candidates
@@ -632,12 +664,15 @@ class MatchPoseEngine:
             if self._i8_pending is None and (self.i8_max_undecided < 1.0 or self.collect_i8_stats):
                 self._queue_i8_stats(n_und, n_a)
         else:
-            if screened:
+            if cfg.mutual:
+                min_dist, argmin, valid, rev_min_dist, rev_argmin, mutual = ops.match_mutual(a_hat, q_hat, n_a, n_q, cfg.dist_th)
+            elif screened:
                 min_dist, argmin, valid = ops.match_screened(a_hat, q_hat, a16, q16, n_a, n_q, cfg.dist_th)
             else:
                 min_dist, argmin, valid = ops.match(a_hat, q_hat, n_a, n_q, cfg.dist_th)
-            corrs, n_valid, n_sel, status = ops.select_corrs(roi_a, roi_q, n_a, n_q, argmin, valid, FW, cfg.n_corrs, cfg.seed,
-                                                             pair_key, corr_rows=self.n_cap)
+            # mutual: the sampler draws from the mutual rows, n_valid counts them, <= 1 of them is ORYON_PAIR_NO_CORR
+            corrs, n_valid, n_sel, status = ops.select_corrs(roi_a, roi_q, n_a, n_q, argmin, mutual if cfg.mutual else valid, FW,
+                                                             cfg.n_corrs, cfg.seed, pair_key, corr_rows=self.n_cap)
         cam_a = cam_a.reshape(B, 9).to(torch.float32).contiguous()
         cam_q = cam_q.reshape(B, 9).to(torch.float32).contiguous()
         pcd_a, pcd_q, n_lift = ops.lift_pairs(corrs, n_sel, (FH, FW), depth_a, depth_q, cam_a, cam_q, status)
@@ -671,4 +706,6 @@ class MatchPoseEngine:
         if keep:
             out.update(roi_a=roi_a, roi_q=roi_q, n_a=n_a, n_q=n_q, min_dist=min_dist, argmin=argmin, valid=valid, corrs=corrs,
                        pcd_a=pcd_a, pcd_q=pcd_q)
+            if cfg.mutual:
+                out.update(mutual=mutual, rev_argmin=rev_argmin, rev_min_dist=rev_min_dist)
         return out

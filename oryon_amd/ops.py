@@ -376,6 +376,29 @@ def match(a_hat: torch.Tensor, q_hat: torch.Tensor, n_a: torch.Tensor, n_q: torc
 
 
 @_on_tensor_device
+def match_mutual(a_hat: torch.Tensor, q_hat: torch.Tensor, n_a: torch.Tensor, n_q: torch.Tensor, threshold: float):
+    """Both directions of `match` from one scan (K1m): -> (min_dist [B,cap_a] f32, argmin [B,cap_a] i32, valid [B,cap_a] u8,
+    rev_min_dist [B,cap_q] f32, rev_argmin [B,cap_q] i32, mutual [B,cap_a] u8).  The first three are `match(a_hat, q_hat, ...)`, the
+    next two the first two of `match(q_hat, a_hat, n_q, n_a, ...)`, bit for bit; mutual = valid & (rev_argmin[argmin] == row)."""
+    dev = _lib.require_gpu(a_hat.device)
+    B, cap_a, Cp = a_hat.shape
+    cap_q = q_hat.shape[1]
+    assert q_hat.shape[0] == B and q_hat.shape[2] == Cp
+    min_dist = torch.empty((B, cap_a), dtype=torch.float32, device=dev)
+    argmin = torch.empty((B, cap_a), dtype=torch.int32, device=dev)
+    valid = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
+    rev_min_dist = torch.empty((B, cap_q), dtype=torch.float32, device=dev)
+    rev_argmin = torch.empty((B, cap_q), dtype=torch.int32, device=dev)
+    mutual = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
+    wsb = lib().oryon_match_mutual_workspace_bytes(B, cap_a, cap_q)
+    ws = _lib.workspace(dev, wsb)
+    check(lib().oryon_match_mutual_f32(ptr(a_hat), ptr(q_hat), B, Cp, cap_a, cap_q, ptr(n_a), ptr(n_q), float(threshold), ptr(min_dist),
+                                       ptr(argmin), ptr(valid), ptr(rev_min_dist), ptr(rev_argmin), ptr(mutual), ptr(ws), wsb,
+                                       stream_ptr(dev)), "oryon_match_mutual_f32")
+    return min_dist, argmin, valid, rev_min_dist, rev_argmin, mutual
+
+
+@_on_tensor_device
 def match_screened(a_hat, q_hat, a16, q16, n_a, n_q, threshold: float):
     """fp16-screened, fp32-exact matcher (K1s).  Same outputs as `match` on every row that can be valid."""
     dev = _lib.require_gpu(a_hat.device)

@@ -29,7 +29,8 @@ def torch_sample_select(t: Tensor, n: int) -> Tensor:
 
 
 def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor, threshold: float,
-                    subsample_source: Optional[int] = None, half_descriptors: bool = False, mode: str = "exact"):
+                    subsample_source: Optional[int] = None, half_descriptors: bool = False, mode: str = "exact",
+                    mutual: bool = False):
     """Deterministic half of the matcher (utils/pcd.py:184-205) on the GPU.
 
     Returns dict(roi1 [N1,2] i64 (y,x), roi2 [N2,2] i64, min_dist [N1] f32, argmin [N1] i64, valid [N1] bool).
@@ -41,9 +42,15 @@ def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor
     "screened6" = the step engine's default route (K0 oryon_gather_mx6 -> oryon_match_corrs_mx6: MX-fp6 screen, lazy tail, K1x3 second
     level, device-RNG sampler): `valid` is exact on every row; `argmin` is exact on the SAMPLED rows only and `min_dist` only where the
     route needed the fp32 comparison (include/oryon_hip.h) - the dict additionally carries `corrs` [n_sel,4] i64 (y1,x1,y2,x2), the
-    sampled correspondences (seed 1, max_corrs 500), and `status`."""
+    sampled correspondences (seed 1, max_corrs 500), and `status`.
+    mutual=True: both directions from one fused exact scan (K1m, csrc/match_mutual.hip), whatever `mode` says - the screened modes
+    carry no reverse screen.  The dict additionally carries `mutual` [N1] bool (valid & rev_argmin[argmin] == row), `rev_argmin` [N2]
+    i64 and `rev_min_dist` [N2] f32: the nearest ANCHOR row of every query row, over the N1 rows matched - after subsample_source that
+    is the subsample, not the whole mask.  With mutual=False the dict, its bytes and the RNG draws are what they always were."""
     if mode not in ("exact", "screened16", "screened8", "screened6"):
         raise ValueError(f"match_presample: unknown mode {mode!r}")
+    if mutual:
+        mode = "exact"
     if mode != "exact" and not (0.0 < threshold <= 0.5):
         mode = "exact"                       # the screens' validity cut needs 1 - 2*threshold >= 0
     dev = require_gpu(feats1.device)
@@ -74,6 +81,9 @@ def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor
                    valid=torch.zeros(n1, dtype=torch.bool, device=dev))
         if mode == "screened6":
             out.update(corrs=torch.zeros((0, 4), dtype=torch.int64, device=dev), status=torch.tensor(1, device=dev))
+        if mutual:
+            out.update(mutual=torch.zeros(n1, dtype=torch.bool, device=dev), rev_argmin=torch.zeros(n2, dtype=torch.int64, device=dev),
+                       rev_min_dist=torch.full((n2,), float("inf"), device=dev))
         return out
     C = f1.shape[1]
     cap1, cap2 = ops.round_up(n1, ops.ROW_PAD), ops.round_up(n2, ops.ROW_PAD)
@@ -96,6 +106,11 @@ def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor
         a_hat, a16 = ops.gather_normalise(f1, roi1_lin, c1, cap1, c_pad=c_pad, want_f16=True)
         q_hat, q16 = ops.gather_normalise(f2, roi2_lin, c2, cap2, c_pad=c_pad, want_f16=True)
         min_dist, argmin, valid = ops.match_screened(a_hat, q_hat, a16, q16, c1, c2, threshold)
+    elif mutual:
+        a_hat = ops.gather_normalise(f1, roi1_lin, c1, cap1)
+        q_hat = ops.gather_normalise(f2, roi2_lin, c2, cap2)
+        min_dist, argmin, valid, rev_min_dist, rev_argmin, mut = ops.match_mutual(a_hat, q_hat, c1, c2, threshold)
+        out.update(mutual=mut[0, :n1].bool(), rev_argmin=rev_argmin[0, :n2].to(torch.int64), rev_min_dist=rev_min_dist[0, :n2])
     else:
         a_hat = ops.gather_normalise(f1, roi1_lin, c1, cap1)
         q_hat = ops.gather_normalise(f2, roi2_lin, c2, cap2)
@@ -105,15 +120,19 @@ def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor
 
 
 def nn_correspondences(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor, threshold: float, max_corrs: int,
-                       subsample_source: Optional[int], corrs_device: str = "cuda") -> Optional[Tensor]:
+                       subsample_source: Optional[int], corrs_device: str = "cuda", mutual: bool = False) -> Optional[Tensor]:
     """Matches between two [D,H,W] feature maps restricted to mask==1; int64 [max_corrs,4] rows
     (y1,x1,y2,x2) on feats1.device, or None when at most one anchor pixel finds a match under the
     threshold (utils/pcd.py:177-216).  The contraction always runs on the GPU and the two
     host RNG draws are always made on the CPU generator.  corrs_device='cuda' selects the reference's fp16-descriptor
-    branch (descriptors rounded to float16, utils/pcd.py:195-197); anything else its fp32 branch."""
+    branch (descriptors rounded to float16, utils/pcd.py:195-197); anything else its fp32 branch.
+    mutual=True (no counterpart in the reference): the rows kept before the second draw are the MUTUAL nearest neighbours (valid, and
+    the matched query pixel's nearest anchor - among the anchors that survived subsample_source - is this one); None when at most one
+    row is mutual.  The same two host draws are made in the same order."""
     orig_device = feats1.device
-    pre = match_presample(feats1, feats2, mask1, mask2, threshold, subsample_source, half_descriptors=(corrs_device == "cuda"))
-    valid_corr = torch.nonzero(pre["valid"]).squeeze(1)
+    pre = match_presample(feats1, feats2, mask1, mask2, threshold, subsample_source, half_descriptors=(corrs_device == "cuda"),
+                          mutual=mutual)
+    valid_corr = torch.nonzero(pre["mutual"] if mutual else pre["valid"]).squeeze(1)
     if valid_corr.shape[0] > 1:
         roi2 = pre["roi2"][pre["argmin"]]
         final_corrs = torch.cat((pre["roi1"][valid_corr], roi2[valid_corr]), dim=1)

@@ -22,6 +22,13 @@ which every Pipeline that run_test.py builds then applies: every solved pose is 
 query's (utils/geo6d.py:157-208 `icp`, csrc/icp.hip), in the per-sample loop and behind the batched engine alike; `icp_plane` refines it
 by point-to-plane ICP of that cloud onto the query's depth map instead (projective association, csrc/icp_plane.hip).
 
+    python run_pose.py --solver ransac --mutual --pairs 8 --batch 4
+
+`--mutual` (test.mutual; off by default) becomes the process-wide default (oryon_amd.engine.set_default_mutual), so every
+`default_args()` and `MatchPoseConfig()` that run_test.py builds selects it: the matcher runs in both directions in one fused scan
+(csrc/match_mutual.hip) and only the mutual nearest neighbours reach the solver.  run_test.py never sees the flag; the summary this
+driver returns - and prints as its last JSON line - carries `"mutual": true`.
+
     python run_pose.py --vsd --data-root /data --dataset nocs --ckpt ... --out preds/nocs.csv
 
 `--vsd` (real-asset mode only) also reports VSD and AR = (VSD + MSSD + MSPD) / 3, the reference's headline column
@@ -49,19 +56,29 @@ def take_refine(argv=None):
     return a.refine, rest
 
 
+class Parsed(tuple):
+    """(solver, the arguments left for run_test.py), with `.mutual`: whether `--mutual` was given (taken out, like `--refine`)."""
+    def __new__(cls, solver, rest, mutual):
+        self = super().__new__(cls, (solver, rest))
+        self.mutual = mutual
+        return self
+
+
 def parse(argv=None):
-    """-> (solver, the arguments left for run_test.py).  `--refine` is checked and taken out as well (take_refine returns it)."""
+    """-> Parsed: (solver, the arguments left for run_test.py) + .mutual.  `--refine` is checked and taken out as well (take_refine
+    returns it), and so is `--mutual` (test.mutual: keep only the mutual nearest neighbours, csrc/match_mutual.hip)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
     ap.add_argument("--solver", choices=["pointdsc", "ransac", "spectral"], default="pointdsc",
                     help="test.solver: PointDSC registration, best_fit_transform_with_RANSAC, or the spectral solver (the last two need no "
                          "PointDSC weights)")
     ap.add_argument("--refine", choices=REFINE_CHOICES, default="none", help="test.refine: ICP refinement of every solved pose (see above)")
+    ap.add_argument("--mutual", action="store_true", help="test.mutual: match in both directions, keep the mutual nearest neighbours")
     ap.add_argument("-h", "--help", action="store_true")
     a, rest = ap.parse_known_args(argv)
     if a.help:
         ap.print_help()
         rest = ["--help"] + rest               # then run_test.py's own help
-    return a.solver, rest
+    return Parsed(a.solver, rest, a.mutual)
 
 
 def take_vsd(argv):
@@ -90,15 +107,22 @@ def add_vsd(summary: dict, rest) -> dict:
 def main(argv=None):
     vsd, argv = take_vsd(argv)
     refine, _ = take_refine(argv)
-    solver, rest = parse(argv)
+    parsed = parse(argv)
+    solver, rest = parsed
     if vsd and "--data-root" not in rest and not any(r.startswith("--data-root=") for r in rest):
         raise SystemExit("run_pose.py --vsd needs real-asset mode (--data-root ...): the synthetic pairs have no object mesh")
     from oryon_amd.engine import set_default_solver
     set_default_solver(solver)
     from oryon_amd.pipeline import set_default_refine
     set_default_refine(refine)
+    from oryon_amd.engine import set_default_mutual
+    set_default_mutual(parsed.mutual)
     import run_test
     summary = run_test.main(rest)
+    if parsed.mutual:
+        summary = dict(summary, mutual=True)
+        if not (vsd and summary.get("pairs")):
+            print(json.dumps(summary))               # run_test.py's line again, with the flag recorded
     return add_vsd(summary, rest) if vsd and summary.get("pairs") else summary
 
 
