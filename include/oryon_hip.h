@@ -200,6 +200,30 @@ int oryon_match_mutual_f32(const float *a_hat, const float *q_hat, int B, int C,
                            float *rev_min_dist, int32_t *rev_argmin, uint8_t *mutual,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* K1r the ratio test with an exclusion disc: a second all-pairs scan with a per-anchor spatial mask (csrc/match_second.hip).
+ *     dist(i, j) = fma(-0.5, dot(a_i, q_j), 0.5), the dot product K1's k-ordered fmaf chain: the bits of oryon_match_f32.
+ *     roi_q[p roi_stride_q + j] is the linear pixel index of query row j in a map W_q wide (as oryon_select_corrs reads it);
+ *     (y*, x*) is the pixel of roi_q[argmin[i]], (y_j, x_j) that of roi_q[j].
+ *     Candidates of row i: all j < n_q with (y_j - y*)^2 + (x_j - x*)^2 >= radius^2 (integers; the rule of the training loss, which
+ *     excludes pixel distance < neg_kernel).  radius = 1 excludes exactly the best row's own pixel (and rows sharing it).
+ *     second_dist / second_argmin [B,cap_a]: the minimum of dist(i, j) over the candidates, first query index on ties; INFINITY and
+ *     index 0 when there is no candidate (n_q == 0 included).  Written for every row i < n_a whatever the gate says; rows >= n_a are
+ *     not written, rows >= n_a / >= n_q of the INPUTS are never used (masked by index).
+ *     keep [B,cap_a] uint8 = gate[i] && min_dist[i] <= __fmul_rn(ratio, second_dist[i]).  gate [B,cap_a] uint8 is K1's valid or
+ *     K1m's mutual; NULL counts as all ones.  second_dist = INFINITY keeps the row (no competitor).  The candidates are a subset
+ *     of the rows K1 minimised over, with the same bits, so second_dist >= min_dist and ratio = 1 returns keep == gate.
+ *     min_dist / argmin are the outputs of oryon_match_f32 or oryon_match_mutual_f32 on the same operands.
+ * 1 <= radius <= 1024, 0 < ratio <= 1, 1 <= W_q <= 65535 and every pixel's row index <= 65535 (a pixel packs into y << 16 | x).
+ * C a multiple of 32, caps multiples of ORYON_MATCH_TILE (cap_q of 256 when C == 32), B <= 65535; B == 0 returns ORYON_OK.
+ * workspace: oryon_match_second_workspace_bytes(B, cap_a): K1's query-split buffers. */
+size_t oryon_match_second_workspace_bytes(int B, int cap_a);
+int oryon_match_second_f32(const float *a_hat, const float *q_hat, int B, int C, int cap_a, int cap_q,
+                           const int32_t *n_a, const int32_t *n_q,
+                           const int32_t *roi_q, int roi_stride_q, int W_q, int radius,
+                           const float *min_dist, const int32_t *argmin, const uint8_t *gate, float ratio,
+                           float *second_dist, int32_t *second_argmin, uint8_t *keep,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* K1s same contract as oryon_match_f32 for every anchor row that can reach the threshold, computed as an fp16-MFMA
  *     screening pass (v_mfma_f32_32x32x16_f16 on the IEEE-half copies written by oryon_gather_normalise_f32) followed by
  *     an exact fp32 re-scoring of the surviving candidates with K1's canonical fmaf chain.  A proven error bound on the

@@ -78,6 +78,9 @@ _PROTOS = {
     "oryon_match_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "oryon_match_mutual_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "oryon_match_mutual_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_float, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "oryon_match_second_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "oryon_match_second_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_float, _P, _P, _P,
+                                       _P, c_size_t, _P]),
     "oryon_match_screened_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "oryon_gather_normalise_q8": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "oryon_gather_q8": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),

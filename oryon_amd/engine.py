@@ -56,6 +56,28 @@ def default_mutual() -> bool:
     return _default_mutual
 
 
+_default_ratio = (0.0, 5)
+
+
+def set_default_ratio(ratio: float, radius: int = 5) -> None:
+    """The process-wide default of test.ratio / test.ratio_radius: what `MatchPoseConfig()` and `pipeline.default_args()` choose when
+    the caller does not say ((0.0, 5) unless set: off).  A driver sets it once, before it builds pipelines (run_pose.py --ratio does)."""
+    global _default_ratio
+    _check_ratio_range(ratio, radius)
+    _default_ratio = (float(ratio), int(radius))
+
+
+def default_ratio() -> Tuple[float, int]:
+    return _default_ratio
+
+
+def _check_ratio_range(ratio, radius) -> None:
+    if not (0.0 <= float(ratio) <= 1.0):                 # a NaN fails too
+        raise ValueError(f"ratio {ratio!r} is outside [0, 1] (0 = off)")
+    if not (1 <= int(radius) <= 1024) or int(radius) != radius:
+        raise ValueError(f"ratio_radius {radius!r} is outside [1, 1024]")
+
+
 @dataclass
 class MatchPoseConfig:
     """Flag names follow configs/config.yaml of the reference (test.* section)."""
@@ -100,15 +122,30 @@ class MatchPoseConfig:
     # screened routes carry no reverse screen, the native C step engine does not know it); half_descriptors composes (the rounding
     # happens before the gather), sample_first does not (a ValueError).
     mutual: bool = field(default_factory=default_mutual)
+    # test.ratio / test.ratio_radius: the ratio test with an exclusion disc (csrc/match_second.hip).  ratio > 0 keeps a row only when
+    # min_dist <= ratio * the best distance to a query pixel at least ratio_radius pixels away from the matched one (radius 1: Lowe's
+    # test; 5 = loss.neg_kernel_size, the margin the descriptors were trained to have).  A second exact scan behind the first (or behind
+    # the mutual one, whose rows it then gates); the sampler draws from the kept rows, n_valid counts them, a pair with at most one ends
+    # ORYON_PAIR_NO_CORR.  Per-call schedule, exact gather, like mutual; sample_first does not combine (a ValueError).  0 = off.
+    ratio: float = field(default_factory=lambda: default_ratio()[0])
+    ratio_radius: int = field(default_factory=lambda: default_ratio()[1])
 
     def __post_init__(self):
         _check_mutual(self)
+        _check_ratio(self)
 
 
 def _check_mutual(cfg: "MatchPoseConfig") -> None:
     if cfg.mutual and cfg.sample_first and cfg.sample_first > 0:
         raise ValueError("mutual=True does not combine with sample_first > 0: the reverse minimum of a first-stage subset of the anchors "
                          "is not the reverse minimum of the pair")
+
+
+def _check_ratio(cfg: "MatchPoseConfig") -> None:
+    _check_ratio_range(cfg.ratio, cfg.ratio_radius)
+    if cfg.ratio > 0 and cfg.sample_first and cfg.sample_first > 0:
+        raise ValueError("ratio > 0 does not combine with sample_first > 0: the second scan behind a first-stage subset of the anchors "
+                         "is not built")
 
 
 def _check_solver(cfg: "MatchPoseConfig", solver) -> bool:
@@ -556,11 +593,13 @@ class MatchPoseEngine:
         dev = _lib.require_gpu(feat_a.device)
         cfg = self.cfg
         _check_mutual(cfg)
+        _check_ratio(cfg)
         B, C, FH, FW = feat_a.shape
         main = torch.cuda.current_stream(dev)
         # the screens' validity cut is 1 - 2*dist_th: thresholds above 0.5 (or non-positive) take the exact scan; so does mutual (no
         # reverse screen exists)
-        screened = cfg.match_mode in ("screened", "screened16") and 64 < C <= 512 and 0.0 < cfg.dist_th <= 0.5 and not cfg.mutual
+        filtered = cfg.mutual or cfg.ratio > 0         # ... and so does the ratio test (no second-minimum screen exists)
+        screened = cfg.match_mode in ("screened", "screened16") and 64 < C <= 512 and 0.0 < cfg.dist_th <= 0.5 and not filtered
         use_i8 = screened and cfg.match_mode == "screened" and C > 128
         if use_i8:
             if self._i8_pending is not None and self._i8_pending[1].query():
@@ -576,7 +615,7 @@ class MatchPoseEngine:
         # the native step engine serves every width up to 512 on the screened route (narrow maps zero-padded to 256 channels by K0);
         # the per-call schedule below keeps its own choice per width (exact scan for C <= 64, fp16 screen for C <= 128)
         native_ok = cfg.match_mode == "screened" and C <= 512 and 0.0 < cfg.dist_th <= 0.5 and (use_i8 or C <= 128)
-        if native_ok and self.native and cfg.solver != "spectral" and not cfg.mutual:   # the C step engine knows neither spectral nor mutual
+        if native_ok and self.native and cfg.solver != "spectral" and not filtered:   # the C step engine knows no spectral, mutual or ratio
             return self._run_native(feat_a, feat_q, mask_a, mask_q, depth_a, depth_q, cam_a, cam_q, pair_key, keep, inputs_event,
                                     inputs_resident, dev)
         if pair_key is None:
@@ -606,6 +645,7 @@ class MatchPoseEngine:
             cap_a = ops.round_up(FH * FW, ops.ROW_PAD)
         cap_q = ops.round_up(FH * FW, ops.ROW_PAD)
         a16 = q16 = a8 = q8 = a_sc = q_sc = q_eps = q_norm = q_hat = roi_a1 = n_a1 = mutual = rev_argmin = rev_min_dist = None
+        second_dist = second_argmin = keep_rows = None
         stage1 = use_i8 and cfg.sample_first > 0 and not keep
         if use_i8:
             # K0v3: anchors -> fp32 + int8 rows, queries -> int8 rows + row norms only (the re-scoring pass reads its few candidates
@@ -670,8 +710,14 @@ class MatchPoseEngine:
                 min_dist, argmin, valid = ops.match_screened(a_hat, q_hat, a16, q16, n_a, n_q, cfg.dist_th)
             else:
                 min_dist, argmin, valid = ops.match(a_hat, q_hat, n_a, n_q, cfg.dist_th)
-            # mutual: the sampler draws from the mutual rows, n_valid counts them, <= 1 of them is ORYON_PAIR_NO_CORR
-            corrs, n_valid, n_sel, status = ops.select_corrs(roi_a, roi_q, n_a, n_q, argmin, mutual if cfg.mutual else valid, FW,
+            # mutual: the sampler draws from the mutual rows, n_valid counts them, <= 1 of them is ORYON_PAIR_NO_CORR; ratio: the same
+            # with the rows the ratio test keeps of them
+            gate = mutual if cfg.mutual else valid
+            if cfg.ratio > 0:
+                second_dist, second_argmin, keep_rows = ops.match_second(a_hat, q_hat, n_a, n_q, roi_q, FW, cfg.ratio_radius, min_dist,
+                                                                         argmin, gate, cfg.ratio)
+                gate = keep_rows
+            corrs, n_valid, n_sel, status = ops.select_corrs(roi_a, roi_q, n_a, n_q, argmin, gate, FW,
                                                              cfg.n_corrs, cfg.seed, pair_key, corr_rows=self.n_cap)
         cam_a = cam_a.reshape(B, 9).to(torch.float32).contiguous()
         cam_q = cam_q.reshape(B, 9).to(torch.float32).contiguous()
@@ -708,4 +754,6 @@ class MatchPoseEngine:
                        pcd_a=pcd_a, pcd_q=pcd_q)
             if cfg.mutual:
                 out.update(mutual=mutual, rev_argmin=rev_argmin, rev_min_dist=rev_min_dist)
+            if cfg.ratio > 0:
+                out.update(second_dist=second_dist, second_argmin=second_argmin, keep=keep_rows)
         return out

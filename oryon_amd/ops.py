@@ -399,6 +399,31 @@ def match_mutual(a_hat: torch.Tensor, q_hat: torch.Tensor, n_a: torch.Tensor, n_
 
 
 @_on_tensor_device
+def match_second(a_hat: torch.Tensor, q_hat: torch.Tensor, n_a: torch.Tensor, n_q: torch.Tensor, roi_q: torch.Tensor, W_q: int, radius: int,
+                 min_dist: torch.Tensor, argmin: torch.Tensor, gate: Optional[torch.Tensor], ratio: float):
+    """The ratio test with an exclusion disc (K1r): -> (second_dist [B,cap_a] f32, second_argmin [B,cap_a] i32, keep [B,cap_a] u8).
+    second_* is the best query row at least `radius` pixels (integer L2, in a map W_q wide; roi_q [B,stride] i32 holds the query rows'
+    linear pixel indices) away from the pixel of argmin's row; keep = gate & (min_dist <= ratio * second_dist), the product rounded
+    to float32.  min_dist / argmin: `match` or `match_mutual` on the same operands; gate: their valid or mutual, None for all ones."""
+    dev = _lib.require_gpu(a_hat.device)
+    B, cap_a, Cp = a_hat.shape
+    cap_q = q_hat.shape[1]
+    assert q_hat.shape[0] == B and q_hat.shape[2] == Cp
+    assert roi_q.dtype == torch.int32 and roi_q.dim() == 2 and roi_q.shape[0] == B
+    assert min_dist.dtype == torch.float32 and argmin.dtype == torch.int32 and min_dist.shape == (B, cap_a) and argmin.shape == (B, cap_a)
+    assert gate is None or (gate.dtype == torch.uint8 and gate.shape == (B, cap_a))
+    second_dist = torch.empty((B, cap_a), dtype=torch.float32, device=dev)
+    second_argmin = torch.empty((B, cap_a), dtype=torch.int32, device=dev)
+    keep = torch.empty((B, cap_a), dtype=torch.uint8, device=dev)
+    wsb = lib().oryon_match_second_workspace_bytes(B, cap_a)
+    ws = _lib.workspace(dev, wsb)
+    check(lib().oryon_match_second_f32(ptr(a_hat), ptr(q_hat), B, Cp, cap_a, cap_q, ptr(n_a), ptr(n_q), ptr(roi_q), roi_q.shape[1], int(W_q),
+                                       int(radius), ptr(min_dist), ptr(argmin), ptr(gate), float(ratio), ptr(second_dist),
+                                       ptr(second_argmin), ptr(keep), ptr(ws), wsb, stream_ptr(dev)), "oryon_match_second_f32")
+    return second_dist, second_argmin, keep
+
+
+@_on_tensor_device
 def match_screened(a_hat, q_hat, a16, q16, n_a, n_q, threshold: float):
     """fp16-screened, fp32-exact matcher (K1s).  Same outputs as `match` on every row that can be valid."""
     dev = _lib.require_gpu(a_hat.device)

@@ -30,7 +30,7 @@ def torch_sample_select(t: Tensor, n: int) -> Tensor:
 
 def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor, threshold: float,
                     subsample_source: Optional[int] = None, half_descriptors: bool = False, mode: str = "exact",
-                    mutual: bool = False):
+                    mutual: bool = False, ratio: float = 0.0, ratio_radius: int = 5):
     """Deterministic half of the matcher (utils/pcd.py:184-205) on the GPU.
 
     Returns dict(roi1 [N1,2] i64 (y,x), roi2 [N2,2] i64, min_dist [N1] f32, argmin [N1] i64, valid [N1] bool).
@@ -46,10 +46,16 @@ def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor
     mutual=True: both directions from one fused exact scan (K1m, csrc/match_mutual.hip), whatever `mode` says - the screened modes
     carry no reverse screen.  The dict additionally carries `mutual` [N1] bool (valid & rev_argmin[argmin] == row), `rev_argmin` [N2]
     i64 and `rev_min_dist` [N2] f32: the nearest ANCHOR row of every query row, over the N1 rows matched - after subsample_source that
-    is the subsample, not the whole mask.  With mutual=False the dict, its bytes and the RNG draws are what they always were."""
+    is the subsample, not the whole mask.  With mutual=False the dict, its bytes and the RNG draws are what they always were.
+    ratio > 0: the ratio test with an exclusion disc (K1r, csrc/match_second.hip) behind the exact scan, whatever `mode` says - the
+    screened modes carry no second-minimum screen.  The dict additionally carries `second_dist` [N1] f32 and `second_argmin` [N1] i64,
+    the best query row at least ratio_radius pixels away from the matched pixel (inf / 0 when there is none), and `keep` [N1] bool =
+    gate & (min_dist <= ratio * second_dist), the gate being `mutual` when mutual=True and `valid` otherwise.  ratio = 0: off."""
     if mode not in ("exact", "screened16", "screened8", "screened6"):
         raise ValueError(f"match_presample: unknown mode {mode!r}")
-    if mutual:
+    if not (0.0 <= ratio <= 1.0) or not (1 <= ratio_radius <= 1024):
+        raise ValueError(f"match_presample: ratio {ratio!r} outside [0, 1] or ratio_radius {ratio_radius!r} outside [1, 1024]")
+    if mutual or ratio > 0:
         mode = "exact"
     if mode != "exact" and not (0.0 < threshold <= 0.5):
         mode = "exact"                       # the screens' validity cut needs 1 - 2*threshold >= 0
@@ -84,6 +90,9 @@ def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor
         if mutual:
             out.update(mutual=torch.zeros(n1, dtype=torch.bool, device=dev), rev_argmin=torch.zeros(n2, dtype=torch.int64, device=dev),
                        rev_min_dist=torch.full((n2,), float("inf"), device=dev))
+        if ratio > 0:
+            out.update(second_dist=torch.full((n1,), float("inf"), device=dev), second_argmin=torch.zeros(n1, dtype=torch.int64, device=dev),
+                       keep=torch.zeros(n1, dtype=torch.bool, device=dev))
         return out
     C = f1.shape[1]
     cap1, cap2 = ops.round_up(n1, ops.ROW_PAD), ops.round_up(n2, ops.ROW_PAD)
@@ -115,6 +124,10 @@ def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor
         a_hat = ops.gather_normalise(f1, roi1_lin, c1, cap1)
         q_hat = ops.gather_normalise(f2, roi2_lin, c2, cap2)
         min_dist, argmin, valid = ops.match(a_hat, q_hat, c1, c2, threshold)
+    if ratio > 0:
+        second_dist, second_argmin, keep = ops.match_second(a_hat, q_hat, c1, c2, roi2_lin.contiguous(), W2, ratio_radius, min_dist, argmin,
+                                                            mut if mutual else valid, ratio)
+        out.update(second_dist=second_dist[0, :n1], second_argmin=second_argmin[0, :n1].to(torch.int64), keep=keep[0, :n1].bool())
     out.update(min_dist=min_dist[0, :n1], argmin=argmin[0, :n1].to(torch.int64), valid=valid[0, :n1].bool())
     return out
 
@@ -129,10 +142,21 @@ def nn_correspondences(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Ten
     mutual=True (no counterpart in the reference): the rows kept before the second draw are the MUTUAL nearest neighbours (valid, and
     the matched query pixel's nearest anchor - among the anchors that survived subsample_source - is this one); None when at most one
     row is mutual.  The same two host draws are made in the same order."""
+    return nn_correspondences_filtered(feats1, feats2, mask1, mask2, threshold, max_corrs, subsample_source, corrs_device, mutual=mutual,
+                                       ratio=0.0)
+
+
+def nn_correspondences_filtered(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor, threshold: float, max_corrs: int,
+                                subsample_source: Optional[int], corrs_device: str = "cuda", mutual: bool = False, ratio: float = 0.0,
+                                ratio_radius: int = 5) -> Optional[Tensor]:
+    """`nn_correspondences` with the matcher's filters (no counterpart in the reference).  ratio > 0: the rows kept before the second
+    draw are those that pass the ratio test with an exclusion disc of ratio_radius pixels (match_presample's `keep`: valid - or
+    mutual, with mutual=True - and min_dist <= ratio * the best distance outside the disc); None when at most one row is kept.
+    The same two host draws are made in the same order; with ratio = 0 this IS nn_correspondences."""
     orig_device = feats1.device
     pre = match_presample(feats1, feats2, mask1, mask2, threshold, subsample_source, half_descriptors=(corrs_device == "cuda"),
-                          mutual=mutual)
-    valid_corr = torch.nonzero(pre["mutual"] if mutual else pre["valid"]).squeeze(1)
+                          mutual=mutual, ratio=ratio, ratio_radius=ratio_radius)
+    valid_corr = torch.nonzero(pre["keep"] if ratio > 0 else pre["mutual"] if mutual else pre["valid"]).squeeze(1)
     if valid_corr.shape[0] > 1:
         roi2 = pre["roi2"][pre["argmin"]]
         final_corrs = torch.cat((pre["roi1"][valid_corr], roi2[valid_corr]), dim=1)

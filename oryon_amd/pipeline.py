@@ -40,9 +40,9 @@ import torch
 from torch import Tensor
 
 from . import _lib, ops
-from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK, PAIR_OK, SOLVERS, default_mutual, default_solver
+from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK, PAIR_OK, SOLVERS, default_mutual, default_ratio, default_solver
 from .geo6d import best_fit_transform_with_RANSAC, spectral_pose
-from .pcd import nn_correspondences
+from .pcd import nn_correspondences, nn_correspondences_filtered
 from .pointdsc import PointDSC, get_pointdsc_pose
 
 
@@ -84,7 +84,11 @@ def default_args(**overrides) -> SimpleNamespace:
                              # test.mutual (csrc/match_mutual.hip; the reference matches in one direction only): keep only the
                              # mutual nearest neighbours (False unless a driver called engine.set_default_mutual).  Read with
                              # getattr(..., False): arg objects without it keep working
-                             mutual=default_mutual()),
+                             mutual=default_mutual(),
+                             # test.ratio / test.ratio_radius (csrc/match_second.hip; no counterpart in the reference): the ratio
+                             # test with an exclusion disc, 0 = off ((0.0, 5) unless a driver called engine.set_default_ratio).  Read
+                             # with getattr(..., 0.0 / 5)
+                             ratio=default_ratio()[0], ratio_radius=default_ratio()[1]),
         loss=SimpleNamespace(hard_negatives=True, pos_margin=0.2, neg_margin=0.9, neg_kernel_size=5, mask_type="dice",
                              w={"mask": 1.0, "pos": 0.5, "neg": 0.5}),
         optimization=SimpleNamespace(optim_type="Adam", scheduler_type="cosine", lr=0.001, momentum=0.0, w_decay=0.0005, gamma=0.1),
@@ -187,8 +191,15 @@ class Pipeline:
         else:
             mask_ai, mask_qi = results["mask_a"][idx], results["mask_q"][idx]
         featmap_ai, featmap_qi = net_output["featmap_a"][idx], net_output["featmap_q"][idx]
-        pred_corrs = nn_correspondences(featmap_ai, featmap_qi, mask_ai, mask_qi, self.args.test.dist_th, self.args.test.n_corrs,
-                                        self.args.test.src_sampling, self.corrs_device, mutual=bool(getattr(self.args.test, "mutual", False)))
+        ratio = float(getattr(self.args.test, "ratio", 0.0))
+        if ratio > 0:
+            pred_corrs = nn_correspondences_filtered(featmap_ai, featmap_qi, mask_ai, mask_qi, self.args.test.dist_th, self.args.test.n_corrs,
+                                                     self.args.test.src_sampling, self.corrs_device,
+                                                     mutual=bool(getattr(self.args.test, "mutual", False)), ratio=ratio,
+                                                     ratio_radius=int(getattr(self.args.test, "ratio_radius", 5)))
+        else:
+            pred_corrs = nn_correspondences(featmap_ai, featmap_qi, mask_ai, mask_qi, self.args.test.dist_th, self.args.test.n_corrs,
+                                            self.args.test.src_sampling, self.corrs_device, mutual=bool(getattr(self.args.test, "mutual", False)))
         if pred_corrs is not None:
             corr_ai, corr_qi = pred_corrs[:, :2], pred_corrs[:, 2:]
             pos_a = featmap_ai[:, corr_ai[:, 0], corr_ai[:, 1]].transpose(1, 0)
@@ -425,6 +436,7 @@ class Pipeline:
                 dist_th=self.args.test.dist_th, n_corrs=self.args.test.n_corrs, src_sampling=self.args.test.src_sampling,
                 seed=self.args.seed if self.args.seed is not None else 1, solver=self.solver,
                 mutual=bool(getattr(self.args.test, "mutual", False)),
+                ratio=float(getattr(self.args.test, "ratio", 0.0)), ratio_radius=int(getattr(self.args.test, "ratio_radius", 5)),
                 **{"spectral_" + f: v for f, v in self._spectral_cfg().items()}))
 
         def stack(x):

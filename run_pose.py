@@ -29,6 +29,13 @@ by point-to-plane ICP of that cloud onto the query's depth map instead (projecti
 (csrc/match_mutual.hip) and only the mutual nearest neighbours reach the solver.  run_test.py never sees the flag; the summary this
 driver returns - and prints as its last JSON line - carries `"mutual": true`.
 
+    python run_pose.py --solver ransac --ratio 0.8 --ratio-radius 5 --pairs 8 --batch 4
+
+`--ratio R [--ratio-radius N]` (test.ratio / test.ratio_radius; off by default, N = 5) becomes the process-wide default
+(oryon_amd.engine.set_default_ratio) in the same way: behind the exact scan a second one (csrc/match_second.hip) finds every anchor's
+best match at least N pixels away from its nearest one, and only rows with min_dist <= R * that distance reach the solver (N = 1 is
+Lowe's ratio test; with `--mutual` the mutual rows are filtered).  The summary carries `"ratio": R, "ratio_radius": N`.
+
     python run_pose.py --vsd --data-root /data --dataset nocs --ckpt ... --out preds/nocs.csv
 
 `--vsd` (real-asset mode only) also reports VSD and AR = (VSD + MSSD + MSPD) / 3, the reference's headline column
@@ -57,28 +64,35 @@ def take_refine(argv=None):
 
 
 class Parsed(tuple):
-    """(solver, the arguments left for run_test.py), with `.mutual`: whether `--mutual` was given (taken out, like `--refine`)."""
-    def __new__(cls, solver, rest, mutual):
+    """(solver, the arguments left for run_test.py), with `.mutual`: whether `--mutual` was given (taken out, like `--refine`), and
+    `.ratio` / `.ratio_radius`: what `--ratio` / `--ratio-radius` gave (0.0 / 5 when absent)."""
+    def __new__(cls, solver, rest, mutual, ratio=0.0, ratio_radius=5):
         self = super().__new__(cls, (solver, rest))
         self.mutual = mutual
+        self.ratio = ratio
+        self.ratio_radius = ratio_radius
         return self
 
 
 def parse(argv=None):
     """-> Parsed: (solver, the arguments left for run_test.py) + .mutual.  `--refine` is checked and taken out as well (take_refine
-    returns it), and so is `--mutual` (test.mutual: keep only the mutual nearest neighbours, csrc/match_mutual.hip)."""
+    returns it), and so are `--mutual` (test.mutual: keep only the mutual nearest neighbours, csrc/match_mutual.hip) and `--ratio` /
+    `--ratio-radius` (test.ratio, test.ratio_radius: the ratio test with an exclusion disc, csrc/match_second.hip)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
     ap.add_argument("--solver", choices=["pointdsc", "ransac", "spectral"], default="pointdsc",
                     help="test.solver: PointDSC registration, best_fit_transform_with_RANSAC, or the spectral solver (the last two need no "
                          "PointDSC weights)")
     ap.add_argument("--refine", choices=REFINE_CHOICES, default="none", help="test.refine: ICP refinement of every solved pose (see above)")
     ap.add_argument("--mutual", action="store_true", help="test.mutual: match in both directions, keep the mutual nearest neighbours")
+    ap.add_argument("--ratio", type=float, default=0.0, help="test.ratio: keep a match only when min_dist <= RATIO * the best distance "
+                                                             "outside the exclusion disc (0 = off)")
+    ap.add_argument("--ratio-radius", type=int, default=5, help="test.ratio_radius: radius of that disc in pixels (1 = Lowe's ratio test)")
     ap.add_argument("-h", "--help", action="store_true")
     a, rest = ap.parse_known_args(argv)
     if a.help:
         ap.print_help()
         rest = ["--help"] + rest               # then run_test.py's own help
-    return Parsed(a.solver, rest, a.mutual)
+    return Parsed(a.solver, rest, a.mutual, a.ratio, a.ratio_radius)
 
 
 def take_vsd(argv):
@@ -117,10 +131,15 @@ def main(argv=None):
     set_default_refine(refine)
     from oryon_amd.engine import set_default_mutual
     set_default_mutual(parsed.mutual)
+    from oryon_amd.engine import set_default_ratio
+    set_default_ratio(parsed.ratio, parsed.ratio_radius)
     import run_test
     summary = run_test.main(rest)
-    if parsed.mutual:
-        summary = dict(summary, mutual=True)
+    if parsed.mutual or parsed.ratio > 0:
+        if parsed.mutual:
+            summary = dict(summary, mutual=True)
+        if parsed.ratio > 0:
+            summary = dict(summary, ratio=parsed.ratio, ratio_radius=parsed.ratio_radius)
         if not (vsd and summary.get("pairs")):
             print(json.dumps(summary))               # run_test.py's line again, with the flag recorded
     return add_vsd(summary, rest) if vsd and summary.get("pairs") else summary
