@@ -980,6 +980,48 @@ int oryon_icp_plane_refine(const double *src, const int32_t *n_src, int cap_src,
                            double normal_jump, const int32_t *status_in, void *workspace, size_t workspace_bytes, float *T, double *T64,
                            int32_t *iters, double *mean_err, int32_t *n_kept, int32_t *idx, int32_t *status_out, void *stream);
 
+/* g4  Depth-consistency verification of K candidate poses per pair (csrc/pose_verify.hip; test.verify): every source point, moved by a
+ *     candidate, is classified against the query's depth map, and the candidate the measurements agree with most is selected.  It
+ *     needs no ground truth and no mesh.  The reference has no counterpart.
+ * DEFINITION.  All arithmetic is float64 without contraction; only + - * / and floor are used and NO sum over rows is formed in floating
+ * point, so the device and tests/pose_verify_restatement.py, its numpy statement, agree EXACTLY in every output.  Per pair: a source
+ * cloud src [n_s,3] float64 metres (the anchor's object cloud, anchor camera frame); the target as in g3: depth [H,W] fp32 millimetres,
+ * mask [H,W] int32 (1 = object), cam9 float64 (fx = cam9[0], cx = cam9[2], fy = cam9[4], cy = cam9[5]); K candidate poses, fp32 4x4,
+ * widened, of which only rows 0-2 are read; tol in metres.  Every source row gets, for every candidate, exactly one class, decided by
+ * these tests in this order; a comparison is exactly as written, and a NaN fails every comparison:
+ *   0 BEHIND     s = ((R0 x + R1 y) + R2 z) + t per coordinate (g3 step 1); BEHIND unless s.z > 0.
+ *   1 OUTSIDE    u = (fx s.x) / s.z + cx, v = (fy s.y) / s.z + cy, px = floor(u + 0.5), py = floor(v + 0.5) (g3 step 2); OUTSIDE unless
+ *                0 <= px <= W - 1 and 0 <= py <= H - 1, tested in float64 before any conversion to an integer: no read leaves the map.
+ *                The whole image is valid here, not g3's window without the one-pixel border.
+ *   2 UNKNOWN    z = depth[py,px]; UNKNOWN unless 0 < z < +inf.
+ *   3 OCCLUDED   d = s.z - double(z) / 1000; OCCLUDED when d > tol: the point lies behind the measured surface (self-occlusion or an
+ *                occluder).  Neutral.
+ *   4 VIOLATION  -d > tol: the point floats in front of a surface the sensor saw - free space violated.
+ *   5 OFF        otherwise, and mask[py,px] != 1: agrees with the depth, but not on the object.
+ *   6 HIT        otherwise, and mask[py,px] == 1.
+ * counts[k][c] = the number of rows of class c under candidate k; the counts of a candidate sum to n_s.
+ * SELECTION, in integers only: best = the candidate with the largest counts[k][HIT]; ties go to the smallest
+ * counts[k][BEHIND] + counts[k][VIOLATION] + counts[k][OFF], then to the smallest k.  A pair with status_in != 0 gets all counts 0,
+ * cls = -1 and best = 0; a pair with n_s = 0 gets the same counts and best = 0.  (The score a caller reports, counts[HIT] / max(n_s, 1),
+ * is formed outside: the candidates of a pair share n_s, so the selection never divides.)
+ *
+ * oryon_pose_verify: src [B,cap_src,3] float64; n_src [B] DEVICE counts, read as in g3 (above the capacity: the capacity; below 0: 0;
+ *   rows beyond the count are never read); depth [B,H,W] fp32, mask [B,H,W] int32, cam9 [B,9] float64; poses [B,K,16] fp32; status_in [B]
+ *   or NULL.  1 <= K <= ORYON_POSE_VERIFY_MAX_POSES, 1 <= cap_src <= ORYON_ICP_MAX_ROWS, 0 <= B <= 65535 (B == 0: nothing to do, returns
+ *   ORYON_OK), H, W >= 1, H W < 2^31, tol >= 0 (a NaN is rejected).  Every check precedes every launch and every dereference.
+ *   workspace: oryon_pose_verify_workspace_bytes(B, cap_src, K) bytes (0 = unsupported shape), 256-byte aligned
+ *     = align256(B * ceil(cap_src / 256) * K * ORYON_POSE_VERIFY_CLASSES * 4).
+ *   Outputs: counts [B,K,7] int32; best [B] int32; cls [B,K,cap_src] int32 or NULL: the class of every row under every candidate, -1
+ *   beyond the pair's count (and everywhere for a pair with status_in != 0).  Two launches, no atomics, nothing read back: outputs are
+ *   identical bytes across runs, streams and batch position.  float64 pointers must be 8-byte aligned. */
+#define ORYON_POSE_VERIFY_CLASSES 7
+#define ORYON_POSE_VERIFY_MAX_POSES 16
+size_t oryon_pose_verify_workspace_bytes(int B, int cap_src, int K);
+int oryon_pose_verify(const double *src, const int32_t *n_src, int cap_src, const float *depth, const int32_t *mask, int H, int W,
+                      const double *cam9, int B, const float *poses /* [B,K,16] */, int K, double tol, const int32_t *status_in,
+                      void *workspace, size_t workspace_bytes, int32_t *counts /* [B,K,7] */, int32_t *best /* [B] */,
+                      int32_t *cls /* [B,K,cap_src] or NULL: class per row, -1 beyond the count */, void *stream);
+
 /* a5  StandardDecoder.forward (models/decoder.py:82-108) on the device, fp32 in / fp32 out, for the decoder the reference builds
  *     (get_decoder, models/decoder.py:119-125: input_dim 128, decoder_dims [64, 32], extra_upsampling, guidance projections 256->32 and
  *     128->16): three Up blocks (ConvTranspose2d 2x2 s2 -> cat guidance -> (conv3x3 - GroupNorm(C/16) - ReLU) x 2, :9-42), the two

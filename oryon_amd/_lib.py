@@ -200,6 +200,8 @@ _PROTOS = {
     "oryon_icp_plane_workspace_bytes": (c_size_t, [c_int, c_int]),
     "oryon_icp_plane_refine": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, _P, c_int, _P, c_int, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, _P, _P, c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "oryon_pose_verify_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "oryon_pose_verify": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, _P, c_int, _P, c_int, ctypes.c_double, _P, _P, c_size_t, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -41,6 +41,16 @@ __device__ __forceinline__ double icp_move(const double *row, double x, double y
     return ((row[0] * x + row[1] * y) + row[2] * z) + row[3];
 }
 
+// The pixel a moved point s (s[2] > 0) projects to, as g3's step 2 states it: u = (fx s.x) / s.z + cx, v alike, fpx = floor(u + 0.5),
+// fpy = floor(v + 0.5) - still float64.  The caller tests them against its window BEFORE converting (a NaN or an infinity fails such a
+// test), so no read leaves the map.  One text for icp_plane.hip and pose_verify.hip.
+__device__ __forceinline__ void icp_project(const double (&s)[3], double fx, double cx, double fy, double cy, double &fpx, double &fpy)
+{
+    const double u = (fx * s[0]) / s[2] + cx, w = (fy * s[1]) / s[2] + cy;
+    fpx = floor(u + 0.5);
+    fpy = floor(w + 0.5);
+}
+
 // The end of an init kernel (one wave per pair): idx = -1, T_0 widened into the state and written out (so a pair that never iterates
 // returns it), the done flag of a pair that does not start, the counters zeroed.  T_init NULL: the identity.  T64, n_kept, idx and
 // status_out may be NULL.

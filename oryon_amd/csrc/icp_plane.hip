@@ -99,8 +99,8 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_plane_assoc_kernel(const doub
 #pragma unroll
     for (int q = 0; q < ICPP_REC; ++q) v[q] = 0.0;
     if (kept) {
-        const double u = (fx * s[0]) / s[2] + cx, w = (fy * s[1]) / s[2] + cy;
-        const double fpx = floor(u + 0.5), fpy = floor(w + 0.5);
+        double fpx, fpy;
+        icp_project(s, fx, cx, fy, cy, fpx, fpy);
         kept = fpx >= 1.0 && fpx <= (double)(W - 2) && fpy >= 1.0 && fpy <= (double)(H - 2);      // NaN and inf fail
         if (kept) {
             const int px = (int)fpx, py = (int)fpy, p = py * W + px;

@@ -151,3 +151,27 @@ def icp_point_to_plane(A, depth_mm, mask, K, init_pose=None, max_iterations=20, 
                                t(mask == 1, np.int32), t(cam9, np.float64), t(T0, np.float32), max_iter=int(max_iterations),
                                tolerance=float(tolerance), max_dist=float(max_dist), normal_jump=float(normal_jump))
     return out["T64"][0].cpu().numpy()
+
+
+def pose_depth_score(A, depth_mm, mask, K, poses, tol=0.01, *, device="cuda") -> dict:
+    """How well the depth map agrees with each candidate pose of the cloud A [n,3] (metres): depth_mm [H,W] millimetres, mask [H,W]
+    (1 = object), K the [3,3] intrinsics, poses [k,4,4] (or one [4,4]), tol in metres -> dict(counts [k,7] int32 - rows BEHIND the
+    camera, OUTSIDE the map, on a pixel of UNKNOWN depth, OCCLUDED, in VIOLATION of free space, on the surface but OFF the object, and
+    HITs - score [k] float64 = counts[:, 6] / max(n, 1), best = the candidate with the most hits (ties: the fewest BEHIND + VIOLATION +
+    OFF, then the first)).  The definition is include/oryon_hip.h's, oryon_pose_verify (csrc/pose_verify.hip); it needs no ground truth
+    and no mesh.  poses and K reach the kernel as float32 values, as the solvers' poses and the pipeline's intrinsics do.  The
+    reference has no counterpart."""
+    A = _as_points(A)
+    dev = torch.device(device)
+    P = np.asarray(poses, dtype=np.float32)
+    P = P.reshape(1, 4, 4) if P.ndim == 2 else P
+    assert P.ndim == 3 and P.shape[1:] == (4, 4) and P.shape[0] >= 1, "poses are [k, 4, 4]"
+    depth_mm, mask = np.asarray(depth_mm), np.asarray(mask)
+    assert depth_mm.ndim == 2 and mask.shape == depth_mm.shape, "depth_mm and mask are [H, W]"
+    n = A.shape[0]
+    t = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dtype=dt))[None].to(dev)
+    cam9 = np.asarray(K, dtype=np.float32).reshape(9).astype(np.float64)
+    src = _cloud(A, dev) if n > 0 else torch.zeros((1, 1, 3), dtype=torch.float64, device=dev)      # a capacity of one row, none in use
+    out = ops.pose_verify(src, torch.tensor([n], dtype=torch.int32, device=dev), t(depth_mm, np.float32), t(mask == 1, np.int32),
+                          t(cam9, np.float64), t(P, np.float32), tol=float(tol))
+    return dict(counts=out["counts"][0].cpu().numpy(), score=out["score"][0].cpu().numpy(), best=int(out["best"][0]))

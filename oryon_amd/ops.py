@@ -1281,6 +1281,65 @@ def icp_plane_refine(src: torch.Tensor, n_src: torch.Tensor, depth: torch.Tensor
     return o
 
 
+POSE_VERIFY_CLASSES, POSE_VERIFY_MAX_POSES = 7, 16      # ORYON_POSE_VERIFY_CLASSES, ORYON_POSE_VERIFY_MAX_POSES (include/oryon_hip.h)
+POSE_VERIFY_NAMES = ("behind", "outside", "unknown", "occluded", "violation", "off", "hit")      # the classes in the order of counts[..., c]
+POSE_VERIFY_HIT = POSE_VERIFY_NAMES.index("hit")
+
+
+def pose_verify(src: torch.Tensor, n_src: torch.Tensor, depth: torch.Tensor, mask: torch.Tensor, cam9: torch.Tensor, poses: torch.Tensor,
+                tol: float = 0.01, status: Optional[torch.Tensor] = None, want_cls: bool = False, workspace: Optional[torch.Tensor] = None):
+    """Depth-consistency verification of K candidate poses per pair (g4, csrc/pose_verify.hip; definition: include/oryon_hip.h,
+    oryon_pose_verify).  src [B,cap_src,3] float64 metres, n_src [B] int32, depth [B,H,W] fp32 millimetres, mask [B,H,W] int32
+    (1 = object), cam9 [B,9] float64, poses [B,K,4,4] fp32 ([B,4,4]: K = 1), status [B] int32 or None - all contiguous device tensors
+    of exactly these dtypes: nothing is converted or copied here, a tensor that does not fit is rejected with the name of the check.
+    tol in metres.  Runs on the current stream with no host round trip -> dict(counts [B,K,7] int32 (BEHIND, OUTSIDE, UNKNOWN, OCCLUDED,
+    VIOLATION, OFF, HIT), best [B] int32, score [B,K] float64 = counts[HIT] / max(n_src, 1), and with want_cls cls [B,K,cap_src]
+    int32: the class of every row, -1 beyond the count)."""
+    req = _icp_requirer("pose_verify")
+    for name, t in (("src", src), ("n_src", n_src), ("depth", depth), ("mask", mask), ("cam9", cam9), ("poses", poses)):
+        req(isinstance(t, torch.Tensor) and t.is_cuda, f"{name}.is_cuda")
+    req(src.dtype == torch.float64, "src.dtype == float64", str(src.dtype))
+    req(src.dim() == 3 and src.shape[2] == 3 and src.shape[1] >= 1, "src.shape == [B,cap_src,3]", str(tuple(src.shape)))
+    B, cap_src = src.shape[0], src.shape[1]
+    req(B >= 1, "B >= 1")
+    req(src.is_contiguous(), "src.is_contiguous")
+    _icp_check_counts(req, B, n_src=n_src, status=status)
+    req(depth.dtype == torch.float32, "depth.dtype == float32", str(depth.dtype))
+    req(depth.dim() == 3 and depth.shape[0] == B, "depth.shape == [B,H,W]", str(tuple(depth.shape)))
+    H, W = depth.shape[1], depth.shape[2]
+    req(H >= 1 and W >= 1 and H * W < 2 ** 31, "H, W >= 1 and H W < 2^31", f"{H} x {W}")
+    req(depth.is_contiguous(), "depth.is_contiguous")
+    req(mask.dtype == torch.int32, "mask.dtype == int32", str(mask.dtype))
+    req(tuple(mask.shape) == (B, H, W), "mask.shape == depth.shape", str(tuple(mask.shape)))
+    req(mask.is_contiguous(), "mask.is_contiguous")
+    req(cam9.dtype == torch.float64, "cam9.dtype == float64", str(cam9.dtype))
+    req(tuple(cam9.shape) == (B, 9), "cam9.shape == [B,9]", str(tuple(cam9.shape)))
+    req(cam9.is_contiguous(), "cam9.is_contiguous")
+    req(poses.dtype == torch.float32, "poses.dtype == float32", str(poses.dtype))
+    req(poses.dim() in (3, 4) and poses.shape[0] == B and tuple(poses.shape[-2:]) == (4, 4) and (poses.dim() == 3 or poses.shape[1] >= 1),
+        "poses.shape == [B,K,4,4] or [B,4,4]", str(tuple(poses.shape)))
+    req(poses.is_contiguous(), "poses.is_contiguous")
+    K = 1 if poses.dim() == 3 else poses.shape[1]
+    req(K <= POSE_VERIFY_MAX_POSES, f"K <= {POSE_VERIFY_MAX_POSES}", str(K))
+    req(all(t.device == src.device for t in (n_src, depth, mask, cam9, poses, status) if t is not None), "one device")
+    req(float(tol) >= 0.0, "tol >= 0", str(tol))
+    req(cap_src <= ICP_MAX_ROWS, f"cap_src <= {ICP_MAX_ROWS}", str(cap_src))
+    dev = _lib.require_gpu(src.device)
+    with torch.cuda.device(dev):
+        ws = _lib.workspace(dev, lib().oryon_pose_verify_workspace_bytes(B, cap_src, K),
+                            f"oryon_pose_verify_workspace_bytes({B}, {cap_src}, {K})", workspace)
+        counts = torch.empty((B, K, POSE_VERIFY_CLASSES), dtype=torch.int32, device=dev)
+        best = torch.empty((B,), dtype=torch.int32, device=dev)
+        cls = torch.empty((B, K, cap_src), dtype=torch.int32, device=dev) if want_cls else None
+        check(lib().oryon_pose_verify(ptr(src), ptr(n_src), cap_src, ptr(depth), ptr(mask), H, W, ptr(cam9), B, ptr(poses), K, float(tol),
+                                      ptr(status), ptr(ws), ws.numel(), ptr(counts), ptr(best), ptr(cls), stream_ptr(dev)), "oryon_pose_verify")
+        score = counts[:, :, POSE_VERIFY_HIT].to(torch.float64) / torch.clamp(n_src, min=1, max=cap_src).to(torch.float64)[:, None]
+    out = dict(counts=counts, best=best, score=score)
+    if want_cls:
+        out["cls"] = cls
+    return out
+
+
 _x3_weights = {}
 # Validation mode of the fp16x3 path (backbone.enable_fp16x3(True, guard=True)): every call first checks max|activation| against the
 # float16 range (one reduction + a host sync per linear - for a first run with a real checkpoint, not for throughput) and evaluates

@@ -14,6 +14,11 @@ refine_max_dist.  `test.refine = icp_plane` refines it by point-to-plane ICP of 
 (projective association, csrc/icp_plane.hip; no counterpart in the reference): the same flags with defaults of their own
 (REFINE_DEFAULTS) and test.refine_normal_jump.
 
+`test.verify = score` (absent or `none`: nothing changes) rates the final pose of every solved pair against the query's depth map
+(csrc/pose_verify.hip; no counterpart in the reference): the share of the anchor's object cloud that lands on the object within
+test.verify_tol of the measured depth, with no ground truth and no mesh.  `test.verify = guard` (needs a refinement) rates the solver's
+pose and the refined one and keeps the refinement only when more of the cloud agrees with it.
+
 and the validation step (pipeline.py:196-247, 579-590):
 
     on_validation_start(objects=None) / validation_step(batch, batch_idx) -> (loss, log) / on_validation_end() -> dict
@@ -69,6 +74,57 @@ def default_refine() -> str:
     return _default_refine
 
 
+# test.verify (csrc/pose_verify.hip; no counterpart in the reference): 'score' rates the final pose of every solved pair by how much
+# of the anchor's object cloud the query's depth map confirms on the object; 'guard' rates the solver's pose and the refined one and
+# keeps the one the measurements agree with more.  A property of the pipeline like test.refine - not a refinement, not a field of
+# MatchPoseConfig.  test.verify_tol (metres): how far a moved point may lie from the measured surface and still agree with it.  The
+# default is a design choice at the scale of the refiners' gates (REFINE_DEFAULTS: 2 cm), not tuned on data.
+VERIFY_MODES = ("none", "score", "guard")
+VERIFY_TOL = 0.01
+_default_verify = ("none", VERIFY_TOL)
+
+
+def _check_verify(mode: str, tol: float) -> Tuple[str, float]:
+    if mode not in VERIFY_MODES:
+        raise ValueError(f"Verification {mode} not implemented")
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise ValueError(f"test.verify_tol must be >= 0 (metres), not {tol}")
+    return mode, tol
+
+
+def set_default_verify(mode: str, tol: float = VERIFY_TOL) -> None:
+    """The process-wide default of test.verify / test.verify_tol: what default_args() carries and what a Pipeline does when its args
+    name neither (('none', 0.01) unless set).  A driver sets it once, before it builds pipelines (run_pose.py --verify does)."""
+    global _default_verify, _latest_verify
+    _default_verify = _check_verify(mode, tol)
+    _latest_verify = None
+
+
+def default_verify() -> Tuple[str, float]:
+    return _default_verify
+
+
+# (mode, tol, log) of the latest Pipeline built with test.verify != 'none' since the last set_default_verify.  A driver that cannot
+# reach the pipeline another module builds (run_pose.py around run_test.py) reads its summary from here.
+_latest_verify: Optional[Tuple[str, float, List[Tuple]]] = None
+
+
+def _reduce_verify(mode: str, tol: float, log: List[Tuple]) -> Dict:
+    """log: per step (status, chosen score, best), each [B] -> the mode, the tolerance, the mean score of the chosen poses over the
+    solved pairs and, for 'guard', how many of them kept their refinement.  Reads the device once per step."""
+    scores = [float(s) for st, sc, _ in log for s in sc[st == PAIR_OK].cpu().tolist()]
+    out = {"verify": mode, "verify_tol": tol, "verify_pairs": len(scores), "verify_score_mean": float(np.mean(scores)) if scores else None}
+    if mode == "guard":
+        out["verify_refinements_kept"] = int(sum(int((b[st == PAIR_OK] == 1).sum()) for st, _, b in log))
+    return out
+
+
+def verify_summary() -> Dict:
+    """Pipeline.verify_summary() of the latest verifying pipeline of this process; {} when there is none."""
+    return {} if _latest_verify is None else _reduce_verify(*_latest_verify)
+
+
 def default_args(**overrides) -> SimpleNamespace:
     """The hot-path subset of configs/config.yaml (same names, same defaults)."""
     args = SimpleNamespace(
@@ -88,7 +144,11 @@ def default_args(**overrides) -> SimpleNamespace:
                              # test.ratio / test.ratio_radius (csrc/match_second.hip; no counterpart in the reference): the ratio
                              # test with an exclusion disc, 0 = off ((0.0, 5) unless a driver called engine.set_default_ratio).  Read
                              # with getattr(..., 0.0 / 5)
-                             ratio=default_ratio()[0], ratio_radius=default_ratio()[1]),
+                             ratio=default_ratio()[0], ratio_radius=default_ratio()[1],
+                             # test.verify / test.verify_tol (csrc/pose_verify.hip; no counterpart in the reference): rate, or
+                             # choose between, the poses of a pair against the query's depth map (('none', 0.01) unless a driver
+                             # called set_default_verify).  Read with getattr: arg objects without them keep working
+                             verify=default_verify()[0], verify_tol=default_verify()[1]),
         loss=SimpleNamespace(hard_negatives=True, pos_margin=0.2, neg_margin=0.9, neg_kernel_size=5, mask_type="dice",
                              w={"mask": 1.0, "pos": 0.5, "neg": 0.5}),
         optimization=SimpleNamespace(optim_type="Adam", scheduler_type="cosine", lr=0.001, momentum=0.0, w_decay=0.0005, gamma=0.1),
@@ -150,7 +210,12 @@ class Pipeline:
         self._valid_fmr: List[float] = []
         self.last_validation: Optional[Dict] = None      # the latest validation_step's {'poses', 'status', 'results', 'losses'}
         self.last_refine: Optional[Dict] = None          # the latest ops.icp_refine / ops.icp_plane_refine result (test.refine)
+        self.last_verify: Optional[Dict] = None          # the latest ops.pose_verify result (test.verify)
+        self._verify_log: List[Tuple] = []               # per step (status, chosen score, best), each [B]: what verify_summary reduces
         self.refine_mode()                               # an unknown test.refine raises here, not at the first pose
+        if self.verify_mode() != "none":                 # and so does an unknown test.verify, or a guard with nothing to choose from
+            global _latest_verify
+            _latest_verify = (self.verify_mode(), self.verify_tol(), self._verify_log)
 
     # ------------------------------------------------------------------ mask post-processing (losses.py:56-60)
     def mask_results(self, batch: Dict, outputs: Dict) -> Dict[str, Tensor]:
@@ -289,8 +354,46 @@ class Pipeline:
         if self.args.test.mask != "predicted":
             return batch["anchor"]["mask"].to(dev), batch["query"]["mask"].to(dev)
         if results is None or "mask_a" not in results:
-            raise KeyError(f"test.refine='{self.refine_mode()}' with test.mask='predicted' needs the predicted masks (results['mask_a'], results['mask_q'])")
+            raise KeyError(f"test.refine='{self.refine_mode()}' / test.verify='{self.verify_mode()}' with test.mask='predicted' needs the "
+                           "predicted masks (results['mask_a'], results['mask_q'])")
         return results["mask_a"], results["mask_q"]
+
+    # ------------------------------------------------------------------ depth-consistency verification (test.verify; csrc/pose_verify.hip)
+    def verify_mode(self) -> str:
+        """test.verify: 'none' (absent = the process-wide default, 'none' unless a driver set it), 'score' - rate the final pose - or
+        'guard' - rate the solver's pose and the refined one, keep the better (needs test.refine != 'none')."""
+        mode, _ = _check_verify(getattr(self.args.test, "verify", default_verify()[0]), self.verify_tol())
+        if mode == "guard" and self.refine_mode() == "none":
+            raise ValueError("test.verify='guard' needs a refinement (test.refine='icp' or 'icp_plane'): nothing to choose from")
+        return mode
+
+    def verify_tol(self) -> float:
+        return float(getattr(self.args.test, "verify_tol", default_verify()[1]))
+
+    def verify_inputs(self, mask_a: Tensor, mask_q: Tensor, depth_a: Tensor, depth_q: Tensor, cam_a: Tensor, cam_q: Tensor,
+                      pair_key: Tensor, clouds: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+        """What verify_poses runs on: the anchor's object cloud exactly as _refine_cloud builds it for the refiners (REFINE_SEED_A,
+        test.refine_points) and refine_target - the query's depth map, its object mask, the intrinsics.  clouds: what refine_inputs
+        returned for the same pair(s), if a refinement ran - its cloud (and, in mode icp_plane, its target) is taken, not rebuilt."""
+        if clouds is not None and "depth" in clouds:
+            return clouds
+        if clouds is not None:
+            src, n_src = clouds["src"], clouds["n_src"]
+        else:
+            src, n_src = self._refine_cloud(mask_a, depth_a, cam_a, self.REFINE_SEED_A, pair_key)
+        return dict(self.refine_target(mask_q, depth_q, cam_q), src=src, n_src=n_src)
+
+    def verify_poses(self, poses: Tensor, status: Optional[Tensor], inputs: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        """ops.pose_verify on the inputs of verify_inputs with test.verify_tol: poses [B,K,4,4] fp32 -> dict(counts [B,K,7], best [B],
+        score [B,K]); a pair with a failure status gets zero counts and best 0."""
+        return ops.pose_verify(inputs["src"], inputs["n_src"], inputs["depth"], inputs["mask"], inputs["cam9"],
+                               poses.to(torch.float32).contiguous(), tol=self.verify_tol(), status=status)
+
+    def verify_summary(self) -> Dict:
+        """What a driver adds to its summary: {} in mode 'none'; else the mode, the tolerance, the mean score of the chosen poses over
+        the solved pairs of every step of this pipeline so far and, for 'guard', how many of them kept their refinement."""
+        mode = self.verify_mode()
+        return {} if mode == "none" else _reduce_verify(mode, self.verify_tol(), self._verify_log)
 
     # ------------------------------------------------------------------ pipeline.py:429-472
     def get_pose(self, batch: Dict, corrs: Tensor, idx: int, results: Optional[Dict] = None, pair_key: Optional[int] = None) -> Tensor:
@@ -321,14 +424,24 @@ class Pipeline:
             pose4 = spectral_pose(pcd_a[0, :m], pcd_q[0, :m], dev, **self._spectral_cfg())
         else:
             pose4 = get_pointdsc_pose(self.pointdsc_solver, pcd_a[0, :m], pcd_q[0, :m], self.device)
-        if self.refine_mode() != "none":
-            mask_a, mask_q = self._refine_masks(batch, results, dev)
-            key = torch.tensor([idx if pair_key is None else pair_key], dtype=torch.int64, device=dev)
-            clouds = self.refine_inputs(mask_a[idx:idx + 1], mask_q[idx:idx + 1], depth_a[None].contiguous(), depth_q[None].contiguous(),
-                                        camera_a, camera_q, key)
-            self.last_refine = self.refine_poses(pose4.to(torch.float32)[None].to(dev), None, clouds)
-            return self.last_refine["T"][0].cpu()
-        return pose4.to(torch.float32)
+        refine, verify = self.refine_mode(), self.verify_mode()
+        if refine == "none" and verify == "none":
+            return pose4.to(torch.float32)
+        mask_a, mask_q = self._refine_masks(batch, results, dev)
+        key = torch.tensor([idx if pair_key is None else pair_key], dtype=torch.int64, device=dev)
+        sides = (mask_a[idx:idx + 1], mask_q[idx:idx + 1], depth_a[None].contiguous(), depth_q[None].contiguous(), camera_a, camera_q, key)
+        start = pose4.to(torch.float32)[None].to(dev)
+        final, clouds = start, None
+        if refine != "none":
+            clouds = self.refine_inputs(*sides)
+            self.last_refine = self.refine_poses(start, None, clouds)
+            final = self.last_refine["T"]
+        if verify != "none":                                   # guard: [solver's, refined] - the solver's pose wins an exact tie
+            cand = torch.stack([start, final], dim=1) if verify == "guard" else final[:, None]
+            self.last_verify = self.verify_poses(cand, None, self.verify_inputs(*sides, clouds=clouds))
+            if verify == "guard":
+                final = cand[:, int(self.last_verify["best"][0])]
+        return final[0].cpu() if refine != "none" else pose4.to(torch.float32)
 
     _SPECTRAL_FIELDS = ("num_iterations", "ratio", "inlier_threshold", "sigma_d", "k", "nms_radius")
 
@@ -411,6 +524,15 @@ class Pipeline:
             records.append(dict(status=status, pred_pose_rel=pred_pose, pred_pose=pred_q))
             if status == PAIR_OK and self.refine_mode() != "none":
                 records[-1]["refine_iters"] = int(self.last_refine["iters"][0])
+            if status == PAIR_OK and self.verify_mode() != "none":         # the chosen candidate's counts and score
+                v = self.last_verify
+                best = int(v["best"][0])
+                records[-1]["verify_counts"] = [int(c) for c in v["counts"][0, best].cpu().tolist()]
+                records[-1]["verify_score"] = float(v["score"][0, best])
+                if self.verify_mode() == "guard":
+                    records[-1]["verify_best"] = best
+                self._verify_log.append((torch.tensor([PAIR_OK]), torch.tensor([records[-1]["verify_score"]], dtype=torch.float64),
+                                         torch.tensor([best])))
         return records
 
     # ------------------------------------------------------------------ batched device path
@@ -445,11 +567,25 @@ class Pipeline:
         key = torch.arange(first_pair_index, first_pair_index + BS, dtype=torch.int64, device=dev)
         out = self._engine.run(outputs["featmap_a"].float().contiguous(), outputs["featmap_q"].float().contiguous(), mask_a,
                                mask_q, depth_a, depth_q, batch["anchor"]["camera"].to(dev), batch["query"]["camera"].to(dev), key)
-        if self.refine_mode() != "none":                         # same stream, no host round trip; failed pairs keep their identity
+        refine, verify = self.refine_mode(), self.verify_mode()
+        clouds = None
+        if refine != "none" or verify != "none":
             rmask_a, rmask_q = self._refine_masks(batch, res, dev)
-            self.last_refine = self.refine_poses(out["pose"], out["status"], self.refine_inputs(
-                rmask_a, rmask_q, depth_a, depth_q, batch["anchor"]["camera"].to(dev), batch["query"]["camera"].to(dev), key))
+            sides = (rmask_a, rmask_q, depth_a, depth_q, batch["anchor"]["camera"].to(dev), batch["query"]["camera"].to(dev), key)
+        if refine != "none":                                     # same stream, no host round trip; failed pairs keep their identity
+            clouds = self.refine_inputs(*sides)
+            self.last_refine = self.refine_poses(out["pose"], out["status"], clouds)
             out["pose_unrefined"], out["pose"], out["refine_iters"] = out["pose"], self.last_refine["T"], self.last_refine["iters"]
+        if verify != "none":                                     # same stream again, nothing read back; failed pairs: zero counts, best 0
+            guard = verify == "guard"
+            cand = torch.stack([out["pose_unrefined"].to(torch.float32), out["pose"]], dim=1) if guard else out["pose"].to(torch.float32)[:, None]
+            v = self.last_verify = self.verify_poses(cand, out["status"], self.verify_inputs(*sides, clouds=clouds))
+            pick = v["best"].to(torch.int64)
+            out["verify_counts"], out["verify_score"] = v["counts"], v["score"].gather(1, pick[:, None])[:, 0]
+            if guard:                                            # [solver's, refined]: the solver's pose wins an exact tie
+                out["pose_refined"], out["verify_best"] = out["pose"], v["best"]
+                out["pose"] = cand.gather(1, pick[:, None, None, None].expand(-1, 1, 4, 4))[:, 0].contiguous()
+            self._verify_log.append((out["status"], out["verify_score"], v["best"]))
         anchor_pose = batch["anchor"]["pose"].to(dev, torch.float32)
         out["pred_q"] = torch.bmm(out["pose"], anchor_pose)
         if res is not None:

@@ -36,6 +36,15 @@ driver returns - and prints as its last JSON line - carries `"mutual": true`.
 best match at least N pixels away from its nearest one, and only rows with min_dist <= R * that distance reach the solver (N = 1 is
 Lowe's ratio test; with `--mutual` the mutual rows are filtered).  The summary carries `"ratio": R, "ratio_radius": N`.
 
+    python run_pose.py --solver ransac --refine icp --verify guard --pairs 8 --batch 4
+
+`--verify {none,score,guard} [--verify-tol M]` (test.verify / test.verify_tol; default none, M = 0.01 m) becomes the process-wide default
+(oryon_amd.pipeline.set_default_verify) in the same way.  `score` rates the final pose of every solved pair against the query's depth
+map (csrc/pose_verify.hip): the share of the anchor's object cloud that lands on the object within M of the measured depth - no ground
+truth, no mesh.  `guard` (needs `--refine`) rates the solver's pose and the refined one and keeps the refinement only when more of the
+cloud agrees with it.  The summary carries `"verify"`, `"verify_tol"`, `"verify_score_mean"` over the solved pairs and, for `guard`,
+`"verify_refinements_kept"`.  M is a design choice at the scale of the refiners' gates, not tuned on data.
+
     python run_pose.py --vsd --data-root /data --dataset nocs --ckpt ... --out preds/nocs.csv
 
 `--vsd` (real-asset mode only) also reports VSD and AR = (VSD + MSSD + MSPD) / 3, the reference's headline column
@@ -53,6 +62,7 @@ if ROOT not in sys.path:
 
 
 REFINE_CHOICES = ["none", "icp", "icp_plane"]          # oryon_amd.pipeline.REFINEMENTS
+VERIFY_CHOICES = ["none", "score", "guard"]            # oryon_amd.pipeline.VERIFY_MODES
 
 
 def take_refine(argv=None):
@@ -64,20 +74,24 @@ def take_refine(argv=None):
 
 
 class Parsed(tuple):
-    """(solver, the arguments left for run_test.py), with `.mutual`: whether `--mutual` was given (taken out, like `--refine`), and
-    `.ratio` / `.ratio_radius`: what `--ratio` / `--ratio-radius` gave (0.0 / 5 when absent)."""
-    def __new__(cls, solver, rest, mutual, ratio=0.0, ratio_radius=5):
+    """(solver, the arguments left for run_test.py), with `.mutual`: whether `--mutual` was given (taken out, like `--refine`),
+    `.ratio` / `.ratio_radius`: what `--ratio` / `--ratio-radius` gave (0.0 / 5 when absent), and `.verify` / `.verify_tol`: what
+    `--verify` / `--verify-tol` gave ('none' / 0.01 when absent)."""
+    def __new__(cls, solver, rest, mutual, ratio=0.0, ratio_radius=5, verify="none", verify_tol=0.01):
         self = super().__new__(cls, (solver, rest))
         self.mutual = mutual
         self.ratio = ratio
         self.ratio_radius = ratio_radius
+        self.verify = verify
+        self.verify_tol = verify_tol
         return self
 
 
 def parse(argv=None):
     """-> Parsed: (solver, the arguments left for run_test.py) + .mutual.  `--refine` is checked and taken out as well (take_refine
     returns it), and so are `--mutual` (test.mutual: keep only the mutual nearest neighbours, csrc/match_mutual.hip) and `--ratio` /
-    `--ratio-radius` (test.ratio, test.ratio_radius: the ratio test with an exclusion disc, csrc/match_second.hip)."""
+    `--ratio-radius` (test.ratio, test.ratio_radius: the ratio test with an exclusion disc, csrc/match_second.hip) and `--verify` /
+    `--verify-tol` (test.verify, test.verify_tol: depth-consistency verification of the poses, csrc/pose_verify.hip)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
     ap.add_argument("--solver", choices=["pointdsc", "ransac", "spectral"], default="pointdsc",
                     help="test.solver: PointDSC registration, best_fit_transform_with_RANSAC, or the spectral solver (the last two need no "
@@ -87,12 +101,15 @@ def parse(argv=None):
     ap.add_argument("--ratio", type=float, default=0.0, help="test.ratio: keep a match only when min_dist <= RATIO * the best distance "
                                                              "outside the exclusion disc (0 = off)")
     ap.add_argument("--ratio-radius", type=int, default=5, help="test.ratio_radius: radius of that disc in pixels (1 = Lowe's ratio test)")
+    ap.add_argument("--verify", choices=VERIFY_CHOICES, default="none", help="test.verify: score the final pose against the query's depth "
+                                                                             "map, or guard a refinement with that score (see above)")
+    ap.add_argument("--verify-tol", type=float, default=0.01, help="test.verify_tol: metres a moved point may lie from the measured surface")
     ap.add_argument("-h", "--help", action="store_true")
     a, rest = ap.parse_known_args(argv)
     if a.help:
         ap.print_help()
         rest = ["--help"] + rest               # then run_test.py's own help
-    return Parsed(a.solver, rest, a.mutual, a.ratio, a.ratio_radius)
+    return Parsed(a.solver, rest, a.mutual, a.ratio, a.ratio_radius, a.verify, a.verify_tol)
 
 
 def take_vsd(argv):
@@ -125,6 +142,10 @@ def main(argv=None):
     solver, rest = parsed
     if vsd and "--data-root" not in rest and not any(r.startswith("--data-root=") for r in rest):
         raise SystemExit("run_pose.py --vsd needs real-asset mode (--data-root ...): the synthetic pairs have no object mesh")
+    if parsed.verify == "guard" and refine == "none":
+        raise SystemExit("run_pose.py --verify guard needs --refine icp or --refine icp_plane: nothing to choose from")
+    if not parsed.verify_tol >= 0.0:
+        raise SystemExit("run_pose.py --verify-tol is a distance in metres, >= 0")
     from oryon_amd.engine import set_default_solver
     set_default_solver(solver)
     from oryon_amd.pipeline import set_default_refine
@@ -133,13 +154,19 @@ def main(argv=None):
     set_default_mutual(parsed.mutual)
     from oryon_amd.engine import set_default_ratio
     set_default_ratio(parsed.ratio, parsed.ratio_radius)
+    from oryon_amd.pipeline import set_default_verify
+    set_default_verify(parsed.verify, parsed.verify_tol)
     import run_test
     summary = run_test.main(rest)
-    if parsed.mutual or parsed.ratio > 0:
+    verified = parsed.verify != "none"
+    if parsed.mutual or parsed.ratio > 0 or verified:
         if parsed.mutual:
             summary = dict(summary, mutual=True)
         if parsed.ratio > 0:
             summary = dict(summary, ratio=parsed.ratio, ratio_radius=parsed.ratio_radius)
+        if verified:
+            from oryon_amd.pipeline import verify_summary         # what the pipelines run_test.py built have rated
+            summary = {**summary, "verify": parsed.verify, "verify_tol": parsed.verify_tol, **verify_summary()}
         if not (vsd and summary.get("pairs")):
             print(json.dumps(summary))               # run_test.py's line again, with the flag recorded
     return add_vsd(summary, rest) if vsd and summary.get("pairs") else summary

@@ -1,10 +1,13 @@
 """ICP refinement time (ops.icp_refine, csrc/icp.hip): B pairs of N x N points, ITERS forced iterations (tolerance = 0: no pair
 finishes early), device events after a warm-up.  GPU box.
 
-    python tools/time_icp.py [B=64] [N=2048] [ITERS=20] [--mode icp|plane]
+    python tools/time_icp.py [B=64] [N=2048] [ITERS=20] [--mode icp|plane|verify]
 
 `--mode plane`: point-to-plane ICP on the depth map instead (ops.icp_plane_refine, csrc/icp_plane.hip): B pairs of N source rows onto
 480 x 640 depth maps, ITERS forced iterations - 2 ITERS + 1 small launches, no candidate search.
+
+`--mode verify`: depth-consistency verification (ops.pose_verify, csrc/pose_verify.hip) of K = 2 candidate poses per pair - the start
+pose of `--mode plane` and the identity, which is the truth here - on the same inputs: two launches per call, ITERS is not used.
 
 Prints one JSON line: ms per call (median and spread over the repeats), the candidate evaluations per second, and - for scale - the
 estimate DESIGN.md "ICP refinement" started from (B ITERS N^2 candidates at ~8 float64 VALU instructions each at the unpacked vector
@@ -78,6 +81,24 @@ def main_plane(B, N, iters):
                       "mean_err_first_pair": float(out["mean_err"][0])}))
 
 
+def main_verify(B, N, K=2):
+    dev = torch.device("cuda", 0)
+    src, depth, mask, cam9, T0 = plane_inputs(B, N, dev)
+    n = torch.full((B,), N, dtype=torch.int32, device=dev)
+    poses = torch.stack([T0, torch.eye(4, dtype=torch.float32, device=dev).expand(B, 4, 4)], dim=1).contiguous()
+    ws = torch.empty((max(ops.lib().oryon_pose_verify_workspace_bytes(B, N, K), 256),), dtype=torch.uint8, device=dev)
+    call = lambda: ops.pose_verify(src, n, depth, mask, cam9, poses, tol=0.01, workspace=ws)
+    for _ in range(3):
+        out = call()
+    torch.cuda.synchronize()
+    assert (out["counts"].sum(dim=2) == N).all(), "every row has one class"
+    ms = timed(call)
+    med = ms[len(ms) // 2]
+    print(json.dumps({"mode": "verify", "B": B, "N": N, "K": K, "map": [480, 640], "launches": 2, "ms_per_call": round(med, 4),
+                      "ms_min": round(ms[0], 4), "ms_max": round(ms[-1], 4), "us_per_pair": round(1e3 * med / B, 2),
+                      "counts_first_pair": out["counts"][0].cpu().tolist(), "best_first_pair": int(out["best"][0])}))
+
+
 def timed(call, reps=7, per=10):
     ms = []
     for _ in range(reps):
@@ -96,11 +117,13 @@ def main(argv):
     if "--mode" in argv:
         at = argv.index("--mode")
         mode, argv = argv[at + 1], argv[:at] + argv[at + 2:]
-    if mode not in ("icp", "plane"):
-        raise SystemExit("--mode icp|plane")
+    if mode not in ("icp", "plane", "verify"):
+        raise SystemExit("--mode icp|plane|verify")
     B, N, iters = (int(a) for a in (argv + ["64", "2048", "20"][len(argv):])[:3])
     if mode == "plane":
         return main_plane(B, N, iters)
+    if mode == "verify":
+        return main_verify(B, N)
     dev = torch.device("cuda", 0)
     src, dst = clouds(B, N, dev)
     n = torch.full((B,), N, dtype=torch.int32, device=dev)
