@@ -4,13 +4,8 @@
 //     dist = 0.5 * (1 - cosine_similarity(A[:,None], B[None], dim=2));  amin / argmin over dim 1;  min_dist < th
 // The reference materialises a [N1,N2,C] temporary; here nothing of size N1xN2 ever exists.
 //
-// Formulation:  S = Q^ * A^T  (rows = query descriptors, columns = anchor descriptors), both operands
-// already gathered + normalised into k-contiguous [N, C] rows by K0.  One workgroup owns a 128-anchor
-// column panel and streams the query rows past it in 128-row tiles; each of its 4 waves holds a 64x64
-// block of S in four 32x32 v_mfma_f32_32x32x2_f32 accumulators.  In that instruction's C/D layout a lane
-// owns ONE column (= one anchor) and 16 rows (= 16 queries), so the running (min, argmin) over queries is
-// lane-local: no cross-lane traffic until the very end (lane l <-> l+32, then the two waves sharing a
-// column panel through LDS).
+// The formulation S = Q^ * A^T, the tile geometry and why a lane's running (min, argmin) over queries needs no cross-lane
+// traffic until the very end are explained in match_tile.h, for this file, match_mutual.hip and match_second.hip alike.
 //
 // Numerics: the f32-input MFMA is an exact k-ordered fmaf chain (guide §3), so
 //     dot = fma(a_{C-1} q_{C-1}, ... fma(a_0 q_0, 0)),   dist = fma(-0.5, dot, 0.5) = 0.5*(1-dot) bitwise,
@@ -23,15 +18,11 @@
 #include <stdlib.h>
 #include "common.h"
 #include "match_common.h"
+#include "match_tile.h"
 
 namespace oryon {
 
-constexpr int MT = ORYON_MATCH_TILE;  // 128 queries x 128 anchors per workgroup step
-constexpr int BK = 32;                // k-tile
-constexpr int LD = BK + 1;            // padded LDS row: ds_read_b32 of a 32-row column is conflict-free
-constexpr int MATCH_THREADS = 256;
 constexpr int MAX_SPLIT = 16;
-constexpr int TILE_FLOATS = MT * LD;
 
 __global__ __launch_bounds__(MATCH_THREADS, 2) void match_f32_kernel(
     const float *__restrict__ a_hat, const float *__restrict__ q_hat, int B, int Cp, int cap_a, int cap_q,
@@ -191,23 +182,9 @@ __global__ __launch_bounds__(MATCH_THREADS, 2) void match_f32_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// Anchor-stationary kernel (C_pad in {32,64,128,256}).  Every wave keeps ITS 32 anchor rows - the MFMA B
-// operand for the whole K range - in registers for the life of the workgroup, so the only thing that moves
-// is the query stream:  HBM/L2 -> LDS by LDS-DMA (global_load_lds, 16 B per lane, no staging VGPRs),
-// LDS -> MFMA A operand by ds_read_b128.
-//   * LDS tile = 32 KB = ROWS query rows x KH floats, double-buffered (64 KB -> 2 workgroups per CU);
-//     ROWS = 64 and KH = 128 for C_pad >= 128 (C_pad = 256 takes two k-parts per query tile).  A wave always
-//     runs 128 MFMAs (8192 cycles) per barrier, on NACC = ROWS/32 >= 2 accumulators issued round-robin so that
-//     back-to-back MFMAs are independent.
-//   * The k-permuted row layout written by K0 (position 8g+4h+j holds k = 8g+2j+h) makes one 16-byte access
-//     deliver what lane (i, h) feeds to four consecutive MFMA steps, while the accumulation order stays the
-//     natural k order (bit-exact vs the oracle).
-//   * LDS image: 256-byte lines, 16-byte slots XOR-swizzled with the row index: slot = chunk ^ (row & 15).
-//     The DMA writes lane-linearly (hardware constraint) from a per-lane pre-swizzled SOURCE address; the
-//     ds_read_b128 of a 16-lane group then hits 16 distinct slots (rows distinct mod 16): conflict-free.
-//   * Work units: (pair, query split) units are dealt round-robin to the 8 XCDs (blockIdx & 7) and all anchor
-//     panels of a unit sit on ONE XCD, so a unit's query stream is fetched once per XCD and shared through
-//     that XCD's L2; several splits per pair keep the tail of the launch short.
+// Anchor-stationary kernel (C_pad in {32,64,128,256}): every wave keeps ITS 32 anchor rows in registers, the query stream goes
+// HBM/L2 -> LDS by LDS-DMA and LDS -> MFMA A operand by ds_read_b128.  The tile geometry, the k-permuted rows, the swizzled LDS image
+// and the (pair, split) work units are explained in match_tile.h, whose match_regb_walk is this loop as a template (K1r runs it).
 template <int CP>
 __global__ __launch_bounds__(MATCH_THREADS, 2) void match_f32_regb_kernel(
     const float *__restrict__ a_hat, const float *__restrict__ q_hat, int B, int cap_a, int cap_q,
@@ -427,7 +404,7 @@ int match_f32_flagged(const float *a_hat, const float *q_hat, int B, int C, int 
                       const int32_t *panel_flag, const uint8_t *row_flag, void *stream)
 {
     const int T = cap_a / MT;
-    const int groups = ((B + 7) / 8) * 8 * T;      // S = 1: one unit per pair
+    const int groups = regb_groups(B, T, 1);       // S = 1: one unit per pair, the same grid for either kernel
     hipStream_t st = as_stream(stream);
 #define LAUNCH_FLAGGED(CPV)                                                                                               \
     hipLaunchKernelGGL((match_f32_regb_kernel<CPV>), dim3(groups), dim3(MATCH_THREADS), 0, st, a_hat, q_hat, B, cap_a, cap_q, \
@@ -449,8 +426,8 @@ using namespace oryon;
 extern "C" size_t oryon_match_workspace_bytes(int B, int cap_a)
 {
     if (B <= 0 || cap_a <= 0) return 0;
-    const int S = pick_split(B, cap_a / MT);
-    return S == 1 ? 0 : (size_t)B * S * cap_a * (sizeof(float) + sizeof(int32_t));
+    SplitWs w;
+    return carve_split(nullptr, w, B, cap_a, pick_split(B, cap_a / MT));
 }
 
 extern "C" int oryon_match_f32(const float *a_hat, const float *q_hat, int B, int C, int cap_a, int cap_q,
@@ -462,16 +439,12 @@ extern "C" int oryon_match_f32(const float *a_hat, const float *q_hat, int B, in
     if (B == 0) return ORYON_OK;
     const int T = cap_a / MT;
     const int S = pick_split(B, T);
-    float *ws_dist = nullptr;
-    int32_t *ws_idx = nullptr;
-    if (S > 1) {
-        const size_t need = (size_t)B * S * cap_a * (sizeof(float) + sizeof(int32_t));
-        ORYON_CHECK_WORKSPACE("oryon_match_f32: ", workspace, workspace_bytes, need);
-        ws_dist = static_cast<float *>(workspace);
-        ws_idx = reinterpret_cast<int32_t *>(ws_dist + (size_t)B * S * cap_a);
-    }
-    int groups = ((B + 7) / 8) * 8 * T * S;                         // staged kernel: pairs dealt to XCDs
-    const int groups_regb = ((B * S + 7) / 8) * 8 * T;                // anchor-stationary kernel: (pair, split) units
+    SplitWs w;
+    const size_t need = carve_split(workspace, w, B, cap_a, S);
+    if (need) ORYON_CHECK_WORKSPACE("oryon_match_f32: ", workspace, workspace_bytes, need);
+    float *ws_dist = w.ws_dist;
+    int32_t *ws_idx = w.ws_idx;
+    const int groups = staged_groups(B, T, S), groups_regb = regb_groups(B, T, S);
     hipStream_t st = as_stream(stream);
 #define LAUNCH_REGB(CPV)                                                                                                  \
     hipLaunchKernelGGL((match_f32_regb_kernel<CPV>), dim3(groups_regb), dim3(MATCH_THREADS), 0, st, a_hat, q_hat, B, cap_a, cap_q, \

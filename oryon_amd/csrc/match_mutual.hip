@@ -24,18 +24,15 @@
 // monotone in `<` on all non-NaN floats; key = u << 32 | index orders lexicographically by (distance, index), which is what K1's
 // strict `<` in ascending index order computes.
 //
-// The tile loops, the LDS image and the LDS-DMA of the two kernels below are those of match_f32_regb_kernel and match_f32_kernel
-// (match.hip, where they are explained); what differs is the fold of a finished tile and the hand-over at the end.
+// The tile loops, the LDS image and the LDS-DMA of the two kernels below are the two walks of match_tile.h (where they are explained),
+// kept here as this file's own text: instantiated from the header the C_pad 32 kernel was slower.  What differs from K1
+// is the fold of a finished tile and the hand-over at the end.
 #include "common.h"
 #include "match_common.h"
+#include "match_tile.h"
 
 namespace oryon {
 
-constexpr int MT = ORYON_MATCH_TILE;
-constexpr int BK = 32;
-constexpr int LD = BK + 1;
-constexpr int MM_THREADS = 256;
-constexpr int TILE_FLOATS = MT * LD;
 constexpr unsigned long long KEY_NONE = ~0ull;       // above every key of a finite or infinite distance
 
 // the order-preserving image of a distance: u(x) < u(y) as unsigned <=> x < y as floats (no NaN, no -0.0)
@@ -94,7 +91,7 @@ __device__ __forceinline__ void rev_flush(unsigned long long *red, int rows, int
 
 // ------------------------------------------------------------------------------------------------ C_pad 32 / 64 / 128 / 256
 template <int CP>
-__global__ __launch_bounds__(MM_THREADS, 2) void match_mutual_regb_kernel(
+__global__ __launch_bounds__(MATCH_THREADS, 2) void match_mutual_regb_kernel(
     const float *__restrict__ a_hat, const float *__restrict__ q_hat, int B, int cap_a, int cap_q,
     const int32_t *__restrict__ n_a, const int32_t *__restrict__ n_q, float thr, int T, int S,
     float *__restrict__ min_dist, int32_t *__restrict__ argmin, uint8_t *__restrict__ valid,
@@ -111,7 +108,7 @@ __global__ __launch_bounds__(MM_THREADS, 2) void match_mutual_regb_kernel(
     constexpr int RG = NACC >= 4 ? 2 : 3;
     constexpr bool NARROW = KH < 64;
     constexpr int LPR = NARROW ? 1 : KH * 4 / 256;
-    static_assert(NACC * NGT == 32 && KP * NGT * 8 == CP && ROWS <= MM_THREADS, "tile geometry");
+    static_assert(NACC * NGT == 32 && KP * NGT * 8 == CP && ROWS <= MATCH_THREADS, "tile geometry");
     __shared__ __attribute__((aligned(256))) char smem[2 * TILE_BYTES];
     __shared__ unsigned long long red[2][ROWS];         // per-query minima of a tile over the workgroup's 128 anchors
 
@@ -291,7 +288,7 @@ __global__ __launch_bounds__(MM_THREADS, 2) void match_mutual_regb_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------ wider descriptors (LDS-staged)
-__global__ __launch_bounds__(MM_THREADS, 2) void match_mutual_staged_kernel(
+__global__ __launch_bounds__(MATCH_THREADS, 2) void match_mutual_staged_kernel(
     const float *__restrict__ a_hat, const float *__restrict__ q_hat, int B, int Cp, int cap_a, int cap_q,
     const int32_t *__restrict__ n_a, const int32_t *__restrict__ n_q, float thr, int T, int S,
     float *__restrict__ min_dist, int32_t *__restrict__ argmin, uint8_t *__restrict__ valid,
@@ -336,7 +333,7 @@ __global__ __launch_bounds__(MM_THREADS, 2) void match_mutual_staged_kernel(
         const float *ab = ap + kt * BK;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int f = t + MM_THREADS * i, row = f >> 3, c4 = f & 7;
+            const int f = t + MATCH_THREADS * i, row = f >> 3, c4 = f & 7;
             rq[i] = *reinterpret_cast<const float4 *>(qb + (size_t)row * Cp + c4 * 4);
             ra[i] = *reinterpret_cast<const float4 *>(ab + (size_t)row * Cp + c4 * 4);
         }
@@ -345,7 +342,7 @@ __global__ __launch_bounds__(MM_THREADS, 2) void match_mutual_staged_kernel(
         float *Qs = smem + buf * 2 * TILE_FLOATS, *As = Qs + TILE_FLOATS;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int f = t + MM_THREADS * i, row = f >> 3, c4 = f & 7;
+            const int f = t + MATCH_THREADS * i, row = f >> 3, c4 = f & 7;
             float *q = Qs + row * LD + c4 * 4, *a = As + row * LD + c4 * 4;
             q[0] = rq[i].x; q[1] = rq[i].y; q[2] = rq[i].z; q[3] = rq[i].w;
             a[0] = ra[i].x; a[1] = ra[i].y; a[2] = ra[i].z; a[3] = ra[i].w;
@@ -515,19 +512,14 @@ __global__ void match_mutual_join_kernel(const unsigned long long *__restrict__ 
     }
 }
 
-struct MutualWs {
+struct MutualWs : SplitWs {
     unsigned long long *keys;
-    float *ws_dist;
-    int32_t *ws_idx;
 };
 static size_t carve_mutual(void *base, MutualWs &w, int B, int cap_a, int cap_q, int S)
 {
     Carver carve(base);
-    const size_t split_rows = S > 1 ? (size_t)B * S * cap_a : 0;
     carve(w.keys, (size_t)B * cap_q);
-    carve(w.ws_dist, split_rows);
-    carve(w.ws_idx, split_rows);
-    return carve.end;
+    return carve_split(base, w, B, cap_a, S, carve.off);
 }
 
 }  // namespace oryon
@@ -561,17 +553,16 @@ extern "C" int oryon_match_mutual_f32(const float *a_hat, const float *q_hat, in
     ORYON_CHECK_WORKSPACE("oryon_match_mutual_f32: ", workspace, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     ORYON_CHECK_HIP(hipMemsetAsync(w.keys, 0xff, (size_t)B * cap_q * sizeof(unsigned long long), st));     // KEY_NONE
-    const int groups = ((B + 7) / 8) * 8 * T * S;                         // staged kernel: pairs dealt to XCDs
-    const int groups_regb = ((B * S + 7) / 8) * 8 * T;                    // anchor-stationary kernel: (pair, split) units
+    const int groups = staged_groups(B, T, S), groups_regb = regb_groups(B, T, S);
 #define LAUNCH_REGB(CPV)                                                                                                       \
-    hipLaunchKernelGGL((match_mutual_regb_kernel<CPV>), dim3(groups_regb), dim3(MM_THREADS), 0, st, a_hat, q_hat, B, cap_a, cap_q, \
+    hipLaunchKernelGGL((match_mutual_regb_kernel<CPV>), dim3(groups_regb), dim3(MATCH_THREADS), 0, st, a_hat, q_hat, B, cap_a, cap_q, \
                        n_a, n_q, threshold, T, S, min_dist, argmin, valid, w.ws_dist, w.ws_idx, w.keys)
     if (C == 32) LAUNCH_REGB(32);
     else if (C == 64) LAUNCH_REGB(64);
     else if (C == 128) LAUNCH_REGB(128);
     else if (C == 256) LAUNCH_REGB(256);
     else
-        hipLaunchKernelGGL(match_mutual_staged_kernel, dim3(groups), dim3(MM_THREADS), 0, st, a_hat, q_hat, B, C, cap_a, cap_q, n_a, n_q,
+        hipLaunchKernelGGL(match_mutual_staged_kernel, dim3(groups), dim3(MATCH_THREADS), 0, st, a_hat, q_hat, B, C, cap_a, cap_q, n_a, n_q,
                            threshold, T, S, min_dist, argmin, valid, w.ws_dist, w.ws_idx, w.keys);
 #undef LAUNCH_REGB
     ORYON_CHECK_LAUNCH();

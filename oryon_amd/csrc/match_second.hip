@@ -307,19 +307,6 @@ __global__ void match_second_merge_kernel(const float *__restrict__ ws_dist, con
     keep[o] = ratio_keep(gate, o, min_dist[o], ratio, d);
 }
 
-struct SecondWs {
-    float *ws_dist;
-    int32_t *ws_idx;
-};
-static size_t carve_second(void *base, SecondWs &w, int B, int cap_a, int S)
-{
-    Carver carve(base);
-    const size_t split_rows = S > 1 ? (size_t)B * S * cap_a : 0;
-    carve(w.ws_dist, split_rows);
-    carve(w.ws_idx, split_rows);
-    return carve.end;
-}
-
 }  // namespace oryon
 
 using namespace oryon;
@@ -327,8 +314,8 @@ using namespace oryon;
 extern "C" size_t oryon_match_second_workspace_bytes(int B, int cap_a)
 {
     if (B <= 0 || cap_a <= 0) return 0;
-    SecondWs w;
-    return carve_second(nullptr, w, B, cap_a, match_f32_split(B, cap_a / MT));
+    SplitWs w;
+    return carve_split(nullptr, w, B, cap_a, match_f32_split(B, cap_a / MT));
 }
 
 extern "C" int oryon_match_second_f32(const float *a_hat, const float *q_hat, int B, int C, int cap_a, int cap_q, const int32_t *n_a,
@@ -351,12 +338,11 @@ extern "C" int oryon_match_second_f32(const float *a_hat, const float *q_hat, in
     if (B == 0) return ORYON_OK;
     const int T = cap_a / MT;
     const int S = match_f32_split(B, T);
-    SecondWs w;
-    const size_t need = carve_second(workspace, w, B, cap_a, S);
+    SplitWs w;
+    const size_t need = carve_split(workspace, w, B, cap_a, S);
     if (need) ORYON_CHECK_WORKSPACE("oryon_match_second_f32: ", workspace, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
-    const int groups = ((B + 7) / 8) * 8 * T * S;                         // staged kernel: pairs dealt to XCDs
-    const int groups_regb = ((B * S + 7) / 8) * 8 * T;                    // anchor-stationary kernel: (pair, split) units
+    const int groups = staged_groups(B, T, S), groups_regb = regb_groups(B, T, S);
 #define LAUNCH_REGB(CPV)                                                                                                          \
     hipLaunchKernelGGL((match_second_regb_kernel<CPV>), dim3(groups_regb), dim3(MATCH_THREADS), 0, st, a_hat, q_hat, B, cap_a, cap_q, \
                        n_a, n_q, roi_q, roi_stride_q, W_q, radius, min_dist, argmin, gate, ratio, T, S, second_dist, second_argmin,  \

@@ -1,8 +1,8 @@
 // The exact matcher's two all-pairs tile walks as templates over what is done with a finished tile: how the query rows stream past a
 // workgroup's 128 anchor columns and through the fp32 MFMA.  They are match_f32_kernel's and match_f32_regb_kernel's loops (match.hip)
-// statement for statement, so the distances have K1's bits; K1r (match_second.hip) is built on them.  K1 itself still carries its own
-// text of the loops: instantiating it from here with its fold changed its register allocation (the C_pad 32 instantiation went from
-// 206 VGPRs to 256 and 84 bytes of scratch), and K1 is not to change under a kernel that only reads its results.
+// statement for statement, so the distances have K1's bits; K1r (match_second.hip) is built on them.  K1 and K1m (match_mutual.hip)
+// still carry their own text of the loops: instantiated from here, each was 0.3 - 0.9 % slower at C_pad 32 (measured).
+// The formulation, the geometry, the LDS image and the LDS-DMA are explained here, once, for all three.
 // What a kernel does with a FINISHED tile of dot products - its fold - is the caller's:
 //
 //     struct Fold {
@@ -11,8 +11,14 @@
 //         void tile(acc, int qt);     // all k of query tile qt are in acc: fold it and leave acc zero
 //     };
 //
-// A fold that needs nothing but the accumulators leaves prefetch / publish empty.  The walks hold barriers: every thread of the workgroup calls them with the same span.
-// The geometry, the LDS image and the LDS-DMA are explained where they were first written, in match.hip.
+// A fold that needs nothing but the accumulators leaves prefetch / publish empty.  The walks hold barriers: every thread of the
+// workgroup calls them with the same span.
+//
+// Formulation:  S = Q^ * A^T  (rows = query descriptors, columns = anchor descriptors), both operands already gathered + normalised into
+// k-contiguous [N, C] rows by K0.  One workgroup owns a 128-anchor column panel and streams the query rows past it.  In the C/D layout
+// of v_mfma_f32_32x32x2_f32 a lane owns ONE column (= one anchor) and 16 rows (= 16 queries), so a running reduction over queries is
+// lane-local: no cross-lane traffic until the very end (lane l <-> l+32; in the staged walk also the two waves that share columns).
+// The f32-input MFMA is an exact k-ordered fmaf chain, and both walks feed it k in the natural order.
 #pragma once
 #include "common.h"
 #include "match_common.h"
@@ -37,7 +43,30 @@ __device__ __forceinline__ TileSpan split_span(int nq, int rows, int S, int spli
     return {qt_begin, (qt_begin + qt_per < nqt) ? qt_begin + qt_per : nqt};
 }
 
+// launch grids of a scan with T anchor panels per pair and S query splits; blocks are dealt to the 8 XCDs round-robin (blockIdx & 7).
+// Anchor-stationary walk: (pair, split) units are dealt to the XCDs and all T anchor panels of a unit sit on ONE XCD, so a unit's query
+// stream is fetched once per XCD and shared through that XCD's L2; several splits per pair keep the tail of the launch short.
+inline int regb_groups(int B, int T, int S) { return ((B * S + 7) / 8) * 8 * T; }
+// staged walk: XCD x gets the pairs {x, x+8, ...}, which keeps every panel and split of a pair on one L2
+inline int staged_groups(int B, int T, int S) { return ((B + 7) / 8) * 8 * T * S; }
+
+// the per-split (distance, index) rows [B, S, cap_a] that a split scan leaves for its merge, carved from base; -> bytes (0 when S == 1)
+struct SplitWs {
+    float *ws_dist;
+    int32_t *ws_idx;
+};
+inline size_t carve_split(void *base, SplitWs &w, int B, int cap_a, int S, size_t start = 0)      // start: what the caller carved in front
+{
+    Carver carve(base, start);
+    const size_t split_rows = S > 1 ? (size_t)B * S * cap_a : 0;
+    carve(w.ws_dist, split_rows);
+    carve(w.ws_idx, split_rows);
+    return carve.end;
+}
+
 // ------------------------------------------------------------------------------------------------ wide descriptors (LDS-staged)
+// Operands that do not fit the register file (e.g. C = 512): both are staged through LDS in k-tiles of 32, 128 query rows x 128 anchor
+// rows per step.
 // smem: 4 * TILE_FLOATS floats, [buf][Q|A][128][33].  ap: the panel's first anchor row, qp: the pair's first query row.
 // Wave grid 2 (query halves, wm) x 2 (anchor halves, wn): acc[mi][ni] is the block of query rows wm*64 + mi*32.. and anchor columns
 // wn*64 + ni*32..
@@ -155,7 +184,17 @@ __device__ __forceinline__ void staged_columns(float *smem, float (&best)[2], in
 }
 
 // ------------------------------------------------------------------------------------------------ C_pad 32 / 64 / 128 / 256
-// Anchor-stationary: the wave's 32 anchor rows stay in registers, the query stream goes HBM/L2 -> LDS by LDS-DMA (match.hip).
+// Anchor-stationary.  Every wave keeps ITS 32 anchor rows - the MFMA B operand for the whole K range - in registers for the life of the
+// workgroup, so the only thing that moves is the query stream:  HBM/L2 -> LDS by LDS-DMA (global_load_lds, 16 B per lane, no staging
+// VGPRs), LDS -> MFMA A operand by ds_read_b128.
+//   * LDS tile = 32 KB = ROWS query rows x KH floats, double-buffered (64 KB -> 2 workgroups per CU); ROWS = 64 and KH = 128 for
+//     C_pad >= 128 (C_pad = 256 takes two k-parts per query tile).  A wave always runs 128 MFMAs (8192 cycles) per barrier, on
+//     NACC = ROWS/32 >= 2 accumulators issued round-robin so that back-to-back MFMAs are independent.
+//   * The k-permuted row layout written by K0 (position 8g+4h+j holds k = 8g+2j+h) makes one 16-byte access deliver what lane (i, h)
+//     feeds to four consecutive MFMA steps, while the accumulation order stays the natural k order (bit-exact vs the oracle).
+//   * LDS image: 256-byte lines, 16-byte slots XOR-swizzled with the row index: slot = chunk ^ (row & 15).  The DMA writes lane-linearly
+//     (hardware constraint) from a per-lane pre-swizzled SOURCE address; the ds_read_b128 of a 16-lane group then hits 16 distinct slots
+//     (rows distinct mod 16): conflict-free.
 template <int CP> struct RegbGeom {
     static constexpr int RB = CP * 4;                          // source row bytes
     static constexpr int ROWS = CP >= 128 ? 64 : 8192 / CP;    // query rows per LDS tile
