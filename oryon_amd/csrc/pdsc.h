@@ -70,10 +70,10 @@ struct PdscWorkspace {
     int32_t *n_seeds; // [B]
     int32_t *knn;     // [B,S_cap,k]
     float *Mmat;      // [B,S_cap,k,k]
-    float *seed_w;    // [B,S_cap,k]
+    float *seed_w;    // [B,S_cap,k] UNUSED: carved and never read (its bytes are part of the pinned workspace sizes)
     float *seed_dist; // [B,S_cap,n_cap] feature distances seed -> every row
-    float *v_hist;    // [B,S_cap,16,64] power-iteration iterates
-    int32_t *close_hist;  // [B,S_cap,16] per-iteration closeness flags
+    float *v_hist;    // [B,S_cap,PDSC_MAX_IT,PDSC_MAX_K] power-iteration iterates (below)
+    int32_t *close_hist;  // [B,S_cap,PDSC_MAX_IT] per-iteration closeness flags
     float *seed_T;    // [B,S_cap,16]
     float *fitness;   // [B,S_cap]
     int32_t *best;    // [B]
@@ -111,8 +111,10 @@ int pdsc_run_refine(const PdscModel &M, const float *src, const float *tgt, cons
                     hipStream_t st);
 
 // the stages behind a (neighbour list [B,S_cap,k], matrix [B,S_cap,k,k]) pair per seed, callable on their own (spectral.hip):
-// power iteration + weighted Kabsch / fitness + first-argmax (v_hist [B,S_cap,16,64], close_hist [B,S_cap,16]), and the refinement
-// with the caller's tau
+// power iteration + weighted Kabsch / fitness + first-argmax, and the refinement with the caller's tau.  The tail's contract:
+// k <= PDSC_MAX_K (one lane per neighbour), at most PDSC_MAX_IT iterates are kept (a caller refuses more, the tail never runs more),
+// v_hist is [B,S_cap,PDSC_MAX_IT,PDSC_MAX_K] and close_hist [B,S_cap,PDSC_MAX_IT].
+constexpr int PDSC_MAX_K = 64, PDSC_MAX_IT = 16;
 int pdsc_run_tail(const float *src, const float *tgt, const int32_t *n_rows, const int32_t *n_seeds, int B, int n_cap, int S_cap, int k,
                   int num_iterations, float inlier_thr, const int32_t *knn, const float *Mmat, float *v_hist, int32_t *close_hist,
                   float *seed_T, float *fitness, int32_t *best, float *T_best, uint8_t *labels, hipStream_t st);

@@ -17,6 +17,116 @@
 
 namespace oryon {
 
+// ------------------------------------------------------------------------------------------------ shared pieces
+// k' = min(k, n - 1): a row has no more neighbours than the other rows of its pair (common.py:68)
+__device__ __forceinline__ int pdsc_k_eff(int k_cfg, int n) { return k_cfg < n - 1 ? k_cfg : n - 1; }
+
+// size of the LDS sorts: the power of two >= n, never below the 256 threads of the sorting workgroup
+__host__ __device__ __forceinline__ int pdsc_sort_size(int n)
+{
+    int P = 256;
+    while (P < n) P <<= 1;
+    return P;
+}
+
+// |T s - t| of one correspondence s = (x, y, z) -> t = (bx, by, bz); T: the first three rows of a row-major 4 x 4
+__device__ __forceinline__ float pdsc_residual(const float *T, float x, float y, float z, float bx, float by, float bz)
+{
+    const float dx = (T[0] * x + T[1] * y + T[2] * z + T[3]) - bx;
+    const float dy = (T[4] * x + T[5] * y + T[6] * z + T[7]) - by;
+    const float dz = (T[8] * x + T[9] * y + T[10] * z + T[11]) - bz;
+    return sqrt_rn(dx * dx + dy * dy + dz * dz);
+}
+
+// XCD-aware block map of the (seed, pair) kernels: the seeds of one pair gather rows of the same feature matrix (256 KB at n = 500,
+// C = 128), so they run on one XCD (linear block id mod 8) and share it through that L2.  gridDim.x is the seed capacity, gridDim.y the
+// pair count rounded up to a multiple of 8: the caller drops b >= the pair count.
+__device__ __forceinline__ void pdsc_seed_block(int &b, int &s)
+{
+    const int lin = blockIdx.x + gridDim.x * blockIdx.y;
+    b = (lin / 8 / (int)gridDim.x) * 8 + (lin & 7);
+    s = (lin / 8) % (int)gridDim.x;
+}
+
+// Bitonic sort of P (key, index) pairs in LDS by a 256-thread workgroup (P a power of two >= 256; the arrays are written and a barrier
+// has passed).  DESC: descending by key, else ascending; ties by ascending index either way (what a stable sort gives).  Every
+// comparison with a NaN key is false, so a NaN key never swaps.  Returns behind the last stage's barrier.
+template <bool DESC>
+__device__ __forceinline__ void pdsc_bitonic_sort(float *key, int *order, int P, int t)
+{
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int e = t; e < P / 2; e += 256) {
+                const int lo = 2 * e - (e & (stride - 1)), hi = lo + stride;      // lo: index with bit `stride` clear
+                const bool up = (lo & size) == 0;
+                const float kl = key[lo], kh = key[hi];
+                const int il = order[lo], ih = order[hi];
+                const bool hi_first = (DESC ? kh > kl : kl > kh) || (kh == kl && ih < il);      // hi belongs before lo
+                if (hi_first == up) {
+                    key[lo] = kh; key[hi] = kl;
+                    order[lo] = ih; order[hi] = il;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// K7a, the part behind a seed's neighbour list kidx[k] (in LDS, visible to the workgroup): the neighbours' feature rows and
+// coordinates go to LDS (kf [k][C + 4]: 16-byte aligned rows for the b128 reads below; kc [k][6]), the list to knn_out [slot][k_cfg], and
+//   M_ab = clamp(1 - (1 - f_a.f_b)/sigma^2, 0) * clamp(1 - (|s_a-s_b| - |t_a-t_b|)^2/sigma_d^2, 0),  M_aa = 0
+// to M_out [slot][k_cfg][k_cfg].  The matrix is symmetric: one thread per unordered pair (a < c2), both entries written.  F: the pair's
+// feature rows (C a multiple of 4, rows 16-byte aligned); row0: the pair's first row in src / tgt; slot = b S_cap + s; nt threads,
+// this one is t.
+__device__ __forceinline__ void pdsc_compat_matrix(const float *__restrict__ F, const float *__restrict__ src, const float *__restrict__ tgt,
+                                                   size_t row0, int C, const int *kidx, float *kf, float *kc, int k, int k_cfg,
+                                                   float inv_sigma2, float inv_sigma_d2, size_t slot, int32_t *__restrict__ knn_out,
+                                                   float *__restrict__ M_out, int t, int nt)
+{
+    for (int e = t; e < k * (C / 4); e += nt) {
+        const int a = e / (C / 4), c4 = e % (C / 4);
+        *reinterpret_cast<float4 *>(kf + a * (C + 4) + 4 * c4) = reinterpret_cast<const float4 *>(F + (size_t)kidx[a] * C)[c4];
+    }
+    for (int e = t; e < k * 3; e += nt) {
+        const int a = e / 3, d = e % 3;
+        kc[a * 6 + d] = src[(row0 + kidx[a]) * 3 + d];
+        kc[a * 6 + 3 + d] = tgt[(row0 + kidx[a]) * 3 + d];
+    }
+    if (t < k) knn_out[slot * k_cfg + t] = kidx[t];
+    __syncthreads();
+    float *Mo = M_out + slot * k_cfg * k_cfg;
+    for (int e = t; e < k; e += nt) Mo[e * k_cfg + e] = 0.0f;
+    const int n_pairs = k * (k - 1) / 2;
+    for (int e = t; e < n_pairs; e += nt) {
+        // e -> (a, c2), a < c2, row-major over the strict upper triangle
+        int a = (int)((2.0f * k - 1.0f - sqrt_rn((2.0f * k - 1.0f) * (2.0f * k - 1.0f) - 8.0f * (float)e)) * 0.5f);
+        while (a > 0 && a * (2 * k - a - 1) / 2 > e) --a;
+        while ((a + 1) * (2 * k - a - 2) / 2 <= e) ++a;
+        const int c2 = a + 1 + (e - a * (2 * k - a - 1) / 2);
+        float dot = 0.0f;
+        const float4 *fa = reinterpret_cast<const float4 *>(kf + a * (C + 4)), *fb = reinterpret_cast<const float4 *>(kf + c2 * (C + 4));
+#pragma unroll 8
+        for (int c4 = 0; c4 < C / 4; ++c4) {
+            const float4 x = fa[c4], y = fb[c4];
+            dot = fmaf(x.x, y.x, dot);
+            dot = fmaf(x.y, y.y, dot);
+            dot = fmaf(x.z, y.z, dot);
+            dot = fmaf(x.w, y.w, dot);
+        }
+        float fm = 1.0f - (1.0f - dot) * inv_sigma2;
+        fm = fm > 0.0f ? fm : 0.0f;
+        const float *pa = kc + a * 6, *pb = kc + c2 * 6;
+        const float dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
+        const float ex = pa[3] - pb[3], ey = pa[4] - pb[4], ez = pa[5] - pb[5];
+        const float df = sqrt_rn(dx * dx + dy * dy + dz * dz) - sqrt_rn(ex * ex + ey * ey + ez * ez);
+        float smv = 1.0f - df * df * inv_sigma_d2;
+        smv = smv > 0.0f ? smv : 0.0f;
+        const float v = fm * smv;
+        Mo[a * k_cfg + c2] = v;
+        Mo[c2 * k_cfg + a] = v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ K5
 // is_local_max_i = AND_j (score_i >= score_j  OR  |s_i - s_j| >= R);  seeds = first S of the descending
 // order of score * is_local_max (ties by ascending index).
@@ -66,8 +176,7 @@ __global__ __launch_bounds__(256) void pdsc_seed_rank_kernel(const float *__rest
     const int n = n_rows[b];
     int S = (int)((double)n * (double)ratio);
     S = S < S_cap ? S : S_cap;
-    int P = 256;
-    while (P < n) P <<= 1;
+    const int P = pdsc_sort_size(n);
     float *key = sm;                                   // [P]
     int *order = reinterpret_cast<int *>(sm + P);       // [P]
     for (int j = t; j < P; j += 256) {
@@ -75,23 +184,7 @@ __global__ __launch_bounds__(256) void pdsc_seed_rank_kernel(const float *__rest
         order[j] = j;
     }
     __syncthreads();
-    // descending by key, ties by ascending index (what a stable descending sort gives)
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int e = t; e < P / 2; e += 256) {
-                const int lo = 2 * e - (e & (stride - 1)), hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const float kl = key[lo], kh = key[hi];
-                const int il = order[lo], ih = order[hi];
-                const bool hi_first = (kh > kl) || (kh == kl && ih < il);      // hi belongs before lo
-                if (hi_first == up) {
-                    key[lo] = kh; key[hi] = kl;
-                    order[lo] = ih; order[hi] = il;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    pdsc_bitonic_sort<true>(key, order, P, t);         // descending by key, ties by ascending index
     for (int r = t; r < S; r += 256) seeds[(size_t)b * S_cap + r] = order[r];
     if (t == 0) n_seeds[b] = S;
 }
@@ -197,9 +290,7 @@ __global__ __launch_bounds__(1024) void pdsc_seeds_fused_kernel(const float *__r
 }
 
 // ------------------------------------------------------------------------------------------------ K6 + K7a
-// One workgroup per (seed, pair): feature-space kNN of the seed row, then the k x k compatibility matrix
-//   M_ab = clamp(1 - (1 - f_a.f_b)/sigma^2, 0) * clamp(1 - (|s_a-s_b| - |t_a-t_b|)^2/sigma_d^2, 0),  M_aa = 0.
-constexpr int KNN_MAX_K = 64;
+// One workgroup per (seed, pair): feature-space kNN of the seed row, then the k x k compatibility matrix (pdsc_compat_matrix above).
 // 2 - 2 f_seed.f_j for every (seed, row) of a pair, with the feature matrix read once per 64-row block instead of once per seed:
 // grid (n_cap/64, B), 4 lanes per row (each a quarter of the seeds), the row's C values in registers, seed features in LDS.
 // The dot product is the same k-ordered fmaf chain the per-seed kernel used.
@@ -305,21 +396,18 @@ __global__ __launch_bounds__(256) void pdsc_knn_matrix_kernel(const float *__res
                                                                const float *__restrict__ dist_pre /* [B,S_cap,n_cap] or NULL */, int n_batch)
 {
     extern __shared__ float sm[];
-    // XCD-aware block map: the seeds of one pair gather rows of the same feature matrix (256 KB at n = 500, C = 128), so they run on one XCD
-    // (linear block id mod 8) and share it through that L2.  gridDim.y is the pair count rounded up to a multiple of 8.
-    const int lin = blockIdx.x + gridDim.x * blockIdx.y;
-    const int b = (lin / 8 / (int)gridDim.x) * 8 + (lin & 7), s = (lin / 8) % (int)gridDim.x;
+    int b, s;
+    pdsc_seed_block(b, s);
     if (b >= n_batch || s >= n_seeds[b]) return;
     const int n = n_rows[b];
-    const int k = k_cfg < n - 1 ? k_cfg : n - 1;
-    int P = 256;                            // sort size: power of two >= n
-    while (P < n) P <<= 1;
+    const int k = pdsc_k_eff(k_cfg, n);
+    const int P = pdsc_sort_size(n);
     float *dist = sm;                       // [P] sort keys
     int *order = reinterpret_cast<int *>(dist + P);           // [P] row indices, sorted along with the keys
     float *fs = reinterpret_cast<float *>(order + P);          // [C] seed feature
-    float *kf = fs + C;                     // [KNN_MAX_K][C+4]: 16-byte aligned rows for the b128 reads of the matrix phase
-    float *kc = kf + KNN_MAX_K * (C + 4);   // [KNN_MAX_K][6]
-    int *kidx = reinterpret_cast<int *>(kc + KNN_MAX_K * 6);  // [KNN_MAX_K]
+    float *kf = fs + C;                     // [PDSC_MAX_K][C+4]
+    float *kc = kf + PDSC_MAX_K * (C + 4);  // [PDSC_MAX_K][6]
+    int *kidx = reinterpret_cast<int *>(kc + PDSC_MAX_K * 6); // [PDSC_MAX_K]
     const int t = threadIdx.x;
     const int seed_row = seeds[(size_t)b * S_cap + s];
     const float *F = feat_n + (size_t)b * n_cap * C;
@@ -354,202 +442,13 @@ __global__ __launch_bounds__(256) void pdsc_knn_matrix_kernel(const float *__res
         order[j] = j;
     }
     __syncthreads();
-    // ascending bitonic sort of (distance, row index): ties resolve to the smaller index; rank 0 is dropped, ranks 1..k are the
-    // neighbours (common.py:68)
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int e = t; e < P / 2; e += 256) {
-                const int lo = 2 * e - (e & (stride - 1));          // index with bit `stride` clear
-                const int hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const float dl = dist[lo], dh = dist[hi];
-                const int il = order[lo], ih = order[hi];
-                const bool lo_gt = (dl > dh) || (dl == dh && il > ih);
-                if (lo_gt == up) {
-                    dist[lo] = dh; dist[hi] = dl;
-                    order[lo] = ih; order[hi] = il;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    // ascending by (distance, row index): ties resolve to the smaller index; rank 0 is dropped, ranks 1..k are the neighbours
+    // (common.py:68)
+    pdsc_bitonic_sort<false>(dist, order, P, t);
     if (t < k) kidx[t] = order[t + 1];
     __syncthreads();
-    for (int e = t; e < k * C; e += 256) {
-        const int a = e / C, c = e % C;
-        kf[a * (C + 4) + c] = F[(size_t)kidx[a] * C + c];
-    }
-    for (int e = t; e < k * 3; e += 256) {
-        const int a = e / 3, d = e % 3;
-        kc[a * 6 + d] = src[((size_t)b * n_cap + kidx[a]) * 3 + d];
-        kc[a * 6 + 3 + d] = tgt[((size_t)b * n_cap + kidx[a]) * 3 + d];
-    }
-    if (t < k) knn_out[((size_t)b * S_cap + s) * k_cfg + t] = kidx[t];
-    __syncthreads();
-    float *Mo = M_out + ((size_t)b * S_cap + s) * k_cfg * k_cfg;
-    // the matrix is symmetric: one thread per unordered pair (a < c2), both entries written; the diagonal is zero
-    for (int e = t; e < k; e += 256) Mo[e * k_cfg + e] = 0.0f;
-    const int n_pairs = k * (k - 1) / 2;
-    for (int e = t; e < n_pairs; e += 256) {
-        // e -> (a, c2), a < c2, row-major over the strict upper triangle
-        int a = (int)((2.0f * k - 1.0f - sqrt_rn((2.0f * k - 1.0f) * (2.0f * k - 1.0f) - 8.0f * (float)e)) * 0.5f);
-        while (a > 0 && a * (2 * k - a - 1) / 2 > e) --a;
-        while ((a + 1) * (2 * k - a - 2) / 2 <= e) ++a;
-        const int c2 = a + 1 + (e - a * (2 * k - a - 1) / 2);
-        float dot = 0.0f;
-        const float4 *fa = reinterpret_cast<const float4 *>(kf + a * (C + 4)), *fb = reinterpret_cast<const float4 *>(kf + c2 * (C + 4));
-        for (int c4 = 0; c4 < C / 4; ++c4) {
-            const float4 x = fa[c4], y = fb[c4];
-            dot = fmaf(x.x, y.x, dot);
-            dot = fmaf(x.y, y.y, dot);
-            dot = fmaf(x.z, y.z, dot);
-            dot = fmaf(x.w, y.w, dot);
-        }
-        float fm = 1.0f - (1.0f - dot) * inv_sigma2;
-        fm = fm > 0.0f ? fm : 0.0f;
-        const float *pa = kc + a * 6, *pb = kc + c2 * 6;
-        const float dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
-        const float ex = pa[3] - pb[3], ey = pa[4] - pb[4], ez = pa[5] - pb[5];
-        const float df = sqrt_rn(dx * dx + dy * dy + dz * dz) - sqrt_rn(ex * ex + ey * ey + ez * ez);
-        float smv = 1.0f - df * df * inv_sigma_d2;
-        smv = smv > 0.0f ? smv : 0.0f;
-        const float v = fm * smv;
-        Mo[a * k_cfg + c2] = v;
-        Mo[c2 * k_cfg + a] = v;
-    }
-}
-
-// The same kNN + compatibility matrix with ONE WAVE per (seed, pair) and no workgroup barrier (round 3; n_cap <= 64 R, distances from
-// pdsc_seed_dist_kernel): the 256-thread kernel above spends its time in the 45 barrier-separated stages of a 512-element bitonic sort of
-// which only ranks 1..k (k = 40) are used (100 us per 64 registrations, 219 us outliers).  Here a lane holds R distances as order-preserving
-// integer keys, sorts its own R (stable odd-even transposition in registers: ties keep the smaller row index first), and the wave then
-// extracts the k + 1 smallest (key, row) pairs one by one: minimum over the lanes' heads (two 6-step xor reductions: key, then the smallest
-// row among the lanes that hold it), the winning lane pops its head.  Same order as the full sort - ascending distance, ties by row index -
-// hence the same neighbours, the same matrix, bit for bit.  The neighbour rows go to LDS (22 KB per wave: 7 waves per CU) for the matrix phase.
-// MEASURED: 91.5 us against 100 us - the kernel is bound by its instruction count (3200 waves x ~7.5 k VALU instructions over 1024 SIMDs:
-// the 780 k-ordered 128-term dot products of the matrix phase and the 41 extraction rounds), not by the barriers; ORYON_PDSC_KNN_WAVE=1
-// selects it, the tests run both.
-// wave-wide minimum on the DPP data path (row shifts inside the 16-lane rows, then the two row broadcasts gfx9 has), result read from lane 63:
-// ~10 dependent VALU instructions; the same reduction written with __shfl_xor is six dependent ds_bpermute round trips (the first version of
-// this kernel, latency-bound on them, was no faster than the sort it replaces)
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
-{
-#define ORYON_DPP_MIN(ctrl, rmask)                                                                                              \
-    {                                                                                                                           \
-        const unsigned o = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, ctrl, rmask, 0xf, false);                      \
-        v = o < v ? o : v;                                                                                                      \
-    }
-    ORYON_DPP_MIN(0x111, 0xf)      // row_shr:1
-    ORYON_DPP_MIN(0x112, 0xf)      // row_shr:2
-    ORYON_DPP_MIN(0x114, 0xf)      // row_shr:4
-    ORYON_DPP_MIN(0x118, 0xf)      // row_shr:8   -> lane 15 of every row holds the row's minimum
-    ORYON_DPP_MIN(0x142, 0xa)      // row_bcast:15 into rows 1 and 3
-    ORYON_DPP_MIN(0x143, 0xc)      // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave's minimum
-#undef ORYON_DPP_MIN
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-template <int C, int R>
-__global__ __launch_bounds__(64) void pdsc_knn_wave_kernel(const float *__restrict__ feat_n, const float *__restrict__ src,
-                                                            const float *__restrict__ tgt, const int32_t *__restrict__ n_rows, int n_cap,
-                                                            const int32_t *__restrict__ n_seeds, int S_cap, int k_cfg, float inv_sigma2,
-                                                            float inv_sigma_d2, int32_t *__restrict__ knn_out, float *__restrict__ M_out,
-                                                            const float *__restrict__ dist_pre /* [B,S_cap,n_cap] */, int n_batch)
-{
-    extern __shared__ float sm[];
-    const int lin = blockIdx.x + gridDim.x * blockIdx.y;
-    const int b = (lin / 8 / (int)gridDim.x) * 8 + (lin & 7), s = (lin / 8) % (int)gridDim.x;
-    if (b >= n_batch || s >= n_seeds[b]) return;
-    const int n = n_rows[b];
-    const int k = k_cfg < n - 1 ? k_cfg : n - 1;
-    float *kf = sm;                               // [k_cfg][C + 4]
-    float *kc = kf + k_cfg * (C + 4);             // [k_cfg][6]
-    const int lane = threadIdx.x;
-    const float *F = feat_n + (size_t)b * n_cap * C;
-    const float *dp = dist_pre + ((size_t)b * S_cap + s) * n_cap;
-    // order-preserving keys (no -0.0 / NaN among 2 - 2 dot); absent rows: the largest key
-    unsigned key[R];
-    int rr[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int j = lane + 64 * r;
-        unsigned kx = 0xffffffffu;
-        if (j < n) {
-            const unsigned bits = __float_as_uint(dp[j]);
-            kx = (bits >> 31) ? ~bits : (bits | 0x80000000u);
-        }
-        key[r] = kx;
-        rr[r] = r;
-    }
-    // the lane's own R entries, ascending, stable (strict >): equal keys keep ascending row order
-#pragma unroll
-    for (int pass = 0; pass < R; ++pass) {
-#pragma unroll
-        for (int r = pass & 1; r + 1 < R; r += 2) {
-            const bool sw = key[r] > key[r + 1];
-            const unsigned ka = key[r], kb = key[r + 1];
-            const int ra = rr[r], rb = rr[r + 1];
-            key[r] = sw ? kb : ka; key[r + 1] = sw ? ka : kb;
-            rr[r] = sw ? rb : ra;  rr[r + 1] = sw ? ra : rb;
-        }
-    }
-    int mine = 0;                                 // lane t holds neighbour t (rank t + 1 of the order)
-    for (int t = 0; t <= k; ++t) {
-        const unsigned mk = wave_min_u32(key[0]);
-        const unsigned cand = key[0] == mk ? (unsigned)(lane + 64 * rr[0]) : 0xffffffffu;
-        const unsigned mi = wave_min_u32(cand);
-        if (lane == (int)(mi & 63u)) {
-#pragma unroll
-            for (int r = 0; r + 1 < R; ++r) { key[r] = key[r + 1]; rr[r] = rr[r + 1]; }
-            key[R - 1] = 0xffffffffu;
-        }
-        if (t >= 1 && lane == t - 1) mine = (int)mi;
-    }
-    if (lane < k) knn_out[((size_t)b * S_cap + s) * k_cfg + lane] = mine;
-    // neighbour features / coordinates -> LDS
-    static_assert(C == 128, "two channels per lane");
-    for (int a = 0; a < k; ++a) {
-        const int row = __shfl(mine, a);
-        const float2 v = reinterpret_cast<const float2 *>(F + (size_t)row * C)[lane];
-        *reinterpret_cast<float2 *>(kf + a * (C + 4) + 2 * lane) = v;
-    }
-    if (lane < k) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            kc[lane * 6 + d] = src[((size_t)b * n_cap + mine) * 3 + d];
-            kc[lane * 6 + 3 + d] = tgt[((size_t)b * n_cap + mine) * 3 + d];
-        }
-    }
-    __syncthreads();
-    float *Mo = M_out + ((size_t)b * S_cap + s) * k_cfg * k_cfg;
-    for (int e = lane; e < k; e += 64) Mo[e * k_cfg + e] = 0.0f;
-    const int n_pairs = k * (k - 1) / 2;
-    for (int e = lane; e < n_pairs; e += 64) {
-        int a = (int)((2.0f * k - 1.0f - sqrt_rn((2.0f * k - 1.0f) * (2.0f * k - 1.0f) - 8.0f * (float)e)) * 0.5f);
-        while (a > 0 && a * (2 * k - a - 1) / 2 > e) --a;
-        while ((a + 1) * (2 * k - a - 2) / 2 <= e) ++a;
-        const int c2 = a + 1 + (e - a * (2 * k - a - 1) / 2);
-        float dot = 0.0f;
-        const float4 *fa = reinterpret_cast<const float4 *>(kf + a * (C + 4)), *fb = reinterpret_cast<const float4 *>(kf + c2 * (C + 4));
-        for (int c4 = 0; c4 < C / 4; ++c4) {
-            const float4 x = fa[c4], y = fb[c4];
-            dot = fmaf(x.x, y.x, dot);
-            dot = fmaf(x.y, y.y, dot);
-            dot = fmaf(x.z, y.z, dot);
-            dot = fmaf(x.w, y.w, dot);
-        }
-        float fm = 1.0f - (1.0f - dot) * inv_sigma2;
-        fm = fm > 0.0f ? fm : 0.0f;
-        const float *pa = kc + a * 6, *pb = kc + c2 * 6;
-        const float dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
-        const float ex = pa[3] - pb[3], ey = pa[4] - pb[4], ez = pa[5] - pb[5];
-        const float df = sqrt_rn(dx * dx + dy * dy + dz * dz) - sqrt_rn(ex * ex + ey * ey + ez * ez);
-        float smv = 1.0f - df * df * inv_sigma_d2;
-        smv = smv > 0.0f ? smv : 0.0f;
-        const float v = fm * smv;
-        Mo[a * k_cfg + c2] = v;
-        Mo[c2 * k_cfg + a] = v;
-    }
+    pdsc_compat_matrix(F, src, tgt, (size_t)b * n_cap, C, kidx, kf, kc, k, k_cfg, inv_sigma2, inv_sigma_d2, (size_t)b * S_cap + s, knn_out,
+                       M_out, t, 256);
 }
 
 // ------------------------------------------------------------------------------------------------ K7b + K8 + K9
@@ -561,7 +460,6 @@ __global__ __launch_bounds__(64) void pdsc_knn_wave_kernel(const float *__restri
 //            fitness over all n correspondences
 //   select   one workgroup per pair: first-argmax over the seeds, best transform, labels
 // Arithmetic per seed is unchanged from the single-workgroup version (seeds only interact through the stopping iteration).
-constexpr int HYP_MAX_IT = 16;
 __global__ __launch_bounds__(64) void pdsc_power_kernel(const int32_t *__restrict__ n_rows, const int32_t *__restrict__ n_seeds,
                                                          int S_cap, int k_cfg, int num_iterations, const float *__restrict__ Mmat,
                                                          float *__restrict__ v_hist /*[B,S_cap,it,64]*/,
@@ -570,19 +468,19 @@ __global__ __launch_bounds__(64) void pdsc_power_kernel(const int32_t *__restric
     const int b = blockIdx.y, s = blockIdx.x, lane = threadIdx.x;
     if (s >= n_seeds[b]) return;
     const int n = n_rows[b];
-    const int k = k_cfg < n - 1 ? k_cfg : n - 1;
-    __shared__ float v_sh[KNN_MAX_K];
-    float mrow[KNN_MAX_K];
+    const int k = pdsc_k_eff(k_cfg, n);
+    __shared__ float v_sh[PDSC_MAX_K];
+    float mrow[PDSC_MAX_K];
     const float *Ms = Mmat + ((size_t)b * S_cap + s) * k_cfg * k_cfg;
 #pragma unroll
-    for (int c = 0; c < KNN_MAX_K; ++c) mrow[c] = (lane < k && c < k) ? Ms[lane * k_cfg + c] : 0.0f;
+    for (int c = 0; c < PDSC_MAX_K; ++c) mrow[c] = (lane < k && c < k) ? Ms[lane * k_cfg + c] : 0.0f;
     float vl = 1.0f;
     for (int it = 0; it < num_iterations; ++it) {
         v_sh[lane] = vl;
         __syncthreads();
         float u = 0.0f;
 #pragma unroll
-        for (int c = 0; c < KNN_MAX_K; ++c)
+        for (int c = 0; c < PDSC_MAX_K; ++c)
             if (c < k) u = fmaf(mrow[c], v_sh[c], u);
         __syncthreads();
         if (lane >= k) u = 0.0f;
@@ -593,7 +491,7 @@ __global__ __launch_bounds__(64) void pdsc_power_kernel(const int32_t *__restric
         const bool close = (lane >= k) || (fabsf(vn - vl) <= 1e-8f + 1e-5f * fabsf(vl));
         const bool all = __all(close);
         const size_t h = ((size_t)b * S_cap + s) * num_iterations + it;
-        v_hist[h * KNN_MAX_K + lane] = vn;
+        v_hist[h * PDSC_MAX_K + lane] = vn;
         if (lane == 0) close_hist[h] = all ? 1 : 0;
         vl = (lane < k) ? vn : 1.0f;
     }
@@ -650,15 +548,15 @@ __global__ __launch_bounds__(256) void pdsc_hyp_fused_kernel(const float *__rest
     constexpr int C = 128;
     static_assert(EPT == 2 || EPT == 4, "lists per wave");
     extern __shared__ float sm[];
-    const int lin = blockIdx.x + gridDim.x * blockIdx.y;
-    const int b = (lin / 8 / (int)gridDim.x) * 8 + (lin & 7), s = (lin / 8) % (int)gridDim.x;
+    int b, s;
+    pdsc_seed_block(b, s);
     if (b >= n_batch || s >= n_seeds[b]) return;
     const int n = n_rows[b];
-    const int k = k_cfg < n - 1 ? k_cfg : n - 1;
+    const int k = pdsc_k_eff(k_cfg, n);
     unsigned long long *lists = reinterpret_cast<unsigned long long *>(sm);     // [4][64] the waves' sorted 64-lists
     float *kf = sm + 512;                                          // [k_cfg][C + 4]
     float *kc = kf + k_cfg * (C + 4);                              // [k_cfg][6]
-    int *kidx = reinterpret_cast<int *>(kc + k_cfg * 6);           // [KNN_MAX_K]
+    int *kidx = reinterpret_cast<int *>(kc + k_cfg * 6);           // [PDSC_MAX_K]
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const float *F = feat_n + (size_t)b * n_cap * C;
     const float *dp = dist_pre + ((size_t)b * S_cap + s) * n_cap;
@@ -706,47 +604,8 @@ __global__ __launch_bounds__(256) void pdsc_hyp_fused_kernel(const float *__rest
         }
     }
     __syncthreads();
-    for (int e = t; e < k * (C / 4); e += 256) {
-        const int a = e / (C / 4), c4 = e % (C / 4);
-        *reinterpret_cast<float4 *>(kf + a * (C + 4) + 4 * c4) = reinterpret_cast<const float4 *>(F + (size_t)kidx[a] * C)[c4];
-    }
-    for (int e = t; e < k * 3; e += 256) {
-        const int a = e / 3, d = e % 3;
-        kc[a * 6 + d] = src[((size_t)b * n_cap + kidx[a]) * 3 + d];
-        kc[a * 6 + 3 + d] = tgt[((size_t)b * n_cap + kidx[a]) * 3 + d];
-    }
-    if (t < k) knn_out[((size_t)b * S_cap + s) * k_cfg + t] = kidx[t];
-    __syncthreads();
-    float *Mo = M_out + ((size_t)b * S_cap + s) * k_cfg * k_cfg;
-    for (int e = t; e < k; e += 256) Mo[e * k_cfg + e] = 0.0f;
-    const int n_pairs = k * (k - 1) / 2;
-    for (int e = t; e < n_pairs; e += 256) {
-        int a = (int)((2.0f * k - 1.0f - sqrt_rn((2.0f * k - 1.0f) * (2.0f * k - 1.0f) - 8.0f * (float)e)) * 0.5f);
-        while (a > 0 && a * (2 * k - a - 1) / 2 > e) --a;
-        while ((a + 1) * (2 * k - a - 2) / 2 <= e) ++a;
-        const int c2 = a + 1 + (e - a * (2 * k - a - 1) / 2);
-        float dot = 0.0f;
-        const float4 *fa = reinterpret_cast<const float4 *>(kf + a * (C + 4)), *fb = reinterpret_cast<const float4 *>(kf + c2 * (C + 4));
-#pragma unroll 8
-        for (int c4 = 0; c4 < C / 4; ++c4) {
-            const float4 x = fa[c4], y = fb[c4];
-            dot = fmaf(x.x, y.x, dot);
-            dot = fmaf(x.y, y.y, dot);
-            dot = fmaf(x.z, y.z, dot);
-            dot = fmaf(x.w, y.w, dot);
-        }
-        float fm = 1.0f - (1.0f - dot) * inv_sigma2;
-        fm = fm > 0.0f ? fm : 0.0f;
-        const float *pa = kc + a * 6, *pb = kc + c2 * 6;
-        const float dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
-        const float ex = pa[3] - pb[3], ey = pa[4] - pb[4], ez = pa[5] - pb[5];
-        const float df = sqrt_rn(dx * dx + dy * dy + dz * dz) - sqrt_rn(ex * ex + ey * ey + ez * ez);
-        float smv = 1.0f - df * df * inv_sigma_d2;
-        smv = smv > 0.0f ? smv : 0.0f;
-        const float v = fm * smv;
-        Mo[a * k_cfg + c2] = v;
-        Mo[c2 * k_cfg + a] = v;
-    }
+    pdsc_compat_matrix(F, src, tgt, (size_t)b * n_cap, C, kidx, kf, kc, k, k_cfg, inv_sigma2, inv_sigma_d2, (size_t)b * S_cap + s, knn_out,
+                       M_out, t, 256);
 }
 
 __global__ __launch_bounds__(64) void pdsc_seed_solve_kernel(const float *__restrict__ src, const float *__restrict__ tgt,
@@ -760,7 +619,7 @@ __global__ __launch_bounds__(64) void pdsc_seed_solve_kernel(const float *__rest
     const int S = n_seeds[b];
     if (s >= S) return;
     const int n = n_rows[b];
-    const int k = k_cfg < n - 1 ? k_cfg : n - 1;
+    const int k = pdsc_k_eff(k_cfg, n);
     // joint stopping iteration: the first one at which every seed of the pair is close (else the last)
     int stop = num_iterations - 1;
     for (int it = 0; it < num_iterations; ++it) {
@@ -769,7 +628,7 @@ __global__ __launch_bounds__(64) void pdsc_seed_solve_kernel(const float *__rest
         if (__all(ok)) { stop = it; break; }
     }
     const float *sp = src + (size_t)b * n_cap * 3, *tp = tgt + (size_t)b * n_cap * 3;
-    const float vv = lane < k ? v_hist[(((size_t)b * S_cap + s) * num_iterations + stop) * KNN_MAX_K + lane] : 0.0f;
+    const float vv = lane < k ? v_hist[(((size_t)b * S_cap + s) * num_iterations + stop) * PDSC_MAX_K + lane] : 0.0f;
     float sum = vv;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
@@ -785,13 +644,8 @@ __global__ __launch_bounds__(64) void pdsc_seed_solve_kernel(const float *__rest
     float T[16];
     acc.solve(T);
     int cnt = 0;
-    for (int j = lane; j < n; j += 64) {
-        const float x = sp[3 * j], y = sp[3 * j + 1], z = sp[3 * j + 2];
-        const float dx = (T[0] * x + T[1] * y + T[2] * z + T[3]) - tp[3 * j];
-        const float dy = (T[4] * x + T[5] * y + T[6] * z + T[7]) - tp[3 * j + 1];
-        const float dz = (T[8] * x + T[9] * y + T[10] * z + T[11]) - tp[3 * j + 2];
-        cnt += (sqrt_rn(dx * dx + dy * dy + dz * dz) < inlier_thr) ? 1 : 0;
-    }
+    for (int j = lane; j < n; j += 64)
+        cnt += (pdsc_residual(T, sp[3 * j], sp[3 * j + 1], sp[3 * j + 2], tp[3 * j], tp[3 * j + 1], tp[3 * j + 2]) < inlier_thr) ? 1 : 0;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
     if (lane == 0) {
@@ -834,13 +688,8 @@ __global__ __launch_bounds__(256) void pdsc_seed_select_kernel(const float *__re
     if (labels)
         for (int j = t; j < n_cap; j += 256) {
             uint8_t lab = 0;
-            if (j < n) {
-                const float x = sp[3 * j], y = sp[3 * j + 1], z = sp[3 * j + 2];
-                const float dx = (T[0] * x + T[1] * y + T[2] * z + T[3]) - tp[3 * j];
-                const float dy = (T[4] * x + T[5] * y + T[6] * z + T[7]) - tp[3 * j + 1];
-                const float dz = (T[8] * x + T[9] * y + T[10] * z + T[11]) - tp[3 * j + 2];
-                lab = (sqrt_rn(dx * dx + dy * dy + dz * dz) < inlier_thr) ? 1 : 0;
-            }
+            if (j < n)
+                lab = (pdsc_residual(T, sp[3 * j], sp[3 * j + 1], sp[3 * j + 2], tp[3 * j], tp[3 * j + 1], tp[3 * j + 2]) < inlier_thr) ? 1 : 0;
             labels[(size_t)b * n_cap + j] = lab;
         }
 }
@@ -879,10 +728,7 @@ __global__ __launch_bounds__(256) void pdsc_refine_kernel(const float *__restric
         for (int j = t; j < n; j += 256) {
             const float x = sp[3 * j], y = sp[3 * j + 1], z = sp[3 * j + 2];
             const float bx = tp[3 * j], by = tp[3 * j + 1], bz = tp[3 * j + 2];
-            const float dx = (T[0] * x + T[1] * y + T[2] * z + T[3]) - bx;
-            const float dy = (T[4] * x + T[5] * y + T[6] * z + T[7]) - by;
-            const float dz = (T[8] * x + T[9] * y + T[10] * z + T[11]) - bz;
-            const float d = sqrt_rn(dx * dx + dy * dy + dz * dz);
+            const float d = pdsc_residual(T, x, y, z, bx, by, bz);
             if (d < tau) {
                 ++cnt;
                 const float q = d / tau;
@@ -935,8 +781,7 @@ int pdsc_run_seeds(const PdscModel &M, const float *src, const float *conf, cons
                            M.cfg.nms_radius, S_cap, M.cfg.ratio, key_scratch, seeds, n_seeds);
         return hipGetLastError() == hipSuccess ? ORYON_OK : ORYON_ERR_HIP;
     }
-    size_t P = 256;
-    while (P < (size_t)n_cap) P <<= 1;
+    const size_t P = pdsc_sort_size(n_cap);
     hipLaunchKernelGGL(pdsc_seed_keys_kernel, dim3(n_cap / 64, B), dim3(256), (size_t)4 * n_cap * sizeof(float), st, src, conf, n_rows, n_cap,
                        M.cfg.nms_radius, key_scratch);
     hipLaunchKernelGGL(pdsc_seed_rank_kernel, dim3(B), dim3(256), 2 * P * sizeof(float), st, key_scratch, n_rows, n_cap, S_cap, M.cfg.ratio,
@@ -950,7 +795,7 @@ int pdsc_run_tail(const float *src, const float *tgt, const int32_t *n_rows, con
                   int num_iterations, float inlier_thr, const int32_t *knn, const float *Mmat, float *v_hist, int32_t *close_hist,
                   float *seed_T, float *fitness, int32_t *best, float *T_best, uint8_t *labels, hipStream_t st)
 {
-    const int nit = num_iterations < HYP_MAX_IT ? num_iterations : HYP_MAX_IT;
+    const int nit = num_iterations < PDSC_MAX_IT ? num_iterations : PDSC_MAX_IT;
     hipLaunchKernelGGL(pdsc_power_kernel, dim3(S_cap, B), dim3(64), 0, st, n_rows, n_seeds, S_cap, k, nit, Mmat, v_hist, close_hist);
     hipLaunchKernelGGL(pdsc_seed_solve_kernel, dim3(S_cap, B), dim3(64), 0, st, src, tgt, n_rows, n_cap, n_seeds, S_cap, k, nit,
                        inlier_thr, knn, v_hist, close_hist, seed_T, fitness);
@@ -964,50 +809,33 @@ int pdsc_run_hypotheses(const PdscModel &M, const PdscWorkspace &ws, const float
                         float *fitness, int32_t *best, float *T_best, uint8_t *labels, hipStream_t st)
 {
     const int C = M.cfg.num_channels, k = M.cfg.k, S_cap = ws.S_cap;
-    size_t P = 256;
-    while (P < (size_t)n_cap) P <<= 1;
-    const size_t sh1 = (2 * P + C + (size_t)KNN_MAX_K * (C + 4) + KNN_MAX_K * 6 + KNN_MAX_K) * sizeof(float);
-    const int nit = M.cfg.num_iterations < HYP_MAX_IT ? M.cfg.num_iterations : HYP_MAX_IT;
-    // round 5: distances + kNN (rank counting) + compatibility matrix + power iteration in ONE launch where the shape allows
-    if (C == 128 && n_cap <= 1024 && k <= KNN_MAX_K - 1 && (size_t)S_cap * 128 * sizeof(float) <= 64 * 1024) {
+    const float inv_sigma2 = 1.0f / (M.sigma * M.sigma), inv_sigma_d2 = 1.0f / (M.sigma_d * M.sigma_d);
+    const dim3 grid(S_cap, (B + 7) / 8 * 8);                          // pdsc_seed_block: pairs rounded up to a multiple of 8
+    const bool seeds_fit_lds = C == 128 && (size_t)S_cap * 128 * sizeof(float) <= 64 * 1024;      // [S_cap][128] seed features
+    // round 5: distances (MFMA) and kNN (wave-level top-64) + compatibility matrix in two launches where the shape allows
+    if (seeds_fit_lds && n_cap <= 1024 && k <= PDSC_MAX_K - 1) {
         const size_t shd = (size_t)((S_cap + 31) / 32 * 32) * 129 * sizeof(float);
         allow_dynamic_lds(reinterpret_cast<const void *>(pdsc_seed_dist_mfma_kernel), (int)shd);
         hipLaunchKernelGGL(pdsc_seed_dist_mfma_kernel, dim3(n_cap / 64, B), dim3(256), shd, st, feat_n, n_rows, n_cap, seeds, n_seeds, S_cap,
                            ws.seed_dist);
-        const int ept = n_cap <= 512 ? 2 : 4;
-        const size_t shf = ((size_t)512 + (size_t)k * (C + 4) + k * 6 + KNN_MAX_K) * sizeof(float);
-        const dim3 grid(S_cap, (B + 7) / 8 * 8);
-        if (ept == 2)
-            hipLaunchKernelGGL(pdsc_hyp_fused_kernel<2>, grid, dim3(256), shf, st, feat_n, src, tgt, n_rows, n_cap, ws.seed_dist, n_seeds, S_cap, k,
-                               1.0f / (M.sigma * M.sigma), 1.0f / (M.sigma_d * M.sigma_d), ws.knn, ws.Mmat, B);
-        else
-            hipLaunchKernelGGL(pdsc_hyp_fused_kernel<4>, grid, dim3(256), shf, st, feat_n, src, tgt, n_rows, n_cap, ws.seed_dist, n_seeds, S_cap, k,
-                               1.0f / (M.sigma * M.sigma), 1.0f / (M.sigma_d * M.sigma_d), ws.knn, ws.Mmat, B);
-        if (hipGetLastError() != hipSuccess) return ORYON_ERR_HIP;
+        const size_t shf = ((size_t)512 + (size_t)k * (C + 4) + k * 6 + PDSC_MAX_K) * sizeof(float);
+        const auto fused = n_cap <= 512 ? pdsc_hyp_fused_kernel<2> : pdsc_hyp_fused_kernel<4>;      // 64-row lists per wave
+        hipLaunchKernelGGL(fused, grid, dim3(256), shf, st, feat_n, src, tgt, n_rows, n_cap, ws.seed_dist, n_seeds, S_cap, k, inv_sigma2,
+                           inv_sigma_d2, ws.knn, ws.Mmat, B);
     } else {
-    const float *dist_pre = nullptr;
-    if (C == 128 && (size_t)S_cap * 128 * sizeof(float) <= 64 * 1024) {
-        hipLaunchKernelGGL((pdsc_seed_dist_kernel<128>), dim3(n_cap / 64, B), dim3(256), (size_t)S_cap * 128 * sizeof(float), st, feat_n, n_rows,
-                           n_cap, seeds, n_seeds, S_cap, ws.seed_dist);
-        dist_pre = ws.seed_dist;
+        const float *dist_pre = nullptr;
+        if (seeds_fit_lds) {
+            hipLaunchKernelGGL((pdsc_seed_dist_kernel<128>), dim3(n_cap / 64, B), dim3(256), (size_t)S_cap * 128 * sizeof(float), st, feat_n,
+                               n_rows, n_cap, seeds, n_seeds, S_cap, ws.seed_dist);
+            dist_pre = ws.seed_dist;
+        }
+        const size_t sh1 = ((size_t)2 * pdsc_sort_size(n_cap) + C + (size_t)PDSC_MAX_K * (C + 4) + PDSC_MAX_K * 6 + PDSC_MAX_K) * sizeof(float);
+        hipLaunchKernelGGL(pdsc_knn_matrix_kernel, grid, dim3(256), sh1, st, feat_n, src, tgt, n_rows, n_cap, C, seeds, n_seeds, S_cap, k,
+                           inv_sigma2, inv_sigma_d2, ws.knn, ws.Mmat, dist_pre, B);
     }
-    // 1: the one-wave-per-seed kernel (same results; 91 vs 100 us per 64 registrations in the kernel trace, no difference in the step: not the default)
-    static const bool knn_wave = dev_env_int("ORYON_PDSC_KNN_WAVE", 0) != 0;
-    if (knn_wave && dist_pre && n_cap <= 1024 && k <= 63) {
-        const size_t shw = ((size_t)k * (128 + 4) + (size_t)k * 6) * sizeof(float);
-        if (n_cap <= 512)
-            hipLaunchKernelGGL((pdsc_knn_wave_kernel<128, 8>), dim3(S_cap, (B + 7) / 8 * 8), dim3(64), shw, st, feat_n, src, tgt, n_rows, n_cap,
-                               n_seeds, S_cap, k, 1.0f / (M.sigma * M.sigma), 1.0f / (M.sigma_d * M.sigma_d), ws.knn, ws.Mmat, dist_pre, B);
-        else
-            hipLaunchKernelGGL((pdsc_knn_wave_kernel<128, 16>), dim3(S_cap, (B + 7) / 8 * 8), dim3(64), shw, st, feat_n, src, tgt, n_rows, n_cap,
-                               n_seeds, S_cap, k, 1.0f / (M.sigma * M.sigma), 1.0f / (M.sigma_d * M.sigma_d), ws.knn, ws.Mmat, dist_pre, B);
-    } else
-    hipLaunchKernelGGL(pdsc_knn_matrix_kernel, dim3(S_cap, (B + 7) / 8 * 8), dim3(256), sh1, st, feat_n, src, tgt, n_rows, n_cap, C, seeds,
-                       n_seeds, S_cap, k, 1.0f / (M.sigma * M.sigma), 1.0f / (M.sigma_d * M.sigma_d), ws.knn, ws.Mmat, dist_pre, B);
     if (hipGetLastError() != hipSuccess) return ORYON_ERR_HIP;
-    }
-    return pdsc_run_tail(src, tgt, n_rows, n_seeds, B, n_cap, S_cap, k, nit, M.cfg.inlier_threshold, ws.knn, ws.Mmat, ws.v_hist, ws.close_hist,
-                         seed_T, fitness, best, T_best, labels, st);
+    return pdsc_run_tail(src, tgt, n_rows, n_seeds, B, n_cap, S_cap, k, M.cfg.num_iterations, M.cfg.inlier_threshold, ws.knn, ws.Mmat,
+                         ws.v_hist, ws.close_hist, seed_T, fitness, best, T_best, labels, st);
 }
 
 int pdsc_run_refine(const PdscModel &M, const float *src, const float *tgt, const int32_t *n_rows, int B, int n_cap,

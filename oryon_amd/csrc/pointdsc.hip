@@ -52,8 +52,8 @@ size_t carve(const oryon_pointdsc_config_t &cfg, int B, int n_cap, void *ws_ptr,
     c(w.Mmat, (size_t)B * S_cap * k * k);
     c(w.seed_w, (size_t)B * S_cap * k);
     c(w.seed_dist, (size_t)B * S_cap * n_cap);
-    c(w.v_hist, (size_t)B * S_cap * 16 * 64);
-    c(w.close_hist, (size_t)B * S_cap * 16);
+    c(w.v_hist, (size_t)B * S_cap * PDSC_MAX_IT * PDSC_MAX_K);
+    c(w.close_hist, (size_t)B * S_cap * PDSC_MAX_IT);
     c(w.seed_T, (size_t)B * S_cap * 16);
     c(w.fitness, (size_t)B * S_cap);
     c(w.best, B);
@@ -117,11 +117,11 @@ extern "C" int oryon_pointdsc_create(oryon_pointdsc_t **handle, const oryon_poin
     ORYON_CHECK_ARG(handle && cfg);
     ORYON_CHECK_ARG(cfg->in_dim == 6 && cfg->num_layers >= 1 && cfg->num_layers <= 64);
     ORYON_CHECK_ARG(cfg->num_channels == 32 || cfg->num_channels == 64 || cfg->num_channels == 128);
-    ORYON_CHECK_ARG(cfg->k >= 1 && cfg->k <= 64 && cfg->num_iterations >= 1 && cfg->ratio > 0.0f && cfg->ratio <= 1.0f);
+    ORYON_CHECK_ARG(cfg->k >= 1 && cfg->k <= PDSC_MAX_K && cfg->num_iterations >= 1 && cfg->ratio > 0.0f && cfg->ratio <= 1.0f);
     ORYON_CHECK_ARG(cfg->sigma_d > 0.0f && cfg->inlier_threshold > 0.0f && cfg->nms_radius >= 0.0f);
-    if (cfg->num_iterations > 16) {      // the power-iteration history (v_hist / close_hist) holds 16 iterates per seed: refuse, never truncate
-        set_error("oryon_pointdsc_create: num_iterations = %d exceeds the 16 iterates the device power iteration keeps per seed "
-                  "(models/pointdsc/PointDSC.py:338-358 would run all of them)", cfg->num_iterations);
+    if (cfg->num_iterations > PDSC_MAX_IT) {      // the power-iteration history (v_hist / close_hist) holds that many iterates per seed: refuse, never truncate
+        set_error("oryon_pointdsc_create: num_iterations = %d exceeds the %d iterates the device power iteration keeps per seed "
+                  "(models/pointdsc/PointDSC.py:338-358 would run all of them)", cfg->num_iterations, PDSC_MAX_IT);
         return ORYON_ERR_INVALID_ARG;
     }
     auto *h = new oryon_pointdsc();

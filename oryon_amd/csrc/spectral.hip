@@ -50,8 +50,7 @@
 namespace oryon {
 namespace {
 constexpr int SP_MAX_ROWS = 2048;
-constexpr int SP_MAX_K = 63;
-constexpr int SP_MAX_IT = 16;
+constexpr int SP_MAX_K = PDSC_MAX_K - 1;
 constexpr int SP_MV_LANES = 8, SP_MV_ROWS = 256 / SP_MV_LANES;     // spectral_matvec_kernel: lanes per row, rows per workgroup
 
 struct SpectralWs {
@@ -63,8 +62,8 @@ struct SpectralWs {
     int32_t *n_seeds;     // [B]
     int32_t *sets;        // [B,S_cap,k]
     float *Mmat;          // [B,S_cap,k,k]
-    float *v_hist;        // [B,S_cap,16,64]
-    int32_t *close_hist;  // [B,S_cap,16]
+    float *v_hist;        // [B,S_cap,PDSC_MAX_IT,PDSC_MAX_K]
+    int32_t *close_hist;  // [B,S_cap,PDSC_MAX_IT]
     float *seed_T;        // [B,S_cap,16]
     float *fitness;       // [B,S_cap]
     int32_t *best;        // [B]
@@ -76,7 +75,7 @@ struct SpectralWs {
 bool supported(const oryon_spectral_config_t *c, int B, int n_cap)
 {
     return c && B >= 1 && B <= 65535 && n_cap > 0 && n_cap % 128 == 0 && n_cap <= SP_MAX_ROWS && c->k >= 2 && c->k <= SP_MAX_K &&
-           c->num_iterations >= 1 && c->num_iterations <= SP_MAX_IT && c->ratio > 0.0f && c->ratio <= 1.0f && c->inlier_threshold > 0.0f &&
+           c->num_iterations >= 1 && c->num_iterations <= PDSC_MAX_IT && c->ratio > 0.0f && c->ratio <= 1.0f && c->inlier_threshold > 0.0f &&
            c->sigma_d > 0.0f && c->nms_radius >= 0.0f;
 }
 
@@ -96,8 +95,8 @@ size_t carve_spectral(const oryon_spectral_config_t &c, int B, int n_cap, void *
     carve(w.n_seeds, (size_t)B);
     carve(w.sets, seeds * k);
     carve(w.Mmat, seeds * k * k);
-    carve(w.v_hist, seeds * SP_MAX_IT * 64);
-    carve(w.close_hist, seeds * SP_MAX_IT);
+    carve(w.v_hist, seeds * PDSC_MAX_IT * PDSC_MAX_K);
+    carve(w.close_hist, seeds * PDSC_MAX_IT);
     carve(w.seed_T, seeds * 16);
     carve(w.fitness, seeds);
     carve(w.best, (size_t)B);
@@ -270,8 +269,8 @@ __global__ __launch_bounds__(256) void spectral_sets_kernel(const float *__restr
     extern __shared__ __attribute__((aligned(16))) int smi[];
     int *keys = smi;                                             // [n_cap]
     uint32_t *row_s = reinterpret_cast<uint32_t *>(keys + n_cap);      // [n_cap / 32], 16-byte aligned (n_cap % 128 == 0)
-    int *kidx = reinterpret_cast<int *>(row_s + n_cap / 32);     // [64]
-    float *kc = reinterpret_cast<float *>(kidx + 64);            // [64][6]
+    int *kidx = reinterpret_cast<int *>(row_s + n_cap / 32);     // [PDSC_MAX_K]
+    float *kc = reinterpret_cast<float *>(kidx + PDSC_MAX_K);    // [PDSC_MAX_K][6]
     const int b = blockIdx.y, slot = blockIdx.x, t = threadIdx.x;
     if (slot >= n_seeds[b]) return;
     const int n = rows_of(n_rows, b, n_cap);
@@ -295,7 +294,7 @@ __global__ __launch_bounds__(256) void spectral_sets_kernel(const float *__restr
         if (j < n) keys[j] = j == seed ? -1 : ((sc << 12) | (4095 - j));
         else if (j < ((n + 3) & ~3)) keys[j] = (int)0x80000000;  // the padding rank_rows reads: greater than no key
     }
-    if (t < 64) kidx[t] = -1;
+    if (t < PDSC_MAX_K) kidx[t] = -1;
     __syncthreads();
     // rank counting: rank_j = #{j' : key_j' > key_j}; a thread owns rows t, t + 256, .. : 2, 4 or 8 of them by the pair's size
     if (n <= 512) rank_rows<2>(keys, n, seed, kk, kidx);
@@ -353,7 +352,7 @@ int run_spectral(const char *who, const oryon_spectral_config_t &c, const float 
     M.cfg.nms_radius = c.nms_radius;
     int rc = pdsc_run_seeds(M, src, ws.conf, n, B, n_cap, S_cap, ws.seeds, ws.n_seeds, ws.seed_key, st);
     if (rc) { set_error("%s: seeds launch failed", who); return rc; }
-    const size_t sh = ((size_t)n_cap + n_cap / 32 + 64 + 64 * 6) * sizeof(int);
+    const size_t sh = ((size_t)n_cap + n_cap / 32 + PDSC_MAX_K + PDSC_MAX_K * 6) * sizeof(int);
     hipLaunchKernelGGL(spectral_sets_kernel, dim3(S_cap, B), dim3(256), sh, st, src, tgt, n, n_cap, ws.compat, ws.seeds, ws.n_seeds, S_cap, k,
                        inv_sigma2, ws.sets, ws.Mmat, out ? out->scores : nullptr);
     if (hipGetLastError() != hipSuccess) { set_error("%s: consensus-set launch failed", who); return ORYON_ERR_HIP; }

@@ -20,7 +20,6 @@ KEPT = [
     "ORYON_PDSC_CLOCKS",
     "ORYON_PDSC_FP32_MFMA",
     "ORYON_PDSC_FUSED_HEAD",
-    "ORYON_PDSC_KNN_WAVE",
     "ORYON_PDSC_ROUTE",
     "ORYON_RESCORE_LANES",
     "ORYON_SCREEN8_ABLATE",
