@@ -1022,6 +1022,35 @@ int oryon_pose_verify(const double *src, const int32_t *n_src, int cap_src, cons
                       void *workspace, size_t workspace_bytes, int32_t *counts /* [B,K,7] */, int32_t *best /* [B] */,
                       int32_t *cls /* [B,K,cap_src] or NULL: class per row, -1 beyond the count */, void *stream);
 
+/* h1  Mask clean-up by connected components (csrc/mask_clean.hip; test.mask_clean): fill the enclosed holes of a binary object mask, then
+ *     keep every component, the largest one, or those within a fraction of the largest.  The reference has no counterpart.
+ * DEFINITION (tests/mask_clean_restatement.py is its numpy statement).  mask [n, H, W] int32, foreground = (mask == 1); out [n, H, W]
+ * int32 holds 0 or 1; every map on its own, in two steps, in integers only:
+ *   1 (fill_holes != 0)  the 4-connected components of the NON-foreground; a component with no pixel in the first or last row or column
+ *     becomes foreground, and `filled` counts those pixels.  (4-connectivity: the dual of the foreground's 8-connectivity.)
+ *   2 the 8-connected components of the foreground after step 1.  A component's label is the smallest linear index y * W + x among its
+ *     pixels, its area is its pixel count, A_max the largest area.  mode 0 (all): keep every component.  mode 1 (largest): keep exactly
+ *     one component, the one of area A_max with the smallest label.  mode 2 (area): keep every component with
+ *     (int64) area * 65536 >= (int64) frac_q16 * A_max; the caller forms frac_q16 = clamp(rint(frac * 65536), 0, 65536) once.
+ * An empty mask gives out = 0 and stats = 0.  labels [n, H, W] int32 or NULL: the step-2 label of every foreground pixel BEFORE the
+ * selection, -1 on the background.  stats [n, ORYON_MASK_CLEAN_STATS] int32 or NULL = {components, A_max, kept components, kept pixels,
+ * removed pixels, filled pixels}.  All three are fully determined by the input: identical bytes across routes, runs and streams.
+ *
+ * oryon_mask_clean: route 0 = the LDS route where H * W <= ORYON_MASK_CLEAN_LDS_PIXELS (one workgroup per map, one launch, the union-find
+ *   state in LDS throughout), else the global route (the same passes as 5 launches, 7 with fill_holes, one more for stats, behind one
+ *   memset of 64 bytes a map; the state in the workspace); route 1 / 2 force one.  0 <= n_maps <= 65535 (0: nothing to do, returns
+ *   ORYON_OK), H, W >= 1, H W < 2^31, out != mask.  Every check precedes every HIP call and every dereference.  Integer atomics only,
+ *   nothing read back, no allocation.
+ *   workspace: oryon_mask_clean_workspace_bytes(n_maps, H, W, route) bytes (0 = rejected arguments), 256-byte aligned
+ *     = align256(64 max(n_maps, 1)), and on the global route + 3 align256(4 n_maps H W). */
+#define ORYON_MASK_CLEAN_STATS 6
+#define ORYON_MASK_CLEAN_LDS_PIXELS 65536          /* what the LDS route holds: 256 x 256, in any shape */
+/* mode: 0 all, 1 largest, 2 area.  route: 0 auto (LDS where H*W fits), 1 LDS, 2 global */
+size_t oryon_mask_clean_workspace_bytes(int n_maps, int H, int W, int route);
+int oryon_mask_clean(const int32_t *mask, int n_maps, int H, int W, int mode, int frac_q16, int fill_holes, int route, int32_t *out,
+                     int32_t *labels /* may be NULL */, int32_t *stats /* may be NULL */, void *workspace, size_t workspace_bytes,
+                     void *stream);
+
 /* a5  StandardDecoder.forward (models/decoder.py:82-108) on the device, fp32 in / fp32 out, for the decoder the reference builds
  *     (get_decoder, models/decoder.py:119-125: input_dim 128, decoder_dims [64, 32], extra_upsampling, guidance projections 256->32 and
  *     128->16): three Up blocks (ConvTranspose2d 2x2 s2 -> cat guidance -> (conv3x3 - GroupNorm(C/16) - ReLU) x 2, :9-42), the two

@@ -202,6 +202,8 @@ _PROTOS = {
                                        ctypes.c_double, _P, _P, c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
     "oryon_pose_verify_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "oryon_pose_verify": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, _P, c_int, _P, c_int, ctypes.c_double, _P, _P, c_size_t, _P, _P, _P, _P]),
+    "oryon_mask_clean_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "oryon_mask_clean": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -1340,6 +1340,53 @@ def pose_verify(src: torch.Tensor, n_src: torch.Tensor, depth: torch.Tensor, mas
     return out
 
 
+MASK_CLEAN_MODES = ("all", "largest", "area")          # oryon_mask_clean's mode 0, 1, 2
+MASK_CLEAN_ROUTES = ("auto", "lds", "global")           # its route 0, 1, 2
+MASK_CLEAN_STATS = ("components", "a_max", "kept_components", "kept_pixels", "removed_pixels", "filled_pixels")      # stats[..., i]
+MASK_CLEAN_LDS_PIXELS = 65536                           # ORYON_MASK_CLEAN_LDS_PIXELS (include/oryon_hip.h): what the LDS route holds
+
+
+def mask_clean_frac_q16(frac: float) -> int:
+    """The one rounding of the area fraction, on the host: the device compares integers only."""
+    return int(min(max(round(float(frac) * 65536.0), 0), 65536))
+
+
+@_on_tensor_device
+def mask_clean(mask: torch.Tensor, mode: str = "largest", frac: float = 0.25, fill_holes: bool = False, route: str = "auto",
+               want_labels: bool = False, want_stats: bool = False):
+    """Mask clean-up by connected components (h1, csrc/mask_clean.hip; definition: include/oryon_hip.h, oryon_mask_clean).
+    mask [n,H,W] or [H,W], foreground = (mask == 1) -> out of the same shape, int32 0 / 1: with fill_holes the enclosed holes
+    (4-connected background that does not reach the border) filled, then of the 8-connected components every one (mode 'all'), the
+    largest (ties: the one that starts first in raster order) or those of at least frac x the largest area ('area').  route: 'auto'
+    (one workgroup per map in LDS up to MASK_CLEAN_LDS_PIXELS pixels, else the global route), 'lds' or 'global'.  Runs on the current
+    stream with no host round trip.  -> out, or (out[, labels][, stats]): labels int32, the smallest linear index of every foreground
+    pixel's component before the selection and -1 on the background; stats [n, 6] ([6] for one map) int32, MASK_CLEAN_STATS."""
+    if mode not in MASK_CLEAN_MODES:
+        raise ValueError(f"mask_clean: mode {mode!r} is none of {MASK_CLEAN_MODES}")
+    if route not in MASK_CLEAN_ROUTES:
+        raise ValueError(f"mask_clean: route {route!r} is none of {MASK_CLEAN_ROUTES}")
+    if not 0.0 <= float(frac) <= 1.0:
+        raise ValueError(f"mask_clean: frac must lie in [0, 1], not {frac}")
+    if not (isinstance(mask, torch.Tensor) and mask.dim() in (2, 3)):
+        raise ValueError("mask_clean: mask is a tensor [n,H,W] or [H,W]")
+    single = mask.dim() == 2
+    dev = _lib.require_gpu(mask.device)
+    m = (mask[None] if single else mask).to(torch.int32).contiguous()
+    n, H, W = m.shape
+    if H < 1 or W < 1:
+        raise ValueError(f"mask_clean: an empty map ({H} x {W})")
+    out = torch.empty_like(m)
+    labels = torch.empty_like(m) if want_labels else None
+    stats = torch.empty((n, len(MASK_CLEAN_STATS)), dtype=torch.int32, device=dev) if want_stats else None
+    if n > 0:
+        r = MASK_CLEAN_ROUTES.index(route)
+        ws = _lib.workspace(dev, lib().oryon_mask_clean_workspace_bytes(n, H, W, r), f"oryon_mask_clean_workspace_bytes({n}, {H}, {W}, {r})")
+        check(lib().oryon_mask_clean(ptr(m), n, H, W, MASK_CLEAN_MODES.index(mode), mask_clean_frac_q16(frac), int(bool(fill_holes)), r,
+                                     ptr(out), ptr(labels), ptr(stats), ptr(ws), ws.numel(), stream_ptr(dev)), "oryon_mask_clean")
+    res = tuple(t[0] if single else t for t in (out, labels, stats) if t is not None)
+    return res[0] if len(res) == 1 else res
+
+
 _x3_weights = {}
 # Validation mode of the fp16x3 path (backbone.enable_fp16x3(True, guard=True)): every call first checks max|activation| against the
 # float16 range (one reduction + a host sync per linear - for a first run with a real checkpoint, not for throughput) and evaluates

@@ -19,6 +19,11 @@ refine_max_dist.  `test.refine = icp_plane` refines it by point-to-plane ICP of 
 test.verify_tol of the measured depth, with no ground truth and no mesh.  `test.verify = guard` (needs a refinement) rates the solver's
 pose and the refined one and keeps the refinement only when more of the cloud agrees with it.
 
+`test.mask_clean = largest | area` and / or `test.mask_fill_holes` (absent, `none` and False: nothing changes, no launch, no new key)
+cleans every binary mask - predicted or external - before the matcher, a refiner or the verifier uses it (csrc/mask_clean.hip; no
+counterpart in the reference): enclosed holes filled, then the largest 8-connected component kept, or every one of at least
+test.mask_clean_frac of the largest area.  The thresholded masks stay in the results as `mask_a_raw` / `mask_q_raw`.
+
 and the validation step (pipeline.py:196-247, 579-590):
 
     on_validation_start(objects=None) / validation_step(batch, batch_idx) -> (loss, log) / on_validation_end() -> dict
@@ -125,6 +130,59 @@ def verify_summary() -> Dict:
     return {} if _latest_verify is None else _reduce_verify(*_latest_verify)
 
 
+# test.mask_clean / test.mask_clean_frac / test.mask_fill_holes (csrc/mask_clean.hip; no counterpart in the reference): clean every
+# binary mask before the matcher, a refiner or the verifier sees it - fill the enclosed holes, then keep the 'largest' 8-connected
+# component or every one of at least mask_clean_frac x the largest 'area'.  A property of the pipeline like test.verify - not a field of
+# MatchPoseConfig: the engine gets cleaned masks.  The fraction's default is a design choice, not tuned on data.
+MASK_CLEAN_MODES = ("none", "largest", "area")
+MASK_CLEAN_FRAC = 0.25
+_default_mask_clean = ("none", MASK_CLEAN_FRAC, False)
+
+
+def _check_mask_clean(mode: str, frac: float, fill_holes: bool) -> Tuple[str, float, bool]:
+    if mode not in MASK_CLEAN_MODES:
+        raise ValueError(f"Mask clean-up {mode} not implemented")
+    frac = float(frac)
+    if not 0.0 <= frac <= 1.0:
+        raise ValueError(f"test.mask_clean_frac must lie in [0, 1], not {frac}")
+    return mode, frac, bool(fill_holes)
+
+
+def set_default_mask_clean(mode: str, frac: float = MASK_CLEAN_FRAC, fill_holes: bool = False) -> None:
+    """The process-wide default of test.mask_clean / test.mask_clean_frac / test.mask_fill_holes: what default_args() carries and what
+    a Pipeline does when its args name none of them (('none', 0.25, False) unless set).  A driver sets it once, before it builds
+    pipelines (run_pose.py --mask-clean does)."""
+    global _default_mask_clean, _latest_mask_clean
+    _default_mask_clean = _check_mask_clean(mode, frac, fill_holes)
+    _latest_mask_clean = None
+
+
+def default_mask_clean() -> Tuple[str, float, bool]:
+    return _default_mask_clean
+
+
+# (mode, frac, fill_holes, log) of the latest Pipeline built with clean-up active since the last set_default_mask_clean: what a driver
+# that cannot reach the pipeline another module builds (run_pose.py around run_test.py) reads its summary from.
+_latest_mask_clean: Optional[Tuple[str, float, bool, List[Tensor]]] = None
+
+
+def _reduce_mask_clean(mode: str, frac: float, fill_holes: bool, log: List[Tensor]) -> Dict:
+    """log: the stats [n, 6] (ops.MASK_CLEAN_STATS) of every cleaned batch of masks, on the device -> the flags, how many masks were
+    cleaned and the means of their statistics.  The only place that reads them back."""
+    out = {"mask_clean": mode, "mask_clean_frac": frac, "mask_fill_holes": fill_holes, "mask_clean_masks": 0}
+    rows = torch.cat([s.reshape(-1, len(ops.MASK_CLEAN_STATS)) for s in log]).cpu().numpy().astype(np.int64) if log else np.zeros((0, 6), np.int64)
+    out["mask_clean_masks"] = int(rows.shape[0])
+    for i, name in enumerate(ops.MASK_CLEAN_STATS):
+        if name != "a_max":
+            out[f"mask_clean_{name}_mean"] = float(rows[:, i].mean()) if rows.shape[0] else None
+    return out
+
+
+def mask_clean_summary() -> Dict:
+    """Pipeline.mask_clean_summary() of the latest cleaning pipeline of this process; {} when there is none."""
+    return {} if _latest_mask_clean is None else _reduce_mask_clean(*_latest_mask_clean)
+
+
 def default_args(**overrides) -> SimpleNamespace:
     """The hot-path subset of configs/config.yaml (same names, same defaults)."""
     args = SimpleNamespace(
@@ -148,7 +206,12 @@ def default_args(**overrides) -> SimpleNamespace:
                              # test.verify / test.verify_tol (csrc/pose_verify.hip; no counterpart in the reference): rate, or
                              # choose between, the poses of a pair against the query's depth map (('none', 0.01) unless a driver
                              # called set_default_verify).  Read with getattr: arg objects without them keep working
-                             verify=default_verify()[0], verify_tol=default_verify()[1]),
+                             verify=default_verify()[0], verify_tol=default_verify()[1],
+                             # test.mask_clean / test.mask_clean_frac / test.mask_fill_holes (csrc/mask_clean.hip; no counterpart in
+                             # the reference): connected-component clean-up of every mask the path uses (('none', 0.25, False) unless
+                             # a driver called set_default_mask_clean).  Read with getattr: arg objects without them keep working
+                             mask_clean=default_mask_clean()[0], mask_clean_frac=default_mask_clean()[1],
+                             mask_fill_holes=default_mask_clean()[2]),
         loss=SimpleNamespace(hard_negatives=True, pos_margin=0.2, neg_margin=0.9, neg_kernel_size=5, mask_type="dice",
                              w={"mask": 1.0, "pos": 0.5, "neg": 0.5}),
         optimization=SimpleNamespace(optim_type="Adam", scheduler_type="cosine", lr=0.001, momentum=0.0, w_decay=0.0005, gamma=0.1),
@@ -216,12 +279,51 @@ class Pipeline:
         if self.verify_mode() != "none":                 # and so does an unknown test.verify, or a guard with nothing to choose from
             global _latest_verify
             _latest_verify = (self.verify_mode(), self.verify_tol(), self._verify_log)
+        self.last_mask_clean: Optional[Dict[str, Tensor]] = None      # the latest step's ops.mask_clean stats per side, on the device
+        self._mask_clean_log: List[Tensor] = []          # every cleaned batch's stats [n, 6], on the device: what mask_clean_summary reduces
+        if self.mask_clean_active():                     # an unknown test.mask_clean or a fraction outside [0, 1] raises here
+            global _latest_mask_clean
+            _latest_mask_clean = (*self.mask_clean_cfg(), self._mask_clean_log)
+
+    # ------------------------------------------------------------------ mask clean-up (test.mask_clean; csrc/mask_clean.hip)
+    def mask_clean_cfg(self) -> Tuple[str, float, bool]:
+        """(test.mask_clean, test.mask_clean_frac, test.mask_fill_holes); absent = the process-wide default, ('none', 0.25, False)
+        unless a driver set it."""
+        d = default_mask_clean()
+        t = self.args.test
+        return _check_mask_clean(getattr(t, "mask_clean", d[0]), getattr(t, "mask_clean_frac", d[1]), getattr(t, "mask_fill_holes", d[2]))
+
+    def mask_clean_active(self) -> bool:
+        mode, _, fill = self.mask_clean_cfg()
+        return mode != "none" or fill
+
+    def clean_masks(self, mask: Tensor, side: Optional[str] = None) -> Tensor:
+        """The one place a mask is cleaned: mask [n,H,W] or [H,W] on the device -> int32 of that shape (ops.mask_clean; 'none' with
+        test.mask_fill_holes runs the kernel in mode 'all'); the mask itself when clean-up is inactive.  side ('a' / 'q'): the stats
+        go under last_mask_clean[side] and into the summary's log, on the device; None: they are not kept."""
+        mode, frac, fill = self.mask_clean_cfg()
+        if mode == "none" and not fill:
+            return mask
+        out, stats = ops.mask_clean(mask, mode="all" if mode == "none" else mode, frac=frac, fill_holes=fill, want_stats=True)
+        if side is not None:
+            self.last_mask_clean = dict(self.last_mask_clean or {}, **{side: stats})
+            self._mask_clean_log.append(stats)
+        return out
+
+    def mask_clean_summary(self) -> Dict:
+        """What a driver adds to its summary: {} when clean-up is inactive; else the flags, the number of masks cleaned so far and the
+        means of their statistics (components, kept components, kept / removed / filled pixels).  Reads the device."""
+        return _reduce_mask_clean(*self.mask_clean_cfg(), self._mask_clean_log) if self.mask_clean_active() else {}
 
     # ------------------------------------------------------------------ mask post-processing (losses.py:56-60)
     def mask_results(self, batch: Dict, outputs: Dict) -> Dict[str, Tensor]:
         th = self.args.test.mask_threshold
         res = {"mask_a": ops.mask_from_logits(outputs["mask_a"].squeeze(1), th),
                "mask_q": ops.mask_from_logits(outputs["mask_q"].squeeze(1), th)}
+        if self.mask_clean_active():                     # the IoUs below rate the mask the path uses; the thresholded one stays beside it
+            for key in ("a", "q"):
+                res["mask_" + key + "_raw"] = res["mask_" + key]
+                res["mask_" + key] = self.clean_masks(res["mask_" + key], key if self.args.test.mask == "predicted" else None)
         for side, key in (("anchor", "a"), ("query", "q")):
             gt = batch.get(side, {}).get("mask") if isinstance(batch.get(side), dict) else None
             pred = res["mask_" + key]
@@ -232,16 +334,17 @@ class Pipeline:
                 res["iou_" + key] = torch.zeros(pred.shape[0], device=pred.device)
         return res
 
-    def _external_masks(self, batch: Dict, idx: int, size: Tuple[int, int]) -> Tuple[Tensor, Tensor]:
+    def _external_masks(self, batch: Dict, idx: int, size: Tuple[int, int], log: bool = True) -> Tuple[Tensor, Tensor]:
+        """log=False: the cleaned masks' stats are not kept (is_detection_valid looks at masks get_featmap_corrs builds again)."""
         dev = _lib.require_gpu(self.device)
         ma = ops.mask_resize_nearest(batch["anchor"]["mask"][idx].to(dev), size)[0]
         mq = ops.mask_resize_nearest(batch["query"]["mask"][idx].to(dev), size)[0]
-        return ma, mq
+        return self.clean_masks(ma, "a" if log else None), self.clean_masks(mq, "q" if log else None)
 
     # ------------------------------------------------------------------ pipeline.py:372-395
     def is_detection_valid(self, results: Dict, batch: Dict, idx: int) -> bool:
         if self.args.test.mask != "predicted":
-            mask_a, mask_q = self._external_masks(batch, idx, tuple(self.args.model.image_encoder.img_size))
+            mask_a, mask_q = self._external_masks(batch, idx, tuple(self.args.model.image_encoder.img_size), log=False)
         else:
             mask_a, mask_q = results["mask_a"][idx], results["mask_q"][idx]
         valid_a = torch.count_nonzero(mask_a == 1)
@@ -350,13 +453,14 @@ class Pipeline:
         return ops.icp_refine(clouds["src"], clouds["dst"], clouds["n_src"], clouds["n_dst"], pose.to(torch.float32).contiguous(),
                               max_iter=max_iter, tolerance=tolerance, max_dist=max_dist, status=status)
 
-    def _refine_masks(self, batch: Dict, results: Optional[Dict], dev) -> Tuple[Tensor, Tensor]:
-        if self.args.test.mask != "predicted":
-            return batch["anchor"]["mask"].to(dev), batch["query"]["mask"].to(dev)
+    def _refine_masks(self, batch: Dict, results: Optional[Dict], dev, pairs: slice = slice(None)) -> Tuple[Tensor, Tensor]:
+        """The masks of the batch's `pairs` the refiners and the verifier build their clouds from."""
+        if self.args.test.mask != "predicted":                   # the external masks at their own size, cleaned like the matcher's
+            return self.clean_masks(batch["anchor"]["mask"][pairs].to(dev)), self.clean_masks(batch["query"]["mask"][pairs].to(dev))
         if results is None or "mask_a" not in results:
             raise KeyError(f"test.refine='{self.refine_mode()}' / test.verify='{self.verify_mode()}' with test.mask='predicted' needs the "
                            "predicted masks (results['mask_a'], results['mask_q'])")
-        return results["mask_a"], results["mask_q"]
+        return results["mask_a"][pairs], results["mask_q"][pairs]
 
     # ------------------------------------------------------------------ depth-consistency verification (test.verify; csrc/pose_verify.hip)
     def verify_mode(self) -> str:
@@ -427,9 +531,9 @@ class Pipeline:
         refine, verify = self.refine_mode(), self.verify_mode()
         if refine == "none" and verify == "none":
             return pose4.to(torch.float32)
-        mask_a, mask_q = self._refine_masks(batch, results, dev)
+        mask_a, mask_q = self._refine_masks(batch, results, dev, slice(idx, idx + 1))
         key = torch.tensor([idx if pair_key is None else pair_key], dtype=torch.int64, device=dev)
-        sides = (mask_a[idx:idx + 1], mask_q[idx:idx + 1], depth_a[None].contiguous(), depth_q[None].contiguous(), camera_a, camera_q, key)
+        sides = (mask_a, mask_q, depth_a[None].contiguous(), depth_q[None].contiguous(), camera_a, camera_q, key)
         start = pose4.to(torch.float32)[None].to(dev)
         final, clouds = start, None
         if refine != "none":
@@ -551,8 +655,8 @@ class Pipeline:
                 raise KeyError("test.mask='predicted' needs the model's mask logits (outputs['mask_a'], outputs['mask_q'])")
             mask_a, mask_q = res["mask_a"], res["mask_q"]
         else:
-            mask_a = ops.mask_resize_nearest(batch["anchor"]["mask"].to(dev), (FH, FW))
-            mask_q = ops.mask_resize_nearest(batch["query"]["mask"].to(dev), (FH, FW))
+            mask_a = self.clean_masks(ops.mask_resize_nearest(batch["anchor"]["mask"].to(dev), (FH, FW)), "a")
+            mask_q = self.clean_masks(ops.mask_resize_nearest(batch["query"]["mask"].to(dev), (FH, FW)), "q")
         if self._engine is None:
             self._engine = MatchPoseEngine(self.pointdsc_solver, MatchPoseConfig(
                 dist_th=self.args.test.dist_th, n_corrs=self.args.test.n_corrs, src_sampling=self.args.test.src_sampling,

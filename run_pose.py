@@ -45,6 +45,15 @@ truth, no mesh.  `guard` (needs `--refine`) rates the solver's pose and the refi
 cloud agrees with it.  The summary carries `"verify"`, `"verify_tol"`, `"verify_score_mean"` over the solved pairs and, for `guard`,
 `"verify_refinements_kept"`.  M is a design choice at the scale of the refiners' gates, not tuned on data.
 
+    python run_pose.py --solver ransac --mask-clean largest --fill-holes --pairs 8 --batch 4
+
+`--mask-clean {none,largest,area} [--mask-clean-frac F] [--fill-holes]` (test.mask_clean / test.mask_clean_frac / test.mask_fill_holes;
+default none, F = 0.25, no filling) becomes the process-wide default (oryon_amd.pipeline.set_default_mask_clean) in the same way: every
+binary mask - predicted or external - is cleaned before the matcher, a refiner or the verifier uses it (csrc/mask_clean.hip): enclosed
+holes filled, then the largest 8-connected component kept, or every one of at least F x the largest area.  The summary carries
+`"mask_clean"`, `"mask_clean_frac"`, `"mask_fill_holes"` and the means of the clean-up's statistics over the masks it saw.  F is a
+design choice, not tuned on data.
+
     python run_pose.py --vsd --data-root /data --dataset nocs --ckpt ... --out preds/nocs.csv
 
 `--vsd` (real-asset mode only) also reports VSD and AR = (VSD + MSSD + MSPD) / 3, the reference's headline column
@@ -63,6 +72,7 @@ if ROOT not in sys.path:
 
 REFINE_CHOICES = ["none", "icp", "icp_plane"]          # oryon_amd.pipeline.REFINEMENTS
 VERIFY_CHOICES = ["none", "score", "guard"]            # oryon_amd.pipeline.VERIFY_MODES
+MASK_CLEAN_CHOICES = ["none", "largest", "area"]       # oryon_amd.pipeline.MASK_CLEAN_MODES
 
 
 def take_refine(argv=None):
@@ -73,17 +83,32 @@ def take_refine(argv=None):
     return a.refine, rest
 
 
+def take_mask_clean(argv=None):
+    """-> (the `--mask-clean` / `--mask-clean-frac` / `--fill-holes` values, argv without them).  A parser of its own that takes no
+    abbreviations: run_test.py's `--mask` is a prefix of `--mask-clean` and must go through untouched."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--mask-clean", choices=MASK_CLEAN_CHOICES, default="none")
+    ap.add_argument("--mask-clean-frac", type=float, default=0.25)
+    ap.add_argument("--fill-holes", action="store_true")
+    return ap.parse_known_args(argv)
+
+
 class Parsed(tuple):
     """(solver, the arguments left for run_test.py), with `.mutual`: whether `--mutual` was given (taken out, like `--refine`),
     `.ratio` / `.ratio_radius`: what `--ratio` / `--ratio-radius` gave (0.0 / 5 when absent), and `.verify` / `.verify_tol`: what
-    `--verify` / `--verify-tol` gave ('none' / 0.01 when absent)."""
-    def __new__(cls, solver, rest, mutual, ratio=0.0, ratio_radius=5, verify="none", verify_tol=0.01):
+    `--verify` / `--verify-tol` gave ('none' / 0.01 when absent), and `.mask_clean` / `.mask_clean_frac` / `.mask_fill_holes`: what
+    `--mask-clean` / `--mask-clean-frac` / `--fill-holes` gave ('none' / 0.25 / False when absent)."""
+    def __new__(cls, solver, rest, mutual, ratio=0.0, ratio_radius=5, verify="none", verify_tol=0.01, mask_clean="none", mask_clean_frac=0.25,
+                mask_fill_holes=False):
         self = super().__new__(cls, (solver, rest))
         self.mutual = mutual
         self.ratio = ratio
         self.ratio_radius = ratio_radius
         self.verify = verify
         self.verify_tol = verify_tol
+        self.mask_clean = mask_clean
+        self.mask_clean_frac = mask_clean_frac
+        self.mask_fill_holes = mask_fill_holes
         return self
 
 
@@ -91,7 +116,9 @@ def parse(argv=None):
     """-> Parsed: (solver, the arguments left for run_test.py) + .mutual.  `--refine` is checked and taken out as well (take_refine
     returns it), and so are `--mutual` (test.mutual: keep only the mutual nearest neighbours, csrc/match_mutual.hip) and `--ratio` /
     `--ratio-radius` (test.ratio, test.ratio_radius: the ratio test with an exclusion disc, csrc/match_second.hip) and `--verify` /
-    `--verify-tol` (test.verify, test.verify_tol: depth-consistency verification of the poses, csrc/pose_verify.hip)."""
+    `--verify-tol` (test.verify, test.verify_tol: depth-consistency verification of the poses, csrc/pose_verify.hip) and `--mask-clean` /
+    `--mask-clean-frac` / `--fill-holes` (test.mask_clean, test.mask_clean_frac, test.mask_fill_holes: connected-component clean-up of
+    the masks, csrc/mask_clean.hip)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
     ap.add_argument("--solver", choices=["pointdsc", "ransac", "spectral"], default="pointdsc",
                     help="test.solver: PointDSC registration, best_fit_transform_with_RANSAC, or the spectral solver (the last two need no "
@@ -105,11 +132,12 @@ def parse(argv=None):
                                                                              "map, or guard a refinement with that score (see above)")
     ap.add_argument("--verify-tol", type=float, default=0.01, help="test.verify_tol: metres a moved point may lie from the measured surface")
     ap.add_argument("-h", "--help", action="store_true")
+    mc, argv = take_mask_clean(argv)
     a, rest = ap.parse_known_args(argv)
     if a.help:
         ap.print_help()
         rest = ["--help"] + rest               # then run_test.py's own help
-    return Parsed(a.solver, rest, a.mutual, a.ratio, a.ratio_radius, a.verify, a.verify_tol)
+    return Parsed(a.solver, rest, a.mutual, a.ratio, a.ratio_radius, a.verify, a.verify_tol, mc.mask_clean, mc.mask_clean_frac, mc.fill_holes)
 
 
 def take_vsd(argv):
@@ -146,6 +174,8 @@ def main(argv=None):
         raise SystemExit("run_pose.py --verify guard needs --refine icp or --refine icp_plane: nothing to choose from")
     if not parsed.verify_tol >= 0.0:
         raise SystemExit("run_pose.py --verify-tol is a distance in metres, >= 0")
+    if not 0.0 <= parsed.mask_clean_frac <= 1.0:
+        raise SystemExit("run_pose.py --mask-clean-frac is a share of the largest component's area, in [0, 1]")
     from oryon_amd.engine import set_default_solver
     set_default_solver(solver)
     from oryon_amd.pipeline import set_default_refine
@@ -156,10 +186,13 @@ def main(argv=None):
     set_default_ratio(parsed.ratio, parsed.ratio_radius)
     from oryon_amd.pipeline import set_default_verify
     set_default_verify(parsed.verify, parsed.verify_tol)
+    from oryon_amd.pipeline import set_default_mask_clean
+    set_default_mask_clean(parsed.mask_clean, parsed.mask_clean_frac, parsed.mask_fill_holes)
     import run_test
     summary = run_test.main(rest)
     verified = parsed.verify != "none"
-    if parsed.mutual or parsed.ratio > 0 or verified:
+    cleaned = parsed.mask_clean != "none" or parsed.mask_fill_holes
+    if parsed.mutual or parsed.ratio > 0 or verified or cleaned:
         if parsed.mutual:
             summary = dict(summary, mutual=True)
         if parsed.ratio > 0:
@@ -167,6 +200,10 @@ def main(argv=None):
         if verified:
             from oryon_amd.pipeline import verify_summary         # what the pipelines run_test.py built have rated
             summary = {**summary, "verify": parsed.verify, "verify_tol": parsed.verify_tol, **verify_summary()}
+        if cleaned:
+            from oryon_amd.pipeline import mask_clean_summary     # what the pipelines run_test.py built have cleaned
+            summary = {**summary, "mask_clean": parsed.mask_clean, "mask_clean_frac": parsed.mask_clean_frac,
+                       "mask_fill_holes": parsed.mask_fill_holes, **mask_clean_summary()}
         if not (vsd and summary.get("pairs")):
             print(json.dumps(summary))               # run_test.py's line again, with the flag recorded
     return add_vsd(summary, rest) if vsd and summary.get("pairs") else summary
