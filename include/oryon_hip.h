@@ -224,6 +224,29 @@ int oryon_match_second_f32(const float *a_hat, const float *q_hat, int B, int C,
                            float *second_dist, int32_t *second_argmin, uint8_t *keep,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* K1n one rank of the one-to-many matcher: the best query row outside the discs round up to three earlier ranks
+ *     (csrc/match_next.hip).  The ranks of anchor row i of a pair:
+ *       c_1 = argmin[i], d_1 = min_dist[i]: K1's outputs.
+ *       dist(i, j) = fma(-0.5, dot(a_i, q_j), 0.5), the dot product K1's k-ordered fmaf chain: the bits of oryon_match_f32 and
+ *       oryon_match_second_f32.
+ *       For r = 2..K the candidates are the rows j < n_q whose pixel lies outside the disc of `radius` round the pixel of EVERY
+ *       earlier rank c_1 .. c_{r-1}: dy^2 + dx^2 >= radius^2 in integers (K1r's rule).  An earlier rank whose index is not in
+ *       [0, n_q) excludes nothing.
+ *       d_r is the minimum of dist(i, j) over the candidates, c_r the first query index on ties; with no candidate d_r = INFINITY
+ *       and c_r = -1, and so for every later rank.  The candidate sets are nested, so d_r >= d_{r-1}.
+ *     One call is one rank: prev_argmin holds n_prev = r - 1 planes (1..3) of [B, cap_a] int32, plane-major (plane k at
+ *     prev_argmin + k B cap_a), next_dist / next_argmin [B, cap_a] receive (d_r, c_r).  With a [K, B, cap_a] table whose plane 0 is
+ *     argmin, rank r reads planes 0 .. r-2 and writes plane r-1.  n_prev = 1 gives oryon_match_second_f32's second_dist bit for
+ *     bit (its second_argmin too, but for -1 where that one writes 0 for "none").
+ *     Rows >= n_a are not written, rows >= n_a / >= n_q of the inputs are never used.  Other operands, limits and the workspace
+ *     (oryon_match_next_workspace_bytes(B, cap_a): K1's query-split buffers) are oryon_match_second_f32's. */
+size_t oryon_match_next_workspace_bytes(int B, int cap_a);
+int oryon_match_next_f32(const float *a_hat, const float *q_hat, int B, int C, int cap_a, int cap_q,
+                         const int32_t *n_a, const int32_t *n_q,
+                         const int32_t *roi_q, int roi_stride_q, int W_q, int radius,
+                         const int32_t *prev_argmin, int n_prev, float *next_dist, int32_t *next_argmin,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* K1s same contract as oryon_match_f32 for every anchor row that can reach the threshold, computed as an fp16-MFMA
  *     screening pass (v_mfma_f32_32x32x16_f16 on the IEEE-half copies written by oryon_gather_normalise_f32) followed by
  *     an exact fp32 re-scoring of the surviving candidates with K1's canonical fmaf chain.  A proven error bound on the
@@ -400,6 +423,35 @@ int oryon_select_corrs(const int32_t *roi_a, const int32_t *roi_q, int roi_strid
                        const int32_t *n_a, const int32_t *n_q, const int32_t *argmin, const uint8_t *valid, int cap_a,
                        int B, int W, int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key,
                        int32_t *scratch, int32_t *corrs, int32_t *n_valid, int32_t *n_sel, int32_t *status, void *stream);
+
+/* K1k one-to-many correspondences: the sampler of oryon_select_corrs, then up to K rows per drawn anchor (csrc/post.hip).
+ *     The sampler draws anchors exactly as oryon_select_corrs does on the same arguments (same gate `valid`, same keys, same slots),
+ *     so n_valid / n_sel / status are that call's and slot s holds anchor row i_s.  The drawn rows of a_hat are gathered into
+ *     [B, cap_s, C], cap_s = round_up(max_corrs, ORYON_MATCH_TILE), and K - 1 rank scans (oryon_match_next_f32's definition) run on
+ *     those cap_s rows only.  Slot s then emits
+ *       its rank-1 row (the row oryon_select_corrs writes), always;
+ *       its rank-r row, r >= 2: (y, x) of the anchor, (y, x) of query row c_r - iff c_r >= 0, d_r < threshold (K1's comparison for
+ *       `valid`, the same float) and d_r <= __fadd_rn(d_1, margin).
+ *     Rows come out in (slot, rank) order, compacted: corrs [B, corr_rows, 4] int32, corr_rows >= K max_corrs; rank [B, corr_rows]
+ *     uint8 (1..K); n_rows [B] <= K max_corrs; rows >= n_rows[b] of corrs and rank are left untouched.
+ *     margin >= 0 is an additive slack on the cosine distance, INFINITY switches it off.  1 <= K <= 4, 1 <= radius <= 1024,
+ *     1 <= W <= 65535 (one map width for both sides, as oryon_select_corrs); the shape limits of oryon_match_second_f32.
+ *     min_dist / argmin / valid [B, cap_a]: oryon_match_f32 on the same operands with `threshold`.
+ *     Optional outputs (NULL = not wanted, K > 1 only): sel_rows [B, cap_s] (anchor row of every slot), cand_dist / cand_argmin
+ *     [K, B, cap_s] (rank r in plane r - 1; slots >= n_sel not written).  n_sel may be NULL.
+ *     K = 1 launches the sampler alone, straight into corrs: the bytes of oryon_select_corrs.  rank and n_rows may then both be
+ *     NULL; given, one more small launch fills them (all ones, n_sel).
+ *     No allocation, no synchronisation; workspace: oryon_topk_corrs_workspace_bytes(B, C, cap_a, max_corrs, K). */
+size_t oryon_topk_corrs_workspace_bytes(int B, int C, int cap_a, int max_corrs, int K);
+int oryon_topk_corrs(const float *a_hat, const float *q_hat, int B, int C, int cap_a, int cap_q,
+                     const int32_t *roi_a, const int32_t *roi_q, int roi_stride_a, int roi_stride_q,
+                     const int32_t *n_a, const int32_t *n_q,
+                     const float *min_dist, const int32_t *argmin, const uint8_t *valid, float threshold,
+                     int W, int max_corrs, int corr_rows, uint64_t seed, const int64_t *pair_key,
+                     int K, int radius, float margin,
+                     int32_t *corrs, uint8_t *rank, int32_t *n_valid, int32_t *n_sel, int32_t *status, int32_t *n_rows,
+                     int32_t *sel_rows, float *cand_dist, int32_t *cand_argmin,
+                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* K2  scale (y,x) to the original image, keep rows inside both images, truncate, gather depth, pin-hole
  *     lift, /1000.  Replaces pipeline.py:447-460 + utils/coordinates.py:5-48 + utils/pcd.py:44-74.

@@ -81,6 +81,8 @@ _PROTOS = {
     "oryon_match_second_workspace_bytes": (c_size_t, [c_int, c_int]),
     "oryon_match_second_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_float, _P, _P, _P,
                                        _P, c_size_t, _P]),
+    "oryon_match_next_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "oryon_match_next_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_size_t, _P]),
     "oryon_match_screened_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "oryon_gather_normalise_q8": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "oryon_gather_q8": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
@@ -117,6 +119,9 @@ _PROTOS = {
     "oryon_sample_first_merge": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     "oryon_select_corrs": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_uint64, _P, _P,
                                    _P, _P, _P, _P, _P]),
+    "oryon_topk_corrs_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "oryon_topk_corrs": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, c_float, c_int, c_int, c_int,
+                                 c_uint64, _P, c_int, c_int, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "oryon_lift_pairs": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P,
                                  _P, _P, _P]),
     "oryon_lift_points": (c_int, [_P, c_int, c_int, _P, _P, _P, c_int, _P, _P]),

@@ -169,6 +169,13 @@ int select_corrs_launch(const int32_t *roi_a, const int32_t *roi_q, int roi_stri
                         int32_t *n_sel, int32_t *status, int32_t *sel_rows, const int32_t *pair_eager, hipStream_t st,
                         const SampledAmbList &amb = SampledAmbList());
 
+// match_next.hip: the launches of one rank scan (oryon_match_next_f32 behind its argument checks) for oryon_topk_corrs; the query-split
+// buffers are carved from workspace at ws_start, match_next_split_bytes is where they end
+size_t match_next_split_bytes(int B, int cap_a, size_t start);
+int match_next_launch(const float *a_hat, const float *q_hat, int B, int C, int cap_a, int cap_q, const int32_t *n_a, const int32_t *n_q,
+                      const int32_t *roi_q, int roi_stride_q, int W_q, int radius, const int32_t *prev, int n_prev, float *next_dist,
+                      int32_t *next_argmin, void *workspace, size_t ws_start, hipStream_t st);
+
 // ------------------------------------------------------------------------------------------------ host steps of K1s8 (match16.hip)
 // What the steps below read: oryon_match_screened8 and oryon_match_screened8_raw fill one, MatchCorrsArgs extends it.
 struct Screen8Args {

@@ -1,6 +1,6 @@
 // The exact matcher's two all-pairs tile walks as templates over what is done with a finished tile: how the query rows stream past a
 // workgroup's 128 anchor columns and through the fp32 MFMA.  They are match_f32_kernel's and match_f32_regb_kernel's loops (match.hip)
-// statement for statement, so the distances have K1's bits; K1r (match_second.hip) is built on them.  K1 and K1m (match_mutual.hip)
+// statement for statement, so the distances have K1's bits; K1r (match_second.hip) and K1n (match_next.hip) are built on them.  K1 and K1m (match_mutual.hip)
 // still carry their own text of the loops: instantiated from here, each was 0.3 - 0.9 % slower at C_pad 32 (measured).
 // The formulation, the geometry, the LDS image and the LDS-DMA are explained here, once, for all three.
 // What a kernel does with a FINISHED tile of dot products - its fold - is the caller's:

@@ -310,6 +310,115 @@ __global__ __launch_bounds__(256) void sample_first_merge_kernel(int corr_rows, 
     if (threadIdx.x == 0) { n_valid1[p] = n_valid2[p]; n_sel1[p] = n_sel2[p]; status1[p] = status2[p]; }
 }
 
+// ------------------------------------------------------------------------------------------------ one-to-many rows (oryon_topk_corrs)
+// The drawn anchor rows of a pair, gathered for the rank scans: slot s < n_sel gets row sel_rows[s] of a_hat and that row's K1 outputs
+// as rank 1 of the candidate tables; slots up to the end of the last 128-row panel the scans touch are zero rows.  Four slots per
+// workgroup, one wave each.
+__global__ __launch_bounds__(256) void topk_gather_kernel(const float *__restrict__ a_hat, const float *__restrict__ min_dist,
+                                                          const int32_t *__restrict__ argmin, const int32_t *__restrict__ sel_rows,
+                                                          const int32_t *__restrict__ n_sel, int cap_a, int cap_s, int C,
+                                                          float *__restrict__ a_s, float *__restrict__ cand_dist,
+                                                          int32_t *__restrict__ cand_argmin)
+{
+    const int p = blockIdx.y, s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int n = min(max(n_sel[p], 0), cap_s);
+    if (s >= (n + ORYON_MATCH_TILE - 1) / ORYON_MATCH_TILE * ORYON_MATCH_TILE) return;
+    float4 *dst = reinterpret_cast<float4 *>(a_s + ((size_t)p * cap_s + s) * C);
+    if (s >= n) {
+        for (int c = lane; c < C / 4; c += 64) dst[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const int row = sel_rows[(size_t)p * cap_s + s];
+    const float4 *src = reinterpret_cast<const float4 *>(a_hat + ((size_t)p * cap_a + row) * C);
+    for (int c = lane; c < C / 4; c += 64) dst[c] = src[c];
+    if (lane == 0) {
+        cand_dist[(size_t)p * cap_s + s] = min_dist[(size_t)p * cap_a + row];
+        cand_argmin[(size_t)p * cap_s + s] = argmin[(size_t)p * cap_a + row];
+    }
+}
+
+// One workgroup per pair: slot s emits its rank-1 row (the sampler's, copied) and every rank r >= 2 whose distance passes K1's
+// `d < thr` and d_r <= d_1 + margin, in (slot, rank) order through an ordered block scan of the slots' row counts.
+__global__ __launch_bounds__(SEL_THREADS) void topk_expand_kernel(const int32_t *__restrict__ rows1, const float *__restrict__ cand_dist,
+                                                                  const int32_t *__restrict__ cand_argmin, const int32_t *__restrict__ n_sel,
+                                                                  const int32_t *__restrict__ roi_q, int stride_q, int W, int B, int cap_s,
+                                                                  int max_corrs, int K, float thr, float margin, int corr_rows,
+                                                                  int32_t *__restrict__ corrs, uint8_t *__restrict__ rank,
+                                                                  int32_t *__restrict__ n_rows)
+{
+    __shared__ int s_wave[SEL_WAVES];
+    const int p = blockIdx.x;
+    const int n = min(max(n_sel[p], 0), max_corrs);
+    const int32_t *rq = roi_q + (size_t)p * stride_q;
+    const size_t plane = (size_t)B * cap_s;
+    int4 *out = reinterpret_cast<int4 *>(corrs + (size_t)p * corr_rows * 4);
+    uint8_t *rk = rank + (size_t)p * corr_rows;
+    int base = 0;
+    for (int s0 = 0; s0 < n; s0 += SEL_THREADS) {
+        const int s = s0 + (int)threadIdx.x;
+        const size_t o = (size_t)p * cap_s + s;
+        unsigned bits = 0u;
+        int j[4] = {0, 0, 0, 0};
+        if (s < n) {
+            bits = 1u;
+            const float lim = __fadd_rn(cand_dist[o], margin);
+            for (int r = 1; r < K; ++r) {
+                const float d = cand_dist[r * plane + o];
+                j[r] = cand_argmin[r * plane + o];
+                if (j[r] >= 0 && d < thr && d <= lim) bits |= 1u << r;
+            }
+        }
+        int tot;
+        int w = base + block_scan_counts_sel(__popc(bits), s_wave, tot);
+        if (bits) {
+            const int4 c1 = *reinterpret_cast<const int4 *>(rows1 + o * 4);
+            out[w] = c1;
+            rk[w++] = 1;
+            for (int r = 1; r < K; ++r)
+                if (bits & (1u << r)) {
+                    const int pq = rq[j[r]];
+                    out[w] = make_int4(c1.x, c1.y, pq / W, pq % W);
+                    rk[w++] = (uint8_t)(r + 1);
+                }
+        }
+        base += tot;
+    }
+    if (threadIdx.x == 0) n_rows[p] = base;
+}
+
+// K = 1: the sampler has written the rows themselves; all that is left is their rank and their count
+__global__ void topk_rank1_kernel(const int32_t *__restrict__ n_sel, int max_corrs, int corr_rows, uint8_t *__restrict__ rank,
+                                  int32_t *__restrict__ n_rows)
+{
+    const int p = blockIdx.x;
+    const int n = min(max(n_sel[p], 0), max_corrs);
+    for (int s = threadIdx.x; s < n; s += blockDim.x) rank[(size_t)p * corr_rows + s] = 1;
+    if (threadIdx.x == 0) n_rows[p] = n;
+}
+
+struct TopkWs {
+    int32_t *scratch, *rows1, *sel_rows, *n_sel, *cand_argmin;
+    float *a_s, *cand_dist;
+    size_t split_start;
+};
+static size_t carve_topk(void *base, TopkWs &w, int B, int C, int cap_a, int cap_s, int K)
+{
+    Carver carve(base);
+    carve(w.scratch, (size_t)B * cap_a);
+    carve(w.n_sel, (size_t)B);
+    if (K > 1) {
+        carve(w.rows1, (size_t)B * cap_s * 4);
+        carve(w.sel_rows, (size_t)B * cap_s);
+        carve(w.a_s, (size_t)B * cap_s * C);
+        carve(w.cand_dist, (size_t)K * B * cap_s);
+        carve(w.cand_argmin, (size_t)K * B * cap_s);
+        w.split_start = carve.off;
+        return align256(match_next_split_bytes(B, cap_s, carve.off));
+    }
+    w.split_start = carve.off;
+    return carve.off;
+}
+
 // internal entry shared with the lazy matcher (match_corrs.hip)
 int select_corrs_launch(const int32_t *roi_a, const int32_t *roi_q, int roi_stride_a, int roi_stride_q, const int32_t *n_a,
                         const int32_t *n_q, const int32_t *argmin, const uint8_t *valid, int cap_a, int B, int W, int max_corrs,
@@ -335,6 +444,79 @@ extern "C" int oryon_select_corrs(const int32_t *roi_a, const int32_t *roi_q, in
     hipLaunchKernelGGL(select_corrs_kernel, dim3(B), dim3(SEL_THREADS), 0, as_stream(stream), roi_a, roi_q, roi_stride_a,
                        roi_stride_q, n_a, n_q, argmin, valid, cap_a, W, max_corrs, corr_rows, seed, pair_key, scratch, corrs,
                        n_valid, n_sel, status, static_cast<int32_t *>(nullptr), static_cast<const int32_t *>(nullptr), SampledAmbList());
+    ORYON_CHECK_LAUNCH();
+    return ORYON_OK;
+}
+
+extern "C" size_t oryon_topk_corrs_workspace_bytes(int B, int C, int cap_a, int max_corrs, int K)
+{
+    if (B <= 0 || C <= 0 || cap_a <= 0 || max_corrs <= 0 || K < 1 || K > 4) return 0;
+    TopkWs w;
+    return carve_topk(nullptr, w, B, C, cap_a, ceil_div(max_corrs, ORYON_MATCH_TILE) * ORYON_MATCH_TILE, K);
+}
+
+extern "C" int oryon_topk_corrs(const float *a_hat, const float *q_hat, int B, int C, int cap_a, int cap_q, const int32_t *roi_a,
+                                const int32_t *roi_q, int roi_stride_a, int roi_stride_q, const int32_t *n_a, const int32_t *n_q,
+                                const float *min_dist, const int32_t *argmin, const uint8_t *valid, float threshold, int W, int max_corrs,
+                                int corr_rows, uint64_t seed, const int64_t *pair_key, int K, int radius, float margin, int32_t *corrs,
+                                uint8_t *rank, int32_t *n_valid, int32_t *n_sel, int32_t *status, int32_t *n_rows, int32_t *sel_rows,
+                                float *cand_dist, int32_t *cand_argmin, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ORYON_CHECK_ARG(a_hat && q_hat && roi_a && roi_q && n_a && n_q);
+    ORYON_CHECK_ARG(min_dist && argmin && valid);
+    ORYON_CHECK_ARG(corrs && n_valid && status);
+    ORYON_CHECK_ARG(K >= 1 && K <= 4);
+    ORYON_CHECK_ARG(K == 1 ? (rank != nullptr) == (n_rows != nullptr) : rank && n_rows);
+    ORYON_CHECK_ARG(K > 1 || (!sel_rows && !cand_dist && !cand_argmin));    // K = 1 is the sampler alone: no tables
+    ORYON_CHECK_ARG(B >= 0 && B <= 65535);
+    ORYON_CHECK_ARG(C > 0 && C % 32 == 0);
+    ORYON_CHECK_ARG(cap_a > 0 && cap_a % ORYON_MATCH_TILE == 0);
+    ORYON_CHECK_ARG(cap_q > 0 && cap_q % ORYON_MATCH_TILE == 0);
+    ORYON_CHECK_ARG(C != 32 || cap_q % 256 == 0);       // the C_pad 32 kernel streams the query rows in tiles of 256
+    ORYON_CHECK_ARG(roi_stride_a > 0 && roi_stride_q > 0);
+    ORYON_CHECK_ARG(W >= 1 && W <= 65535);              // a pixel packs into one word: y << 16 | x
+    ORYON_CHECK_ARG(radius >= 1 && radius <= 1024);
+    ORYON_CHECK_ARG(margin >= 0.0f);                    // a NaN fails
+    ORYON_CHECK_ARG(max_corrs > 0 && max_corrs <= (1 << 20));
+    ORYON_CHECK_ARG(corr_rows >= K * max_corrs);
+    if (B == 0) return ORYON_OK;
+    const int cap_s = ceil_div(max_corrs, ORYON_MATCH_TILE) * ORYON_MATCH_TILE;
+    TopkWs w;
+    const size_t need = carve_topk(workspace, w, B, C, cap_a, cap_s, K);
+    ORYON_CHECK_WORKSPACE("oryon_topk_corrs: ", workspace, workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    int32_t *nsel = n_sel ? n_sel : w.n_sel;
+    if (K == 1) {
+        hipLaunchKernelGGL(select_corrs_kernel, dim3(B), dim3(SEL_THREADS), 0, st, roi_a, roi_q, roi_stride_a, roi_stride_q, n_a, n_q, argmin,
+                           valid, cap_a, W, max_corrs, corr_rows, seed, pair_key, w.scratch, corrs, n_valid, nsel, status,
+                           static_cast<int32_t *>(nullptr), static_cast<const int32_t *>(nullptr), SampledAmbList());
+        ORYON_CHECK_LAUNCH();
+        if (rank) {
+            hipLaunchKernelGGL(topk_rank1_kernel, dim3(B), dim3(256), 0, st, nsel, max_corrs, corr_rows, rank, n_rows);
+            ORYON_CHECK_LAUNCH();
+        }
+        return ORYON_OK;
+    }
+    int32_t *sel = sel_rows ? sel_rows : w.sel_rows;
+    float *cd = cand_dist ? cand_dist : w.cand_dist;
+    int32_t *ca = cand_argmin ? cand_argmin : w.cand_argmin;
+    // the sampler, into rows of stride cap_s: its draws - and its rank-1 rows - are oryon_select_corrs's
+    hipLaunchKernelGGL(select_corrs_kernel, dim3(B), dim3(SEL_THREADS), 0, st, roi_a, roi_q, roi_stride_a, roi_stride_q, n_a, n_q, argmin,
+                       valid, cap_a, W, max_corrs, cap_s, seed, pair_key, w.scratch, w.rows1, n_valid, nsel, status, sel,
+                       static_cast<const int32_t *>(nullptr), SampledAmbList());
+    ORYON_CHECK_LAUNCH();
+    hipLaunchKernelGGL(topk_gather_kernel, dim3(cap_s / 4, B), dim3(256), 0, st, a_hat, min_dist, argmin, sel, nsel, cap_a, cap_s, C, w.a_s, cd,
+                       ca);
+    ORYON_CHECK_LAUNCH();
+    const size_t plane = (size_t)B * cap_s;
+    for (int r = 1; r < K; ++r)         // rank r + 1 of the drawn rows: reads planes 0 .. r - 1, writes plane r
+        if (match_next_launch(w.a_s, q_hat, B, C, cap_s, cap_q, nsel, n_q, roi_q, roi_stride_q, W, radius, ca, r, cd + r * plane,
+                              ca + r * plane, workspace, w.split_start, st) != ORYON_OK) {
+            set_error("%s: launch failed (rank scan %d)", __func__, r + 1);
+            return ORYON_ERR_HIP;
+        }
+    hipLaunchKernelGGL(topk_expand_kernel, dim3(B), dim3(SEL_THREADS), 0, st, w.rows1, cd, ca, nsel, roi_q, roi_stride_q, W, B, cap_s,
+                       max_corrs, K, threshold, margin, corr_rows, corrs, rank, n_rows);
     ORYON_CHECK_LAUNCH();
     return ORYON_OK;
 }

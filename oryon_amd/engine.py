@@ -71,6 +71,35 @@ def default_ratio() -> Tuple[float, int]:
     return _default_ratio
 
 
+_default_topk = (1, 5, 0.1)
+
+
+def set_default_topk(topk: int, radius: int = 5, margin: float = 0.1) -> None:
+    """The process-wide default of test.topk / test.topk_radius / test.topk_margin: what `MatchPoseConfig()` and
+    `pipeline.default_args()` choose when the caller does not say ((1, 5, 0.1) unless set: off).  A driver sets it once, before it
+    builds pipelines (run_pose.py --topk does)."""
+    global _default_topk
+    _check_topk_range(topk, radius, margin)
+    _default_topk = (int(topk), int(radius), float(margin))
+
+
+def default_topk() -> Tuple[int, int, float]:
+    return _default_topk
+
+
+TOPK_MAX = 4
+SOLVER_ROW_CAP = 2048          # rows per pair that PointDSC, ransac and spectral accept
+
+
+def _check_topk_range(topk, radius, margin) -> None:
+    if int(topk) != topk or not (1 <= int(topk) <= TOPK_MAX):
+        raise ValueError(f"topk {topk!r} is outside [1, {TOPK_MAX}] (1 = off)")
+    if not (1 <= int(radius) <= 1024) or int(radius) != radius:
+        raise ValueError(f"topk_radius {radius!r} is outside [1, 1024]")
+    if not (float(margin) >= 0.0):                       # a NaN fails too; inf switches the margin off
+        raise ValueError(f"topk_margin {margin!r} is negative")
+
+
 def _check_ratio_range(ratio, radius) -> None:
     if not (0.0 <= float(ratio) <= 1.0):                 # a NaN fails too
         raise ValueError(f"ratio {ratio!r} is outside [0, 1] (0 = off)")
@@ -122,6 +151,16 @@ class MatchPoseConfig:
     # screened routes carry no reverse screen, the native C step engine does not know it); half_descriptors composes (the rounding
     # happens before the gather), sample_first does not (a ValueError).
     mutual: bool = field(default_factory=default_mutual)
+    # test.topk / test.topk_radius / test.topk_margin: one-to-many correspondences (csrc/match_next.hip, oryon_topk_corrs).  topk = K > 1
+    # hands the solver up to K rows per drawn anchor: its nearest query pixel and the K - 1 next best ones, each at least topk_radius
+    # pixels from every earlier one, kept while under dist_th and within topk_margin (cosine distance, additive) of the nearest.  The
+    # sampler's draws are those of topk = 1; the solvers, built to pick a consistent subset, see up to K * n_corrs rows (at most 2048).
+    # radius 5 = loss.neg_kernel_size and margin 0.1 = half of loss.pos_margin are design choices, not measured on real data.  Exact
+    # scan, per-call schedule; mutual, ratio and sample_first do not combine (a ValueError).  1 = off.  (The fields stand in front of
+    # ratio / ratio_radius, which stay the last two.)
+    topk: int = field(default_factory=lambda: default_topk()[0])
+    topk_radius: int = field(default_factory=lambda: default_topk()[1])
+    topk_margin: float = field(default_factory=lambda: default_topk()[2])
     # test.ratio / test.ratio_radius: the ratio test with an exclusion disc (csrc/match_second.hip).  ratio > 0 keeps a row only when
     # min_dist <= ratio * the best distance to a query pixel at least ratio_radius pixels away from the matched one (radius 1: Lowe's
     # test; 5 = loss.neg_kernel_size, the margin the descriptors were trained to have).  A second exact scan behind the first (or behind
@@ -133,6 +172,7 @@ class MatchPoseConfig:
     def __post_init__(self):
         _check_mutual(self)
         _check_ratio(self)
+        _check_topk(self)
 
 
 def _check_mutual(cfg: "MatchPoseConfig") -> None:
@@ -146,6 +186,21 @@ def _check_ratio(cfg: "MatchPoseConfig") -> None:
     if cfg.ratio > 0 and cfg.sample_first and cfg.sample_first > 0:
         raise ValueError("ratio > 0 does not combine with sample_first > 0: the second scan behind a first-stage subset of the anchors "
                          "is not built")
+
+
+def _check_topk(cfg: "MatchPoseConfig") -> None:
+    _check_topk_range(cfg.topk, cfg.topk_radius, cfg.topk_margin)
+    if cfg.topk > 1 and ops.round_up(int(cfg.n_corrs) * int(cfg.topk), 128) > SOLVER_ROW_CAP:
+        raise ValueError(f"n_corrs {cfg.n_corrs} x topk {cfg.topk} rounds up to more than {SOLVER_ROW_CAP} rows per pair, the solvers' row cap")
+    if cfg.topk > 1:
+        if cfg.mutual:
+            raise ValueError("topk > 1 does not combine with mutual=True: there are no reverse ranks to cross-check ranks 2..K against")
+        if cfg.ratio > 0:
+            raise ValueError("topk > 1 does not combine with ratio > 0: the ratio test deletes the ambiguous anchors whose alternatives "
+                             "topk keeps")
+        if cfg.sample_first and cfg.sample_first > 0:
+            raise ValueError("topk > 1 does not combine with sample_first > 0: the rank scans behind a first-stage subset of the anchors "
+                             "are not built")
 
 
 def _check_solver(cfg: "MatchPoseConfig", solver) -> bool:
@@ -352,7 +407,7 @@ class MatchPoseEngine:
         self.solver = solver
         self.cfg = cfg or MatchPoseConfig()
         _check_solver(self.cfg, solver)
-        self.n_cap = ops.round_up(self.cfg.n_corrs, 128)
+        self.n_cap = ops.round_up(self.cfg.n_corrs * self.cfg.topk, 128)
         self.overlap = overlap_registration
         self.overlap_gather = overlap_gather
         self.native = native
@@ -594,11 +649,15 @@ class MatchPoseEngine:
         cfg = self.cfg
         _check_mutual(cfg)
         _check_ratio(cfg)
+        _check_topk(cfg)
+        if cfg.topk > 1:
+            self.n_cap = ops.round_up(cfg.n_corrs * cfg.topk, 128)
         B, C, FH, FW = feat_a.shape
         main = torch.cuda.current_stream(dev)
         # the screens' validity cut is 1 - 2*dist_th: thresholds above 0.5 (or non-positive) take the exact scan; so does mutual (no
         # reverse screen exists)
-        filtered = cfg.mutual or cfg.ratio > 0         # ... and so does the ratio test (no second-minimum screen exists)
+        # ... and so do the ratio test (no second-minimum screen exists) and topk > 1 (no screen of the later ranks)
+        filtered = cfg.mutual or cfg.ratio > 0 or cfg.topk > 1
         screened = cfg.match_mode in ("screened", "screened16") and 64 < C <= 512 and 0.0 < cfg.dist_th <= 0.5 and not filtered
         use_i8 = screened and cfg.match_mode == "screened" and C > 128
         if use_i8:
@@ -645,7 +704,7 @@ class MatchPoseEngine:
             cap_a = ops.round_up(FH * FW, ops.ROW_PAD)
         cap_q = ops.round_up(FH * FW, ops.ROW_PAD)
         a16 = q16 = a8 = q8 = a_sc = q_sc = q_eps = q_norm = q_hat = roi_a1 = n_a1 = mutual = rev_argmin = rev_min_dist = None
-        second_dist = second_argmin = keep_rows = None
+        second_dist = second_argmin = keep_rows = topk_out = None
         stage1 = use_i8 and cfg.sample_first > 0 and not keep
         if use_i8:
             # K0v3: anchors -> fp32 + int8 rows, queries -> int8 rows + row norms only (the re-scoring pass reads its few candidates
@@ -717,8 +776,15 @@ class MatchPoseEngine:
                 second_dist, second_argmin, keep_rows = ops.match_second(a_hat, q_hat, n_a, n_q, roi_q, FW, cfg.ratio_radius, min_dist,
                                                                          argmin, gate, cfg.ratio)
                 gate = keep_rows
-            corrs, n_valid, n_sel, status = ops.select_corrs(roi_a, roi_q, n_a, n_q, argmin, gate, FW,
-                                                             cfg.n_corrs, cfg.seed, pair_key, corr_rows=self.n_cap)
+            if cfg.topk > 1:
+                # the sampler's draws, then the rank scans on the drawn rows only and up to topk rows per slot
+                topk_out = ops.topk_corrs(a_hat, q_hat, roi_a, roi_q, n_a, n_q, min_dist, argmin, valid, cfg.dist_th, FW, cfg.n_corrs,
+                                          cfg.seed, cfg.topk, cfg.topk_radius, cfg.topk_margin, pair_key, corr_rows=self.n_cap,
+                                          tables=keep)
+                corrs, n_valid, status, n_sel = topk_out["corrs"], topk_out["n_valid"], topk_out["status"], topk_out["n_rows"]
+            else:
+                corrs, n_valid, n_sel, status = ops.select_corrs(roi_a, roi_q, n_a, n_q, argmin, gate, FW,
+                                                                 cfg.n_corrs, cfg.seed, pair_key, corr_rows=self.n_cap)
         cam_a = cam_a.reshape(B, 9).to(torch.float32).contiguous()
         cam_q = cam_q.reshape(B, 9).to(torch.float32).contiguous()
         pcd_a, pcd_q, n_lift = ops.lift_pairs(corrs, n_sel, (FH, FW), depth_a, depth_q, cam_a, cam_q, status)
@@ -747,6 +813,8 @@ class MatchPoseEngine:
             pose, status_out = self._register(pcd_a, pcd_q, n_lift, status, pair_key, 0)
             done = None
         out = dict(pose=pose, status=status_out, n_valid=n_valid, n_lifted=n_lift)
+        if topk_out is not None:
+            out["n_rows"] = topk_out["n_rows"]
         if done is not None:
             out["_done"] = done
         if keep:
@@ -756,4 +824,7 @@ class MatchPoseEngine:
                 out.update(mutual=mutual, rev_argmin=rev_argmin, rev_min_dist=rev_min_dist)
             if cfg.ratio > 0:
                 out.update(second_dist=second_dist, second_argmin=second_argmin, keep=keep_rows)
+            if topk_out is not None:
+                out.update(sel_rows=topk_out["sel_rows"], cand_dist=topk_out["cand_dist"], cand_argmin=topk_out["cand_argmin"],
+                           corr_rank=topk_out["rank"])
         return out

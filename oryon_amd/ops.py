@@ -424,6 +424,68 @@ def match_second(a_hat: torch.Tensor, q_hat: torch.Tensor, n_a: torch.Tensor, n_
 
 
 @_on_tensor_device
+def match_next(a_hat: torch.Tensor, q_hat: torch.Tensor, n_a: torch.Tensor, n_q: torch.Tensor, roi_q: torch.Tensor, W_q: int, radius: int,
+               prev_argmin: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """One rank of the one-to-many matcher (K1n): -> (next_dist [B,cap_a] f32, next_argmin [B,cap_a] i32), the best query row outside
+    the discs of `radius` pixels round the pixels of the earlier ranks prev_argmin [n_prev,B,cap_a] i32 (n_prev 1..3); index -1 and
+    inf where no row is left.  out: the two tensors to write (e.g. the next plane of a [K,B,cap_a] table) instead of fresh ones."""
+    dev = _lib.require_gpu(a_hat.device)
+    B, cap_a, Cp = a_hat.shape
+    cap_q = q_hat.shape[1]
+    assert q_hat.shape[0] == B and q_hat.shape[2] == Cp
+    assert a_hat.dtype == torch.float32 and q_hat.dtype == torch.float32
+    assert roi_q.dtype == torch.int32 and roi_q.dim() == 2 and roi_q.shape[0] == B
+    assert prev_argmin.dtype == torch.int32 and prev_argmin.dim() == 3 and prev_argmin.shape[1:] == (B, cap_a)
+    if out is None:
+        out = (torch.empty((B, cap_a), dtype=torch.float32, device=dev), torch.empty((B, cap_a), dtype=torch.int32, device=dev))
+    next_dist, next_argmin = out
+    assert next_dist.dtype == torch.float32 and next_argmin.dtype == torch.int32 and next_dist.shape == (B, cap_a) == next_argmin.shape
+    wsb = lib().oryon_match_next_workspace_bytes(B, cap_a)
+    ws = _lib.workspace(dev, wsb)
+    check(lib().oryon_match_next_f32(ptr(a_hat), ptr(q_hat), B, Cp, cap_a, cap_q, ptr(n_a), ptr(n_q), ptr(roi_q), roi_q.shape[1], int(W_q),
+                                     int(radius), ptr(prev_argmin), prev_argmin.shape[0], ptr(next_dist), ptr(next_argmin), ptr(ws), wsb,
+                                     stream_ptr(dev)), "oryon_match_next_f32")
+    return next_dist, next_argmin
+
+
+@_on_tensor_device
+def topk_corrs(a_hat: torch.Tensor, q_hat: torch.Tensor, roi_a: torch.Tensor, roi_q: torch.Tensor, n_a: torch.Tensor, n_q: torch.Tensor,
+               min_dist: torch.Tensor, argmin: torch.Tensor, valid: torch.Tensor, threshold: float, W: int, max_corrs: int, seed: int,
+               topk: int, radius: int, margin: float, pair_key=None, corr_rows: Optional[int] = None, tables: bool = False):
+    """One-to-many correspondences (K1k): the draws of `select_corrs`, then up to `topk` rows per drawn anchor.
+    -> dict(corrs [B,corr_rows,4] i32, rank [B,corr_rows] u8, n_valid, n_sel, status, n_rows [B] i32); corr_rows defaults to
+    topk * max_corrs, rows >= n_rows stay zero.  tables (topk > 1): also sel_rows [B,cap_s] i32 and cand_dist f32 / cand_argmin i32
+    [topk,B,cap_s], cap_s = round_up(max_corrs, 128), slots >= n_sel as allocated (NaN / -2)."""
+    dev = _lib.require_gpu(a_hat.device)
+    B, cap_a, Cp = a_hat.shape
+    cap_q = q_hat.shape[1]
+    K = int(topk)
+    assert q_hat.shape[0] == B and q_hat.shape[2] == Cp and a_hat.dtype == torch.float32 and q_hat.dtype == torch.float32
+    assert roi_a.dtype == torch.int32 and roi_q.dtype == torch.int32 and roi_a.dim() == 2 and roi_q.dim() == 2
+    assert min_dist.dtype == torch.float32 and argmin.dtype == torch.int32 and valid.dtype == torch.uint8
+    assert min_dist.shape == (B, cap_a) == argmin.shape == valid.shape
+    corr_rows = int(corr_rows or K * int(max_corrs))
+    cap_s = round_up(max_corrs, MATCH_TILE)
+    out = dict(corrs=torch.zeros((B, corr_rows, 4), dtype=torch.int32, device=dev),
+               rank=torch.zeros((B, corr_rows), dtype=torch.uint8, device=dev),
+               n_valid=torch.empty((B,), dtype=torch.int32, device=dev), n_sel=torch.empty((B,), dtype=torch.int32, device=dev),
+               status=torch.empty((B,), dtype=torch.int32, device=dev), n_rows=torch.empty((B,), dtype=torch.int32, device=dev))
+    if tables and K > 1:
+        out["sel_rows"] = torch.full((B, cap_s), -2, dtype=torch.int32, device=dev)
+        out["cand_dist"] = torch.full((K, B, cap_s), float("nan"), dtype=torch.float32, device=dev)
+        out["cand_argmin"] = torch.full((K, B, cap_s), -2, dtype=torch.int32, device=dev)
+    wsb = lib().oryon_topk_corrs_workspace_bytes(B, Cp, cap_a, int(max_corrs), K)
+    ws = _lib.workspace(dev, wsb, "oryon_topk_corrs_workspace_bytes")
+    check(lib().oryon_topk_corrs(ptr(a_hat), ptr(q_hat), B, Cp, cap_a, cap_q, ptr(roi_a), ptr(roi_q), roi_a.shape[1], roi_q.shape[1],
+                                 ptr(n_a), ptr(n_q), ptr(min_dist), ptr(argmin), ptr(valid), float(threshold), int(W), int(max_corrs),
+                                 corr_rows, int(seed) & (2**64 - 1), ptr(pair_key), K, int(radius), float(margin), ptr(out["corrs"]),
+                                 ptr(out["rank"]), ptr(out["n_valid"]), ptr(out["n_sel"]), ptr(out["status"]), ptr(out["n_rows"]),
+                                 ptr(out.get("sel_rows")), ptr(out.get("cand_dist")), ptr(out.get("cand_argmin")), ptr(ws), wsb,
+                                 stream_ptr(dev)), "oryon_topk_corrs")
+    return out
+
+
+@_on_tensor_device
 def match_screened(a_hat, q_hat, a16, q16, n_a, n_q, threshold: float):
     """fp16-screened, fp32-exact matcher (K1s).  Same outputs as `match` on every row that can be valid."""
     dev = _lib.require_gpu(a_hat.device)

@@ -30,7 +30,7 @@ def torch_sample_select(t: Tensor, n: int) -> Tensor:
 
 def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor, threshold: float,
                     subsample_source: Optional[int] = None, half_descriptors: bool = False, mode: str = "exact",
-                    mutual: bool = False, ratio: float = 0.0, ratio_radius: int = 5):
+                    mutual: bool = False, ratio: float = 0.0, ratio_radius: int = 5, topk: int = 1, topk_radius: int = 5):
     """Deterministic half of the matcher (utils/pcd.py:184-205) on the GPU.
 
     Returns dict(roi1 [N1,2] i64 (y,x), roi2 [N2,2] i64, min_dist [N1] f32, argmin [N1] i64, valid [N1] bool).
@@ -50,12 +50,22 @@ def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor
     ratio > 0: the ratio test with an exclusion disc (K1r, csrc/match_second.hip) behind the exact scan, whatever `mode` says - the
     screened modes carry no second-minimum screen.  The dict additionally carries `second_dist` [N1] f32 and `second_argmin` [N1] i64,
     the best query row at least ratio_radius pixels away from the matched pixel (inf / 0 when there is none), and `keep` [N1] bool =
-    gate & (min_dist <= ratio * second_dist), the gate being `mutual` when mutual=True and `valid` otherwise.  ratio = 0: off."""
+    gate & (min_dist <= ratio * second_dist), the gate being `mutual` when mutual=True and `valid` otherwise.  ratio = 0: off.
+    topk = K > 1: the ranks of the one-to-many matcher (K1n, csrc/match_next.hip) behind the exact scan, whatever `mode` says.  The
+    dict additionally carries `cand_dist` [K,N1] f32 and `cand_argmin` [K,N1] i64: rank 1 is (min_dist, argmin), rank r the best query
+    row at least topk_radius pixels away from the pixels of all earlier ranks ((inf, -1) when there is none).  This is the per-sample
+    reference form: K - 1 full scans over ALL N1 rows (the batched engine scans the drawn rows only).  Does not combine with mutual
+    or ratio (a ValueError).  topk = 1: off - the dict, its bytes and the RNG draws are what they always were."""
     if mode not in ("exact", "screened16", "screened8", "screened6"):
         raise ValueError(f"match_presample: unknown mode {mode!r}")
     if not (0.0 <= ratio <= 1.0) or not (1 <= ratio_radius <= 1024):
         raise ValueError(f"match_presample: ratio {ratio!r} outside [0, 1] or ratio_radius {ratio_radius!r} outside [1, 1024]")
-    if mutual or ratio > 0:
+    if int(topk) != topk or not (1 <= topk <= 4) or not (1 <= topk_radius <= 1024):
+        raise ValueError(f"match_presample: topk {topk!r} outside [1, 4] or topk_radius {topk_radius!r} outside [1, 1024]")
+    if topk > 1 and (mutual or ratio > 0):
+        raise ValueError("match_presample: topk > 1 does not combine with mutual (no reverse ranks) or ratio > 0 (the ratio test deletes "
+                         "what topk keeps)")
+    if mutual or ratio > 0 or topk > 1:
         mode = "exact"
     if mode != "exact" and not (0.0 < threshold <= 0.5):
         mode = "exact"                       # the screens' validity cut needs 1 - 2*threshold >= 0
@@ -93,6 +103,9 @@ def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor
         if ratio > 0:
             out.update(second_dist=torch.full((n1,), float("inf"), device=dev), second_argmin=torch.zeros(n1, dtype=torch.int64, device=dev),
                        keep=torch.zeros(n1, dtype=torch.bool, device=dev))
+        if topk > 1:
+            out.update(cand_dist=torch.full((topk, n1), float("inf"), device=dev),
+                       cand_argmin=torch.full((topk, n1), -1, dtype=torch.int64, device=dev))
         return out
     C = f1.shape[1]
     cap1, cap2 = ops.round_up(n1, ops.ROW_PAD), ops.round_up(n2, ops.ROW_PAD)
@@ -128,6 +141,14 @@ def match_presample(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor
         second_dist, second_argmin, keep = ops.match_second(a_hat, q_hat, c1, c2, roi2_lin.contiguous(), W2, ratio_radius, min_dist, argmin,
                                                             mut if mutual else valid, ratio)
         out.update(second_dist=second_dist[0, :n1], second_argmin=second_argmin[0, :n1].to(torch.int64), keep=keep[0, :n1].bool())
+    if topk > 1:
+        cand_dist = torch.empty((topk,) + tuple(min_dist.shape), dtype=torch.float32, device=dev)
+        cand_argmin = torch.empty((topk,) + tuple(argmin.shape), dtype=torch.int32, device=dev)
+        cand_dist[0], cand_argmin[0] = min_dist, argmin
+        roi2_c = roi2_lin.contiguous()
+        for r in range(1, topk):                         # rank r + 1: reads planes 0 .. r - 1, writes plane r
+            ops.match_next(a_hat, q_hat, c1, c2, roi2_c, W2, topk_radius, cand_argmin[:r], out=(cand_dist[r], cand_argmin[r]))
+        out.update(cand_dist=cand_dist[:, 0, :n1], cand_argmin=cand_argmin[:, 0, :n1].to(torch.int64))
     out.update(min_dist=min_dist[0, :n1], argmin=argmin[0, :n1].to(torch.int64), valid=valid[0, :n1].bool())
     return out
 
@@ -163,6 +184,41 @@ def nn_correspondences_filtered(feats1: Tensor, feats2: Tensor, mask1: Tensor, m
         idxs = torch_sample_select(final_corrs, max_corrs).to(final_corrs.device)
         return final_corrs[idxs].to(orig_device)
     return None
+
+
+def nn_correspondences_topk(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2: Tensor, threshold: float, max_corrs: int,
+                            subsample_source: Optional[int], corrs_device: str = "cuda", topk: int = 1, topk_radius: int = 5,
+                            topk_margin: float = 0.1) -> Optional[Tensor]:
+    """`nn_correspondences` with up to topk rows per drawn anchor (no counterpart in the reference).  The same two host draws are
+    made in the same order; every drawn row is then followed by its ranks 2..topk (match_presample's cand_*) that lie under the
+    threshold (K1's `d < threshold` in float32) and within topk_margin of the nearest (d_r <= d_1 + margin, the sum rounded to
+    float32; inf switches the margin off).  int64 [n,4] rows in (draw, rank) order, max_corrs <= n <= topk * max_corrs, or None as
+    nn_correspondences.  The default radius (loss.neg_kernel_size) and margin (half of loss.pos_margin) are design choices.
+    With topk = 1 this IS nn_correspondences."""
+    if topk == 1:
+        return nn_correspondences_filtered(feats1, feats2, mask1, mask2, threshold, max_corrs, subsample_source, corrs_device)
+    if not (float(topk_margin) >= 0.0):
+        raise ValueError(f"nn_correspondences_topk: topk_margin {topk_margin!r} is negative")
+    orig_device = feats1.device
+    pre = match_presample(feats1, feats2, mask1, mask2, threshold, subsample_source, half_descriptors=(corrs_device == "cuda"),
+                          topk=topk, topk_radius=topk_radius)
+    valid_corr = torch.nonzero(pre["valid"]).squeeze(1)
+    if valid_corr.shape[0] <= 1:
+        return None
+    roi2 = pre["roi2"][pre["argmin"]]
+    final_corrs = torch.cat((pre["roi1"][valid_corr], roi2[valid_corr]), dim=1)
+    idxs = torch_sample_select(final_corrs, max_corrs).to(final_corrs.device)
+    rows = valid_corr[idxs]                              # the anchor row of every draw
+    dev = rows.device
+    cd, ca = pre["cand_dist"][:, rows], pre["cand_argmin"][:, rows]                  # [K, n]
+    lim = cd[0] + torch.tensor(topk_margin, dtype=torch.float32, device=dev)        # float32 sum
+    take = (ca >= 0) & (cd < torch.tensor(threshold, dtype=torch.float32, device=dev)) & (cd <= lim[None])
+    take[0] = True
+    anchor = pre["roi1"][rows][None].expand(topk, -1, -1)
+    query = pre["roi2"][ca.clamp(min=0)]
+    query[0] = final_corrs[idxs][:, 2:]
+    allrows = torch.cat((anchor, query), dim=2).transpose(0, 1)                      # [n, K, 4]: (draw, rank) order
+    return allrows[take.transpose(0, 1)].to(orig_device)
 
 
 def lift_pcd(depth: Tensor, camera: Tensor, xy_idxs: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:

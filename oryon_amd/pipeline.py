@@ -50,9 +50,9 @@ import torch
 from torch import Tensor
 
 from . import _lib, ops
-from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK, PAIR_OK, SOLVERS, default_mutual, default_ratio, default_solver
+from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK, PAIR_OK, SOLVERS, default_mutual, default_ratio, default_solver, default_topk
 from .geo6d import best_fit_transform_with_RANSAC, spectral_pose
-from .pcd import nn_correspondences, nn_correspondences_filtered
+from .pcd import nn_correspondences, nn_correspondences_filtered, nn_correspondences_topk
 from .pointdsc import PointDSC, get_pointdsc_pose
 
 
@@ -203,6 +203,10 @@ def default_args(**overrides) -> SimpleNamespace:
                              # test with an exclusion disc, 0 = off ((0.0, 5) unless a driver called engine.set_default_ratio).  Read
                              # with getattr(..., 0.0 / 5)
                              ratio=default_ratio()[0], ratio_radius=default_ratio()[1],
+                             # test.topk / test.topk_radius / test.topk_margin (csrc/match_next.hip; no counterpart in the reference):
+                             # up to topk rows per drawn anchor, 1 = off ((1, 5, 0.1) unless a driver called
+                             # engine.set_default_topk).  Read with getattr(..., 1 / 5 / 0.1)
+                             topk=default_topk()[0], topk_radius=default_topk()[1], topk_margin=default_topk()[2],
                              # test.verify / test.verify_tol (csrc/pose_verify.hip; no counterpart in the reference): rate, or
                              # choose between, the poses of a pair against the query's depth map (('none', 0.01) unless a driver
                              # called set_default_verify).  Read with getattr: arg objects without them keep working
@@ -360,7 +364,17 @@ class Pipeline:
             mask_ai, mask_qi = results["mask_a"][idx], results["mask_q"][idx]
         featmap_ai, featmap_qi = net_output["featmap_a"][idx], net_output["featmap_q"][idx]
         ratio = float(getattr(self.args.test, "ratio", 0.0))
-        if ratio > 0:
+        topk = int(getattr(self.args.test, "topk", 1))
+        if topk > 1:
+            # the checks of the batched route (K, the solvers' row cap, no mutual / ratio) before anything runs
+            MatchPoseConfig(n_corrs=self.args.test.n_corrs, solver=self.solver, mutual=bool(getattr(self.args.test, "mutual", False)),
+                            ratio=ratio, topk=topk, topk_radius=int(getattr(self.args.test, "topk_radius", 5)),
+                            topk_margin=float(getattr(self.args.test, "topk_margin", 0.1)))
+            pred_corrs = nn_correspondences_topk(featmap_ai, featmap_qi, mask_ai, mask_qi, self.args.test.dist_th, self.args.test.n_corrs,
+                                                 self.args.test.src_sampling, self.corrs_device, topk=topk,
+                                                 topk_radius=int(getattr(self.args.test, "topk_radius", 5)),
+                                                 topk_margin=float(getattr(self.args.test, "topk_margin", 0.1)))
+        elif ratio > 0:
             pred_corrs = nn_correspondences_filtered(featmap_ai, featmap_qi, mask_ai, mask_qi, self.args.test.dist_th, self.args.test.n_corrs,
                                                      self.args.test.src_sampling, self.corrs_device,
                                                      mutual=bool(getattr(self.args.test, "mutual", False)), ratio=ratio,
@@ -663,6 +677,8 @@ class Pipeline:
                 seed=self.args.seed if self.args.seed is not None else 1, solver=self.solver,
                 mutual=bool(getattr(self.args.test, "mutual", False)),
                 ratio=float(getattr(self.args.test, "ratio", 0.0)), ratio_radius=int(getattr(self.args.test, "ratio_radius", 5)),
+                topk=int(getattr(self.args.test, "topk", 1)), topk_radius=int(getattr(self.args.test, "topk_radius", 5)),
+                topk_margin=float(getattr(self.args.test, "topk_margin", 0.1)),
                 **{"spectral_" + f: v for f, v in self._spectral_cfg().items()}))
 
         def stack(x):

@@ -36,6 +36,14 @@ driver returns - and prints as its last JSON line - carries `"mutual": true`.
 best match at least N pixels away from its nearest one, and only rows with min_dist <= R * that distance reach the solver (N = 1 is
 Lowe's ratio test; with `--mutual` the mutual rows are filtered).  The summary carries `"ratio": R, "ratio_radius": N`.
 
+    python run_pose.py --solver ransac --topk 2 --topk-radius 5 --topk-margin 0.1 --pairs 8 --batch 4
+
+`--topk K [--topk-radius N] [--topk-margin M]` (test.topk / test.topk_radius / test.topk_margin; off by default: K = 1, N = 5, M = 0.1)
+becomes the process-wide default (oryon_amd.engine.set_default_topk) in the same way: every drawn anchor hands the solver up to K rows -
+its nearest query pixel and the K - 1 next best ones, each at least N pixels from all earlier ones (csrc/match_next.hip), kept while
+under test.dist_th and within M (cosine distance) of the nearest.  K <= 4 and K * n_corrs <= 2048; `--mutual`, `--ratio` and K > 1 do
+not combine.  The summary carries `"topk": K, "topk_radius": N, "topk_margin": M`.  N and M are design choices, not tuned on data.
+
     python run_pose.py --solver ransac --refine icp --verify guard --pairs 8 --batch 4
 
 `--verify {none,score,guard} [--verify-tol M]` (test.verify / test.verify_tol; default none, M = 0.01 m) becomes the process-wide default
@@ -93,13 +101,23 @@ def take_mask_clean(argv=None):
     return ap.parse_known_args(argv)
 
 
+def take_topk(argv=None):
+    """-> (the `--topk` / `--topk-radius` / `--topk-margin` values, argv without them); a parser of its own that takes no abbreviations."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--topk", type=int, default=1)
+    ap.add_argument("--topk-radius", type=int, default=5)
+    ap.add_argument("--topk-margin", type=float, default=0.1)
+    return ap.parse_known_args(argv)
+
+
 class Parsed(tuple):
     """(solver, the arguments left for run_test.py), with `.mutual`: whether `--mutual` was given (taken out, like `--refine`),
     `.ratio` / `.ratio_radius`: what `--ratio` / `--ratio-radius` gave (0.0 / 5 when absent), and `.verify` / `.verify_tol`: what
     `--verify` / `--verify-tol` gave ('none' / 0.01 when absent), and `.mask_clean` / `.mask_clean_frac` / `.mask_fill_holes`: what
-    `--mask-clean` / `--mask-clean-frac` / `--fill-holes` gave ('none' / 0.25 / False when absent)."""
+    `--mask-clean` / `--mask-clean-frac` / `--fill-holes` gave ('none' / 0.25 / False when absent), and `.topk` / `.topk_radius` /
+    `.topk_margin`: what `--topk` / `--topk-radius` / `--topk-margin` gave (1 / 5 / 0.1 when absent)."""
     def __new__(cls, solver, rest, mutual, ratio=0.0, ratio_radius=5, verify="none", verify_tol=0.01, mask_clean="none", mask_clean_frac=0.25,
-                mask_fill_holes=False):
+                mask_fill_holes=False, topk=1, topk_radius=5, topk_margin=0.1):
         self = super().__new__(cls, (solver, rest))
         self.mutual = mutual
         self.ratio = ratio
@@ -109,6 +127,9 @@ class Parsed(tuple):
         self.mask_clean = mask_clean
         self.mask_clean_frac = mask_clean_frac
         self.mask_fill_holes = mask_fill_holes
+        self.topk = topk
+        self.topk_radius = topk_radius
+        self.topk_margin = topk_margin
         return self
 
 
@@ -118,7 +139,8 @@ def parse(argv=None):
     `--ratio-radius` (test.ratio, test.ratio_radius: the ratio test with an exclusion disc, csrc/match_second.hip) and `--verify` /
     `--verify-tol` (test.verify, test.verify_tol: depth-consistency verification of the poses, csrc/pose_verify.hip) and `--mask-clean` /
     `--mask-clean-frac` / `--fill-holes` (test.mask_clean, test.mask_clean_frac, test.mask_fill_holes: connected-component clean-up of
-    the masks, csrc/mask_clean.hip)."""
+    the masks, csrc/mask_clean.hip) and `--topk` / `--topk-radius` / `--topk-margin` (test.topk, test.topk_radius, test.topk_margin:
+    up to K rows per drawn anchor, csrc/match_next.hip)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
     ap.add_argument("--solver", choices=["pointdsc", "ransac", "spectral"], default="pointdsc",
                     help="test.solver: PointDSC registration, best_fit_transform_with_RANSAC, or the spectral solver (the last two need no "
@@ -133,11 +155,13 @@ def parse(argv=None):
     ap.add_argument("--verify-tol", type=float, default=0.01, help="test.verify_tol: metres a moved point may lie from the measured surface")
     ap.add_argument("-h", "--help", action="store_true")
     mc, argv = take_mask_clean(argv)
+    tk, argv = take_topk(argv)
     a, rest = ap.parse_known_args(argv)
     if a.help:
         ap.print_help()
         rest = ["--help"] + rest               # then run_test.py's own help
-    return Parsed(a.solver, rest, a.mutual, a.ratio, a.ratio_radius, a.verify, a.verify_tol, mc.mask_clean, mc.mask_clean_frac, mc.fill_holes)
+    return Parsed(a.solver, rest, a.mutual, a.ratio, a.ratio_radius, a.verify, a.verify_tol, mc.mask_clean, mc.mask_clean_frac, mc.fill_holes,
+                  tk.topk, tk.topk_radius, tk.topk_margin)
 
 
 def take_vsd(argv):
@@ -176,6 +200,13 @@ def main(argv=None):
         raise SystemExit("run_pose.py --verify-tol is a distance in metres, >= 0")
     if not 0.0 <= parsed.mask_clean_frac <= 1.0:
         raise SystemExit("run_pose.py --mask-clean-frac is a share of the largest component's area, in [0, 1]")
+    if parsed.topk > 1 and (parsed.mutual or parsed.ratio > 0):
+        raise SystemExit("run_pose.py --topk K > 1 does not combine with --mutual (no reverse ranks) or --ratio (it deletes what --topk keeps)")
+    from oryon_amd.engine import set_default_topk
+    try:
+        set_default_topk(parsed.topk, parsed.topk_radius, parsed.topk_margin)
+    except ValueError as e:
+        raise SystemExit(f"run_pose.py: {e}")
     from oryon_amd.engine import set_default_solver
     set_default_solver(solver)
     from oryon_amd.pipeline import set_default_refine
@@ -192,11 +223,13 @@ def main(argv=None):
     summary = run_test.main(rest)
     verified = parsed.verify != "none"
     cleaned = parsed.mask_clean != "none" or parsed.mask_fill_holes
-    if parsed.mutual or parsed.ratio > 0 or verified or cleaned:
+    if parsed.mutual or parsed.ratio > 0 or verified or cleaned or parsed.topk > 1:
         if parsed.mutual:
             summary = dict(summary, mutual=True)
         if parsed.ratio > 0:
             summary = dict(summary, ratio=parsed.ratio, ratio_radius=parsed.ratio_radius)
+        if parsed.topk > 1:
+            summary = dict(summary, topk=parsed.topk, topk_radius=parsed.topk_radius, topk_margin=parsed.topk_margin)
         if verified:
             from oryon_amd.pipeline import verify_summary         # what the pipelines run_test.py built have rated
             summary = {**summary, "verify": parsed.verify, "verify_tol": parsed.verify_tol, **verify_summary()}
