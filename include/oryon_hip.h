@@ -464,6 +464,48 @@ int oryon_lift_pairs(const int32_t *corrs, const int32_t *n_corr, int B, int n_c
                      const float *cam_a, const float *cam_q, const int32_t *status, float *pcd_a, float *pcd_q,
                      int32_t *n_out, void *stream);
 
+/* K1x sub-pixel refinement of selected correspondences (csrc/match_subpix.hip; no counterpart in the reference): where, between the
+ *     pixels of the query map, the descriptor distance to the anchor is smallest.  A pure post-pass on the rows a sampler selected.
+ * feat_a / feat_q [B, C, FH, FW] fp32, C <= 512, in `layout` (ORYON_LAYOUT_NCHW | ORYON_LAYOUT_NHWC); corrs [B, n_cap, 4] int32
+ * (y_a, x_a, y_q, x_q); n_corr [B] (clamped to [0, n_cap]) or NULL (n_cap rows each); status [B] or NULL (pairs whose status !=
+ * ORYON_PAIR_OK do no work); curv_min >= 0.
+ *     All in float64 on the fp32 inputs.  With eps = 1e-8 and u^ = u / max(|u|, eps):
+ *       f(i, j) = 0.5 (1 - <a^, q^>) for the query pixel (y_q + i, x_q + j), i, j in {-1, 0, 1} - whether the query mask holds it or not;
+ *     the least-squares quadratic through the nine values (facet model):
+ *       g_x  = sum_i (f(i,1) - f(i,-1)) / 6                  g_y  = sum_j (f(1,j) - f(-1,j)) / 6
+ *       h_xx = sum_i (f(i,1) - 2 f(i,0) + f(i,-1)) / 3       h_yy = sum_j (f(1,j) - 2 f(0,j) + f(-1,j)) / 3
+ *       h_xy = (f(1,1) - f(1,-1) - f(-1,1) + f(-1,-1)) / 4
+ *       l_min = (h_xx + h_yy) / 2 - sqrt((h_xx - h_yy)^2 / 4 + h_xy^2),   o = -H^-1 g.
+ *     flags [B, n_cap] uint8, in this order:
+ *       1 border:  y_q outside [1, FH - 2] or x_q outside [1, FW - 2] (or the anchor pixel outside its map: nothing is read)
+ *       2 flat or not a minimum:  l_min < curv_min
+ *       3 outside:  not max(|o_x|, |o_y|) <= 1 (a NaN lands here)
+ *       0 refined: otherwise; o clamped to [-0.5, 0.5] per axis.
+ *     offsets [B, n_cap, 2] fp32 (dy, dx): the clamped o of flag 0, zero for flags 1 to 3.  counts [B, 4] int32: rows per flag value.
+ *     Rows >= n_corr[b] and skipped pairs: offsets and flags zero, not counted.
+ *     The channel sums run in an order fixed by C alone: the bytes do not depend on the batch position, the stream, the run or the
+ *     layout.  Two launches, no allocation, no synchronisation, no atomics. */
+int oryon_subpix_refine(const float *feat_a, const float *feat_q, int B, int C, int FH, int FW, int layout, const int32_t *corrs,
+                        const int32_t *n_corr, const int32_t *status, int n_cap, float curv_min, float *offsets, uint8_t *flags,
+                        int32_t *counts, void *stream);
+
+/* K2x K2 on refined query coordinates: oryon_lift_pairs' arguments plus offsets [B, n_cap, 2] fp32 (dy, dx on the query side, in
+ *     feature-map pixels; NULL = zeros) and depth_jump_mm >= 0; the same outputs, compaction and zero tail.
+ *     Every operation is one correctly rounded fp32 operation, in this order, nothing contracted (s_* = K2's scale factors):
+ *       y_a' = float(y_a) * s_ya, x_a' alike;   y_q' = (float(y_q) + dy) * s_yq, x_q' alike;
+ *       a row is kept when 0 <= y' < H and 0 <= x' < W on both sides (K2's rule on the refined coordinates; a NaN offset drops the row);
+ *       per side, i0 = (int)y', j0 = (int)x', f_y = y' - i0, f_x = x' - j0, z00 = depth[i0, j0], z01 = depth[i0, j0 + 1], z10 =
+ *       depth[i0 + 1, j0], z11 = depth[i0 + 1, j0 + 1]:
+ *         if i0 + 1 < H, j0 + 1 < W, all four > 0 and max - min <= depth_jump_mm:
+ *           z = (1 - f_y) * ((1 - f_x) * z00 + f_x * z01) + f_y * ((1 - f_x) * z10 + f_x * z11)
+ *         else z = z00: the pixel K2 reads, a zero depth included, as the reference does;
+ *       X = ((x' - cx) * z) / fx / 1000, Y = ((y' - cy) * z) / fy / 1000, Z = z / 1000 on the FLOAT coordinates.
+ *     Pixel (i, j) stands for the point (i, j), not (i + 0.5, j + 0.5): the reference's convention (none), kept on purpose. */
+int oryon_lift_pairs_subpix(const int32_t *corrs, const float *offsets, const int32_t *n_corr, int B, int n_cap, int FH, int FW,
+                            const float *depth_a, int HA, int WA, const float *depth_q, int HQ, int WQ, const float *cam_a,
+                            const float *cam_q, const int32_t *status, float depth_jump_mm, float *pcd_a, float *pcd_q, int32_t *n_out,
+                            void *stream);
+
 /* K2' lift_pcd itself (utils/pcd.py:35-81 with xy_idxs): selected pixels of ONE depth map [H,W] fp32 ->
  *     [n,3] fp32 in the depth's unit (millimetres), X = ((x - cx) * z) / fx etc., no fma contraction.
  *     x_idx / y_idx [n] int32 must be inside the image (the reference would raise an IndexError). */

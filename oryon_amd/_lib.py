@@ -124,6 +124,9 @@ _PROTOS = {
                                  c_uint64, _P, c_int, c_int, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "oryon_lift_pairs": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P,
                                  _P, _P, _P]),
+    "oryon_subpix_refine": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_float, _P, _P, _P, _P]),
+    "oryon_lift_pairs_subpix": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, _P, _P, c_float,
+                                        _P, _P, _P, _P]),
     "oryon_lift_points": (c_int, [_P, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
     "oryon_kabsch_batched": (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     "oryon_split_f16x3": (c_int, [_P, c_int64, _P, _P, _P]),

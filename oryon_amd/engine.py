@@ -87,6 +87,29 @@ def default_topk() -> Tuple[int, int, float]:
     return _default_topk
 
 
+_default_subpixel = (False, 1e-4, 0.02)
+
+
+def set_default_subpixel(on: bool, curv_min: float = 1e-4, depth_jump: float = 0.02) -> None:
+    """The process-wide default of test.subpixel / test.subpixel_curv_min / test.subpixel_depth_jump: what `MatchPoseConfig()` and
+    `pipeline.default_args()` choose when the caller does not say ((False, 1e-4, 0.02) unless set: off).  A driver sets it once,
+    before it builds pipelines (run_pose.py --subpixel does)."""
+    global _default_subpixel
+    _check_subpixel_range(curv_min, depth_jump)
+    _default_subpixel = (bool(on), float(curv_min), float(depth_jump))
+
+
+def default_subpixel() -> Tuple[bool, float, float]:
+    return _default_subpixel
+
+
+def _check_subpixel_range(curv_min, depth_jump) -> None:
+    if not (0.0 <= float(curv_min) < float("inf")):      # a NaN fails too
+        raise ValueError(f"subpixel_curv_min {curv_min!r} is not a finite curvature >= 0")
+    if not (float(depth_jump) >= 0.0):                   # inf takes every measured 2 x 2 block
+        raise ValueError(f"subpixel_depth_jump {depth_jump!r} is negative (metres)")
+
+
 TOPK_MAX = 4
 SOLVER_ROW_CAP = 2048          # rows per pair that PointDSC, ransac and spectral accept
 
@@ -151,6 +174,18 @@ class MatchPoseConfig:
     # screened routes carry no reverse screen, the native C step engine does not know it); half_descriptors composes (the rounding
     # happens before the gather), sample_first does not (a ValueError).
     mutual: bool = field(default_factory=default_mutual)
+    # test.subpixel / test.subpixel_curv_min / test.subpixel_depth_jump: sub-pixel refinement of the selected rows
+    # (csrc/match_subpix.hip; no counterpart in the reference).  A quadratic through the descriptor distance of the 3 x 3 query pixels
+    # around every selected match gives a (dy, dx) offset; rows at the map's border, rows whose fit is flatter than subpixel_curv_min
+    # and rows whose fitted minimum lies more than a pixel away keep their pixel.  The lift then reads the depth bilinearly at the
+    # refined position where the four depths around it are measured and within subpixel_depth_jump metres of each other (the scale
+    # of pipeline.REFINE_DEFAULTS' normal_jump), else the pixel K2 reads.  Which rows are selected does not change.  A post-pass on
+    # the per-call schedule (the native C step engine does not know it) behind whatever match route the other fields choose; composes
+    # with mutual, ratio, topk (every rank row is refined on its own) and every solver.  Both numbers are design choices, not tuned
+    # on data.  (The fields stand in front of topk: ratio / ratio_radius stay the last two.)
+    subpixel: bool = field(default_factory=lambda: default_subpixel()[0])
+    subpixel_curv_min: float = field(default_factory=lambda: default_subpixel()[1])
+    subpixel_depth_jump: float = field(default_factory=lambda: default_subpixel()[2])
     # test.topk / test.topk_radius / test.topk_margin: one-to-many correspondences (csrc/match_next.hip, oryon_topk_corrs).  topk = K > 1
     # hands the solver up to K rows per drawn anchor: its nearest query pixel and the K - 1 next best ones, each at least topk_radius
     # pixels from every earlier one, kept while under dist_th and within topk_margin (cosine distance, additive) of the nearest.  The
@@ -173,6 +208,11 @@ class MatchPoseConfig:
         _check_mutual(self)
         _check_ratio(self)
         _check_topk(self)
+        _check_subpixel(self)
+
+
+def _check_subpixel(cfg: "MatchPoseConfig") -> None:
+    _check_subpixel_range(cfg.subpixel_curv_min, cfg.subpixel_depth_jump)
 
 
 def _check_mutual(cfg: "MatchPoseConfig") -> None:
@@ -650,6 +690,7 @@ class MatchPoseEngine:
         _check_mutual(cfg)
         _check_ratio(cfg)
         _check_topk(cfg)
+        _check_subpixel(cfg)
         if cfg.topk > 1:
             self.n_cap = ops.round_up(cfg.n_corrs * cfg.topk, 128)
         B, C, FH, FW = feat_a.shape
@@ -674,7 +715,8 @@ class MatchPoseEngine:
         # the native step engine serves every width up to 512 on the screened route (narrow maps zero-padded to 256 channels by K0);
         # the per-call schedule below keeps its own choice per width (exact scan for C <= 64, fp16 screen for C <= 128)
         native_ok = cfg.match_mode == "screened" and C <= 512 and 0.0 < cfg.dist_th <= 0.5 and (use_i8 or C <= 128)
-        if native_ok and self.native and cfg.solver != "spectral" and not filtered:   # the C step engine knows no spectral, mutual or ratio
+        # the C step engine knows no spectral, mutual, ratio or sub-pixel refinement
+        if native_ok and self.native and cfg.solver != "spectral" and not filtered and not cfg.subpixel:
             return self._run_native(feat_a, feat_q, mask_a, mask_q, depth_a, depth_q, cam_a, cam_q, pair_key, keep, inputs_event,
                                     inputs_resident, dev)
         if pair_key is None:
@@ -694,6 +736,10 @@ class MatchPoseEngine:
             # every route but the int8 one takes pre-rounded maps (one extra pass; K0v3 rounds on the way in).  The rounding runs on
             # the stream that consumes it (the gather stream when there is one, after its wait for the inputs)
             feat_a, feat_q = ops.round_to_f16(feat_a), ops.round_to_f16(feat_q)
+        # the maps the sub-pixel fit reads: the matcher's - the int8 gather rounds on its way in, so there the fit needs maps of its own
+        fit_a, fit_q = feat_a, feat_q
+        if cfg.half_descriptors and use_i8 and cfg.subpixel:
+            fit_a, fit_q = ops.round_to_f16(feat_a), ops.round_to_f16(feat_q)
         # two launches on the callers' tensors instead of a torch.cat + one launch: no torch arithmetic inside the step
         roi_a, n_a = ops.roi_compact(mask_a.reshape(B, FH, FW))
         roi_q, n_q = ops.roi_compact(mask_q.reshape(B, FH, FW))
@@ -704,7 +750,7 @@ class MatchPoseEngine:
             cap_a = ops.round_up(FH * FW, ops.ROW_PAD)
         cap_q = ops.round_up(FH * FW, ops.ROW_PAD)
         a16 = q16 = a8 = q8 = a_sc = q_sc = q_eps = q_norm = q_hat = roi_a1 = n_a1 = mutual = rev_argmin = rev_min_dist = None
-        second_dist = second_argmin = keep_rows = topk_out = None
+        second_dist = second_argmin = keep_rows = topk_out = subpix = None
         stage1 = use_i8 and cfg.sample_first > 0 and not keep
         if use_i8:
             # K0v3: anchors -> fp32 + int8 rows, queries -> int8 rows + row norms only (the re-scoring pass reads its few candidates
@@ -735,7 +781,7 @@ class MatchPoseEngine:
             self._py_mark(2, main)
             # EVERY tensor allocated under the gather stream and read on the main stream: without the record the allocator would hand
             # its memory to the next batch's gather (which runs ahead) while this batch's matcher still reads it
-            rounded = (feat_a, feat_q) if cfg.half_descriptors and not use_i8 else ()
+            rounded = (fit_a, fit_q) if cfg.half_descriptors and (cfg.subpixel or not use_i8) else ()
             for t_ in (roi_a, roi_q, n_a, n_q, a_hat, q_hat, a16, q16, a8, q8, a_sc, q_sc, q_eps, q_norm, roi_a1, n_a1) + rounded:
                 if t_ is not None:
                     t_.record_stream(main)
@@ -787,7 +833,13 @@ class MatchPoseEngine:
                                                                  cfg.n_corrs, cfg.seed, pair_key, corr_rows=self.n_cap)
         cam_a = cam_a.reshape(B, 9).to(torch.float32).contiguous()
         cam_q = cam_q.reshape(B, 9).to(torch.float32).contiguous()
-        pcd_a, pcd_q, n_lift = ops.lift_pairs(corrs, n_sel, (FH, FW), depth_a, depth_q, cam_a, cam_q, status)
+        if cfg.subpixel:
+            # a post-pass on the selected rows (every rank row of topk on its own), then K2 on the refined query coordinates
+            subpix = ops.subpix_refine(fit_a, fit_q, corrs, n_sel, status, cfg.subpixel_curv_min)
+            pcd_a, pcd_q, n_lift = ops.lift_pairs_subpix(corrs, n_sel, (FH, FW), depth_a, depth_q, cam_a, cam_q, status,
+                                                         offsets=subpix["offsets"], depth_jump=cfg.subpixel_depth_jump)
+        else:
+            pcd_a, pcd_q, n_lift = ops.lift_pairs(corrs, n_sel, (FH, FW), depth_a, depth_q, cam_a, cam_q, status)
         if self.overlap:
             # registrations of consecutive batches alternate between two streams (and two workspaces): their many small,
             # low-occupancy launches then overlap each other as well as the next batch's matching
@@ -815,6 +867,8 @@ class MatchPoseEngine:
         out = dict(pose=pose, status=status_out, n_valid=n_valid, n_lifted=n_lift)
         if topk_out is not None:
             out["n_rows"] = topk_out["n_rows"]
+        if subpix is not None:
+            out.update(subpix_offsets=subpix["offsets"], subpix_flags=subpix["flags"], subpix_counts=subpix["counts"])
         if done is not None:
             out["_done"] = done
         if keep:

@@ -765,6 +765,54 @@ def lift_pairs(corrs: torch.Tensor, n_corr: Optional[torch.Tensor], feat_hw, dep
     return pa, pq, n_out
 
 
+SUBPIX_FLAGS = ("refined", "border", "flat", "outside")      # the flag values 0..3 of oryon_subpix_refine, the order of counts[..., f]
+
+
+@_on_tensor_device
+def subpix_refine(feat_a: torch.Tensor, feat_q: torch.Tensor, corrs: torch.Tensor, n_corr: Optional[torch.Tensor] = None,
+                  status: Optional[torch.Tensor] = None, curv_min: float = 1e-4):
+    """Sub-pixel refinement of selected correspondences (csrc/match_subpix.hip; definition: include/oryon_hip.h, oryon_subpix_refine).
+    feat_* [B,C,FH,FW] fp32 (contiguous or channels_last, both of one layout), corrs [B,n_cap,4] i32, n_corr / status [B] i32 or None
+    -> dict(offsets [B,n_cap,2] fp32 (dy, dx), flags [B,n_cap] uint8, counts [B,4] i32 in the order of SUBPIX_FLAGS)."""
+    dev = _lib.require_gpu(feat_a.device)
+    assert feat_a.dtype == torch.float32 and feat_q.dtype == torch.float32 and feat_a.dim() == 4 and feat_a.shape == feat_q.shape
+    assert corrs.dtype == torch.int32 and corrs.dim() == 3 and corrs.shape[0] == feat_a.shape[0] and corrs.shape[2] == 4
+    feat_a, layout = map_layout(feat_a)
+    feat_q, layout_q = map_layout(feat_q)
+    if layout_q != layout:                       # one layout argument: the odd one out is copied
+        feat_a, feat_q, layout = feat_a.contiguous(), feat_q.contiguous(), LAYOUT_NCHW
+    B, C, FH, FW = feat_a.shape
+    n_cap = corrs.shape[1]
+    offsets = torch.empty((B, n_cap, 2), dtype=torch.float32, device=dev)      # the kernel writes every row
+    flags = torch.empty((B, n_cap), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    check(lib().oryon_subpix_refine(feat_a.data_ptr(), feat_q.data_ptr(), B, C, FH, FW, layout, ptr(corrs), ptr(n_corr), ptr(status), n_cap,
+                                    float(curv_min), ptr(offsets), ptr(flags), ptr(counts), stream_ptr(dev)), "oryon_subpix_refine")
+    return dict(offsets=offsets, flags=flags, counts=counts)
+
+
+@_on_tensor_device
+def lift_pairs_subpix(corrs: torch.Tensor, n_corr: Optional[torch.Tensor], feat_hw, depth_a: torch.Tensor, depth_q: torch.Tensor,
+                      cam_a: torch.Tensor, cam_q: torch.Tensor, status: Optional[torch.Tensor] = None,
+                      offsets: Optional[torch.Tensor] = None, depth_jump: float = 0.02):
+    """lift_pairs on refined query coordinates (oryon_lift_pairs_subpix): offsets [B,n_cap,2] fp32 (dy, dx; None = zeros), depth_jump
+    in metres (the four depths under a bilinear read may differ by no more) -> (pcd_a, pcd_q [B,n_cap,3] metres, n_out [B])."""
+    dev = _lib.require_gpu(corrs.device)
+    B, n_cap = corrs.shape[0], corrs.shape[1]
+    assert corrs.dtype == torch.int32 and depth_a.dtype == torch.float32 and depth_q.dtype == torch.float32
+    assert cam_a.dtype == torch.float32 and cam_a.shape == (B, 9) and cam_q.shape == (B, 9)
+    assert offsets is None or (offsets.dtype == torch.float32 and tuple(offsets.shape) == (B, n_cap, 2))
+    pa = torch.empty((B, n_cap, 3), dtype=torch.float32, device=dev)      # the kernel zeroes the rows past the lifted count
+    pq = torch.empty((B, n_cap, 3), dtype=torch.float32, device=dev)
+    n_out = torch.empty((B,), dtype=torch.int32, device=dev)
+    check(lib().oryon_lift_pairs_subpix(ptr(corrs), ptr(offsets), ptr(n_corr), B, n_cap, int(feat_hw[0]), int(feat_hw[1]),
+                                        ptr(depth_a.contiguous()), depth_a.shape[1], depth_a.shape[2],
+                                        ptr(depth_q.contiguous()), depth_q.shape[1], depth_q.shape[2],
+                                        ptr(cam_a.contiguous()), ptr(cam_q.contiguous()), ptr(status), float(depth_jump) * 1000.0,
+                                        ptr(pa), ptr(pq), ptr(n_out), stream_ptr(dev)), "oryon_lift_pairs_subpix")
+    return pa, pq, n_out
+
+
 @_on_tensor_device
 def lift_points(depth: torch.Tensor, cam9: torch.Tensor, x_idx: torch.Tensor, y_idx: torch.Tensor) -> torch.Tensor:
     """depth [H,W] f32, cam9 [9] f32, pixel indices [n] -> [n,3] f32 in the depth's unit."""

@@ -221,6 +221,20 @@ def nn_correspondences_topk(feats1: Tensor, feats2: Tensor, mask1: Tensor, mask2
     return allrows[take.transpose(0, 1)].to(orig_device)
 
 
+def subpixel_offsets(feats1: Tensor, feats2: Tensor, corrs: Tensor, curv_min: float = 1e-4) -> Tuple[Tensor, Tensor]:
+    """Sub-pixel refinement of the rows `nn_correspondences` (or one of its variants) returned, per sample (no counterpart in the
+    reference; ops.subpix_refine, csrc/match_subpix.hip): feats1 / feats2 [D,H,W], corrs [n,4] (y1,x1,y2,x2) -> (offsets [n,2] float32
+    (dy, dx) to add to (y2, x2), flags [n] uint8: 0 refined, 1 border, 2 flat or not a minimum, 3 minimum more than a pixel away) on
+    feats1.device.  The fit reads the maps as given, in float32, whatever rounding the matcher applied to find the rows."""
+    dev = require_gpu(feats1.device)
+    n = corrs.shape[0]
+    if n == 0:
+        return torch.zeros((0, 2), dtype=torch.float32, device=dev), torch.zeros((0,), dtype=torch.uint8, device=dev)
+    out = ops.subpix_refine(feats1.to(dev, torch.float32)[None].contiguous(), feats2.to(dev, torch.float32)[None].contiguous(),
+                            corrs.to(dev).to(torch.int32).contiguous()[None], curv_min=curv_min)
+    return out["offsets"][0], out["flags"][0]
+
+
 def lift_pcd(depth: Tensor, camera: Tensor, xy_idxs: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
     """Depth [H,W,1] (millimetres) + flattened K [9] -> [N,3] points (millimetres), fp32
     (utils/pcd.py:35-81).  With xy_idxs=(x_idx, y_idx) only those pixels are lifted; the caller divides

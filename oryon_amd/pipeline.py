@@ -50,9 +50,9 @@ import torch
 from torch import Tensor
 
 from . import _lib, ops
-from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK, PAIR_OK, SOLVERS, default_mutual, default_ratio, default_solver, default_topk
+from .engine import MatchPoseConfig, MatchPoseEngine, PAIR_NO_CORR, PAIR_NO_MASK, PAIR_OK, SOLVERS, default_mutual, default_ratio, default_solver, default_subpixel, default_topk
 from .geo6d import best_fit_transform_with_RANSAC, spectral_pose
-from .pcd import nn_correspondences, nn_correspondences_filtered, nn_correspondences_topk
+from .pcd import nn_correspondences, nn_correspondences_filtered, nn_correspondences_topk, subpixel_offsets
 from .pointdsc import PointDSC, get_pointdsc_pose
 
 
@@ -183,6 +183,29 @@ def mask_clean_summary() -> Dict:
     return {} if _latest_mask_clean is None else _reduce_mask_clean(*_latest_mask_clean)
 
 
+# The log of the latest Pipeline built with test.subpixel (csrc/match_subpix.hip): what a driver that cannot reach the pipeline
+# another module builds (run_pose.py around run_test.py) reads its summary from.
+_latest_subpixel: Optional[List[Tuple[Tensor, Tensor]]] = None
+
+
+def _reduce_subpixel(log: List[Tuple[Tensor, Tensor]]) -> Dict:
+    """log: per step (flags [n] uint8, offsets [n, 2] fp32) of the rows handed to the lift, on the device -> the rows per flag value
+    and the mean |offset| (pixels of the feature map) of the refined rows.  The only place that reads them back."""
+    flags = torch.cat([f.reshape(-1) for f, _ in log]).cpu().numpy() if log else np.zeros((0,), np.uint8)
+    offs = torch.cat([o.reshape(-1, 2) for _, o in log]).cpu().numpy().astype(np.float64) if log else np.zeros((0, 2))
+    out = {"subpixel_rows": int(flags.shape[0])}
+    for i, name in enumerate(ops.SUBPIX_FLAGS):
+        out[f"subpixel_{name}"] = int((flags == i).sum())
+    ref = offs[flags == 0]
+    out["subpixel_offset_mean"] = float(np.hypot(ref[:, 0], ref[:, 1]).mean()) if ref.shape[0] else None
+    return out
+
+
+def subpixel_summary() -> Dict:
+    """Pipeline.subpixel_summary() of the latest refining pipeline of this process; {} when there is none."""
+    return {} if _latest_subpixel is None else _reduce_subpixel(_latest_subpixel)
+
+
 def default_args(**overrides) -> SimpleNamespace:
     """The hot-path subset of configs/config.yaml (same names, same defaults)."""
     args = SimpleNamespace(
@@ -207,6 +230,11 @@ def default_args(**overrides) -> SimpleNamespace:
                              # up to topk rows per drawn anchor, 1 = off ((1, 5, 0.1) unless a driver called
                              # engine.set_default_topk).  Read with getattr(..., 1 / 5 / 0.1)
                              topk=default_topk()[0], topk_radius=default_topk()[1], topk_margin=default_topk()[2],
+                             # test.subpixel / test.subpixel_curv_min / test.subpixel_depth_jump (csrc/match_subpix.hip; no
+                             # counterpart in the reference): sub-pixel refinement of the selected rows, off ((False, 1e-4, 0.02)
+                             # unless a driver called engine.set_default_subpixel).  Read with getattr(..., False / 1e-4 / 0.02)
+                             subpixel=default_subpixel()[0], subpixel_curv_min=default_subpixel()[1],
+                             subpixel_depth_jump=default_subpixel()[2],
                              # test.verify / test.verify_tol (csrc/pose_verify.hip; no counterpart in the reference): rate, or
                              # choose between, the poses of a pair against the query's depth map (('none', 0.01) unless a driver
                              # called set_default_verify).  Read with getattr: arg objects without them keep working
@@ -288,6 +316,27 @@ class Pipeline:
         if self.mask_clean_active():                     # an unknown test.mask_clean or a fraction outside [0, 1] raises here
             global _latest_mask_clean
             _latest_mask_clean = (*self.mask_clean_cfg(), self._mask_clean_log)
+        self.last_subpixel: Optional[Tuple[Tensor, Tensor]] = None    # the latest (offsets [n,2], flags [n]) of the per-sample route
+        self._subpixel_log: List[Tuple[Tensor, Tensor]] = []          # per step (flags, offsets) of the rows handed to the lift
+        if self.subpixel_cfg()[0]:                       # a negative curvature floor or depth jump raises here
+            global _latest_subpixel
+            _latest_subpixel = self._subpixel_log
+
+    # ------------------------------------------------------------------ sub-pixel refinement (test.subpixel; csrc/match_subpix.hip)
+    def subpixel_cfg(self) -> Tuple[bool, float, float]:
+        """(test.subpixel, test.subpixel_curv_min, test.subpixel_depth_jump); absent = (False, 1e-4, 0.02).  Checked as
+        MatchPoseConfig checks them."""
+        on = bool(getattr(self.args.test, "subpixel", False))
+        curv, jump = float(getattr(self.args.test, "subpixel_curv_min", 1e-4)), float(getattr(self.args.test, "subpixel_depth_jump", 0.02))
+        if on:
+            MatchPoseConfig(solver="ransac", subpixel=True, subpixel_curv_min=curv, subpixel_depth_jump=jump)
+        return on, curv, jump
+
+    def subpixel_summary(self) -> Dict:
+        """What a driver adds to its summary: {} when test.subpixel is off; else, over the steps of this pipeline so far, the rows handed
+        to the lift, how many of them carry each flag (refined, border, flat, outside) and the mean |offset| of the refined ones in
+        feature-map pixels."""
+        return _reduce_subpixel(self._subpixel_log) if self.subpixel_cfg()[0] else {}
 
     # ------------------------------------------------------------------ mask clean-up (test.mask_clean; csrc/mask_clean.hip)
     def mask_clean_cfg(self) -> Tuple[str, float, bool]:
@@ -382,6 +431,9 @@ class Pipeline:
         else:
             pred_corrs = nn_correspondences(featmap_ai, featmap_qi, mask_ai, mask_qi, self.args.test.dist_th, self.args.test.n_corrs,
                                             self.args.test.src_sampling, self.corrs_device, mutual=bool(getattr(self.args.test, "mutual", False)))
+        self.last_subpixel = None
+        if pred_corrs is not None and self.subpixel_cfg()[0]:    # the refinement of the rows just drawn; get_pose takes it as offsets=
+            self.last_subpixel = subpixel_offsets(featmap_ai, featmap_qi, pred_corrs, self.subpixel_cfg()[1])
         if pred_corrs is not None:
             corr_ai, corr_qi = pred_corrs[:, :2], pred_corrs[:, 2:]
             pos_a = featmap_ai[:, corr_ai[:, 0], corr_ai[:, 1]].transpose(1, 0)
@@ -513,10 +565,20 @@ class Pipeline:
         mode = self.verify_mode()
         return {} if mode == "none" else _reduce_verify(mode, self.verify_tol(), self._verify_log)
 
+    def _subpixel_offsets_of_step(self) -> Optional[Tensor]:
+        """The offsets get_featmap_corrs just computed (None when test.subpixel is off), logged for subpixel_summary."""
+        if self.last_subpixel is None:
+            return None
+        offsets, flags = self.last_subpixel
+        self._subpixel_log.append((flags, offsets))
+        return offsets
+
     # ------------------------------------------------------------------ pipeline.py:429-472
-    def get_pose(self, batch: Dict, corrs: Tensor, idx: int, results: Optional[Dict] = None, pair_key: Optional[int] = None) -> Tensor:
+    def get_pose(self, batch: Dict, corrs: Tensor, idx: int, results: Optional[Dict] = None, pair_key: Optional[int] = None,
+                 offsets: Optional[Tensor] = None) -> Tensor:
         """results: the masks' post-processing (mask_results), needed by test.refine = icp with predicted masks only; pair_key: the
-        pair's global index (default idx), which keys the refinement's subsample."""
+        pair's global index (default idx), which keys the refinement's subsample; offsets: [n,2] fp32 sub-pixel (dy, dx) of the rows'
+        query pixels (pcd.subpixel_offsets) - given, the lift is ops.lift_pairs_subpix with test.subpixel_depth_jump."""
         dev = _lib.require_gpu(self.device)
         depth_a = batch["anchor"]["orig_depth"][idx].squeeze().to(dev, torch.float32)
         depth_q = batch["query"]["orig_depth"][idx].squeeze().to(dev, torch.float32)
@@ -529,8 +591,13 @@ class Pipeline:
             raise RuntimeError(f"test.solver was changed from '{self.solver}' to '{self.args.test.solver}' after this Pipeline was built: "
                                "the solver is fixed at construction, build a new Pipeline")
         c = corrs.to(dev).to(torch.int32).contiguous()[None]
-        pcd_a, pcd_q, n = ops.lift_pairs(c, None, (HO, WO), depth_a[None].contiguous(), depth_q[None].contiguous(),
-                                         camera_a, camera_q)
+        if offsets is not None:
+            pcd_a, pcd_q, n = ops.lift_pairs_subpix(c, None, (HO, WO), depth_a[None].contiguous(), depth_q[None].contiguous(), camera_a,
+                                                    camera_q, offsets=offsets.to(dev, torch.float32).contiguous()[None],
+                                                    depth_jump=self.subpixel_cfg()[2])
+        else:
+            pcd_a, pcd_q, n = ops.lift_pairs(c, None, (HO, WO), depth_a[None].contiguous(), depth_q[None].contiguous(),
+                                             camera_a, camera_q)
         m = int(n.item())
         if self.args.test.solver == "ransac":                  # pipeline.py:462-466
             pose = best_fit_transform_with_RANSAC(pcd_a[0, :m], pcd_q[0, :m], max_iter=10000, fix_percent=0.9999, match_err=0.001,
@@ -628,7 +695,8 @@ class Pipeline:
             if self.is_detection_valid(results, batch, i_b):
                 pred_corrs, _, _ = self.get_featmap_corrs(batch, outputs, results, idx=i_b)
                 if pred_corrs is not None:
-                    pred_pose = self.get_pose(batch, pred_corrs, idx=i_b, results=results, pair_key=first_pair_index + i_b)
+                    pred_pose = self.get_pose(batch, pred_corrs, idx=i_b, results=results, pair_key=first_pair_index + i_b,
+                                              offsets=self._subpixel_offsets_of_step())
                     pred_q = pred_pose @ batch["anchor"]["pose"][i_b].cpu().detach().to(torch.float32)
                 else:
                     status, pred_pose = PAIR_NO_CORR, torch.eye(4)
@@ -679,6 +747,7 @@ class Pipeline:
                 ratio=float(getattr(self.args.test, "ratio", 0.0)), ratio_radius=int(getattr(self.args.test, "ratio_radius", 5)),
                 topk=int(getattr(self.args.test, "topk", 1)), topk_radius=int(getattr(self.args.test, "topk_radius", 5)),
                 topk_margin=float(getattr(self.args.test, "topk_margin", 0.1)),
+                subpixel=self.subpixel_cfg()[0], subpixel_curv_min=self.subpixel_cfg()[1], subpixel_depth_jump=self.subpixel_cfg()[2],
                 **{"spectral_" + f: v for f, v in self._spectral_cfg().items()}))
 
         def stack(x):
@@ -687,6 +756,10 @@ class Pipeline:
         key = torch.arange(first_pair_index, first_pair_index + BS, dtype=torch.int64, device=dev)
         out = self._engine.run(outputs["featmap_a"].float().contiguous(), outputs["featmap_q"].float().contiguous(), mask_a,
                                mask_q, depth_a, depth_q, batch["anchor"]["camera"].to(dev), batch["query"]["camera"].to(dev), key)
+        if "subpix_flags" in out:                                # the rows handed to the lift: [0, n_rows) of every solved pair
+            n_rows = out["n_rows"] if "n_rows" in out else torch.where(out["status"] == PAIR_OK, self.args.test.n_corrs, 0)
+            live = torch.arange(out["subpix_flags"].shape[1], device=dev)[None] < n_rows[:, None]
+            self._subpixel_log.append((out["subpix_flags"][live], out["subpix_offsets"][live]))
         refine, verify = self.refine_mode(), self.verify_mode()
         clouds = None
         if refine != "none" or verify != "none":
@@ -831,7 +904,7 @@ class Pipeline:
             elif self.is_detection_valid(results, batch, i_b):
                 pred_corrs, _, _ = self.get_featmap_corrs(batch, outputs, results, idx=i_b)
                 if pred_corrs is not None:
-                    pred_pose = self.get_pose(batch, pred_corrs, idx=i_b, results=results)
+                    pred_pose = self.get_pose(batch, pred_corrs, idx=i_b, results=results, offsets=self._subpixel_offsets_of_step())
                 else:
                     st = PAIR_NO_CORR
             else:

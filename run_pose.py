@@ -62,6 +62,15 @@ holes filled, then the largest 8-connected component kept, or every one of at le
 `"mask_clean"`, `"mask_clean_frac"`, `"mask_fill_holes"` and the means of the clean-up's statistics over the masks it saw.  F is a
 design choice, not tuned on data.
 
+    python run_pose.py --solver ransac --subpixel --subpixel-curv-min 1e-4 --subpixel-depth-jump 0.02 --pairs 8 --batch 4
+
+`--subpixel [--subpixel-curv-min X] [--subpixel-depth-jump M]` (test.subpixel / test.subpixel_curv_min / test.subpixel_depth_jump; off by
+default, X = 1e-4, M = 0.02 m) becomes the process-wide default (oryon_amd.engine.set_default_subpixel) in the same way: every selected
+correspondence gets a sub-pixel offset on the query side from a quadratic fit of the descriptor distance over the 3 x 3 pixels around the
+match (csrc/match_subpix.hip), and the lift reads the depth bilinearly there where the four depths around it lie within M of each other.
+Composes with every other flag.  The summary carries `"subpixel"`, the two numbers, the rows per flag (refined, border, flat, outside)
+and the mean |offset| of the refined rows.  X and M are design choices, not tuned on data.
+
     python run_pose.py --vsd --data-root /data --dataset nocs --ckpt ... --out preds/nocs.csv
 
 `--vsd` (real-asset mode only) also reports VSD and AR = (VSD + MSSD + MSPD) / 3, the reference's headline column
@@ -110,14 +119,27 @@ def take_topk(argv=None):
     return ap.parse_known_args(argv)
 
 
+def take_subpixel(argv=None):
+    """-> (the `--subpixel` / `--subpixel-curv-min` / `--subpixel-depth-jump` values, argv without them); a parser of its own that takes
+    no abbreviations."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--subpixel", action="store_true")
+    ap.add_argument("--subpixel-curv-min", type=float, default=1e-4)
+    ap.add_argument("--subpixel-depth-jump", type=float, default=0.02)
+    return ap.parse_known_args(argv)
+
+
 class Parsed(tuple):
     """(solver, the arguments left for run_test.py), with `.mutual`: whether `--mutual` was given (taken out, like `--refine`),
     `.ratio` / `.ratio_radius`: what `--ratio` / `--ratio-radius` gave (0.0 / 5 when absent), and `.verify` / `.verify_tol`: what
     `--verify` / `--verify-tol` gave ('none' / 0.01 when absent), and `.mask_clean` / `.mask_clean_frac` / `.mask_fill_holes`: what
     `--mask-clean` / `--mask-clean-frac` / `--fill-holes` gave ('none' / 0.25 / False when absent), and `.topk` / `.topk_radius` /
-    `.topk_margin`: what `--topk` / `--topk-radius` / `--topk-margin` gave (1 / 5 / 0.1 when absent)."""
+    `.topk_margin`: what `--topk` / `--topk-radius` / `--topk-margin` gave (1 / 5 / 0.1 when absent), and `.subpixel` /
+    `.subpixel_curv_min` / `.subpixel_depth_jump`: what `--subpixel` / `--subpixel-curv-min` / `--subpixel-depth-jump` gave (False / 1e-4 /
+    0.02 when absent)."""
     def __new__(cls, solver, rest, mutual, ratio=0.0, ratio_radius=5, verify="none", verify_tol=0.01, mask_clean="none", mask_clean_frac=0.25,
-                mask_fill_holes=False, topk=1, topk_radius=5, topk_margin=0.1):
+                mask_fill_holes=False, topk=1, topk_radius=5, topk_margin=0.1, subpixel=False, subpixel_curv_min=1e-4,
+                subpixel_depth_jump=0.02):
         self = super().__new__(cls, (solver, rest))
         self.mutual = mutual
         self.ratio = ratio
@@ -130,6 +152,9 @@ class Parsed(tuple):
         self.topk = topk
         self.topk_radius = topk_radius
         self.topk_margin = topk_margin
+        self.subpixel = subpixel
+        self.subpixel_curv_min = subpixel_curv_min
+        self.subpixel_depth_jump = subpixel_depth_jump
         return self
 
 
@@ -140,7 +165,8 @@ def parse(argv=None):
     `--verify-tol` (test.verify, test.verify_tol: depth-consistency verification of the poses, csrc/pose_verify.hip) and `--mask-clean` /
     `--mask-clean-frac` / `--fill-holes` (test.mask_clean, test.mask_clean_frac, test.mask_fill_holes: connected-component clean-up of
     the masks, csrc/mask_clean.hip) and `--topk` / `--topk-radius` / `--topk-margin` (test.topk, test.topk_radius, test.topk_margin:
-    up to K rows per drawn anchor, csrc/match_next.hip)."""
+    up to K rows per drawn anchor, csrc/match_next.hip) and `--subpixel` / `--subpixel-curv-min` / `--subpixel-depth-jump` (test.subpixel,
+    test.subpixel_curv_min, test.subpixel_depth_jump: sub-pixel refinement of the selected rows, csrc/match_subpix.hip)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
     ap.add_argument("--solver", choices=["pointdsc", "ransac", "spectral"], default="pointdsc",
                     help="test.solver: PointDSC registration, best_fit_transform_with_RANSAC, or the spectral solver (the last two need no "
@@ -156,12 +182,13 @@ def parse(argv=None):
     ap.add_argument("-h", "--help", action="store_true")
     mc, argv = take_mask_clean(argv)
     tk, argv = take_topk(argv)
+    sp, argv = take_subpixel(argv)
     a, rest = ap.parse_known_args(argv)
     if a.help:
         ap.print_help()
         rest = ["--help"] + rest               # then run_test.py's own help
     return Parsed(a.solver, rest, a.mutual, a.ratio, a.ratio_radius, a.verify, a.verify_tol, mc.mask_clean, mc.mask_clean_frac, mc.fill_holes,
-                  tk.topk, tk.topk_radius, tk.topk_margin)
+                  tk.topk, tk.topk_radius, tk.topk_margin, sp.subpixel, sp.subpixel_curv_min, sp.subpixel_depth_jump)
 
 
 def take_vsd(argv):
@@ -207,6 +234,11 @@ def main(argv=None):
         set_default_topk(parsed.topk, parsed.topk_radius, parsed.topk_margin)
     except ValueError as e:
         raise SystemExit(f"run_pose.py: {e}")
+    from oryon_amd.engine import set_default_subpixel
+    try:
+        set_default_subpixel(parsed.subpixel, parsed.subpixel_curv_min, parsed.subpixel_depth_jump)
+    except ValueError as e:
+        raise SystemExit(f"run_pose.py: {e}")
     from oryon_amd.engine import set_default_solver
     set_default_solver(solver)
     from oryon_amd.pipeline import set_default_refine
@@ -223,13 +255,17 @@ def main(argv=None):
     summary = run_test.main(rest)
     verified = parsed.verify != "none"
     cleaned = parsed.mask_clean != "none" or parsed.mask_fill_holes
-    if parsed.mutual or parsed.ratio > 0 or verified or cleaned or parsed.topk > 1:
+    if parsed.mutual or parsed.ratio > 0 or verified or cleaned or parsed.topk > 1 or parsed.subpixel:
         if parsed.mutual:
             summary = dict(summary, mutual=True)
         if parsed.ratio > 0:
             summary = dict(summary, ratio=parsed.ratio, ratio_radius=parsed.ratio_radius)
         if parsed.topk > 1:
             summary = dict(summary, topk=parsed.topk, topk_radius=parsed.topk_radius, topk_margin=parsed.topk_margin)
+        if parsed.subpixel:
+            from oryon_amd.pipeline import subpixel_summary       # what the pipelines run_test.py built have refined
+            summary = {**summary, "subpixel": True, "subpixel_curv_min": parsed.subpixel_curv_min,
+                       "subpixel_depth_jump": parsed.subpixel_depth_jump, **subpixel_summary()}
         if verified:
             from oryon_amd.pipeline import verify_summary         # what the pipelines run_test.py built have rated
             summary = {**summary, "verify": parsed.verify, "verify_tol": parsed.verify_tol, **verify_summary()}
