@@ -1,7 +1,8 @@
 // The exact matcher's two all-pairs tile walks as templates over what is done with a finished tile: how the query rows stream past a
 // workgroup's 128 anchor columns and through the fp32 MFMA.  They are match_f32_kernel's and match_f32_regb_kernel's loops (match.hip)
-// statement for statement, so the distances have K1's bits; K1r (match_second.hip) and K1n (match_next.hip) are built on them.  K1 and K1m (match_mutual.hip)
-// still carry their own text of the loops: instantiated from here, each was 0.3 - 0.9 % slower at C_pad 32 (measured).
+// statement for statement, so the distances have K1's bits; the scan with exclusion discs (match_disc.h: K1r, match_second.hip, and K1n,
+// match_next.hip) is built on them.  K1 and K1m (match_mutual.hip) still carry their own text of the loops: instantiated from here,
+// each was 0.3 - 0.9 % slower at C_pad 32 (measured).
 // The formulation, the geometry, the LDS image and the LDS-DMA are explained here, once, for all three.
 // What a kernel does with a FINISHED tile of dot products - its fold - is the caller's:
 //
@@ -30,6 +31,7 @@ constexpr int BK = 32;                // k-tile
 constexpr int LD = BK + 1;            // padded LDS row: ds_read_b32 of a 32-row column is conflict-free
 constexpr int MATCH_THREADS = 256;
 constexpr int TILE_FLOATS = MT * LD;
+constexpr int ROW_NONE = 0x7fffffff;  // the index of a running (distance, index) that has no row yet: lex_min lets any row replace it
 
 // query tiles [begin, end) of split `split` of S over nq rows in tiles of `rows`
 struct TileSpan {
@@ -175,7 +177,7 @@ __device__ __forceinline__ void staged_columns(float *smem, float (&best)[2], in
     }
     __syncthreads();
     d = INFINITY;
-    i = 0x7fffffff;
+    i = ROW_NONE;
     if (t < MT) {
         d = sd[t];
         i = si[t];
